@@ -12,6 +12,10 @@ results to every rank; such a run also reports BASELINE config 4
 
 `value` is the device-resident rate; rates.host_buffer_call is the PCIe-inclusive
 rate of the host-buffer entry point.  Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR writes what the timed path returned in its last step (forces
+and status record of every instance, all ranks) as DIR/<name>.npy, so that two
+builds can be compared output for output on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -31,6 +35,7 @@ sys.path.insert(0, str(REPO))
 
 FP64_PEAK_TFLOPS = 78.6          # MI355X FP64 vector = matrix peak
 W_ALG_KFLOP_PER_KNOT = 159.0     # W_alg(N) = 159 N kFLOP per solve
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
 
 
 def load_pkg():
@@ -41,6 +46,24 @@ def load_pkg():
     sys.modules[name] = mod
     spec.loader.exec_module(mod)
     return mod
+
+
+def dump_outputs(out_dir: Path, forces: np.ndarray, info: np.ndarray) -> None:
+    """forces.npy [n, nu] and info_<field>.npy [n] (every field of qmpc_info), all float64.  A batch above
+    DUMP_LIMIT_BYTES is represented by a fixed, seeded sample of instances in ascending order; rows.npy then holds
+    their indices."""
+    n = len(forces)
+    row_bytes = 8 * (forces.shape[1] + len(info.dtype.names))
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        # 4 KB left for the .npy headers
+        rows = np.sort(np.random.default_rng(0).choice(n, (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8), replace=False))
+    arrays = {"forces": forces[rows], **{"info_" + k: info[k][rows] for k in info.dtype.names}}
+    if len(rows) < n:
+        arrays["rows"] = rows
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
 
 
 def flush_c_stdio():
@@ -228,7 +251,11 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="DIAGNOSTIC: run the multi-rank code path (process group, async all_gather per step, barriers) "
                          "even with one rank, to exercise the RCCL calls on a single GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", type=Path,
+                    help="write the timed path's outputs of its last step (forces and status records) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -356,7 +383,7 @@ def main():
         # status of EVERY rank's instances (the gathered blocks carry them)
         info = np.ascontiguousarray(allb[:, Bl * nu:].cpu().numpy()).view(pkg.INFO_DTYPE).reshape(world, Bl)
         forces = last[:Bl * nu].view(Bl, nu).cpu().numpy().copy()
-        return {"elapsed": elapsed, "kernel_ms": kernel_ms, "info": info, "forces": forces, "rec": rec,
+        return {"elapsed": elapsed, "kernel_ms": kernel_ms, "info": info, "forces": forces, "rec": rec, "blocks": allb,
                 "solver": solver, "d_in": d_in, "ranks": ranks, "gather_wait_ms": pst["gather_wait_ms"] / steps}
 
     def kernel_name(batch, horizon=None, slv=None):
@@ -397,6 +424,9 @@ def main():
     solver, d_in, d_f = leg["solver"], leg["d_in"], leg["forces"]
     n_ok = int((info["status"] == 0).sum())
     mean_iters = float(info["iterations"].mean())
+    if args.dump_outputs is not None and rank == 0:
+        # what a caller of the timed path holds after its last step: every rank's forces and status records
+        dump_outputs(args.dump_outputs, leg["blocks"][:, :B * NU].reshape(world * B, NU).cpu().numpy(), info.reshape(-1))
 
     # BASELINE config 4 beside the weak-scaling value: 262144 Go1 instances, N=10, sharded over the ranks
     # (32768 per GPU at 8 GPUs), same pipeline, a few steps.  Every rank takes part (collectives).

@@ -670,15 +670,17 @@ def test_independent_handles_overlap_on_their_streams(pkg, lib):
     sq.close(); sc.close(); fresh.close(); s20.close(); s10.close()
 
 
-def test_bench_line_contract(pkg, lib):
+def test_bench_line_contract(pkg, lib, tmp_path):
     """bench.py prints ONE JSON line with the contract keys, the roofline and cpu_baseline objects and the
-    secondary two-batches-in-flight figure (whose outputs equal the single-stream ones)."""
+    secondary two-batches-in-flight figure (whose outputs equal the single-stream ones); --dump-outputs writes the
+    timed path's last-step forces and status records, equal to a host-buffer solve of the same seeded batch."""
     import subprocess
     import sys
 
     repo = Path(__file__).resolve().parents[1]
-    r = subprocess.run([sys.executable, str(repo / "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "256"],
-                       capture_output=True, text=True, timeout=600)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, str(repo / "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "256",
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -696,6 +698,15 @@ def test_bench_line_contract(pkg, lib):
     assert cb["kind"] in ("reference", "port") and cb["cores"] >= 1 and cb["value"] > 0
     assert cb["force_linf_instances"] == 256 and cb["force_linf_gpu_vs_cpu"] < 1e-6      # the stated tolerance
     assert d["two_in_flight"]["outputs_identical"] is True and d["config"]["converged"] == 256
+    s = pkg.Solver(pkg.default_params(10, pkg.MODE_CONVERGED, lib), 256, device=0, lib=lib)
+    f_ref, i_ref = s.solve(pkg.random_go1_trot_states(256, config_id=2))
+    s.close()
+    assert sorted(p.name for p in dump.iterdir()) == sorted(["forces.npy"] + [f"info_{k}.npy" for k in pkg.INFO_DTYPE.names])
+    f = np.load(dump / "forces.npy")
+    assert f.dtype == np.float64 and np.array_equal(f, f_ref)
+    for k in pkg.INFO_DTYPE.names:
+        a = np.load(dump / f"info_{k}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, i_ref[k].astype(np.float64)), k
 
 
 def test_randomised_parameter_sets_match_oracle(pkg, lib, oracle):

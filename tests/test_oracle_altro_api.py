@@ -118,13 +118,13 @@ def test_bicycle_mpc_loop_against_the_references_closed_loop_golden():
     within 2e-3 m / rad of the reference's over 200 steps, the iteration profile (1 ... 15 per solve) within a few
     iterations everywhere and exact on half of the steps.  Multipliers and penalty are re-initialised by every
     Solve(): carrying them over (tried: SetWarmStart) moves the loop far from the golden."""
-    import filecmp
+    import hashlib
 
     golden = Path(__file__).parent / "golden"
-    ref = Path("/root/reference/legged_ctrl/src/test/test_altro")
-    if ref.exists():    # build container: the fixtures are the reference's own data files, untouched
-        assert filecmp.cmp(golden / "scotty.json", ref / "scotty.json", shallow=False)
-        assert filecmp.cmp(golden / "scotty_mpc.json", ref / "scotty_mpc.json", shallow=False)
+    # the fixtures are the reference's own data files, untouched: SHA-256 of legged_ctrl/src/test/test_altro/<name>
+    for name, sha in (("scotty.json", "66246041e9f77a1d376fdb0a3ea16ae5861a9a6595cc5722d37bd068a15e05da"),
+                      ("scotty_mpc.json", "3849a1571528af5e9700572b80f5c9b0be2566d49155ebe5fec7b875c20269ed")):
+        assert hashlib.sha256((golden / name).read_bytes()).hexdigest() == sha, name
     subprocess.run(["make", "-C", str(ORACLE), "altro_compat_check"], check=True, capture_output=True)
     out = subprocess.run([str(ORACLE / "altro_compat_check"), str(golden)], check=True, capture_output=True, text=True).stdout
     name, *kv = out.split()
