@@ -286,7 +286,9 @@ enum qmpc_query_what {
                                            hand-off's rounding family); 0: pure lane kernel (switched off, another model / mode,
                                            or the records could not be allocated -- ~1e-10 N apart, not bit-identical) */
   QMPC_QUERY_HANDOFF_ALLOC_FAILED = 2,  /* 1: the records' allocation failed on this handle (also reported on stderr) */
-  QMPC_QUERY_KERNEL_FOR_BATCH     = 3,  /* arg = batch: the qmpc_kernel_family a plain solve of that size launches */
+  QMPC_QUERY_KERNEL_FOR_BATCH     = 3,  /* arg = batch: the qmpc_kernel_family a plain solve of that size launches.
+                                           It answers for a call with status records (info != NULL): without them a
+                                           lane-kernel batch runs the pure lane kernel, never the hand-off */
   QMPC_QUERY_LAST_KERNEL          = 4,  /* family of the most recent solve launch */
   QMPC_QUERY_LANE_CAP             = 5,  /* arg = 1 plain solve / 2 cold closed loop / 3 warm closed loop: iteration cap of the
                                            capped lane launch (0: no hand-off) */

@@ -597,7 +597,7 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_upload_params(int
 __attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_launch(int nl, int pslot, int batch, hipStream_t s, const void* dev_params,
                                                                        const double* rec, double* forces, qmpc_info* info, double* ws,
                                                                        unsigned waves, unsigned used, int lanes, const int* perm, double* traj_u,
-                                                                       double* traj_x, size_t lds, long long* prof) {
+                                                                       double* traj_x, size_t lds, long long* prof, int pair) {
   const bool convex = nl == -4;
   if (convex) nl = 4;
 #if QL_UNIT == 2
@@ -619,9 +619,8 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_launch(int nl, in
       hipLaunchKernelGGL((qmpc_lane_ref_kernel<4, MD_CONVEX>), dim3(waves), dim3(kLaneWave), lds, s, pslot, rec, forces, info, batch, ws, used,
                          lanes, perm, traj_u, traj_x, prof);
     else {
-      static const int pair_ref_env = std::getenv("QMPC_LANE_PAIR") ? std::atoi(std::getenv("QMPC_LANE_PAIR")) : 1;
       hipLaunchKernelGGL(qmpc_lane_ref_kernel<4>, dim3(waves), dim3(kLaneWave), lds, s, pslot, rec, forces, info, batch, ws, used,
-                         (lanes == 32 && pair_ref_env) ? -34 : lanes, perm, traj_u, traj_x, prof);
+                         (lanes == 32 && pair) ? -34 : lanes, perm, traj_u, traj_x, prof);
     }
 #if defined(QL_PROFILE)
     {
@@ -644,7 +643,7 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_launch(int nl, in
 __attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_upload_params(int pslot, hipStream_t s, const void* dev_params);
 __attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_launch(int nl, int pslot, int batch, hipStream_t s, const void* dev_params, const double* rec, double* forces,
                                 qmpc_info* info, double* ws, unsigned waves, unsigned used, int lanes, const int* perm, double* traj_u, double* traj_x,
-                                size_t lds, long long* prof);
+                                size_t lds, long long* prof, int pair);
 #endif
 #if QL_UNIT != 2
 // called from qmpc_hip.hip (declared there); hidden: not part of the C ABI
@@ -673,7 +672,7 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_launch(int nl, int ps
                                                                    qmpc_info* info, double* ws, unsigned slots, int* scratch,
                                                                    int upload_params, const double* u_init, double* traj_u,
                                                                    int check_prev, int order_prev, double* traj_x, int iter_cap,
-                                                                   int* hcount, int* hsel, double* hstate, int hcap) {
+                                                                   int* hcount, int* hsel, double* hstate, int hcap, int pair) {
   // nl: 4 (QuatMpc), 8 (the 8-contact-point model) or -4 (ConvexMpc's model: four points, world-frame forces)
   const bool convex = nl == -4;
   if (convex) nl = 4;
@@ -710,8 +709,7 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_launch(int nl, int ps
     perm = scratch + 512;
   }
   // batches that would occupy at most half of the chip's SIMDs with full wavefronts run with 32 lanes per wavefront
-  static const int lanes_env = std::getenv("QMPC_LANE_WIDTH") ? std::atoi(std::getenv("QMPC_LANE_WIDTH")) : 0;
-  const int lanes = lanes_env == 32 || lanes_env == 64 ? lanes_env : ((size_t)batch * 2 <= slots ? 32 : 64);
+  const int lanes = (size_t)batch * 2 <= slots ? 32 : 64;
   const unsigned need = (unsigned)(((size_t)batch + lanes - 1) / lanes);
   const unsigned waves = need < slots / kLaneWave ? need : slots / kLaneWave;
   const unsigned used = waves * (unsigned)lanes;     // instances in flight: the batch stride
@@ -726,7 +724,7 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_launch(int nl, int ps
   if (P.mode == QMPC_MODE_REFERENCE) {      // the reference's own solver mode (QuatMpc with four or eight contact points, ConvexMpc): qmpc_lane_ref_kernel
     if (u_init) return hipErrorInvalidValue;
     return qmpc_lane_ref_launch(convex ? -4 : nl, pslot, batch, s, upload_params ? dev_params : nullptr, rec, forces, info, ws, waves, used, lanes, perm,
-                                traj_u, traj_x, lds, prof);
+                                traj_u, traj_x, lds, prof, pair);
   }
   if (nl == 8)
     hipLaunchKernelGGL(qmpc_lane_kernel<8>, dim3(waves), dim3(kLaneWave), lds, s, pslot, rec, forces, info, batch, ws, used, lanes, perm, prof,
@@ -736,8 +734,7 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_launch(int nl, int ps
                        perm, prof, u_init, traj_u, check_prev, traj_x, iter_cap, hcount, hsel, hstate, hcap);
   else {
     // half-filled wavefronts of the four-point quaternion model: lane pairs (the kernel reads -32 as "32 instances, pairs")
-    static const int pair_env = std::getenv("QMPC_LANE_PAIR") ? std::atoi(std::getenv("QMPC_LANE_PAIR")) : 1;
-    const int lanes_arg = (lanes == 32 && pair_env) ? (pair_env == 2 ? -33 : (pair_env == 4 ? -32 : -34)) : lanes;      // 4: cold rounds only      // QMPC_LANE_PAIR=2: split the trial pass only
+    const int lanes_arg = (lanes == 32 && pair) ? (pair == 2 ? -33 : (pair == 4 ? -32 : -34)) : lanes;      // 4: cold rounds only      // QMPC_LANE_PAIR=2: split the trial pass only
     hipLaunchKernelGGL(qmpc_lane_kernel<4>, dim3(waves), dim3(kLaneWave), lds, s, pslot, rec, forces, info, batch, ws, used, lanes_arg, perm, prof,
                        u_init, traj_u, check_prev, traj_x, iter_cap, hcount, hsel, hstate, hcap);
   }

@@ -197,18 +197,6 @@ __global__ __launch_bounds__(64, OCC) void qmpc_ref8_w_kernel(
 using namespace qmpc_wform_tu;
 
 // called from qmpc_hip.hip (declared there); hidden: not part of the C ABI
-// kd_global: 0 everything in LDS (WVAR 3), 1 gains / records / blocks in the workspace (5), 2 the slack arrays as well (6)
-__attribute__((visibility("hidden"))) size_t qmpc_wform_lds_bytes(int N, int kd_global, int nl, int convex) {
-  LayoutW LW;
-  return (size_t)(nl == 8 ? make_layout_w<8>(N, &LW, kd_global != 0, kd_global == 2)
-                          : make_layout_w<4>(N, &LW, kd_global != 0, kd_global == 2, convex != 0)).total * sizeof(double);
-}
-// the reference-mode body's layout (full: the direction slots exist for eight points too); kd_global: 0 / 1
-__attribute__((visibility("hidden"))) size_t qmpc_wform_ref_lds_bytes(int N, int kd_global, int nl, int convex) {
-  LayoutW LW;
-  return (size_t)(nl == 8 ? make_layout_w<8>(N, &LW, kd_global != 0, false, false, true)
-                          : make_layout_w<4>(N, &LW, kd_global != 0, false, convex != 0, true)).total * sizeof(double);
-}
 __attribute__((visibility("hidden"))) size_t qmpc_wform_slice_doubles(int N, int nl) { return nl == 8 ? wform_slice<8>(N, true) : wform_slice<4>(N, true); }
 __attribute__((visibility("hidden"))) hipError_t qmpc_wform_set_lds(int bytes) {
   const void* k[21] = {reinterpret_cast<const void*>(qmpc_ref8_w_kernel<3, 1>), reinterpret_cast<const void*>(qmpc_ref8_w_kernel<5, 1>),
@@ -229,57 +217,34 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_wform_set_lds(int bytes) {
   }
   return hipSuccess;
 }
-// var: 3 everything in LDS, 5 gains in the workspace gws
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch(int var, int prof, int batch, size_t lds, hipStream_t s,
+// model: QMPC_MODEL_* (eight contact points: records of 64 doubles, 24 forces per instance; ConvexMpc: records of 48 doubles,
+// 12 world-frame forces); var: 3 everything in LDS, 5 gains in the workspace gws, 6 the slack arrays there too;
+// prof: QuatMpc's per-phase cycle counters (3 and 5)
+__attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch(int model, int var, int prof, int batch, size_t lds, hipStream_t s,
                                                                    const void* dev_params, size_t dev_params_size,
                                                                    const qmpc_input* in, double* forces, qmpc_info* info,
                                                                    double* traj_u, double* traj_x, long long* prof_out, double* gws) {
   if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
   DevParams P;
   std::memcpy(&P, dev_params, sizeof P);
-#define QMPC_LAUNCH_W(PR, V) \
-  hipLaunchKernelGGL((qmpc_solve_w_kernel<PR, V>), dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, \
-                     batch, prof_out, gws)
-  if (var == 6) {
-    QMPC_LAUNCH_W(false, 6);
+#define QMPC_LAUNCH_W(kern, ...) \
+  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, batch, __VA_ARGS__)
+  if (model == QMPC_MODEL_QUAT8) {
+    if (var == 6) QMPC_LAUNCH_W(qmpc_solve8_w_kernel<6>, gws);
+    else if (var == 5) QMPC_LAUNCH_W(qmpc_solve8_w_kernel<5>, gws);
+    else QMPC_LAUNCH_W(qmpc_solve8_w_kernel<3>, gws);
+  } else if (model == QMPC_MODEL_CONVEX) {
+    if (var == 6) QMPC_LAUNCH_W(qmpc_solve_cw_kernel<6>, gws);
+    else if (var == 5) QMPC_LAUNCH_W(qmpc_solve_cw_kernel<5>, gws);
+    else QMPC_LAUNCH_W(qmpc_solve_cw_kernel<3>, gws);
+  } else if (var == 6) {
+    QMPC_LAUNCH_W((qmpc_solve_w_kernel<false, 6>), prof_out, gws);
   } else if (var == 5) {
-    if (prof) QMPC_LAUNCH_W(true, 5); else QMPC_LAUNCH_W(false, 5);
+    if (prof) QMPC_LAUNCH_W((qmpc_solve_w_kernel<true, 5>), prof_out, gws); else QMPC_LAUNCH_W((qmpc_solve_w_kernel<false, 5>), prof_out, gws);
   } else {
-    if (prof) QMPC_LAUNCH_W(true, 3); else QMPC_LAUNCH_W(false, 3);
+    if (prof) QMPC_LAUNCH_W((qmpc_solve_w_kernel<true, 3>), prof_out, gws); else QMPC_LAUNCH_W((qmpc_solve_w_kernel<false, 3>), prof_out, gws);
   }
 #undef QMPC_LAUNCH_W
-  return hipGetLastError();
-}
-// eight contact points (records of 64 doubles, 24 forces per instance); var as above
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch8(int var, int batch, size_t lds, hipStream_t s, const void* dev_params,
-                                                                    size_t dev_params_size, const void* in, double* forces, qmpc_info* info,
-                                                                    double* traj_u, double* traj_x, double* gws) {
-  if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
-  DevParams P;
-  std::memcpy(&P, dev_params, sizeof P);
-  const qmpc_input* in_ = static_cast<const qmpc_input*>(in);
-  if (var == 6)
-    hipLaunchKernelGGL(qmpc_solve8_w_kernel<6>, dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
-  else if (var == 5)
-    hipLaunchKernelGGL(qmpc_solve8_w_kernel<5>, dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
-  else
-    hipLaunchKernelGGL(qmpc_solve8_w_kernel<3>, dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
-  return hipGetLastError();
-}
-// ConvexMpc's problem (records of 48 doubles, 12 world-frame forces per instance); var as above
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch_convex(int var, int batch, size_t lds, hipStream_t s, const void* dev_params,
-                                                                          size_t dev_params_size, const void* in, double* forces,
-                                                                          qmpc_info* info, double* traj_u, double* traj_x, double* gws) {
-  if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
-  DevParams P;
-  std::memcpy(&P, dev_params, sizeof P);
-  const qmpc_input* in_ = static_cast<const qmpc_input*>(in);
-  if (var == 6)
-    hipLaunchKernelGGL(qmpc_solve_cw_kernel<6>, dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
-  else if (var == 5)
-    hipLaunchKernelGGL(qmpc_solve_cw_kernel<5>, dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
-  else
-    hipLaunchKernelGGL(qmpc_solve_cw_kernel<3>, dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
   return hipGetLastError();
 }
 // the instances sel[0 .. *sel_count) (device memory), `grid` workgroups walking the list
@@ -299,50 +264,31 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch_list(int var,
                        sel_count, gws, hstate, hcap);
   return hipGetLastError();
 }
-// reference mode; var: 3 everything in LDS, 5 gains in the workspace gws
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_ref_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_params,
-                                                                       size_t dev_params_size, const qmpc_input* in, double* forces,
-                                                                       qmpc_info* info, double* traj_u, double* traj_x, double* gws) {
+// reference mode; model and var as above (3 / 5)
+__attribute__((visibility("hidden"))) hipError_t qmpc_wform_ref_launch(int model, int var, int batch, size_t lds, hipStream_t s,
+                                                                       const void* dev_params, size_t dev_params_size, const qmpc_input* in,
+                                                                       double* forces, qmpc_info* info, double* traj_u, double* traj_x,
+                                                                       double* gws) {
   if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
   DevParams P;
   std::memcpy(&P, dev_params, sizeof P);
   // one instance per SIMD at most -- a small batch, or a horizon whose LDS (> 20 KB: N >= 11) leaves a CU four instances
   // anyway: the whole register file (the 256-register instantiation spills 157 VGPRs and would gain no occupancy for it)
-  if (var == 5 && (batch <= 1024 || lds > 20 * 1024))
-    hipLaunchKernelGGL((qmpc_ref_w_kernel<5, 1>), dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, batch, gws);
-  else if (var == 5)
-    hipLaunchKernelGGL(qmpc_ref_w_kernel<5>, dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, batch, gws);
-  else
-    hipLaunchKernelGGL(qmpc_ref_w_kernel<3>, dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, batch, gws);
-  return hipGetLastError();
-}
-// reference mode of the eight-point model: everything in LDS (3; one instance per CU) or gains / records / blocks in the workspace (5)
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_ref_launch8(int var, int batch, size_t lds, hipStream_t s, const void* dev_params,
-                                                                        size_t dev_params_size, const void* in, double* forces,
-                                                                        qmpc_info* info, double* traj_u, double* traj_x, double* gws) {
-  if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
-  DevParams P;
-  std::memcpy(&P, dev_params, sizeof P);
-  const qmpc_input* in_ = static_cast<const qmpc_input*>(in);
-  if (var == 5)
-    hipLaunchKernelGGL((qmpc_ref8_w_kernel<5, 1>), dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
-  else
-    hipLaunchKernelGGL((qmpc_ref8_w_kernel<3, 1>), dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
-  return hipGetLastError();
-}
-// reference mode of ConvexMpc's problem; same variants
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_ref_launch_convex(int var, int batch, size_t lds, hipStream_t s, const void* dev_params,
-                                                                              size_t dev_params_size, const void* in, double* forces,
-                                                                              qmpc_info* info, double* traj_u, double* traj_x, double* gws) {
-  if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
-  DevParams P;
-  std::memcpy(&P, dev_params, sizeof P);
-  const qmpc_input* in_ = static_cast<const qmpc_input*>(in);
-  if (var == 5 && (batch <= 1024 || lds > 20 * 1024))
-    hipLaunchKernelGGL((qmpc_ref_cw_kernel<5, 1>), dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
-  else if (var == 5)
-    hipLaunchKernelGGL((qmpc_ref_cw_kernel<5, 2>), dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
-  else
-    hipLaunchKernelGGL((qmpc_ref_cw_kernel<3, 1>), dim3((unsigned)batch), dim3(kWave), lds, s, P, in_, forces, info, traj_u, traj_x, batch, gws);
+  const bool one_wave = batch <= 1024 || lds > 20 * 1024;
+#define QMPC_LAUNCH_W(kern) \
+  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, batch, gws)
+  if (model == QMPC_MODEL_QUAT8) {      // everything in LDS (one instance per CU) or gains / records / blocks in the workspace
+    if (var == 5) QMPC_LAUNCH_W((qmpc_ref8_w_kernel<5, 1>));
+    else QMPC_LAUNCH_W((qmpc_ref8_w_kernel<3, 1>));
+  } else if (model == QMPC_MODEL_CONVEX) {
+    if (var == 5 && one_wave) QMPC_LAUNCH_W((qmpc_ref_cw_kernel<5, 1>));
+    else if (var == 5) QMPC_LAUNCH_W((qmpc_ref_cw_kernel<5, 2>));
+    else QMPC_LAUNCH_W((qmpc_ref_cw_kernel<3, 1>));
+  } else {
+    if (var == 5 && one_wave) QMPC_LAUNCH_W((qmpc_ref_w_kernel<5, 1>));
+    else if (var == 5) QMPC_LAUNCH_W(qmpc_ref_w_kernel<5>);
+    else QMPC_LAUNCH_W(qmpc_ref_w_kernel<3>);
+  }
+#undef QMPC_LAUNCH_W
   return hipGetLastError();
 }
