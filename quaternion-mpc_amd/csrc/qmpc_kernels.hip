@@ -22,21 +22,6 @@
 //   qmpc_linearize_kernel, qmpc_leg_kernel, self-test kernels
 #include "qmpc_device.h"
 
-#ifndef QMPC_V2_WAVES
-#define QMPC_V2_WAVES 2
-#endif
-#ifndef QMPC_PF_K
-#define QMPC_PF_K true   // prefetch the next knot's gain row / frame in the rollout (all variants)
-#endif
-#ifndef QMPC_PIPE_ALL
-#define QMPC_PIPE_ALL false  // pipelined operand build in the workspace variants: measured slower (register pressure)
-#endif
-#ifndef QMPC_LEANOPS
-#define QMPC_LEANOPS true    // workspace variants: h Bw0 entries re-read from LDS in the operand build (register pressure)
-#endif
-#ifndef QMPC_NL8_WAVES
-#define QMPC_NL8_WAVES 2
-#endif
 
 namespace qmpc {
 
@@ -776,9 +761,9 @@ __device__ __forceinline__ void roll_load(const Layout& L, const double* sm, con
   r.T[0] = T[0]; r.T[1] = T[1]; r.T[2] = T[2];
   r.uo = sm[L.U + D::NU * k + uj];
 }
-// PF_X: also prefetch the old state (LDS variant: registers to spare); the global-gains
-// variant is register-bound (2 waves/SIMD) and prefetches only its high-latency gain row / T_l
-template <class MD, bool PF_X, bool PF_K, bool LEAN, bool PROF>
+// The next knot's gain row / frame is prefetched one knot ahead.  PF_X: also prefetch the old state (LDS variant: registers
+// to spare); the global-gains variant is register-bound (2 waves/SIMD) and prefetches only its high-latency gain row / T_l
+template <class MD, bool PF_X, bool LEAN, bool PROF>
 __device__ inline void rollout_closed(const DevParams& P, const Layout& L, double* sm, const double* KD,
                                       const double* ROT, double alpha, int lane, Prof<PROF>& prof) {
   typedef typename MD::D D;
@@ -796,9 +781,8 @@ __device__ inline void rollout_closed(const DevParams& P, const Layout& L, doubl
 #pragma unroll
     for (int i = 0; i < 13; ++i) sm[L.Xc + i] = xc[i];
   RollLoads cur, nxt;
-  if (PF_K) roll_load<D, PF_X>(L, sm, KD, ROT, 0, uj, ql, qa, cur);
+  roll_load<D, PF_X>(L, sm, KD, ROT, 0, uj, ql, qa, cur);
   for (int k = 0; k < N; ++k) {
-    if (!PF_K) roll_load<D, PF_X>(L, sm, KD, ROT, k, uj, ql, qa, cur);
     if (!PF_X)
 #pragma unroll
       for (int i = 0; i < 13; ++i) cur.xo[i] = sm[L.X + 13 * k + i];
@@ -820,7 +804,7 @@ __device__ inline void rollout_closed(const DevParams& P, const Layout& L, doubl
       unew = cur.uo + inc;
     }
     prof.tick(PH_R_GAIN);
-    if (PF_K && k + 1 < N) roll_load<D, PF_X>(L, sm, KD, ROT, k + 1, uj, ql, qa, nxt);   // one knot ahead
+    if (k + 1 < N) roll_load<D, PF_X>(L, sm, KD, ROT, k + 1, uj, ql, qa, nxt);   // one knot ahead
     // broadcast the new inputs from their owner lanes (4l+a) with v_readlane: no LDS round trip
     double un[D::NU];
 #pragma unroll
@@ -832,7 +816,7 @@ __device__ inline void rollout_closed(const DevParams& P, const Layout& L, doubl
     if (lane == 0)
 #pragma unroll
       for (int i = 0; i < 13; ++i) sm[L.Xc + 13 * (k + 1) + i] = xn[i];
-    if (PF_K) cur = nxt;
+    cur = nxt;
     prof.tick(PH_R_STEP);
   }
   QSYNC();
@@ -954,7 +938,7 @@ __device__ inline double cost_plain(const DevParams& P, const Layout& L, double*
 // VAR 0: everything in LDS; 1: gains / rotation blocks in the global workspace gws (one slice per instance);
 // 2: the slack / multiplier arrays there as well
 #define QMPC_SOLVE_WAVES(MD, VAR) \
-  ((VAR) == 0 || (VAR) == 3 ? 1 : (MD::NL != 4 ? ((VAR) == 2 ? QMPC_NL8_WAVES : 1) : ((VAR) == 2 ? QMPC_V2_WAVES : 2)))
+  ((VAR) == 0 || (VAR) == 3 ? 1 : (MD::NL != 4 ? ((VAR) == 2 ? 2 : 1) : 2))
 template <class MD, bool PROF, int VAR>
 __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(MD, VAR)) void qmpc_solve_kernel(
     DevParams P, const qmpc_input* __restrict__ in_, double* __restrict__ forces, qmpc_info* __restrict__ info,

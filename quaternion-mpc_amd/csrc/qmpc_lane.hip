@@ -29,9 +29,9 @@
 // The file is compiled as TWO units of the library (__graft_entry__.py): QL_UNIT 1 -- the converged mode's kernel, the sort
 // kernels and the launcher (qmpc_lane.hip itself, scheduling strategy max-ilp: +3 % for the pair forms, nothing for the plain
 // ones) -- and QL_UNIT 2 -- the reference mode's kernel with its own launcher (qmpc_lane_ref.hip includes this file; the default
-// strategy: max-ilp costs that kernel 5-8 %).  QL_UNIT 0 (tools/lane_variants.py): everything in one unit.
-#ifndef QL_UNIT
-#define QL_UNIT 0
+// strategy: max-ilp costs that kernel 5-8 %, profiles/HISTORY_r06.md).
+#if !defined(QL_UNIT) || (QL_UNIT != 1 && QL_UNIT != 2)
+#error "QL_UNIT must be 1 (the converged mode's unit) or 2 (the reference mode's unit)"
 #endif
 namespace qmpc {
 namespace lane {
@@ -382,14 +382,7 @@ __global__ __launch_bounds__(kLaneWave) void qmpc_lane_kernel(int pslot, const d
   // the launcher hands them to the wave-per-instance kernel (straggler hand-off, qmpc_hip.hip)
   const int itmax = (iter_cap > 0 && iter_cap < P.iterations_max) ? iter_cap : P.iterations_max;
   const size_t block_elems = (size_t)make_wsoff<NL>(P.N).total * kLaneWave;
-#if defined(QL_DIAG_ALIAS)
-  // diagnostic builds only (tools/lane_variants.py, profiles/r06_lane_traffic_bound.txt): every wavefront of an XCD works in
-  // ONE workspace block, so every access hits that XCD's L2 -- the results are garbage, the instruction stream is not
-  // (QL_DIAG_ROUNDS fixes the control flow)
-  const unsigned long long wsb = reinterpret_cast<unsigned long long>(ws + (size_t)(blockIdx.x % QL_DIAG_ALIAS) * block_elems);
-#else
   const unsigned long long wsb = reinterpret_cast<unsigned long long>(ws + (size_t)blockIdx.x * block_elems);
-#endif
   // Lane pairs (four-point quaternion model, batches that fill half of every wavefront): lanes i and i + 32 take the SAME instance;
   // every pass runs duplicated on the partner -- a wave64 FP64 instruction issues its four passes whatever the mask -- except the
   // per-point blocks of the trial pass, which the pair splits (pass_C<..., PAIR>).  QMPC_LANE_PAIR=0 restores the masked half.
@@ -425,33 +418,6 @@ __global__ __launch_bounds__(kLaneWave) void qmpc_lane_kernel(int pslot, const d
     for (int i = 0; i < LP_COUNT; ++i) st.t[i] = 0;
     st.last = clock64();
     int rounds = 0;
-#endif
-#if defined(QL_DIAG_ROUNDS)
-    // diagnostic builds only: a FIXED number of rounds whatever the iterates do (no convergence test, no failure exit), so
-    // that variants whose data are garbage (aliased workspace, elided stores) run the instruction stream of a real launch
-    for (int round = 0; round < QL_DIAG_ROUNDS; ++round) {
-      if (active) {
-        if (warm && __any(st.rho != 0.0)) {
-          if (kPairable && pairm && pair_b && pair_w) call_A<NL, true, MD, kPairable>(a, Kp, sp); else call_A<NL, true, MD>(a, Kp, sp);
-        } else if (kPairable && pairm && pair_b) call_A<NL, false, MD, kPairable>(a, Kp, sp);
-        else call_A<NL, false, MD>(a, Kp, sp);
-        double sg = P.sigma;
-        const double amin = fmin(st.last_ap, st.last_ad);
-        if (st.it > 1 && amin >= 0.99) sg = P.sigma_fast;
-        else if (st.it > 1 && amin < 0.2) sg = fmax(sg, 0.8);
-        else if (st.it > 1 && amin < 0.5) sg = fmax(sg, 0.5);
-        st.target = sg * st.mu;
-        const bool wrows = warm && __any(st.rho != 0.0);
-        const bool pb = kPairable && pairm && pair_b;
-        if (wrows) { if (pb && pair_w) call_B<NL, true, MD, kPairable>(a, Kp, sp); else call_B<NL, true, MD>(a, Kp, sp); }
-        else if (pb) call_B<NL, false, MD, kPairable>(a, Kp, sp);
-        else call_B<NL, false, MD>(a, Kp, sp);
-        if (wrows) { if (kPairable && pairm && pair_w) call_C<NL, true, MD, kPairable>(a, Kp, sp); else call_C<NL, true, MD>(a, Kp, sp); }
-        else if (kPairable && pairm) call_C<NL, false, MD, kPairable>(a, Kp, sp);
-        else call_C<NL, false, MD>(a, Kp, sp);
-      }
-    }
-    if (active) { st.status = QMPC_OK; active = false; }
 #endif
     while (__any(active)) {
       if (active) {
@@ -547,7 +513,7 @@ __global__ __launch_bounds__(256) void qmpc_lane_sort_count(const double* __rest
   __syncthreads();
   if (hist[threadIdx.x]) atomicAdd(&scratch[threadIdx.x], hist[threadIdx.x]);
 }
-#if QL_UNIT != 2      // (not a template: defined once)
+#if QL_UNIT == 1      // (not a template: defined once)
 __global__ __launch_bounds__(64) void qmpc_lane_sort_scan(int* __restrict__ scratch) {
   if (threadIdx.x != 0) return;
   int run = 0;
@@ -583,16 +549,11 @@ __global__ __launch_bounds__(256) void qmpc_lane_sort_scatter(const double* __re
 using namespace qmpc;
 using namespace qmpc::lane;
 
-// the reference mode's launch (its own unit of the library when QL_UNIT is 1 / 2: the kernel is scheduled differently, see the top
-// of the file); dev_params: the block to upload into THIS unit's table first, or null (uploaded already)
-#if QL_UNIT != 1
-__attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_upload_params(int pslot, hipStream_t s, const void* dev_params) {
+// the reference mode's launch (its own unit of the library: the kernel is scheduled differently, see the top of the file);
+// dev_params: the block to upload into THIS unit's table first, or null (uploaded already)
 #if QL_UNIT == 2
+__attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_upload_params(int pslot, hipStream_t s, const void* dev_params) {
   return hipMemcpyToSymbolAsync(HIP_SYMBOL(ql_params), dev_params, sizeof(DevParams), sizeof(DevParams) * (size_t)pslot, hipMemcpyHostToDevice, s);
-#else
-  (void)pslot; (void)s; (void)dev_params;
-  return hipSuccess;      // one unit: one table
-#endif
 }
 __attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_launch(int nl, int pslot, int batch, hipStream_t s, const void* dev_params,
                                                                        const double* rec, double* forces, qmpc_info* info, double* ws,
@@ -600,12 +561,10 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_launch(int nl, in
                                                                        double* traj_x, size_t lds, long long* prof, int pair) {
   const bool convex = nl == -4;
   if (convex) nl = 4;
-#if QL_UNIT == 2
   if (dev_params) {
     const hipError_t e = qmpc_lane_ref_upload_params(pslot, s, dev_params);
     if (e != hipSuccess) return e;
   }
-#endif
 #if defined(QL_PROFILE)
   long long* d_prof = prof;
   DevParams P;
@@ -645,7 +604,7 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_ref_launch(int nl, in
                                 qmpc_info* info, double* ws, unsigned waves, unsigned used, int lanes, const int* perm, double* traj_u, double* traj_x,
                                 size_t lds, long long* prof, int pair);
 #endif
-#if QL_UNIT != 2
+#if QL_UNIT == 1
 // called from qmpc_hip.hip (declared there); hidden: not part of the C ABI
 __attribute__((visibility("hidden"))) size_t qmpc_lane_ws_bytes(int N, int nl, unsigned slots, int wide) {
   return sizeof(double) * lane_ws_elements(N, nl, wide != 0) * (size_t)slots;      // wide: handles in the reference's solver mode
@@ -761,4 +720,4 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_launch(int nl, int ps
 #endif
   return hipGetLastError();
 }
-#endif      // QL_UNIT != 2
+#endif      // QL_UNIT == 1

@@ -127,9 +127,6 @@ struct LaneK {
   double refp[13];       // reference parameters: pos vel acc quat_d
 };
 
-#ifndef QL_AL_G2_AHEAD
-#define QL_AL_G2_AHEAD 2      // second gain block of the trial rollouts: 0 at the top of its knot, 1 a whole knot ahead (it spills: 14.2 -> 17.0 ms at 65536 instances), 2 at the end of the previous knot
-#endif
 // workspace offsets in ELEMENTS of one lane's column (element e of lane s of a wave lives at wave_base[64 e + s])
 struct WsOff {
   int X, U, dU, S, LAM, G, RC, total, G2;
@@ -172,14 +169,7 @@ inline size_t lane_ws_elements(int N, int nl, bool wide = false) {
 // rows of the point (LegAhead), three doubles at a time, instead of living in 6 NL registers through every pass: where
 // the compiler parked them in scratch by itself it re-loaded them at the top of each point's block, behind the
 // prefetches just issued (the memory counter is in order: waiting for the re-load waited for the prefetch).
-constexpr bool kFootAhead = true;
 typedef QL_PRIV_AS const double* FootPtr;
-#ifndef QL_NT_ST         // the plain forms' sweep stores are non-temporal (nothing re-reads a row before the workspace has streamed
-#define QL_NT_ST 1         // through the caches once): config 3 -2 %, B=65536 N=10 -1 %; the pair forms (half the bytes per wavefront:
-#endif                    // their rows do come back from the L2) keep ordinary stores (StOwn): +1 % with the hint
-#ifndef QL_NT_LD
-#define QL_NT_LD 0
-#endif
 struct Ctx {
   QL_GLOBAL_AS double* ws;   // this wave's block of the workspace: [element][lane]
   unsigned wrow;             // bytes per workspace row (8 x lanes per wave)
@@ -196,38 +186,18 @@ struct Ctx {
   QL_FN QL_GLOBAL_AS double& W(int e) const {
     return *reinterpret_cast<QL_GLOBAL_AS double*>(reinterpret_cast<QL_GLOBAL_AS char*>(ws) + ((unsigned)e * wrow + woff));
   }
-  // store of a pass (the hot sweeps A / B / C): the same instruction as `W(e) = v`.  Diagnostic builds
-  // (-DQL_DIAG_NOSTORE, tools/lane_variants.py: the traffic-bound experiment of profiles/r06_lane_traffic_bound.txt)
-  // keep the value alive and drop the store.
+  // store of a pass (the hot sweeps A / B / C): non-temporal, since nothing re-reads a row before the workspace has streamed
+  // through the caches once (plain forms: config 3 -2 %, B=65536 N=10 -1 %; profiles/HISTORY_r06.md)
   QL_FN void St(int e, double v) const {
-#if defined(QL_DIAG_NOSTORE) && QL_DEVICE
-    asm volatile("" ::"v"(v));
-#elif defined(QL_PAIR_ST_LOWER) && QL_DEVICE
-    if (!half) W(e) = v;      // pair mode: the partner lanes' copies of a duplicated pass carry the same values to the same addresses
-#elif QL_NT_ST && QL_DEVICE
+#if QL_DEVICE
     __builtin_nontemporal_store(v, &W(e));
 #else
     W(e) = v;
 #endif
   }
-  // a row read that nothing re-reads before the workspace has streamed through the caches once (experiment: QL_NT_LD)
-  QL_FN double Ld(int e) const {
-#if QL_NT_LD && QL_DEVICE
-    return __builtin_nontemporal_load(&W(e));
-#else
-    return W(e);
-#endif
-  }
-  // a store that is this lane's OWN in pair mode (the split trial pass: each partner writes its point's increments)
-  QL_FN void StOwn(int e, double v) const {
-#if defined(QL_DIAG_NOSTORE) && QL_DEVICE
-    asm volatile("" ::"v"(v));
-#elif QL_NT_ST && QL_DEVICE
-    __builtin_nontemporal_store(v, &W(e));
-#else
-    W(e) = v;
-#endif
-  }
+  // a store that is this lane's OWN in pair mode (the split trial pass: each partner writes its point's increments); the
+  // same instruction as St
+  QL_FN void StOwn(int e, double v) const { St(e, v); }
   QL_FN QL_LDS_AS double& PL(int i) const {
     return *reinterpret_cast<QL_LDS_AS double*>(reinterpret_cast<QL_LDS_AS char*>(pl) + ((unsigned)i * prow + poff));
   }
@@ -295,7 +265,7 @@ struct Ctx {
   }
 };
 
-// optional phase-level cycle accounting (diagnostic builds: -DQL_PROFILE; tools/lane_prof.sh)
+// optional phase-level cycle accounting (diagnostic builds: -DQL_PROFILE, __graft_entry__.build_hip(profile_lane=True))
 enum { LP_A = 0, LP_B_HEAD, LP_B_LEGS, LP_B_EXPAND, LP_B_MP, LP_B_CONGR, LP_B_FACT, LP_B_UPD, LP_B_GAIN, LP_C_HEAD, LP_C_LEGS,
        LP_C_STEP, LP_COUNT };
 // compiler-level memory fence: values read from the lane-private rows before it are re-read after it instead of being
@@ -340,7 +310,7 @@ QL_FN unsigned ql_partner_addr() { return 0; }
 #endif
 // scheduling barrier: the instruction scheduler moves nothing across it (two unrolled per-point blocks whose temporaries
 // would otherwise be live together)
-#if QL_DEVICE && !defined(QL_NO_SCHED_BARRIER)
+#if QL_DEVICE
 #define QL_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
 #else
 #define QL_SCHED_BARRIER() do { } while (0)
@@ -352,7 +322,7 @@ QL_FN unsigned ql_partner_addr() { return 0; }
 #else
 #define QL_WAIT_VMEM() do { } while (0)
 #endif
-#if QL_DEVICE && !defined(QL_NO_FENCE)
+#if QL_DEVICE
 #define QL_FENCE() asm volatile("" ::: "memory")
 #else
 #define QL_FENCE() do { } while (0)
@@ -772,9 +742,8 @@ struct LegAheadT<false> {
 };
 template <class RT>
 QL_FN void fetch_foot(const Ctx& c, FootPtr fp, int l, RT& R) {
-  if (kFootAhead)
 #pragma unroll
-    for (int a = 0; a < 3; ++a) R.foot[a] = (c.foot_row >= 0) ? c.SR(c.foot_row + 3 * l + a) : fp[3 * l + a];
+  for (int a = 0; a < 3; ++a) R.foot[a] = (c.foot_row >= 0) ? c.SR(c.foot_row + 3 * l + a) : fp[3 * l + a];
 }
 template <int NL, bool WITH_DU = false, class RT>
 QL_FN void fetch_ahead(const Ctx& c, const WsOff& O, int k, int l, RT& R, FootPtr fp, bool rcrows = false) {     // k, l wave-uniform run-time values
@@ -782,17 +751,17 @@ QL_FN void fetch_ahead(const Ctx& c, const WsOff& O, int k, int l, RT& R, FootPt
   if constexpr (RT::kHasRc) {
     if (rcrows)
 #pragma unroll
-      for (int i = 0; i < 6; ++i) R.rc[i] = c.Ld(O.RC + 6 * NL * k + 6 * l + i);
+      for (int i = 0; i < 6; ++i) R.rc[i] = c.W(O.RC + 6 * NL * k + 6 * l + i);
   }
 #pragma unroll
-  for (int a = 0; a < 3; ++a) R.u[a] = c.Ld(O.U + 3 * NL * k + 3 * l + a);
+  for (int a = 0; a < 3; ++a) R.u[a] = c.W(O.U + 3 * NL * k + 3 * l + a);
   if (WITH_DU)
 #pragma unroll
-    for (int a = 0; a < 3; ++a) R.du[a] = c.Ld(O.dU + 3 * NL * k + 3 * l + a);
+    for (int a = 0; a < 3; ++a) R.du[a] = c.W(O.dU + 3 * NL * k + 3 * l + a);
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    R.s[i] = c.Ld(O.S + 6 * NL * k + 6 * l + i);
-    R.lam[i] = c.Ld(O.LAM + 6 * NL * k + 6 * l + i);
+    R.s[i] = c.W(O.S + 6 * NL * k + 6 * l + i);
+    R.lam[i] = c.W(O.LAM + 6 * NL * k + 6 * l + i);
   }
 }
 // wave-uniform stance mask: bit l set when any lane of the wavefront has contact point l in stance
@@ -815,62 +784,6 @@ QL_FN int next_bit(unsigned m, int l) {
   return -1;
 }
 
-#ifndef QL_PF_CH      // old state and gains of pass C one knot ahead
-#define QL_PF_CH 1
-#endif
-#ifndef QL_C_SPLIT       // pass C, plain form: the two points of a pair jointly in one basic block (0), one after the other, each
-                         // re-fetching its rows after its own block (1), or both re-fetching after the second block (2: the first
-                         // point's next rows are not in flight under the second point's temporaries -- no spill inside the loop)
-#define QL_C_SPLIT 2
-#endif
-#ifndef QL_C_CR_PER_LEG  // ... rebuilding the cone rows per point instead of keeping 24 registers through the pass
-#define QL_C_CR_PER_LEG 0
-#endif
-#ifndef QL_C_SPEC        // pass C, pair form: the sweep exists twice (both diagonal pairs in stance / one) instead of once with the
-#define QL_C_SPEC 0      // second pair's block under a wave-uniform condition
-#endif
-#ifndef QL_A_KNOT_AHEAD  // pass A, plain form, four points: a buffer per point, fetched a knot ahead
-#define QL_A_KNOT_AHEAD 1
-#endif
-#ifndef QL_A_PAIR_AHEAD  // pass A, pair form: per-round row buffers fetched a knot ahead
-#define QL_A_PAIR_AHEAD 0
-#endif
-#ifndef QL_B_BPERM       // pass B, pair forms, step 5: the partner's z through ds_bpermute instead of swap + select
-#define QL_B_BPERM 1
-#endif
-#ifndef QL_CAL_KLDS_PLAIN   // ... in the plain forms as well (the lanes' own slots of the LDS block)
-#define QL_CAL_KLDS_PLAIN 1
-#endif
-#ifndef QL_CAL_KLDS      // reference mode's trial sweep, pair form: per-instance constants in LDS staging rows
-#define QL_CAL_KLDS 30      // bits: 1 cone rows (off: with them read per knot the per-point block contracts its sums differently from the plain form), 2 gravity, 4 wd0, 8 contact points, 16 reference parameters
-#endif
-#ifndef QL_B_KLDS        // pass B, pair forms: the per-instance constants in LDS staging rows instead of private memory
-#define QL_B_KLDS 1
-#endif
-#ifndef QL_B_PARK        // pass B, pair forms: p waits in LDS staging rows across the contact points
-#define QL_B_PARK 0
-#endif
-#ifndef QL_B_XSTAGE      // pass B, pair forms: the knot's state through the LDS staging rows (global_load_lds)
-#define QL_B_XSTAGE 1
-#endif
-#ifndef QL_B_COLSPLIT    // pass B, pair form: the twelve gain columns split between the partner lanes
-#define QL_B_COLSPLIT 1
-#endif
-#ifndef QL_B_RW          // pair forms: the point's input weights from wave-uniform reads and a per-lane choice (1) or indexed per lane (0)
-#define QL_B_RW 1
-#endif
-#ifndef QL_C_RW
-#define QL_C_RW 1
-#endif
-#ifndef QL_C_FIRST_RT    // pass C, pair form: the first pair in stance runs unconditionally with a run-time pair index
-#define QL_C_FIRST_RT 1
-#endif
-#ifndef QL_B_XAHEAD      // pass B: the state of the stage cost is requested before the column sweep
-#define QL_B_XAHEAD 1
-#endif
-#ifndef QL_CR_PER_KNOT    // pass B rebuilds the cone rows per knot instead of keeping 24 registers through the factorisations
-#define QL_CR_PER_KNOT 1
-#endif
 
 // ---- set-up: record -> constants, initial guess U = u_ref (QuatMpc.cpp:253), slacks and multipliers ------------------
 // warm_launch (wave-uniform): the launch carries previous solutions; the rows' initial slack residuals are then kept per
@@ -1058,15 +971,11 @@ QL_FN void pass_A(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
   LegAheadT<WARM> R;         // rows, inputs and trial increments of the NEXT contact point in processing order (not at the first
                       // iteration: nothing is pending then and every input is at its reference)
   // Plain form of the four-point models: one buffer PER POINT, fetched a whole knot ahead (point l of knot k + 1 is requested
-  // when point l of knot k has been copied out): the sweep has the registers (84 doubles) that the other two do not.  Worth
-  // 1 % only: with 1024 full wavefronts streaming this sweep sits at the HBM roof (40 KB per wavefront and knot in ~8 k cycles
-  // = 10 TB/s asked for), not on a latency (profiles/HISTORY_r06.md).
-  constexpr bool kKnotAhead = QL_A_KNOT_AHEAD && NL == 4 && !PAIR;
+  // when point l of knot k has been copied out): the sweep has the registers (84 doubles) that the pair form and the eight-point
+  // model do not.  Worth 1 % only: with 1024 full wavefronts streaming this sweep sits at the HBM roof (40 KB per wavefront and
+  // knot in ~8 k cycles = 10 TB/s asked for), not on a latency (profiles/HISTORY_r06.md).
+  constexpr bool kKnotAhead = NL == 4 && !PAIR;
   LegAheadT<WARM> Rk[kKnotAhead ? NL : 1];
-  // Pair form: one buffer per ROUND (this lane's point of the round), fetched a whole knot ahead as well -- the pair form of this
-  // sweep uses a fifth of the accumulation registers, and one round of it is shorter than a trip to HBM
-  constexpr bool kPairAhead = QL_A_PAIR_AHEAD && NL == 4 && PAIR;
-  LegAheadT<WARM> Rp[kPairAhead ? NL / 2 : 1];
   // pair form: the stance points of the wavefront in ascending order, four bits each (0xF: none)
   unsigned plist = 0xFFFFu;
   int pcount = 0;
@@ -1089,14 +998,6 @@ QL_FN void pass_A(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
       if (!first) fetch_ahead<NL, true>(c, O, 0, l, Rk[l], fp, rcrows);
       else fetch_foot(c, fp, l, Rk[l]);
     }
-  } else if constexpr (kPairAhead) {
-#pragma unroll
-    for (int rd = 0; rd < NL / 2; ++rd) {
-      if (2 * rd >= pcount) continue;       // wave-uniform
-      bool ex;
-      if (!first) fetch_ahead<NL, true>(c, O, 0, pair_point(rd, ex), Rp[rd], fp, rcrows);
-      else fetch_foot(c, fp, pair_point(rd, ex), Rp[rd]);
-    }
   } else {
     bool ex;
     const int l0 = PAIR ? pair_point(0, ex) : first_bit(order);
@@ -1116,16 +1017,15 @@ QL_FN void pass_A(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
         const unsigned pa_ = (plist >> (8 * rd)) & 0xFu, pb_ = (plist >> (8 * rd + 4)) & 0xFu;
         const bool on_lo = (st.con >> pa_) & 1u, on_hi = pb_ != 0xFu && ((st.con >> (pb_ & 3u)) & 1u);
         const bool more = 2 * (rd + 1) < pcount;      // another round of this knot follows
-        LegAheadT<WARM>& Rr = kPairAhead ? Rp[kPairAhead ? rd : 0] : R;      // this lane's rows of the round
         double u[3] = {0.0, 0.0, st.uz}, r[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) r[a] = Rr.foot[a];
+        for (int a = 0; a < 3; ++a) r[a] = R.foot[a];
         double rcl[6];
 #pragma unroll
-        for (int i = 0; i < 6; ++i) rcl[i] = rcrows ? Rr.rc[i] : rc0[i];
+        for (int i = 0; i < 6; ++i) rcl[i] = rcrows ? R.rc[i] : rc0[i];
         if (first) {
           bool ex;
-          if (!kPairAhead) fetch_foot(c, fp, pair_point(more ? rd + 1 : 0, ex), Rr);      // (a round's own buffer keeps its position)
+          fetch_foot(c, fp, pair_point(more ? rd + 1 : 0, ex), R);
           if (warm)      // the warm guess (once per solve: read in place)
 #pragma unroll
             for (int a = 0; a < 3; ++a) u[a] = c.W(O.U + 3 * NL * k + 3 * lm + a);
@@ -1133,21 +1033,20 @@ QL_FN void pass_A(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
           double du[3], sv[6], lv[6], so[6], lo[6], s1v[6], l1v[6];
           unsigned kap = 0;
 #pragma unroll
-          for (int a = 0; a < 3; ++a) { u[a] = Rr.u[a]; du[a] = Rr.du[a]; }
+          for (int a = 0; a < 3; ++a) { u[a] = R.u[a]; du[a] = R.du[a]; }
 #pragma unroll
           for (int i = 0; i < 6; ++i) {
-            lv[i] = Rr.lam[i];
-            kap |= (Rr.s[i] < 0.0) ? (1u << i) : 0u;
-            sv[i] = fabs(Rr.s[i]);
-            so[i] = Rr.s[i];
-            lo[i] = Rr.lam[i];
+            lv[i] = R.lam[i];
+            kap |= (R.s[i] < 0.0) ? (1u << i) : 0u;
+            sv[i] = fabs(R.s[i]);
+            so[i] = R.s[i];
+            lo[i] = R.lam[i];
             s1v[i] = 0.0;
             l1v[i] = 0.0;
           }
           {     // this lane's next rows: its point of the next round of this knot, or of the first round of the next knot
             bool ex;
-            if (kPairAhead) fetch_ahead<NL, true>(c, O, kn, lm, Rr, fp, rcrows);      // the same round, one knot on (the last knot re-reads itself)
-            else fetch_ahead<NL, true>(c, O, more ? k : kn, pair_point(more ? rd + 1 : 0, ex), Rr, fp, rcrows);
+            fetch_ahead<NL, true>(c, O, more ? k : kn, pair_point(more ? rd + 1 : 0, ex), R, fp, rcrows);
           }
           if (on_m) {
 #pragma unroll
@@ -1218,7 +1117,7 @@ QL_FN void pass_A(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
       LegAheadT<WARM>& Rc = kKnotAhead ? Rk[kKnotAhead ? l : 0] : R;      // this point's rows
       double u[3] = {0.0, 0.0, st.uz}, r[3];
 #pragma unroll
-      for (int a = 0; a < 3; ++a) r[a] = kFootAhead ? Rc.foot[a] : K.foot[3 * l + a];
+      for (int a = 0; a < 3; ++a) r[a] = Rc.foot[a];
       double rcl[6];
 #pragma unroll
       for (int i = 0; i < 6; ++i) rcl[i] = rcrows ? Rc.rc[i] : rc0[i];
@@ -1395,7 +1294,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
   // Pair forms: the per-instance constants of the pass (rotation, wd0, contact points: 24 values) wait in LDS staging rows
   // 25.. instead of private memory -- the register allocator keeps none of them across a knot, and what it re-reads from
   // scratch at the top of every knot comes back through the vector-memory counter, behind the sweep's stores and the prefetches
-  constexpr bool kKLds = PAIR && QL_B_KLDS && QL_DEVICE;
+  constexpr bool kKLds = PAIR && QL_DEVICE;
   constexpr int kRotRow = 25, kWdRow = 34, kFootRow = 37;
   if constexpr (kKLds) {
 #pragma unroll
@@ -1405,11 +1304,6 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
 #pragma unroll
     for (int i = 0; i < 3 * NL; ++i) c.SRst(kFootRow + i, K.foot[i]);
     c.foot_row = kFootRow;
-  }
-  if (!QL_CR_PER_KNOT) {
-    double s0[6];
-    cone_rows(P, K.rot, cr);
-    initial_rows(P, cr, st.uz, s0, rc0);
   }
   const unsigned order = any_stance<NL>(st.con);      // at least one bit: the lanes of this call have a stance point
   const bool rcrows = WARM && QL_ANY(st.rho != 0.0);
@@ -1453,14 +1347,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
   }
   // Pair forms: the knot's state for the stage cost (step 6) goes through the LDS staging rows 0..12, requested a whole knot
   // before its use (the plain cold form requests it into registers before the column sweep, kXAhead below)
-  constexpr bool kXStage = PAIR && QL_B_XSTAGE && QL_DEVICE;
-  // Pair forms: the gradient p of the cost-to-go (24 registers, idle from the end of a knot to step 4 of the next -- across the
-  // contact points, where the pressure peaks) waits in the staging rows 13..24: what the register allocator would otherwise
-  // park in scratch comes back through the vector-memory counter, i.e. behind every store and prefetch in flight
-  constexpr bool kPark = PAIR && QL_B_PARK && QL_DEVICE;
-  if constexpr (kPark)
-#pragma unroll
-    for (int i = 0; i < 12; ++i) c.SRst(13 + i, pv[i]);
+  constexpr bool kXStage = PAIR && QL_DEVICE;
   for (int k = N - 1; k >= 0; --k) {
     QL_FENCE();
     c.relane();
@@ -1482,7 +1369,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     const int kn = (k > 0) ? k - 1 : 0;
     double Wk[4] = {0, 0, 0, 0};       // ConvexMpc's model: Iw^-1 at this knot's midpoint yaw
     if constexpr (MD == MD_CONVEX) cv_winv_mid(P, c.W(O.X + 13 * k + 2), c.W(O.X + 13 * k + 8), Wk);
-    if (QL_CR_PER_KNOT) {      // rebuilt per knot: 24 registers that need not live through the factorisations
+    {      // the cone rows, rebuilt per knot: 24 registers that need not live through the factorisations
       double s0[6];
       if constexpr (kKLds) {
         double rotk[9];
@@ -1549,7 +1436,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
               lv[i] = act ? al->rho : 0.0;
             }
           }
-          leg_block(P, cr, rcl, lm, sv, lv, kap, AL ? 1.0 : st.rho, AL ? 0.0 : st.target, u, st.uz, lb, QL_B_RW ? Rw : nullptr);
+          leg_block(P, cr, rcl, lm, sv, lv, kap, AL ? 1.0 : st.rho, AL ? 0.0 : st.target, u, st.uz, lb, Rw);
           double V[18];
 #pragma unroll
           for (int i = 0; i < 9; ++i) V[i] = lb.T[i];
@@ -1611,7 +1498,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
       double u[3], sv[6], lv[6], r[3];
       unsigned kap = 0;
 #pragma unroll
-      for (int a = 0; a < 3; ++a) { u[a] = R.u[a]; r[a] = kFootAhead ? R.foot[a] : K.foot[3 * l + a]; }
+      for (int a = 0; a < 3; ++a) { u[a] = R.u[a]; r[a] = R.foot[a]; }
       double rcl[6];
 #pragma unroll
       for (int i = 0; i < 6; ++i) rcl[i] = rcrows ? R.rc[i] : rc0[i];
@@ -1730,9 +1617,6 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     c.relane();
     QL_TICK(st, LP_B_EXPAND);
     double q6[6] = {0, 0, 0, 0, 0, 0}, ak = 0.0;      // AL only: q6 = G y0 + r6,  ak = y0'G y0 + 2 y0'r6 + gam
-    if constexpr (kPark && AL)
-#pragma unroll
-      for (int i = 0; i < 12; ++i) pv[i] = c.SR(13 + i);
     if constexpr (AL) {
       double y0v[6];
 #pragma unroll
@@ -1888,9 +1772,6 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     c.relane();
     QL_TICK(st, LP_B_FACT);
     // ---- 4. P <- Abar' P Abar, p <- Abar' p  in place on the symmetric storage; What = A1^-1 (Wt - h A3) ----
-    if constexpr (kPark && !AL)
-#pragma unroll
-      for (int i = 0; i < 12; ++i) pv[i] = c.SR(13 + i);
     {
       double F[9], W[9], t1[9], t2[9], t3[9], Rb[9];
       rdblk(c, 1, 1, F);
@@ -1978,7 +1859,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     // Every sum of products of this step is written as an explicit chain: which product of `a b + c d` the compiler contracts
     // depends on the instantiation, and the forms of this pass have to return each other's bits.
     //
-    // Pair form (QL_B_COLSPLIT): the step is SPLIT between the partner lanes.  The lower lane owns the columns 0..5 of Y / of the
+    // Pair form: the step is SPLIT between the partner lanes.  The lower lane owns the columns 0..5 of Y / of the
     // gains / of the cost-to-go's upper-left block, the upper lane the columns 6..11 and the lower-right block: each forms only
     // ITS six columns Y_h (36 registers instead of 72), solves them, stores their gains and updates its diagonal block.  The
     // off-diagonal block P(i, 6 + j) -= Y_i' Z Y_(6+j) needs one column of each lane: after every round the lanes swap the z
@@ -1987,7 +1868,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     // below, so that both lanes run the same row indices in the same instruction).  The plain form computes every entry by the
     // same expression -- the (i, 6 + j) with i outside S(j) while it holds z_i, i.e. in column i.
     const double mf = m1 - P.h * m2;
-    constexpr bool kColSplit = PAIR && QL_B_COLSPLIT;
+    constexpr bool kColSplit = PAIR;
     constexpr int NY = kColSplit ? 6 : 12;
     double Y[NY][6];
     auto y_col = [&](const double (&pc)[12], double (&y)[6]) {      // column of Y from a column of P
@@ -2024,7 +1905,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     // free here (the next knot's first point is fetched after the sweep), and read right behind that fetch the state cost a
     // full memory latency per knot.  Plain cold form only: the pair-split and the warm instantiations have no 26 registers
     // to spare (they spill 30 .. 120 B with it)
-    constexpr bool kXAhead = QL_B_XAHEAD && !PAIR && !WARM && !AL;
+    constexpr bool kXAhead = !PAIR && !WARM && !AL;
     double xk[13];
     if (kXAhead)
 #pragma unroll
@@ -2075,18 +1956,9 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
         }
         // the partner's z: z_(6+p) on the lower lane, z_p on the upper
         double zp[6];
-        if (QL_B_BPERM) {
-          const unsigned pa = ql_partner_addr();
+        const unsigned pa = ql_partner_addr();
 #pragma unroll
-          for (int t = 0; t < 6; ++t) zp[t] = ql_partner(z[t], pa);
-        } else {
-#pragma unroll
-          for (int t = 0; t < 6; ++t) {
-            double lo, hi;
-            ql_pair(z[t], lo, hi);
-            zp[t] = c.half ? lo : hi;
-          }
-        }
+        for (int t = 0; t < 6; ++t) zp[t] = ql_partner(z[t], pa);
         // off-diagonal block: P(q, 6 + p) -= Y_q . z_(6+p) on the lower lane, P(p, 6 + q) -= Y_(6+q) . z_p on the upper, q in S(p);
         // the entry (p, 6 + p) is the lower lane's
 #pragma unroll
@@ -2188,9 +2060,6 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
 #pragma unroll
       for (int i = 0; i < 12; ++i) pv[i] += lx[i];
     }
-    if constexpr (kPark)
-#pragma unroll
-      for (int i = 0; i < 12; ++i) c.SRst(13 + i, pv[i]);
     QL_FENCE();
     c.relane();
     QL_TICK(st, LP_B_GAIN);
@@ -2223,7 +2092,7 @@ QL_FN void leg_compute_C(const DevParams& P, const LaneK<NL>& K, const double cr
   for (int i = 0; i < 6; ++i) rc0[i] = rcrows ? R.rc[i] : rc0_[i];
   double u[3], r[3];
 #pragma unroll
-  for (int a = 0; a < 3; ++a) { u[a] = R.u[a]; r[a] = kFootAhead ? R.foot[a] : K.foot[3 * l + a]; }
+  for (int a = 0; a < 3; ++a) { u[a] = R.u[a]; r[a] = R.foot[a]; }
   if constexpr (MD == MD_CONVEX) {
     cv_leg_bw0(Wk, r, o.B);
 #pragma unroll
@@ -2314,12 +2183,10 @@ QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
   }
   const bool rcrows = WARM && QL_ANY(st.rho != 0.0);
   LegAheadT<WARM> Ra, Rb;
-  if (QL_PF_CH) {
 #pragma unroll
-    for (int i = 0; i < 13; ++i) xo[i] = xc[i];
+  for (int i = 0; i < 13; ++i) xo[i] = xc[i];
 #pragma unroll
-    for (int i = 0; i < D::GAIN; ++i) gn[i] = c.W(O.G + i);
-  }
+  for (int i = 0; i < D::GAIN; ++i) gn[i] = c.W(O.G + i);
   // The loads above are COMPLETE before the loop is entered: the compiler prices the wait for the gains at the head of a knot
   // on the entry path too, where three of them were the youngest loads in flight -- which made it a wait for everything in
   // flight (vmcnt(0)) at the head of EVERY knot, the rows' prefetch and the increments' stores included.  One exposed latency
@@ -2336,25 +2203,13 @@ QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
   }
   double rp = 0.0, dnA = 0.0, ddA = 1.0, dnB = 0.0, ddB = 1.0, stp = 0.0;      // (A: first points of the pairs, B: second points)
   bool bad = false;
-  // The sweep over the knots exists TWICE in the pair form -- for wavefronts with both diagonal pairs in stance and for those with
-  // one (run-time pair index) -- so that a knot is straight-line code.  With the second pair's block under a wave-uniform `if`
-  // inside ONE loop (i) the rows prefetched for the next knot had to be in the same registers at the join whichever path was
-  // taken -- the compiler put copies on the skipping path, and a copy is a use: a trot wavefront waited for its prefetch right
-  // after issuing it -- and (ii) the wait for the gains at the head of the next knot was priced on the path that skips every
-  // block, where the gains' own loads are the youngest in flight: a wait for everything (vmcnt(0)) at every head.
-  const int pf = first_bit(porder);
-  auto sweep = [&](auto both_c) {
-  constexpr bool BOTH = decltype(both_c)::value;
+  const int pf = first_bit(porder);      // pair form: the first pair in stance, a run-time index
+  // (the sweep stays a generic lambda called once: written out in place, the same source is inlined and allocated differently)
+  auto sweep = [&](auto) {
   for (int k = 0; k < N; ++k) {
     const int kn = (k + 1 < N) ? k + 1 : k;      // the last knot re-reads itself
     // dx = xc (-) X_k in error coordinates (inverse Cayley map, QuaternionUtils.cpp:16-18)
     double dx[12];
-    if (!QL_PF_CH) {
-#pragma unroll
-      for (int i = 0; i < 13; ++i) xo[i] = c.W(O.X + 13 * k + i);
-#pragma unroll
-      for (int i = 0; i < D::GAIN; ++i) gn[i] = c.W(O.G + D::GAIN * k + i);
-    }
     double Wk[4] = {0, 0, 0, 0};       // ConvexMpc's model: Iw^-1 at the OLD knot state's midpoint yaw (the linearisation point)
     if constexpr (MD == MD_CONVEX) {
       cv_winv_mid(P, xo[2], xo[8], Wk);
@@ -2391,16 +2246,14 @@ QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
         zeta[2 * i + 1] += (double)g1 * dx[j];
       }
     // next knot's old state and gains into the registers just consumed
-    if (QL_PF_CH) {
 #pragma unroll
-      for (int i = 0; i < 13; ++i) xo[i] = c.W(O.X + 13 * kn + i);
+    for (int i = 0; i < 13; ++i) xo[i] = c.W(O.X + 13 * kn + i);
 #pragma unroll
-      for (int i = 0; i < D::GAIN; ++i) gn[i] = c.W(O.G + D::GAIN * kn + i);
-      // ... all of them HERE: left to itself the scheduler sinks the six feed-forward entries below the per-point blocks (their
-      // registers double as zeta), where they are the youngest loads in flight at the next head -- a wait for them is a wait
-      // for everything (vmcnt(0)): the rows' prefetch and the increments' stores included
-      QL_SCHED_BARRIER();
-    }
+    for (int i = 0; i < D::GAIN; ++i) gn[i] = c.W(O.G + D::GAIN * kn + i);
+    // ... all of them HERE: left to itself the scheduler sinks the six feed-forward entries below the per-point blocks (their
+    // registers double as zeta), where they are the youngest loads in flight at the next head -- a wait for them is a wait
+    // for everything (vmcnt(0)): the rows' prefetch and the increments' stores included
+    QL_SCHED_BARRIER();
     QL_TICK(st, LP_C_HEAD);
     double F[3] = {0, 0, 0}, wd[3] = {wd0[0], wd0[1], wd0[2]};
     auto pair_blk = [&](const int pr) {
@@ -2412,7 +2265,7 @@ QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
       double Rw[3];      // this lane's point's weights: two wave-uniform reads and a per-lane choice (see leg_block)
 #pragma unroll
       for (int a = 0; a < 3; ++a) Rw[a] = c.half ? ql_uniform(P.R[3 * (lb & 3) + a]) : ql_uniform(P.R[3 * (la & 3) + a]);
-      leg_compute_C<NL, MD>(P, K, cr, rc0, Ra, lm, zeta, st, om, rcrows, Wk, QL_C_RW ? Rw : nullptr);
+      leg_compute_C<NL, MD>(P, K, cr, rc0, Ra, lm, zeta, st, om, rcrows, Wk, Rw);
       {     // the next pair's row into the registers just consumed
         const int pn = next_bit(porder, pr);
         const int kq = pn >= 0 ? k : kn, pq = pn >= 0 ? pn : first_bit(porder);
@@ -2445,31 +2298,21 @@ QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
       }
     };
     if constexpr (PAIR) {
-      if (BOTH) { pair_blk(0); pair_blk(1); }
-      else if (QL_C_FIRST_RT) {
-        pair_blk(pf);
-        if (!QL_C_SPEC)
+      pair_blk(pf);      // the first pair in stance unconditionally
 #pragma unroll
-          for (int pr = 1; pr < NL / 2; ++pr)
-            if (pr > pf && ((porder >> pr) & 1u)) pair_blk(pr);       // wave-uniform
-      } else {
-#pragma unroll
-        for (int pr = 0; pr < NL / 2; ++pr)
-          if ((porder >> pr) & 1u) pair_blk(pr);       // wave-uniform
-      }
+      for (int pr = 1; pr < NL / 2; ++pr)
+        if (pr > pf && ((porder >> pr) & 1u)) pair_blk(pr);       // wave-uniform
     } else
 #pragma unroll
     for (int pr = 0; pr < NL / 2; ++pr) {
       const int la = pair_leg<NL>(pr, 0), lb = pair_leg<NL>(pr, 1);
       const bool on_a = (st.con >> la) & 1u, on_b = (st.con >> lb) & 1u;
-      if (PAIR) {
-      } else
       if ((porder >> pr) & 1u) {       // wave-uniform
-#if QL_C_SPLIT
-        // one point at a time: compute, fetch the point's NEXT rows into the registers just consumed, use the result -- so that
-        // neither the two points' temporaries nor their results are live together (the joint form needs 140 ... 360 B of scratch
-        // per lane, and a scratch re-load behind the prefetches waits for them: the memory counter is in order).  The sums are
-        // formed in the joint form's order: first point, then second.
+        // one point at a time: compute, use the result, and after the second point fetch both points' NEXT rows into the
+        // registers just consumed -- so that neither the two points' temporaries nor their results are live together, and the
+        // first point's next rows are not in flight under the second point's temporaries (no spill inside the loop; the joint
+        // form needs 140 ... 360 B of scratch per lane, profiles/HISTORY_r06.md).  The sums are formed in the plain order: first
+        // point, then second.
         const int pn = next_bit(porder, pr);
         const int kq = pn >= 0 ? k : kn, pq = pn >= 0 ? pn : first_bit(porder);
 #pragma unroll
@@ -2477,22 +2320,12 @@ QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
           const int lh = hb ? lb : la;
           const bool on_h = hb ? on_b : on_a;
           LegOutC oh;
-          if (QL_C_CR_PER_LEG) {
-            double s0[6];
-            cone_rows(P, K.rot, cr);
-            initial_rows(P, cr, st.uz, s0, rc0);
-          }
           if (hb) {
             leg_compute_C<NL, MD>(P, K, cr, rc0, Rb, lh, zeta, st, oh, rcrows, Wk);
-#if QL_C_SPLIT == 2
             fetch_ahead<NL>(c, O, kq, NL == 4 ? pq : 2 * pq, Ra, fp, rcrows);
-#endif
             fetch_ahead<NL>(c, O, kq, NL == 4 ? 3 - pq : 2 * pq + 1, Rb, fp, rcrows);
           } else {
             leg_compute_C<NL, MD>(P, K, cr, rc0, Ra, lh, zeta, st, oh, rcrows, Wk);
-#if QL_C_SPLIT != 2
-            fetch_ahead<NL>(c, O, kq, NL == 4 ? pq : 2 * pq, Ra, fp, rcrows);
-#endif
           }
 #pragma unroll
           for (int a = 0; a < 3; ++a) c.St(O.dU + 3 * NL * k + 3 * lh + a, oh.du[a]);      // every lane: no store under a per-lane condition (see pass A)
@@ -2508,42 +2341,6 @@ QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
           }
           QL_SCHED_BARRIER();
         }
-#else
-        LegOutC oa, ob;
-        leg_compute_C<NL, MD>(P, K, cr, rc0, Ra, la, zeta, st, oa, rcrows, Wk);
-        leg_compute_C<NL, MD>(P, K, cr, rc0, Rb, lb, zeta, st, ob, rcrows, Wk);
-        {     // the next pair's rows into the registers just consumed
-          const int pn = next_bit(porder, pr);
-          const int kq = pn >= 0 ? k : kn, pq = pn >= 0 ? pn : first_bit(porder);
-          fetch_ahead<NL>(c, O, kq, NL == 4 ? pq : 2 * pq, Ra, fp, rcrows);
-          fetch_ahead<NL>(c, O, kq, NL == 4 ? 3 - pq : 2 * pq + 1, Rb, fp, rcrows);
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {      // every lane: no store under a per-lane condition (see pass A)
-          c.St(O.dU + 3 * NL * k + 3 * la + a, oa.du[a]);
-          c.St(O.dU + 3 * NL * k + 3 * lb + a, ob.du[a]);
-        }
-        if (on_a) {
-#pragma unroll
-          for (int a = 0; a < 3; ++a) {
-            F[a] += oa.u[a];
-            if constexpr (MD != MD_CONVEX) wd[a] += oa.B[3 * a] * oa.u[0] + oa.B[3 * a + 1] * oa.u[1] + oa.B[3 * a + 2] * oa.u[2];
-          }
-          if constexpr (MD == MD_CONVEX) cv_cross_acc(oa.r, oa.u, wd);
-          rp = fmax(rp, oa.rp); stp = fmax(stp, oa.stp); bad = bad || oa.bad;
-          { const bool better = oa.dn * ddA > dnA * oa.dd; dnA = better ? oa.dn : dnA; ddA = better ? oa.dd : ddA; }
-        }
-        if (on_b) {
-#pragma unroll
-          for (int a = 0; a < 3; ++a) {
-            F[a] += ob.u[a];
-            if constexpr (MD != MD_CONVEX) wd[a] += ob.B[3 * a] * ob.u[0] + ob.B[3 * a + 1] * ob.u[1] + ob.B[3 * a + 2] * ob.u[2];
-          }
-          if constexpr (MD == MD_CONVEX) cv_cross_acc(ob.r, ob.u, wd);
-          rp = fmax(rp, ob.rp); stp = fmax(stp, ob.stp); bad = bad || ob.bad;
-          { const bool better = ob.dn * ddA > dnA * ob.dd; dnA = better ? ob.dn : dnA; ddA = better ? ob.dd : ddA; }      // (one running ratio in the plain form)
-        }
-#endif
       }
     }
     QL_TICK(st, LP_C_LEGS);
@@ -2554,8 +2351,7 @@ QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
     QL_TICK(st, LP_C_STEP);
   }
   };
-  if (QL_C_SPEC && PAIR && porder == 3u) sweep(std::true_type{});
-  else sweep(std::false_type{});
+  sweep(0);
   if (PAIR) {      // the partner's candidates: the lower lane tracked the first points (A), the upper lane the second (B)
     double lo, hi;
     ql_pair(rp, lo, hi); rp = fmax(lo, hi);
@@ -2809,11 +2605,11 @@ QL_FN void pass_C_AL(const DevParams& P, const Ctx& c, const WsOff& O, const Lan
   // LDS and are read where they are used -- in registers across the knots they end up in scratch, and a scratch re-load comes
   // back through the vector-memory counter, behind the rows in flight.  The LDS block is free in this pass (the cost-to-go matrix
   // of the backward pass lives there, and that pass rebuilds it from the terminal cost at every call): the pair form uses the
-  // staging rows (upper halves), the plain form the lanes' own slots of the same rows.
-  constexpr bool kKLds = QL_CAL_KLDS && QL_DEVICE && (PAIR || QL_CAL_KLDS_PLAIN);
+  // staging rows (upper halves), the plain form the lanes' own slots of the same rows.  The cone rows are stored there too but
+  // read from registers: read per knot, the per-point block contracts its sums differently from the plain form.
+  constexpr bool kKLds = QL_DEVICE;
   auto kld = [&](int h) -> double { return PAIR ? c.SR(h) : (double)c.PL(h); };
   auto kst = [&](int h, double v) { if (PAIR) c.SRst(h, v); else c.PL(h) = v; };
-  constexpr bool kLCr = kKLds && (QL_CAL_KLDS & 1), kLGb = kKLds && (QL_CAL_KLDS & 2), kLWd = kKLds && (QL_CAL_KLDS & 4), kLFoot = kKLds && (QL_CAL_KLDS & 8), kLRef = kKLds && (QL_CAL_KLDS & 16);
   constexpr int kCrRow = 0, kGbRow = 18, kWdRow = 21, kFootRow = 24, kRefRow = 24 + 3 * NL;
   if constexpr (kKLds) {
 #pragma unroll
@@ -2843,18 +2639,14 @@ QL_FN void pass_C_AL(const DevParams& P, const Ctx& c, const WsOff& O, const Lan
     for (int i = 0; i < 13; ++i) xc[q][i] = c.W(O.X + i);
   const unsigned order = any_stance<NL>(st.con);
   // old state, gains, inputs and multipliers of a knot are fetched one knot ahead, into the registers just consumed
-  // (gains in double precision: columns 0..5 and zeta0 travel one knot ahead like before, columns 6..11 are fetched at the top
-  // of their knot and used after the first half)
+  // (gains in double precision: columns 0..5 and zeta0 travel one knot ahead like before, columns 6..11 are fetched at the end
+  // of the previous knot, see below)
   double xo[13], gn[D::GAIN], g2[D::GAIN2], uk[3 * NL], lk[6 * NL];
   auto load_head = [&](int k) {
 #pragma unroll
     for (int i = 0; i < 13; ++i) xo[i] = c.W(O.X + 13 * k + i);
 #pragma unroll
     for (int i = 0; i < D::GAIN; ++i) gn[i] = c.W(O.G + D::GAIN * k + i);
-#if QL_AL_G2_AHEAD == 1
-#pragma unroll
-    for (int i = 0; i < D::GAIN2; ++i) g2[i] = c.W(O.G2 + D::GAIN2 * k + i);
-#endif
   };
   auto load_leg = [&](int k, int l) {
 #pragma unroll
@@ -2876,10 +2668,8 @@ QL_FN void pass_C_AL(const DevParams& P, const Ctx& c, const WsOff& O, const Lan
   for (int pr = 0; pr < NL / 2; ++pr)
     porder |= (((order >> pair_leg<NL>(pr, 0)) | (order >> pair_leg<NL>(pr, 1))) & 1u) << pr;
   load_head(0);
-#if QL_AL_G2_AHEAD == 2
 #pragma unroll
   for (int i = 0; i < D::GAIN2; ++i) g2[i] = c.W(O.G2 + i);
-#endif
   if constexpr (PAIR) {
 #pragma unroll
     for (int pr = 0; pr < NL / 2; ++pr) if ((porder >> pr) & 1u) load_pair(0, pr);
@@ -2899,16 +2689,11 @@ QL_FN void pass_C_AL(const DevParams& P, const Ctx& c, const WsOff& O, const Lan
     double cr[18], gb[3], refk[13];
     if constexpr (kKLds) QL_FENCE();      // (the reads below stay inside their knot)
 #pragma unroll
-    for (int i = 0; i < 13; ++i) refk[i] = kLRef ? kld(kRefRow + i) : K.refp[i];
-    if constexpr (!kLCr)
+    for (int i = 0; i < 13; ++i) refk[i] = kKLds ? kld(kRefRow + i) : K.refp[i];
 #pragma unroll
-      for (int i = 0; i < 18; ++i) cr[i] = cr_[i];
+    for (int i = 0; i < 18; ++i) cr[i] = cr_[i];
 #pragma unroll
     for (int a = 0; a < 3; ++a) gb[a] = gb_[a];
-#if QL_AL_G2_AHEAD == 0
-#pragma unroll
-    for (int i = 0; i < D::GAIN2; ++i) g2[i] = c.W(O.G2 + D::GAIN2 * k + i);
-#endif
     double Wk[4] = {0, 0, 0, 0};       // ConvexMpc's model: Iw^-1 at the OLD knot state's midpoint yaw (the linearisation point)
     if constexpr (MD == MD_CONVEX) cv_winv_mid(P, xo[2], xo[8], Wk);
     {
@@ -2964,11 +2749,7 @@ QL_FN void pass_C_AL(const DevParams& P, const Ctx& c, const WsOff& O, const Lan
 #pragma unroll
     for (int q = 0; q < NH; ++q)
 #pragma unroll
-      for (int a = 0; a < 3; ++a) { F[q][a] = 0.0; wd[q][a] = kLWd ? kld(kWdRow + a) : K.wd0[a]; }
-    if constexpr (kLCr) {
-#pragma unroll
-      for (int i = 0; i < 18; ++i) cr[i] = kld(kCrRow + i);
-    }
+      for (int a = 0; a < 3; ++a) { F[q][a] = 0.0; wd[q][a] = kKLds ? kld(kWdRow + a) : K.wd0[a]; }
     // one contact point: AL weights, factorised block, the trials' increments, new inputs, torque shares and merit terms
     auto point = [&](const double u[3], const double lam[6], const double r[3], const double Rw[3], int l, double dq[NA][3],
                      double fun[NA][3], double ftq[NA][3], double ju[NA], double at[NA][6]) {
@@ -3044,7 +2825,7 @@ QL_FN void pass_C_AL(const DevParams& P, const Ctx& c, const WsOff& O, const Lan
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
           u[a] = uk[3 * pr + a];
-          r[a] = kLFoot ? kld(kFootRow + 3 * lm + a) : (c.half ? K.foot[3 * lb_ + a] : K.foot[3 * la + a]);
+          r[a] = kKLds ? kld(kFootRow + 3 * lm + a) : (c.half ? K.foot[3 * lb_ + a] : K.foot[3 * la + a]);
           Rw[a] = c.half ? ql_uniform(P.R[3 * (lb_ & 3) + a]) : ql_uniform(P.R[3 * (la & 3) + a]);
         }
 #pragma unroll
@@ -3117,7 +2898,7 @@ QL_FN void pass_C_AL(const DevParams& P, const Ctx& c, const WsOff& O, const Lan
         const double Rw[3] = {P.R[(3 * l) % 12], P.R[(3 * l + 1) % 12], P.R[(3 * l + 2) % 12]};
         double rl[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) rl[a] = kLFoot ? kld(kFootRow + 3 * l + a) : K.foot[3 * l + a];
+        for (int a = 0; a < 3; ++a) rl[a] = kKLds ? kld(kFootRow + 3 * l + a) : K.foot[3 * l + a];
         point(u, lam, rl, Rw, l, dq, fun, ftq, ju, at);
 #pragma unroll
         for (int q = 0; q < NA; ++q) {
@@ -3146,16 +2927,15 @@ QL_FN void pass_C_AL(const DevParams& P, const Ctx& c, const WsOff& O, const Lan
           for (int a = 0; a < 3; ++a) c.St((q == 0 ? O.dU : O.RC) + 3 * NL * k + 3 * l + a, dq[q][a]);
     }
     }
-#if QL_AL_G2_AHEAD == 2
     // the next knot's second gain block: issued once the per-point phase has released its registers, covered by the state steps
+    // (profiles/HISTORY_r05.md: 13.9 ms at 65536 instances; at the top of its own knot 14.2 ms, a whole knot ahead it spills: 17.0 ms)
 #pragma unroll
     for (int i = 0; i < D::GAIN2; ++i) g2[i] = c.W(O.G2 + D::GAIN2 * kn + i);
-#endif
 #pragma unroll
     for (int q = 0; q < NH; ++q) {
       if constexpr (MD == MD_CONVEX) cv_step_fw(P, xc[q], F[q], wd[q], xn);
       else {
-        if constexpr (kLGb)
+        if constexpr (kKLds)
 #pragma unroll
           for (int a = 0; a < 3; ++a) gb[a] = kld(kGbRow + a);
         srbd_step_fw(P, gb, xc[q], F[q], wd[q], xn);
@@ -3168,7 +2948,7 @@ QL_FN void pass_C_AL(const DevParams& P, const Ctx& c, const WsOff& O, const Lan
   for (int q = 0; q < NH; ++q) {
     double refN[13];
 #pragma unroll
-    for (int i = 0; i < 13; ++i) refN[i] = kLRef ? kld(kRefRow + i) : K.refp[i];
+    for (int i = 0; i < 13; ++i) refN[i] = kKLds ? kld(kRefRow + i) : K.refp[i];
     Jp[q] += al_state_cost<MD>(P, refN, N, xc[q]);
   }
   double JpF[NA], alF[NA];

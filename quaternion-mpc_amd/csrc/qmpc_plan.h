@@ -227,7 +227,7 @@ static inline qmpc_plan plan(const qmpc_select& s, int batch, qmpc_call kind, bo
     // measured, persistent vs per-tick: +25 % (256), +28 % (1024), +8 % (2048), -3 % (4096); with the warm start, whose
     // iteration counts spread more: +61 % (1024), +33 % (2048), +8 % (4096), -14 % (16384)
     // (ConvexMpc's own solver mode: the persistent kernel exists on the wrench-form reference bodies only)
-    // Round 6 (tools/r06_loop_decide.sh, profiles/r06_loop_decide.txt): the workspace-form instantiations (two waves per SIMD,
+    // Round 6 (profiles/r06_loop_decide.txt, profiles/HISTORY_r06.md): the workspace-form instantiations (two waves per SIMD,
     // 256 registers, 41 ... 165 spilled VGPRs outside their inner loops) were measured against the per-tick form on every
     // configuration that selects them -- persistent +8 ... +45 % everywhere except ConvexMpc's own solver mode in the workspace
     // form (N=20, 2048 robots: 0.849 vs 0.832 ms per tick), which therefore takes the per-tick form unless forced.

@@ -54,7 +54,7 @@
     rotation_prepass<D, true>(P, L, sm, sl, ROT, rho, lane);
     if (KDG) __syncthreads();
     double dV1 = 0.0;
-    if (backward_pass<MD, false, (!KDG || QMPC_PIPE_ALL), (D::TU > 1)>(P, L, sm, KD, ROT, lane, conmask, prof, &dV1)) {
+    if (backward_pass<MD, false, !KDG, (D::TU > 1)>(P, L, sm, KD, ROT, lane, conmask, prof, &dV1)) {
       status = QMPC_NOT_PD;
       --iter;
       break;
@@ -99,7 +99,7 @@
       }
     } else {
     for (int ls = 0; ls <= P.linesearch_max; ++ls) {
-      rollout_closed<MD, !KDG, QMPC_PF_K, LEAN, false>(P, L, sm, KD, ROT, alpha, lane, prof);
+      rollout_closed<MD, !KDG, LEAN, false>(P, L, sm, KD, ROT, alpha, lane, prof);
       Jn = ref_merit<MD, true>(P, L, sm, sl, rho, conmask, lane, &Jn_plain, &vn);
       const double expected = alpha * dV1;
       const double slack = 1e-12 * fmax(1.0, fabs(J));

@@ -91,10 +91,10 @@
     rotation_prepass<D>(P, L, sm, sl, ROT, target, lane);
     if (KDG) __syncthreads();
     prof.tick(PH_PREPASS);
-    if (backward_pass<MD, PROF, (!KDG || QMPC_PIPE_ALL), (SLG || D::TU > 1), QMPC_LEANOPS && KDG>(P, L, sm, KD, ROT, lane, conmask, prof)) { status = QMPC_NOT_PD; break; }
+    if (backward_pass<MD, PROF, !KDG, (SLG || D::TU > 1), KDG>(P, L, sm, KD, ROT, lane, conmask, prof)) { status = QMPC_NOT_PD; break; }
     if (KDG) __syncthreads();
     double ap, ad;
-    rollout_closed<MD, !KDG, QMPC_PF_K, LEAN, PROF>(P, L, sm, KD, ROT, 1.0, lane, prof);  // trial step
+    rollout_closed<MD, !KDG, LEAN, PROF>(P, L, sm, KD, ROT, 1.0, lane, prof);  // trial step
     prof.tick(PH_ROLL);
     ipm_directions<D>(P, L, sm, sl, target, lane, &ap, &ad, &last_step);
     last_ap = ap; last_ad = ad;

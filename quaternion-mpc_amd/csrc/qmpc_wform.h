@@ -386,9 +386,6 @@ struct ColOps {
 // loads.  The three column multipliers wt[t] / at[t] of a lane sit 3 doubles apart in the knot's record (immediate
 // offsets of one index register); the Wt block of the M fragment and the A1 / A3 blocks of the N = Abar - I fragment
 // ARE those multipliers on the lanes whose fragment row is 3 + t.
-#ifndef QMPC_W_FUSED_ROWS
-#define QMPC_W_FUSED_ROWS 1      // input recovery + directions, and the apply step, one lane per (knot, contact point)
-#endif
 constexpr int kZeroSlots = 54;      // cst[54..63] hold 0.0 (cst[] is used up to slot 52)
 template <int NL> __host__ __device__ constexpr int kZeroSlotsT() { return NL == 4 ? kZeroSlots : 70; }      // 8 points: cst[] is used up to slot 68 of 80
 struct BwPat {
@@ -449,11 +446,7 @@ struct BwPat {
 // acc += sum_t x[lane 3 + t of the row] * m[t]: three v_fmac_f64 with a DPP source (row_newbcast on src0 of the 64-bit
 // VOP2 form, gfx90a+).  The leading s_nop covers the VALU-write -> DPP-read hazard, which the compiler does not track
 // through inline asm.
-#ifndef QMPC_COL_FUSED
-#define QMPC_COL_FUSED 1
-#endif
 __device__ __forceinline__ double fma_bcast345(double acc, double x, const double m[3]) {
-#if QMPC_COL_FUSED
   asm("s_nop 1\n\t"
       "v_fmac_f64_dpp %0, %1, %2 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
       "v_fmac_f64_dpp %0, %1, %3 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
@@ -461,11 +454,6 @@ __device__ __forceinline__ double fma_bcast345(double acc, double x, const doubl
       : "+v"(acc)
       : "v"(x), "v"(m[0]), "v"(m[1]), "v"(m[2]));
   return acc;
-#else
-  acc = fma(m[0], row_bcast<3>(x), acc);
-  acc = fma(m[1], row_bcast<4>(x), acc);
-  return fma(m[2], row_bcast<5>(x), acc);
-#endif
 }
 // x M   (columns 0..5 of the result; M = [[m1 I, 0], [0, Wt], [m2 I, 0], [0, h I]]): lane c < 3 takes m1 x[c] + m2 x[c+6],
 // lane 3 + b takes sum_t x[3+t] Wt[t][b] + h x[9+b]; wt[t] = Wt[t][c-3] on lanes 3..5, 0 elsewhere
@@ -482,59 +470,6 @@ __device__ __forceinline__ double times_Abar(double x, const ColOps& co, const d
   return fma_bcast345(r, x, at);
 }
 
-// One Gauss-Jordan step on pivot J < 6 of the pair (M | Rr) held in two fragment registers (rows 0..3 and 4..7):
-// row J is eliminated from every other row.  Returns -1 / pivot: the diagonal is divided out at the end, and a later step
-// does not touch an earlier pivot (its column is already zero in the later pivot rows).
-// PERM: the pivot row reaches the other row groups through v_permlane16/32_swap (VALU) instead of ds_bpermute (LDS)
-#ifndef QMPC_GJ_PERM
-#define QMPC_GJ_PERM 0
-#endif
-#ifndef QMPC_GJ_FUSED
-#define QMPC_GJ_FUSED 0     // measured: 1.76 M against 1.82 M solves/s -- the 64-bit DPP form issues slower than mov + fma
-#endif
-template <int J, bool INV = false>
-__device__ __forceinline__ double gj6_step(double M[2], double Rr[2], int c, int g, bool& pd, double* Iv = nullptr) {
-  constexpr int ej = J >> 2, gj = J & 3;
-  double mrow, rrow, irow = 0.0;
-  if (QMPC_GJ_PERM) {
-    mrow = rowgroup_bcast<gj>(M[ej]);
-    rrow = rowgroup_bcast<gj>(Rr[ej]);
-    if (INV) irow = rowgroup_bcast<gj>(Iv[ej]);
-  } else {
-    const int src = (gj << 4) | c;
-    mrow = __shfl(M[ej], src);      // row J, same column, all row groups
-    rrow = __shfl(Rr[ej], src);
-    if (INV) irow = __shfl(Iv[ej], src);
-  }
-  const double piv = read_lane(M[ej], (gj << 4) | J);
-  pd = pd && (piv > 0.0);          // false for a NaN pivot too (fmin / fmax would drop it silently)
-  const double ninv = -fast_rcp(piv);
-#if QMPC_GJ_FUSED
-  // X[r][c] += X[r][J] * (-row_J[c] / piv) as ONE v_fmac_f64 with a DPP source per fragment register; the DPP row mask
-  // (one bit per row group) leaves the pivot row itself untouched.  The right-hand side first: it reads the old column J.
-  const double nm = ninv * mrow, nr = ninv * rrow;
-  constexpr int m0 = (ej == 0) ? (0xf ^ (1 << gj)) : 0xf, m1 = (ej == 1) ? (0xf ^ (1 << gj)) : 0xf;
-  asm("s_nop 1\n\t"
-      "v_fmac_f64_dpp %2, %0, %5 row_newbcast:%6 row_mask:%7 bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %3, %1, %5 row_newbcast:%6 row_mask:%8 bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %0, %4 row_newbcast:%6 row_mask:%7 bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %1, %1, %4 row_newbcast:%6 row_mask:%8 bank_mask:0xf"
-      : "+v"(M[0]), "+v"(M[1]), "+v"(Rr[0]), "+v"(Rr[1])
-      : "v"(nm), "v"(nr), "n"(J), "n"(m0), "n"(m1));
-  static_assert(!INV, "the fused form does not track the inverse");
-#else
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const double col = row_bcast<J>(M[e]);
-    const double f = ((e == ej) && (g == gj)) ? 0.0 : col * ninv;
-    M[e] = fma(f, mrow, M[e]);
-    Rr[e] = fma(f, rrow, Rr[e]);
-    if (INV) Iv[e] = fma(f, irow, Iv[e]);
-  }
-#endif
-  return ninv;
-}
-
 // Two Gauss-Jordan steps at once: the 2 x 2 pivot block B = [[a, b], [b, d]] on rows / columns (J0, J0 + 1), J0 = 0, 2, 4 (both
 // rows live in the same fragment register, in adjacent row groups).  Every other row r loses its columns J0, J0 + 1:
 //   row_r += f0 row_J0 + f1 row_J1,   (f0, f1) = -(M[r][J0], M[r][J0+1]) B^-1,   B^-1 = [[d, -b], [-b, a]] / det
@@ -543,10 +478,9 @@ __device__ __forceinline__ double gj6_step(double M[2], double Rr[2], int c, int
 // divided out at the end.  One reciprocal (of det = a d - b^2 > 0 together with a > 0: Sylvester) and one round of
 // cross-row-group broadcasts per PAIR of pivots: the serial chain of the stage solve has three links instead of six
 // (round 5: stage solve 950 -> see profiles/r05_phase_cycles.txt).  Block Cholesky: as stable as the scalar pivots
-// (the cancellation in det is the one the scalar Schur complement d - b^2 / a carries).
-#ifndef QMPC_GJ_BLOCK2
-#define QMPC_GJ_BLOCK2 1
-#endif
+// (the cancellation in det is the one the scalar Schur complement d - b^2 / a carries).  The scalar-pivot form and two
+// other forms of the step (row broadcast through v_permlane*_swap, v_fmac_f64 with a DPP source: 1.76 M against 1.82 M
+// solves/s) were measured and dropped (profiles/HISTORY_r0N.md).
 template <int J0, bool INV = false>
 __device__ __forceinline__ void gj6_pair_step(double M[2], double Rr[2], int c, int g, bool& pd, double* Iv = nullptr) {
   constexpr int ej = J0 >> 2, g0 = J0 & 3, g1 = g0 + 1;
@@ -678,29 +612,16 @@ __device__ inline int backward_pass_w(const DevParams& P, const Layout& L, const
       Iv[1] = (g < 2 && c == 4 + g) ? 1.0 : 0.0;
     }
     double Xf[2];
-#if QMPC_GJ_BLOCK2
     gj6_pair_step<0, REFINE>(Wm, Qf, c, g, pd, Iv);
     gj6_pair_step<2, REFINE>(Wm, Qf, c, g, pd, Iv);
     gj6_pair_step<4, REFINE>(Wm, Qf, c, g, pd, Iv);
-    const double nd0 = 1.0, nd1 = 1.0;      // (the pivot rows leave the block steps as -B^-1 row)
-    Xf[0] = Qf[0];
+    Xf[0] = Qf[0];      // (the pivot rows leave the block steps as -B^-1 row: nothing to divide out)
     Xf[1] = rowok1 ? Qf[1] : 0.0;
-#else
-    const double n0 = gj6_step<0, REFINE>(Wm, Qf, c, g, pd, Iv);
-    const double n1 = gj6_step<1, REFINE>(Wm, Qf, c, g, pd, Iv);
-    const double n2 = gj6_step<2, REFINE>(Wm, Qf, c, g, pd, Iv);
-    const double n3 = gj6_step<3, REFINE>(Wm, Qf, c, g, pd, Iv);
-    const double n4 = gj6_step<4, REFINE>(Wm, Qf, c, g, pd, Iv);
-    const double n5 = gj6_step<5, REFINE>(Wm, Qf, c, g, pd, Iv);
-    const double nd0 = (g == 0) ? n0 : (g == 1 ? n1 : (g == 2 ? n2 : n3)), nd1 = (g == 0) ? n4 : n5;
-    Xf[0] = Qf[0] * nd0;      // X = -diag^-1 Q
-    Xf[1] = rowok1 ? Qf[1] * nd1 : 0.0;
-#endif
     if (REFINE) {
       // -r = C + X + G (S6 X);  v = S6 (-r);  X <- X - W'^-1 v   (nWi = -W'^-1 = n_r Iv, rows 6, 7 zero like every operand here)
       double nWi[2], T1[2], nr[2], vv[2];
-      nWi[0] = Iv[0] * nd0;
-      nWi[1] = (g < 2) ? Iv[1] * nd1 : 0.0;
+      nWi[0] = Iv[0];
+      nWi[1] = (g < 2) ? Iv[1] : 0.0;
       {
         const d4 a = mtm2(S6, Xf, z4);
         T1[0] = a[0]; T1[1] = a[1];
@@ -1335,7 +1256,7 @@ __device__ inline void apply_w(const DevParams& P, const Layout& L, double* sl, 
 __device__ __forceinline__ int trial_states_slot(const Layout& L, int g) {      // knots 1..N of group g's trajectory
   return g == 0 ? L.Xc + 13 : (g == 1 ? L.S : (g == 2 ? L.DLAM : L.XT));
 }
-template <bool PF, int MD = WM_QUAT, int NL = 4>
+template <int MD = WM_QUAT, int NL = 4>
 __device__ inline double rollout_trials_w(const DevParams& P, const Layout& L, const LayoutW& LW, double* sm,
                                           const double* KD, double* ZG, double alpha_g, int lane) {
   typedef typename std::conditional<MD == WM_CONVEX, ConvexModel, typename std::conditional<NL == 8, Quat8Model, QuatModel>::type>::type TM;
@@ -1356,9 +1277,9 @@ __device__ inline double rollout_trials_w(const DevParams& P, const Layout& L, c
 #pragma unroll
     for (int i = 0; i < 13; ++i) sm[L.Xc + i] = xc[i];
   double Jx = TM::knot_cost(P, sm + L.refp, sm + L.uref, 0, xc, nullptr);
-  // one knot; PF: the next knot's gains / old state / Jacobian blocks are loaded meanwhile into the other register set
-  auto knot = [&](int k, RollLoadsW& cur, RollLoadsW& nxt) {
-    if (!PF) roll_load_w(L, LW, sm, KD, k, row, wi, cur);
+  // one knot: its gains / old state / Jacobian blocks are loaded at its top
+  auto knot = [&](int k, RollLoadsW& cur) {
+    roll_load_w(L, LW, sm, KD, k, row, wi, cur);
     double dx[12], e[12];
     if (MD == WM_CONVEX) {
 #pragma unroll
@@ -1382,7 +1303,6 @@ __device__ inline double rollout_trials_w(const DevParams& P, const Layout& L, c
     const double s = (p0 + p1) + (p2 + p3);
     const double wn = (MD == WM_CONVEX) ? s : cur.wk + s;
     if (r >= 6 && r < 12) zg[6 * k + r - 6] = s;
-    if (PF && k + 1 < N) roll_load_w(L, LW, sm, KD, k + 1, row, wi, nxt);
     double w[6];
     w[0] = dpp_mov<0x150>(wn); w[1] = dpp_mov<0x151>(wn); w[2] = dpp_mov<0x152>(wn);      // row_newbcast:0..5
     w[3] = dpp_mov<0x153>(wn); w[4] = dpp_mov<0x154>(wn); w[5] = dpp_mov<0x155>(wn);
@@ -1402,17 +1322,8 @@ __device__ inline double rollout_trials_w(const DevParams& P, const Layout& L, c
       for (int i = 0; i < 13; ++i) xg[13 * k + i] = xn[i];
     Jx += TM::knot_cost(P, sm + L.refp, sm + L.uref, k + 1, xc, nullptr);
   };
-  if (PF) {
-    RollLoadsW ra, rb;
-    roll_load_w(L, LW, sm, KD, 0, row, wi, ra);
-    for (int k = 0; k < N; k += 2) {
-      knot(k, ra, rb);
-      if (k + 1 < N) knot(k + 1, rb, ra);
-    }
-  } else {
-    RollLoadsW ra;
-    for (int k = 0; k < N; ++k) knot(k, ra, ra);
-  }
+  RollLoadsW ra;
+  for (int k = 0; k < N; ++k) knot(k, ra);
   QSYNC();
   return Jx;
 }
@@ -1506,11 +1417,8 @@ __device__ inline void trial_inputs_w(const DevParams& P, const Layout& L, const
 // addresses (lanes without a term read a 0.0 slot).  Bbar_k' y_{k+1} = Wr' (M_k' y_{k+1}) leaves a 6-vector per knot in `my`
 // (lanes 0..2 the force part, 3..5 the torque part); the gradient rows are then formed one lane per (knot, contact point):
 //   gu = R (u - u_ref) + c_l mf + Bw0_l' mt + sum_i max(lambda_i + rho c_i, 0) a_i.
-#ifndef QMPC_STAT_ATTR
-#define QMPC_STAT_ATTR inline
-#endif
 template <int MD = WM_QUAT, int NL = 4>
-__device__ QMPC_STAT_ATTR double stationarity_w(const DevParams& P, const Layout& L, double* sm, const double* sl, double* my,
+__device__ inline double stationarity_w(const DevParams& P, const Layout& L, double* sm, const double* sl, double* my,
                                         const double* Rl, double rho, unsigned conmask, int lane) {
   typedef Dim<NL> D;
   constexpr int LSH = (NL == 8) ? 3 : 2;

@@ -143,28 +143,18 @@
     QSYNC();
     double ap, ad;
     rollout_closed_w<PROF, !KDG, WNL, WMT>(P, L, LW, sm, KD, ROT, lane, prof);      // trial step
-#if QMPC_W_FUSED_ROWS
     prof.tick(PH_ROLL);
-    {
+    {      // input recovery + directions, one lane per (knot, contact point)
       double stp_;      // a non-finite trial step is not applied and must not become the reported step
       if (recover_directions_w<WNL, WMT, LEAN>(P, L, sm, sl, ROT, target, lane, &ap, &ad, &stp_, kapbits)) { status = QMPC_NOT_PD; break; }
       last_step = stp_;
     }
-#else
-    if (recover_inputs_w<WNL, WMT>(P, L, sm, ROT, lane)) { status = QMPC_NOT_PD; break; }
-    prof.tick(PH_ROLL);
-    ipm_directions<WD>(P, L, sm, sl, target, lane, &ap, &ad, &last_step);
-#endif
     last_ap = ap; last_ad = ad;
     prof.tick(PH_DIRS);
     if (LEAN) apply_w<WNL, true>(P, L, sl, ap, ad, conmask, lane, kapbits, sl_part, rc_part, sm, target);   // (before dU is scaled)
     if (ap < 1.0) rollout_scaled_w<WNL, WMT>(P, L, LW, sm, ap, lane);    // shortened primal step
     prof.tick(PH_ROLL);
-#if QMPC_W_FUSED_ROWS
     if (!LEAN) apply_w<WNL, false>(P, L, sl, ap, ad, conmask, lane, kapbits, sl_part, rc_part);
-#else
-    ipm_apply<WD>(P, L, sl, ap, ad, conmask, lane, kapbits, sl_part, rc_part);
-#endif
     prof.tick(PH_APPLY);
     for (int i = lane; i < N * NU; i += kWave) sm[L.U + i] += sm[L.dU + i];
     for (int i = lane; i < (N + 1) * 13; i += kWave) sm[L.X + i] = sm[L.Xc + i];

@@ -7,15 +7,6 @@
 //   WVAR (3: everything in LDS; 5: gains / per-point records / per-knot blocks in the workspace);  DevParams P;
 //   const qmpc_input* in_;  double* forces;  qmpc_info* info;  double* traj_u, * traj_x;  double* gws;  int wslot, b, lane;
 //   double sm[].  Slot use: LAM = lambda, RC = c(U), S = candidate inputs (scratch), DS = y0 of the backward pass (6 per knot).
-#ifndef QMPC_TRIALS_PF
-#define QMPC_TRIALS_PF 0
-#endif
-#ifndef QMPC_REF_REFINE
-#define QMPC_REF_REFINE 1      // iterative refinement of the 6 x 6 stage solve (backward_pass_w<.., REFINE>): truncated iterates keep their rounding
-#endif
-#ifndef QMPC_REF_REFINE_MINN
-#define QMPC_REF_REFINE_MINN 12
-#endif
 #ifndef QMPC_WMODEL
 #define QMPC_WMODEL WM_QUAT      // WM_CONVEX: ConvexMpc's problem (its own mode: five AL-iLQR iterations, ConvexMpc.cpp:36-38)
 #define QMPC_WMODEL_DEFAULTED 1
@@ -88,10 +79,11 @@
     RP_BEGIN();
     prepass_w<true, WNL, WMT>(P, L, sm, sl, ROT, GK, rho, lane);
     if (KDG) bp.init<WNL, WMT>(P, L, lane);
-    // horizons beyond QMPC_REF_REFINE_MINN: the 6 x 6 stage solves with one step of iterative refinement (qmpc_wform.h: REFINE);
-    // up to there the plain elimination already agrees with the oracle to 4e-8 N and is 10 % faster (wave-uniform branch)
-    // (ConvexMpc's problem: at every horizon -- with 5 ms knots only R = 1e-6 sees the force directions)
-    const int bp_fail = (QMPC_REF_REFINE != 0 && (N > QMPC_REF_REFINE_MINN || WMT == WM_CONVEX))
+    // horizons beyond kRefineMinN: the 6 x 6 stage solves with one step of iterative refinement (qmpc_wform.h: REFINE; truncated
+    // iterates keep their rounding); up to there the plain elimination already agrees with the oracle to 4e-8 N and is 10 %
+    // faster (wave-uniform branch) (ConvexMpc's problem: at every horizon -- with 5 ms knots only R = 1e-6 sees the force directions)
+    constexpr int kRefineMinN = 12;
+    const int bp_fail = (N > kRefineMinN || WMT == WM_CONVEX)
                             ? backward_pass_w<false, true, WMT>(P, L, bp, sm, KD, GK, lane, prof, Y0)
                             : backward_pass_w<false, false, WMT>(P, L, bp, sm, KD, GK, lane, prof, Y0);
     if (bp_fail) {
@@ -112,7 +104,7 @@
     for (int ls = 0; ls <= P.linesearch_max && !accepted; ls += 4) {
       const int grp = lane >> 4;
       const double ag = alpha * (grp == 0 ? 1.0 : (grp == 1 ? 0.5 : (grp == 2 ? 0.25 : 0.125)));
-      const double Jx = rollout_trials_w<QMPC_TRIALS_PF && !KDG, WMT, WNL>(P, L, LW, sm, KD, ZG, ag, lane);
+      const double Jx = rollout_trials_w<WMT, WNL>(P, L, LW, sm, KD, ZG, ag, lane);
       double Ju[4], mer[4], vi[4];
       trial_inputs_w<WMT, WNL>(P, L, sm, sl, ROT, ZG, Rl, alpha, rho, lane, Ju, mer, vi);
 #pragma unroll
@@ -168,12 +160,7 @@
     ref_cone_refresh<WD>(P, L, sm, sl, conmask, lane);
     QSYNC();
     RP_BEGIN();
-#ifdef QMPC_STAT_TWICE
-    double stat = stationarity_w<WMT, WNL>(P, L, sm, sl, Y0, Rl, rho, conmask, lane);
-    if (stat > -1.0) stat = stationarity_w<WMT, WNL>(P, L, sm, sl, Y0, Rl, rho * (1.0 + 1e-300 * stat), conmask, lane);
-#else
     const double stat = stationarity_w<WMT, WNL>(P, L, sm, sl, Y0, Rl, rho, conmask, lane);
-#endif
     RP_END(rp_st);
     if (stat < P.tol_stat && viol < P.tol_feas) {
       status = QMPC_OK;
