@@ -53,12 +53,15 @@ typedef enum qmpc_status {
   QMPC_NAN_INPUT = 3,       /* non-finite input record; zero forces            */
   QMPC_LINESEARCH_FAIL = 4, /* no step length reduced the merit function       */
   QMPC_NOT_PD = 5,          /* Quu lost positive definiteness                  */
+  QMPC_BAD_PARAMS = 6,      /* per-instance parameter record rejected
+                               (qmpc_solve_instances); zero forces             */
   /* call-level only */
   QMPC_BAD_ARGUMENT = 16,
   QMPC_NO_DEVICE = 17,      /* HIP runtime / device missing: fail loudly       */
   QMPC_HIP_ERROR = 18,
   QMPC_BATCH_TOO_LARGE = 19,
-  QMPC_UNSUPPORTED = 20     /* optional dependency missing (RCCL for qmpc_gather)  */
+  QMPC_UNSUPPORTED = 20     /* optional dependency missing (RCCL for qmpc_gather), or a
+                               call the handle does not support                 */
 } qmpc_status;
 
 /* ---- solver mode --------------------------------------------------------- */
@@ -293,7 +296,9 @@ enum qmpc_query_what {
   QMPC_QUERY_LANE_CAP             = 5,  /* arg = 1 plain solve / 2 cold closed loop / 3 warm closed loop: iteration cap of the
                                            capped lane launch (0: no hand-off) */
   QMPC_QUERY_DEVICE_BYTES         = 6,  /* device memory the handle holds right now */
-  QMPC_QUERY_ZERO_COPY            = 7   /* 1: host-buffer calls of wave-kernel batches run zero-copy */
+  QMPC_QUERY_ZERO_COPY            = 7,  /* 1: host-buffer calls of wave-kernel batches run zero-copy */
+  QMPC_QUERY_KERNEL_FOR_INSTANCES = 8   /* arg = batch: the qmpc_kernel_family qmpc_solve_instances* launches for that size
+                                           (QMPC_KERNEL_NONE: the handle refuses the call) */
 };
 enum qmpc_kernel_family {
   QMPC_KERNEL_NONE         = 0,
@@ -305,6 +310,54 @@ enum qmpc_kernel_family {
   QMPC_KERNEL_LANE_HANDOFF = 6    /* lane per instance to an iteration cap, stragglers continued by the wave kernel */
 };
 qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value);
+
+/* ---- per-instance robot and cost parameters (QuatMpc handle, converged mode) ----------------------------------------
+ * One launch solves `batch` instances, each with its own robot and tuning: instance i is solved with the handle's
+ * qmpc_params except for the seven fields of iparams[i] below (the handle's own values of those fields are ignored in
+ * this call).  Horizon, knot spacing, mode, drop_ang_vel, tolerances and interior-point settings stay per handle, and so
+ * do the reference's fixed trunk mass and CoM offset in the gravity torque.  Use cases: Monte-Carlo robustness sweeps
+ * over payload, inertia and friction, fleets of differently loaded robots, sweeps over the cost weights.
+ *
+ * Per instance, a record with a non-finite field, mass <= 0, a singular inertia, an r_weight <= 0, a negative q_weight
+ * or w, mu <= 0 or fz_max <= 0 gives that instance QMPC_BAD_PARAMS: zero forces, zero trajectory rows, 0 iterations.
+ * The other instances are unaffected.  Call-level: QMPC_UNSUPPORTED for a ConvexMpc or 8-point handle, a reference-mode
+ * handle, or a handle whose knobs leave no wrench-form kernel for the batch (QMPC_WFORM=0); QMPC_BATCH_TOO_LARGE above
+ * max_batch; QMPC_BAD_ARGUMENT for null pointers.
+ *
+ * Kernel: the wave-per-instance wrench-form kernel a plain solve of the same size takes (everything in LDS, or the
+ * workspace form), with its parameters read per workgroup; where the plain solve takes that kernel too, results are
+ * bit-identical to qmpc_solve on a handle carrying the same values.  There is NO lane-per-instance form: batches at and
+ * above the lane kernel's switch-over (14336 at N <= 12) stay on the wave workspace form (3.6 M solves/s at N=10 where
+ * the lane kernel does 7-9 M), and agree with the plain solve there to ~1e-10 N (another rounding family).  Not covered either: the
+ * reference mode, ConvexMpc, the 8-point model, warm starts, the closed loop.
+ *
+ * The handle's per-instance buffers (the records and one expanded parameter block per instance, about 760 B x max_batch)
+ * are allocated on first use, or now by qmpc_prepare_instances (e.g. before a stream capture). */
+typedef struct qmpc_instance_params {   /* 38 doubles, 304 B */
+  double mass;
+  double inertia[9];        /* row-major, as qmpc_params.inertia */
+  double mu;
+  double fz_max;
+  double q_weights[13];
+  double r_weights[12];
+  double w;
+} qmpc_instance_params;
+
+/* the seven fields of *p, as a record (e.g. to broadcast a handle's robot and edit one field per instance) */
+void        qmpc_instance_params_from(const qmpc_params* p, qmpc_instance_params* out);
+int32_t     qmpc_sizeof_instance_params(void);
+/* Synchronous, host buffers: in [batch], iparams [batch], forces_body [batch][12]; info, traj_u ([batch][N][12]) and
+ * traj_x ([batch][N+1][13]) may be NULL.  Copies explicitly on the handle's stream. */
+qmpc_status qmpc_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_input* in,
+                                 const qmpc_instance_params* iparams, double* forces_body, qmpc_info* info,
+                                 double* traj_u, double* traj_x);
+/* Device buffers, stream-ordered (NULL stream = the handle's), nothing synchronised; d_info may be NULL.  Same rule as
+ * qmpc_solve_device: one launch in flight per handle. */
+qmpc_status qmpc_solve_instances_device(qmpc_handle* h, int32_t batch, const qmpc_input* d_in,
+                                        const qmpc_instance_params* d_iparams, double* d_forces_body,
+                                        qmpc_info* d_info, void* stream);
+/* allocate the per-instance buffers now (qmpc_prepare does not) */
+qmpc_status qmpc_prepare_instances(qmpc_handle* h);
 
 /* Multi-GPU: the single collective of the path.  All-gathers `count` doubles per rank (e.g. the
  * [B/G][12] force block, or forces + qmpc_info records laid out in one buffer) from every rank's `d_local` into

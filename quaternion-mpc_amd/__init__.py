@@ -25,7 +25,7 @@ LIB_PATH = PKG_DIR / "csrc" / "libqmpc_hip.so"
 NX, NE, NU, NLEG, NC = 13, 12, 12, 4, 24
 
 # status codes (include/qmpc.h)
-OK, MAX_ITER, NO_CONTACT, NAN_INPUT, LINESEARCH_FAIL, NOT_PD = 0, 1, 2, 3, 4, 5
+OK, MAX_ITER, NO_CONTACT, NAN_INPUT, LINESEARCH_FAIL, NOT_PD, BAD_PARAMS = 0, 1, 2, 3, 4, 5, 6
 BAD_ARGUMENT, NO_DEVICE, HIP_ERROR, BATCH_TOO_LARGE, UNSUPPORTED = 16, 17, 18, 19, 20
 MODE_CONVERGED, MODE_REFERENCE = 0, 1
 MODEL_QUAT, MODEL_CONVEX, MODEL_QUAT8 = 0, 1, 2
@@ -168,6 +168,49 @@ class LoopParams(C.Structure):
                 ("contact_height", C.c_double), ("warm_start", C.c_double)]
 
 
+# struct qmpc_instance_params (qmpc_solve_instances*): one instance's robot and cost weights, 38 doubles = 304 B
+INSTANCE_PARAMS_DTYPE = np.dtype(
+    [
+        ("mass", "<f8"),
+        ("inertia", "<f8", (9,)),
+        ("mu", "<f8"),
+        ("fz_max", "<f8"),
+        ("q_weights", "<f8", (13,)),
+        ("r_weights", "<f8", (12,)),
+        ("w", "<f8"),
+    ],
+    align=False,
+)
+assert INSTANCE_PARAMS_DTYPE.itemsize == 38 * 8
+
+
+def instance_params(params: "Params", batch: int = 1) -> np.ndarray:
+    """[batch] per-instance records all carrying the seven fields of `params` (edit fields per instance afterwards)."""
+    out = np.zeros(int(batch), dtype=INSTANCE_PARAMS_DTYPE)
+    out["mass"] = params.mass
+    out["inertia"] = np.asarray(params.inertia[:], dtype=np.float64)
+    out["mu"] = params.mu
+    out["fz_max"] = params.fz_max
+    out["q_weights"] = np.asarray(params.q_weights[:], dtype=np.float64)
+    out["r_weights"] = np.asarray(params.r_weights[:], dtype=np.float64)
+    out["w"] = params.w
+    return out
+
+
+def params_with(params: "Params", rec) -> "Params":
+    """A copy of `params` with the seven fields of one per-instance record in place (the handle a plain solve of that
+    instance would use)."""
+    out = params.copy()
+    out.mass = float(rec["mass"])
+    out.inertia[:] = [float(x) for x in np.asarray(rec["inertia"]).ravel()]
+    out.mu = float(rec["mu"])
+    out.fz_max = float(rec["fz_max"])
+    out.q_weights[:] = [float(x) for x in rec["q_weights"]]
+    out.r_weights[:] = [float(x) for x in rec["r_weights"]]
+    out.w = float(rec["w"])
+    return out
+
+
 # struct qmpc_info: 2 x int32 + 4 doubles = 40 B
 INFO_DTYPE = np.dtype(
     [
@@ -240,6 +283,14 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_prepare.restype = i32
     lib.qmpc_query.argtypes = [vp, i32, C.c_int64, C.POINTER(C.c_int64)]
     lib.qmpc_query.restype = i32
+    lib.qmpc_instance_params_from.argtypes = [C.POINTER(Params), vp]
+    lib.qmpc_instance_params_from.restype = None
+    lib.qmpc_solve_instances.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.qmpc_solve_instances.restype = i32
+    lib.qmpc_solve_instances_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    lib.qmpc_solve_instances_device.restype = i32
+    lib.qmpc_prepare_instances.argtypes = [vp]
+    lib.qmpc_prepare_instances.restype = i32
     lib.qmpc_gather.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.qmpc_gather.restype = i32
     lib.qmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -309,7 +360,7 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp]
     lib.qmpc_loop_run_device.restype = i32
     for name in ("qmpc_sizeof_input", "qmpc_sizeof_params", "qmpc_sizeof_info", "qmpc_sizeof_convex_input",
-                 "qmpc_sizeof_input8", "qmpc_sizeof_loop_state"):
+                 "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = i32
     if lib.qmpc_sizeof_input() != INPUT_DTYPE.itemsize:
@@ -324,6 +375,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         raise RuntimeError("qmpc_info ABI size mismatch")
     if lib.qmpc_sizeof_loop_state() != LOOP_STATE_DTYPE.itemsize:
         raise RuntimeError("qmpc_loop_state ABI size mismatch")
+    if lib.qmpc_sizeof_instance_params() != INSTANCE_PARAMS_DTYPE.itemsize:
+        raise RuntimeError("qmpc_instance_params ABI size mismatch")
     return lib
 
 
@@ -381,11 +434,16 @@ EXPORTED_SYMBOLS = (
     "qmpc_host_free",
     "qmpc_prepare",
     "qmpc_query",
+    "qmpc_instance_params_from",
+    "qmpc_sizeof_instance_params",
+    "qmpc_solve_instances",
+    "qmpc_solve_instances_device",
+    "qmpc_prepare_instances",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
 QUERY_HANDOFF_ACTIVE, QUERY_HANDOFF_ALLOC_FAILED, QUERY_KERNEL_FOR_BATCH, QUERY_LAST_KERNEL, QUERY_LANE_CAP, \
-    QUERY_DEVICE_BYTES, QUERY_ZERO_COPY = 1, 2, 3, 4, 5, 6, 7
+    QUERY_DEVICE_BYTES, QUERY_ZERO_COPY, QUERY_KERNEL_FOR_INSTANCES = 1, 2, 3, 4, 5, 6, 7, 8
 KERNEL_FAMILY = {0: "none", 1: "wform_lds", 2: "wform_ws", 3: "dense_lds", 4: "dense_ws", 5: "lane", 6: "lane_handoff"}
 
 
@@ -595,6 +653,39 @@ class Solver:
         if st != OK:
             raise QmpcError(st, "qmpc_solve_device")
 
+    def solve_instances(self, inputs: np.ndarray, iparams: np.ndarray, want_traj: bool = False):
+        """qmpc_solve_instances: instance i solved with the handle's parameters and the seven fields of iparams[i]
+        (INSTANCE_PARAMS_DTYPE).  Returns (forces [B,12], info) or, with want_traj, also traj_u [B,N,12] and traj_x [B,N+1,13]."""
+        inputs = np.ascontiguousarray(inputs, dtype=INPUT_DTYPE)
+        iparams = np.ascontiguousarray(iparams, dtype=INSTANCE_PARAMS_DTYPE)
+        B, N = inputs.shape[0], self.params.horizon
+        if iparams.shape != (B,):
+            raise ValueError(f"iparams: shape {iparams.shape}, expected ({B},)")
+        forces = np.zeros((B, NU), dtype=np.float64)
+        info = np.zeros(B, dtype=INFO_DTYPE)
+        tu = np.zeros((B, N, NU)) if want_traj else None
+        tx = np.zeros((B, N + 1, NX)) if want_traj else None
+        st = self.lib.qmpc_solve_instances(self._h, B, _ptr(inputs), _ptr(iparams), _ptr(forces), _ptr(info), _ptr(tu), _ptr(tx))
+        if st != OK:
+            raise QmpcError(st, "qmpc_solve_instances")
+        return (forces, info, tu, tx) if want_traj else (forces, info)
+
+    def solve_instances_device(self, batch: int, d_in: int, d_iparams: int, d_forces: int, d_info: int, stream: int = 0):
+        """qmpc_solve_instances_device: device pointers (ints), stream-ordered, no synchronisation."""
+        st = self.lib.qmpc_solve_instances_device(self._h, int(batch), C.c_void_p(d_in), C.c_void_p(d_iparams), C.c_void_p(d_forces),
+                                                  C.c_void_p(d_info) if d_info else None, C.c_void_p(stream) if stream else None)
+        if st != OK:
+            raise QmpcError(st, "qmpc_solve_instances_device")
+
+    def kernel_for_instances(self, batch: int) -> str:
+        return KERNEL_FAMILY[self.query(QUERY_KERNEL_FOR_INSTANCES, batch)]
+
+    def prepare_instances(self):
+        """Allocate the per-instance buffers now (qmpc_prepare_instances)."""
+        st = self.lib.qmpc_prepare_instances(self._h)
+        if st != OK:
+            raise QmpcError(st, "qmpc_prepare_instances")
+
     def solve_async(self, inputs: np.ndarray, forces: np.ndarray, info: np.ndarray = None):
         """Host buffers, non-blocking (qmpc_solve_async); the arrays must stay alive until wait()."""
         assert inputs.dtype == INPUT_DTYPE and inputs.flags.c_contiguous and forces.flags.c_contiguous
@@ -800,5 +891,5 @@ class Solver:
 
 
 from .scenarios import (go1_stand_input, quat_to_rot, random_go1_trot_states,  # noqa: E402,F401
-                        random_go1_convex_states, random_biped8_states)
+                        random_go1_convex_states, random_biped8_states, random_go1_variants)
 from .sharding import StepPipeline, gather_forces, shard_range, solve_sharded  # noqa: E402,F401

@@ -48,6 +48,9 @@ hipError_t qmpc_wform_ref_launch(int model, int var, int batch, size_t lds, hipS
 hipError_t qmpc_wform_launch_list(int var, int grid, size_t lds, hipStream_t s, const void* dev_params, size_t dev_params_size,
                                   const qmpc_input* in, double* forces, qmpc_info* info, double* traj_u, double* traj_x,
                                   const int* sel, const int* sel_count, double* gws, const double* hstate, int hcap);
+hipError_t qmpc_wform_inst_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_params, size_t dev_params_size,
+                                  const qmpc_instance_params* rec, void* dev_out, int* status_out, const qmpc_input* in, double* forces,
+                                  qmpc_info* info, double* traj_u, double* traj_x, double* gws);
 
 // qmpc_lane.hip (third translation unit): the lane-per-instance kernel of large batches
 size_t qmpc_lane_ws_bytes(int N, int nl, unsigned slots, int wide);
@@ -102,6 +105,8 @@ struct qmpc_handle {
   struct { double* forces; qmpc_info* info; size_t fbytes, ibytes; } pending;   // copy-out owed to a pageable caller (qmpc_wait)
   int stage_in_busy;           // a non-blocking zero-copy launch may still be READING its records from h_stage_in: the staging is
                                // not refilled before the stream has drained (qmpc_solve_async with a pageable `in`, pinned outputs)
+  unsigned char* d_inst;       // per-instance parameters (qmpc_solve_instances*), on first use: [max_batch] DevParams | [max_batch]
+                               // qmpc_instance_params (staging of the host-buffer call) | [max_batch] int verdicts
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -149,6 +154,7 @@ const char* qmpc_status_string(int32_t s) {
     case QMPC_NAN_INPUT: return "non-finite input";
     case QMPC_LINESEARCH_FAIL: return "line search failed";
     case QMPC_NOT_PD: return "Quu not positive definite";
+    case QMPC_BAD_PARAMS: return "invalid per-instance parameters";
     case QMPC_BAD_ARGUMENT: return "bad argument";
     case QMPC_NO_DEVICE: return "no HIP device (there is no CPU fallback)";
     case QMPC_HIP_ERROR: return "HIP runtime error";
@@ -351,6 +357,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_traj_x) (void)hipFree(h->d_traj_x);
   if (h->d_A) (void)hipFree(h->d_A);
   if (h->d_B) (void)hipFree(h->d_B);
+  if (h->d_inst) (void)hipFree(h->d_inst);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -801,6 +808,106 @@ qmpc_status qmpc_prepare(qmpc_handle* h, int32_t batch) {
   return QMPC_OK;
 }
 
+// ---- per-instance robot and cost parameters (QuatMpc, converged mode; qmpc_wform.hip: qmpc_solve_w_inst_kernel) -------------
+static_assert(sizeof(qmpc_instance_params) == 38 * sizeof(double), "qmpc_instance_params is 38 doubles");
+int32_t qmpc_sizeof_instance_params(void) { return (int32_t)sizeof(qmpc_instance_params); }
+
+void qmpc_instance_params_from(const qmpc_params* p, qmpc_instance_params* out) {
+  if (!p || !out) return;
+  out->mass = p->mass;
+  std::memcpy(out->inertia, p->inertia, sizeof out->inertia);
+  out->mu = p->mu;
+  out->fz_max = p->fz_max;
+  std::memcpy(out->q_weights, p->q_weights, sizeof out->q_weights);
+  std::memcpy(out->r_weights, p->r_weights, sizeof out->r_weights);
+  out->w = p->w;
+}
+
+static size_t instance_bytes(int max_batch) {
+  return (sizeof(DevParams) + sizeof(qmpc_instance_params) + sizeof(int)) * (size_t)max_batch;
+}
+static qmpc_status ensure_instance_buffers(qmpc_handle* h) {
+  if (!h->d_inst) HIP_TRY(hipMalloc(&h->d_inst, instance_bytes(h->max_batch)));
+  return QMPC_OK;
+}
+static DevParams* inst_dev(qmpc_handle* h) { return reinterpret_cast<DevParams*>(h->d_inst); }
+static qmpc_instance_params* inst_rec(qmpc_handle* h) {
+  return reinterpret_cast<qmpc_instance_params*>(h->d_inst + sizeof(DevParams) * (size_t)h->max_batch);
+}
+static int* inst_status(qmpc_handle* h) {
+  return reinterpret_cast<int*>(h->d_inst + (sizeof(DevParams) + sizeof(qmpc_instance_params)) * (size_t)h->max_batch);
+}
+
+// the call-level checks both entry points share (after the null-pointer ones)
+static qmpc_status instances_check(const qmpc_handle* h, int32_t batch) {
+  if (h->params.model != QMPC_MODEL_QUAT || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
+  if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
+  if (batch > 0 && plan_instances(h->sel, batch).family == QMPC_KERNEL_NONE) return QMPC_UNSUPPORTED;
+  return QMPC_OK;
+}
+
+// expansion kernel + solve kernel on stream s; d_rec: the records in device-addressable memory
+static qmpc_status launch_instances(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_rec,
+                                    double* d_forces, qmpc_info* d_info, double* d_tu, double* d_tx, hipStream_t s) {
+  const qmpc_plan p = plan_instances(h->sel, batch);
+  const qmpc_status es = ensure_instance_buffers(h);
+  if (es != QMPC_OK) return es;
+  HIP_TRY(hipEventRecord(h->ev0, s));
+  HIP_TRY(qmpc_wform_inst_launch(p.variant, (int)batch, p.lds, s, &h->dev, sizeof h->dev, d_rec, inst_dev(h), inst_status(h), d_in,
+                                 d_forces, d_info, d_tu, d_tx, p.gws ? h->d_gws : nullptr));
+  h->last_kernel = p.family;
+  HIP_TRY(hipEventRecord(h->ev1, s));
+  h->timed = true;
+  return QMPC_OK;
+}
+
+qmpc_status qmpc_solve_instances_device(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_iparams,
+                                        double* d_forces_body, qmpc_info* d_info, void* stream) {
+  if (!h || batch < 0 || (batch > 0 && (!d_in || !d_iparams || !d_forces_body))) return QMPC_BAD_ARGUMENT;
+  const qmpc_status cs = instances_check(h, batch);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  HIP_TRY(hipSetDevice(h->device));
+  return launch_instances(h, batch, d_in, d_iparams, d_forces_body, d_info, nullptr, nullptr, stream ? (hipStream_t)stream : h->stream);
+}
+
+qmpc_status qmpc_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_input* in, const qmpc_instance_params* iparams,
+                                 double* forces_body, qmpc_info* info, double* traj_u, double* traj_x) {
+  if (!h || batch < 0 || (batch > 0 && (!in || !iparams || !forces_body))) return QMPC_BAD_ARGUMENT;
+  const qmpc_status cs = instances_check(h, batch);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  HIP_TRY(hipSetDevice(h->device));
+  // an earlier qmpc_solve_async was never waited for: complete it first (it owes a pageable caller its copy-out)
+  if (h->pending.forces || h->pending.info || h->stage_in_busy) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    finish_pending(h);
+    h->stage_in_busy = 0;
+  }
+  const int N = h->params.horizon;
+  const qmpc_status es = ensure_instance_buffers(h);
+  if (es != QMPC_OK) return es;
+  if (traj_u && !h->d_traj_u) HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * N * (size_t)h->max_batch));
+  if (traj_x && !h->d_traj_x) HIP_TRY(hipMalloc(&h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch));
+  HIP_TRY(hipMemcpyAsync(h->d_in, in, sizeof(qmpc_input) * (size_t)batch, hipMemcpyDefault, h->stream));
+  HIP_TRY(hipMemcpyAsync(inst_rec(h), iparams, sizeof(qmpc_instance_params) * (size_t)batch, hipMemcpyDefault, h->stream));
+  const qmpc_status st = launch_instances(h, batch, h->d_in, inst_rec(h), h->d_forces, h->d_info, traj_u ? h->d_traj_u : nullptr,
+                                          traj_x ? h->d_traj_x : nullptr, h->stream);
+  if (st != QMPC_OK) return st;
+  HIP_TRY(hipMemcpyAsync(forces_body, h->d_forces, sizeof(double) * 12 * (size_t)batch, hipMemcpyDefault, h->stream));
+  if (info) HIP_TRY(hipMemcpyAsync(info, h->d_info, sizeof(qmpc_info) * (size_t)batch, hipMemcpyDefault, h->stream));
+  if (traj_u) HIP_TRY(hipMemcpyAsync(traj_u, h->d_traj_u, sizeof(double) * 12 * N * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  if (traj_x) HIP_TRY(hipMemcpyAsync(traj_x, h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return QMPC_OK;
+}
+
+qmpc_status qmpc_prepare_instances(qmpc_handle* h) {
+  if (!h) return QMPC_BAD_ARGUMENT;
+  const qmpc_status cs = instances_check(h, 0);
+  if (cs != QMPC_OK) return cs;
+  HIP_TRY(hipSetDevice(h->device));
+  return ensure_instance_buffers(h);
+}
+
 qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value) {
   if (!h || !value) return QMPC_BAD_ARGUMENT;
   switch (what) {
@@ -825,11 +932,16 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_traj_u) b += sizeof(double) * nu * N * (size_t)h->max_batch;
       if (h->d_traj_x) b += sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch;
       if (h->d_A) b += 2 * sizeof(double) * 144 * N * (size_t)h->max_batch;
+      if (h->d_inst) b += instance_bytes(h->max_batch);
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
       return QMPC_OK;
     }
     case QMPC_QUERY_ZERO_COPY: *value = h->zero_copy; return QMPC_OK;
+    case QMPC_QUERY_KERNEL_FOR_INSTANCES:
+      if (arg < 1 || arg > h->max_batch) return QMPC_BAD_ARGUMENT;
+      *value = plan_instances(h->sel, (int)arg).family;
+      return QMPC_OK;
     default: return QMPC_BAD_ARGUMENT;
   }
 }

@@ -8,6 +8,13 @@
 
 #include "../../include/qmpc.h"
 
+// the helpers the expansion kernel of qmpc_solve_instances (qmpc_wform.hip) shares with the host: one source for both
+#if defined(__HIPCC__)
+#define QP_HD __host__ __device__
+#else
+#define QP_HD
+#endif
+
 namespace qmpc {
 
 // Device copy of qmpc_params plus derived constants (host fills it).
@@ -33,6 +40,42 @@ struct DevParams {
   int linesearch_max;
 };
 
+// 1 / mass and the cofactor inverse of the 3x3 inertia (Eigen's fixed-size inverse(), AltroUtils.cpp:391); false: singular.
+// Contraction off: the host (fill_dev_params) and the device (qmpc_expand_instances_kernel) round every product alike.
+QP_HD inline bool derive_inertial(double mass, const double* A, double* inv_mass, double* Iinv) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  *inv_mass = 1.0 / mass;
+  const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
+  const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
+  if (!(__builtin_fabs(det) > 0.0)) return false;
+  const double id = 1.0 / det;
+  Iinv[0] = c00 * id; Iinv[1] = (A[2] * A[7] - A[1] * A[8]) * id; Iinv[2] = (A[1] * A[5] - A[2] * A[4]) * id;
+  Iinv[3] = c01 * id; Iinv[4] = (A[0] * A[8] - A[2] * A[6]) * id; Iinv[5] = (A[2] * A[3] - A[0] * A[5]) * id;
+  Iinv[6] = c02 * id; Iinv[7] = (A[1] * A[6] - A[0] * A[7]) * id; Iinv[8] = (A[0] * A[4] - A[1] * A[3]) * id;
+  return true;
+}
+
+// The handle's DevParams with the seven fields of a per-instance record (qmpc_solve_instances) in place, and the record's
+// verdict: QMPC_OK, or QMPC_BAD_PARAMS for a non-finite field, mass <= 0, a singular inertia, an r_weight <= 0, a negative
+// q_weight or w, mu <= 0 or fz_max <= 0 (*d is written either way).
+QP_HD inline int apply_instance_params(const DevParams& base, const qmpc_instance_params& r, DevParams* d) {
+  *d = base;
+  const double* v = &r.mass;      // the record is 38 doubles
+  bool ok = true;
+  for (int i = 0; i < (int)(sizeof r / sizeof(double)); ++i) ok = ok && __builtin_isfinite(v[i]);
+  d->mass = r.mass;
+  ok = derive_inertial(r.mass, r.inertia, &d->inv_mass, d->Iinv) && ok;
+  ok = ok && r.mass > 0.0 && r.mu > 0.0 && r.fz_max > 0.0 && r.w >= 0.0;
+  for (int j = 0; j < 13; ++j) { d->Q[j] = r.q_weights[j]; ok = ok && r.q_weights[j] >= 0.0; }
+  for (int j = 0; j < 12; ++j) { d->R[j] = r.r_weights[j]; ok = ok && r.r_weights[j] > 0.0; }
+  d->w = r.w;
+  d->mu = r.mu;
+  d->fz_max = r.fz_max;
+  return ok ? QMPC_OK : QMPC_BAD_PARAMS;
+}
+
 // qmpc_params -> DevParams; QMPC_OK or QMPC_BAD_ARGUMENT
 inline int fill_dev_params(const qmpc_params* p, DevParams* d) {
   if (!p || p->horizon < 1 || p->horizon > QMPC_MAX_HORIZON) return QMPC_BAD_ARGUMENT;
@@ -51,16 +94,7 @@ inline int fill_dev_params(const qmpc_params* p, DevParams* d) {
   d->hh = (double)(p->h / 2);  // float division, as `h / 2` in AltroUtils.cpp:16,94
   d->h_ref = p->h_ref;
   d->mass = p->mass;
-  d->inv_mass = 1.0 / p->mass;
-  // cofactor inverse of the 3x3 inertia (Eigen's fixed-size inverse(), AltroUtils.cpp:391)
-  const double* A = p->inertia;
-  const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
-  const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
-  if (!(std::fabs(det) > 0.0)) return QMPC_BAD_ARGUMENT;
-  const double id = 1.0 / det;
-  d->Iinv[0] = c00 * id; d->Iinv[1] = (A[2] * A[7] - A[1] * A[8]) * id; d->Iinv[2] = (A[1] * A[5] - A[2] * A[4]) * id;
-  d->Iinv[3] = c01 * id; d->Iinv[4] = (A[0] * A[8] - A[2] * A[6]) * id; d->Iinv[5] = (A[2] * A[3] - A[0] * A[5]) * id;
-  d->Iinv[6] = c02 * id; d->Iinv[7] = (A[1] * A[6] - A[0] * A[7]) * id; d->Iinv[8] = (A[0] * A[4] - A[1] * A[3]) * id;
+  if (!derive_inertial(p->mass, p->inertia, &d->inv_mass, d->Iinv)) return QMPC_BAD_ARGUMENT;
   std::memcpy(d->Q, p->q_weights, sizeof d->Q);
   std::memcpy(d->R, p->r_weights, sizeof d->R);
   for (int j = 0; j < 12; ++j) if (!(d->R[j] > 0.0)) return QMPC_BAD_ARGUMENT;

@@ -276,4 +276,17 @@ static inline qmpc_plan plan(const qmpc_select& s, int batch, qmpc_call kind, bo
   return wave(body());
 }
 
+// The plan of qmpc_solve_instances* (per-instance parameters, qmpc_wform.hip: qmpc_solve_w_inst_kernel): the wrench-form
+// variant (3 / 5 / 6, with its LDS and workspace) that a plain solve of `batch` instances takes on the wave kernels -- also
+// where a plain solve would go to the lane kernel, which has no per-instance form.  NONE: not QuatMpc's problem in the
+// converged mode, or no wrench-form kernel for this batch under the handle's knobs (QMPC_WFORM=0, QMPC_WFORM=3 beyond the
+// all-LDS sizes, ...).
+static inline qmpc_plan plan_instances(const qmpc_select& s, int batch) {
+  if (s.model != QMPC_MODEL_QUAT || s.mode != QMPC_MODE_CONVERGED || !s.wform) return qmpc_plan();
+  qmpc_select w = s;
+  w.lane_slot = false;      // no lane kernel to go to: plan() keeps the wave kernels' own rule at every batch size
+  const qmpc_plan p = plan(w, batch, QMPC_CALL_PLAIN, true, false);
+  return (p.family == QMPC_KERNEL_WFORM_LDS || p.family == QMPC_KERNEL_WFORM_WS) ? p : qmpc_plan();
+}
+
 }  // namespace qmpc

@@ -60,6 +60,51 @@ __global__ __launch_bounds__(64, (WVAR == 5 || WVAR == 6) ? 2 : 1) void qmpc_sol
 #include "qmpc_wform_body.inc"
 }
 
+// ---- the same solve with per-instance robot and cost parameters (qmpc_solve_instances*) -----------------------------------
+// The handle's parameters with each instance's mass, inertia, friction, force bound and cost weights in place, built on the
+// device by qmpc_expand_instances_kernel: Pi[b] for instance b, pstatus[b] its record's verdict.  The body reads every
+// physical quantity through P, so binding P to the instance's block is the whole difference from qmpc_solve_w_kernel; the
+// block address depends on blockIdx.x only, and the reads stay scalar loads (s_load), as those of the by-value kernel
+// argument do.
+template <int WVAR>
+__global__ __launch_bounds__(64, (WVAR == 5 || WVAR == 6) ? 2 : 1) void qmpc_solve_w_inst_kernel(
+    const DevParams* __restrict__ Pi, const qmpc_input* __restrict__ in_, double* __restrict__ forces, qmpc_info* __restrict__ info,
+    double* __restrict__ traj_u, double* __restrict__ traj_x, int batch, double* __restrict__ gws, const int* __restrict__ pstatus) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int b = blockIdx.x;
+  if (b >= batch) return;
+  const int wslot = b;
+  const int lane = threadIdx.x;
+  constexpr bool PROF = false;
+  long long* prof_out = nullptr;
+  constexpr int warm_t = 0;
+  constexpr const double* resume = nullptr;
+  if (pstatus[b] != QMPC_OK) {      // a rejected record: zero forces and trajectory rows, no iteration
+    const int N = Pi[b].N;
+    if (lane < 12) forces[12 * (size_t)b + lane] = 0.0;
+    if (lane == 0 && info) {
+      qmpc_info r = {QMPC_BAD_PARAMS, 0, 0.0, 0.0, 0.0, 0.0};
+      info[b] = r;
+    }
+    if (traj_u) for (int i = lane; i < N * 12; i += kWave) traj_u[(size_t)b * N * 12 + i] = 0.0;
+    if (traj_x) for (int i = lane; i < (N + 1) * 13; i += kWave) traj_x[(size_t)b * (N + 1) * 13 + i] = 0.0;
+    return;
+  }
+  const DevParams& P = Pi[b];
+#include "qmpc_wform_body.inc"
+}
+
+// One thread per instance: the handle's DevParams `base` with record rec[i]'s fields in place -> out[i], the verdict ->
+// status[i] (qmpc_params_dev.h: apply_instance_params, the arithmetic of the host's fill_dev_params)
+__global__ __launch_bounds__(256) void qmpc_expand_instances_kernel(DevParams base, const qmpc_instance_params* __restrict__ rec,
+                                                                    DevParams* __restrict__ out, int* __restrict__ status, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  DevParams d;
+  status[i] = apply_instance_params(base, rec[i], &d);
+  out[i] = d;
+}
+
 // ---- the same solve for EIGHT contact points (QuatModelT<8>: the synthetic biped of BASELINE config 5; round 5) ----------
 // The wrench space is 6-dimensional whatever the number of contact points: the backward pass, the closed-loop rollout and
 // the gains are those of the four-point kernel; the per-point phases (pre-pass, input recovery + directions, apply) walk
@@ -199,7 +244,7 @@ using namespace qmpc_wform_tu;
 // called from qmpc_hip.hip (declared there); hidden: not part of the C ABI
 __attribute__((visibility("hidden"))) size_t qmpc_wform_slice_doubles(int N, int nl) { return nl == 8 ? wform_slice<8>(N, true) : wform_slice<4>(N, true); }
 __attribute__((visibility("hidden"))) hipError_t qmpc_wform_set_lds(int bytes) {
-  const void* k[21] = {reinterpret_cast<const void*>(qmpc_ref8_w_kernel<3, 1>), reinterpret_cast<const void*>(qmpc_ref8_w_kernel<5, 1>),
+  const void* k[24] = {reinterpret_cast<const void*>(qmpc_ref8_w_kernel<3, 1>), reinterpret_cast<const void*>(qmpc_ref8_w_kernel<5, 1>),
                       reinterpret_cast<const void*>(qmpc_solve_w_kernel<false, 3>), reinterpret_cast<const void*>(qmpc_solve_w_kernel<true, 3>),
                       reinterpret_cast<const void*>(qmpc_solve_w_kernel<false, 5>), reinterpret_cast<const void*>(qmpc_solve_w_kernel<true, 5>),
                       reinterpret_cast<const void*>(qmpc_solve_w_list_kernel<3>), reinterpret_cast<const void*>(qmpc_solve_w_list_kernel<5>),
@@ -210,8 +255,10 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_wform_set_lds(int bytes) {
                       reinterpret_cast<const void*>(qmpc_solve_w_kernel<false, 6>), reinterpret_cast<const void*>(qmpc_solve_cw_kernel<6>),
                       reinterpret_cast<const void*>(qmpc_solve8_w_kernel<6>),
                       reinterpret_cast<const void*>(qmpc_ref_cw_kernel<3, 1>), reinterpret_cast<const void*>(qmpc_ref_cw_kernel<5, 1>),
-                      reinterpret_cast<const void*>(qmpc_ref_cw_kernel<5, 2>)};
-  for (int i = 0; i < 21; ++i) {
+                      reinterpret_cast<const void*>(qmpc_ref_cw_kernel<5, 2>),
+                      reinterpret_cast<const void*>(qmpc_solve_w_inst_kernel<3>), reinterpret_cast<const void*>(qmpc_solve_w_inst_kernel<5>),
+                      reinterpret_cast<const void*>(qmpc_solve_w_inst_kernel<6>)};
+  for (int i = 0; i < 24; ++i) {
     const hipError_t e = hipFuncSetAttribute(k[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) return e;
   }
@@ -245,6 +292,27 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch(int model, in
     if (prof) QMPC_LAUNCH_W((qmpc_solve_w_kernel<true, 3>), prof_out, gws); else QMPC_LAUNCH_W((qmpc_solve_w_kernel<false, 3>), prof_out, gws);
   }
 #undef QMPC_LAUNCH_W
+  return hipGetLastError();
+}
+// per-instance parameters (qmpc_solve_instances*): expand the records rec[0 .. batch) against the handle's parameters into
+// dev_out / status_out (device buffers of `batch` entries), then solve with variant var (3 / 5 / 6) reading them
+__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_params,
+                                                                        size_t dev_params_size, const qmpc_instance_params* rec, void* dev_out,
+                                                                        int* status_out, const qmpc_input* in, double* forces, qmpc_info* info,
+                                                                        double* traj_u, double* traj_x, double* gws) {
+  if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
+  DevParams P;
+  std::memcpy(&P, dev_params, sizeof P);
+  DevParams* Pi = static_cast<DevParams*>(dev_out);
+  hipLaunchKernelGGL(qmpc_expand_instances_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, P, rec, Pi, status_out, batch);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+#define QMPC_LAUNCH_WI(kern) \
+  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, Pi, in, forces, info, traj_u, traj_x, batch, gws, status_out)
+  if (var == 6) QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<6>);
+  else if (var == 5) QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<5>);
+  else QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<3>);
+#undef QMPC_LAUNCH_WI
   return hipGetLastError();
 }
 // the instances sel[0 .. *sel_count) (device memory), `grid` workgroups walking the list

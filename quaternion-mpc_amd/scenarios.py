@@ -234,3 +234,28 @@ def random_biped8_states(batch: int, config_id: int = 5, first: int = 0, tilt_ma
     qd /= np.linalg.norm(qd, axis=-1, keepdims=True)
     rec["quat_d"] = qd
     return rec
+
+
+def random_go1_variants(batch: int, seed: int = 0, first: int = 0, base=None) -> np.ndarray:
+    """`batch` per-instance records (``struct qmpc_instance_params``, for Solver.solve_instances) of Go1 variants around
+    `base` (default: the Go1 values of qmpc_default_params), instance indices first .. first+batch-1, same counter-based
+    generator as the states: mass U(10, 16) kg; inertia scaled by the mass ratio times U(0.8, 1.2) per axis (D I D with
+    D = diag(sqrt(scale)), so it stays symmetric positive definite); mu U(0.3, 0.9); fz_max U(80, 200) N; Q and R each
+    scaled by one U(0.5, 2) factor; w unchanged."""
+    from . import default_params, instance_params
+
+    base = default_params(10) if base is None else base
+    rec = instance_params(base, batch)
+    idx = np.arange(first, first + batch, dtype=np.uint64)
+    u = _uniform(0x5EED1000 + int(seed), idx, 8)
+    mass = 10.0 + 6.0 * u[:, 0]
+    scale = (mass / base.mass)[:, None] * (0.8 + 0.4 * u[:, 1:4])
+    d = np.sqrt(scale)
+    inertia = np.asarray(base.inertia[:], dtype=np.float64).reshape(3, 3)
+    rec["mass"] = mass
+    rec["inertia"] = (d[:, :, None] * inertia[None] * d[:, None, :]).reshape(batch, 9)
+    rec["mu"] = 0.3 + 0.6 * u[:, 4]
+    rec["fz_max"] = 80.0 + 120.0 * u[:, 5]
+    rec["q_weights"] *= (0.5 + 1.5 * u[:, 6])[:, None]
+    rec["r_weights"] *= (0.5 + 1.5 * u[:, 7])[:, None]
+    return rec
