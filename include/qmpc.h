@@ -297,8 +297,12 @@ enum qmpc_query_what {
                                            capped lane launch (0: no hand-off) */
   QMPC_QUERY_DEVICE_BYTES         = 6,  /* device memory the handle holds right now */
   QMPC_QUERY_ZERO_COPY            = 7,  /* 1: host-buffer calls of wave-kernel batches run zero-copy */
-  QMPC_QUERY_KERNEL_FOR_INSTANCES = 8   /* arg = batch: the qmpc_kernel_family qmpc_solve_instances* launches for that size
+  QMPC_QUERY_KERNEL_FOR_INSTANCES = 8,  /* arg = batch: the qmpc_kernel_family qmpc_solve_instances* launches for that size
                                            (QMPC_KERNEL_NONE: the handle refuses the call) */
+  QMPC_QUERY_LOOP_INSTANCES_PLAN  = 9   /* arg = batch (bits 0-31) | 1 << 32 with controller records | 1 << 33 with
+                                           lp->warm_start: the launch qmpc_loop_run_instances* takes, 16 * form + family --
+                                           form 1 the persistent kernel, 2 the per-tick sequence; family the
+                                           qmpc_kernel_family of its solve.  0: the call is refused */
 };
 enum qmpc_kernel_family {
   QMPC_KERNEL_NONE         = 0,
@@ -329,7 +333,8 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
  * bit-identical to qmpc_solve on a handle carrying the same values.  There is NO lane-per-instance form: batches at and
  * above the lane kernel's switch-over (14336 at N <= 12) stay on the wave workspace form (3.6 M solves/s at N=10 where
  * the lane kernel does 7-9 M), and agree with the plain solve there to ~1e-10 N (another rounding family).  Not covered either: the
- * reference mode, ConvexMpc, the 8-point model, warm starts, the closed loop.
+ * reference mode, ConvexMpc, the 8-point model, warm starts.  The closed loop has its own entry points with these records:
+ * qmpc_loop_run_instances* below.
  *
  * The handle's per-instance buffers (the records and one expanded parameter block per instance, about 760 B x max_batch)
  * are allocated on first use, or now by qmpc_prepare_instances (e.g. before a stream capture). */
@@ -569,6 +574,60 @@ qmpc_status qmpc_loop_joint_commands(qmpc_handle* h, const qmpc_leg_geometry* g,
 qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* lp, const qmpc_leg_geometry* g,
                                        int32_t batch, qmpc_loop_state* d_states, double* d_joint_pos, int32_t ticks,
                                        qmpc_joint_command* d_cmd, qmpc_joint_command* d_trace_cmd, void* stream);
+
+/* ---- closed loop with per-robot controller and plant (QuatMpc handle, converged mode) --------------------------------
+ * One launch sequence runs `batch` robots, each with its own controller tuning and its own TRUE robot: the question of a
+ * Monte-Carlo robustness sweep (does the robot stay up and track its command when the real robot differs from the one
+ * its controller assumes?) and of fleets of differently loaded robots.  Everything else is the closed loop of
+ * qmpc_loop_run_device: the same tick, the persistent kernel or the captured per-tick graph, the same traces.
+ *
+ *   ctrl[i]   robot i's controller: the handle's qmpc_params with the seven fields of ctrl[i] in place, exactly as in
+ *             qmpc_solve_instances.  NULL: the handle's parameters for every robot.
+ *   plant[i]  robot i's plant integrates with plant[i].mass and .inertia and adds the constant disturbance wrench
+ *             (ext_force_world at the CoM in the world frame, ext_torque_body in the body frame).  NULL: each robot's
+ *             plant is its controller's robot -- ctrl[i]'s mass and inertia, or the handle's where ctrl is NULL -- with no
+ *             disturbance.  A disturbance component that is exactly zero adds no arithmetic: a record with zero
+ *             disturbance integrates to the bits of the plain loop's plant with the same mass and inertia.
+ *   both NULL exactly qmpc_loop_run_device.
+ *
+ * Invalid records: a controller record by the rule of qmpc_solve_instances; a plant record with a non-finite field,
+ * mass <= 0 or a singular inertia.  The robot of an invalid record is FROZEN: its state record is left untouched except
+ * status = QMPC_BAD_PARAMS and iterations = 0 (tick does not advance), its trace rows are zero.  Every other robot is
+ * unaffected, bit for bit.
+ *
+ * Call level: QMPC_BAD_ARGUMENT for null pointers and for an 8-point handle (as qmpc_loop_run); QMPC_UNSUPPORTED, when
+ * ctrl or plant is non-NULL, for a ConvexMpc or reference-mode handle; with ctrl non-NULL also for lp->warm_start != 0
+ * and for a handle whose knobs leave no wrench-form kernel (QMPC_WFORM=0); QMPC_BATCH_TOO_LARGE above max_batch.  With
+ * plant only, everything the plain loop supports works, the warm start included, and the per-tick form keeps the plain
+ * loop's solve (lane kernel and hand-off included).  The joint-level loop is not covered: run
+ * qmpc_loop_joint_commands_device on the states afterwards.
+ *
+ * Launch (qmpc_query QMPC_QUERY_LOOP_INSTANCES_PLAN): the persistent kernel up to the plain loop's threshold (2048
+ * robots, 4096 warm) on the wrench-form variant the plain loop takes; beyond, the per-tick sequence, whose solve is the
+ * per-instance wrench-form kernel (qmpc_solve_instances*) with ctrl, the plain loop's solve without.  The records are
+ * expanded once per call.  Buffers: those of qmpc_prepare_instances (764 B x max_batch) and per-robot plant blocks
+ * (264 B x max_batch), allocated on first use; a call with ticks = 0 allocates both and launches nothing (e.g. before
+ * the caller's own stream capture).  The per-tick form captures its tick after every allocation. */
+typedef struct qmpc_plant_params {   /* 16 doubles, 128 B: the TRUE robot the plant integrates */
+  double mass;
+  double inertia[9];                 /* row-major, same convention as qmpc_params.inertia */
+  double ext_force_world[3];         /* constant disturbance at the CoM, world frame [N] */
+  double ext_torque_body[3];         /* constant disturbance torque, body frame [N m] */
+} qmpc_plant_params;
+/* mass and inertia of *p, zero disturbance */
+void    qmpc_plant_params_from(const qmpc_params* p, qmpc_plant_params* out);
+int32_t qmpc_sizeof_plant_params(void);
+/* Host buffers: states [batch] in/out, ctrl / plant [batch] (either may be NULL), trace_forces [ticks][batch][12] and
+ * trace_contacts [ticks][batch][4] may be NULL.  Synchronous. */
+qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                    int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant,
+                                    double* trace_forces, double* trace_contacts);
+/* Device buffers, stream-ordered (NULL stream = the handle's). */
+qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch,
+                                           qmpc_loop_state* d_states, int32_t ticks,
+                                           const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                           double* d_trace_forces, double* d_trace_contacts, void* stream);
+
 /* Stand-pose joint angles (0, 0.67, -1.3 per leg: the reference's Gazebo start pose) for `batch`
  * robots, host buffer [batch][12]. */
 void qmpc_loop_joint_init(double* joint_pos, int32_t batch);

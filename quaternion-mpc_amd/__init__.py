@@ -211,6 +211,27 @@ def params_with(params: "Params", rec) -> "Params":
     return out
 
 
+# struct qmpc_plant_params (qmpc_loop_run_instances*): one robot's TRUE plant, 16 doubles = 128 B
+PLANT_PARAMS_DTYPE = np.dtype(
+    [
+        ("mass", "<f8"),
+        ("inertia", "<f8", (9,)),
+        ("ext_force_world", "<f8", (3,)),
+        ("ext_torque_body", "<f8", (3,)),
+    ],
+    align=False,
+)
+assert PLANT_PARAMS_DTYPE.itemsize == 16 * 8
+
+
+def plant_params(params: "Params", batch: int = 1) -> np.ndarray:
+    """[batch] plant records all carrying the mass and inertia of `params`, no disturbance (edit per robot afterwards)."""
+    out = np.zeros(int(batch), dtype=PLANT_PARAMS_DTYPE)
+    out["mass"] = params.mass
+    out["inertia"] = np.asarray(params.inertia[:], dtype=np.float64)
+    return out
+
+
 # struct qmpc_info: 2 x int32 + 4 doubles = 40 B
 INFO_DTYPE = np.dtype(
     [
@@ -290,6 +311,12 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_solve_instances_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.qmpc_solve_instances_device.restype = i32
     lib.qmpc_prepare_instances.argtypes = [vp]
+    lib.qmpc_plant_params_from.argtypes = [C.POINTER(Params), vp]
+    lib.qmpc_plant_params_from.restype = None
+    lib.qmpc_loop_run_instances.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp]
+    lib.qmpc_loop_run_instances.restype = i32
+    lib.qmpc_loop_run_instances_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, vp]
+    lib.qmpc_loop_run_instances_device.restype = i32
     lib.qmpc_prepare_instances.restype = i32
     lib.qmpc_gather.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.qmpc_gather.restype = i32
@@ -360,7 +387,7 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp]
     lib.qmpc_loop_run_device.restype = i32
     for name in ("qmpc_sizeof_input", "qmpc_sizeof_params", "qmpc_sizeof_info", "qmpc_sizeof_convex_input",
-                 "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params"):
+                 "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params", "qmpc_sizeof_plant_params"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = i32
     if lib.qmpc_sizeof_input() != INPUT_DTYPE.itemsize:
@@ -377,6 +404,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         raise RuntimeError("qmpc_loop_state ABI size mismatch")
     if lib.qmpc_sizeof_instance_params() != INSTANCE_PARAMS_DTYPE.itemsize:
         raise RuntimeError("qmpc_instance_params ABI size mismatch")
+    if lib.qmpc_sizeof_plant_params() != PLANT_PARAMS_DTYPE.itemsize:
+        raise RuntimeError("qmpc_plant_params ABI size mismatch")
     return lib
 
 
@@ -439,11 +468,15 @@ EXPORTED_SYMBOLS = (
     "qmpc_solve_instances",
     "qmpc_solve_instances_device",
     "qmpc_prepare_instances",
+    "qmpc_plant_params_from",
+    "qmpc_sizeof_plant_params",
+    "qmpc_loop_run_instances",
+    "qmpc_loop_run_instances_device",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
 QUERY_HANDOFF_ACTIVE, QUERY_HANDOFF_ALLOC_FAILED, QUERY_KERNEL_FOR_BATCH, QUERY_LAST_KERNEL, QUERY_LANE_CAP, \
-    QUERY_DEVICE_BYTES, QUERY_ZERO_COPY, QUERY_KERNEL_FOR_INSTANCES = 1, 2, 3, 4, 5, 6, 7, 8
+    QUERY_DEVICE_BYTES, QUERY_ZERO_COPY, QUERY_KERNEL_FOR_INSTANCES, QUERY_LOOP_INSTANCES_PLAN = 1, 2, 3, 4, 5, 6, 7, 8, 9
 KERNEL_FAMILY = {0: "none", 1: "wform_lds", 2: "wform_ws", 3: "dense_lds", 4: "dense_ws", 5: "lane", 6: "lane_handoff"}
 
 
@@ -677,6 +710,47 @@ class Solver:
         if st != OK:
             raise QmpcError(st, "qmpc_solve_instances_device")
 
+    def loop_run_instances(self, states: np.ndarray, ticks: int, lp: LoopParams | None = None, ctrl: np.ndarray | None = None,
+                           plant: np.ndarray | None = None, trace: bool = False):
+        """qmpc_loop_run_instances: `ticks` ticks of the closed loop, robot i with controller ctrl[i] (INSTANCE_PARAMS_DTYPE; None:
+        the handle's) and TRUE plant plant[i] (PLANT_PARAMS_DTYPE; None: the controller's robot, no disturbance).  Returns the
+        final states (and, with trace, forces [ticks][B][12] and contacts [ticks][B][4]), as loop_run."""
+        lp = lp or default_loop_params(self.lib)
+        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
+        B = st.shape[0]
+        if ctrl is not None:
+            ctrl = np.ascontiguousarray(ctrl, dtype=INSTANCE_PARAMS_DTYPE)
+            if ctrl.shape != (B,):
+                raise ValueError(f"ctrl: shape {ctrl.shape}, expected ({B},)")
+        if plant is not None:
+            plant = np.ascontiguousarray(plant, dtype=PLANT_PARAMS_DTYPE)
+            if plant.shape != (B,):
+                raise ValueError(f"plant: shape {plant.shape}, expected ({B},)")
+        tf = np.zeros((ticks, B, 12)) if trace else None
+        tc = np.zeros((ticks, B, 4)) if trace else None
+        rc = self.lib.qmpc_loop_run_instances(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_instances")
+        return (st, tf, tc) if trace else st
+
+    def loop_run_instances_device(self, batch: int, d_states: int, ticks: int, lp: LoopParams | None = None, d_ctrl: int = 0,
+                                  d_plant: int = 0, d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_instances_device: device pointers (ints; 0 = NULL), stream-ordered."""
+        lp = lp or default_loop_params(self.lib)
+        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        rc = self.lib.qmpc_loop_run_instances_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
+                                                     p(d_trace_forces), p(d_trace_contacts), p(stream))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_instances_device")
+
+    def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
+        """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
+        as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN)."""
+        v = self.query(QUERY_LOOP_INSTANCES_PLAN, int(batch) | (int(bool(ctrl)) << 32) | (int(bool(warm)) << 33))
+        if v == 0:
+            return None
+        return ({1: "persistent", 2: "per_tick"}[v // 16], KERNEL_FAMILY[v % 16])
+
     def kernel_for_instances(self, batch: int) -> str:
         return KERNEL_FAMILY[self.query(QUERY_KERNEL_FOR_INSTANCES, batch)]
 
@@ -891,5 +965,5 @@ class Solver:
 
 
 from .scenarios import (go1_stand_input, quat_to_rot, random_go1_trot_states,  # noqa: E402,F401
-                        random_go1_convex_states, random_biped8_states, random_go1_variants)
+                        random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_plants)
 from .sharding import StepPipeline, gather_forces, shard_range, solve_sharded  # noqa: E402,F401

@@ -51,6 +51,23 @@ hipError_t qmpc_wform_launch_list(int var, int grid, size_t lds, hipStream_t s, 
 hipError_t qmpc_wform_inst_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_params, size_t dev_params_size,
                                   const qmpc_instance_params* rec, void* dev_out, int* status_out, const qmpc_input* in, double* forces,
                                   qmpc_info* info, double* traj_u, double* traj_x, double* gws);
+hipError_t qmpc_wform_inst_expand_launch(int batch, hipStream_t s, const void* dev_params, size_t dev_params_size,
+                                         const qmpc_instance_params* rec, void* dev_out, int* status_out);
+hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
+                                        const qmpc_input* in, double* forces, qmpc_info* info, double* gws);
+
+// qmpc_loop_inst.hip (fifth translation unit): the closed loop with per-robot controller and plant records
+hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, const qmpc_plant_params* plant,
+                                        const qmpc_instance_params* ctrl, const int* ctrl_status, void* bcast_out, void* plants_out,
+                                        int batch);
+hipError_t qmpc_loop_inst_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,
+                                       const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, double* forces,
+                                       qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws);
+hipError_t qmpc_loop_inst_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, int* row,
+                                       const void* plants, int batch);
+hipError_t qmpc_loop_inst_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, const double* forces,
+                                      const qmpc_info* info, double* trace_f, double* trace_c, const int* row, const void* plants,
+                                      int batch);
 
 // qmpc_lane.hip (third translation unit): the lane-per-instance kernel of large batches
 size_t qmpc_lane_ws_bytes(int N, int nl, unsigned slots, int wide);
@@ -107,6 +124,8 @@ struct qmpc_handle {
                                // not refilled before the stream has drained (qmpc_solve_async with a pageable `in`, pinned outputs)
   unsigned char* d_inst;       // per-instance parameters (qmpc_solve_instances*), on first use: [max_batch] DevParams | [max_batch]
                                // qmpc_instance_params (staging of the host-buffer call) | [max_batch] int verdicts
+  unsigned char* d_plant;      // per-robot plants of qmpc_loop_run_instances*, on first use: [max_batch] PlantDev | [max_batch]
+                               // qmpc_plant_params (staging of the host-buffer call)
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -358,6 +377,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_A) (void)hipFree(h->d_A);
   if (h->d_B) (void)hipFree(h->d_B);
   if (h->d_inst) (void)hipFree(h->d_inst);
+  if (h->d_plant) (void)hipFree(h->d_plant);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -831,6 +851,19 @@ static qmpc_status ensure_instance_buffers(qmpc_handle* h) {
   return QMPC_OK;
 }
 static DevParams* inst_dev(qmpc_handle* h) { return reinterpret_cast<DevParams*>(h->d_inst); }
+// ... and the per-robot plants of the closed loop (qmpc_loop_run_instances*), on its first use (a call with ticks = 0 allocates
+// them and launches nothing)
+static_assert(sizeof(qmpc_plant_params) == 16 * sizeof(double), "qmpc_plant_params is 16 doubles");
+static_assert(sizeof(PlantDev) == 136, "PlantDev: 16 doubles and the verdict");
+static size_t plant_bytes(int max_batch) { return (sizeof(PlantDev) + sizeof(qmpc_plant_params)) * (size_t)max_batch; }
+static qmpc_status ensure_plant_buffers(qmpc_handle* h) {
+  if (!h->d_plant) HIP_TRY(hipMalloc(&h->d_plant, plant_bytes(h->max_batch)));
+  return QMPC_OK;
+}
+static PlantDev* plant_dev(qmpc_handle* h) { return reinterpret_cast<PlantDev*>(h->d_plant); }
+static qmpc_plant_params* plant_rec(qmpc_handle* h) {
+  return reinterpret_cast<qmpc_plant_params*>(h->d_plant + sizeof(PlantDev) * (size_t)h->max_batch);
+}
 static qmpc_instance_params* inst_rec(qmpc_handle* h) {
   return reinterpret_cast<qmpc_instance_params*>(h->d_inst + sizeof(DevParams) * (size_t)h->max_batch);
 }
@@ -933,6 +966,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_traj_x) b += sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch;
       if (h->d_A) b += 2 * sizeof(double) * 144 * N * (size_t)h->max_batch;
       if (h->d_inst) b += instance_bytes(h->max_batch);
+      if (h->d_plant) b += plant_bytes(h->max_batch);
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
       return QMPC_OK;
@@ -942,6 +976,13 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (arg < 1 || arg > h->max_batch) return QMPC_BAD_ARGUMENT;
       *value = plan_instances(h->sel, (int)arg).family;
       return QMPC_OK;
+    case QMPC_QUERY_LOOP_INSTANCES_PLAN: {
+      const int64_t b = arg & 0xffffffffLL;
+      if (b < 1 || b > h->max_batch) return QMPC_BAD_ARGUMENT;
+      const qmpc_plan p = plan_loop_instances(h->sel, (int)b, (arg >> 32) & 1, (arg >> 33) & 1, h->handoff_failed);
+      *value = p.family == QMPC_KERNEL_NONE ? 0 : 16 * (p.fused ? 1 : 2) + p.family;
+      return QMPC_OK;
+    }
     default: return QMPC_BAD_ARGUMENT;
   }
 }
@@ -1232,6 +1273,75 @@ void qmpc_loop_state_init(qmpc_loop_state* s, const qmpc_loop_params* lp, const 
   }
 }
 
+// The solve of one tick of the closed loop in the per-tick form (h->d_in -> h->d_forces, h->d_info); first: the cold first
+// tick of a warm-started call
+static qmpc_status loop_tick_solve(qmpc_handle* h, int32_t batch, hipStream_t s, bool warm, bool first, bool convex) {
+  if (warm) {
+    const qmpc_plan p = plan(h->sel, batch, first ? QMPC_CALL_WARM_LOOP_FIRST : QMPC_CALL_WARM_LOOP_TICK, true, h->handoff_failed);
+    // the lane kernel hands the stragglers of the warm-started ticks over (not of the cold first one): the records carry the
+    // rows' initial residuals
+    if (p.variant == 4) {
+      const qmpc_status st = launch_lane(h, p, batch, h->d_in, h->d_forces, h->d_info, s, first ? nullptr : h->d_traj_u, h->d_traj_u,
+                                         /*check_prev=*/1, nullptr, false);
+      if (st != QMPC_OK) return st;
+    } else {
+      HIP_TRY(qmpc_warm_launch(p.variant, convex ? 1 : 0, (int)batch, p.lds, s, &h->dev, sizeof h->dev, h->d_in, first ? nullptr : h->d_traj_u,
+                               h->d_forces, h->d_info, h->d_traj_u, p.gws ? h->d_gws : nullptr, /*check_prev=*/1));
+    }
+    return QMPC_OK;
+  }
+  return launch_solve(h, batch, h->d_in, h->d_forces, h->d_info, nullptr, nullptr, s, QMPC_CALL_LOOP_TICK);
+}
+
+// The per-tick form of the closed loop: `one_tick(first)` enqueues one tick (three kernels, four with the joint level); it is
+// captured once into a graph and replayed (the sequence is launch-bound for small batches); plain launches when capture is not
+// available on this stream.  tick_plan: the plan of the solve of the tick the loop repeats.
+extern "C++" {      // (a template, inside the extern "C" block of the entry points)
+template <class Tick>
+static qmpc_status replay_ticks(qmpc_handle* h, const qmpc_plan& tick_plan, hipStream_t s, int32_t ticks, bool warm, Tick&& one_tick) {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  bool captured = false;
+  int t_start = 0;
+  // Large batches solve with the lane-per-instance kernel in every tick: its workspace (and, where the ticks hand over, the
+  // hand-off records) is allocated and its parameter block uploaded HERE, once, on the stream -- neither belongs inside the
+  // capture below (an allocation is not capturable, and the parameters do not change between the ticks of a call).
+  if (tick_plan.variant == 4) {
+    const qmpc_status es = ensure_lane_buffers(h);
+    if (es != QMPC_OK) return es;
+    HIP_TRY(qmpc_lane_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
+    if (tick_plan.iter_cap) (void)ensure_handoff_buffers(h);
+  }
+  if (warm) {                            // the cold first tick is not the tick the graph repeats
+    const qmpc_status st = one_tick(true);
+    if (st != QMPC_OK) return st;
+    t_start = 1;
+  }
+  if (ticks - t_start > 1 && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+    const qmpc_status st = one_tick(false);
+    const hipError_t ee = hipStreamEndCapture(s, &graph);
+    if (st == QMPC_OK && ee == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess)
+      captured = true;
+    else
+      (void)hipGetLastError();
+  }
+  qmpc_status rs = QMPC_OK;
+  for (int t = t_start; t < ticks && rs == QMPC_OK; ++t) {
+    if (captured) {
+      if (hipGraphLaunch(exec, s) != hipSuccess) rs = QMPC_HIP_ERROR;
+    } else {
+      rs = one_tick(!warm);
+    }
+  }
+  if (exec) {
+    (void)hipStreamSynchronize(s);        // the executable graph must outlive its launches
+    (void)hipGraphExecDestroy(exec);
+  }
+  if (graph) (void)hipGraphDestroy(graph);
+  return rs;
+}
+}  // extern "C++"
+
 // g != NULL: the joint-level kernel closes every tick (d_joint_pos in/out, d_cmd = the last tick's commands, d_trace_cmd
 // one row per tick; either of the two may be NULL)
 static qmpc_status loop_run_impl(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
@@ -1268,22 +1378,8 @@ static qmpc_status loop_run_impl(qmpc_handle* h, const qmpc_loop_params* lp, int
     else
       hipLaunchKernelGGL(qmpc_loop_front_kernel, dim3(blocks), dim3(64), 0, s, LP, d_states, h->d_in, h->d_loop_row, (int)batch);
     HIP_TRY(hipGetLastError());
-    if (warm) {
-      const qmpc_plan p = plan(h->sel, batch, first ? QMPC_CALL_WARM_LOOP_FIRST : QMPC_CALL_WARM_LOOP_TICK, true, h->handoff_failed);
-      // the lane kernel hands the stragglers of the warm-started ticks over (not of the cold first one): the records carry the
-      // rows' initial residuals
-      if (p.variant == 4) {
-        const qmpc_status st = launch_lane(h, p, batch, h->d_in, h->d_forces, h->d_info, s, first ? nullptr : h->d_traj_u, h->d_traj_u,
-                                           /*check_prev=*/1, nullptr, false);
-        if (st != QMPC_OK) return st;
-      } else {
-        HIP_TRY(qmpc_warm_launch(p.variant, convex ? 1 : 0, (int)batch, p.lds, s, &h->dev, sizeof h->dev, h->d_in, first ? nullptr : h->d_traj_u,
-                                 h->d_forces, h->d_info, h->d_traj_u, p.gws ? h->d_gws : nullptr, /*check_prev=*/1));
-      }
-    } else {
-      const qmpc_status st = launch_solve(h, batch, h->d_in, h->d_forces, h->d_info, nullptr, nullptr, s, QMPC_CALL_LOOP_TICK);
-      if (st != QMPC_OK) return st;
-    }
+    const qmpc_status st = loop_tick_solve(h, batch, s, warm, first, convex);
+    if (st != QMPC_OK) return st;
     if (convex)
       hipLaunchKernelGGL(qmpc_loop_post_kernel<true>, dim3(blocks), dim3(64), 0, s, h->dev, LP, d_states, (const double*)h->d_forces,
                          (const qmpc_info*)h->d_info, d_trace_forces, d_trace_contacts, (const int*)h->d_loop_row, (int)batch);
@@ -1307,48 +1403,7 @@ static qmpc_status loop_run_impl(qmpc_handle* h, const qmpc_loop_params* lp, int
                               lp_plan.gws ? h->d_gws : nullptr, g, d_joint_pos, d_cmd, d_trace_cmd));
     return QMPC_OK;
   }
-  // one tick = three kernels (four with the joint level): captured once into a graph and replayed (the sequence is launch-bound for small
-  // batches); plain launches when capture is not available on this stream
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  bool captured = false;
-  int t_start = 0;
-  // Large batches solve with the lane-per-instance kernel in every tick: its workspace (and, where the ticks hand over, the
-  // hand-off records) is allocated and its parameter block uploaded HERE, once, on the stream -- neither belongs inside the
-  // capture below (an allocation is not capturable, and the parameters do not change between the ticks of a call).
-  if (lp_plan.variant == 4) {
-    const qmpc_status es = ensure_lane_buffers(h);
-    if (es != QMPC_OK) return es;
-    HIP_TRY(qmpc_lane_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
-    if (lp_plan.iter_cap) (void)ensure_handoff_buffers(h);
-  }
-  if (warm) {                            // the cold first tick is not the tick the graph repeats
-    const qmpc_status st = one_tick(true);
-    if (st != QMPC_OK) return st;
-    t_start = 1;
-  }
-  if (ticks - t_start > 1 && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-    const qmpc_status st = one_tick(false);
-    const hipError_t ee = hipStreamEndCapture(s, &graph);
-    if (st == QMPC_OK && ee == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess)
-      captured = true;
-    else
-      (void)hipGetLastError();
-  }
-  qmpc_status rs = QMPC_OK;
-  for (int t = t_start; t < ticks && rs == QMPC_OK; ++t) {
-    if (captured) {
-      if (hipGraphLaunch(exec, s) != hipSuccess) rs = QMPC_HIP_ERROR;
-    } else {
-      rs = one_tick(!warm);
-    }
-  }
-  if (exec) {
-    (void)hipStreamSynchronize(s);        // the executable graph must outlive its launches
-    (void)hipGraphExecDestroy(exec);
-  }
-  if (graph) (void)hipGraphDestroy(graph);
-  return rs;
+  return replay_ticks(h, lp_plan, s, ticks, warm, one_tick);
 }
 
 qmpc_status qmpc_loop_run_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
@@ -1396,6 +1451,114 @@ qmpc_status qmpc_loop_run(qmpc_handle* h, const qmpc_loop_params* lp, int32_t ba
     if (hipStreamSynchronize(h->stream) != hipSuccess) rs = QMPC_HIP_ERROR;
   } while (0);
   return rs;
+}
+
+// ---- the closed loop with per-robot controller and plant records (qmpc_loop_inst.hip) -------------------------------------
+static_assert(sizeof(qmpc_plant_params) == 128, "qmpc_plant_params is 128 B");
+int32_t qmpc_sizeof_plant_params(void) { return (int32_t)sizeof(qmpc_plant_params); }
+
+void qmpc_plant_params_from(const qmpc_params* p, qmpc_plant_params* out) {
+  if (!p || !out) return;
+  std::memset(out, 0, sizeof *out);
+  out->mass = p->mass;
+  std::memcpy(out->inertia, p->inertia, sizeof out->inertia);
+}
+
+// the call-level checks of both entry points, for a call with at least one kind of record (QMPC_OK: go on)
+static qmpc_status loop_instances_check(const qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, bool has_ctrl) {
+  if (h->params.model != QMPC_MODEL_QUAT && h->params.model != QMPC_MODEL_CONVEX) return QMPC_BAD_ARGUMENT;
+  if (h->params.model != QMPC_MODEL_QUAT || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
+  if (has_ctrl && (lp->warm_start != 0.0 || !h->sel.wform)) return QMPC_UNSUPPORTED;
+  if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
+  if (batch > 0 && plan_loop_instances(h->sel, batch, has_ctrl, lp->warm_start != 0.0, h->handoff_failed).family == QMPC_KERNEL_NONE)
+    return QMPC_UNSUPPORTED;
+  return QMPC_OK;
+}
+
+qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                           int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                           double* d_trace_forces, double* d_trace_contacts, void* stream) {
+  if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !d_states)) return QMPC_BAD_ARGUMENT;
+  if (!d_ctrl && !d_plant)
+    return loop_run_impl(h, lp, batch, d_states, ticks, d_trace_forces, d_trace_contacts, nullptr, nullptr, nullptr, nullptr, stream);
+  const qmpc_status cs = loop_instances_check(h, lp, batch, d_ctrl != nullptr);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  const bool warm = lp->warm_start != 0.0;
+  const qmpc_plan lpp = plan_loop_instances(h->sel, batch, d_ctrl != nullptr, warm, h->handoff_failed);
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  qmpc_status es = ensure_instance_buffers(h);
+  if (es == QMPC_OK) es = ensure_plant_buffers(h);
+  if (es != QMPC_OK || ticks == 0) return es;      // ticks = 0: the buffers only (e.g. before the caller's stream capture)
+  if (!h->d_loop_row) HIP_TRY(hipMalloc(&h->d_loop_row, sizeof(int)));
+  HIP_TRY(hipMemsetAsync(h->d_loop_row, 0xFF, sizeof(int), s));     // row counter = -1 (per-tick form)
+  const qmpc_loop_params LP = *lp;
+  // the records are expanded once per call: the controllers' blocks (or, for the persistent kernel without controller records,
+  // the handle's block per robot) and the plant blocks with each robot's verdict
+  if (d_ctrl) HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_ctrl, inst_dev(h), inst_status(h)));
+  HIP_TRY(qmpc_loop_inst_expand_launch(s, &h->dev, sizeof h->dev, d_plant, d_ctrl, d_ctrl ? inst_status(h) : nullptr,
+                                       (!d_ctrl && lpp.fused) ? inst_dev(h) : nullptr, plant_dev(h), (int)batch));
+  if (lpp.fused) {
+    HIP_TRY(qmpc_loop_inst_fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, d_states, h->d_in, h->d_forces,
+                                        h->d_info, d_trace_forces, d_trace_contacts, (int)ticks, lpp.gws ? h->d_gws : nullptr));
+    return QMPC_OK;
+  }
+  if (warm && !h->d_traj_u)
+    HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * (size_t)h->params.horizon * (size_t)h->max_batch));
+  auto one_tick = [&](bool first) -> qmpc_status {
+    HIP_TRY(qmpc_loop_inst_front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch));
+    if (d_ctrl) {      // the per-instance wrench-form kernel on the blocks expanded above
+      HIP_TRY(qmpc_wform_inst_solve_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces,
+                                           h->d_info, lpp.gws ? h->d_gws : nullptr));
+      h->last_kernel = lpp.family;
+    } else {           // the plain loop's solve
+      const qmpc_status st = loop_tick_solve(h, batch, s, warm, first, false);
+      if (st != QMPC_OK) return st;
+    }
+    HIP_TRY(qmpc_loop_inst_post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts,
+                                       h->d_loop_row, plant_dev(h), (int)batch));
+    return QMPC_OK;
+  };
+  return replay_ticks(h, lpp, s, ticks, warm, one_tick);
+}
+
+qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                    const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                    double* trace_contacts) {
+  if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !states)) return QMPC_BAD_ARGUMENT;
+  if (!ctrl && !plant) return qmpc_loop_run(h, lp, batch, states, ticks, trace_forces, trace_contacts);
+  const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  HIP_TRY(hipSetDevice(h->device));
+  qmpc_status es = ensure_instance_buffers(h);
+  if (es == QMPC_OK) es = ensure_plant_buffers(h);
+  if (es != QMPC_OK || ticks == 0) return es;
+  // staging that belongs to the handle and only grows: [states | force trace | contact trace] (as qmpc_loop_run); the records go
+  // to the staging halves of the per-instance and plant buffers
+  const size_t B = (size_t)batch, T = (size_t)ticks;
+  const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
+               n_tc = trace_contacts ? 4 * B * T : 0;
+  if (h->loop_cap < n_st + n_tf + n_tc) {
+    if (h->d_loop) (void)hipFree(h->d_loop);
+    h->d_loop = nullptr;
+    h->loop_cap = 0;
+    HIP_TRY(hipMalloc(&h->d_loop, sizeof(double) * (n_st + n_tf + n_tc)));
+    h->loop_cap = n_st + n_tf + n_tc;
+  }
+  qmpc_loop_state* d_st = reinterpret_cast<qmpc_loop_state*>(h->d_loop);
+  double* d_tf = trace_forces ? h->d_loop + n_st : nullptr;
+  double* d_tc = trace_contacts ? h->d_loop + n_st + n_tf : nullptr;
+  HIP_TRY(hipMemcpyAsync(d_st, states, sizeof(qmpc_loop_state) * B, hipMemcpyHostToDevice, h->stream));
+  if (ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
+  if (plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
+  const qmpc_status rs = qmpc_loop_run_instances_device(h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
+                                                        d_tf, d_tc, nullptr);
+  if (rs != QMPC_OK) return rs;
+  HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
+  if (d_tf) HIP_TRY(hipMemcpyAsync(trace_forces, d_tf, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream));
+  if (d_tc) HIP_TRY(hipMemcpyAsync(trace_contacts, d_tc, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return QMPC_OK;
 }
 
 // Diagnostic: per-instance phase cycle counts (s_memtime) of one solve launch.

@@ -394,6 +394,41 @@ QMPC_LOOP_FN void loop_post_one(const DevParams& P, const qmpc_loop_params& LP, 
         for (int a = 0; a < 3; ++a) s.foot_pos_world[3 * l + a] = s.leg[l].fsm_pos[a];
   s.tick += 1.0;
 }
+// The back end with the robot's own TRUE plant (qmpc_loop_run_instances*: QuatMpc's body-frame forces, converged mode):
+// loop_post_one with pl's mass, inverse inertia and disturbance wrench in the plant step; bit-identical to loop_post_one where
+// pl carries the handle's mass and inertia and no disturbance.  Instantiated in qmpc_loop_inst.hip only (both launch forms there).
+template <int OCC = 1>
+QMPC_LOOP_FN void loop_post_plant_one(const PlantDev& pl, const qmpc_loop_params& LP, qmpc_loop_state& s,
+                                      const double* __restrict__ forces, const qmpc_info& inf, double* __restrict__ trace_f,
+                                      double* __restrict__ trace_c) {
+#pragma clang fp contract(off)
+  const int status = inf.status;
+  s.status = (double)status;
+  s.iterations = (double)inf.iterations;
+  const bool accepted = status == QMPC_OK || status == QMPC_MAX_ITER;     // (the converged mode only)
+  double R[9];
+  qmpc_loop::quat_to_rot(s.quat, R);
+  if (accepted)
+    for (int a = 0; a < 12; ++a) s.forces_body[a] = forces[a];
+  for (int l = 0; l < 4; ++l)
+    for (int r = 0; r < 3; ++r)
+      s.grf_world[3 * l + r] = R[3 * r] * s.forces_body[3 * l] + R[3 * r + 1] * s.forces_body[3 * l + 1] +
+                               R[3 * r + 2] * s.forces_body[3 * l + 2];
+  if (trace_f) for (int a = 0; a < 12; ++a) trace_f[a] = s.forces_body[a];
+  if (trace_c) for (int a = 0; a < 4; ++a) trace_c[a] = s.contacts[a];
+  double x[13];
+  for (int a = 0; a < 3; ++a) { x[a] = s.pos_world[a]; x[7 + a] = s.lin_vel_world[a]; x[10 + a] = s.ang_vel_body[a]; }
+  for (int a = 0; a < 4; ++a) x[3 + a] = s.quat[a];
+  qmpc_loop::plant_step_ext(x, s.forces_body, s.foot_pos_world, 4, pl.mass, pl.Iinv, pl.force, pl.torque, LP.dt);
+  for (int a = 0; a < 3; ++a) { s.pos_world[a] = x[a]; s.lin_vel_world[a] = x[7 + a]; s.ang_vel_body[a] = x[10 + a]; }
+  for (int a = 0; a < 4; ++a) s.quat[a] = x[3 + a];
+  if (s.movement_mode != 0.0)
+    for (int l = 0; l < 4; ++l)
+      if (s.contacts[l] == 0.0)
+        for (int a = 0; a < 3; ++a) s.foot_pos_world[3 * l + a] = s.leg[l].fsm_pos[a];
+  s.tick += 1.0;
+}
+
 #ifndef QMPC_FUSED_TU
 template <bool WORLD>
 __global__ __launch_bounds__(64) void qmpc_loop_post_kernel(DevParams P, qmpc_loop_params LP, qmpc_loop_state* __restrict__ st,

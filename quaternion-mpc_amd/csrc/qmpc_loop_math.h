@@ -102,6 +102,57 @@ QMPC_HD void plant_step(double* x, const double* u, const double* feet_world, in
   for (int i = 3; i < 7; ++i) x[i] = x[i] / n;
 }
 
+// The same plant under a constant disturbance wrench as well (the closed loop with per-robot plants,
+// qmpc_loop_run_instances*): f_ext in the world frame at the CoM, tau_ext in the body frame,
+//   v' = (R(q) sum(u) + f_ext)/m + g,  w' = Iinv (sum(r_l x u_l) + tau_ext).
+// A component that is exactly zero adds nothing -- not even `+ 0.0`, which would turn a -0.0 into +0.0 -- so a zero
+// disturbance gives the bits of plant_step.  plant_rate / plant_step are left as they are (their callers' code is
+// unchanged); this is their text with the two additions.
+QMPC_HD void plant_rate_ext(const double* x, const double* u, const double* feet_world, int nleg, double mass,
+                            const double* Iinv, const double* f_ext, const double* tau_ext, double* xd) {
+  QMPC_NO_CONTRACT
+  double R[9];
+  quat_to_rot(&x[3], R);
+  double F[3] = {0.0, 0.0, 0.0}, tau[3] = {0.0, 0.0, 0.0};
+  for (int l = 0; l < nleg; ++l) {
+    const double d[3] = {feet_world[3 * l] - x[0], feet_world[3 * l + 1] - x[1], feet_world[3 * l + 2] - x[2]};
+    const double r[3] = {R[0] * d[0] + R[3] * d[1] + R[6] * d[2], R[1] * d[0] + R[4] * d[1] + R[7] * d[2],
+                         R[2] * d[0] + R[5] * d[1] + R[8] * d[2]};
+    const double* f = &u[3 * l];
+    F[0] += f[0]; F[1] += f[1]; F[2] += f[2];
+    tau[0] += r[1] * f[2] - r[2] * f[1];
+    tau[1] += r[2] * f[0] - r[0] * f[2];
+    tau[2] += r[0] * f[1] - r[1] * f[0];
+  }
+  for (int a = 0; a < 3; ++a)
+    if (tau_ext[a] != 0.0) tau[a] += tau_ext[a];
+  xd[0] = x[7]; xd[1] = x[8]; xd[2] = x[9];
+  const double s = x[3], qx = x[4], qy = x[5], qz = x[6], wx = x[10], wy = x[11], wz = x[12];
+  xd[3] = 0.5 * (-qx * wx - qy * wy - qz * wz);
+  xd[4] = 0.5 * (s * wx - qz * wy + qy * wz);
+  xd[5] = 0.5 * (qz * wx + s * wy - qx * wz);
+  xd[6] = 0.5 * (-qy * wx + qx * wy + s * wz);
+  for (int a = 0; a < 3; ++a) {
+    double fw = R[3 * a] * F[0] + R[3 * a + 1] * F[1] + R[3 * a + 2] * F[2];
+    if (f_ext[a] != 0.0) fw += f_ext[a];
+    xd[7 + a] = fw / mass;
+    xd[10 + a] = Iinv[3 * a] * tau[0] + Iinv[3 * a + 1] * tau[1] + Iinv[3 * a + 2] * tau[2];
+  }
+  xd[9] += -9.81;
+}
+
+QMPC_HD void plant_step_ext(double* x, const double* u, const double* feet_world, int nleg, double mass,
+                            const double* Iinv, const double* f_ext, const double* tau_ext, double dt) {
+  QMPC_NO_CONTRACT
+  double k1[13], xm[13], k2[13];
+  plant_rate_ext(x, u, feet_world, nleg, mass, Iinv, f_ext, tau_ext, k1);
+  for (int i = 0; i < 13; ++i) xm[i] = x[i] + 0.5 * dt * k1[i];
+  plant_rate_ext(xm, u, feet_world, nleg, mass, Iinv, f_ext, tau_ext, k2);
+  for (int i = 0; i < 13; ++i) x[i] = x[i] + dt * k2[i];
+  const double n = sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] + x[6] * x[6]);
+  for (int i = 3; i < 7; ++i) x[i] = x[i] / n;
+}
+
 // Condition matrix of the swing-foot quintic p(t) = sum_k a_k t^k (QuinticCurve::get_foot_swing_target,
 // Utils.cpp:236-293): rows p(0), p(T), p'(0), p'(T), p(T/2), p'(T/2).  Generated, with the reference's FLOAT
 // evaluation order so that every entry carries the same rounding as upstream's hand-written expressions: a power is

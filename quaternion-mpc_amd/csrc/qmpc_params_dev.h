@@ -76,6 +76,34 @@ QP_HD inline int apply_instance_params(const DevParams& base, const qmpc_instanc
   return ok ? QMPC_OK : QMPC_BAD_PARAMS;
 }
 
+// One robot's TRUE plant in the closed loop with per-robot records (qmpc_loop_run_instances*), as the kernels read it: the mass,
+// the inverse inertia (derive_inertial: bit-identical to DevParams::Iinv for the same inertia), the constant disturbance
+// wrench and the robot's verdict (QMPC_OK, or QMPC_BAD_PARAMS: the robot is frozen).  136 B.
+struct PlantDev {
+  double mass;
+  double Iinv[9];
+  double force[3];     // world frame, at the CoM [N]
+  double torque[3];    // body frame [N m]
+  int status;
+  int pad_;
+};
+
+// A plant record -> PlantDev (*d is written either way) and its verdict: QMPC_OK, or QMPC_BAD_PARAMS for a non-finite
+// field, mass <= 0 or a singular inertia.
+QP_HD inline int apply_plant_params(const qmpc_plant_params& r, PlantDev* d) {
+  const double* v = &r.mass;      // the record is 16 doubles
+  bool ok = true;
+  for (int i = 0; i < (int)(sizeof r / sizeof(double)); ++i) ok = ok && __builtin_isfinite(v[i]);
+  double inv_mass;
+  d->mass = r.mass;
+  ok = derive_inertial(r.mass, r.inertia, &inv_mass, d->Iinv) && ok;
+  ok = ok && r.mass > 0.0;
+  for (int a = 0; a < 3; ++a) { d->force[a] = r.ext_force_world[a]; d->torque[a] = r.ext_torque_body[a]; }
+  d->status = ok ? QMPC_OK : QMPC_BAD_PARAMS;
+  d->pad_ = 0;
+  return d->status;
+}
+
 // qmpc_params -> DevParams; QMPC_OK or QMPC_BAD_ARGUMENT
 inline int fill_dev_params(const qmpc_params* p, DevParams* d) {
   if (!p || p->horizon < 1 || p->horizon > QMPC_MAX_HORIZON) return QMPC_BAD_ARGUMENT;

@@ -289,4 +289,23 @@ static inline qmpc_plan plan_instances(const qmpc_select& s, int batch) {
   return (p.family == QMPC_KERNEL_WFORM_LDS || p.family == QMPC_KERNEL_WFORM_WS) ? p : qmpc_plan();
 }
 
+// The plan of qmpc_loop_run_instances* (the closed loop with per-robot controller and / or plant records; qmpc_loop_inst.hip).
+// `has_ctrl`: controller records are given (their solve is the per-instance wrench-form kernel), `warm`: lp->warm_start.
+//   persistent  where the plain loop of this batch takes its persistent kernel (2048 robots, 4096 warm, or QMPC_LOOP_FUSED)
+//               on a wrench-form variant: that very variant (qmpc_loop_fused_inst_kernel<3|5|6>), fused = true;
+//   per tick    otherwise: with controller records the plan of qmpc_solve_instances* (plan_instances), without them the
+//               plain loop's tick (lane kernel and hand-off included); fused = false.
+// NONE: not QuatMpc's problem in the converged mode, controller records with the warm start (the per-tick form has no
+// warm-started per-instance kernel) or with no wrench-form kernel for the batch (QMPC_WFORM=0, ...).
+static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, bool has_ctrl, bool warm, bool handoff_failed = false) {
+  if (s.model != QMPC_MODEL_QUAT || s.mode != QMPC_MODE_CONVERGED) return qmpc_plan();
+  if (has_ctrl && (warm || !s.wform)) return qmpc_plan();
+  const qmpc_plan f = plan(s, batch, warm ? QMPC_CALL_WARM_LOOP : QMPC_CALL_LOOP, true, handoff_failed);
+  if (f.fused && (f.variant == 3 || f.variant == 5 || f.variant == 6)) return f;
+  qmpc_plan p = has_ctrl ? plan_instances(s, batch)
+                         : plan(s, batch, warm ? QMPC_CALL_WARM_LOOP_TICK : QMPC_CALL_LOOP_TICK, true, handoff_failed);
+  p.fused = false;
+  return p;
+}
+
 }  // namespace qmpc

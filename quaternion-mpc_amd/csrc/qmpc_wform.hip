@@ -315,6 +315,29 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_launch(int var,
 #undef QMPC_LAUNCH_WI
   return hipGetLastError();
 }
+// the two halves of qmpc_wform_inst_launch, for the closed loop with per-robot records (qmpc_loop_run_instances*): the
+// expansion once per call, the solve every tick (dev_blocks / status: the expanded blocks and verdicts)
+__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_expand_launch(int batch, hipStream_t s, const void* dev_params, size_t dev_params_size,
+                                                                               const qmpc_instance_params* rec, void* dev_out, int* status_out) {
+  if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
+  DevParams P;
+  std::memcpy(&P, dev_params, sizeof P);
+  hipLaunchKernelGGL(qmpc_expand_instances_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, P, rec,
+                     static_cast<DevParams*>(dev_out), status_out, batch);
+  return hipGetLastError();
+}
+__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks,
+                                                                              const int* status, const qmpc_input* in, double* forces,
+                                                                              qmpc_info* info, double* gws) {
+  const DevParams* Pi = static_cast<const DevParams*>(dev_blocks);
+#define QMPC_LAUNCH_WI(kern) \
+  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, Pi, in, forces, info, (double*)nullptr, (double*)nullptr, batch, gws, status)
+  if (var == 6) QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<6>);
+  else if (var == 5) QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<5>);
+  else QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<3>);
+#undef QMPC_LAUNCH_WI
+  return hipGetLastError();
+}
 // the instances sel[0 .. *sel_count) (device memory), `grid` workgroups walking the list
 __attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch_list(int var, int grid, size_t lds, hipStream_t s, const void* dev_params,
                                                                         size_t dev_params_size, const qmpc_input* in, double* forces,

@@ -11,6 +11,7 @@
 #pragma once
 
 #include "../csrc/qmpc_loop_math.h"
+#include "../csrc/qmpc_params_dev.h"      // derive_inertial: the plant blocks' inverse inertia
 #include <type_traits>
 
 #include "ConvexMpcHip.h"
@@ -40,8 +41,12 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
  public:
   using ClosedLoopHostBase<State>::state;
   static constexpr bool kConvex = std::is_same<Mpc, ConvexMpcHipT<State>>::value;
+  // ctrl / plant (optional, QuatMpc only): robot i of qmpc_loop_run_instances* -- the controller record applied to the
+  // handle's parameters before it is created, the plant record's mass, inertia and disturbance wrench in the plant step
+  // (null: the plant is the controller's robot, no disturbance)
   ClosedLoopHostT(const QmpcApi& api, const qmpc_loop_params& lp, const qmpc_loop_state& init, int horizon, int device,
-                  int mode = QMPC_MODE_CONVERGED, int drop_ang_vel = 1)
+                  int mode = QMPC_MODE_CONVERGED, int drop_ang_vel = 1, const qmpc_instance_params* ctrl = nullptr,
+                  const qmpc_plant_params* plant = nullptr)
       : lp_(lp) {
     if (kConvex) {                     // gazebo_go1_convex_mpc.yaml: 5 ms, the Euler-angle state's weights, mu 0.6, fz_max 200
       state.param.mpc_update_period = 5.0;
@@ -66,9 +71,15 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     for (int a = 0; a < 3; ++a) state.ctrl.torso_lin_vel_d_rel[a] = init.lin_vel_d_rel[a];
     refresh_feedback();
     state.estimator_init = true;
-    make_mpc(api, device, mode, drop_ang_vel);            // QuatMpc takes torso_pos_d_world from the feedback (QuatMpc.cpp:13-20)
+    make_mpc(api, device, mode, drop_ang_vel, ctrl);      // QuatMpc takes torso_pos_d_world from the feedback (QuatMpc.cpp:13-20)
     if (kConvex) { state.joy.body_x = init.pos_d_world[0]; state.joy.body_y = init.pos_d_world[1]; }
     qmpc_loop::inv3(mpc->params().inertia, Iinv_);          // the plant of the device loop uses the handle's mass / inertia
+    if (plant) {                                             // ... or, per robot, its own (qmpc_loop_run_instances*)
+      plant_ = *plant;
+      has_plant_ = true;
+      double inv_mass;
+      qmpc::derive_inertial(plant_.mass, plant_.inertia, &inv_mass, Iinv_);   // the device's plant blocks: bit-identical
+    }
   }
   ~ClosedLoopHostT() override { delete mpc; }
   qmpc_status device_status() const override { return mpc->last_status(); }
@@ -116,7 +127,10 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     const bool ok = mpc->grf_update(state);
     double u[12];
     for (int a = 0; a < 12; ++a) u[a] = state.ctrl.optimized_input[a];
-    qmpc_loop::plant_step(x_, u, feet_, NUM_LEG, mpc->params().mass, Iinv_, lp_.dt);
+    if (has_plant_)
+      qmpc_loop::plant_step_ext(x_, u, feet_, NUM_LEG, plant_.mass, Iinv_, plant_.ext_force_world, plant_.ext_torque_body, lp_.dt);
+    else
+      qmpc_loop::plant_step(x_, u, feet_, NUM_LEG, mpc->params().mass, Iinv_, lp_.dt);
     if (state.ctrl.movement_mode != 0)
       for (int l = 0; l < NUM_LEG; ++l)
         if (!state.ctrl.plan_contacts[l])
@@ -220,13 +234,14 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
 
  private:
   template <class M = Mpc>
-  typename std::enable_if<std::is_same<M, ConvexMpcHipT<State>>::value>::type make_mpc(const QmpcApi& api, int device, int mode, int) {
+  typename std::enable_if<std::is_same<M, ConvexMpcHipT<State>>::value>::type make_mpc(const QmpcApi& api, int device, int mode, int,
+                                                                                      const qmpc_instance_params*) {
     mpc = new Mpc(state, api, device, mode);
   }
   template <class M = Mpc>
   typename std::enable_if<!std::is_same<M, ConvexMpcHipT<State>>::value>::type make_mpc(const QmpcApi& api, int device, int mode,
-                                                                                       int drop_ang_vel) {
-    mpc = new Mpc(state, api, device, mode, drop_ang_vel);
+                                                                                       int drop_ang_vel, const qmpc_instance_params* ctrl) {
+    mpc = new Mpc(state, api, device, mode, drop_ang_vel, ctrl);
   }
   template <class M = Mpc>
   typename std::enable_if<std::is_same<M, ConvexMpcHipT<State>>::value>::type warm(bool) {}
@@ -243,6 +258,8 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   double x_[13];
   double feet_[12];
   double Iinv_[9];
+  qmpc_plant_params plant_{};
+  bool has_plant_ = false;
   long ticks_ = 0;
 };
 

@@ -61,7 +61,10 @@ class QuatMpcHipT : public LeggedMpcHipT<State> {
   // `;` ends the comma initialiser one line early, QuatMpc.cpp:242-245), so the MPC plans from zero angular velocity at
   // every tick.  On the robot the legs damp the body; on an ideal rigid-body plant that leaves the attitude loop without
   // a rate term (robots lose balance after 6-9 s).  0 feeds the measured angular velocity, as evidently meant.
-  QuatMpcHipT(State& state, const QmpcApi& api, int device = 0, int mode = QMPC_MODE_CONVERGED, int drop_ang_vel = 1)
+  // ctrl (optional): a per-robot controller record (qmpc_instance_params) whose seven fields replace the robot and cost
+  // parameters below before the handle is created -- the controller robot i of qmpc_loop_run_instances* runs
+  QuatMpcHipT(State& state, const QmpcApi& api, int device = 0, int mode = QMPC_MODE_CONVERGED, int drop_ang_vel = 1,
+              const qmpc_instance_params* ctrl = nullptr)
       : api_(api), mode_(mode) {   // QuatMpc.cpp:8-55
     for (int i = 0; i < 3; ++i) {
       torso_lin_vel_d_body_filter[i] = MovingWindowFilterHip(100);
@@ -89,6 +92,15 @@ class QuatMpcHipT : public LeggedMpcHipT<State> {
     params_.mu = state.param.mu;
     params_.fz_max = state.param.fz_max;
     params_.drop_ang_vel = drop_ang_vel;
+    if (ctrl) {
+      params_.mass = ctrl->mass;
+      for (int i = 0; i < 9; ++i) params_.inertia[i] = ctrl->inertia[i];
+      params_.mu = ctrl->mu;
+      params_.fz_max = ctrl->fz_max;
+      for (int i = 0; i < 13; ++i) params_.q_weights[i] = ctrl->q_weights[i];
+      for (int i = 0; i < 12; ++i) params_.r_weights[i] = ctrl->r_weights[i];
+      params_.w = ctrl->w;
+    }
     last_status_ = api_.create ? api_.create(&params_, 1, device, &handle_) : QMPC_NO_DEVICE;
   }
   ~QuatMpcHipT() override {

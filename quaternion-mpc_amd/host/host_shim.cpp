@@ -184,6 +184,15 @@ void* qh_loop_create_opts(const char* lib_path, int horizon, int mode, int drop_
   h->loop = new legged::ClosedLoopHostT<LeggedStateLite>(api, *lp, *init, horizon, 0, mode, drop_ang_vel);
   return h;
 }
+// robot i of qmpc_loop_run_instances*: its controller record (or NULL) and its plant record (or NULL)
+void* qh_loop_create_robot(const char* lib_path, int horizon, const qmpc_loop_params* lp, const qmpc_loop_state* init,
+                           const qmpc_instance_params* ctrl, const qmpc_plant_params* plant) {
+  LoopHarness* h = new LoopHarness();
+  legged::QmpcApi api;
+  if (!(lib_path && lib_path[0]) || !bind_api(&h->base, lib_path, api)) { delete h; return nullptr; }
+  h->loop = new legged::ClosedLoopHostT<LeggedStateLite>(api, *lp, *init, horizon, 0, QMPC_MODE_CONVERGED, 1, ctrl, plant);
+  return h;
+}
 // the sibling controller in the same loop: ConvexMpcHipT (gazebo_go1_convex_mpc.yaml values)
 void* qh_loop_create_convex_mode(const char* lib_path, int horizon, int mode, const qmpc_loop_params* lp, const qmpc_loop_state* init) {
   LoopHarness* h = new LoopHarness();

@@ -259,3 +259,29 @@ def random_go1_variants(batch: int, seed: int = 0, first: int = 0, base=None) ->
     rec["q_weights"] *= (0.5 + 1.5 * u[:, 6])[:, None]
     rec["r_weights"] *= (0.5 + 1.5 * u[:, 7])[:, None]
     return rec
+
+
+def random_go1_plants(batch: int, seed: int = 0, first: int = 0, base=None, payload=(0.0, 4.0), inertia_scale=(0.8, 1.2),
+                      force=(0.0, 0.0)) -> np.ndarray:
+    """`batch` TRUE-plant records (``struct qmpc_plant_params``, for Solver.loop_run_instances) of Go1 robots around `base`
+    (default: qmpc_default_params' Go1), robot indices first .. first+batch-1, the counter-based generator of
+    random_go1_variants: a payload U(payload) kg on top of the base mass, the inertia scaled by the mass ratio times
+    U(inertia_scale) per axis (D I D, D = diag(sqrt(scale)): symmetric positive definite), and a constant horizontal
+    disturbance force of magnitude U(force) N at the CoM in a uniformly random direction (no disturbance torque)."""
+    from . import default_params, plant_params
+
+    base = default_params(10) if base is None else base
+    rec = plant_params(base, batch)
+    idx = np.arange(first, first + batch, dtype=np.uint64)
+    u = _uniform(0x5EED2000 + int(seed), idx, 6)
+    mass = base.mass + payload[0] + (payload[1] - payload[0]) * u[:, 0]
+    scale = (mass / base.mass)[:, None] * (inertia_scale[0] + (inertia_scale[1] - inertia_scale[0]) * u[:, 1:4])
+    d = np.sqrt(scale)
+    inertia = np.asarray(base.inertia[:], dtype=np.float64).reshape(3, 3)
+    rec["mass"] = mass
+    rec["inertia"] = (d[:, :, None] * inertia[None] * d[:, None, :]).reshape(batch, 9)
+    mag = force[0] + (force[1] - force[0]) * u[:, 4]
+    ang = 2.0 * np.pi * u[:, 5]
+    rec["ext_force_world"][:, 0] = mag * np.cos(ang)
+    rec["ext_force_world"][:, 1] = mag * np.sin(ang)
+    return rec
