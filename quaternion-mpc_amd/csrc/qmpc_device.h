@@ -22,7 +22,21 @@
 namespace qmpc {
 
 constexpr int kWave = 64;
-constexpr int LD = 16;          // leading dimension of every LDS matrix: [12][16]
+
+// qmpc_create raises the dynamic LDS limit of every kernel of the launch tables (qmpc_kernel_slots.h) to the CU's 160 KB: the
+// attribute belongs to the kernel, not to a handle, so handles with different horizons coexist
+template <class... Tables>
+hipError_t set_max_lds(const Tables&... tables) {
+  hipError_t e = hipSuccess;
+  auto one = [&e](const auto& table) {
+    for (auto k : table)
+      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  };
+  (one(tables), ...);
+  return e;
+}
+
+constexpr int LD = 16;         // leading dimension of every LDS matrix: [12][16]
 constexpr int MAT = 12 * LD;    // 192 doubles = 3 MFMA fragments of 64 lanes
 
 typedef double d4 __attribute__((ext_vector_type(4)));

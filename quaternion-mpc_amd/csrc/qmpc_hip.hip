@@ -21,42 +21,54 @@
 #include <mutex>
 #include <new>
 
+#include "qmpc_kernel_slots.h"
 #include "qmpc_plan_fill.h"
 
 using namespace qmpc;
 
-// qmpc_loop_fused.hip (second translation unit): the closed loop's persistent kernel
-hipError_t qmpc_fused_set_lds(int var, int bytes);
+// the launch tables of this unit (slots: qmpc_kernel_slots.h): the round-1 solve kernels (the profiling ones included), the
+// reference mode's and the linearisation
+static decltype(&qmpc_solve_kernel<QuatModel, false, 0>) const kDenseSolve[] = {
+    qmpc_solve_kernel<QuatModel, false, 0>,   qmpc_solve_kernel<QuatModel, false, 1>,   qmpc_solve_kernel<QuatModel, false, 2>,
+    qmpc_solve_kernel<ConvexModel, false, 0>, qmpc_solve_kernel<ConvexModel, false, 1>, qmpc_solve_kernel<ConvexModel, false, 2>,
+    qmpc_solve_kernel<Quat8Model, false, 1>,  qmpc_solve_kernel<Quat8Model, false, 2>,
+    qmpc_solve_kernel<QuatModel, true, 0>,    qmpc_solve_kernel<QuatModel, true, 1>};
+static decltype(&qmpc_ref_kernel<QuatModel, 0>) const kDenseRef[] = {qmpc_ref_kernel<QuatModel, 0>, qmpc_ref_kernel<QuatModel, 1>,
+                                                                      qmpc_ref_kernel<ConvexModel, 0>, qmpc_ref_kernel<ConvexModel, 1>,
+                                                                      qmpc_ref_kernel<Quat8Model, 1>};
+static decltype(&qmpc_linearize_kernel<QuatModel>) const kLinearize[] = {qmpc_linearize_kernel<QuatModel>, qmpc_linearize_kernel<ConvexModel>};
+static_assert(sizeof kDenseSolve / sizeof kDenseSolve[0] == kDenseSolveSlots && sizeof kDenseRef / sizeof kDenseRef[0] == kDenseRefSlots &&
+                  sizeof kLinearize / sizeof kLinearize[0] == kLinearizeSlots,
+              "qmpc_kernel_slots.h");
+
+// qmpc_loop_fused.hip (second translation unit): the closed loop's persistent kernel and the warm-started solve
+hipError_t qmpc_loop_fused_set_lds();
 hipError_t qmpc_fused_launch(int var, int reference_mode, int convex, int batch, size_t lds, hipStream_t s, const void* dev_params, size_t dev_params_size,
                              const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, double* forces,
                              qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws,
                              const qmpc_leg_geometry* geom, double* joint_pos, qmpc_joint_command* cmd,
                              qmpc_joint_command* trace_cmd);
-hipError_t qmpc_warm_set_lds(int bytes);
 hipError_t qmpc_warm_launch(int var, int convex, int batch, size_t lds, hipStream_t s, const void* dev_params, size_t dev_params_size,
                             const qmpc_input* in, const double* u_init, double* forces, qmpc_info* info, double* traj_u,
                             double* gws, int check_prev);
 
 // qmpc_wform.hip (fourth translation unit): the wave-per-instance kernel with the wrench-form elimination (small batches)
 size_t qmpc_wform_slice_doubles(int N, int nl);
-hipError_t qmpc_wform_set_lds(int bytes);
-hipError_t qmpc_wform_launch(int model, int var, int prof, int batch, size_t lds, hipStream_t s, const void* dev_params, size_t dev_params_size,
-                             const qmpc_input* in, double* forces, qmpc_info* info, double* traj_u, double* traj_x,
-                             long long* prof_out, double* gws);
-hipError_t qmpc_wform_ref_launch(int model, int var, int batch, size_t lds, hipStream_t s, const void* dev_params, size_t dev_params_size,
-                                 const qmpc_input* in, double* forces, qmpc_info* info, double* traj_u, double* traj_x, double* gws);
+hipError_t qmpc_wform_set_lds();
+hipError_t qmpc_wform_launch(int model, int ref, int var, int prof, int batch, size_t lds, hipStream_t s, const void* dev_params,
+                             size_t dev_params_size, const qmpc_input* in, double* forces, qmpc_info* info, double* traj_u,
+                             double* traj_x, long long* prof_out, double* gws);
 hipError_t qmpc_wform_launch_list(int var, int grid, size_t lds, hipStream_t s, const void* dev_params, size_t dev_params_size,
                                   const qmpc_input* in, double* forces, qmpc_info* info, double* traj_u, double* traj_x,
                                   const int* sel, const int* sel_count, double* gws, const double* hstate, int hcap);
-hipError_t qmpc_wform_inst_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_params, size_t dev_params_size,
-                                  const qmpc_instance_params* rec, void* dev_out, int* status_out, const qmpc_input* in, double* forces,
-                                  qmpc_info* info, double* traj_u, double* traj_x, double* gws);
 hipError_t qmpc_wform_inst_expand_launch(int batch, hipStream_t s, const void* dev_params, size_t dev_params_size,
                                          const qmpc_instance_params* rec, void* dev_out, int* status_out);
 hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
-                                        const qmpc_input* in, double* forces, qmpc_info* info, double* gws);
+                                        const qmpc_input* in, double* forces, qmpc_info* info, double* traj_u, double* traj_x,
+                                        double* gws);
 
 // qmpc_loop_inst.hip (fifth translation unit): the closed loop with per-robot controller and plant records
+hipError_t qmpc_loop_inst_set_lds();
 hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, const qmpc_plant_params* plant,
                                         const qmpc_instance_params* ctrl, const int* ctrl_status, void* bcast_out, void* plants_out,
                                         int batch);
@@ -275,45 +287,11 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   HIP_TRY(hipMalloc(&h->d_in, sizeof(double) * (32 + 4 * nl) * (size_t)max_batch));
   HIP_TRY(hipMalloc(&h->d_forces, sizeof(double) * nu * (size_t)max_batch));
   HIP_TRY(hipMalloc(&h->d_info, sizeof(qmpc_info) * (size_t)max_batch));
-  // the attribute belongs to the kernel, not to the handle: always raise it to the CU's 160 KB so that handles
-  // with different horizons can coexist (a smaller value set by a later handle would fail the earlier one's launches)
-#define QMPC_SET_LDS(kern, bytes) \
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (bytes) <= 160 * 1024 ? 160 * 1024 : (int)(bytes)))
-  if (params->model == QMPC_MODEL_QUAT8) {
-    QMPC_SET_LDS((qmpc_solve_kernel<Quat8Model, false, 1>), h->sel.lds[0][1]);   // never everything in LDS
-    QMPC_SET_LDS((qmpc_solve_kernel<Quat8Model, false, 2>), h->sel.lds[0][2]);
-  } else if (params->model == QMPC_MODEL_CONVEX) {
-    if (h->sel.lds[0][0] <= 160 * 1024) QMPC_SET_LDS((qmpc_solve_kernel<ConvexModel, false, 0>), h->sel.lds[0][0]);
-    QMPC_SET_LDS((qmpc_solve_kernel<ConvexModel, false, 1>), h->sel.lds[0][1]);
-    QMPC_SET_LDS((qmpc_solve_kernel<ConvexModel, false, 2>), h->sel.lds[0][2]);
-    QMPC_SET_LDS(qmpc_linearize_kernel<ConvexModel>, h->sel.lds[0][1]);
-  } else {
-    if (h->sel.lds[0][0] <= 160 * 1024) {
-      QMPC_SET_LDS((qmpc_solve_kernel<QuatModel, false, 0>), h->sel.lds[0][0]);
-      QMPC_SET_LDS((qmpc_solve_kernel<QuatModel, true, 0>), h->sel.lds[0][0]);
-    }
-    QMPC_SET_LDS((qmpc_solve_kernel<QuatModel, false, 1>), h->sel.lds[0][1]);
-    QMPC_SET_LDS((qmpc_solve_kernel<QuatModel, true, 1>), h->sel.lds[0][1]);
-    QMPC_SET_LDS((qmpc_solve_kernel<QuatModel, false, 2>), h->sel.lds[0][2]);
-    QMPC_SET_LDS(qmpc_linearize_kernel<QuatModel>, h->sel.lds[0][1]);
-  }
-  if (params->model != QMPC_MODEL_QUAT8)
-    for (int v = 0; v < 7; ++v) if (v != 4) HIP_TRY(qmpc_fused_set_lds(v, 160 * 1024));     // the closed loop's persistent kernels
-  if (params->model != QMPC_MODEL_QUAT8) HIP_TRY(qmpc_warm_set_lds(160 * 1024));
-  HIP_TRY(qmpc_wform_set_lds(160 * 1024));
-  if (params->mode == QMPC_MODE_REFERENCE) {
-    if (params->model == QMPC_MODEL_QUAT8) {
-      QMPC_SET_LDS((qmpc_ref_kernel<Quat8Model, 1>), h->sel.lds[0][1]);     // never everything in LDS
-    } else if (params->model == QMPC_MODEL_CONVEX) {
-      if (h->sel.lds[0][0] <= 160 * 1024) QMPC_SET_LDS((qmpc_ref_kernel<ConvexModel, 0>), h->sel.lds[0][0]);
-      QMPC_SET_LDS((qmpc_ref_kernel<ConvexModel, 1>), h->sel.lds[0][1]);
-    } else {
-      if (h->sel.lds[0][0] <= 160 * 1024) QMPC_SET_LDS((qmpc_ref_kernel<QuatModel, 0>), h->sel.lds[0][0]);
-      QMPC_SET_LDS((qmpc_ref_kernel<QuatModel, 1>), h->sel.lds[0][1]);
-    }
-  }
-#undef QMPC_SET_LDS
+  // the dynamic LDS limit of every wave kernel of the library (qmpc_fill_select has refused the layouts beyond 160 KB)
+  HIP_TRY(set_max_lds(kDenseSolve, kDenseRef, kLinearize));
+  HIP_TRY(qmpc_loop_fused_set_lds());
+  HIP_TRY(qmpc_wform_set_lds());
+  HIP_TRY(qmpc_loop_inst_set_lds());
   HIP_TRY(hipMalloc(&h->d_gws, sizeof(double) * (size_t)N * (13 * nu + 21 * nl + 30 * nl) * (size_t)max_batch));
   return QMPC_OK;
 }
@@ -468,42 +446,17 @@ static qmpc_status launch_solve(qmpc_handle* h, int32_t batch, const qmpc_input*
     const qmpc_status ls = launch_lane(h, p, batch, d_in, d_forces, d_info, s, nullptr, d_tu, 0, d_tx, h->sel.handoff_restart);
     if (ls != QMPC_OK) return ls;
   } else if (p.variant >= 3) {      // the wrench-form kernels (qmpc_wform.hip)
-    HIP_TRY(ref ? qmpc_wform_ref_launch(h->params.model, p.variant, (int)batch, p.lds, s, &h->dev, sizeof h->dev, d_in, d_forces, d_info,
-                                        d_tu, d_tx, gws)
-                : qmpc_wform_launch(h->params.model, p.variant, 0, (int)batch, p.lds, s, &h->dev, sizeof h->dev, d_in, d_forces, d_info,
-                                    d_tu, d_tx, nullptr, gws));
-  } else if (ref) {      // the reference's own AL-iLQR mode on the round-1 kernels (qmpc_ref.hip)
-#define QMPC_LAUNCH_REF(kern) \
-  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), p.lds, s, h->dev, d_in, d_forces, d_info, d_tu, d_tx, (int)batch, gws)
-    if (h->params.model == QMPC_MODEL_QUAT8) {
-      QMPC_LAUNCH_REF((qmpc_ref_kernel<Quat8Model, 1>));
-    } else if (h->params.model == QMPC_MODEL_CONVEX) {
-      if (p.variant == 1) QMPC_LAUNCH_REF((qmpc_ref_kernel<ConvexModel, 1>));
-      else QMPC_LAUNCH_REF((qmpc_ref_kernel<ConvexModel, 0>));
-    } else {
-      if (p.variant == 1) QMPC_LAUNCH_REF((qmpc_ref_kernel<QuatModel, 1>));
-      else QMPC_LAUNCH_REF((qmpc_ref_kernel<QuatModel, 0>));
-    }
-#undef QMPC_LAUNCH_REF
-    HIP_TRY(hipGetLastError());
-  } else {
-    const int var = p.variant;
-#define QMPC_LAUNCH(kern) \
-  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), p.lds, s, h->dev, d_in, d_forces, d_info, d_tu, d_tx, \
-                     (int)batch, (long long*)nullptr, gws)
-    if (h->params.model == QMPC_MODEL_QUAT8) {
-      if (var == 2) QMPC_LAUNCH((qmpc_solve_kernel<Quat8Model, false, 2>));
-      else QMPC_LAUNCH((qmpc_solve_kernel<Quat8Model, false, 1>));
-    } else if (h->params.model == QMPC_MODEL_CONVEX) {
-      if (var == 2) QMPC_LAUNCH((qmpc_solve_kernel<ConvexModel, false, 2>));
-      else if (var == 1) QMPC_LAUNCH((qmpc_solve_kernel<ConvexModel, false, 1>));
-      else QMPC_LAUNCH((qmpc_solve_kernel<ConvexModel, false, 0>));
-    } else {
-      if (var == 2) QMPC_LAUNCH((qmpc_solve_kernel<QuatModel, false, 2>));
-      else if (var == 1) QMPC_LAUNCH((qmpc_solve_kernel<QuatModel, false, 1>));
-      else QMPC_LAUNCH((qmpc_solve_kernel<QuatModel, false, 0>));
-    }
-#undef QMPC_LAUNCH
+    HIP_TRY(qmpc_wform_launch(h->params.model, ref, p.variant, 0, (int)batch, p.lds, s, &h->dev, sizeof h->dev, d_in, d_forces, d_info, d_tu,
+                              d_tx, nullptr, gws));
+  } else {      // the round-1 kernels; the reference's own AL-iLQR mode on them: qmpc_ref.hip
+    const int model = h->params.model;
+    const int k = ref ? dense_ref_slot(model, p.variant) : dense_solve_slot(model, p.variant, false);
+    if (k < 0) HIP_TRY(hipErrorInvalidValue);
+    if (ref)
+      hipLaunchKernelGGL(kDenseRef[k], dim3((unsigned)batch), dim3(kWave), p.lds, s, h->dev, d_in, d_forces, d_info, d_tu, d_tx, (int)batch, gws);
+    else
+      hipLaunchKernelGGL(kDenseSolve[k], dim3((unsigned)batch), dim3(kWave), p.lds, s, h->dev, d_in, d_forces, d_info, d_tu, d_tx, (int)batch,
+                         (long long*)nullptr, gws);
     HIP_TRY(hipGetLastError());
   }
   h->last_kernel = p.family;
@@ -759,12 +712,8 @@ static qmpc_status linearize_host(qmpc_handle* h, int32_t batch, const qmpc_inpu
   if (!h->d_B) HIP_TRY(hipMalloc(&h->d_B, nA));
   if (!h->d_traj_x) HIP_TRY(hipMalloc(&h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch));
   HIP_TRY(hipMemcpyAsync(h->d_in, in, sizeof(qmpc_input) * (size_t)batch, hipMemcpyHostToDevice, h->stream));
-  if (model == QMPC_MODEL_CONVEX)
-    hipLaunchKernelGGL(qmpc_linearize_kernel<ConvexModel>, dim3((unsigned)batch), dim3(kWave), h->sel.lds[0][1], h->stream,
-                       h->dev, h->d_in, h->d_A, h->d_B, h->d_traj_x, (int)batch);
-  else
-    hipLaunchKernelGGL(qmpc_linearize_kernel<QuatModel>, dim3((unsigned)batch), dim3(kWave), h->sel.lds[0][1], h->stream,
-                       h->dev, h->d_in, h->d_A, h->d_B, h->d_traj_x, (int)batch);
+  hipLaunchKernelGGL(kLinearize[linearize_slot(model)], dim3((unsigned)batch), dim3(kWave), h->sel.lds[0][1], h->stream, h->dev, h->d_in,
+                     h->d_A, h->d_B, h->d_traj_x, (int)batch);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(Abar, h->d_A, sizeof(double) * 144 * N * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(Bbar, h->d_B, sizeof(double) * 144 * N * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
@@ -886,8 +835,9 @@ static qmpc_status launch_instances(qmpc_handle* h, int32_t batch, const qmpc_in
   const qmpc_status es = ensure_instance_buffers(h);
   if (es != QMPC_OK) return es;
   HIP_TRY(hipEventRecord(h->ev0, s));
-  HIP_TRY(qmpc_wform_inst_launch(p.variant, (int)batch, p.lds, s, &h->dev, sizeof h->dev, d_rec, inst_dev(h), inst_status(h), d_in,
-                                 d_forces, d_info, d_tu, d_tx, p.gws ? h->d_gws : nullptr));
+  HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_rec, inst_dev(h), inst_status(h)));
+  HIP_TRY(qmpc_wform_inst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, d_forces, d_info, d_tu, d_tx,
+                                       p.gws ? h->d_gws : nullptr));
   h->last_kernel = p.family;
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
@@ -1342,6 +1292,17 @@ static qmpc_status replay_ticks(qmpc_handle* h, const qmpc_plan& tick_plan, hipS
 }
 }  // extern "C++"
 
+// The closed loop's set-up on stream s: the trace row counter, reset to -1 stream-ordered (no host staging), and for a warm start
+// in the per-tick form the handle's trajectory buffer, through which the solution travels from tick to tick (the persistent
+// kernel keeps it in LDS; the first tick of a call starts cold)
+static qmpc_status loop_setup(qmpc_handle* h, hipStream_t s, bool warm_ticks) {
+  if (!h->d_loop_row) HIP_TRY(hipMalloc(&h->d_loop_row, sizeof(int)));
+  HIP_TRY(hipMemsetAsync(h->d_loop_row, 0xFF, sizeof(int), s));
+  if (warm_ticks && !h->d_traj_u)
+    HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * (size_t)h->params.horizon * (size_t)h->max_batch));
+  return QMPC_OK;
+}
+
 // g != NULL: the joint-level kernel closes every tick (d_joint_pos in/out, d_cmd = the last tick's commands, d_trace_cmd
 // one row per tick; either of the two may be NULL)
 static qmpc_status loop_run_impl(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
@@ -1359,18 +1320,14 @@ static qmpc_status loop_run_impl(qmpc_handle* h, const qmpc_loop_params* lp, int
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  if (!h->d_loop_row) HIP_TRY(hipMalloc(&h->d_loop_row, sizeof(int)));
-  HIP_TRY(hipMemsetAsync(h->d_loop_row, 0xFF, sizeof(int), s));     // row counter = -1, stream-ordered (no host staging)
+  const bool warm = lp->warm_start != 0.0 && h->params.mode == QMPC_MODE_CONVERGED;
+  const qmpc_status ss = loop_setup(h, s, warm);
+  if (ss != QMPC_OK) return ss;
   const unsigned blocks = (unsigned)((batch + 63) / 64);
   const qmpc_loop_params LP = *lp;
   LegGeom G;
   std::memset(&G, 0, sizeof G);
   if (g) std::memcpy(&G, g, sizeof G);
-  // warm start in the per-tick form: the solution travels from tick to tick through the handle's trajectory buffer (the
-  // persistent kernel keeps it in LDS); the first tick of a call starts cold
-  const bool warm = lp->warm_start != 0.0 && h->params.mode == QMPC_MODE_CONVERGED;
-  if (warm && !h->d_traj_u)
-    HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * (size_t)h->params.horizon * (size_t)h->max_batch));
   auto one_tick = [&](bool first) -> qmpc_status {
     if (convex)
       hipLaunchKernelGGL(qmpc_loop_front_convex_kernel, dim3(blocks), dim3(64), 0, s, LP, d_states,
@@ -1419,14 +1376,12 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
   return loop_run_impl(h, lp, batch, d_states, ticks, nullptr, nullptr, g, d_joint_pos, d_cmd, d_trace_cmd, stream);
 }
 
-qmpc_status qmpc_loop_run(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
-                          int32_t ticks, double* trace_forces, double* trace_contacts) {
-  if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !states)) return QMPC_BAD_ARGUMENT;
-  if (h->params.model != QMPC_MODEL_QUAT && h->params.model != QMPC_MODEL_CONVEX) return QMPC_BAD_ARGUMENT;
-  if (batch == 0 || ticks == 0) return QMPC_OK;
-  if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
-  HIP_TRY(hipSetDevice(h->device));
-  // staging that belongs to the handle and only grows: [states | force trace | contact trace]
+// The host-buffer closed loop (qmpc_loop_run*, its arguments checked): states, the records given and the traces through the
+// handle's staging, which only grows -- [states | force trace | contact trace]; the records go to the staging halves of the
+// per-instance and plant buffers (allocated by the caller)
+static qmpc_status loop_run_host(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                 const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                 double* trace_contacts) {
   const size_t B = (size_t)batch, T = (size_t)ticks;
   const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
                n_tc = trace_contacts ? 4 * B * T : 0;
@@ -1440,17 +1395,27 @@ qmpc_status qmpc_loop_run(qmpc_handle* h, const qmpc_loop_params* lp, int32_t ba
   qmpc_loop_state* d_st = reinterpret_cast<qmpc_loop_state*>(h->d_loop);
   double* d_tf = trace_forces ? h->d_loop + n_st : nullptr;
   double* d_tc = trace_contacts ? h->d_loop + n_st + n_tf : nullptr;
-  qmpc_status rs = QMPC_OK;
-  do {
-    if (hipMemcpyAsync(d_st, states, sizeof(qmpc_loop_state) * B, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rs = QMPC_HIP_ERROR; break; }
-    rs = qmpc_loop_run_device(h, lp, batch, d_st, ticks, d_tf, d_tc, nullptr);
-    if (rs != QMPC_OK) break;
-    if (hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { rs = QMPC_HIP_ERROR; break; }
-    if (d_tf && hipMemcpyAsync(trace_forces, d_tf, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { rs = QMPC_HIP_ERROR; break; }
-    if (d_tc && hipMemcpyAsync(trace_contacts, d_tc, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { rs = QMPC_HIP_ERROR; break; }
-    if (hipStreamSynchronize(h->stream) != hipSuccess) rs = QMPC_HIP_ERROR;
-  } while (0);
-  return rs;
+  HIP_TRY(hipMemcpyAsync(d_st, states, sizeof(qmpc_loop_state) * B, hipMemcpyHostToDevice, h->stream));
+  if (ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
+  if (plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
+  const qmpc_status rs = qmpc_loop_run_instances_device(h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
+                                                        d_tf, d_tc, nullptr);
+  if (rs != QMPC_OK) return rs;
+  HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
+  if (d_tf) HIP_TRY(hipMemcpyAsync(trace_forces, d_tf, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream));
+  if (d_tc) HIP_TRY(hipMemcpyAsync(trace_contacts, d_tc, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return QMPC_OK;
+}
+
+qmpc_status qmpc_loop_run(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                          int32_t ticks, double* trace_forces, double* trace_contacts) {
+  if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !states)) return QMPC_BAD_ARGUMENT;
+  if (h->params.model != QMPC_MODEL_QUAT && h->params.model != QMPC_MODEL_CONVEX) return QMPC_BAD_ARGUMENT;
+  if (batch == 0 || ticks == 0) return QMPC_OK;
+  if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
+  HIP_TRY(hipSetDevice(h->device));
+  return loop_run_host(h, lp, batch, states, ticks, nullptr, nullptr, trace_forces, trace_contacts);
 }
 
 // ---- the closed loop with per-robot controller and plant records (qmpc_loop_inst.hip) -------------------------------------
@@ -1490,8 +1455,8 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
   qmpc_status es = ensure_instance_buffers(h);
   if (es == QMPC_OK) es = ensure_plant_buffers(h);
   if (es != QMPC_OK || ticks == 0) return es;      // ticks = 0: the buffers only (e.g. before the caller's stream capture)
-  if (!h->d_loop_row) HIP_TRY(hipMalloc(&h->d_loop_row, sizeof(int)));
-  HIP_TRY(hipMemsetAsync(h->d_loop_row, 0xFF, sizeof(int), s));     // row counter = -1 (per-tick form)
+  const qmpc_status ss = loop_setup(h, s, warm && !lpp.fused);
+  if (ss != QMPC_OK) return ss;
   const qmpc_loop_params LP = *lp;
   // the records are expanded once per call: the controllers' blocks (or, for the persistent kernel without controller records,
   // the handle's block per robot) and the plant blocks with each robot's verdict
@@ -1503,13 +1468,11 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
                                         h->d_info, d_trace_forces, d_trace_contacts, (int)ticks, lpp.gws ? h->d_gws : nullptr));
     return QMPC_OK;
   }
-  if (warm && !h->d_traj_u)
-    HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * (size_t)h->params.horizon * (size_t)h->max_batch));
   auto one_tick = [&](bool first) -> qmpc_status {
     HIP_TRY(qmpc_loop_inst_front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch));
     if (d_ctrl) {      // the per-instance wrench-form kernel on the blocks expanded above
       HIP_TRY(qmpc_wform_inst_solve_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces,
-                                           h->d_info, lpp.gws ? h->d_gws : nullptr));
+                                           h->d_info, nullptr, nullptr, lpp.gws ? h->d_gws : nullptr));
       h->last_kernel = lpp.family;
     } else {           // the plain loop's solve
       const qmpc_status st = loop_tick_solve(h, batch, s, warm, first, false);
@@ -1533,32 +1496,7 @@ qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, 
   qmpc_status es = ensure_instance_buffers(h);
   if (es == QMPC_OK) es = ensure_plant_buffers(h);
   if (es != QMPC_OK || ticks == 0) return es;
-  // staging that belongs to the handle and only grows: [states | force trace | contact trace] (as qmpc_loop_run); the records go
-  // to the staging halves of the per-instance and plant buffers
-  const size_t B = (size_t)batch, T = (size_t)ticks;
-  const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
-               n_tc = trace_contacts ? 4 * B * T : 0;
-  if (h->loop_cap < n_st + n_tf + n_tc) {
-    if (h->d_loop) (void)hipFree(h->d_loop);
-    h->d_loop = nullptr;
-    h->loop_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_loop, sizeof(double) * (n_st + n_tf + n_tc)));
-    h->loop_cap = n_st + n_tf + n_tc;
-  }
-  qmpc_loop_state* d_st = reinterpret_cast<qmpc_loop_state*>(h->d_loop);
-  double* d_tf = trace_forces ? h->d_loop + n_st : nullptr;
-  double* d_tc = trace_contacts ? h->d_loop + n_st + n_tf : nullptr;
-  HIP_TRY(hipMemcpyAsync(d_st, states, sizeof(qmpc_loop_state) * B, hipMemcpyHostToDevice, h->stream));
-  if (ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
-  if (plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
-  const qmpc_status rs = qmpc_loop_run_instances_device(h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
-                                                        d_tf, d_tc, nullptr);
-  if (rs != QMPC_OK) return rs;
-  HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
-  if (d_tf) HIP_TRY(hipMemcpyAsync(trace_forces, d_tf, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream));
-  if (d_tc) HIP_TRY(hipMemcpyAsync(trace_contacts, d_tc, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return QMPC_OK;
+  return loop_run_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts);
 }
 
 // Diagnostic: per-instance phase cycle counts (s_memtime) of one solve launch.
@@ -1575,18 +1513,16 @@ qmpc_status qmpc_debug_profile(qmpc_handle* h, int32_t batch, const qmpc_input* 
   HIP_TRY(hipMemsetAsync(d_prof, 0, sizeof(long long) * 16 * (size_t)batch, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_in, in, sizeof(qmpc_input) * (size_t)batch, hipMemcpyHostToDevice, h->stream));
   const qmpc_plan p = plan(h->sel, batch, QMPC_CALL_PROFILE, true, h->handoff_failed);
-  if (p.variant >= 3)
-    HIP_TRY(qmpc_wform_launch(QMPC_MODEL_QUAT, p.variant, 1, (int)batch, p.lds, h->stream, &h->dev, sizeof h->dev, h->d_in, h->d_forces, h->d_info,
+  if (p.variant >= 3) {
+    HIP_TRY(qmpc_wform_launch(QMPC_MODEL_QUAT, 0, p.variant, 1, (int)batch, p.lds, h->stream, &h->dev, sizeof h->dev, h->d_in, h->d_forces, h->d_info,
                               nullptr, nullptr, d_prof, p.gws ? h->d_gws : nullptr));
-  else if (p.variant == 1)
-    hipLaunchKernelGGL((qmpc_solve_kernel<QuatModel, true, 1>), dim3((unsigned)batch), dim3(kWave), p.lds, h->stream,
-                       h->dev, h->d_in, h->d_forces, h->d_info, (double*)nullptr, (double*)nullptr, (int)batch, d_prof,
-                       h->d_gws);
-  else
-    hipLaunchKernelGGL((qmpc_solve_kernel<QuatModel, true, 0>), dim3((unsigned)batch), dim3(kWave), p.lds, h->stream,
-                       h->dev, h->d_in, h->d_forces, h->d_info, (double*)nullptr, (double*)nullptr, (int)batch, d_prof,
-                       (double*)nullptr);
-  HIP_TRY(hipGetLastError());
+  } else {
+    const int k = dense_solve_slot(QMPC_MODEL_QUAT, p.variant, true);
+    if (k < 0) HIP_TRY(hipErrorInvalidValue);
+    hipLaunchKernelGGL(kDenseSolve[k], dim3((unsigned)batch), dim3(kWave), p.lds, h->stream, h->dev, h->d_in, h->d_forces, h->d_info,
+                       (double*)nullptr, (double*)nullptr, (int)batch, d_prof, p.gws ? h->d_gws : nullptr);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipMemcpyAsync(cycles_out, d_prof, sizeof(long long) * 16 * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipFree(d_prof));

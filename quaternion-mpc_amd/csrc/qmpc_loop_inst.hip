@@ -19,6 +19,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "qmpc_kernel_slots.h"
+
 namespace qmpc_inst_tu {
 
 // One thread per robot: the robot's plant block (from plant[i], or from ctrl[i]'s mass and inertia with no disturbance when
@@ -145,6 +147,7 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QuatModel, VAR)) void qmpc_loo
 }  // namespace qmpc_inst_tu
 
 using namespace qmpc_inst_tu;
+using namespace qmpc;
 
 // called from qmpc_hip.hip (declared there); hidden: not part of the C ABI
 // expand the plant records (or the controller's robots) of `batch` robots into plants_out; bcast_out (or null): the handle's
@@ -161,28 +164,22 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_loop_inst_expand_launch(hi
   return hipGetLastError();
 }
 
+// the launch table of this unit: the persistent kernels by wrench-form variant 3 / 5 / 6 (qmpc_kernel_slots.h: wform_index)
+static decltype(&qmpc_loop_fused_inst_kernel<3>) const kLoopInst[] = {qmpc_loop_fused_inst_kernel<3>, qmpc_loop_fused_inst_kernel<5>,
+                                                                     qmpc_loop_fused_inst_kernel<6>};
+static_assert(sizeof kLoopInst / sizeof kLoopInst[0] == kWformVars, "qmpc_kernel_slots.h");
+
+__attribute__((visibility("hidden"))) hipError_t qmpc_loop_inst_set_lds() { return set_max_lds(kLoopInst); }
+
 // one launch for all ticks: var 3 / 5 / 6 (qmpc_plan.h: plan_loop_instances)
 __attribute__((visibility("hidden"))) hipError_t qmpc_loop_inst_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks,
                                                                              const void* plants, const qmpc_loop_params* lp, qmpc_loop_state* st,
                                                                              qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f,
                                                                              double* trace_c, int ticks, double* gws) {
-  const void* k = var == 6 ? reinterpret_cast<const void*>(qmpc_loop_fused_inst_kernel<6>)
-                  : var == 5 ? reinterpret_cast<const void*>(qmpc_loop_fused_inst_kernel<5>)
-                  : var == 3 ? reinterpret_cast<const void*>(qmpc_loop_fused_inst_kernel<3>) : nullptr;
-  if (!k) return hipErrorInvalidValue;
-  // the dynamic LDS limit of the persistent kernels (qmpc_fused_set_lds sets it for the plain ones at qmpc_create)
-  const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  const DevParams* Pi = static_cast<const DevParams*>(dev_blocks);
-  const PlantDev* pl = static_cast<const PlantDev*>(plants);
-  const qmpc_loop_params LP = *lp;
-#define QMPC_LAUNCH_FI(V) \
-  hipLaunchKernelGGL(qmpc_loop_fused_inst_kernel<V>, dim3((unsigned)batch), dim3(kWave), lds, s, Pi, pl, LP, st, rec, forces, info, \
-                     trace_f, trace_c, ticks, batch, gws)
-  if (var == 6) QMPC_LAUNCH_FI(6);
-  else if (var == 5) QMPC_LAUNCH_FI(5);
-  else QMPC_LAUNCH_FI(3);
-#undef QMPC_LAUNCH_FI
+  const int k = wform_index(var);
+  if (k < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kLoopInst[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks),
+                     static_cast<const PlantDev*>(plants), *lp, st, rec, forces, info, trace_f, trace_c, ticks, batch, gws);
   return hipGetLastError();
 }
 

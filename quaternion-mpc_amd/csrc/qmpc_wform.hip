@@ -239,103 +239,48 @@ __global__ __launch_bounds__(64, OCC) void qmpc_ref8_w_kernel(
 
 #include <cstring>
 
+#include "qmpc_kernel_slots.h"
+
 using namespace qmpc_wform_tu;
+using namespace qmpc;
+
+// the launch tables of this unit (slots: qmpc_kernel_slots.h)
+static decltype(&qmpc_solve_w_kernel<false, 3>) const kWformQuat[] = {
+    qmpc_solve_w_kernel<false, 3>, qmpc_solve_w_kernel<false, 5>, qmpc_solve_w_kernel<false, 6>,
+    qmpc_solve_w_kernel<true, 3>, qmpc_solve_w_kernel<true, 5>};
+static decltype(&qmpc_solve8_w_kernel<3>) const kWform[] = {
+    qmpc_solve8_w_kernel<3>, qmpc_solve8_w_kernel<5>, qmpc_solve8_w_kernel<6>,
+    qmpc_solve_cw_kernel<3>, qmpc_solve_cw_kernel<5>, qmpc_solve_cw_kernel<6>,
+    qmpc_ref_w_kernel<3, 1>, qmpc_ref_w_kernel<5, 1>, qmpc_ref_w_kernel<5, 2>,
+    qmpc_ref_cw_kernel<3, 1>, qmpc_ref_cw_kernel<5, 1>, qmpc_ref_cw_kernel<5, 2>,
+    qmpc_ref8_w_kernel<3, 1>, qmpc_ref8_w_kernel<5, 1>};
+static decltype(&qmpc_solve_w_list_kernel<3>) const kWformList[] = {qmpc_solve_w_list_kernel<3>, qmpc_solve_w_list_kernel<5>};
+static decltype(&qmpc_solve_w_inst_kernel<3>) const kWformInst[] = {qmpc_solve_w_inst_kernel<3>, qmpc_solve_w_inst_kernel<5>,
+                                                                     qmpc_solve_w_inst_kernel<6>};
+static_assert(sizeof kWformQuat / sizeof kWformQuat[0] == kWformQuatSlots && sizeof kWform / sizeof kWform[0] == kWformSlots &&
+                  sizeof kWformList / sizeof kWformList[0] == kWformListSlots && sizeof kWformInst / sizeof kWformInst[0] == kWformVars,
+              "qmpc_kernel_slots.h");
 
 // called from qmpc_hip.hip (declared there); hidden: not part of the C ABI
 __attribute__((visibility("hidden"))) size_t qmpc_wform_slice_doubles(int N, int nl) { return nl == 8 ? wform_slice<8>(N, true) : wform_slice<4>(N, true); }
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_set_lds(int bytes) {
-  const void* k[24] = {reinterpret_cast<const void*>(qmpc_ref8_w_kernel<3, 1>), reinterpret_cast<const void*>(qmpc_ref8_w_kernel<5, 1>),
-                      reinterpret_cast<const void*>(qmpc_solve_w_kernel<false, 3>), reinterpret_cast<const void*>(qmpc_solve_w_kernel<true, 3>),
-                      reinterpret_cast<const void*>(qmpc_solve_w_kernel<false, 5>), reinterpret_cast<const void*>(qmpc_solve_w_kernel<true, 5>),
-                      reinterpret_cast<const void*>(qmpc_solve_w_list_kernel<3>), reinterpret_cast<const void*>(qmpc_solve_w_list_kernel<5>),
-                      reinterpret_cast<const void*>(qmpc_ref_w_kernel<3>), reinterpret_cast<const void*>(qmpc_ref_w_kernel<5>),
-                      reinterpret_cast<const void*>(qmpc_ref_w_kernel<5, 1>),
-                      reinterpret_cast<const void*>(qmpc_solve8_w_kernel<3>), reinterpret_cast<const void*>(qmpc_solve8_w_kernel<5>),
-                      reinterpret_cast<const void*>(qmpc_solve_cw_kernel<3>), reinterpret_cast<const void*>(qmpc_solve_cw_kernel<5>),
-                      reinterpret_cast<const void*>(qmpc_solve_w_kernel<false, 6>), reinterpret_cast<const void*>(qmpc_solve_cw_kernel<6>),
-                      reinterpret_cast<const void*>(qmpc_solve8_w_kernel<6>),
-                      reinterpret_cast<const void*>(qmpc_ref_cw_kernel<3, 1>), reinterpret_cast<const void*>(qmpc_ref_cw_kernel<5, 1>),
-                      reinterpret_cast<const void*>(qmpc_ref_cw_kernel<5, 2>),
-                      reinterpret_cast<const void*>(qmpc_solve_w_inst_kernel<3>), reinterpret_cast<const void*>(qmpc_solve_w_inst_kernel<5>),
-                      reinterpret_cast<const void*>(qmpc_solve_w_inst_kernel<6>)};
-  for (int i = 0; i < 24; ++i) {
-    const hipError_t e = hipFuncSetAttribute(k[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
+__attribute__((visibility("hidden"))) hipError_t qmpc_wform_set_lds() { return set_max_lds(kWformQuat, kWform, kWformList, kWformInst); }
 // model: QMPC_MODEL_* (eight contact points: records of 64 doubles, 24 forces per instance; ConvexMpc: records of 48 doubles,
-// 12 world-frame forces); var: 3 everything in LDS, 5 gains in the workspace gws, 6 the slack arrays there too;
-// prof: QuatMpc's per-phase cycle counters (3 and 5)
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch(int model, int var, int prof, int batch, size_t lds, hipStream_t s,
+// 12 world-frame forces); ref: the reference mode; var: 3 everything in LDS, 5 gains in the workspace gws, 6 the slack arrays
+// there too (converged mode); prof: QuatMpc's per-phase cycle counters
+__attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch(int model, int ref, int var, int prof, int batch, size_t lds, hipStream_t s,
                                                                    const void* dev_params, size_t dev_params_size,
                                                                    const qmpc_input* in, double* forces, qmpc_info* info,
                                                                    double* traj_u, double* traj_x, long long* prof_out, double* gws) {
   if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
   DevParams P;
   std::memcpy(&P, dev_params, sizeof P);
-#define QMPC_LAUNCH_W(kern, ...) \
-  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, batch, __VA_ARGS__)
-  if (model == QMPC_MODEL_QUAT8) {
-    if (var == 6) QMPC_LAUNCH_W(qmpc_solve8_w_kernel<6>, gws);
-    else if (var == 5) QMPC_LAUNCH_W(qmpc_solve8_w_kernel<5>, gws);
-    else QMPC_LAUNCH_W(qmpc_solve8_w_kernel<3>, gws);
-  } else if (model == QMPC_MODEL_CONVEX) {
-    if (var == 6) QMPC_LAUNCH_W(qmpc_solve_cw_kernel<6>, gws);
-    else if (var == 5) QMPC_LAUNCH_W(qmpc_solve_cw_kernel<5>, gws);
-    else QMPC_LAUNCH_W(qmpc_solve_cw_kernel<3>, gws);
-  } else if (var == 6) {
-    QMPC_LAUNCH_W((qmpc_solve_w_kernel<false, 6>), prof_out, gws);
-  } else if (var == 5) {
-    if (prof) QMPC_LAUNCH_W((qmpc_solve_w_kernel<true, 5>), prof_out, gws); else QMPC_LAUNCH_W((qmpc_solve_w_kernel<false, 5>), prof_out, gws);
-  } else {
-    if (prof) QMPC_LAUNCH_W((qmpc_solve_w_kernel<true, 3>), prof_out, gws); else QMPC_LAUNCH_W((qmpc_solve_w_kernel<false, 3>), prof_out, gws);
-  }
-#undef QMPC_LAUNCH_W
-  return hipGetLastError();
-}
-// per-instance parameters (qmpc_solve_instances*): expand the records rec[0 .. batch) against the handle's parameters into
-// dev_out / status_out (device buffers of `batch` entries), then solve with variant var (3 / 5 / 6) reading them
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_params,
-                                                                        size_t dev_params_size, const qmpc_instance_params* rec, void* dev_out,
-                                                                        int* status_out, const qmpc_input* in, double* forces, qmpc_info* info,
-                                                                        double* traj_u, double* traj_x, double* gws) {
-  if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
-  DevParams P;
-  std::memcpy(&P, dev_params, sizeof P);
-  DevParams* Pi = static_cast<DevParams*>(dev_out);
-  hipLaunchKernelGGL(qmpc_expand_instances_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, P, rec, Pi, status_out, batch);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-#define QMPC_LAUNCH_WI(kern) \
-  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, Pi, in, forces, info, traj_u, traj_x, batch, gws, status_out)
-  if (var == 6) QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<6>);
-  else if (var == 5) QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<5>);
-  else QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<3>);
-#undef QMPC_LAUNCH_WI
-  return hipGetLastError();
-}
-// the two halves of qmpc_wform_inst_launch, for the closed loop with per-robot records (qmpc_loop_run_instances*): the
-// expansion once per call, the solve every tick (dev_blocks / status: the expanded blocks and verdicts)
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_expand_launch(int batch, hipStream_t s, const void* dev_params, size_t dev_params_size,
-                                                                               const qmpc_instance_params* rec, void* dev_out, int* status_out) {
-  if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
-  DevParams P;
-  std::memcpy(&P, dev_params, sizeof P);
-  hipLaunchKernelGGL(qmpc_expand_instances_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, P, rec,
-                     static_cast<DevParams*>(dev_out), status_out, batch);
-  return hipGetLastError();
-}
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks,
-                                                                              const int* status, const qmpc_input* in, double* forces,
-                                                                              qmpc_info* info, double* gws) {
-  const DevParams* Pi = static_cast<const DevParams*>(dev_blocks);
-#define QMPC_LAUNCH_WI(kern) \
-  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, Pi, in, forces, info, (double*)nullptr, (double*)nullptr, batch, gws, status)
-  if (var == 6) QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<6>);
-  else if (var == 5) QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<5>);
-  else QMPC_LAUNCH_WI(qmpc_solve_w_inst_kernel<3>);
-#undef QMPC_LAUNCH_WI
+  const bool quat = model == QMPC_MODEL_QUAT && !ref;
+  const int k = quat ? wform_quat_slot(var, prof != 0) : wform_slot(model, ref != 0, var, wform_ref_one_wave(batch, lds));
+  if (k < 0) return hipErrorInvalidValue;
+  if (quat)
+    hipLaunchKernelGGL(kWformQuat[k], dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, batch, prof_out, gws);
+  else
+    hipLaunchKernelGGL(kWform[k], dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, batch, gws);
   return hipGetLastError();
 }
 // the instances sel[0 .. *sel_count) (device memory), `grid` workgroups walking the list
@@ -347,39 +292,31 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_wform_launch_list(int var,
   if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
   DevParams P;
   std::memcpy(&P, dev_params, sizeof P);
-  if (var == 5)
-    hipLaunchKernelGGL(qmpc_solve_w_list_kernel<5>, dim3((unsigned)grid), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, sel,
-                       sel_count, gws, hstate, hcap);
-  else
-    hipLaunchKernelGGL(qmpc_solve_w_list_kernel<3>, dim3((unsigned)grid), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, sel,
-                       sel_count, gws, hstate, hcap);
+  const int k = wform_list_slot(var);
+  if (k < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kWformList[k], dim3((unsigned)grid), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, sel, sel_count, gws,
+                     hstate, hcap);
   return hipGetLastError();
 }
-// reference mode; model and var as above (3 / 5)
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_ref_launch(int model, int var, int batch, size_t lds, hipStream_t s,
-                                                                       const void* dev_params, size_t dev_params_size, const qmpc_input* in,
-                                                                       double* forces, qmpc_info* info, double* traj_u, double* traj_x,
-                                                                       double* gws) {
+// per-instance parameters (qmpc_solve_instances*; the closed loop with per-robot records expands once per call and solves every
+// tick): expand the records rec[0 .. batch) against the handle's parameters into dev_out / status_out (device buffers of `batch`
+// entries) ...
+__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_expand_launch(int batch, hipStream_t s, const void* dev_params, size_t dev_params_size,
+                                                                               const qmpc_instance_params* rec, void* dev_out, int* status_out) {
   if (dev_params_size != sizeof(DevParams)) return hipErrorInvalidValue;
   DevParams P;
   std::memcpy(&P, dev_params, sizeof P);
-  // one instance per SIMD at most -- a small batch, or a horizon whose LDS (> 20 KB: N >= 11) leaves a CU four instances
-  // anyway: the whole register file (the 256-register instantiation spills 157 VGPRs and would gain no occupancy for it)
-  const bool one_wave = batch <= 1024 || lds > 20 * 1024;
-#define QMPC_LAUNCH_W(kern) \
-  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, P, in, forces, info, traj_u, traj_x, batch, gws)
-  if (model == QMPC_MODEL_QUAT8) {      // everything in LDS (one instance per CU) or gains / records / blocks in the workspace
-    if (var == 5) QMPC_LAUNCH_W((qmpc_ref8_w_kernel<5, 1>));
-    else QMPC_LAUNCH_W((qmpc_ref8_w_kernel<3, 1>));
-  } else if (model == QMPC_MODEL_CONVEX) {
-    if (var == 5 && one_wave) QMPC_LAUNCH_W((qmpc_ref_cw_kernel<5, 1>));
-    else if (var == 5) QMPC_LAUNCH_W((qmpc_ref_cw_kernel<5, 2>));
-    else QMPC_LAUNCH_W((qmpc_ref_cw_kernel<3, 1>));
-  } else {
-    if (var == 5 && one_wave) QMPC_LAUNCH_W((qmpc_ref_w_kernel<5, 1>));
-    else if (var == 5) QMPC_LAUNCH_W(qmpc_ref_w_kernel<5>);
-    else QMPC_LAUNCH_W(qmpc_ref_w_kernel<3>);
-  }
-#undef QMPC_LAUNCH_W
+  hipLaunchKernelGGL(qmpc_expand_instances_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, P, rec,
+                     static_cast<DevParams*>(dev_out), status_out, batch);
+  return hipGetLastError();
+}
+// ... and solve with variant var (3 / 5 / 6) reading the expanded blocks and verdicts (dev_blocks / status)
+__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks,
+                                                                              const int* status, const qmpc_input* in, double* forces,
+                                                                              qmpc_info* info, double* traj_u, double* traj_x, double* gws) {
+  const int k = wform_index(var);
+  if (k < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kWformInst[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks), in, forces, info,
+                     traj_u, traj_x, batch, gws, status);
   return hipGetLastError();
 }

@@ -7,9 +7,12 @@
 // headers as the library's, and the selection state from the same filler as qmpc_create's.
 //   plan_host              the table on stdout
 //   plan_host --write F    ... into F
+//   plan_host --kernels    check that every plan of the enumeration, and of qmpc_solve_instances* and qmpc_loop_run_instances*
+//                          on the same configurations, names a kernel of its unit's launch table (qmpc_kernel_slots.h)
 #define QMPC_FUSED_TU 1      // the templates of the kernel headers only: no kernel is instantiated here
 #include "../../quaternion-mpc_amd/csrc/qmpc_kernels.hip"
 #include "../../quaternion-mpc_amd/csrc/qmpc_wform.h"
+#include "../../quaternion-mpc_amd/csrc/qmpc_kernel_slots.h"
 #include "../../quaternion-mpc_amd/csrc/qmpc_plan_fill.h"
 
 #include <algorithm>
@@ -54,14 +57,45 @@ std::string row(const qmpc::qmpc_plan& p) {
   return b;
 }
 
+// Whether the launch table slot the launchers take for plan p of a call of kind `call` exists (qmpc_hip.hip: launch_solve,
+// loop_tick_solve, qmpc_solve_warm_device, qmpc_debug_profile, loop_run_impl, launch_lane, launch_instances,
+// qmpc_loop_run_instances_device); joint: the JOINT half of the persistent kernels; inst: a per-instance kernel (per-instance
+// solve, persistent loop with per-robot records).  A plan of no wave kernel (NONE, the lane kernel) needs none.
+bool has_kernel(const qmpc::qmpc_select& s, const qmpc::qmpc_plan& p, qmpc::qmpc_call call, int batch, bool joint, bool inst) {
+  using namespace qmpc;
+  const bool ref = s.mode == QMPC_MODE_REFERENCE, convex = s.model == QMPC_MODEL_CONVEX;
+  const bool warm = call == QMPC_CALL_WARM || call == QMPC_CALL_WARM_LOOP_FIRST || call == QMPC_CALL_WARM_LOOP_TICK || call == QMPC_CALL_WARM_LOOP;
+  if (p.family == QMPC_KERNEL_NONE || p.family == QMPC_KERNEL_LANE) return true;
+  if (inst) return wform_index(p.variant) >= 0;
+  if (p.family == QMPC_KERNEL_LANE_HANDOFF) return wform_list_slot(p.handoff_variant) >= 0;
+  if (p.fused) return fused_slot(p.variant, ref, convex, joint) >= 0;
+  if (warm) return warm_slot(p.variant, convex) >= 0;
+  if (call == QMPC_CALL_PROFILE) return p.variant >= 3 ? wform_quat_slot(p.variant, true) >= 0 : dense_solve_slot(s.model, p.variant, true) >= 0;
+  if (p.variant >= 3)
+    return (s.model == QMPC_MODEL_QUAT && !ref) ? wform_quat_slot(p.variant, false) >= 0
+                                                : wform_slot(s.model, ref, p.variant, wform_ref_one_wave(batch, p.lds)) >= 0;
+  return ref ? dense_ref_slot(s.model, p.variant) >= 0 : dense_solve_slot(s.model, p.variant, false) >= 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   FILE* out = stdout;
+  const bool kernels = argc == 2 && std::strcmp(argv[1], "--kernels") == 0;
   if (argc == 3 && std::strcmp(argv[1], "--write") == 0) out = std::fopen(argv[2], "w");
-  else if (argc != 1) { std::fprintf(stderr, "usage: plan_host [--write FILE]\n"); return 2; }
+  else if (argc != 1 && !kernels) { std::fprintf(stderr, "usage: plan_host [--write FILE | --kernels]\n"); return 2; }
   if (!out) return 1;
-  std::fprintf(out, "# per configuration and call kind, from the smallest batch of each run with one plan: kind batch | family variant lds gws "
+  long checked = 0, missing = 0;
+  auto check = [&](const qmpc::qmpc_select& sel, const qmpc::qmpc_plan& p, qmpc::qmpc_call call, int b, const char* cfg, bool inst) {
+    for (int joint = 0; joint < (p.fused && !inst ? 2 : 1); ++joint) {
+      ++checked;
+      if (!has_kernel(sel, p, call, b, joint, inst) && ++missing <= 20)
+        std::fprintf(stderr, "no kernel: %s, call %d%s batch %d: family %d variant %d joint %d\n", cfg, (int)call, inst ? " (per instance)" : "",
+                     b, p.family, p.variant, joint);
+    }
+  };
+  if (!kernels)
+    std::fprintf(out, "# per configuration and call kind, from the smallest batch of each run with one plan: kind batch | family variant lds gws "
                     "handoff_variant iter_cap handoff_grid upload_params order_prev fused\n");
   const int horizons[] = {1, 2, 4, 10, 12, 13, 16, 20, 21, 22, 23, 32};
   for (int model = 0; model < 3; ++model)
@@ -85,19 +119,40 @@ int main(int argc, char** argv) {
                 for (int d = -1; d <= 1; ++d) batches.insert(256 * (int)((160 * 1024) / lds) + d);
           for (int t : {sel.lane_min_batch, sel.lane_min_loop_cold, sel.lane_min_warm, sel.lane_ref_min, qmpc::kLaneRefMinLoop})
             for (int d = -1; d <= 1; ++d) batches.insert(t + d);
-          std::fprintf(out, "# %s %s N=%d %s\n", kModel[model], kMode[mode], N, k.name);
+          char cfg[128];
+          std::snprintf(cfg, sizeof cfg, "%s %s N=%d %s", kModel[model], kMode[mode], N, k.name);
+          if (!kernels) std::fprintf(out, "# %s\n", cfg);
           for (int kind = 0; kind <= (int)qmpc::QMPC_CALL_COUNT; ++kind) {      // the last: a plain solve without status records
             const bool has_info = kind != (int)qmpc::QMPC_CALL_COUNT;
             const qmpc::qmpc_call call = has_info ? (qmpc::qmpc_call)kind : qmpc::QMPC_CALL_PLAIN;
             std::string prev;
             for (int b : batches) {
               if (b < 1) continue;
-              const std::string r = row(qmpc::plan(sel, b, call, has_info, k.handoff_failed));
+              const qmpc::qmpc_plan p = qmpc::plan(sel, b, call, has_info, k.handoff_failed);
+              if (kernels) {
+                check(sel, p, call, b, cfg, false);
+                continue;
+              }
+              const std::string r = row(p);
               if (r == prev) continue;
               std::fprintf(out, "%s%s %d %s\n", kKind[call], has_info ? "" : "-noinfo", b, r.c_str());
               prev = r;
             }
           }
+          if (!kernels) continue;
+          for (int b : batches) {      // the per-instance solve and the closed loop with per-robot records (controller / plant)
+            if (b < 1) continue;
+            check(sel, qmpc::plan_instances(sel, b), qmpc::QMPC_CALL_PLAIN, b, cfg, true);
+            for (int rec = 0; rec < 4; ++rec) {
+              const bool ctrl = rec & 1, warm = rec & 2;
+              const qmpc::qmpc_plan pl = qmpc::plan_loop_instances(sel, b, ctrl, warm, k.handoff_failed);
+              check(sel, pl, warm ? qmpc::QMPC_CALL_WARM_LOOP_TICK : qmpc::QMPC_CALL_LOOP_TICK, b, cfg, pl.fused || ctrl);
+            }
+          }
         }
+  if (kernels) {
+    std::printf("%ld plans checked, %ld without a kernel\n", checked, missing);
+    return missing ? 1 : 0;
+  }
   return out == stdout ? 0 : (std::fclose(out) == 0 ? 0 : 1);
 }
