@@ -157,12 +157,18 @@ typedef unsigned u2v __attribute__((ext_vector_type(2)));
 
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov(double x) {
-  int lo = __double2loint(x), hi = __double2hiint(x);
   // every lane of these controls has a valid source and the masks are full, so the `old` operand is dead:
   // bound_ctrl lets the compiler drop its initialisation (two v_mov + a hazard nop per DPP pair)
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
+  if constexpr (CTRL >= 0x150 && CTRL <= 0x15F) {
+    // row_newbcast is the one control the 64-bit DPP form has (gfx90a+): one v_mov_b64_dpp, one issue slot, instead of
+    // a v_mov_b32_dpp per half
+    return __builtin_amdgcn_update_dpp(0.0, x, CTRL, 0xF, 0xF, true);
+  } else {
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+  }
 }
 // v_permlane16_swap(x,x): [0] = rows (r0,r0,r2,r2), [1] = rows (r1,r1,r3,r3)
 __device__ __forceinline__ void swap16(double x, double& even, double& odd) {
@@ -229,10 +235,13 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 // value of lane (g, J) of the same 16-lane row (DPP row_newbcast, no LDS)
 template <int J>
 __device__ __forceinline__ double row_bcast(double x) {
-  int lo = __double2loint(x), hi = __double2hiint(x);
-  lo = __builtin_amdgcn_update_dpp(0, lo, 0x150 + J, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, 0x150 + J, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
+  return dpp_mov<0x150 + J>(x);
+}
+// ... in the 16-lane rows of ROWS (a bit per row); the lanes of the other rows keep `keep`: the select rides on the
+// DPP row mask
+template <int J, int ROWS>
+__device__ __forceinline__ double row_bcast_rows(double x, double keep) {
+  return __builtin_amdgcn_update_dpp(keep, x, 0x150 + J, ROWS, 0xF, false);
 }
 // wave-uniform copy of lane l's value (v_readlane -> SGPRs)
 __device__ __forceinline__ double read_lane(double x, int l) {

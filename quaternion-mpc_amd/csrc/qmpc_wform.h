@@ -369,6 +369,20 @@ __device__ __forceinline__ d4 mtm2(const double X[2], const double Y[2], d4 acc)
   acc = __builtin_amdgcn_mfma_f64_16x16x4f64(X[1], Y[1], acc, 0, 0, 0);
   return acc;
 }
+// the initial accumulator of a product of which only fragment rows 0..7 (a, b) or 0..11 (a, b, c) are read afterwards:
+// an element of the accumulator only reaches the same element of the result, so the other elements are left
+// uninitialised ON PURPOSE -- they start from whatever their registers hold and nothing reads what becomes of them
+// (filling them with 0.0 cost two to four v_mov per product; the knot has four such products)
+__device__ __forceinline__ d4 acc_rows(double a, double b) {
+  d4 v;
+  v[0] = a; v[1] = b;
+  return v;
+}
+__device__ __forceinline__ d4 acc_rows(double a, double b, double c) {
+  d4 v;
+  v[0] = a; v[1] = b; v[2] = c;
+  return v;
+}
 // per-lane multipliers of the two column operations (lane c = column c of the fragment)
 struct ColOps {
   double m1c, m2c, keep, hsel;
@@ -443,31 +457,61 @@ struct BwPat {
     }
   }
 };
-// acc += sum_t x[lane 3 + t of the row] * m[t]: three v_fmac_f64 with a DPP source (row_newbcast on src0 of the 64-bit
-// VOP2 form, gfx90a+).  The leading s_nop covers the VALU-write -> DPP-read hazard, which the compiler does not track
-// through inline asm.
-__device__ __forceinline__ double fma_bcast345(double acc, double x, const double m[3]) {
-  asm("s_nop 1\n\t"
-      "v_fmac_f64_dpp %0, %1, %2 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %3 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %4 row_newbcast:5 row_mask:0xf bank_mask:0xf"
-      : "+v"(acc)
-      : "v"(x), "v"(m[0]), "v"(m[1]), "v"(m[2]));
-  return acc;
+// r_i = fma(cs, sh_i, r_i), then r_i += sum_t x_i[lane 3 + t of the row] * m[t] (t = 0, 1, 2 in this order), for two (_x2) or
+// three (_x3) values side by side: v_fmac_f64 with a DPP source (row_newbcast on src0 of the 64-bit VOP2 form, gfx90a+) for the sums.  The
+// compiler does not track the VALU-write -> DPP-read hazard (two wait states) through inline asm; the plain v_fmac_f64
+// of every value lead the block, so that at least two instructions that are no DPP reads stand between whatever wrote
+// an x_i and its first DPP read here -- no s_nop, and the dependent chains of the values interleave.  Each value sees the same
+// operations in the same order as one value alone would.
+__device__ __forceinline__ void fma_bcast345_x2(double r[2], const double x[2], const double sh[2], double cs, const double m[3]) {
+  asm("v_fmac_f64 %0, %4, %5\n\t"
+      "v_fmac_f64 %1, %4, %6\n\t"
+      "v_fmac_f64_dpp %0, %2, %7 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %1, %3, %7 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %2, %8 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %1, %3, %8 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %2, %9 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %1, %3, %9 row_newbcast:5 row_mask:0xf bank_mask:0xf"
+      : "+v"(r[0]), "+v"(r[1])
+      : "v"(x[0]), "v"(x[1]), "v"(cs), "v"(sh[0]), "v"(sh[1]), "v"(m[0]), "v"(m[1]), "v"(m[2]));
+}
+__device__ __forceinline__ void fma_bcast345_x3(double r[3], const double x[3], const double sh[3], double cs, const double m[3]) {
+  asm("v_fmac_f64 %0, %6, %7\n\t"
+      "v_fmac_f64 %1, %6, %8\n\t"
+      "v_fmac_f64 %2, %6, %9\n\t"
+      "v_fmac_f64_dpp %0, %3, %10 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %1, %4, %10 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %2, %5, %10 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %3, %11 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %1, %4, %11 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %2, %5, %11 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %0, %3, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %1, %4, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %2, %5, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf"
+      : "+v"(r[0]), "+v"(r[1]), "+v"(r[2])
+      : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(cs), "v"(sh[0]), "v"(sh[1]), "v"(sh[2]), "v"(m[0]), "v"(m[1]), "v"(m[2]));
 }
 // x M   (columns 0..5 of the result; M = [[m1 I, 0], [0, Wt], [m2 I, 0], [0, h I]]): lane c < 3 takes m1 x[c] + m2 x[c+6],
-// lane 3 + b takes sum_t x[3+t] Wt[t][b] + h x[9+b]; wt[t] = Wt[t][c-3] on lanes 3..5, 0 elsewhere
-__device__ __forceinline__ double times_M(double x, const ColOps& co, const double wt[3]) {
-  double r = co.m1c * x;
-  r = fma(co.m2c, dpp_mov<0x106>(x), r);       // row_shl:6: lane c reads lane c + 6
-  return fma_bcast345(r, x, wt);
+// lane 3 + b takes sum_t x[3+t] Wt[t][b] + h x[9+b]; wt[t] = Wt[t][c-3] on lanes 3..5, 0 elsewhere.  Two fragments at once.
+__device__ __forceinline__ void times_M(const double x[2], const ColOps& co, const double wt[3], double r[2]) {
+  double sh[2];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    r[e] = co.m1c * x[e];
+    sh[e] = dpp_mov<0x106>(x[e]);       // row_shl:6: lane c reads lane c + 6
+  }
+  fma_bcast345_x2(r, x, sh, co.m2c, wt);
 }
 // x Abar_aug  (Abar = [[I,0,hI,0],[0,A1,0,A3],[0,0,I,0],[0,0,0,I]], the gradient column 12 untouched):
-// at[t] = A1[t][c-3] on lanes 3..5, A3[t][c-9] on lanes 9..11, 0 elsewhere
-__device__ __forceinline__ double times_Abar(double x, const ColOps& co, const double at[3]) {
-  double r = co.keep * x;
-  r = fma(co.hsel, dpp_mov<0x116>(x), r);      // row_shr:6: lane c reads lane c - 6
-  return fma_bcast345(r, x, at);
+// at[t] = A1[t][c-3] on lanes 3..5, A3[t][c-9] on lanes 9..11, 0 elsewhere.  Three fragments at once.
+__device__ __forceinline__ void times_Abar(const double x[3], const ColOps& co, const double at[3], double r[3]) {
+  double sh[3];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    r[e] = co.keep * x[e];
+    sh[e] = dpp_mov<0x116>(x[e]);       // row_shr:6: lane c reads lane c - 6
+  }
+  fma_bcast345_x3(r, x, sh, co.hsel, at);
 }
 
 // Two Gauss-Jordan steps at once: the 2 x 2 pivot block B = [[a, b], [b, d]] on rows / columns (J0, J0 + 1), J0 = 0, 2, 4 (both
@@ -482,7 +526,7 @@ __device__ __forceinline__ double times_Abar(double x, const ColOps& co, const d
 // other forms of the step (row broadcast through v_permlane*_swap, v_fmac_f64 with a DPP source: 1.76 M against 1.82 M
 // solves/s) were measured and dropped (profiles/HISTORY_r0N.md).
 template <int J0, bool INV = false>
-__device__ __forceinline__ void gj6_pair_step(double M[2], double Rr[2], int c, int g, bool& pd, double* Iv = nullptr) {
+__device__ __forceinline__ void gj6_pair_step(double M[2], double Rr[2], double pc[2], int c, int g, bool& pd, double* Iv = nullptr) {
   constexpr int ej = J0 >> 2, g0 = J0 & 3, g1 = g0 + 1;
   static_assert((J0 & 1) == 0 && J0 < 6, "pivot pairs (0,1), (2,3), (4,5)");
   const int s0 = (g0 << 4) | c, s1 = (g1 << 4) | c;
@@ -498,13 +542,21 @@ __device__ __forceinline__ void gj6_pair_step(double M[2], double Rr[2], int c, 
   const double ia = a * rd, ib = b * rd, id = d * rd;
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
-    double c0 = row_bcast<J0>(M[e]), c1 = row_bcast<J0 + 1>(M[e]);
+    double c0, c1;
     double bm = M[e], br = Rr[e], bi = INV ? Iv[e] : 0.0;
     if (e == ej) {
+      // the pivot rows take (c0, c1) = e_1, e_2 instead of their own entries: row group g IS the DPP row, so the broadcast
+      // writes the other two rows only and the pivot rows keep what pc[] holds there, (1, 0) on row g0 and (0, 1) on row
+      // g1 (no select follows).  pc[] is carried from step to step: its pivot rows are never written, its other rows
+      // are rewritten by every step, so the broadcast lands in place and nothing is copied first.
       const bool p0 = g == g0, p1 = g == g1;
-      c0 = p0 ? 1.0 : (p1 ? 0.0 : c0);
-      c1 = p1 ? 1.0 : (p0 ? 0.0 : c1);
+      constexpr int others = 0xF & ~((1 << g0) | (1 << g1));
+      c0 = pc[0] = row_bcast_rows<J0, others>(M[e], pc[0]);
+      c1 = pc[1] = row_bcast_rows<J0 + 1, others>(M[e], pc[1]);
       if (p0 || p1) { bm = 0.0; br = 0.0; bi = 0.0; }
+    } else {
+      c0 = row_bcast<J0>(M[e]);
+      c1 = row_bcast<J0 + 1>(M[e]);
     }
     const double f0 = fma(ib, c1, -(id * c0)), f1 = fma(ib, c0, -(ia * c1));
     M[e] = fma(f1, m1, fma(f0, m0, bm));
@@ -548,34 +600,44 @@ __device__ inline int backward_pass_w(const DevParams& P, const Layout& L, const
   }
   bool pd = true;
   const d4 z4 = {0.0, 0.0, 0.0, 0.0};
-  // operands of a knot (independent of the cost-to-go): loaded one knot ahead, right after the first products are issued
+  // unit columns of the pivot rows of gj6_pair_step, by pivot row groups (0, 1) [pivots 0, 1 and 4, 5] and (2, 3)
+  double pc01[2] = {(g == 0) ? 1.0 : 0.0, (g == 1) ? 1.0 : 0.0}, pc23[2] = {(g == 2) ? 1.0 : 0.0, (g == 3) ? 1.0 : 0.0};
+  // operands of a knot (independent of the cost-to-go), each loaded into the registers it is used from, long before the
+  // use and after the last use of the previous knot's: wt / gr (needed by steps 1-4) for the NEXT knot once step 4 has
+  // issued, at / xt (needed by step 8 only) at the head of their own knot.  No second set, no copy at the loop's end.
   struct KnotOps { double wt[3], at[3], gr[2], xt[3]; };
-  auto load_ops = [&](KnotOps& o) {       // the knot the running indices point at; then one knot back
+  auto load_head = [&](KnotOps& o) {       // wt, gr of the knot the running indices point at; then one knot back
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      o.wt[t] = sm[ix_w + 3 * t]; o.at[t] = sm[ix_a + 3 * t]; o.xt[t] = sm[ix_x[t]];
-      ix_x[t] -= bp.st_x[t];
-    }
-    ix_w -= bp.st_w; ix_a -= bp.st_a;
+    for (int t = 0; t < 3; ++t) o.wt[t] = sm[ix_w + 3 * t];
+    ix_w -= bp.st_w;
 #pragma unroll
     for (int e = 0; e < 2; ++e) { o.gr[e] = GK[ix_g[e]]; ix_g[e] -= bp.st_g[e]; }
   };
-  KnotOps ops, opn;
-  load_ops(ops);
+  auto load_tail = [&](KnotOps& o) {       // at, xt likewise
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      o.at[t] = sm[ix_a + 3 * t]; o.xt[t] = sm[ix_x[t]];
+      ix_x[t] -= bp.st_x[t];
+    }
+    ix_a -= bp.st_a;
+  };
+  KnotOps ops;
+  load_head(ops);
   for (int k = N - 1; k >= 0; --k) {
     double wt[3], Mf[3], Nf[2], R6f[2];
     const double* at = ops.at;
-    const double* Gf = ops.gr;
     const double* xt = ops.xt;
+    const double Gf[2] = {ops.gr[0], ops.gr[1]};
 #pragma unroll
     for (int t = 0; t < 3; ++t) wt[t] = wscale * ops.wt[t];
+    load_tail(ops);
     Mf[0] = fma(msel[0], wt[0], Mc[0]);
     Mf[1] = fma(msel[1], wt[1], fma(msel[2], wt[2], Mc[1]));
     Mf[2] = Mc[2];
     Nf[0] = fma(nsel[0], at[0], Nc[0]);
     Nf[1] = fma(nsel[1], at[1], fma(nsel[2], at[2], Nc[1]));
-    R6f[0] = bp.c12 ? ops.gr[0] : 0.0;
-    R6f[1] = bp.c12 ? ops.gr[1] : 0.0;
+    R6f[0] = bp.c12 ? Gf[0] : 0.0;
+    R6f[1] = bp.c12 ? Gf[1] : 0.0;
     tick_dep(prof, PH_BUILD, Pf[0], Pf[1]);
     // ---- 1. Yp = M' [P | p]  (6 x 13) ----
     double Yp[2];
@@ -583,7 +645,6 @@ __device__ inline int backward_pass_w(const DevParams& P, const Layout& L, const
       const d4 a = mtm3(Mf, Pf, z4);
       Yp[0] = a[0]; Yp[1] = a[1];
     }
-    if (k > 0) load_ops(opn);
     if (y0out && bp.c12) {
       if (g < 4) y0out[6 * k + g] = Yp[0];
       if (g < 2) y0out[6 * k + 4 + g] = Yp[1];
@@ -591,19 +652,19 @@ __device__ inline int backward_pass_w(const DevParams& P, const Layout& L, const
     tick_dep(prof, PH_DRAIN, Yp[0], Yp[1]);
     // ---- 2. S6 = Yp_fb M  (column operation) ----
     double S6[2];
-    S6[0] = times_M(Yp[0], co, wt);
-    S6[1] = times_M(Yp[1], co, wt);
+    times_M(Yp, co, wt, S6);
     // ---- 3. C = G Yp + [0 | r6] ;  4. Q = S6 C,  W' = S6 + Q_fb M ----
     double Cf[2], Qf[2], Wm[2];
     {
-      const d4 ini = {R6f[0], R6f[1], 0.0, 0.0};
-      const d4 a = mtm2(Gf, Yp, ini);
+      const d4 a = mtm2(Gf, Yp, acc_rows(R6f[0], R6f[1]));
       Cf[0] = a[0]; Cf[1] = a[1];
       const d4 b = mtm2(S6, Cf, z4);
       Qf[0] = b[0]; Qf[1] = b[1];
     }
-    Wm[0] = S6[0] + times_M(Qf[0], co, wt);
-    Wm[1] = S6[1] + times_M(Qf[1], co, wt);
+    times_M(Qf, co, wt, Wm);
+    Wm[0] = S6[0] + Wm[0];
+    Wm[1] = S6[1] + Wm[1];
+    if (k > 0) load_head(ops);
     tick_dep(prof, PH_MFMA, Wm[0], Wm[1]);
     // ---- 5. W' X = -Q ----
     double Iv[2];
@@ -612,9 +673,9 @@ __device__ inline int backward_pass_w(const DevParams& P, const Layout& L, const
       Iv[1] = (g < 2 && c == 4 + g) ? 1.0 : 0.0;
     }
     double Xf[2];
-    gj6_pair_step<0, REFINE>(Wm, Qf, c, g, pd, Iv);
-    gj6_pair_step<2, REFINE>(Wm, Qf, c, g, pd, Iv);
-    gj6_pair_step<4, REFINE>(Wm, Qf, c, g, pd, Iv);
+    gj6_pair_step<0, REFINE>(Wm, Qf, pc01, c, g, pd, Iv);
+    gj6_pair_step<2, REFINE>(Wm, Qf, pc23, c, g, pd, Iv);
+    gj6_pair_step<4, REFINE>(Wm, Qf, pc01, c, g, pd, Iv);
     Xf[0] = Qf[0];      // (the pivot rows leave the block steps as -B^-1 row: nothing to divide out)
     Xf[1] = rowok1 ? Qf[1] : 0.0;
     if (REFINE) {
@@ -646,23 +707,19 @@ __device__ inline int backward_pass_w(const DevParams& P, const Layout& L, const
     // ---- 6. Pi = [P | p] + Yp_fb' X ;  7. gains [Xz | xz] = Yp + S6 X ----
     double Pi[3];
     {
-      const d4 ini = {Pf[0], Pf[1], Pf[2], 0.0};
-      const d4 a = mtm2(Yp, Xf, ini);
+      const d4 a = mtm2(Yp, Xf, acc_rows(Pf[0], Pf[1], Pf[2]));
       Pi[0] = a[0]; Pi[1] = a[1]; Pi[2] = a[2];
     }
     double Zf[2];
     {
-      const d4 ini = {Yp[0], Yp[1], 0.0, 0.0};
-      const d4 a = mtm2(S6, Xf, ini);
+      const d4 a = mtm2(S6, Xf, acc_rows(Yp[0], Yp[1]));
       Zf[0] = a[0]; Zf[1] = a[1];
     }
     // ---- 8. [P | p]_k = [lxx | lx] + Abar' (Pi Abar_aug) ----
     double Uf[3];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) Uf[e] = times_Abar(Pi[e], co, at);
+    times_Abar(Pi, co, at, Uf);
     {
-      const d4 ini = {Uf[0] + (qadd[0] + xt[0]), Uf[1] + (qadd[1] + xt[1]), Uf[2] + (qadd[2] + xt[2]), 0.0};
-      const d4 a = mtm2(Nf, Uf, ini);
+      const d4 a = mtm2(Nf, Uf, acc_rows(Uf[0] + (qadd[0] + xt[0]), Uf[1] + (qadd[1] + xt[1]), Uf[2] + (qadd[2] + xt[2])));
       Pf[0] = a[0]; Pf[1] = a[1]; Pf[2] = a[2];
     }
     {
@@ -672,7 +729,6 @@ __device__ inline int backward_pass_w(const DevParams& P, const Layout& L, const
         if (kwo[e] >= 0) { KDk[kwo[e]] = Xf[e]; KDk[kwo[e] + 78] = Zf[e]; }
       }
     }
-    ops = opn;
     tick_dep(prof, PH_PUPD, Pf[0], Pf[1]);
   }
   return !pd;

@@ -124,9 +124,9 @@
   double mu = 0.0, resid = 0.0, last_step = resume ? resume[3] : 1e300, last_ap = resume ? resume[1] : 0.0,
          last_ad = resume ? resume[2] : 0.0;
   status = QMPC_MAX_ITER;
+  mu = wave_sum(sl_part) * inv_rows;
+  resid = wave_max(rc_part);
   for (it = it_start; it <= P.iterations_max + 1; ++it) {
-    mu = wave_sum(sl_part) * inv_rows;
-    resid = wave_max(rc_part);
     if (mu <= P.mu_final && resid <= P.tol_feas && last_step <= P.tol_step) { status = QMPC_OK; break; }
     if (it > P.iterations_max) break;
     double sg = P.sigma;
@@ -159,11 +159,19 @@
     for (int i = lane; i < N * NU; i += kWave) sm[L.U + i] += sm[L.dU + i];
     for (int i = lane; i < (N + 1) * 13; i += kWave) sm[L.X + i] = sm[L.Xc + i];
     QSYNC();
-    wrench_from_inputs<false, WNL>(P, L, LW, sm, lane);
+    iters = it;
+    // everything the test at the head of the next pass reads is known here: a pass that ends the solve (converged, or
+    // the cap reached) leaves without the wrenches and expansions at the new iterate, which nothing reads any more
+    mu = wave_sum(sl_part) * inv_rows;
+    resid = wave_max(rc_part);
+    if ((mu <= P.mu_final && resid <= P.tol_feas && last_step <= P.tol_step) || it >= P.iterations_max) continue;
+    // after a shortened step rollout_scaled_w has left the wrenches of U + dU in place: the same numbers as those of the
+    // stored sum (every sum of wrench_from_inputs starts from +0.0, which absorbs a zero of either sign: the u + 0.0
+    // of this form and the u + du of that one cannot give different wrenches)
+    if (!(ap < 1.0)) wrench_from_inputs<false, WNL>(P, L, LW, sm, lane);
     prof.tick(PH_MISC);
     expansions_w<WNL, WMT>(P, L, LW, sm, lane);
     prof.tick(PH_EXPAND);
-    iters = it;
   }
   if (lane < NU) forces[NU * (size_t)b + lane] = sm[L.U + lane];
   if (traj_u) for (int i = lane; i < N * NU; i += kWave) traj_u[(size_t)b * N * NU + i] = sm[L.U + i];
