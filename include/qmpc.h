@@ -299,10 +299,11 @@ enum qmpc_query_what {
   QMPC_QUERY_ZERO_COPY            = 7,  /* 1: host-buffer calls of wave-kernel batches run zero-copy */
   QMPC_QUERY_KERNEL_FOR_INSTANCES = 8,  /* arg = batch: the qmpc_kernel_family qmpc_solve_instances* launches for that size
                                            (QMPC_KERNEL_NONE: the handle refuses the call) */
-  QMPC_QUERY_LOOP_INSTANCES_PLAN  = 9   /* arg = batch (bits 0-31) | 1 << 32 with controller records | 1 << 33 with
+  QMPC_QUERY_LOOP_INSTANCES_PLAN  = 9,  /* arg = batch (bits 0-31) | 1 << 32 with controller records | 1 << 33 with
                                            lp->warm_start: the launch qmpc_loop_run_instances* takes, 16 * form + family --
                                            form 1 the persistent kernel, 2 the per-tick sequence; family the
                                            qmpc_kernel_family of its solve.  0: the call is refused */
+  QMPC_QUERY_INSTANCES_POLICY     = 10  /* the handle's policy for qmpc_solve_instances*, a qmpc_instances_policy value */
 };
 enum qmpc_kernel_family {
   QMPC_KERNEL_NONE         = 0,
@@ -330,11 +331,25 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
  *
  * Kernel: the wave-per-instance wrench-form kernel a plain solve of the same size takes (everything in LDS, or the
  * workspace form), with its parameters read per workgroup; where the plain solve takes that kernel too, results are
- * bit-identical to qmpc_solve on a handle carrying the same values.  There is NO lane-per-instance form: batches at and
- * above the lane kernel's switch-over (14336 at N <= 12) stay on the wave workspace form (3.6 M solves/s at N=10 where
- * the lane kernel does 7-9 M), and agree with the plain solve there to ~1e-10 N (another rounding family).  Not covered either: the
- * reference mode, ConvexMpc, the 8-point model, warm starts.  The closed loop has its own entry points with these records:
- * qmpc_loop_run_instances* below.
+ * bit-identical to qmpc_solve on a handle carrying the same values.  By default (QMPC_INSTANCES_WAVE) that holds at every
+ * size: batches at and above the lane kernel's switch-over (14336 at N <= 12) stay on the wave workspace form (3.6 M
+ * solves/s at N=10), and agree with the plain solve there to ~1e-10 N (another rounding family).
+ *
+ * The lane-per-instance form is chosen per handle: qmpc_set_instances_policy(h, QMPC_INSTANCES_AUTO).  From the measured
+ * switch-over on (16384 instances at every horizon; the knob QMPC_LANE_INST_MIN overrides it) the call then runs
+ * qmpc_lane_inst_kernel -- the plain lane kernel's passes with the seven record fields read per LANE from a parameter block
+ * laid out like the lane workspace -- to the plain solve's iteration cap, and the per-instance list kernel continues the
+ * stragglers (QMPC_KERNEL_LANE_HANDOFF; QMPC_KERNEL_LANE without status records or hand-off).  Below the switch-over AUTO
+ * is the wave form above.  AUTO results belong to the lane / hand-off rounding family: ~1e-10 N from the wave family's, and
+ * bit-identical to qmpc_solve's lane / hand-off results on a handle carrying the same values (forces, info, trajectories;
+ * DESIGN.md section 3k).  Measured at N=10, random records: 6.2 M solves/s at 32768 and 7.2 M at 65536 instances, where the
+ * wave form does 3.8 M and the plain solve 7.0 / 8.8 M.  Memory: the lane workspace and the
+ * hand-off records of plain solves (qmpc_prepare) plus 312 B per resident lane of parameter rows; under AUTO
+ * qmpc_prepare_instances and qmpc_prepare allocate them, under WAVE they allocate what they always did.  A handle that
+ * refuses the call under WAVE refuses it under AUTO.
+ *
+ * Not covered: the reference mode, ConvexMpc, the 8-point model, warm starts.  The closed loop has its own entry points
+ * with these records, qmpc_loop_run_instances* below; with controller records it keeps the wave form under either policy.
  *
  * The handle's per-instance buffers (the records and one expanded parameter block per instance, about 760 B x max_batch)
  * are allocated on first use, or now by qmpc_prepare_instances (e.g. before a stream capture). */
@@ -361,8 +376,16 @@ qmpc_status qmpc_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_input
 qmpc_status qmpc_solve_instances_device(qmpc_handle* h, int32_t batch, const qmpc_input* d_in,
                                         const qmpc_instance_params* d_iparams, double* d_forces_body,
                                         qmpc_info* d_info, void* stream);
-/* allocate the per-instance buffers now (qmpc_prepare does not) */
+/* allocate the per-instance buffers now (qmpc_prepare does not); under QMPC_INSTANCES_AUTO also the lane kernel's */
 qmpc_status qmpc_prepare_instances(qmpc_handle* h);
+/* Which kernel family qmpc_solve_instances* may take on this handle; holds until it is changed.  QMPC_BAD_ARGUMENT for a
+ * null handle or an unknown value.  qmpc_query(QMPC_QUERY_KERNEL_FOR_INSTANCES / QMPC_QUERY_LAST_KERNEL) answer under the
+ * current policy. */
+typedef enum qmpc_instances_policy {
+  QMPC_INSTANCES_WAVE = 0,   /* default: the wave wrench-form kernels at every size */
+  QMPC_INSTANCES_AUTO = 1    /* lane per instance (with the straggler hand-off) from the measured switch-over on */
+} qmpc_instances_policy;
+qmpc_status qmpc_set_instances_policy(qmpc_handle* h, int32_t policy);
 
 /* Multi-GPU: the single collective of the path.  All-gathers `count` doubles per rank (e.g. the
  * [B/G][12] force block, or forces + qmpc_info records laid out in one buffer) from every rank's `d_local` into

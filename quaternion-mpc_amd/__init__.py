@@ -318,6 +318,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_instances_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, vp]
     lib.qmpc_loop_run_instances_device.restype = i32
     lib.qmpc_prepare_instances.restype = i32
+    lib.qmpc_set_instances_policy.argtypes = [vp, i32]
+    lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_gather.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.qmpc_gather.restype = i32
     lib.qmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -472,11 +474,16 @@ EXPORTED_SYMBOLS = (
     "qmpc_sizeof_plant_params",
     "qmpc_loop_run_instances",
     "qmpc_loop_run_instances_device",
+    "qmpc_set_instances_policy",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
 QUERY_HANDOFF_ACTIVE, QUERY_HANDOFF_ALLOC_FAILED, QUERY_KERNEL_FOR_BATCH, QUERY_LAST_KERNEL, QUERY_LANE_CAP, \
     QUERY_DEVICE_BYTES, QUERY_ZERO_COPY, QUERY_KERNEL_FOR_INSTANCES, QUERY_LOOP_INSTANCES_PLAN = 1, 2, 3, 4, 5, 6, 7, 8, 9
+QUERY_INSTANCES_POLICY = 10
+# enum qmpc_instances_policy
+INSTANCES_WAVE, INSTANCES_AUTO = 0, 1
+INSTANCES_POLICY = {"wave": INSTANCES_WAVE, "auto": INSTANCES_AUTO}
 KERNEL_FAMILY = {0: "none", 1: "wform_lds", 2: "wform_ws", 3: "dense_lds", 4: "dense_ws", 5: "lane", 6: "lane_handoff"}
 
 
@@ -753,6 +760,18 @@ class Solver:
 
     def kernel_for_instances(self, batch: int) -> str:
         return KERNEL_FAMILY[self.query(QUERY_KERNEL_FOR_INSTANCES, batch)]
+
+    def set_instances_policy(self, policy: str | int):
+        """Which kernel family solve_instances* may take on this handle (qmpc_set_instances_policy): "wave" (default: the wave
+        wrench-form kernels at every size) or "auto" (lane per instance with the straggler hand-off from the measured
+        switch-over on)."""
+        value = INSTANCES_POLICY[policy] if isinstance(policy, str) else int(policy)
+        st = self.lib.qmpc_set_instances_policy(self._h, value)
+        if st != OK:
+            raise QmpcError(st, "qmpc_set_instances_policy")
+
+    def instances_policy(self) -> str:
+        return {v: k for k, v in INSTANCES_POLICY.items()}[self.query(QUERY_INSTANCES_POLICY)]
 
     def prepare_instances(self):
         """Allocate the per-instance buffers now (qmpc_prepare_instances)."""

@@ -92,6 +92,18 @@ hipError_t qmpc_lane_launch(int nl, int pslot, int batch, hipStream_t s, const v
                             int* hcount, int* hsel, double* hstate, int hcap, int pair);
 size_t qmpc_lane_handoff_list_bytes(int batch);
 size_t qmpc_lane_handoff_record_doubles(int N);
+hipError_t qmpc_lane_sort_launch(int batch, hipStream_t s, const void* in, int* scratch);
+
+// qmpc_lane_inst.hip / qmpc_wform_inst_list.hip: per-instance parameters on the lane kernel and its hand-off (QMPC_INSTANCES_AUTO)
+size_t qmpc_lane_inst_param_bytes(unsigned slots);
+hipError_t qmpc_lane_inst_launch(int pslot, int batch, hipStream_t s, const void* dev_params, size_t dev_params_size, const void* in,
+                                 const void* dev_blocks, const int* status, double* forces, qmpc_info* info, double* ws, double* prm,
+                                 unsigned slots, const int* perm, double* traj_u, double* traj_x, int iter_cap, int* hcount, int* hsel,
+                                 double* hstate, int hcap, int pair);
+hipError_t qmpc_wform_inst_list_set_lds();
+hipError_t qmpc_wform_inst_list_launch(int var, int grid, size_t lds, hipStream_t s, const void* dev_blocks, const qmpc_input* in,
+                                       double* forces, qmpc_info* info, double* traj_u, double* traj_x, const int* sel,
+                                       const int* sel_count, double* gws, const double* hstate, int hcap);
 
 struct qmpc_handle {
   qmpc_params params;
@@ -136,6 +148,8 @@ struct qmpc_handle {
                                // not refilled before the stream has drained (qmpc_solve_async with a pageable `in`, pinned outputs)
   unsigned char* d_inst;       // per-instance parameters (qmpc_solve_instances*), on first use: [max_batch] DevParams | [max_batch]
                                // qmpc_instance_params (staging of the host-buffer call) | [max_batch] int verdicts
+  int inst_policy;             // qmpc_instances_policy of qmpc_solve_instances* (qmpc_set_instances_policy; default WAVE)
+  double* d_lane_prm;          // ... under AUTO: the resident wavefronts' parameter blocks [LPR_ROWS][lane_slots], on first use
   unsigned char* d_plant;      // per-robot plants of qmpc_loop_run_instances*, on first use: [max_batch] PlantDev | [max_batch]
                                // qmpc_plant_params (staging of the host-buffer call)
 };
@@ -292,6 +306,7 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   HIP_TRY(qmpc_loop_fused_set_lds());
   HIP_TRY(qmpc_wform_set_lds());
   HIP_TRY(qmpc_loop_inst_set_lds());
+  HIP_TRY(qmpc_wform_inst_list_set_lds());
   HIP_TRY(hipMalloc(&h->d_gws, sizeof(double) * (size_t)N * (13 * nu + 21 * nl + 30 * nl) * (size_t)max_batch));
   return QMPC_OK;
 }
@@ -355,6 +370,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_A) (void)hipFree(h->d_A);
   if (h->d_B) (void)hipFree(h->d_B);
   if (h->d_inst) (void)hipFree(h->d_inst);
+  if (h->d_lane_prm) (void)hipFree(h->d_lane_prm);
   if (h->d_plant) (void)hipFree(h->d_plant);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -751,6 +767,8 @@ static bool handoff_active(const qmpc_handle* h) {
 // hand-off records, the pinned staging of the host-buffer calls.  Afterwards no solve of up to `batch` instances allocates
 // (safe inside the caller's own stream capture) and qmpc_query(QMPC_QUERY_HANDOFF_ACTIVE) says which family of roundings
 // the handle's large-batch results belong to.
+static qmpc_status ensure_instance_buffers(qmpc_handle* h);
+static qmpc_status ensure_lane_inst_buffers(qmpc_handle* h, bool handoff);
 qmpc_status qmpc_prepare(qmpc_handle* h, int32_t batch) {
   if (!h || batch < 1) return QMPC_BAD_ARGUMENT;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
@@ -762,6 +780,12 @@ qmpc_status qmpc_prepare(qmpc_handle* h, int32_t batch) {
     const qmpc_status es = ensure_lane_buffers(h);
     if (es != QMPC_OK) return es;
     if (handoff_active(h)) (void)ensure_handoff_buffers(h);
+  }
+  // ... and for qmpc_solve_instances* of this size under QMPC_INSTANCES_AUTO, with the per-instance buffers
+  if (h->inst_policy == QMPC_INSTANCES_AUTO && plan_instances(h->sel, batch, h->inst_policy, true, h->handoff_failed).variant == 4) {
+    qmpc_status es = ensure_instance_buffers(h);
+    if (es == QMPC_OK) es = ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_PLAIN, h->handoff_failed) != 0);
+    if (es != QMPC_OK) return es;
   }
   // the pinned staging of the host-buffer calls: ALWAYS (a handle prepared for a lane-kernel batch may still be handed a smaller
   // batch on host buffers, which runs zero-copy), and the buffers the closed loops and the trajectory / warm-started calls
@@ -828,14 +852,46 @@ static qmpc_status instances_check(const qmpc_handle* h, int32_t batch) {
   return QMPC_OK;
 }
 
+// the lane kernel's buffers for per-instance records (QMPC_INSTANCES_AUTO): the plain lane kernel's workspace and sort scratch,
+// the parameter blocks of the resident wavefronts and, where the handle hands stragglers over, the hand-off records
+static qmpc_status ensure_lane_inst_buffers(qmpc_handle* h, bool handoff) {
+  const qmpc_status es = ensure_lane_buffers(h);
+  if (es != QMPC_OK) return es;
+  if (!h->d_lane_prm) HIP_TRY(hipMalloc(&h->d_lane_prm, qmpc_lane_inst_param_bytes(h->lane_slots)));
+  if (handoff) (void)ensure_handoff_buffers(h);
+  return QMPC_OK;
+}
+// some batch of the handle takes the lane kernel in qmpc_solve_instances* under its current policy
+static bool instances_lane_possible(const qmpc_handle* h) {
+  return plan_instances(h->sel, h->max_batch, h->inst_policy, true, h->handoff_failed).variant == 4;
+}
+
 // expansion kernel + solve kernel on stream s; d_rec: the records in device-addressable memory
 static qmpc_status launch_instances(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_rec,
                                     double* d_forces, qmpc_info* d_info, double* d_tu, double* d_tx, hipStream_t s) {
-  const qmpc_plan p = plan_instances(h->sel, batch);
+  qmpc_plan p = plan_instances(h->sel, batch, h->inst_policy, d_info != nullptr, h->handoff_failed);
   const qmpc_status es = ensure_instance_buffers(h);
   if (es != QMPC_OK) return es;
+  if (p.variant == 4) {
+    const qmpc_status ls = ensure_lane_inst_buffers(h, false);
+    if (ls != QMPC_OK) return ls;
+    // (the hand-off records are allocated on first use; without them the pure lane kernel)
+    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan_instances(h->sel, batch, h->inst_policy, true, h->handoff_failed);
+  }
   HIP_TRY(hipEventRecord(h->ev0, s));
   HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_rec, inst_dev(h), inst_status(h)));
+  if (p.variant == 4) {      // expansion, stance sort, the capped lane kernel, the per-instance list kernel: stream-ordered
+    const bool cap = p.iter_cap > 0;
+    if (h->sel.lane_sort) HIP_TRY(qmpc_lane_sort_launch((int)batch, s, d_in, h->d_lane_scratch));
+    HIP_TRY(qmpc_lane_inst_launch(h->lane_pslot, (int)batch, s, &h->dev, sizeof h->dev, d_in, inst_dev(h), inst_status(h), d_forces, d_info,
+                                  h->d_lane_ws, h->d_lane_prm, h->lane_slots, h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr, d_tu, d_tx,
+                                  p.iter_cap, cap ? h->d_handoff : nullptr, cap ? h->d_handoff + 64 : nullptr, cap ? h->d_hstate : nullptr,
+                                  h->hstate_cap, h->sel.lane_pair));
+    if (cap)
+      HIP_TRY(qmpc_wform_inst_list_launch(p.handoff_variant, p.handoff_grid, p.lds, s, inst_dev(h), d_in, d_forces, d_info, d_tu, d_tx,
+                                          h->d_handoff + 64, h->d_handoff, p.gws ? h->d_gws : nullptr,
+                                          h->sel.handoff_restart ? nullptr : h->d_hstate, h->hstate_cap));
+  } else
   HIP_TRY(qmpc_wform_inst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, d_forces, d_info, d_tu, d_tx,
                                        p.gws ? h->d_gws : nullptr));
   h->last_kernel = p.family;
@@ -888,7 +944,15 @@ qmpc_status qmpc_prepare_instances(qmpc_handle* h) {
   const qmpc_status cs = instances_check(h, 0);
   if (cs != QMPC_OK) return cs;
   HIP_TRY(hipSetDevice(h->device));
-  return ensure_instance_buffers(h);
+  const qmpc_status es = ensure_instance_buffers(h);
+  if (es != QMPC_OK || !instances_lane_possible(h)) return es;
+  return ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_PLAIN, h->handoff_failed) != 0);
+}
+
+qmpc_status qmpc_set_instances_policy(qmpc_handle* h, int32_t policy) {
+  if (!h || (policy != QMPC_INSTANCES_WAVE && policy != QMPC_INSTANCES_AUTO)) return QMPC_BAD_ARGUMENT;
+  h->inst_policy = policy;
+  return QMPC_OK;
 }
 
 qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value) {
@@ -916,6 +980,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_traj_x) b += sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch;
       if (h->d_A) b += 2 * sizeof(double) * 144 * N * (size_t)h->max_batch;
       if (h->d_inst) b += instance_bytes(h->max_batch);
+      if (h->d_lane_prm) b += qmpc_lane_inst_param_bytes(h->lane_slots);
       if (h->d_plant) b += plant_bytes(h->max_batch);
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
@@ -924,8 +989,9 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
     case QMPC_QUERY_ZERO_COPY: *value = h->zero_copy; return QMPC_OK;
     case QMPC_QUERY_KERNEL_FOR_INSTANCES:
       if (arg < 1 || arg > h->max_batch) return QMPC_BAD_ARGUMENT;
-      *value = plan_instances(h->sel, (int)arg).family;
+      *value = plan_instances(h->sel, (int)arg, h->inst_policy, true, h->handoff_failed).family;
       return QMPC_OK;
+    case QMPC_QUERY_INSTANCES_POLICY: *value = h->inst_policy; return QMPC_OK;
     case QMPC_QUERY_LOOP_INSTANCES_PLAN: {
       const int64_t b = arg & 0xffffffffLL;
       if (b < 1 || b > h->max_batch) return QMPC_BAD_ARGUMENT;

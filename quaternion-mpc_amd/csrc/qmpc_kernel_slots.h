@@ -84,4 +84,9 @@ static inline int wform_slot(int model, bool ref, int var, bool one_wave) {
 constexpr int kWformListSlots = 2;
 static inline int wform_list_slot(int var) { return var == 3 || var == 5 ? wform_index(var) : -1; }
 
+// ---- qmpc_wform_inst_list.hip -------------------------------------------------------------------------------------------
+// qmpc_solve_w_list_inst_kernel<WVAR> (the hand-off of qmpc_solve_instances* on the lane kernel): 3 5
+constexpr int kWformListInstSlots = 2;
+static inline int wform_list_inst_slot(int var) { return wform_list_slot(var); }
+
 }  // namespace qmpc

@@ -17,7 +17,8 @@
 //
 // Calls served: qmpc_solve* / qmpc_solve8* / qmpc_convex_solve* (with or without trajectory outputs), qmpc_solve_warm* and
 // the per-tick form of the device-resident closed loop (cold or warm-started), converged mode, from the switch-over batch
-// size of qmpc_hip.hip on.
+// size of qmpc_hip.hip on.  qmpc_solve_instances* under QMPC_INSTANCES_AUTO: the same kernel body with per-lane parameters,
+// qmpc_lane_inst.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -30,8 +31,10 @@
 // kernels and the launcher (qmpc_lane.hip itself, scheduling strategy max-ilp: +3 % for the pair forms, nothing for the plain
 // ones) -- and QL_UNIT 2 -- the reference mode's kernel with its own launcher (qmpc_lane_ref.hip includes this file; the default
 // strategy: max-ilp costs that kernel 5-8 %, profiles/HISTORY_r06.md).
-#if !defined(QL_UNIT) || (QL_UNIT != 1 && QL_UNIT != 2)
-#error "QL_UNIT must be 1 (the converged mode's unit) or 2 (the reference mode's unit)"
+// QL_UNIT 3 (qmpc_lane_inst.hip includes this file): the converged mode's kernel with per-lane robot and cost parameters
+// (qmpc_solve_instances* under QMPC_INSTANCES_AUTO) -- what it shares with the two units above is the text up to the kernels.
+#if !defined(QL_UNIT) || (QL_UNIT != 1 && QL_UNIT != 2 && QL_UNIT != 3)
+#error "QL_UNIT must be 1 (the converged mode's unit), 2 (the reference mode's unit) or 3 (per-lane parameters)"
 #endif
 namespace qmpc {
 namespace lane {
@@ -718,6 +721,18 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_launch(int nl, int ps
     }
   }
 #endif
+  return hipGetLastError();
+}
+// the counting sort alone, for the four-point records of qmpc_lane_inst_kernel's launches (qmpc_lane_inst.hip): the
+// permutation is left at scratch + 512
+__attribute__((visibility("hidden"))) hipError_t qmpc_lane_sort_launch(int batch, hipStream_t s, const void* in, int* scratch) {
+  const double* rec = static_cast<const double*>(in);
+  const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(int) * 512, s);
+  if (e != hipSuccess) return e;
+  const unsigned blocks = (unsigned)((batch + 255) / 256);
+  hipLaunchKernelGGL(qmpc_lane_sort_count<4>, dim3(blocks), dim3(256), 0, s, rec, batch, scratch, LDim<4>::R_CON, (const qmpc_info*)nullptr);
+  hipLaunchKernelGGL(qmpc_lane_sort_scan, dim3(1), dim3(64), 0, s, scratch);
+  hipLaunchKernelGGL(qmpc_lane_sort_scatter<4>, dim3(blocks), dim3(256), 0, s, rec, batch, scratch, LDim<4>::R_CON, (const qmpc_info*)nullptr);
   return hipGetLastError();
 }
 #endif      // QL_UNIT == 1

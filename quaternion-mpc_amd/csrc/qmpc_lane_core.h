@@ -265,6 +265,74 @@ struct Ctx {
   }
 };
 
+// ---- the source of the INSTANCE fields of the parameters (template parameter PT of the passes) -------------------------------
+// DevParams itself: every field is wave-uniform and read from the handle's block with scalar loads (plain solves).
+// LaneParams (qmpc_solve_instances* on the lane kernel, qmpc_lane_inst.hip): the 39 doubles that a per-instance record sets --
+// mass, 1 / mass, Iinv, Q, R, w, mu, fz_max -- are THE LANE'S OWN, kept as rows of a parameter block laid out [element][lane]
+// like the workspace (the set-up writes them once from the instance's expanded block; a pass reads a value where it uses it, one
+// coalesced 512-byte row per wave instruction, and holds none of them in a register across a knot).  Everything else -- the
+// horizon, which is the trip count of every sweep, the time steps, the tolerances and the interior-point settings -- stays the
+// handle's and keeps coming from the uniform block.  The members carry DevParams' names, so the passes are ONE text.
+enum { LPR_MASS = 0, LPR_INV_MASS = 1, LPR_IINV = 2, LPR_Q = 11, LPR_R = 24, LPR_W = 36, LPR_MU = 37, LPR_FZ_MAX = 38, LPR_ROWS = 39 };
+struct LaneVal {      // a per-lane value (ql_uniform() must not broadcast it)
+  double v;
+  QL_FN operator double() const { return v; }
+};
+struct LaneRows {     // rows e0 .. of the parameter block, this lane's column
+  QL_GLOBAL_AS const double* base;
+  unsigned wrow;
+  mutable unsigned woff;
+  int e0;
+  QL_FN LaneVal operator[](int i) const {
+    const LaneVal r = {*reinterpret_cast<QL_GLOBAL_AS const double*>(reinterpret_cast<QL_GLOBAL_AS const char*>(base) + ((unsigned)(e0 + i) * wrow + woff))};
+    return r;
+  }
+};
+struct LaneRow {      // one row
+  LaneRows r;
+  QL_FN operator double() const { return r[0]; }
+};
+struct LaneParams {
+  const int& N;
+  const int& mode;
+  const int& iterations_max;
+  const int& drop_ang_vel;
+  const double &h, &hh, &h_ref;
+  const double &tol_feas, &tol_step, &mu0, &mu_final, &sigma, &sigma_fast, &tau;
+  LaneRow mass, inv_mass;
+  LaneRows Iinv, Q, R;
+  LaneRow w, mu, fz_max;
+  // U: the handle's block; prm: this wavefront's parameter block; wrow / woff: as Ctx's
+  QL_FN LaneParams(const DevParams& U, QL_GLOBAL_AS const double* prm, unsigned wrow, unsigned woff)
+      : N(U.N), mode(U.mode), iterations_max(U.iterations_max), drop_ang_vel(U.drop_ang_vel), h(U.h), hh(U.hh), h_ref(U.h_ref),
+        tol_feas(U.tol_feas), tol_step(U.tol_step), mu0(U.mu0), mu_final(U.mu_final), sigma(U.sigma), sigma_fast(U.sigma_fast),
+        tau(U.tau), mass{{prm, wrow, woff, LPR_MASS}}, inv_mass{{prm, wrow, woff, LPR_INV_MASS}}, Iinv{prm, wrow, woff, LPR_IINV},
+        Q{prm, wrow, woff, LPR_Q}, R{prm, wrow, woff, LPR_R}, w{{prm, wrow, woff, LPR_W}}, mu{{prm, wrow, woff, LPR_MU}},
+        fz_max{{prm, wrow, woff, LPR_FZ_MAX}} {}
+  LaneParams(const LaneParams&) = delete;
+  QL_FN void relane(unsigned o) const {
+    mass.r.woff = o; inv_mass.r.woff = o; Iinv.woff = o; Q.woff = o; R.woff = o; w.r.woff = o; mu.r.woff = o; fz_max.r.woff = o;
+  }
+};
+// the instance fields of the lane's expanded block d (apply_instance_params) -> its column of the parameter block
+QL_FN void lane_params_store(const DevParams& d, QL_GLOBAL_AS double* prm, unsigned wrow, unsigned woff) {
+  auto row = [&](int e) -> QL_GLOBAL_AS double& {
+    return *reinterpret_cast<QL_GLOBAL_AS double*>(reinterpret_cast<QL_GLOBAL_AS char*>(prm) + ((unsigned)e * wrow + woff));
+  };
+  row(LPR_MASS) = d.mass;
+  row(LPR_INV_MASS) = d.inv_mass;
+  for (int i = 0; i < 9; ++i) row(LPR_IINV + i) = d.Iinv[i];
+  for (int i = 0; i < 13; ++i) row(LPR_Q + i) = d.Q[i];
+  for (int i = 0; i < 12; ++i) row(LPR_R + i) = d.R[i];
+  row(LPR_W) = d.w;
+  row(LPR_MU) = d.mu;
+  row(LPR_FZ_MAX) = d.fz_max;
+}
+QL_FN double ql_uniform(LaneVal x) { return x.v; }
+// after Ctx::relane(): the parameter rows are addressed through the recomputed offset too (nothing to do for the uniform block)
+QL_FN void ql_relane(const DevParams&, const Ctx&) {}
+QL_FN void ql_relane(const LaneParams& P, const Ctx& c) { P.relane(c.woff); }
+
 // optional phase-level cycle accounting (diagnostic builds: -DQL_PROFILE, __graft_entry__.build_hip(profile_lane=True))
 enum { LP_A = 0, LP_B_HEAD, LP_B_LEGS, LP_B_EXPAND, LP_B_MP, LP_B_CONGR, LP_B_FACT, LP_B_UPD, LP_B_GAIN, LP_C_HEAD, LP_C_LEGS,
        LP_C_STEP, LP_COUNT };
@@ -430,7 +498,8 @@ QL_FN void omega_mul(const double* w, const double* v, double* o) {
 }
 
 // Bw0_l = Iinv skew(r_l) (AltroUtils.cpp:431-434) for a stance contact point
-QL_FN void leg_bw0(const DevParams& P, const double r[3], double B[9]) {
+template <class PT>
+QL_FN void leg_bw0(const PT& P, const double r[3], double B[9]) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const double i0 = P.Iinv[3 * a], i1 = P.Iinv[3 * a + 1], i2 = P.Iinv[3 * a + 2];
@@ -441,7 +510,8 @@ QL_FN void leg_bw0(const DevParams& P, const double r[3], double B[9]) {
 }
 
 // explicit midpoint step (AltroUtils.cpp:9-22 on :363-392) given the force sum F and the angular acceleration wd
-QL_FN void srbd_step_fw(const DevParams& P, const double gb[3], const double* x, const double F[3], const double wd[3],
+template <class PT>
+QL_FN void srbd_step_fw(const PT& P, const double gb[3], const double* x, const double F[3], const double wd[3],
                         double* xn) {
   double vd[3];
 #pragma unroll
@@ -567,7 +637,8 @@ QL_FN void cv_expansion(const DevParams& P, const double* x, const double tau[3]
 }
 
 // reference state of knot k (QuatMpc.cpp:148-176) from refp = pos(3) vel(3) acc(3) quat_d(4)
-QL_FN void xref_at(const DevParams& P, const double rp[13], int k, double* xr) {
+template <class PT>
+QL_FN void xref_at(const PT& P, const double rp[13], int k, double* xr) {
   const double t = (double)k * P.h_ref;
   const double h_ms = P.h_ref * 1000.0;
   xr[0] = rp[0] + rp[3] * k * h_ms / 1000.0 + 0.5 * rp[6] * t * t;
@@ -579,7 +650,8 @@ QL_FN void xref_at(const DevParams& P, const double rp[13], int k, double* xr) {
 }
 
 // cone rows a_i' = (C_mat R)_i  (QuatMpc.cpp:47-52,203): (1,0,-mu),(-1,0,-mu),(0,1,-mu),(0,-1,-mu),(0,0,1),(0,0,-1) times R
-QL_FN void cone_rows(const DevParams& P, const double rot[9], double cr[18]) {
+template <class PT>
+QL_FN void cone_rows(const PT& P, const double rot[9], double cr[18]) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const double m = P.mu * rot[6 + a];
@@ -592,7 +664,8 @@ QL_FN void cone_rows(const DevParams& P, const double rot[9], double cr[18]) {
   }
 }
 // slack residual of row i at the initial guess u = u_ref (the same at every knot and stance point): c0 + max(-c0, 1)
-QL_FN void initial_rows(const DevParams& P, const double cr[18], double uz, double s0[6], double rc0[6]) {
+template <class PT>
+QL_FN void initial_rows(const PT& P, const double cr[18], double uz, double s0[6], double rc0[6]) {
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
     double c0 = cr[3 * i + 2] * uz;
@@ -615,7 +688,8 @@ struct LegBlk {
 // Rw: the point's three input weights when the CALLER has them (the pair forms, where the point index differs between the
 // partner lanes: indexing P.R per lane is a vector load -- in flight together with the prefetches, and waiting for it is waiting
 // for them); null: P.R[3 (l mod 4) ..] with a wave-uniform l (scalar loads)
-QL_FN void leg_block(const DevParams& P, const double cr[18], const double rc0[6], int l, const double sv[6],
+template <class PT>
+QL_FN void leg_block(const PT& P, const double cr[18], const double rc0[6], int l, const double sv[6],
                      const double lv[6], unsigned kap, double rho, double target, const double u[3], double uz, LegBlk& o,
                      const double* Rw = nullptr) {
   double w[6], gi[6];
@@ -790,8 +864,8 @@ QL_FN int next_bit(unsigned m, int l) {
 // knot (O.RC) for EVERY lane of the launch.  u_prev: this instance's previous inputs [N][3 NL] or null (cold start of
 // this instance).  The warm guess is the rule of qmpc_solve_body.inc: the previous solution shifted by one knot (the last
 // knot repeats), swing points pinned to 0, a component that was 0 (the point has just landed) starts from u_ref.
-template <int NL, int MD = MD_QUAT>
-QL_FN void lane_setup(const DevParams& P, const Ctx& c, const WsOff& O, const double* rec, LaneK<NL>& K, LaneState& st,
+template <int NL, int MD = MD_QUAT, class PT>
+QL_FN void lane_setup(const PT& P, const Ctx& c, const WsOff& O, const double* rec, LaneK<NL>& K, LaneState& st,
                       bool warm_launch = false, const double* u_prev = nullptr) {
   typedef LDim<NL> D;
   const int N = P.N;
@@ -939,8 +1013,8 @@ QL_FN void lane_setup(const DevParams& P, const Ctx& c, const WsOff& O, const do
 // accumulated in the same order here: the sum of s * lambda is a chain of fused multiply-adds that runs over the lower lane's
 // six rows, crosses to the upper lane (v_permlane32_swap), runs over its six rows and crosses back; force and torque sums
 // take the two shares as (acc + first) + second.  A pair-mode launch returns the bits of a plain one.
-template <int NL, bool WARM = false, int MD = MD_QUAT, bool PAIR = false>
-QL_FN void pass_A(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, LaneState& st, bool first_in, FootPtr fp) {
+template <int NL, bool WARM = false, int MD = MD_QUAT, bool PAIR = false, class PT>
+QL_FN void pass_A(const PT& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, LaneState& st, bool first_in, FootPtr fp) {
   static_assert(!PAIR || (MD != MD_CONVEX && NL == 4), "pair split: the four-point quaternion model");
   constexpr bool warm = WARM;
 #if QL_DEVICE
@@ -1210,8 +1284,8 @@ QL_FN void pass_A(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
 //   6. stage cost of knot k (the state is re-read: keeping its expansion live through 3-5 would cost 18 registers)
 // The order keeps at most P (90) + Y (78) + Z, S6 (42) + a dozen temporaries live -- the 512-register budget of a
 // wave that owns its SIMD.  Returns false when S6 loses positive definiteness (QMPC_NOT_PD).
-template <int NL, int MD = MD_QUAT>
-QL_FN void cost_expansion(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, int k, double lx[12],
+template <int NL, int MD = MD_QUAT, class PT>
+QL_FN void cost_expansion(const PT& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, int k, double lx[12],
                           double lxx[6], const double* xpre = nullptr) {
   double x[13];
 #pragma unroll
@@ -1280,8 +1354,8 @@ struct LaneAL {
 // PAIR (lane pairs, see Ctx and pass_C): the stance points of the wavefront, in ascending order, are taken two at a time -- the
 // first of a round by the lower partner lane, the second by the upper -- and each lane's contribution to wd, r6 and G (30
 // doubles) reaches both partners through v_permlane32_swap, added in the plain form's order (first point, then second).
-template <int NL, bool WARM = false, int MD = MD_QUAT, bool AL = false, bool PAIR = false>
-QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const LaneK<NL>& K, LaneState& st, FootPtr fp,
+template <int NL, bool WARM = false, int MD = MD_QUAT, bool AL = false, bool PAIR = false, class PT>
+QL_FN bool pass_B(const PT& P, const Ctx& c_in, const WsOff& O, const LaneK<NL>& K, LaneState& st, FootPtr fp,
                   LaneAL* al = nullptr) {
   static_assert(!PAIR || (MD != MD_CONVEX && NL == 4), "pair split: the four-point quaternion model");
   Ctx c = c_in;
@@ -1351,6 +1425,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
   for (int k = N - 1; k >= 0; --k) {
     QL_FENCE();
     c.relane();
+    ql_relane(P, c);
     QL_TICK(st, LP_B_HEAD);
     if constexpr (kXStage) {
       c.template stage<8>(O.X + 13 * k, 0);
@@ -1404,6 +1479,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
         if (2 * (rd + 1) < pcount) {     // the next round's rows into the registers just copied out
           bool ex;
           c.relane();
+          ql_relane(P, c);
           fetch_ahead<NL>(c, O, k, pair_point(rd + 1, ex), R, fp, rcrows);
         }
         double wp[3] = {0, 0, 0}, r6p[6] = {0, 0, 0, 0, 0, 0}, G6p[21], gamp = 0.0;
@@ -1511,6 +1587,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
       {     // the next point's rows into the registers just copied out
         const int ln = next_bit(order, l);
         c.relane();
+        ql_relane(P, c);
         // (the first point of the NEXT knot is fetched after the main phase: 18 doubles fewer live through it, and the
         // cost expansion and the head of the next knot are time enough for the rows to arrive)
         if (ln >= 0) fetch_ahead<NL>(c, O, k, ln, R, fp, rcrows);
@@ -1566,6 +1643,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     }
     QL_FENCE();
     c.relane();
+    ql_relane(P, c);
     QL_TICK(st, LP_B_LEGS);
     // ---- 2. dynamics expansion (AltroUtils.cpp:78-110,153-168 in compact form) ----
     double A1[9], A3[9], Wt[9];
@@ -1615,6 +1693,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     }
     QL_FENCE();
     c.relane();
+    ql_relane(P, c);
     QL_TICK(st, LP_B_EXPAND);
     double q6[6] = {0, 0, 0, 0, 0, 0}, ak = 0.0;      // AL only: q6 = G y0 + r6,  ak = y0'G y0 + 2 y0'r6 + gam
     if constexpr (AL) {
@@ -1770,6 +1849,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     }
     QL_FENCE();
     c.relane();
+    ql_relane(P, c);
     QL_TICK(st, LP_B_FACT);
     // ---- 4. P <- Abar' P Abar, p <- Abar' p  in place on the symmetric storage; What = A1^-1 (Wt - h A3) ----
     {
@@ -1854,6 +1934,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     }
     QL_FENCE();
     c.relane();
+    ql_relane(P, c);
     QL_TICK(st, LP_B_CONGR);
     // ---- 5. Y = Mt' P (rows f: mf P_p. + m2 P_v. ; rows t: What' P_f. + h P_w.), column by column ----
     // Every sum of products of this step is written as an explicit chain: which product of `a b + c d` the compiler contracts
@@ -1900,6 +1981,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     }
     QL_FENCE();
     c.relane();
+    ql_relane(P, c);
     QL_TICK(st, LP_B_MP);
     // the knot's state for the stage cost (step 6), requested before the column sweep: the registers of the point rows are
     // free here (the next knot's first point is fetched after the sweep), and read right behind that fetch the state cost a
@@ -1938,6 +2020,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
       for (int p = 0; p < 6; ++p) {
         double z[6], xg[6];
         c.relane();
+        ql_relane(P, c);
         col_solve(Y[p], z, xg);
         if (AL) {      // double precision: columns 0..5 in the slot (lower lane), 6..11 in the second block (upper lane)
           const int base = c.half ? O.G2 + D::GAIN2 * k + 6 * p : O.G + D::GAIN * k + 6 * p;
@@ -1978,6 +2061,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     for (int j = kColSplit ? 12 : 0; j < 13; ++j) {
       double yj[6], z[6], xg[6];
       c.relane();
+      ql_relane(P, c);
       constexpr int kY0 = kColSplit ? 0 : 1;      // (the plain form's column index, 0 where the split form never reads Y[j])
 #pragma unroll
       for (int i = 0; i < 6; ++i) yj[i] = (j < 12) ? Y[j < 12 ? j * kY0 : 0][i] : yg[i];
@@ -2038,6 +2122,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     }
     QL_FENCE();
     c.relane();
+    ql_relane(P, c);
     QL_TICK(st, LP_B_UPD);
     if (PAIR) { bool ex; fetch_ahead<NL>(c, O, kn, pair_point(0, ex), R, fp, rcrows); }
     else fetch_ahead<NL>(c, O, kn, first_bit(order), R, fp, rcrows);
@@ -2062,6 +2147,7 @@ QL_FN bool pass_B(const DevParams& P, const Ctx& c_in, const WsOff& O, const Lan
     }
     QL_FENCE();
     c.relane();
+    ql_relane(P, c);
     QL_TICK(st, LP_B_GAIN);
   }
   if constexpr (AL) al->dV1 = dV1;
@@ -2083,8 +2169,8 @@ struct LegOutC {
   double rp, dn, dd, stp;     // largest -ds_i / s_i; the row with the largest -dlam_i / lam_i as numerator / denominator
   bool bad;                   // a component of du is not finite (fmax / fmin drop NaNs silently)
 };
-template <int NL, int MD = MD_QUAT, class RT>
-QL_FN void leg_compute_C(const DevParams& P, const LaneK<NL>& K, const double cr[18], const double rc0_[6], const RT& R,
+template <int NL, int MD = MD_QUAT, class RT, class PT>
+QL_FN void leg_compute_C(const PT& P, const LaneK<NL>& K, const double cr[18], const double rc0_[6], const RT& R,
                          int l, const double zeta[6], const LaneState& st, LegOutC& o, bool rcrows, const double* Wk = nullptr,
                          const double* Rw = nullptr) {
   double rc0[6];
@@ -2155,8 +2241,8 @@ QL_FN void leg_compute_C(const DevParams& P, const LaneK<NL>& K, const double cr
 // candidates are combined once, at the end of the pass.  Both partner lanes add the two shares in the plain form's order,
 // (F + a) + b, and scan the two points' multiplier-ratio candidates in its order too (a running maximum compared by
 // cross-multiplication picks among near-equal rows by position): a pair-mode launch returns the bits of a plain one.
-template <int NL, bool WARM = false, int MD = MD_QUAT, bool PAIR = false>
-QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, LaneState& st, FootPtr fp) {
+template <int NL, bool WARM = false, int MD = MD_QUAT, bool PAIR = false, class PT>
+QL_FN void pass_C(const PT& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, LaneState& st, FootPtr fp) {
   static_assert(!PAIR || MD != MD_CONVEX, "pair split: the quaternion model");
   typedef LDim<NL> D;
   const int N = P.N;
@@ -2370,8 +2456,8 @@ QL_FN void pass_C(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<
 
 // ---- one interior-point iteration of one lane: the control flow of qmpc_solve_body.inc ------------------------------
 // returns true while the instance needs more iterations
-template <int NL, int MD = MD_QUAT>
-QL_FN bool lane_iteration(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, LaneState& st, bool warm = false) {
+template <int NL, int MD = MD_QUAT, class PT>
+QL_FN bool lane_iteration(const PT& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, LaneState& st, bool warm = false) {
   st.it += 1;
   // (the kernel takes the warm instantiations only while some lane of the wavefront still carries a slack residual)
   if (warm && st.rho != 0.0) pass_A<NL, true, MD>(P, c, O, K, st, st.it == 1, (FootPtr)K.foot);
@@ -3224,8 +3310,8 @@ QL_FN void lane_solve_ref(const DevParams& P, const Ctx& c, const WsOff& O, cons
 
 // ---- outputs: GetInput(u, 0) (QuatMpc.cpp:264-265) and the info record -----------------------------------------------
 // traj_u: this instance's [N][3 NL] input trajectory (the next tick's warm start), or null
-template <int NL, int MD = MD_QUAT>
-QL_FN void lane_finish(const DevParams& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, const LaneState& st,
+template <int NL, int MD = MD_QUAT, class PT>
+QL_FN void lane_finish(const PT& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K, const LaneState& st,
                        double* forces, qmpc_info* info, double* traj_u = nullptr, double* traj_x = nullptr) {
   const int N = P.N;
   const bool solved = st.status != QMPC_NAN_INPUT && st.status != QMPC_NO_CONTACT;

@@ -1,0 +1,216 @@
+// Third unit of the lane-per-instance kernels: the converged mode's kernel with PER-LANE robot and cost parameters
+// (qmpc_lane_inst_kernel: qmpc_solve_instances* under QMPC_INSTANCES_AUTO, include/qmpc.h) with its launcher and its own
+// parameter table.  The passes are those of qmpc_lane_kernel<4, MD_QUAT>, instantiated on LaneParams (qmpc_lane_core.h): the 39
+// doubles a per-instance record sets are read from the wavefront's parameter block, laid out [element][lane] like the
+// workspace, everything else from the handle's block in constant memory.  Cold launches of the four-point quaternion model
+// only; the plain and the pair forms.  A unit of its own: the units of qmpc_lane.hip keep their code to the byte.
+#define QL_UNIT 3
+#include "qmpc_lane.hip"
+
+namespace qmpc {
+namespace lane {
+
+struct InstArgs {
+  PassArgs a;
+  unsigned pr_lo, pr_hi;     // this wave's parameter block
+};
+__device__ __forceinline__ QL_GLOBAL_AS const double* inst_prm(const InstArgs& a) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane(a.pr_lo), hi = __builtin_amdgcn_readfirstlane(a.pr_hi);
+  return reinterpret_cast<QL_GLOBAL_AS const double*>(((unsigned long long)hi << 32) | lo);
+}
+// U: the handle's block (scalar loads); P: the passes' parameter source
+#define QL_INST_PARAMS(a)                                                         \
+  const DevParams& U = ql_params[__builtin_amdgcn_readfirstlane((a).a.pslot)];    \
+  const LaneParams P(U, inst_prm(a), 8u * kLaneWave, (a).a.lane8)
+
+// pi: the instance's expanded block (qmpc_expand_instances_kernel); its instance fields become the lane's rows first
+__device__ __noinline__ void call_setup_inst(InstArgs a, unsigned long long rec, unsigned long long pi, QL_PRIV_AS LaneK<4>* Kp,
+                                             QL_PRIV_AS LaneState* sp) {
+  QL_INST_PARAMS(a);
+  const Ctx c = pass_ctx<4>(a.a);
+  const WsOff O = make_wsoff<4>(U.N);
+  lane_params_store(*reinterpret_cast<const DevParams*>(pi), const_cast<QL_GLOBAL_AS double*>(inst_prm(a)), 8u * kLaneWave, a.a.lane8);
+  LaneK<4> K;
+  LaneState st;
+  lane_setup<4, MD_QUAT>(P, c, O, reinterpret_cast<const double*>(rec), K, st, false, nullptr);
+  priv_store(Kp, K);
+  priv_store(sp, st);
+}
+template <bool PAIR>
+__device__ __noinline__ void call_A_inst(InstArgs a, QL_PRIV_AS const LaneK<4>* Kp, QL_PRIV_AS LaneState* sp) {
+  QL_INST_PARAMS(a);
+  const Ctx c = pass_ctx<4>(a.a);
+  const WsOff O = make_wsoff<4>(U.N);
+  LaneK<4> K;
+  priv_load(K, Kp);
+  LaneState st;
+  priv_load(st, (QL_PRIV_AS const LaneState*)sp);
+  st.it += 1;
+  pass_A<4, false, MD_QUAT, PAIR>(P, c, O, K, st, st.it == 1, (FootPtr)Kp->foot);
+  priv_store(sp, st);
+}
+template <bool PAIR>
+__device__ __noinline__ bool call_B_inst(InstArgs a, QL_PRIV_AS const LaneK<4>* Kp, QL_PRIV_AS LaneState* sp) {
+  QL_INST_PARAMS(a);
+  const Ctx c = pass_ctx<4>(a.a);
+  const WsOff O = make_wsoff<4>(U.N);
+  LaneK<4> K;
+  priv_load(K, Kp);
+  LaneState st;
+  priv_load(st, (QL_PRIV_AS const LaneState*)sp);
+  const bool ok = pass_B<4, false, MD_QUAT, false, PAIR>(P, c, O, K, st, (FootPtr)Kp->foot);
+#if defined(QL_PROFILE)
+  priv_store(sp, st);
+#endif
+  return ok;
+}
+template <bool PAIR>
+__device__ __noinline__ void call_C_inst(InstArgs a, QL_PRIV_AS const LaneK<4>* Kp, QL_PRIV_AS LaneState* sp) {
+  QL_INST_PARAMS(a);
+  const Ctx c = pass_ctx<4>(a.a);
+  const WsOff O = make_wsoff<4>(U.N);
+  LaneK<4> K;
+  priv_load(K, Kp);
+  LaneState st;
+  priv_load(st, (QL_PRIV_AS const LaneState*)sp);
+  pass_C<4, false, MD_QUAT, PAIR>(P, c, O, K, st, (FootPtr)Kp->foot);
+  if (!st.bad_step) st.iters = st.it;
+  priv_store(sp, st);
+}
+__device__ __noinline__ void call_finish_inst(InstArgs a, QL_PRIV_AS const LaneK<4>* Kp, QL_PRIV_AS const LaneState* sp,
+                                              unsigned long long forces, unsigned long long info, unsigned long long traj_u,
+                                              unsigned long long traj_x) {
+  QL_INST_PARAMS(a);
+  const Ctx c = pass_ctx<4>(a.a);
+  const WsOff O = make_wsoff<4>(U.N);
+  LaneK<4> K;
+  priv_load(K, Kp);
+  LaneState st;
+  priv_load(st, sp);
+  lane_finish<4, MD_QUAT>(P, c, O, K, st, reinterpret_cast<double*>(forces), reinterpret_cast<qmpc_info*>(info),
+                          reinterpret_cast<double*>(traj_u), reinterpret_cast<double*>(traj_x));
+}
+
+// qmpc_lane_kernel<4, MD_QUAT>'s cold launch with Pi[b] / pstatus[b] (the expanded block and the verdict of instance b) and prm,
+// the parameter blocks of the resident wavefronts (LPR_ROWS rows of 64 lanes each).  Same persistent wavefronts, same sort
+// (perm maps a position to b: the parameters are indexed by b), same 32 / 64 lanes and lane pairs, same cap and hand-off records.
+// A lane whose record was rejected runs no iteration: zero forces and trajectory rows, {QMPC_BAD_PARAMS, 0, ...}, never on the
+// hand-off list.
+__global__ __launch_bounds__(kLaneWave) void qmpc_lane_inst_kernel(int pslot, const double* __restrict__ in, const DevParams* __restrict__ Pi,
+                                                                   const int* __restrict__ pstatus, double* __restrict__ forces,
+                                                                   qmpc_info* __restrict__ info, int batch, double* __restrict__ ws,
+                                                                   double* __restrict__ prm, unsigned slots, int lanes,
+                                                                   const int* __restrict__ perm, double* traj_u, double* traj_x,
+                                                                   int iter_cap, int* __restrict__ hcount, int* __restrict__ hsel,
+                                                                   double* __restrict__ hstate, int hcap) {
+  typedef LDim<4> D;
+  const int lane = threadIdx.x;
+  const DevParams& P = ql_params[pslot];
+  const int itmax = (iter_cap > 0 && iter_cap < P.iterations_max) ? iter_cap : P.iterations_max;
+  const size_t block_elems = (size_t)make_wsoff<4>(P.N).total * kLaneWave;
+  const unsigned long long wsb = reinterpret_cast<unsigned long long>(ws + (size_t)blockIdx.x * block_elems);
+  const unsigned long long prb = reinterpret_cast<unsigned long long>(prm + (size_t)blockIdx.x * LPR_ROWS * kLaneWave);
+  // (the launcher passes -34 for lane pairs: a cold launch splits every pass)
+  const bool pairm = lanes < 0;
+  if (lanes < 0) lanes = 32;
+  const int lane_i = pairm ? (lane & 31) : lane;
+  const InstArgs a = {{pslot, (unsigned)wsb, (unsigned)(wsb >> 32), 8u * (unsigned)lane_i, 0u, pairm ? (unsigned)(lane >> 5) : 0u,
+                       pairm ? 0xF8u : 0x1F8u},
+                      (unsigned)prb, (unsigned)(prb >> 32)};
+  const size_t tstride = (size_t)P.N * D::NU;
+  const size_t xstride = (size_t)(P.N + 1) * 13;
+  LaneK<4> K;
+  LaneState st;
+  QL_PRIV_AS LaneK<4>* Kp = (QL_PRIV_AS LaneK<4>*)&K;
+  QL_PRIV_AS LaneState* sp = (QL_PRIV_AS LaneState*)&st;
+  for (long long base = (long long)blockIdx.x * lanes; base < batch; base += slots) {
+    const long long pos = base + lane_i;
+    const bool valid = (pairm || lane < lanes) && pos < batch;
+    const int b = valid ? (perm ? perm[pos] : (int)pos) : 0;
+    const bool rejected = valid && pstatus[b] != QMPC_OK;
+    bool active = false;
+    st.status = QMPC_BAD_PARAMS;
+    if (valid && !rejected) {
+      call_setup_inst(a, reinterpret_cast<unsigned long long>(in + (size_t)b * D::REC), reinterpret_cast<unsigned long long>(Pi + b), Kp, sp);
+      active = st.active;
+    }
+    while (__any(active)) {
+      if (active) {
+        // one interior-point iteration: the control flow of qmpc_lane_kernel's cold rounds
+        if (pairm) call_A_inst<true>(a, Kp, sp); else call_A_inst<false>(a, Kp, sp);
+        const double resid = st.rho * st.rcmax;
+        if (st.mu <= P.mu_final && resid <= P.tol_feas && st.last_step <= P.tol_step) { st.status = QMPC_OK; active = false; }
+        else if (st.it > itmax) { st.status = QMPC_MAX_ITER; active = false; }
+        else {
+          double sg = P.sigma;
+          const double amin = fmin(st.last_ap, st.last_ad);
+          if (st.it > 1 && amin >= 0.99) sg = P.sigma_fast;
+          else if (st.it > 1 && amin < 0.2) sg = fmax(sg, 0.8);
+          else if (st.it > 1 && amin < 0.5) sg = fmax(sg, 0.5);
+          st.target = sg * st.mu;
+          const bool okB = pairm ? call_B_inst<true>(a, Kp, sp) : call_B_inst<false>(a, Kp, sp);
+          if (!okB) { st.status = QMPC_NOT_PD; active = false; }
+          else {
+            if (pairm) call_C_inst<true>(a, Kp, sp); else call_C_inst<false>(a, Kp, sp);
+            if (st.bad_step) { st.status = QMPC_NOT_PD; active = false; }
+          }
+        }
+      }
+    }
+    if (valid && !rejected)
+      call_finish_inst(a, Kp, sp, reinterpret_cast<unsigned long long>(forces + (size_t)b * D::NU),
+                       info ? reinterpret_cast<unsigned long long>(info + b) : 0ull,
+                       traj_u ? reinterpret_cast<unsigned long long>(traj_u + (size_t)b * tstride) : 0ull,
+                       traj_x ? reinterpret_cast<unsigned long long>(traj_x + (size_t)b * xstride) : 0ull);
+    if (rejected && (!pairm || lane < 32)) {
+      for (int j = 0; j < D::NU; ++j) forces[(size_t)b * D::NU + j] = 0.0;
+      if (info) {
+        const qmpc_info r = {QMPC_BAD_PARAMS, 0, 0.0, 0.0, 0.0, 0.0};
+        info[b] = r;
+      }
+      if (traj_u) for (size_t i = 0; i < tstride; ++i) traj_u[(size_t)b * tstride + i] = 0.0;
+      if (traj_x) for (size_t i = 0; i < xstride; ++i) traj_x[(size_t)b * xstride + i] = 0.0;
+    }
+    if (hcount && valid && !rejected && (!pairm || lane < 32) && itmax < P.iterations_max && st.status == QMPC_MAX_ITER) {
+      const int ord = atomicAdd(hcount, 1);
+      hsel[ord] = b;
+      if (ord < hcap) call_dump<4>(a.a, sp, reinterpret_cast<unsigned long long>(hstate + (size_t)ord * (8 + 84 * (size_t)P.N)), 0);
+    }
+  }
+}
+
+}  // namespace lane
+}  // namespace qmpc
+
+__attribute__((visibility("hidden"))) size_t qmpc_lane_inst_param_bytes(unsigned slots) {
+  return sizeof(double) * (size_t)LPR_ROWS * (size_t)slots;
+}
+// The launch of qmpc_lane_kernel<4> (qmpc_lane_launch) for per-instance records: dev_params is uploaded into this unit's table,
+// dev_blocks / status are the expansion kernel's outputs, prm qmpc_lane_inst_param_bytes(slots) bytes, perm the sort's
+// permutation (qmpc_lane_sort_launch) or null.
+__attribute__((visibility("hidden"))) hipError_t qmpc_lane_inst_launch(int pslot, int batch, hipStream_t s, const void* dev_params,
+                                                                        size_t dev_params_size, const void* in, const void* dev_blocks,
+                                                                        const int* status, double* forces, qmpc_info* info, double* ws,
+                                                                        double* prm, unsigned slots, const int* perm, double* traj_u,
+                                                                        double* traj_x, int iter_cap, int* hcount, int* hsel,
+                                                                        double* hstate, int hcap, int pair) {
+  if (dev_params_size != sizeof(DevParams) || slots % kLaneWave || pslot < 0 || pslot >= kParamSlots) return hipErrorInvalidValue;
+  hipError_t e = hipMemcpyToSymbolAsync(HIP_SYMBOL(ql_params), dev_params, sizeof(DevParams), sizeof(DevParams) * (size_t)pslot,
+                                        hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return e;
+  if (hcount) {
+    e = hipMemsetAsync(hcount, 0, 2 * sizeof(int), s);      // the list's length and the list kernel's cursor
+    if (e != hipSuccess) return e;
+  }
+  // (the rule of qmpc_lane_launch) batches that would occupy at most half of the chip's SIMDs with full wavefronts run with 32
+  // lanes per wavefront, as lane pairs unless QMPC_LANE_PAIR=0
+  const int lanes = (size_t)batch * 2 <= slots ? 32 : 64;
+  const unsigned need = (unsigned)(((size_t)batch + lanes - 1) / lanes);
+  const unsigned waves = need < slots / kLaneWave ? need : slots / kLaneWave;
+  const unsigned used = waves * (unsigned)lanes;
+  const size_t lds = sizeof(double) * kLaneWave * LDim<4>::PLDS;
+  hipLaunchKernelGGL(qmpc_lane_inst_kernel, dim3(waves), dim3(kLaneWave), lds, s, pslot, static_cast<const double*>(in),
+                     static_cast<const DevParams*>(dev_blocks), status, forces, info, batch, ws, prm, used, (lanes == 32 && pair) ? -34 : lanes,
+                     perm, traj_u, traj_x, iter_cap, hcount, hsel, hstate, hcap);
+  return hipGetLastError();
+}

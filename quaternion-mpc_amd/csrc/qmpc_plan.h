@@ -19,6 +19,7 @@ namespace qmpc {
 //   QMPC_WFORM            1 (default) the wrench-form kernels where they apply, 0 the round-1 family only, 3 its all-LDS form only
 //   QMPC_LANE_MIN         the converged mode's switch-over to the lane kernel (plain solves, warm starts and loops alike)
 //   QMPC_LANE_REF_MIN     ... the reference mode's (its closed loop included)
+//   QMPC_LANE_INST_MIN    ... of qmpc_solve_instances* under QMPC_INSTANCES_AUTO (per-instance parameters on the lane kernel)
 //   QMPC_LANE_CAP, QMPC_LANE_CAP_LOOP, QMPC_LANE_CAP_WARM
 //                         iteration cap of the lane kernel before the straggler hand-off: cold plain solves, cold-started
 //                         loops, warm-started loop ticks (0: no hand-off)
@@ -39,6 +40,7 @@ struct qmpc_select {
   int lane_min_batch;     // batches from this size on take the lane-per-instance kernel
   int lane_min_loop_cold; // ... in the ticks of a cold-started closed loop
   int lane_min_warm;      // ... in warm-started solves and loop ticks (their lane passes are not pair-split)
+  int lane_min_inst;      // ... in qmpc_solve_instances* under QMPC_INSTANCES_AUTO (the lane kernel with per-lane parameters)
   int lane_ref_min;       // reference-mode batches from this size on take the lane kernel
   bool lane_ref_min_env;  // ... set by QMPC_LANE_REF_MIN (then the closed loop's own switch-over does not apply)
   int lane_cap, lane_cap_loop, lane_cap_warm;
@@ -278,7 +280,7 @@ static inline qmpc_plan plan(const qmpc_select& s, int batch, qmpc_call kind, bo
 
 // The plan of qmpc_solve_instances* (per-instance parameters, qmpc_wform.hip: qmpc_solve_w_inst_kernel): the wrench-form
 // variant (3 / 5 / 6, with its LDS and workspace) that a plain solve of `batch` instances takes on the wave kernels -- also
-// where a plain solve would go to the lane kernel, which has no per-instance form.  NONE: not QuatMpc's problem in the
+// where a plain solve would go to the lane kernel (the default policy QMPC_INSTANCES_WAVE; the lane form: the overload below).  NONE: not QuatMpc's problem in the
 // converged mode, or no wrench-form kernel for this batch under the handle's knobs (QMPC_WFORM=0, QMPC_WFORM=3 beyond the
 // all-LDS sizes, ...).
 static inline qmpc_plan plan_instances(const qmpc_select& s, int batch) {
@@ -287,6 +289,21 @@ static inline qmpc_plan plan_instances(const qmpc_select& s, int batch) {
   w.lane_slot = false;      // no lane kernel to go to: plan() keeps the wave kernels' own rule at every batch size
   const qmpc_plan p = plan(w, batch, QMPC_CALL_PLAIN, true, false);
   return (p.family == QMPC_KERNEL_WFORM_LDS || p.family == QMPC_KERNEL_WFORM_WS) ? p : qmpc_plan();
+}
+
+// ... under the handle's qmpc_instances_policy.  WAVE: the rule above.  AUTO: the same where it refuses the call, on a handle
+// without a slot of the lane kernel's parameter table and below the switch-over lane_min_inst; from there on the lane fields
+// of the plain solve's plan for this batch (qmpc_lane_inst_kernel to the plain solve's cap and qmpc_solve_w_list_inst_kernel
+// on what it leaves: LANE_HANDOFF; LANE where the plain solve does not hand off).  QMPC_VARIANT=4: the pure lane kernel at
+// every batch size, as for plain solves.
+static inline qmpc_plan plan_instances(const qmpc_select& s, int batch, int policy, bool has_info, bool handoff_failed) {
+  const qmpc_plan w = plan_instances(s, batch);
+  if (policy != QMPC_INSTANCES_AUTO || w.family == QMPC_KERNEL_NONE || !s.lane_slot) return w;
+  if (s.variant != 4 && batch < s.lane_min_inst) return w;
+  qmpc_select l = s;
+  l.lane_min_batch = 0;      // the switch-over is this call's own: the plain plan only names the lane kernel's fields
+  const qmpc_plan p = plan(l, batch, QMPC_CALL_PLAIN, has_info, handoff_failed);
+  return p.variant == 4 ? p : w;
 }
 
 // The plan of qmpc_loop_run_instances* (the closed loop with per-robot controller and / or plant records; qmpc_loop_inst.hip).

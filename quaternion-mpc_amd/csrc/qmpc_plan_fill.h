@@ -89,6 +89,14 @@ constexpr int kLaneRefMinBatch8 = 49152;
 constexpr int kLaneRefMinBatchConvex = 22528;
 constexpr int kLaneRefMinBatchConvexLong = 19456;
 
+// qmpc_solve_instances* under QMPC_INSTANCES_AUTO: the lane kernel with per-lane parameters and its hand-off (qmpc_lane_inst.hip)
+// against the per-instance wave kernel (qmpc_solve_w_inst_kernel), random-variant records, batches 8192 ... 65536 in steps of
+// 2048 (tools/lane_switch_scan.py --instances, profiles/r08_instance_lane_scan.txt): the smallest scanned size from which the lane
+// path is faster at every larger one.  N=10 14336: wave 4.16 vs lane 4.49 ms, 16384: 4.64 vs 4.53, 18432: 5.20 vs 4.59, 65536: 17.1 vs
+// 9.0; N=20 14336: 9.63 vs 10.20, 16384: 10.55 vs 10.43, 18432: 12.5 vs 10.7, 65536: 37.2 vs 19.7.  (Later than the plain solve's
+// 14336 / 14848: this call also pays the expansion kernel and the per-lane rows.)
+constexpr int kLaneMinInst = 16384;           // horizons up to 12
+constexpr int kLaneMinInstLong = 16384;       // longer horizons
 // env(name): the knob's value as a string, or null (qmpc_create passes std::getenv; qmpc_plan.h lists the knobs);
 // lane_slot: qmpc_create obtained a slot of the lane kernel's parameter table.  false: qmpc_create refuses the horizon (the
 // round-1 workspace layout does not fit a CU).
@@ -123,6 +131,7 @@ inline bool qmpc_fill_select(qmpc_select* h, const qmpc_params* params, Env env,
   h->lane_min_loop_cold = lm ? h->lane_min_batch : (kLaneMinLoopCold < h->lane_min_batch ? kLaneMinLoopCold : h->lane_min_batch);
   h->lane_min_warm = (lm || params->model != QMPC_MODEL_QUAT) ? h->lane_min_batch
                                                               : (N <= 12 ? kLaneMinWarm : (N <= 22 ? kLaneMinWarmLong : kLaneMinWarmVeryLong));
+  h->lane_min_inst = knob("QMPC_LANE_INST_MIN", N <= 12 ? kLaneMinInst : kLaneMinInstLong);
   // Straggler hand-off (cold plain solves of QuatMpc's problem on the lane kernel): a launch of the lane kernel lasts as
   // long as its slowest instance -- 23 interior-point iterations at N=10 (mean 13.6), 31 at N=20 (mean 14.6) -- while
   // only 8 % / 10 % of the instances are still running after 16 / 17.  The lane kernel stops there, leaves the state of

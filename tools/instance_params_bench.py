@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Plain solve against the per-instance-parameter solve (qmpc_solve_instances_device) on the same records, uniform records
-(every instance carries the handle's values), device buffers, one handle per size.  The two calls alternate, each timed with
-device events around the call on the same stream after warm-up; median of the repetitions.  The per-instance call includes its
-expansion kernel (one DevParams block per instance); run under `rocprofv3 --kernel-trace --stats` for that kernel's own time.
-    python tools/instance_params_bench.py [--reps 10] [--warmup 3] [--sizes 10:1024,10:8192,...] [--json FILE]"""
+"""Plain solve against the per-instance-parameter solve (qmpc_solve_instances_device) on the same states, device buffers, one
+handle per size.  Columns: the plain solve, the per-instance call under QMPC_INSTANCES_WAVE and / or QMPC_INSTANCES_AUTO
+(--policy), each with uniform records (every instance carries the handle's values) and with random-variant records
+(random_go1_variants).  The calls alternate within a repetition, each timed with device events around the call on the same stream
+after warm-up; median of the repetitions.  The per-instance calls include their expansion kernel (one DevParams block per
+instance) and, under AUTO, the stance sort and the hand-off.
+    python tools/instance_params_bench.py [--policy wave|auto|both] [--reps 10] [--warmup 3] [--sizes 10:1024,...] [--json FILE]"""
 import argparse
 import importlib.util
 import json
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sizes", default=DEFAULT_SIZES)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--policy", default="both", choices=("wave", "auto", "both"))
     a = ap.parse_args()
     import torch
 
@@ -42,18 +45,28 @@ def main():
         p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
         rec = pkg.random_go1_trot_states(B, config_id=2)
         s = pkg.Solver(p, B, device=0, lib=lib)
+        policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
+        if "auto" in policies:
+            s.set_instances_policy("auto")      # the buffers of every call below are allocated here, not in a timed call
         s.prepare(B)
         s.prepare_instances()
         d_in = torch.from_numpy(rec.view(np.uint8).copy()).cuda()
-        d_ip = torch.from_numpy(pkg.instance_params(p, B).view(np.uint8).copy()).cuda()
+        records = {"uniform": pkg.instance_params(p, B), "variants": pkg.random_go1_variants(B, seed=13, base=p)}
+        d_ip = {k: torch.from_numpy(v.view(np.uint8).copy()).cuda() for k, v in records.items()}
         d_f = torch.zeros((B, 12), dtype=torch.float64, device="cuda")
         d_info = torch.zeros(B * pkg.INFO_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         stream = torch.cuda.Stream()      # a stream of its own: the default stream's handle is 0, i.e. the solver's own stream
         st = stream.cuda_stream
         torch.cuda.synchronize()
-        calls = {"plain": lambda: s.solve_device(B, d_in.data_ptr(), d_f.data_ptr(), d_info.data_ptr(), stream=st),
-                 "instances": lambda: s.solve_instances_device(B, d_in.data_ptr(), d_ip.data_ptr(), d_f.data_ptr(), d_info.data_ptr(),
-                                                               stream=st)}
+
+        def inst(policy, kind):
+            s.set_instances_policy(policy)
+            s.solve_instances_device(B, d_in.data_ptr(), d_ip[kind].data_ptr(), d_f.data_ptr(), d_info.data_ptr(), stream=st)
+
+        calls = {"plain": lambda: s.solve_device(B, d_in.data_ptr(), d_f.data_ptr(), d_info.data_ptr(), stream=st)}
+        for pol in policies:
+            for kind in records:
+                calls[f"{pol}_{kind}"] = (lambda pol=pol, kind=kind: inst(pol, kind))
         times = {k: [] for k in calls}
         for r in range(a.warmup + a.reps):
             for k, fn in calls.items():
@@ -64,16 +77,25 @@ def main():
                 e1.synchronize()
                 if r >= a.warmup:
                     times[k].append(e0.elapsed_time(e1))
-        fam = {"plain": s.kernel_for_batch(B), "instances": s.kernel_for_instances(B)}
+        row = {"N": N, "B": B, "plain_kernel": s.kernel_for_batch(B)}
+        for pol in policies:
+            s.set_instances_policy(pol)
+            row[f"{pol}_kernel"] = s.kernel_for_instances(B)
         s.close()
-        ms = {k: float(np.median(v)) for k, v in times.items()}
-        row = {"N": N, "B": B, "plain_kernel": fam["plain"], "instances_kernel": fam["instances"], "plain_ms": ms["plain"],
-               "instances_ms": ms["instances"], "plain_Msolves_s": B / ms["plain"] / 1e3, "instances_Msolves_s": B / ms["instances"] / 1e3,
-               "ratio": ms["instances"] / ms["plain"]}
+        line = f"N={N:2d} B={B:6d}"
+        for k, v in times.items():
+            ms = float(np.median(v))
+            row[f"{k}_ms"], row[f"{k}_Msolves_s"] = ms, B / ms / 1e3
+            row[f"{k}_spread"] = float((np.percentile(v, 75) - np.percentile(v, 25)) / ms)
+            line += f"  {k} {ms:7.3f} ms {B / ms / 1e3:6.3f} M/s"
+        for pol in policies:
+            line += f"  [{pol}: {row[pol + '_kernel']}]"
+        if "auto" in policies and "wave" in policies:
+            line += f"  auto/wave variants x{row['wave_variants_ms'] / row['auto_variants_ms']:.3f}"
+        if "auto" in policies:
+            line += f"  auto/plain {row['auto_variants_ms'] / row['plain_ms']:.3f}"
         rows.append(row)
-        print(f"N={N:2d} B={B:6d}  plain {fam['plain']:>12s} {ms['plain']:8.3f} ms {row['plain_Msolves_s']:6.3f} M/s   "
-              f"instances {fam['instances']:>9s} {ms['instances']:8.3f} ms {row['instances_Msolves_s']:6.3f} M/s   "
-              f"ratio {row['ratio']:.3f}", flush=True)
+        print(line, flush=True)
     if a.json:
         Path(a.json).parent.mkdir(parents=True, exist_ok=True)
         Path(a.json).write_text(json.dumps(rows, indent=1) + "\n")

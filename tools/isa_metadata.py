@@ -14,7 +14,9 @@ print("columns: kernel | vgpr_count | agpr_count | sgpr_count | vgpr_spill_count
 WAVE = ["-mllvm", "-disable-machine-licm", "-mllvm", "-disable-machine-sink"]
 for tu, extra in (("qmpc_hip.hip", WAVE), ("qmpc_loop_fused.hip", WAVE), ("qmpc_loop_inst.hip", WAVE), ("qmpc_wform.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
                   ("qmpc_lane.hip", ["-mllvm", "-disable-lsr", "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-DQL_UNIT=1"]),
-                  ("qmpc_lane_ref.hip", ["-mllvm", "-disable-lsr", "-DQL_UNIT=2"])):
+                  ("qmpc_lane_ref.hip", ["-mllvm", "-disable-lsr", "-DQL_UNIT=2"]),
+                  ("qmpc_lane_inst.hip", ["-mllvm", "-disable-lsr", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
+                  ("qmpc_wform_inst_list.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"])):
     with tempfile.TemporaryDirectory() as d:
         asm = Path(d) / "tu.s"
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", *extra, "-std=c++17", "-S", "--cuda-device-only", "-o", str(asm),

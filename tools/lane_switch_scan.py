@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Switch-over between the wave-per-instance kernels and the lane kernel (+ hand-off) in converged mode: the library's own
 choice with QMPC_LANE_MIN huge (wave side) and 1 (lane side), same records, kernel-side time between the handle's events.
-GPU box:  python tools/lane_switch_scan.py [--cases N:B,...]"""
+GPU box:  python tools/lane_switch_scan.py [--cases N:B,...]
+--instances: the same for qmpc_solve_instances_device with random-variant records -- QMPC_INSTANCES_WAVE against
+QMPC_INSTANCES_AUTO with QMPC_LANE_INST_MIN=1 on one handle per horizon, batches 8192 ... 65536 in steps of 2048 at N=10 and N=20
+(the switch-over lane_min_inst of qmpc_plan_fill.h is the smallest size from which the lane path wins at every larger one)."""
 import argparse, os, sys
 from pathlib import Path
 import numpy as np
@@ -11,9 +14,44 @@ import __graft_entry__ as g  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--cases", default="10:12288,10:16384,10:20480,10:24576,16:12288,16:16384,16:20480,20:12288,20:16384,20:20480,24:12288,24:16384")
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--instances", action="store_true")
+ap.add_argument("--horizons", default="10,20")
 a = ap.parse_args()
 pkg = g._load_pkg(); lib = pkg.load_library()
 import torch  # noqa: E402
+if a.instances:
+    os.environ["QMPC_LANE_INST_MIN"] = "1"
+    BMAX = 65536
+    for N in (int(x) for x in a.horizons.split(",")):
+        p = pkg.default_params(N, 0, lib)
+        rec = pkg.random_go1_trot_states(BMAX, config_id=3 if N == 20 else 2)
+        ip = pkg.random_go1_variants(BMAX, seed=13, base=p)
+        d_in = torch.from_numpy(rec.view(np.uint8).copy()).cuda(); d_ip = torch.from_numpy(ip.view(np.uint8).copy()).cuda()
+        d_f = torch.zeros(BMAX, 12, dtype=torch.float64, device="cuda"); d_i = torch.zeros(BMAX, 5, dtype=torch.float64, device="cuda")
+        s = pkg.Solver(p, BMAX, 0, lib)
+        s.set_instances_policy("auto"); s.prepare(BMAX); s.prepare_instances()
+        first = None
+        wins = []
+        for B in range(8192, BMAX + 1, 2048):
+            ms = {"wave": [], "auto": []}
+            for r in range(a.reps + 2):
+                for pol in ms:
+                    s.set_instances_policy(pol)
+                    s.solve_instances_device(B, d_in.data_ptr(), d_ip.data_ptr(), d_f.data_ptr(), d_i.data_ptr()); s.wait()
+                    if r >= 2: ms[pol].append(s.last_kernel_ms())
+            kern = {}
+            for pol in ms:
+                s.set_instances_policy(pol); kern[pol] = s.kernel_for_instances(B)
+            mw, ml = float(np.median(ms["wave"])), float(np.median(ms["auto"]))
+            wins.append((B, ml < mw))
+            print(f"N={N} B={B}: wave {kern['wave']} {mw:.3f} ms ({B / mw / 1e3:.3f} M/s) vs auto {kern['auto']} {ml:.3f} ms ({B / ml / 1e3:.3f} M/s)  "
+                  f"auto/wave x{mw / ml:.3f}", flush=True)
+        s.close()
+        for B, w in reversed(wins):
+            if not w: break
+            first = B
+        print(f"N={N}: the lane path is faster at every scanned size from {first} on", flush=True)
+    sys.exit(0)
 for case in a.cases.split(","):
     N, B = (int(x) for x in case.split(":"))
     p = pkg.default_params(N, 0, lib)
