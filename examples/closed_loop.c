@@ -5,6 +5,8 @@
  *       -Wl,-rpath,'$ORIGIN/../quaternion-mpc_amd/csrc' -lm
  * usage: closed_loop [robots=64] [ticks=400] [warm=0]     (one tick = 5 ms; warm=1: every solve starts from the previous
  *        tick's solution and a low initial barrier -- the same forces in about half the iterations)
+ * The walking phase runs through qmpc_loop_run_outcomes, which accumulates a 128-byte outcome record per robot on the device
+ * (lowest height, worst tilt and tracking error, rejected solves, the tick it went down); robot 0's is printed.
  * Prints where the robots ended up; exits non-zero if a robot fell, a solve failed, or there is no GPU (there is no
  * CPU fallback: qmpc_create then returns QMPC_NO_DEVICE). */
 #include <math.h>
@@ -39,11 +41,26 @@ int main(int argc, char** argv) {
   }
   st = qmpc_loop_run(h, &lp, robots, s, /*ticks=*/10, NULL, NULL);        /* stand: the gait FSM resets */
   for (int i = 0; i < robots && st == QMPC_OK; ++i) s[i].movement_mode = 1.0;   /* the state is plain data between runs */
-  if (st == QMPC_OK) st = qmpc_loop_run(h, &lp, robots, s, ticks, NULL, NULL);
+  /* the walk, with one outcome record per robot (no per-robot controller or plant records: plain robots) */
+  qmpc_outcome_params op;
+  qmpc_default_outcome_params(&op);
+  qmpc_loop_outcome* oc = malloc(sizeof *oc * (size_t)robots);
+  qmpc_loop_outcome_init(oc, robots);
+  if (st == QMPC_OK) st = qmpc_loop_run_outcomes(h, &lp, robots, s, ticks, NULL, NULL, NULL, NULL, &op, oc);
   if (st != QMPC_OK) {
     fprintf(stderr, "qmpc_loop_run: %s\n", qmpc_status_string(st));
     return 3;
   }
+  int down = 0;
+  for (int i = 0; i < robots; ++i) down += oc[i].down_tick >= 0.0;
+  printf("robot   0 outcome: %.0f ticks, down tick %.0f, lowest height %.3f m, lowest cos(tilt) %.4f, worst height error %.3f m,\n"
+         "                   velocity error worst %.3f rms %.3f m/s, worst |w| %.2f rad/s, largest f_z %.1f N, solves not OK %.0f, "
+         "rejected %.0f, iterations mean %.1f max %.0f\n",
+         oc[0].ticks, oc[0].down_tick, oc[0].min_height, oc[0].min_upright, oc[0].max_height_err, oc[0].max_vel_err,
+         sqrt(oc[0].sum_vel_err_sq / oc[0].ticks), oc[0].max_ang_vel, oc[0].max_force_z, oc[0].not_ok_ticks, oc[0].rejected_ticks,
+         oc[0].iterations_sum / oc[0].ticks, oc[0].iterations_max);
+  printf("outcome records: %d of %d robots went down\n", down, robots);
+  free(oc);
   int bad = 0;
   double far = 0.0;
   for (int i = 0; i < robots; ++i) {

@@ -651,6 +651,71 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
                                            const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                            double* d_trace_forces, double* d_trace_contacts, void* stream);
 
+/* ---- per-robot outcome records of the closed loop (robustness sweeps) -------------------------------------------------
+ * The other half of the question above: did robot i stay up, how far did it tilt, how well did it track its command, how
+ * often was its solve rejected?  qmpc_loop_run_outcomes* is qmpc_loop_run_instances* -- the same robots, launch forms
+ * (QMPC_QUERY_LOOP_INSTANCES_PLAN answers for it too), states and traces, bit for bit -- and accumulates one 128-byte record
+ * per robot on the device inside the tick, instead of 6.5 KB of state per robot and tick crossing the link.
+ *
+ * A record is evaluated on the robot's state AFTER the post step of a tick: the new plant state, this tick's lin_vel_d_rel
+ * and joy, the applied forces_body, status and iterations (loop_outcome_one, csrc/qmpc_loop_math.h: one source for the
+ * device, the host class and the tests).  Minima and maxima skip non-finite values (a comparison with NaN selects nothing).
+ * The robot is DOWN when pos_world[2] or the upright value is non-finite or below its threshold; the tick that leaves it
+ * down is accumulated, then the record is frozen: down_tick is set and nothing further is added, in this call or a later one
+ * with the same record.  Records are in/out and accumulate over calls: start from qmpc_loop_outcome_init.
+ *
+ * op->stop_when_down == 0: the robot is simulated on exactly as by qmpc_loop_run_instances*.  != 0: from the tick after its
+ * down tick the robot is halted like the robot of an invalid record -- no solve runs for it (the persistent kernel's
+ * wavefront leaves; in the per-tick form its input record gets a NaN attitude, which every solve kernel rejects before its
+ * first iteration), its trace rows are zero -- and its state record is left untouched, so state.tick stays at down_tick.
+ * A robot whose record comes in with down_tick >= 0 is halted from the first tick of the call.
+ * The robot of an invalid controller or plant record (QMPC_BAD_PARAMS) leaves its outcome record untouched.
+ *
+ * Scope and refusals: those of qmpc_loop_run_instances* with records -- a QuatMpc handle in the converged mode;
+ * QMPC_UNSUPPORTED for a ConvexMpc or reference-mode handle, QMPC_BAD_ARGUMENT for an 8-point handle, with ctrl also
+ * QMPC_UNSUPPORTED for lp->warm_start != 0 or a handle without a wrench-form kernel -- and QMPC_BAD_ARGUMENT for a NULL op
+ * or outcomes.  ctrl and plant may both be NULL: plain robots on the handle's parameters (still a QuatMpc converged
+ * handle).  Buffers: those of qmpc_loop_run_instances*; the host-buffer call adds a staging buffer for the records (128 B x
+ * max_batch) on its first use.  No other call allocates it. */
+typedef struct qmpc_outcome_params {   /* 4 doubles */
+  double down_height;     /* default 0.15 m: down when pos_world[2] is below */
+  double down_upright;    /* default 0.5 (cos of 60 deg tilt): down when the upright value is below */
+  double stop_when_down;  /* 0 (default): go on simulating; != 0: halt the robot after its down tick */
+  double reserved;        /* 0 */
+} qmpc_outcome_params;
+typedef struct qmpc_loop_outcome {     /* 16 doubles, 128 B; in/out: accumulates over calls */
+  double ticks;               /* ticks accumulated into this record */
+  double down_tick;           /* state.tick after the first tick that left the robot down; -1: never */
+  double min_height;          /* min pos_world[2] */
+  double min_upright;         /* min of the (3,3) entry of quat_to_rot(quat) = cos(tilt) */
+  double max_height_err;      /* max |pos_world[2] - joy[2]| */
+  double max_vel_err;         /* max e_v, e_v = |(R' lin_vel_world)_xy - lin_vel_d_rel_xy|_2 */
+  double sum_vel_err_sq;      /* sum of e_v^2 (RMS = sqrt(sum / ticks)) */
+  double max_ang_vel;         /* max |ang_vel_body|_inf */
+  double max_force_z;         /* max over legs of the applied forces_body[3 leg + 2] */
+  double not_ok_ticks;        /* ticks whose solve status != QMPC_OK */
+  double rejected_ticks;      /* ticks whose solve was not applied (status neither QMPC_OK nor QMPC_MAX_ITER) */
+  double first_rejected_tick; /* state.tick after the first such tick; -1: never */
+  double iterations_sum, iterations_max;
+  double reserved[2];         /* 0 */
+} qmpc_loop_outcome;
+void    qmpc_default_outcome_params(qmpc_outcome_params* op);
+/* Host-side: `batch` empty records -- counters and sums 0, down_tick and first_rejected_tick -1, minima +inf, maxima -inf.
+ * Every byte is written. */
+void    qmpc_loop_outcome_init(qmpc_loop_outcome* outcomes, int32_t batch);
+int32_t qmpc_sizeof_loop_outcome(void);
+/* Host buffers: qmpc_loop_run_instances' arguments, then op and outcomes [batch] in/out.  Synchronous. */
+qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                   int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant,
+                                   double* trace_forces, double* trace_contacts, const qmpc_outcome_params* op,
+                                   qmpc_loop_outcome* outcomes);
+/* Device buffers (op is a host pointer, read during the call), stream-ordered (NULL stream = the handle's). */
+qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch,
+                                          qmpc_loop_state* d_states, int32_t ticks,
+                                          const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                          double* d_trace_forces, double* d_trace_contacts,
+                                          const qmpc_outcome_params* op, qmpc_loop_outcome* d_outcomes, void* stream);
+
 /* Stand-pose joint angles (0, 0.67, -1.3 per leg: the reference's Gazebo start pose) for `batch`
  * robots, host buffer [batch][12]. */
 void qmpc_loop_joint_init(double* joint_pos, int32_t batch);

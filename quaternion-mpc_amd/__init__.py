@@ -232,6 +232,35 @@ def plant_params(params: "Params", batch: int = 1) -> np.ndarray:
     return out
 
 
+# struct qmpc_loop_outcome (qmpc_loop_run_outcomes*): one robot's outcome record, 16 doubles = 128 B
+LOOP_OUTCOME_DTYPE = np.dtype(
+    [
+        ("ticks", "<f8"),
+        ("down_tick", "<f8"),
+        ("min_height", "<f8"),
+        ("min_upright", "<f8"),
+        ("max_height_err", "<f8"),
+        ("max_vel_err", "<f8"),
+        ("sum_vel_err_sq", "<f8"),
+        ("max_ang_vel", "<f8"),
+        ("max_force_z", "<f8"),
+        ("not_ok_ticks", "<f8"),
+        ("rejected_ticks", "<f8"),
+        ("first_rejected_tick", "<f8"),
+        ("iterations_sum", "<f8"),
+        ("iterations_max", "<f8"),
+        ("reserved", "<f8", (2,)),
+    ],
+    align=False,
+)
+assert LOOP_OUTCOME_DTYPE.itemsize == 16 * 8
+
+
+class OutcomeParams(C.Structure):
+    """struct qmpc_outcome_params"""
+    _fields_ = [("down_height", C.c_double), ("down_upright", C.c_double), ("stop_when_down", C.c_double), ("reserved", C.c_double)]
+
+
 # struct qmpc_info: 2 x int32 + 4 doubles = 40 B
 INFO_DTYPE = np.dtype(
     [
@@ -318,6 +347,14 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_instances_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, vp]
     lib.qmpc_loop_run_instances_device.restype = i32
     lib.qmpc_prepare_instances.restype = i32
+    lib.qmpc_default_outcome_params.argtypes = [C.POINTER(OutcomeParams)]
+    lib.qmpc_default_outcome_params.restype = None
+    lib.qmpc_loop_outcome_init.argtypes = [vp, i32]
+    lib.qmpc_loop_outcome_init.restype = None
+    lib.qmpc_loop_run_outcomes.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp]
+    lib.qmpc_loop_run_outcomes.restype = i32
+    lib.qmpc_loop_run_outcomes_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp]
+    lib.qmpc_loop_run_outcomes_device.restype = i32
     lib.qmpc_set_instances_policy.argtypes = [vp, i32]
     lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_gather.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
@@ -389,7 +426,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp]
     lib.qmpc_loop_run_device.restype = i32
     for name in ("qmpc_sizeof_input", "qmpc_sizeof_params", "qmpc_sizeof_info", "qmpc_sizeof_convex_input",
-                 "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params", "qmpc_sizeof_plant_params"):
+                 "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params", "qmpc_sizeof_plant_params",
+                 "qmpc_sizeof_loop_outcome"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = i32
     if lib.qmpc_sizeof_input() != INPUT_DTYPE.itemsize:
@@ -408,6 +446,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         raise RuntimeError("qmpc_instance_params ABI size mismatch")
     if lib.qmpc_sizeof_plant_params() != PLANT_PARAMS_DTYPE.itemsize:
         raise RuntimeError("qmpc_plant_params ABI size mismatch")
+    if lib.qmpc_sizeof_loop_outcome() != LOOP_OUTCOME_DTYPE.itemsize or C.sizeof(OutcomeParams) != 32:
+        raise RuntimeError("qmpc_loop_outcome ABI size mismatch")
     return lib
 
 
@@ -475,6 +515,11 @@ EXPORTED_SYMBOLS = (
     "qmpc_loop_run_instances",
     "qmpc_loop_run_instances_device",
     "qmpc_set_instances_policy",
+    "qmpc_default_outcome_params",
+    "qmpc_loop_outcome_init",
+    "qmpc_sizeof_loop_outcome",
+    "qmpc_loop_run_outcomes",
+    "qmpc_loop_run_outcomes_device",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
@@ -515,6 +560,54 @@ def default_loop_params(lib: C.CDLL | None = None) -> LoopParams:
     lp = LoopParams()
     lib.qmpc_default_loop_params(C.byref(lp))
     return lp
+
+
+def default_outcome_params(lib: C.CDLL | None = None, stop_when_down: bool = False) -> OutcomeParams:
+    """qmpc_default_outcome_params: down below 0.15 m or beyond 60 degrees of tilt; stop_when_down halts a robot after its down tick."""
+    lib = lib or load_library()
+    op = OutcomeParams()
+    lib.qmpc_default_outcome_params(C.byref(op))
+    op.stop_when_down = 1.0 if stop_when_down else 0.0
+    return op
+
+
+def loop_outcomes(B: int, lib: C.CDLL | None = None) -> np.ndarray:
+    """[B] empty outcome records (qmpc_loop_outcome_init)."""
+    lib = lib or load_library()
+    out = np.zeros(int(B), dtype=LOOP_OUTCOME_DTYPE)
+    lib.qmpc_loop_outcome_init(_ptr(out), int(B))
+    return out
+
+
+def summarize_outcomes(o: np.ndarray) -> dict:
+    """A fleet's outcome records in a few figures (numpy only): robots down and a histogram of their down ticks, worst and
+    median tracking figures over the robots that accumulated at least one tick, solve statistics."""
+    o = np.ascontiguousarray(o, dtype=LOOP_OUTCOME_DTYPE).ravel()
+    seen = o[o["ticks"] > 0]
+    down = o["down_tick"] >= 0
+    out = {"robots": int(o.size), "evaluated": int(seen.size), "down": int(down.sum()),
+           "down_fraction": float(down.mean()) if o.size else 0.0}
+    dt = o["down_tick"][down].astype(np.int64)
+    if dt.size:
+        ticks, counts = np.unique(dt, return_counts=True)
+        out["down_tick_histogram"] = {int(t): int(c) for t, c in zip(ticks, counts)}
+        out["first_down_tick"], out["median_down_tick"] = int(dt.min()), float(np.median(dt))
+    else:
+        out["down_tick_histogram"] = {}
+    if seen.size:
+        rms = np.sqrt(seen["sum_vel_err_sq"] / seen["ticks"])
+        out.update(
+            min_height=float(seen["min_height"].min()), median_min_height=float(np.median(seen["min_height"])),
+            min_upright=float(seen["min_upright"].min()), median_min_upright=float(np.median(seen["min_upright"])),
+            worst_height_err=float(seen["max_height_err"].max()), median_height_err=float(np.median(seen["max_height_err"])),
+            worst_vel_err=float(seen["max_vel_err"].max()), median_vel_err=float(np.median(seen["max_vel_err"])),
+            worst_rms_vel_err=float(rms.max()), median_rms_vel_err=float(np.median(rms)),
+            worst_ang_vel=float(seen["max_ang_vel"].max()), worst_force_z=float(seen["max_force_z"].max()),
+            not_ok_ticks=int(seen["not_ok_ticks"].sum()), rejected_ticks=int(seen["rejected_ticks"].sum()),
+            robots_with_rejected_solves=int((seen["rejected_ticks"] > 0).sum()),
+            mean_iterations=float(seen["iterations_sum"].sum() / seen["ticks"].sum()),
+            max_iterations=int(seen["iterations_max"].max()))
+    return out
 
 
 def loop_states(commands, lp: LoopParams | None = None, height: float = 0.3, yaw=0.0, lib: C.CDLL | None = None) -> np.ndarray:
@@ -749,6 +842,50 @@ class Solver:
                                                      p(d_trace_forces), p(d_trace_contacts), p(stream))
         if rc != OK:
             raise QmpcError(rc, "qmpc_loop_run_instances_device")
+
+    def loop_run_outcomes(self, states: np.ndarray, ticks: int, lp: LoopParams | None = None, ctrl: np.ndarray | None = None,
+                          plant: np.ndarray | None = None, op: OutcomeParams | None = None, outcomes: np.ndarray | None = None,
+                          trace: bool = False):
+        """qmpc_loop_run_outcomes: loop_run_instances that also accumulates one outcome record per robot (LOOP_OUTCOME_DTYPE) on
+        the device.  outcomes: the records to go on accumulating into (None: empty ones); op: default_outcome_params().  Returns
+        (states, outcomes[, forces, contacts]); the arguments are not modified."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
+        B = st.shape[0]
+        if ctrl is not None:
+            ctrl = np.ascontiguousarray(ctrl, dtype=INSTANCE_PARAMS_DTYPE)
+            if ctrl.shape != (B,):
+                raise ValueError(f"ctrl: shape {ctrl.shape}, expected ({B},)")
+        if plant is not None:
+            plant = np.ascontiguousarray(plant, dtype=PLANT_PARAMS_DTYPE)
+            if plant.shape != (B,):
+                raise ValueError(f"plant: shape {plant.shape}, expected ({B},)")
+        if outcomes is None:
+            oc = loop_outcomes(B, self.lib)
+        else:
+            oc = np.ascontiguousarray(outcomes, dtype=LOOP_OUTCOME_DTYPE).copy()
+            if oc.shape != (B,):
+                raise ValueError(f"outcomes: shape {oc.shape}, expected ({B},)")
+        tf = np.zeros((ticks, B, 12)) if trace else None
+        tc = np.zeros((ticks, B, 4)) if trace else None
+        rc = self.lib.qmpc_loop_run_outcomes(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
+                                             C.byref(op), _ptr(oc))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_outcomes")
+        return (st, oc, tf, tc) if trace else (st, oc)
+
+    def loop_run_outcomes_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, lp: LoopParams | None = None,
+                                 op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0,
+                                 d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_outcomes_device: device pointers (ints; 0 = NULL), stream-ordered."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        rc = self.lib.qmpc_loop_run_outcomes_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
+                                                    p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(stream))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_outcomes_device")
 
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <new>
 
@@ -80,6 +81,20 @@ hipError_t qmpc_loop_inst_front_launch(hipStream_t s, const qmpc_loop_params* lp
 hipError_t qmpc_loop_inst_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, const double* forces,
                                       const qmpc_info* info, double* trace_f, double* trace_c, const int* row, const void* plants,
                                       int batch);
+
+// qmpc_loop_outcome.hip: the same closed loop accumulating per-robot outcome records (qmpc_loop_run_outcomes*)
+hipError_t qmpc_loop_outcome_set_lds();
+hipError_t qmpc_loop_outcome_expand_base_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, void* bcast_out,
+                                                void* plants_out, int batch);
+hipError_t qmpc_loop_outcome_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,
+                                          const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st,
+                                          qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f, double* trace_c,
+                                          qmpc_loop_outcome* outcomes, int ticks, double* gws);
+hipError_t qmpc_loop_outcome_front_launch(hipStream_t s, const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st,
+                                          qmpc_input* rec, int* row, const void* plants, const qmpc_loop_outcome* outcomes, int batch);
+hipError_t qmpc_loop_outcome_post_launch(hipStream_t s, const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st,
+                                         const double* forces, const qmpc_info* info, double* trace_f, double* trace_c, const int* row,
+                                         const void* plants, qmpc_loop_outcome* outcomes, int batch);
 
 // qmpc_lane.hip (third translation unit): the lane-per-instance kernel of large batches
 size_t qmpc_lane_ws_bytes(int N, int nl, unsigned slots, int wide);
@@ -152,6 +167,7 @@ struct qmpc_handle {
   double* d_lane_prm;          // ... under AUTO: the resident wavefronts' parameter blocks [LPR_ROWS][lane_slots], on first use
   unsigned char* d_plant;      // per-robot plants of qmpc_loop_run_instances*, on first use: [max_batch] PlantDev | [max_batch]
                                // qmpc_plant_params (staging of the host-buffer call)
+  qmpc_loop_outcome* d_outcome;   // staging of qmpc_loop_run_outcomes (the host-buffer call), on its first use: [max_batch] records
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -306,6 +322,7 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   HIP_TRY(qmpc_loop_fused_set_lds());
   HIP_TRY(qmpc_wform_set_lds());
   HIP_TRY(qmpc_loop_inst_set_lds());
+  HIP_TRY(qmpc_loop_outcome_set_lds());
   HIP_TRY(qmpc_wform_inst_list_set_lds());
   HIP_TRY(hipMalloc(&h->d_gws, sizeof(double) * (size_t)N * (13 * nu + 21 * nl + 30 * nl) * (size_t)max_batch));
   return QMPC_OK;
@@ -372,6 +389,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_inst) (void)hipFree(h->d_inst);
   if (h->d_lane_prm) (void)hipFree(h->d_lane_prm);
   if (h->d_plant) (void)hipFree(h->d_plant);
+  if (h->d_outcome) (void)hipFree(h->d_outcome);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -982,6 +1000,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_inst) b += instance_bytes(h->max_batch);
       if (h->d_lane_prm) b += qmpc_lane_inst_param_bytes(h->lane_slots);
       if (h->d_plant) b += plant_bytes(h->max_batch);
+      if (h->d_outcome) b += sizeof(qmpc_loop_outcome) * (size_t)h->max_batch;
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
       return QMPC_OK;
@@ -1563,6 +1582,119 @@ qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, 
   if (es == QMPC_OK) es = ensure_plant_buffers(h);
   if (es != QMPC_OK || ticks == 0) return es;
   return loop_run_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts);
+}
+
+// ---- the same closed loop with per-robot outcome records (qmpc_loop_outcome.hip) -------------------------------------------
+static_assert(sizeof(qmpc_loop_outcome) == 128 && sizeof(qmpc_outcome_params) == 32, "qmpc_loop_outcome is 128 B, its parameters 4 doubles");
+int32_t qmpc_sizeof_loop_outcome(void) { return (int32_t)sizeof(qmpc_loop_outcome); }
+
+void qmpc_default_outcome_params(qmpc_outcome_params* op) {
+  if (!op) return;
+  std::memset(op, 0, sizeof *op);
+  op->down_height = 0.15;
+  op->down_upright = 0.5;
+}
+
+void qmpc_loop_outcome_init(qmpc_loop_outcome* o, int32_t batch) {
+  if (!o) return;
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int32_t i = 0; i < batch; ++i) {
+    std::memset(&o[i], 0, sizeof o[i]);
+    o[i].down_tick = -1.0;
+    o[i].first_rejected_tick = -1.0;
+    o[i].min_height = o[i].min_upright = inf;
+    o[i].max_height_err = o[i].max_vel_err = o[i].max_ang_vel = o[i].max_force_z = o[i].iterations_max = -inf;
+  }
+}
+
+// The call of qmpc_loop_run_instances_device with the outcome kernels in place of its own.  Without records (both NULL) every
+// robot's plant block carries the handle's mass and inverse inertia: the call-level checks are those of a call with plant records.
+qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                          int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                          double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                          qmpc_loop_outcome* d_outcomes, void* stream) {
+  if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!d_states || !d_outcomes))) return QMPC_BAD_ARGUMENT;
+  const qmpc_status cs = loop_instances_check(h, lp, batch, d_ctrl != nullptr);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  const bool warm = lp->warm_start != 0.0;
+  const qmpc_plan lpp = plan_loop_instances(h->sel, batch, d_ctrl != nullptr, warm, h->handoff_failed);
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  qmpc_status es = ensure_instance_buffers(h);
+  if (es == QMPC_OK) es = ensure_plant_buffers(h);
+  if (es != QMPC_OK || ticks == 0) return es;      // ticks = 0: the buffers only
+  const qmpc_status ss = loop_setup(h, s, warm && !lpp.fused);
+  if (ss != QMPC_OK) return ss;
+  const qmpc_loop_params LP = *lp;
+  const qmpc_outcome_params OP = *op;
+  if (d_ctrl) HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_ctrl, inst_dev(h), inst_status(h)));
+  void* bcast = (!d_ctrl && lpp.fused) ? inst_dev(h) : nullptr;
+  if (d_ctrl || d_plant)
+    HIP_TRY(qmpc_loop_inst_expand_launch(s, &h->dev, sizeof h->dev, d_plant, d_ctrl, d_ctrl ? inst_status(h) : nullptr, bcast,
+                                         plant_dev(h), (int)batch));
+  else
+    HIP_TRY(qmpc_loop_outcome_expand_base_launch(s, &h->dev, sizeof h->dev, bcast, plant_dev(h), (int)batch));
+  if (lpp.fused) {
+    HIP_TRY(qmpc_loop_outcome_fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, &OP, d_states, h->d_in,
+                                           h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, d_outcomes, (int)ticks,
+                                           lpp.gws ? h->d_gws : nullptr));
+    return QMPC_OK;
+  }
+  auto one_tick = [&](bool first) -> qmpc_status {
+    HIP_TRY(qmpc_loop_outcome_front_launch(s, &LP, &OP, d_states, h->d_in, h->d_loop_row, plant_dev(h), d_outcomes, (int)batch));
+    if (d_ctrl) {
+      HIP_TRY(qmpc_wform_inst_solve_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces,
+                                           h->d_info, nullptr, nullptr, lpp.gws ? h->d_gws : nullptr));
+      h->last_kernel = lpp.family;
+    } else {
+      const qmpc_status st = loop_tick_solve(h, batch, s, warm, first, false);
+      if (st != QMPC_OK) return st;
+    }
+    HIP_TRY(qmpc_loop_outcome_post_launch(s, &LP, &OP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts,
+                                          h->d_loop_row, plant_dev(h), d_outcomes, (int)batch));
+    return QMPC_OK;
+  };
+  return replay_ticks(h, lpp, s, ticks, warm, one_tick);
+}
+
+qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                   const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                   double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes) {
+  if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!states || !outcomes))) return QMPC_BAD_ARGUMENT;
+  const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  HIP_TRY(hipSetDevice(h->device));
+  qmpc_status es = ensure_instance_buffers(h);
+  if (es == QMPC_OK) es = ensure_plant_buffers(h);
+  if (es != QMPC_OK || ticks == 0) return es;
+  if (!h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
+  // states and traces through the staging of qmpc_loop_run (loop_run_host), the records through their own
+  const size_t B = (size_t)batch, T = (size_t)ticks;
+  const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
+               n_tc = trace_contacts ? 4 * B * T : 0;
+  if (h->loop_cap < n_st + n_tf + n_tc) {
+    if (h->d_loop) (void)hipFree(h->d_loop);
+    h->d_loop = nullptr;
+    h->loop_cap = 0;
+    HIP_TRY(hipMalloc(&h->d_loop, sizeof(double) * (n_st + n_tf + n_tc)));
+    h->loop_cap = n_st + n_tf + n_tc;
+  }
+  qmpc_loop_state* d_st = reinterpret_cast<qmpc_loop_state*>(h->d_loop);
+  double* d_tf = trace_forces ? h->d_loop + n_st : nullptr;
+  double* d_tc = trace_contacts ? h->d_loop + n_st + n_tf : nullptr;
+  HIP_TRY(hipMemcpyAsync(d_st, states, sizeof(qmpc_loop_state) * B, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_outcome, outcomes, sizeof(qmpc_loop_outcome) * B, hipMemcpyHostToDevice, h->stream));
+  if (ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
+  if (plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
+  const qmpc_status rs = qmpc_loop_run_outcomes_device(h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr,
+                                                       plant ? plant_rec(h) : nullptr, d_tf, d_tc, op, h->d_outcome, nullptr);
+  if (rs != QMPC_OK) return rs;
+  HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(outcomes, h->d_outcome, sizeof(qmpc_loop_outcome) * B, hipMemcpyDeviceToHost, h->stream));
+  if (d_tf) HIP_TRY(hipMemcpyAsync(trace_forces, d_tf, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream));
+  if (d_tc) HIP_TRY(hipMemcpyAsync(trace_contacts, d_tc, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return QMPC_OK;
 }
 
 // Diagnostic: per-instance phase cycle counts (s_memtime) of one solve launch.

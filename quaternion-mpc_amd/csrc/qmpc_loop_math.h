@@ -6,6 +6,8 @@
 
 #include <math.h>
 
+#include "../../include/qmpc.h"      // the outcome record of loop_outcome_one
+
 #if defined(__HIPCC__)
 #define QMPC_HD __host__ __device__ inline
 #else
@@ -151,6 +153,49 @@ QMPC_HD void plant_step_ext(double* x, const double* u, const double* feet_world
   for (int i = 0; i < 13; ++i) x[i] = x[i] + dt * k2[i];
   const double n = sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] + x[6] * x[6]);
   for (int i = 3; i < 7; ++i) x[i] = x[i] / n;
+}
+
+// One tick of a robot's outcome record (qmpc_loop_run_outcomes*, include/qmpc.h): s is the robot's state AFTER the post step of
+// the tick -- the new plant state, this tick's lin_vel_d_rel and joy, the applied forces_body, status and iterations.  A record
+// whose down_tick is set is frozen.  Minima and maxima are selections by `<` / `>`: a non-finite value selects nothing (it
+// makes the robot down instead).  The tick that leaves the robot down is accumulated, then down_tick = s.tick.
+// One source for the device kernels (qmpc_loop_outcome.hip), the host class (host/ClosedLoopHost.h) and the native test.
+QMPC_HD void loop_outcome_one(const qmpc_outcome_params& op, const qmpc_loop_state& s, qmpc_loop_outcome& o) {
+  QMPC_NO_CONTRACT
+  if (o.down_tick >= 0.0) return;
+  double R[9];
+  quat_to_rot(s.quat, R);
+  const double height = s.pos_world[2], upright = R[8];
+  o.ticks += 1.0;
+  if (height < o.min_height) o.min_height = height;
+  if (upright < o.min_upright) o.min_upright = upright;
+  const double he = fabs(height - s.joy[2]);
+  if (he > o.max_height_err) o.max_height_err = he;
+  const double vx = R[0] * s.lin_vel_world[0] + R[3] * s.lin_vel_world[1] + R[6] * s.lin_vel_world[2];
+  const double vy = R[1] * s.lin_vel_world[0] + R[4] * s.lin_vel_world[1] + R[7] * s.lin_vel_world[2];
+  const double dx = vx - s.lin_vel_d_rel[0], dy = vy - s.lin_vel_d_rel[1];
+  const double e2 = dx * dx + dy * dy;
+  const double ev = sqrt(e2);
+  if (ev > o.max_vel_err) o.max_vel_err = ev;
+  o.sum_vel_err_sq += e2;
+  for (int a = 0; a < 3; ++a) {
+    const double w = fabs(s.ang_vel_body[a]);
+    if (w > o.max_ang_vel) o.max_ang_vel = w;
+  }
+  for (int l = 0; l < 4; ++l)
+    if (s.forces_body[3 * l + 2] > o.max_force_z) o.max_force_z = s.forces_body[3 * l + 2];
+  if (s.status != (double)QMPC_OK) {
+    o.not_ok_ticks += 1.0;
+    if (s.status != (double)QMPC_MAX_ITER) {
+      o.rejected_ticks += 1.0;
+      if (o.first_rejected_tick < 0.0) o.first_rejected_tick = s.tick;
+    }
+  }
+  o.iterations_sum += s.iterations;
+  if (s.iterations > o.iterations_max) o.iterations_max = s.iterations;
+  // down: either value non-finite (x - x is 0 only for a finite x) or below its threshold
+  const bool finite = (height - height == 0.0) && (upright - upright == 0.0);
+  if (!finite || height < op.down_height || upright < op.down_upright) o.down_tick = s.tick;
 }
 
 // Condition matrix of the swing-foot quintic p(t) = sum_k a_k t^k (QuinticCurve::get_foot_swing_target,

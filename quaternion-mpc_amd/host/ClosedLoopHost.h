@@ -31,6 +31,9 @@ class ClosedLoopHostBase {
   virtual void joint_commands(double* joint_pos_io, qmpc_joint_feedback* fb, qmpc_joint_command* cmd) = 0;
   virtual qmpc_status device_status() const = 0;
   virtual void set_warm_start(bool on) = 0;
+  // the robot's outcome record (qmpc_loop_run_outcomes*): fed by every tick, thresholds as set here (default: the ABI's)
+  virtual void set_outcome_params(const qmpc_outcome_params& op) = 0;
+  virtual const qmpc_loop_outcome& outcome() const = 0;
   State state;
 };
 
@@ -48,6 +51,8 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
                   int mode = QMPC_MODE_CONVERGED, int drop_ang_vel = 1, const qmpc_instance_params* ctrl = nullptr,
                   const qmpc_plant_params* plant = nullptr)
       : lp_(lp) {
+    op_.down_height = 0.15; op_.down_upright = 0.5; op_.stop_when_down = 0.0; op_.reserved = 0.0;   // qmpc_default_outcome_params
+    reset_outcome();
     if (kConvex) {                     // gazebo_go1_convex_mpc.yaml: 5 ms, the Euler-angle state's weights, mu 0.6, fz_max 200
       state.param.mpc_update_period = 5.0;
       const double q[13] = {3.0, 3.0, 3.0, 1.0, 1.0, 20.0, 0.0, 0.0, 3.0, 2.0, 3.0, 2.0, 0.0};
@@ -84,6 +89,14 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   ~ClosedLoopHostT() override { delete mpc; }
   qmpc_status device_status() const override { return mpc->last_status(); }
   void set_warm_start(bool on) override { warm(on); }
+  void set_outcome_params(const qmpc_outcome_params& op) override { op_ = op; }
+  const qmpc_loop_outcome& outcome() const override { return outcome_; }
+  void reset_outcome() {                                    // qmpc_loop_outcome_init
+    std::memset(&outcome_, 0, sizeof outcome_);
+    outcome_.down_tick = outcome_.first_rejected_tick = -1.0;
+    outcome_.min_height = outcome_.min_upright = HUGE_VAL;
+    outcome_.max_height_err = outcome_.max_vel_err = outcome_.max_ang_vel = outcome_.max_force_z = outcome_.iterations_max = -HUGE_VAL;
+  }
 
   // what BaseInterface::fbk_update derives from the estimator for the fields the tick reads
   void refresh_feedback() {
@@ -136,6 +149,12 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
         if (!state.ctrl.plan_contacts[l])
           for (int a = 0; a < 3; ++a) feet_[3 * l + a] = mpc->leg_FSM[l].FSM_foot_pos_target_world[a];
     ticks_ += 1;
+    {   // the outcome step of the device tick, on the same record layout: the arithmetic is the device's (qmpc_loop_math.h).
+        // The host robot goes on ticking when it is down (stop_when_down is the device loop's); its record is frozen then.
+      qmpc_loop_state after;
+      export_state(&after);
+      qmpc_loop::loop_outcome_one(op_, after, outcome_);
+    }
     return ok;
   }
 
@@ -260,6 +279,8 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   double Iinv_[9];
   qmpc_plant_params plant_{};
   bool has_plant_ = false;
+  qmpc_outcome_params op_;
+  qmpc_loop_outcome outcome_;
   long ticks_ = 0;
 };
 

@@ -261,6 +261,9 @@ void qh_leg_inverse(int batch, const double* foot_pos_body, const double* cur_jo
 void qh_loop_set_warm_start(void* p, int on) { static_cast<LoopHarness*>(p)->loop->set_warm_start(on != 0); }
 void qh_loop_set_sin_ang_vel(void* p, int on) { static_cast<LoopHarness*>(p)->loop->state.joy.sin_ang_vel = on != 0; }
 void qh_loop_export(void* p, qmpc_loop_state* out) { static_cast<LoopHarness*>(p)->loop->export_state(out); }
+// the robot's outcome record (qmpc_loop_outcome) after the ticks made so far; its thresholds (default: qmpc_default_outcome_params)
+void qh_loop_outcome(void* p, qmpc_loop_outcome* out) { *out = static_cast<LoopHarness*>(p)->loop->outcome(); }
+void qh_loop_set_outcome_params(void* p, const qmpc_outcome_params* op) { static_cast<LoopHarness*>(p)->loop->set_outcome_params(*op); }
 void qh_loop_destroy(void* p) {
   LoopHarness* h = static_cast<LoopHarness*>(p);
   if (!h) return;

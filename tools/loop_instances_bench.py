@@ -4,7 +4,12 @@ plant records (qmpc_loop_run_instances_device), uniform records (every robot car
 walking with different commands, device buffers, one handle per size.  The three calls alternate on the same states (copied
 back before each call), each timed with device events around the call after warm-up; median of the repetitions.  The
 per-robot calls include their expansion kernels.
-    python tools/loop_instances_bench.py [--reps 5] [--warmup 1] [--ticks 50] [--sizes 10:1024,10:4096,10:65536] [--json FILE]"""
+    python tools/loop_instances_bench.py [--reps 5] [--warmup 1] [--ticks 50] [--sizes 10:1024,10:4096,10:65536] [--json FILE]
+--outcomes: the same two per-robot calls through qmpc_loop_run_outcomes_device as well (empty records before every call), each
+    next to its qmpc_loop_run_instances_device twin: what accumulating the outcome records costs, as same-job pairs.
+--outcomes --stop: instead, a population of which half certainly falls (robots standing at 0.3 m, every second one pressed down
+    with 1000 N) through the outcome call with stop_when_down = 0 and = 1: time of each, and the solves that ran to the
+    iteration cap (from the records; for the run that does not stop, from a run whose thresholds never freeze a record)."""
 import argparse
 import importlib.util
 import json
@@ -26,6 +31,57 @@ def load_pkg():
     return mod
 
 
+def falling(pkg, lib, torch, N, B, a):
+    """the population of which half certainly falls, with and without stop_when_down (see the module docstring)"""
+    p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+    lp = pkg.default_loop_params(lib)
+    T = a.ticks
+    st = pkg.loop_states([[0.0, 0.0, 0.30, 0.0, 0.0, 0.0, 0.0]] * B, lp, height=0.3, yaw=np.linspace(-3, 3, B), lib=lib)
+    plant = pkg.plant_params(p, B)
+    plant["ext_force_world"][1::2, 2] = -1000.0
+    s = pkg.Solver(p, B, device=0, lib=lib)
+    s.prepare(B)
+    s.prepare_instances()
+    dev = lambda x: torch.from_numpy(x.view(np.uint8).copy()).cuda()      # noqa: E731
+    d_st0, d_oc0, d_plant = dev(st), dev(pkg.loop_outcomes(B, lib)), dev(plant)
+    d_st, d_oc = d_st0.clone(), d_oc0.clone()
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    torch.cuda.synchronize()
+    never = pkg.default_outcome_params(lib)
+    never.down_height = never.down_upright = -1e300      # only a non-finite state freezes a record: every solve is counted
+    ops = {"go": pkg.default_outcome_params(lib), "stop": pkg.default_outcome_params(lib, stop_when_down=True), "count": never}
+    times, recs = {k: [] for k in ops}, {}
+    for r in range(a.warmup + a.reps):
+        for k, op in ops.items():
+            with torch.cuda.stream(stream):
+                d_st.copy_(d_st0)
+                d_oc.copy_(d_oc0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            s.loop_run_outcomes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), lp, op, d_plant=d_plant.data_ptr(), stream=sp)
+            e1.record(stream)
+            e1.synchronize()
+            if r >= a.warmup:
+                times[k].append(e0.elapsed_time(e1))
+            recs[k] = d_oc.cpu().numpy().view(pkg.LOOP_OUTCOME_DTYPE).reshape(B)
+    form = s.loop_instances_plan(B, False, False)
+    s.close()
+    capped = lambda o: int((o["not_ok_ticks"] - o["rejected_ticks"]).sum())      # noqa: E731  (status QMPC_MAX_ITER)
+    ms = {k: float(np.median(v)) for k, v in times.items()}
+    row = {"N": N, "B": B, "ticks": T, "form": form, "down": int((recs["go"]["down_tick"] >= 0).sum()),
+           "go_ms": ms["go"], "stop_ms": ms["stop"], "stop_over_go": ms["stop"] / ms["go"],
+           "go_solves": int(recs["count"]["ticks"].sum()), "stop_solves": int(recs["stop"]["ticks"].sum()),
+           "go_capped_solves": capped(recs["count"]), "stop_capped_solves": capped(recs["stop"]),
+           "go_rejected_solves": int(recs["count"]["rejected_ticks"].sum()), "stop_rejected_solves": int(recs["stop"]["rejected_ticks"].sum())}
+    print(f"N={N:2d} B={B:6d} {form}: {row['down']} of {B} robots down within {T} ticks   simulated on {ms['go']:9.3f} ms "
+          f"(min {min(times['go']):.3f}, max {max(times['go']):.3f}; {row['go_solves']} solves, {row['go_capped_solves']} at the iteration cap, "
+          f"{row['go_rejected_solves']} rejected)   stop_when_down {ms['stop']:9.3f} ms (min {min(times['stop']):.3f}, max {max(times['stop']):.3f}; "
+          f"{row['stop_solves']} solves, {row['stop_capped_solves']} at the cap, {row['stop_rejected_solves']} rejected)   "
+          f"stop / go {row['stop_over_go']:.3f}", flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -33,14 +89,21 @@ def main():
     ap.add_argument("--ticks", type=int, default=50)
     ap.add_argument("--sizes", default=DEFAULT_SIZES)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--outcomes", action="store_true")
+    ap.add_argument("--stop", action="store_true")
     a = ap.parse_args()
     import torch
 
     pkg = load_pkg()
     lib = pkg.load_library()
     rows = []
+    if a.stop and not a.outcomes:
+        ap.error("--stop goes with --outcomes")
     for item in a.sizes.split(","):
         N, B = (int(x) for x in item.split(":"))
+        if a.stop:
+            rows.append(falling(pkg, lib, torch, N, B, a))
+            continue
         p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
         lp = pkg.default_loop_params(lib)
         rng = np.random.default_rng(5)
@@ -67,11 +130,22 @@ def main():
                  "plant": lambda: s.loop_run_instances_device(B, d_st.data_ptr(), T, lp, d_plant=d_plant.data_ptr(), stream=sp),
                  "ctrl_plant": lambda: s.loop_run_instances_device(B, d_st.data_ptr(), T, lp, d_ctrl=d_ctrl.data_ptr(),
                                                                    d_plant=d_plant.data_ptr(), stream=sp)}
+        if a.outcomes:
+            op = pkg.default_outcome_params(lib)
+            d_oc0 = torch.from_numpy(pkg.loop_outcomes(B, lib).view(np.uint8).copy()).cuda()
+            d_oc = d_oc0.clone()
+            calls["plant_outcomes"] = lambda: s.loop_run_outcomes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), lp, op,
+                                                                         d_plant=d_plant.data_ptr(), stream=sp)
+            calls["ctrl_plant_outcomes"] = lambda: s.loop_run_outcomes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), lp, op,
+                                                                              d_ctrl=d_ctrl.data_ptr(), d_plant=d_plant.data_ptr(), stream=sp)
+            calls = {k: calls[k] for k in ("plain", "plant", "plant_outcomes", "ctrl_plant", "ctrl_plant_outcomes")}
         times = {k: [] for k in calls}
         for r in range(a.warmup + a.reps):
             for k, fn in calls.items():
                 with torch.cuda.stream(stream):
                     d_st.copy_(d_st0)
+                    if a.outcomes:
+                        d_oc.copy_(d_oc0)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
                 fn()
@@ -80,6 +154,7 @@ def main():
                 if r >= a.warmup:
                     times[k].append(e0.elapsed_time(e1))
         forms = {"plain": None, "plant": s.loop_instances_plan(B, False, False), "ctrl_plant": s.loop_instances_plan(B, True, False)}
+        forms["plant_outcomes"], forms["ctrl_plant_outcomes"] = forms["plant"], forms["ctrl_plant"]
         s.close()
         ms = {k: float(np.median(v)) for k, v in times.items()}
         row = {"N": N, "B": B, "ticks": T}
@@ -93,6 +168,14 @@ def main():
         print(f"N={N:2d} B={B:6d}  plain {row['plain_Mrobot_ticks_s']:7.3f} M/s   plant {row['plant_Mrobot_ticks_s']:7.3f} M/s "
               f"({row['plant_ratio']:.3f}, {forms['plant']})   ctrl+plant {row['ctrl_plant_Mrobot_ticks_s']:7.3f} M/s "
               f"({row['ctrl_plant_ratio']:.3f}, {forms['ctrl_plant']})", flush=True)
+        if a.outcomes:
+            for k in ("plant", "ctrl_plant"):
+                spread = (max(times[k]) - min(times[k])) / ms[k]
+                row[k + "_outcomes_ratio"] = ms[k + "_outcomes"] / ms[k]
+                row[k + "_spread"] = spread
+                print(f"            {k:10s} instances call {ms[k]:9.3f} ms (min {min(times[k]):.3f}, max {max(times[k]):.3f})   outcome call "
+                      f"{ms[k + '_outcomes']:9.3f} ms (min {min(times[k + '_outcomes']):.3f}, max {max(times[k + '_outcomes']):.3f})   "
+                      f"outcome / instances {row[k + '_outcomes_ratio']:.4f}", flush=True)
     if a.json:
         Path(a.json).parent.mkdir(parents=True, exist_ok=True)
         Path(a.json).write_text(json.dumps(rows, indent=1) + "\n")

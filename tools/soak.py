@@ -70,10 +70,17 @@ if a.closed_loop:
     st = s.loop_run(st_init, 8, lp)
     st["movement_mode"] = cmds[:, 6]
     st0 = st.copy()
-    st, tf, tc = s.loop_run(st, a.ticks, lp, trace=True)
+    if a.mode == 0:      # the converged mode: the same loop accumulating per-robot outcome records on the device (the same bits)
+        st, oc, tf, tc = s.loop_run_outcomes(st, a.ticks, lp, trace=True)
+    else:
+        (st, tf, tc), oc = s.loop_run(st, a.ticks, lp, trace=True), None
     dt = time.time() - t0
     s.close()
-    down = (st["pos_world"][:, 2] < 0.15) | ~np.isfinite(st["pos_world"][:, 2])
+    down = (st["pos_world"][:, 2] < 0.15) | ~np.isfinite(st["pos_world"][:, 2])      # by the last state
+    if oc is not None:      # by the records: down at ANY tick (below 0.15 m or tilted beyond 60 degrees), and when
+        summary = pkg.summarize_outcomes(oc)
+        print("outcome records:", summary)
+        down = oc["down_tick"] >= 0
     fell = int(down.sum())
     if fell:
         print("down by movement_mode:", {int(m): int((down & (cmds[:, 6] == m)).sum()) for m in (0, 1)})
