@@ -378,12 +378,14 @@ qmpc_status qmpc_solve_instances_device(qmpc_handle* h, int32_t batch, const qmp
                                         qmpc_info* d_info, void* stream);
 /* allocate the per-instance buffers now (qmpc_prepare does not); under QMPC_INSTANCES_AUTO also the lane kernel's */
 qmpc_status qmpc_prepare_instances(qmpc_handle* h);
-/* Which kernel family qmpc_solve_instances* may take on this handle; holds until it is changed.  QMPC_BAD_ARGUMENT for a
- * null handle or an unknown value.  qmpc_query(QMPC_QUERY_KERNEL_FOR_INSTANCES / QMPC_QUERY_LAST_KERNEL) answer under the
- * current policy. */
+/* Which kernel family the calls with per-instance controller records may take on this handle -- qmpc_solve_instances* and the
+ * per-tick solves of qmpc_loop_run_instances* / qmpc_loop_run_outcomes* with ctrl; holds until it is changed.
+ * QMPC_BAD_ARGUMENT for a null handle or an unknown value.  qmpc_query(QMPC_QUERY_KERNEL_FOR_INSTANCES /
+ * QMPC_QUERY_LOOP_INSTANCES_PLAN / QMPC_QUERY_LAST_KERNEL) answer under the current policy, and qmpc_prepare allocates for it. */
 typedef enum qmpc_instances_policy {
   QMPC_INSTANCES_WAVE = 0,   /* default: the wave wrench-form kernels at every size */
-  QMPC_INSTANCES_AUTO = 1    /* lane per instance (with the straggler hand-off) from the measured switch-over on */
+  QMPC_INSTANCES_AUTO = 1    /* lane per instance (with the straggler hand-off) from the switch-over on: 16384 instances in
+                                qmpc_solve_instances* and in the closed loops' ticks with controller records */
 } qmpc_instances_policy;
 qmpc_status qmpc_set_instances_policy(qmpc_handle* h, int32_t policy);
 
@@ -630,7 +632,19 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
  * per-instance wrench-form kernel (qmpc_solve_instances*) with ctrl, the plain loop's solve without.  The records are
  * expanded once per call.  Buffers: those of qmpc_prepare_instances (764 B x max_batch) and per-robot plant blocks
  * (264 B x max_batch), allocated on first use; a call with ticks = 0 allocates both and launches nothing (e.g. before
- * the caller's own stream capture).  The per-tick form captures its tick after every allocation. */
+ * the caller's own stream capture).  The per-tick form captures its tick after every allocation.
+ *
+ * Under qmpc_set_instances_policy(h, QMPC_INSTANCES_AUTO) the per-tick solve with ctrl takes the lane kernel from the
+ * switch-over on (the larger of qmpc_solve_instances*' and the cold-started loop's: 16384 robots; QMPC_LANE_INST_MIN and
+ * QMPC_LANE_MIN move it): in every tick the stance sort -- ordered by the previous tick's iteration counts too, robots that
+ * will not solve (invalid record, frozen, halted) in a class of their own at the end, where they fill whole wavefronts that
+ * leave at once -- then qmpc_lane_inst_kernel to the loop's iteration cap and the per-instance list kernel on the stragglers
+ * (QMPC_KERNEL_LANE_HANDOFF; QMPC_KERNEL_LANE without hand-off).  The results then belong to the lane / hand-off rounding
+ * family: with uniform records the bytes of qmpc_loop_run_device at the same size, ~1e-10 N per solve from the wave
+ * family's.  Below the switch-over, without ctrl and under the default policy nothing changes, bit for bit.  The lane
+ * kernel's buffers (workspace, sort scratch, per-lane parameter rows, hand-off records) are allocated before the tick is
+ * captured, by a call with ticks = 0 too, and by qmpc_prepare(h, batch) under AUTO when `batch` robots with ctrl take
+ * this form; under the default policy no call allocates them. */
 typedef struct qmpc_plant_params {   /* 16 doubles, 128 B: the TRUE robot the plant integrates */
   double mass;
   double inertia[9];                 /* row-major, same convention as qmpc_params.inertia */
@@ -676,7 +690,9 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
  * QMPC_UNSUPPORTED for lp->warm_start != 0 or a handle without a wrench-form kernel -- and QMPC_BAD_ARGUMENT for a NULL op
  * or outcomes.  ctrl and plant may both be NULL: plain robots on the handle's parameters (still a QuatMpc converged
  * handle).  Buffers: those of qmpc_loop_run_instances*; the host-buffer call adds a staging buffer for the records (128 B x
- * max_batch) on its first use.  No other call allocates it. */
+ * max_batch) on its first use.  No other call allocates it.  Under QMPC_INSTANCES_AUTO the ticks with ctrl take the lane
+ * form of qmpc_loop_run_instances* from the same switch-over on; a halted robot then sorts into the class that will not
+ * solve, so a fleet of which many are down runs in fewer wavefronts. */
 typedef struct qmpc_outcome_params {   /* 4 doubles */
   double down_height;     /* default 0.15 m: down when pos_world[2] is below */
   double down_upright;    /* default 0.5 (cos of 60 deg tilt): down when the upright value is below */

@@ -889,7 +889,8 @@ class Solver:
 
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
-        as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN)."""
+        as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN).  Answers under the handle's
+        instances policy: with ctrl under "auto" the per-tick form is ("per_tick", "lane_handoff" / "lane") from the switch-over on."""
         v = self.query(QUERY_LOOP_INSTANCES_PLAN, int(batch) | (int(bool(ctrl)) << 32) | (int(bool(warm)) << 33))
         if v == 0:
             return None
@@ -899,9 +900,9 @@ class Solver:
         return KERNEL_FAMILY[self.query(QUERY_KERNEL_FOR_INSTANCES, batch)]
 
     def set_instances_policy(self, policy: str | int):
-        """Which kernel family solve_instances* may take on this handle (qmpc_set_instances_policy): "wave" (default: the wave
-        wrench-form kernels at every size) or "auto" (lane per instance with the straggler hand-off from the measured
-        switch-over on)."""
+        """Which kernel family solve_instances* and the ticks of loop_run_instances* / loop_run_outcomes* with controller records
+        may take on this handle (qmpc_set_instances_policy): "wave" (default: the wave wrench-form kernels at every size) or
+        "auto" (lane per instance with the straggler hand-off from the switch-over on).  prepare() allocates for the policy set."""
         value = INSTANCES_POLICY[policy] if isinstance(policy, str) else int(policy)
         st = self.lib.qmpc_set_instances_policy(self._h, value)
         if st != OK:

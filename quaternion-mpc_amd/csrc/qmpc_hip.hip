@@ -115,6 +115,13 @@ hipError_t qmpc_lane_inst_launch(int pslot, int batch, hipStream_t s, const void
                                  const void* dev_blocks, const int* status, double* forces, qmpc_info* info, double* ws, double* prm,
                                  unsigned slots, const int* perm, double* traj_u, double* traj_x, int iter_cap, int* hcount, int* hsel,
                                  double* hstate, int hcap, int pair);
+hipError_t qmpc_lane_inst_upload_params(int pslot, hipStream_t s, const void* dev_params, size_t dev_params_size);
+hipError_t qmpc_lane_inst_launch_only(int pslot, int batch, hipStream_t s, const void* in, const void* dev_blocks, const int* status,
+                                      double* forces, qmpc_info* info, double* ws, double* prm, unsigned slots, const int* perm,
+                                      double* traj_u, double* traj_x, int iter_cap, int* hcount, int* hsel, double* hstate, int hcap,
+                                      int pair);
+hipError_t qmpc_lane_inst_sort_loop_launch(int batch, hipStream_t s, const void* in, const qmpc_info* prev, const int* status,
+                                           int idle_last, int* scratch);
 hipError_t qmpc_wform_inst_list_set_lds();
 hipError_t qmpc_wform_inst_list_launch(int var, int grid, size_t lds, hipStream_t s, const void* dev_blocks, const qmpc_input* in,
                                        double* forces, qmpc_info* info, double* traj_u, double* traj_x, const int* sel,
@@ -787,6 +794,7 @@ static bool handoff_active(const qmpc_handle* h) {
 // the handle's large-batch results belong to.
 static qmpc_status ensure_instance_buffers(qmpc_handle* h);
 static qmpc_status ensure_lane_inst_buffers(qmpc_handle* h, bool handoff);
+static qmpc_status ensure_plant_buffers(qmpc_handle* h);
 qmpc_status qmpc_prepare(qmpc_handle* h, int32_t batch) {
   if (!h || batch < 1) return QMPC_BAD_ARGUMENT;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
@@ -803,6 +811,14 @@ qmpc_status qmpc_prepare(qmpc_handle* h, int32_t batch) {
   if (h->inst_policy == QMPC_INSTANCES_AUTO && plan_instances(h->sel, batch, h->inst_policy, true, h->handoff_failed).variant == 4) {
     qmpc_status es = ensure_instance_buffers(h);
     if (es == QMPC_OK) es = ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_PLAIN, h->handoff_failed) != 0);
+    if (es != QMPC_OK) return es;
+  }
+  // ... and for the ticks of qmpc_loop_run_instances* / qmpc_loop_run_outcomes* with controller records, with the plant blocks
+  if (h->inst_policy == QMPC_INSTANCES_AUTO &&
+      plan_loop_instances(h->sel, batch, true, false, h->inst_policy, h->handoff_failed).variant == 4) {
+    qmpc_status es = ensure_instance_buffers(h);
+    if (es == QMPC_OK) es = ensure_plant_buffers(h);
+    if (es == QMPC_OK) es = ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_LOOP_TICK, h->handoff_failed) != 0);
     if (es != QMPC_OK) return es;
   }
   // the pinned staging of the host-buffer calls: ALWAYS (a handle prepared for a lane-kernel batch may still be handed a smaller
@@ -1014,7 +1030,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
     case QMPC_QUERY_LOOP_INSTANCES_PLAN: {
       const int64_t b = arg & 0xffffffffLL;
       if (b < 1 || b > h->max_batch) return QMPC_BAD_ARGUMENT;
-      const qmpc_plan p = plan_loop_instances(h->sel, (int)b, (arg >> 32) & 1, (arg >> 33) & 1, h->handoff_failed);
+      const qmpc_plan p = plan_loop_instances(h->sel, (int)b, (arg >> 32) & 1, (arg >> 33) & 1, h->inst_policy, h->handoff_failed);
       *value = p.family == QMPC_KERNEL_NONE ? 0 : 16 * (p.fused ? 1 : 2) + p.family;
       return QMPC_OK;
     }
@@ -1525,6 +1541,50 @@ static qmpc_status loop_instances_check(const qmpc_handle* h, const qmpc_loop_pa
   return QMPC_OK;
 }
 
+// The buffers of a call with records, allocated before anything is launched or captured (a call with ticks = 0 stops after
+// this): the per-instance and plant blocks and, where the ticks' solve is the lane kernel with per-lane parameters
+// (QMPC_INSTANCES_AUTO), its workspace, sort scratch, parameter rows and hand-off records.  *lpp: the call's plan -- re-planned
+// without the hand-off where its records could not be allocated.
+static qmpc_status loop_instances_buffers(qmpc_handle* h, int32_t batch, bool has_ctrl, bool warm, qmpc_plan* lpp) {
+  qmpc_status es = ensure_instance_buffers(h);
+  if (es == QMPC_OK) es = ensure_plant_buffers(h);
+  if (es != QMPC_OK) return es;
+  qmpc_plan p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed);
+  if (has_ctrl && !p.fused && p.variant == 4) {
+    es = ensure_lane_inst_buffers(h, false);
+    if (es != QMPC_OK) return es;
+    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed);
+  }
+  if (lpp) *lpp = p;
+  return QMPC_OK;
+}
+
+// The solve of one tick with controller records, as `p` plans it (h->d_in -> h->d_forces, h->d_info; the blocks expanded and the
+// buffers allocated already, the lane kernel's parameter block uploaded: nothing here but kernels and the hand-off counter's
+// memset, so the tick can be captured).  The lane form: the sort (stance mask, the previous records' iteration classes, robots
+// that will not solve last), qmpc_lane_inst_kernel to the cap, the per-instance list kernel on what it leaves.
+static qmpc_status loop_inst_tick_solve(qmpc_handle* h, const qmpc_plan& p, int32_t batch, hipStream_t s) {
+  if (p.variant == 4) {
+    const bool cap = p.iter_cap > 0;
+    if (h->sel.lane_sort)
+      HIP_TRY(qmpc_lane_inst_sort_loop_launch((int)batch, s, h->d_in, p.order_prev ? h->d_info : nullptr, inst_status(h),
+                                              h->sel.lane_sort_idle, h->d_lane_scratch));
+    HIP_TRY(qmpc_lane_inst_launch_only(h->lane_pslot, (int)batch, s, h->d_in, inst_dev(h), inst_status(h), h->d_forces, h->d_info,
+                                       h->d_lane_ws, h->d_lane_prm, h->lane_slots, h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr,
+                                       nullptr, nullptr, p.iter_cap, cap ? h->d_handoff : nullptr, cap ? h->d_handoff + 64 : nullptr,
+                                       cap ? h->d_hstate : nullptr, h->hstate_cap, h->sel.lane_pair));
+    if (cap)
+      HIP_TRY(qmpc_wform_inst_list_launch(p.handoff_variant, p.handoff_grid, p.lds, s, inst_dev(h), h->d_in, h->d_forces, h->d_info, nullptr,
+                                          nullptr, h->d_handoff + 64, h->d_handoff, p.gws ? h->d_gws : nullptr,
+                                          h->sel.handoff_restart ? nullptr : h->d_hstate, h->hstate_cap));
+  } else {      // the per-instance wrench-form kernel
+    HIP_TRY(qmpc_wform_inst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces, h->d_info,
+                                         nullptr, nullptr, p.gws ? h->d_gws : nullptr));
+  }
+  h->last_kernel = p.family;
+  return QMPC_OK;
+}
+
 qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
                                            int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                            double* d_trace_forces, double* d_trace_contacts, void* stream) {
@@ -1534,11 +1594,10 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
   const qmpc_status cs = loop_instances_check(h, lp, batch, d_ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
   const bool warm = lp->warm_start != 0.0;
-  const qmpc_plan lpp = plan_loop_instances(h->sel, batch, d_ctrl != nullptr, warm, h->handoff_failed);
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  qmpc_status es = ensure_instance_buffers(h);
-  if (es == QMPC_OK) es = ensure_plant_buffers(h);
+  qmpc_plan lpp;
+  const qmpc_status es = loop_instances_buffers(h, batch, d_ctrl != nullptr, warm, &lpp);
   if (es != QMPC_OK || ticks == 0) return es;      // ticks = 0: the buffers only (e.g. before the caller's stream capture)
   const qmpc_status ss = loop_setup(h, s, warm && !lpp.fused);
   if (ss != QMPC_OK) return ss;
@@ -1555,18 +1614,15 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
   }
   auto one_tick = [&](bool first) -> qmpc_status {
     HIP_TRY(qmpc_loop_inst_front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch));
-    if (d_ctrl) {      // the per-instance wrench-form kernel on the blocks expanded above
-      HIP_TRY(qmpc_wform_inst_solve_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces,
-                                           h->d_info, nullptr, nullptr, lpp.gws ? h->d_gws : nullptr));
-      h->last_kernel = lpp.family;
-    } else {           // the plain loop's solve
-      const qmpc_status st = loop_tick_solve(h, batch, s, warm, first, false);
-      if (st != QMPC_OK) return st;
-    }
+    // with controller records the solve on the blocks expanded above, without them the plain loop's
+    const qmpc_status st = d_ctrl ? loop_inst_tick_solve(h, lpp, batch, s) : loop_tick_solve(h, batch, s, warm, first, false);
+    if (st != QMPC_OK) return st;
     HIP_TRY(qmpc_loop_inst_post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts,
                                        h->d_loop_row, plant_dev(h), (int)batch));
     return QMPC_OK;
   };
+  // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
+  if (d_ctrl && lpp.variant == 4) HIP_TRY(qmpc_lane_inst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   return replay_ticks(h, lpp, s, ticks, warm, one_tick);
 }
 
@@ -1578,8 +1634,7 @@ qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, 
   const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
   HIP_TRY(hipSetDevice(h->device));
-  qmpc_status es = ensure_instance_buffers(h);
-  if (es == QMPC_OK) es = ensure_plant_buffers(h);
+  const qmpc_status es = loop_instances_buffers(h, batch, ctrl != nullptr, lp->warm_start != 0.0, nullptr);
   if (es != QMPC_OK || ticks == 0) return es;
   return loop_run_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts);
 }
@@ -1617,11 +1672,10 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
   const qmpc_status cs = loop_instances_check(h, lp, batch, d_ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
   const bool warm = lp->warm_start != 0.0;
-  const qmpc_plan lpp = plan_loop_instances(h->sel, batch, d_ctrl != nullptr, warm, h->handoff_failed);
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  qmpc_status es = ensure_instance_buffers(h);
-  if (es == QMPC_OK) es = ensure_plant_buffers(h);
+  qmpc_plan lpp;
+  const qmpc_status es = loop_instances_buffers(h, batch, d_ctrl != nullptr, warm, &lpp);
   if (es != QMPC_OK || ticks == 0) return es;      // ticks = 0: the buffers only
   const qmpc_status ss = loop_setup(h, s, warm && !lpp.fused);
   if (ss != QMPC_OK) return ss;
@@ -1642,18 +1696,14 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
   }
   auto one_tick = [&](bool first) -> qmpc_status {
     HIP_TRY(qmpc_loop_outcome_front_launch(s, &LP, &OP, d_states, h->d_in, h->d_loop_row, plant_dev(h), d_outcomes, (int)batch));
-    if (d_ctrl) {
-      HIP_TRY(qmpc_wform_inst_solve_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces,
-                                           h->d_info, nullptr, nullptr, lpp.gws ? h->d_gws : nullptr));
-      h->last_kernel = lpp.family;
-    } else {
-      const qmpc_status st = loop_tick_solve(h, batch, s, warm, first, false);
-      if (st != QMPC_OK) return st;
-    }
+    const qmpc_status st = d_ctrl ? loop_inst_tick_solve(h, lpp, batch, s) : loop_tick_solve(h, batch, s, warm, first, false);
+    if (st != QMPC_OK) return st;
     HIP_TRY(qmpc_loop_outcome_post_launch(s, &LP, &OP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts,
                                           h->d_loop_row, plant_dev(h), d_outcomes, (int)batch));
     return QMPC_OK;
   };
+  // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
+  if (d_ctrl && lpp.variant == 4) HIP_TRY(qmpc_lane_inst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   return replay_ticks(h, lpp, s, ticks, warm, one_tick);
 }
 
@@ -1664,8 +1714,7 @@ qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, i
   const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
   HIP_TRY(hipSetDevice(h->device));
-  qmpc_status es = ensure_instance_buffers(h);
-  if (es == QMPC_OK) es = ensure_plant_buffers(h);
+  const qmpc_status es = loop_instances_buffers(h, batch, ctrl != nullptr, lp->warm_start != 0.0, nullptr);
   if (es != QMPC_OK || ticks == 0) return es;
   if (!h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
   // states and traces through the staging of qmpc_loop_run (loop_run_host), the records through their own

@@ -179,27 +179,89 @@ __global__ __launch_bounds__(kLaneWave) void qmpc_lane_inst_kernel(int pslot, co
   }
 }
 
+// ---- the sort of a closed-loop tick with controller records ---------------------------------------------------------------------
+// The plain loop tick's keys (stance_key with the previous records: the stance mask and 16 classes of the last iteration count,
+// 256 keys) and one class more, ordered after all of them: robots that will NOT solve in this tick -- a rejected record
+// (status[b] != QMPC_OK) or the non-finite attitude the front kernels give frozen and halted robots (word 0 of the record).
+// Spread over the wavefronts by their stance masks they would shorten none; at the end of the order they fill whole wavefronts,
+// which leave after the set-up.  scratch as for qmpc_lane_sort_*: hist[256] | cursor[256] | perm[batch]; the last class is not
+// counted: after the scan nothing reads hist any more, and hist[0] becomes its cursor (it begins where the counted keys end).
+constexpr unsigned kKeyIdle = 256;
+__device__ __forceinline__ unsigned loop_sort_key(const double* __restrict__ in, int b, const qmpc_info* __restrict__ prev,
+                                                  const int* __restrict__ status, int idle_last) {
+  if (idle_last && (status[b] != QMPC_OK || !isfinite(in[(size_t)b * LDim<4>::REC]))) return kKeyIdle;
+  return stance_key<4>(in, b, LDim<4>::R_CON, prev);
+}
+__global__ __launch_bounds__(256) void qmpc_lane_loop_sort_count(const double* __restrict__ in, int batch, int* __restrict__ scratch,
+                                                                 const qmpc_info* __restrict__ prev, const int* __restrict__ status,
+                                                                 int idle_last) {
+  __shared__ int hist[256];
+  hist[threadIdx.x] = 0;
+  __syncthreads();
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < batch) {
+    const unsigned key = loop_sort_key(in, b, prev, status, idle_last);
+    if (key < kKeyIdle) atomicAdd(&hist[key], 1);
+  }
+  __syncthreads();
+  if (hist[threadIdx.x]) atomicAdd(&scratch[threadIdx.x], hist[threadIdx.x]);
+}
+__global__ __launch_bounds__(64) void qmpc_lane_loop_sort_scan(int* __restrict__ scratch) {
+  if (threadIdx.x != 0) return;
+  int run = 0;
+  for (int k = 0; k < 256; ++k) {
+    const int n = scratch[k];
+    scratch[256 + k] = run;
+    run += n;
+  }
+  scratch[0] = run;      // the cursor of the class that will not solve
+}
+__global__ __launch_bounds__(256) void qmpc_lane_loop_sort_scatter(const double* __restrict__ in, int batch, int* __restrict__ scratch,
+                                                                   const qmpc_info* __restrict__ prev, const int* __restrict__ status,
+                                                                   int idle_last) {
+  __shared__ int hist[257], base[257];
+  hist[threadIdx.x] = 0;
+  if (threadIdx.x == 0) hist[kKeyIdle] = 0;
+  __syncthreads();
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  unsigned key = 0;
+  int rank = 0;
+  if (b < batch) {
+    key = loop_sort_key(in, b, prev, status, idle_last);
+    rank = atomicAdd(&hist[key], 1);
+  }
+  __syncthreads();
+  if (hist[threadIdx.x]) base[threadIdx.x] = atomicAdd(&scratch[256 + threadIdx.x], hist[threadIdx.x]);
+  if (threadIdx.x == 0 && hist[kKeyIdle]) base[kKeyIdle] = atomicAdd(&scratch[0], hist[kKeyIdle]);
+  __syncthreads();
+  if (b < batch) scratch[512 + base[key] + rank] = b;
+}
+
 }  // namespace lane
 }  // namespace qmpc
 
 __attribute__((visibility("hidden"))) size_t qmpc_lane_inst_param_bytes(unsigned slots) {
   return sizeof(double) * (size_t)LPR_ROWS * (size_t)slots;
 }
-// The launch of qmpc_lane_kernel<4> (qmpc_lane_launch) for per-instance records: dev_params is uploaded into this unit's table,
-// dev_blocks / status are the expansion kernel's outputs, prm qmpc_lane_inst_param_bytes(slots) bytes, perm the sort's
-// permutation (qmpc_lane_sort_launch) or null.
-__attribute__((visibility("hidden"))) hipError_t qmpc_lane_inst_launch(int pslot, int batch, hipStream_t s, const void* dev_params,
-                                                                        size_t dev_params_size, const void* in, const void* dev_blocks,
-                                                                        const int* status, double* forces, qmpc_info* info, double* ws,
-                                                                        double* prm, unsigned slots, const int* perm, double* traj_u,
-                                                                        double* traj_x, int iter_cap, int* hcount, int* hsel,
-                                                                        double* hstate, int hcap, int pair) {
-  if (dev_params_size != sizeof(DevParams) || slots % kLaneWave || pslot < 0 || pslot >= kParamSlots) return hipErrorInvalidValue;
-  hipError_t e = hipMemcpyToSymbolAsync(HIP_SYMBOL(ql_params), dev_params, sizeof(DevParams), sizeof(DevParams) * (size_t)pslot,
-                                        hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return e;
+// The launch of qmpc_lane_kernel<4> (qmpc_lane_launch) for per-instance records in two parts.  The upload: the handle's block
+// into this unit's table (once per closed-loop call, outside its capture; before every launch of qmpc_solve_instances*).
+__attribute__((visibility("hidden"))) hipError_t qmpc_lane_inst_upload_params(int pslot, hipStream_t s, const void* dev_params,
+                                                                               size_t dev_params_size) {
+  if (dev_params_size != sizeof(DevParams) || pslot < 0 || pslot >= kParamSlots) return hipErrorInvalidValue;
+  return hipMemcpyToSymbolAsync(HIP_SYMBOL(ql_params), dev_params, sizeof(DevParams), sizeof(DevParams) * (size_t)pslot,
+                                hipMemcpyHostToDevice, s);
+}
+// ... and the launch (the hand-off counter's memset and the kernel: capturable): dev_blocks / status are the expansion kernel's
+// outputs, prm qmpc_lane_inst_param_bytes(slots) bytes, perm the sort's permutation (qmpc_lane_sort_launch,
+// qmpc_lane_inst_sort_loop_launch) or null.
+__attribute__((visibility("hidden"))) hipError_t qmpc_lane_inst_launch_only(int pslot, int batch, hipStream_t s, const void* in,
+                                                                             const void* dev_blocks, const int* status, double* forces,
+                                                                             qmpc_info* info, double* ws, double* prm, unsigned slots,
+                                                                             const int* perm, double* traj_u, double* traj_x, int iter_cap,
+                                                                             int* hcount, int* hsel, double* hstate, int hcap, int pair) {
+  if (slots % kLaneWave || pslot < 0 || pslot >= kParamSlots) return hipErrorInvalidValue;
   if (hcount) {
-    e = hipMemsetAsync(hcount, 0, 2 * sizeof(int), s);      // the list's length and the list kernel's cursor
+    const hipError_t e = hipMemsetAsync(hcount, 0, 2 * sizeof(int), s);      // the list's length and the list kernel's cursor
     if (e != hipSuccess) return e;
   }
   // (the rule of qmpc_lane_launch) batches that would occupy at most half of the chip's SIMDs with full wavefronts run with 32
@@ -212,5 +274,32 @@ __attribute__((visibility("hidden"))) hipError_t qmpc_lane_inst_launch(int pslot
   hipLaunchKernelGGL(qmpc_lane_inst_kernel, dim3(waves), dim3(kLaneWave), lds, s, pslot, static_cast<const double*>(in),
                      static_cast<const DevParams*>(dev_blocks), status, forces, info, batch, ws, prm, used, (lanes == 32 && pair) ? -34 : lanes,
                      perm, traj_u, traj_x, iter_cap, hcount, hsel, hstate, hcap);
+  return hipGetLastError();
+}
+// both parts: a launch of qmpc_solve_instances*
+__attribute__((visibility("hidden"))) hipError_t qmpc_lane_inst_launch(int pslot, int batch, hipStream_t s, const void* dev_params,
+                                                                        size_t dev_params_size, const void* in, const void* dev_blocks,
+                                                                        const int* status, double* forces, qmpc_info* info, double* ws,
+                                                                        double* prm, unsigned slots, const int* perm, double* traj_u,
+                                                                        double* traj_x, int iter_cap, int* hcount, int* hsel,
+                                                                        double* hstate, int hcap, int pair) {
+  if (slots % kLaneWave) return hipErrorInvalidValue;
+  const hipError_t e = qmpc_lane_inst_upload_params(pslot, s, dev_params, dev_params_size);
+  if (e != hipSuccess) return e;
+  return qmpc_lane_inst_launch_only(pslot, batch, s, in, dev_blocks, status, forces, info, ws, prm, slots, perm, traj_u, traj_x, iter_cap,
+                                    hcount, hsel, hstate, hcap, pair);
+}
+// The sort of a closed-loop tick with controller records (scratch: qmpc_lane_scratch_bytes(batch) bytes; the permutation is left at
+// scratch + 512).  prev: the previous solves' records (the handle's output buffer) or null; status: the expansion's verdicts;
+// idle_last = 0: the plain loop tick's keys for every robot.
+__attribute__((visibility("hidden"))) hipError_t qmpc_lane_inst_sort_loop_launch(int batch, hipStream_t s, const void* in, const qmpc_info* prev,
+                                                                                  const int* status, int idle_last, int* scratch) {
+  const double* rec = static_cast<const double*>(in);
+  const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(int) * 512, s);
+  if (e != hipSuccess) return e;
+  const unsigned blocks = (unsigned)((batch + 255) / 256);
+  hipLaunchKernelGGL(qmpc_lane_loop_sort_count, dim3(blocks), dim3(256), 0, s, rec, batch, scratch, prev, status, idle_last);
+  hipLaunchKernelGGL(qmpc_lane_loop_sort_scan, dim3(1), dim3(64), 0, s, scratch);
+  hipLaunchKernelGGL(qmpc_lane_loop_sort_scatter, dim3(blocks), dim3(256), 0, s, rec, batch, scratch, prev, status, idle_last);
   return hipGetLastError();
 }

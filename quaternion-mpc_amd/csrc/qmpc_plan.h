@@ -19,12 +19,16 @@ namespace qmpc {
 //   QMPC_WFORM            1 (default) the wrench-form kernels where they apply, 0 the round-1 family only, 3 its all-LDS form only
 //   QMPC_LANE_MIN         the converged mode's switch-over to the lane kernel (plain solves, warm starts and loops alike)
 //   QMPC_LANE_REF_MIN     ... the reference mode's (its closed loop included)
-//   QMPC_LANE_INST_MIN    ... of qmpc_solve_instances* under QMPC_INSTANCES_AUTO (per-instance parameters on the lane kernel)
+//   QMPC_LANE_INST_MIN    ... of qmpc_solve_instances* under QMPC_INSTANCES_AUTO (per-instance parameters on the lane kernel); the
+//                         ticks of qmpc_loop_run_instances* / qmpc_loop_run_outcomes* with controller records switch over at the
+//                         larger of this and the cold-started loop's own switch-over (QMPC_LANE_MIN moves that one)
 //   QMPC_LANE_CAP, QMPC_LANE_CAP_LOOP, QMPC_LANE_CAP_WARM
 //                         iteration cap of the lane kernel before the straggler hand-off: cold plain solves, cold-started
 //                         loops, warm-started loop ticks (0: no hand-off)
 //   QMPC_HANDOFF_RESTART  1: the hand-off's wave kernel ignores the state records and solves the list from scratch
 //   QMPC_LANE_SORT        0: the lane kernel takes the batch in its own order (default 1: sorted by stance mask)
+//   QMPC_LANE_SORT_IDLE   0: the sort of a loop tick with controller records on the lane kernel keeps robots that will not solve
+//                         (rejected record, frozen, halted) among the others (diagnostic; default 1: a class of their own, last)
 //   QMPC_LANE_PAIR        0: half-filled lane wavefronts run with half their lanes masked, not as lane pairs (2, 4: partial splits)
 //   QMPC_LOOP_FUSED       0 / 1: the closed loop's per-tick launches / persistent kernel at every batch size
 //   QMPC_REF_WFORM_MAXN   the longest horizon the reference mode takes the wrench form on (default: all)
@@ -46,6 +50,7 @@ struct qmpc_select {
   int lane_cap, lane_cap_loop, lane_cap_warm;
   bool handoff_restart;
   int lane_sort, lane_pair, loop_fused, ref_wform_maxn, zero_copy;
+  int lane_sort_idle;     // loop ticks with controller records on the lane kernel: robots that will not solve sort last
 };
 
 static inline int model_nl(int model) { return model == QMPC_MODEL_QUAT8 ? 8 : 4; }
@@ -321,6 +326,25 @@ static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, boo
   if (f.fused && (f.variant == 3 || f.variant == 5 || f.variant == 6)) return f;
   qmpc_plan p = has_ctrl ? plan_instances(s, batch)
                          : plan(s, batch, warm ? QMPC_CALL_WARM_LOOP_TICK : QMPC_CALL_LOOP_TICK, true, handoff_failed);
+  p.fused = false;
+  return p;
+}
+
+// ... under the handle's qmpc_instances_policy.  WAVE: the rule above.  AUTO: the same without controller records, where it
+// refuses the call, where it takes the persistent kernel, on a handle without a slot of the lane kernel's parameter table and
+// below the switch-over -- the larger of the two switch-overs the tick combines, qmpc_solve_instances*' (lane_min_inst) and the
+// cold-started loop's (lane_min_loop_cold): 16384 robots with the defaults (16384 and 14336 / 14848).  From there on the lane fields of the plain loop's
+// cold tick for this batch (qmpc_lane_inst_kernel to the loop's cap, the per-instance list kernel on what it leaves, the batch
+// ordered by the previous records too, the parameter block uploaded once per call).  QMPC_VARIANT=4: the pure lane kernel
+// wherever the per-tick form runs, as for the plain loop.
+static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, bool has_ctrl, bool warm, int policy, bool handoff_failed) {
+  const qmpc_plan w = plan_loop_instances(s, batch, has_ctrl, warm, handoff_failed);
+  if (!has_ctrl || policy != QMPC_INSTANCES_AUTO || w.family == QMPC_KERNEL_NONE || w.fused || !s.lane_slot) return w;
+  if (s.variant != 4 && batch < (s.lane_min_inst > s.lane_min_loop_cold ? s.lane_min_inst : s.lane_min_loop_cold)) return w;
+  qmpc_select l = s;
+  l.lane_min_loop_cold = 0;      // the switch-over is this call's own: the plain tick's plan only names the lane kernel's fields
+  qmpc_plan p = plan(l, batch, QMPC_CALL_LOOP_TICK, true, handoff_failed);
+  if (p.variant != 4) return w;
   p.fused = false;
   return p;
 }

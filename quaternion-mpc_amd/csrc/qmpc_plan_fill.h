@@ -149,6 +149,7 @@ inline bool qmpc_fill_select(qmpc_select* h, const qmpc_params* params, Env env,
   h->handoff_restart = knob("QMPC_HANDOFF_RESTART", 0) != 0;
   h->lane_sort = knob("QMPC_LANE_SORT", 1);
   h->lane_pair = knob("QMPC_LANE_PAIR", 1);
+  h->lane_sort_idle = knob("QMPC_LANE_SORT_IDLE", 1);
   const char* lf = env("QMPC_LOOP_FUSED");
   h->loop_fused = lf ? (lf[0] == '0' ? 0 : 1) : -1;
   h->ref_wform_maxn = knob("QMPC_REF_WFORM_MAXN", QMPC_MAX_HORIZON);

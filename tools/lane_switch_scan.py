@@ -4,7 +4,10 @@ choice with QMPC_LANE_MIN huge (wave side) and 1 (lane side), same records, kern
 GPU box:  python tools/lane_switch_scan.py [--cases N:B,...]
 --instances: the same for qmpc_solve_instances_device with random-variant records -- QMPC_INSTANCES_WAVE against
 QMPC_INSTANCES_AUTO with QMPC_LANE_INST_MIN=1 on one handle per horizon, batches 8192 ... 65536 in steps of 2048 at N=10 and N=20
-(the switch-over lane_min_inst of qmpc_plan_fill.h is the smallest size from which the lane path wins at every larger one)."""
+(the switch-over lane_min_inst of qmpc_plan_fill.h is the smallest size from which the lane path wins at every larger one).
+--loop-instances: the same for the ticks of qmpc_loop_run_instances_device with random-variant controller and plant records -- WAVE
+against AUTO with QMPC_LANE_INST_MIN=1 and QMPC_LANE_MIN=1 on one handle per horizon, robots walking with different commands,
+--ticks ticks per call timed with device events (the switch-over of plan_loop_instances' policy overload, qmpc_plan.h)."""
 import argparse, os, sys
 from pathlib import Path
 import numpy as np
@@ -15,10 +18,64 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--cases", default="10:12288,10:16384,10:20480,10:24576,16:12288,16:16384,16:20480,20:12288,20:16384,20:20480,24:12288,24:16384")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--instances", action="store_true")
+ap.add_argument("--loop-instances", action="store_true")
+ap.add_argument("--ticks", type=int, default=20)
+ap.add_argument("--step", type=int, default=2048)
 ap.add_argument("--horizons", default="10,20")
 a = ap.parse_args()
 pkg = g._load_pkg(); lib = pkg.load_library()
 import torch  # noqa: E402
+if a.loop_instances:
+    os.environ["QMPC_LANE_INST_MIN"] = "1"
+    os.environ["QMPC_LANE_MIN"] = "1"      # (the tick's switch-over is the larger of the two)
+    BMAX, T = 65536, a.ticks
+    for N in (int(x) for x in a.horizons.split(",")):
+        p = pkg.default_params(N, 0, lib)
+        lp = pkg.default_loop_params(lib)
+        rng = np.random.default_rng(5)
+        cmds = np.zeros((BMAX, 7))
+        cmds[:, 0] = rng.uniform(-0.4, 0.4, BMAX); cmds[:, 1] = rng.uniform(-0.15, 0.15, BMAX)
+        cmds[:, 2] = rng.uniform(0.26, 0.32, BMAX); cmds[:, 5] = rng.uniform(-0.4, 0.4, BMAX)
+        cmds[:, 6] = (rng.random(BMAX) < 0.85).astype(float)
+        stand = cmds.copy(); stand[:, 6] = 0.0
+        st = pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, BMAX), lib=lib)
+        ctrl = pkg.random_go1_variants(BMAX, seed=13, base=p); ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
+        plant = pkg.random_go1_plants(BMAX, seed=11, base=p, payload=(-1.0, 3.0), force=(0.0, 10.0))
+        s = pkg.Solver(p, BMAX, 0, lib)
+        s.set_instances_policy("auto"); s.prepare(BMAX); s.prepare_instances()
+        st = s.loop_run_instances(st, 6, lp, ctrl=ctrl, plant=plant)
+        st["movement_mode"] = cmds[:, 6]
+        st = s.loop_run_instances(st, 10, lp, ctrl=ctrl, plant=plant)      # in gait
+        dev = lambda x: torch.from_numpy(x.view(np.uint8).copy()).cuda()  # noqa: E731
+        d_st0, d_ctrl, d_plant = dev(st), dev(ctrl), dev(plant)
+        d_st = d_st0.clone()
+        stream = torch.cuda.Stream(); torch.cuda.synchronize()
+        first, wins = None, []
+        for B in range(8192, BMAX + 1, a.step):
+            ms = {"wave": [], "auto": []}
+            for r in range(a.reps + 1):
+                for pol in ms:
+                    s.set_instances_policy(pol)
+                    with torch.cuda.stream(stream):
+                        d_st.copy_(d_st0)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    s.loop_run_instances_device(B, d_st.data_ptr(), T, lp, d_ctrl=d_ctrl.data_ptr(), d_plant=d_plant.data_ptr(), stream=stream.cuda_stream)
+                    e1.record(stream); e1.synchronize()
+                    if r >= 1: ms[pol].append(e0.elapsed_time(e1))
+            form = {}
+            for pol in ms:
+                s.set_instances_policy(pol); form[pol] = s.loop_instances_plan(B, True, False)[1]
+            mw, ml = float(np.median(ms["wave"])), float(np.median(ms["auto"]))
+            wins.append((B, ml < mw))
+            print(f"N={N} B={B}: wave {form['wave']} {mw:.3f} ms ({B * T / mw / 1e3:.3f} M robot-ticks/s) vs auto {form['auto']} {ml:.3f} ms "
+                  f"({B * T / ml / 1e3:.3f} M)  auto/wave x{mw / ml:.3f}", flush=True)
+        s.close()
+        for B, w in reversed(wins):
+            if not w: break
+            first = B
+        print(f"N={N}: the lane ticks are faster at every scanned size from {first} on", flush=True)
+    sys.exit(0)
 if a.instances:
     os.environ["QMPC_LANE_INST_MIN"] = "1"
     BMAX = 65536

@@ -9,7 +9,13 @@ per-robot calls include their expansion kernels.
     next to its qmpc_loop_run_instances_device twin: what accumulating the outcome records costs, as same-job pairs.
 --outcomes --stop: instead, a population of which half certainly falls (robots standing at 0.3 m, every second one pressed down
     with 1000 N) through the outcome call with stop_when_down = 0 and = 1: time of each, and the solves that ran to the
-    iteration cap (from the records; for the run that does not stop, from a run whose thresholds never freeze a record)."""
+    iteration cap (from the records; for the run that does not stop, from a run whose thresholds never freeze a record).
+--policy wave|auto|both: the handle's qmpc_instances_policy for the calls with controller records (default wave).  both: every
+    such call twice in the same job on the same records, under WAVE (the per-instance wave kernel in every tick) and under AUTO
+    (the lane kernel with per-lane parameters and its hand-off from the switch-over on), next to the plain loop's figure.  With
+    --outcomes --stop the falling population runs with uniform controller records under each policy asked for (auto: e.g. with
+    and without QMPC_LANE_SORT_IDLE=0 in the environment, the sort's class for robots that will not solve).
+--records uniform|random: every robot carries the handle's values (default), or random_go1_variants / random_go1_plants."""
 import argparse
 import importlib.util
 import json
@@ -31,8 +37,9 @@ def load_pkg():
     return mod
 
 
-def falling(pkg, lib, torch, N, B, a):
-    """the population of which half certainly falls, with and without stop_when_down (see the module docstring)"""
+def falling(pkg, lib, torch, N, B, a, policy=None):
+    """the population of which half certainly falls, with and without stop_when_down (see the module docstring); policy: None,
+    or the policy under which the call runs with uniform controller records"""
     p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
     lp = pkg.default_loop_params(lib)
     T = a.ticks
@@ -40,10 +47,13 @@ def falling(pkg, lib, torch, N, B, a):
     plant = pkg.plant_params(p, B)
     plant["ext_force_world"][1::2, 2] = -1000.0
     s = pkg.Solver(p, B, device=0, lib=lib)
+    if policy:
+        s.set_instances_policy(policy)
     s.prepare(B)
     s.prepare_instances()
     dev = lambda x: torch.from_numpy(x.view(np.uint8).copy()).cuda()      # noqa: E731
     d_st0, d_oc0, d_plant = dev(st), dev(pkg.loop_outcomes(B, lib)), dev(plant)
+    d_ctrl = dev(pkg.instance_params(p, B)) if policy else None
     d_st, d_oc = d_st0.clone(), d_oc0.clone()
     stream = torch.cuda.Stream()
     sp = stream.cuda_stream
@@ -59,22 +69,23 @@ def falling(pkg, lib, torch, N, B, a):
                 d_oc.copy_(d_oc0)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
-            s.loop_run_outcomes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), lp, op, d_plant=d_plant.data_ptr(), stream=sp)
+            s.loop_run_outcomes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), lp, op, d_ctrl=d_ctrl.data_ptr() if policy else 0,
+                                       d_plant=d_plant.data_ptr(), stream=sp)
             e1.record(stream)
             e1.synchronize()
             if r >= a.warmup:
                 times[k].append(e0.elapsed_time(e1))
             recs[k] = d_oc.cpu().numpy().view(pkg.LOOP_OUTCOME_DTYPE).reshape(B)
-    form = s.loop_instances_plan(B, False, False)
+    form = s.loop_instances_plan(B, policy is not None, False)
     s.close()
     capped = lambda o: int((o["not_ok_ticks"] - o["rejected_ticks"]).sum())      # noqa: E731  (status QMPC_MAX_ITER)
     ms = {k: float(np.median(v)) for k, v in times.items()}
-    row = {"N": N, "B": B, "ticks": T, "form": form, "down": int((recs["go"]["down_tick"] >= 0).sum()),
+    row = {"N": N, "B": B, "ticks": T, "policy": policy, "form": form, "down": int((recs["go"]["down_tick"] >= 0).sum()),
            "go_ms": ms["go"], "stop_ms": ms["stop"], "stop_over_go": ms["stop"] / ms["go"],
            "go_solves": int(recs["count"]["ticks"].sum()), "stop_solves": int(recs["stop"]["ticks"].sum()),
            "go_capped_solves": capped(recs["count"]), "stop_capped_solves": capped(recs["stop"]),
            "go_rejected_solves": int(recs["count"]["rejected_ticks"].sum()), "stop_rejected_solves": int(recs["stop"]["rejected_ticks"].sum())}
-    print(f"N={N:2d} B={B:6d} {form}: {row['down']} of {B} robots down within {T} ticks   simulated on {ms['go']:9.3f} ms "
+    print(f"N={N:2d} B={B:6d} {'policy ' + policy + ' ' if policy else ''}{form}: {row['down']} of {B} robots down within {T} ticks   simulated on {ms['go']:9.3f} ms "
           f"(min {min(times['go']):.3f}, max {max(times['go']):.3f}; {row['go_solves']} solves, {row['go_capped_solves']} at the iteration cap, "
           f"{row['go_rejected_solves']} rejected)   stop_when_down {ms['stop']:9.3f} ms (min {min(times['stop']):.3f}, max {max(times['stop']):.3f}; "
           f"{row['stop_solves']} solves, {row['stop_capped_solves']} at the cap, {row['stop_rejected_solves']} rejected)   "
@@ -91,6 +102,8 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--outcomes", action="store_true")
     ap.add_argument("--stop", action="store_true")
+    ap.add_argument("--policy", choices=("wave", "auto", "both"), default="wave")
+    ap.add_argument("--records", choices=("uniform", "random"), default="uniform")
     a = ap.parse_args()
     import torch
 
@@ -101,8 +114,12 @@ def main():
         ap.error("--stop goes with --outcomes")
     for item in a.sizes.split(","):
         N, B = (int(x) for x in item.split(":"))
+        policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
         if a.stop:
-            rows.append(falling(pkg, lib, torch, N, B, a))
+            if a.policy == "wave":      # (as before the policy existed: plant records only)
+                rows.append(falling(pkg, lib, torch, N, B, a))
+            else:
+                rows.extend(falling(pkg, lib, torch, N, B, a, pol) for pol in policies)
             continue
         p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
         lp = pkg.default_loop_params(lib)
@@ -114,31 +131,54 @@ def main():
         stand = cmds.copy(); stand[:, 6] = 0.0
         st = pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, B), lib=lib)
         s = pkg.Solver(p, B, device=0, lib=lib)
-        s.prepare(B)
+        for pol in policies:      # (the buffers of every policy asked for: allocated before anything is timed)
+            s.set_instances_policy(pol)
+            s.prepare(B)
         s.prepare_instances()
         st = s.loop_run(st, 6, lp)
         st["movement_mode"] = cmds[:, 6]
         d_st0 = torch.from_numpy(st.view(np.uint8).copy()).cuda()
         d_st = d_st0.clone()
-        d_ctrl = torch.from_numpy(pkg.instance_params(p, B).view(np.uint8).copy()).cuda()
-        d_plant = torch.from_numpy(pkg.plant_params(p, B).view(np.uint8).copy()).cuda()
+        if a.records == "random":
+            ctrl = pkg.random_go1_variants(B, seed=12, base=p)
+            ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
+            plant = pkg.random_go1_plants(B, seed=11, base=p, payload=(-1.0, 3.0), force=(0.0, 10.0))
+        else:
+            ctrl, plant = pkg.instance_params(p, B), pkg.plant_params(p, B)
+        d_ctrl = torch.from_numpy(ctrl.view(np.uint8).copy()).cuda()
+        d_plant = torch.from_numpy(plant.view(np.uint8).copy()).cuda()
         stream = torch.cuda.Stream()
         sp = stream.cuda_stream
         torch.cuda.synchronize()
         T = a.ticks
+        # the calls with controller records: "ctrl_plant" under the first policy asked for, "ctrl_plant_auto" the second of both
+        suffix = {pol: ("" if i == 0 else "_" + pol) for i, pol in enumerate(policies)}
+
+        def ctrl_call(pol):
+            s.set_instances_policy(pol)
+            s.loop_run_instances_device(B, d_st.data_ptr(), T, lp, d_ctrl=d_ctrl.data_ptr(), d_plant=d_plant.data_ptr(), stream=sp)
+
+        def ctrl_outcomes_call(pol):
+            s.set_instances_policy(pol)
+            s.loop_run_outcomes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), lp, op, d_ctrl=d_ctrl.data_ptr(), d_plant=d_plant.data_ptr(),
+                                       stream=sp)
+
         calls = {"plain": lambda: s.loop_run_device(B, d_st.data_ptr(), T, lp, stream=sp),
-                 "plant": lambda: s.loop_run_instances_device(B, d_st.data_ptr(), T, lp, d_plant=d_plant.data_ptr(), stream=sp),
-                 "ctrl_plant": lambda: s.loop_run_instances_device(B, d_st.data_ptr(), T, lp, d_ctrl=d_ctrl.data_ptr(),
-                                                                   d_plant=d_plant.data_ptr(), stream=sp)}
+                 "plant": lambda: s.loop_run_instances_device(B, d_st.data_ptr(), T, lp, d_plant=d_plant.data_ptr(), stream=sp)}
+        for pol in policies:
+            calls["ctrl_plant" + suffix[pol]] = lambda pol=pol: ctrl_call(pol)
         if a.outcomes:
             op = pkg.default_outcome_params(lib)
             d_oc0 = torch.from_numpy(pkg.loop_outcomes(B, lib).view(np.uint8).copy()).cuda()
             d_oc = d_oc0.clone()
             calls["plant_outcomes"] = lambda: s.loop_run_outcomes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), lp, op,
                                                                          d_plant=d_plant.data_ptr(), stream=sp)
-            calls["ctrl_plant_outcomes"] = lambda: s.loop_run_outcomes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), lp, op,
-                                                                              d_ctrl=d_ctrl.data_ptr(), d_plant=d_plant.data_ptr(), stream=sp)
-            calls = {k: calls[k] for k in ("plain", "plant", "plant_outcomes", "ctrl_plant", "ctrl_plant_outcomes")}
+            for pol in policies:
+                calls["ctrl_plant" + suffix[pol] + "_outcomes"] = lambda pol=pol: ctrl_outcomes_call(pol)
+            order = ["plain", "plant", "plant_outcomes"]
+            for pol in policies:
+                order += ["ctrl_plant" + suffix[pol], "ctrl_plant" + suffix[pol] + "_outcomes"]
+            calls = {k: calls[k] for k in order}
         times = {k: [] for k in calls}
         for r in range(a.warmup + a.reps):
             for k, fn in calls.items():
@@ -153,11 +193,14 @@ def main():
                 e1.synchronize()
                 if r >= a.warmup:
                     times[k].append(e0.elapsed_time(e1))
-        forms = {"plain": None, "plant": s.loop_instances_plan(B, False, False), "ctrl_plant": s.loop_instances_plan(B, True, False)}
-        forms["plant_outcomes"], forms["ctrl_plant_outcomes"] = forms["plant"], forms["ctrl_plant"]
+        forms = {"plain": None, "plant": s.loop_instances_plan(B, False, False)}
+        forms["plant_outcomes"] = forms["plant"]
+        for pol in policies:
+            s.set_instances_policy(pol)
+            forms["ctrl_plant" + suffix[pol]] = forms["ctrl_plant" + suffix[pol] + "_outcomes"] = s.loop_instances_plan(B, True, False)
         s.close()
         ms = {k: float(np.median(v)) for k, v in times.items()}
-        row = {"N": N, "B": B, "ticks": T}
+        row = {"N": N, "B": B, "ticks": T, "records": a.records, "policy": policies[0]}
         for k in calls:
             row[k + "_ms"] = ms[k]
             row[k + "_Mrobot_ticks_s"] = B * T / ms[k] / 1e3
@@ -167,9 +210,17 @@ def main():
         rows.append(row)
         print(f"N={N:2d} B={B:6d}  plain {row['plain_Mrobot_ticks_s']:7.3f} M/s   plant {row['plant_Mrobot_ticks_s']:7.3f} M/s "
               f"({row['plant_ratio']:.3f}, {forms['plant']})   ctrl+plant {row['ctrl_plant_Mrobot_ticks_s']:7.3f} M/s "
-              f"({row['ctrl_plant_ratio']:.3f}, {forms['ctrl_plant']})", flush=True)
+              f"({row['ctrl_plant_ratio']:.3f}, {policies[0]} policy, {forms['ctrl_plant']})", flush=True)
+        for pol in policies[1:]:
+            k = "ctrl_plant" + suffix[pol]
+            row[k + "_ratio"] = row[k + "_Mrobot_ticks_s"] / row["plain_Mrobot_ticks_s"]
+            row[k + "_over_" + policies[0]] = row[k + "_Mrobot_ticks_s"] / row["ctrl_plant_Mrobot_ticks_s"]
+            print(f"            {a.records} records, ctrl+plant under {pol}: {row[k + '_Mrobot_ticks_s']:7.3f} M/s ({row[k + '_ratio']:.3f} of plain, "
+                  f"{forms[k]})   {pol} / {policies[0]} x{row[k + '_over_' + policies[0]]:.3f}   ms min/median/max {min(times[k]):.3f} / "
+                  f"{ms[k]:.3f} / {max(times[k]):.3f} against {min(times['ctrl_plant']):.3f} / {ms['ctrl_plant']:.3f} / {max(times['ctrl_plant']):.3f}",
+                  flush=True)
         if a.outcomes:
-            for k in ("plant", "ctrl_plant"):
+            for k in ["plant"] + ["ctrl_plant" + suffix[pol] for pol in policies]:
                 spread = (max(times[k]) - min(times[k])) / ms[k]
                 row[k + "_outcomes_ratio"] = ms[k + "_outcomes"] / ms[k]
                 row[k + "_spread"] = spread
