@@ -732,6 +732,51 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
                                           double* d_trace_forces, double* d_trace_contacts,
                                           const qmpc_outcome_params* op, qmpc_loop_outcome* d_outcomes, void* stream);
 
+/* ---- timed push disturbances per robot (push recovery sweeps) ----------------------------------------------------------
+ * The plant's disturbance wrench is constant over a call; a push needs a window in time.  qmpc_loop_run_pushes* is
+ * qmpc_loop_run_outcomes* -- the same robots, launch forms (QMPC_QUERY_LOOP_INSTANCES_PLAN answers for it too), states,
+ * traces, outcome records, halting and freezing -- whose plant step integrates under the EFFECTIVE wrench of the tick.  Each
+ * robot carries pushes_per_robot windows: robot i's are push[i * pushes_per_robot + k].  The controller is not told.
+ *
+ * Window k acts in the tick that takes state.tick from t to t + 1 when t >= start_tick and t < start_tick + ticks (plain
+ * double comparisons: fractional values are legal and only shift where they flip; ticks <= 0 never acts).  state.tick is
+ * absolute, so a window spans calls: one call of T ticks equals calls of T1 + T2 ticks with the same records.
+ *
+ * Effective wrench, per component: start from the plant record's constant value (0 without plant records) and walk the
+ * windows in index order.  An active window whose component is not exactly zero REPLACES the running value when that is
+ * exactly zero and is ADDED to it with one IEEE add otherwise; an inactive window or an exactly zero component adds no
+ * arithmetic (the rule of the plant's own disturbance; loop_push_wrench, csrc/qmpc_loop_math.h: one source for the device,
+ * the host class and the tests).  So records that never act give the bytes of qmpc_loop_run_outcomes*, and one window over
+ * the whole run on a plant without constant disturbance gives the bytes of that plant with the wrench as its disturbance.
+ *
+ * push == NULL: pushes_per_robot is ignored and the call IS qmpc_loop_run_outcomes*.  A robot one of whose windows has a
+ * non-finite field is frozen with QMPC_BAD_PARAMS exactly like the robot of an invalid plant record: state untouched except
+ * status and iterations, zero trace rows, outcome record untouched, every other robot unaffected bit for bit.
+ * Call level: QMPC_BAD_ARGUMENT for a non-NULL push with pushes_per_robot outside 1 .. QMPC_MAX_PUSHES; everything else is
+ * the outcome call's refusal, unchanged.  Buffers: those of qmpc_loop_run_outcomes*; the device call reads d_push in place;
+ * the host-buffer call stages the windows in a buffer of its own (64 B x pushes_per_robot x max_batch), allocated on its
+ * first use -- a call with ticks = 0 included -- and grown when pushes_per_robot grows.  No other call allocates it. */
+#define QMPC_MAX_PUSHES 8
+typedef struct qmpc_push_params {   /* 8 doubles, 64 B: one push window of one robot */
+  double start_tick;        /* first tick it acts in, counted in state.tick (absolute: carries over calls) */
+  double ticks;             /* length of the window in ticks; <= 0: no push */
+  double force_world[3];    /* at the CoM, world frame [N] */
+  double torque_body[3];    /* body frame [N m] */
+} qmpc_push_params;
+int32_t qmpc_sizeof_push_params(void);
+/* Host buffers: qmpc_loop_run_outcomes' arguments, then push [batch][pushes_per_robot].  Synchronous. */
+qmpc_status qmpc_loop_run_pushes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                 int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant,
+                                 double* trace_forces, double* trace_contacts, const qmpc_outcome_params* op,
+                                 qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int32_t pushes_per_robot);
+/* Device buffers (op is a host pointer, read during the call), stream-ordered (NULL stream = the handle's). */
+qmpc_status qmpc_loop_run_pushes_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch,
+                                        qmpc_loop_state* d_states, int32_t ticks,
+                                        const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                        double* d_trace_forces, double* d_trace_contacts,
+                                        const qmpc_outcome_params* op, qmpc_loop_outcome* d_outcomes,
+                                        const qmpc_push_params* d_push, int32_t pushes_per_robot, void* stream);
+
 /* Stand-pose joint angles (0, 0.67, -1.3 per leg: the reference's Gazebo start pose) for `batch`
  * robots, host buffer [batch][12]. */
 void qmpc_loop_joint_init(double* joint_pos, int32_t batch);

@@ -261,6 +261,25 @@ class OutcomeParams(C.Structure):
     _fields_ = [("down_height", C.c_double), ("down_upright", C.c_double), ("stop_when_down", C.c_double), ("reserved", C.c_double)]
 
 
+# struct qmpc_push_params (qmpc_loop_run_pushes*): one push window of one robot, 8 doubles = 64 B
+PUSH_PARAMS_DTYPE = np.dtype(
+    [
+        ("start_tick", "<f8"),
+        ("ticks", "<f8"),
+        ("force_world", "<f8", (3,)),
+        ("torque_body", "<f8", (3,)),
+    ],
+    align=False,
+)
+assert PUSH_PARAMS_DTYPE.itemsize == 8 * 8
+MAX_PUSHES = 8      # QMPC_MAX_PUSHES
+
+
+def push_params(batch: int, per_robot: int = 1) -> np.ndarray:
+    """[batch][per_robot] push windows, all fields zero: no push (fill start_tick, ticks, force_world, torque_body per robot)."""
+    return np.zeros((int(batch), int(per_robot)), dtype=PUSH_PARAMS_DTYPE)
+
+
 # struct qmpc_info: 2 x int32 + 4 doubles = 40 B
 INFO_DTYPE = np.dtype(
     [
@@ -355,6 +374,11 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_outcomes.restype = i32
     lib.qmpc_loop_run_outcomes_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp]
     lib.qmpc_loop_run_outcomes_device.restype = i32
+    lib.qmpc_loop_run_pushes.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32]
+    lib.qmpc_loop_run_pushes.restype = i32
+    lib.qmpc_loop_run_pushes_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
+                                                i32, vp]
+    lib.qmpc_loop_run_pushes_device.restype = i32
     lib.qmpc_set_instances_policy.argtypes = [vp, i32]
     lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_gather.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
@@ -427,7 +451,7 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_device.restype = i32
     for name in ("qmpc_sizeof_input", "qmpc_sizeof_params", "qmpc_sizeof_info", "qmpc_sizeof_convex_input",
                  "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params", "qmpc_sizeof_plant_params",
-                 "qmpc_sizeof_loop_outcome"):
+                 "qmpc_sizeof_loop_outcome", "qmpc_sizeof_push_params"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = i32
     if lib.qmpc_sizeof_input() != INPUT_DTYPE.itemsize:
@@ -448,6 +472,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         raise RuntimeError("qmpc_plant_params ABI size mismatch")
     if lib.qmpc_sizeof_loop_outcome() != LOOP_OUTCOME_DTYPE.itemsize or C.sizeof(OutcomeParams) != 32:
         raise RuntimeError("qmpc_loop_outcome ABI size mismatch")
+    if lib.qmpc_sizeof_push_params() != PUSH_PARAMS_DTYPE.itemsize:
+        raise RuntimeError("qmpc_push_params ABI size mismatch")
     return lib
 
 
@@ -520,6 +546,9 @@ EXPORTED_SYMBOLS = (
     "qmpc_sizeof_loop_outcome",
     "qmpc_loop_run_outcomes",
     "qmpc_loop_run_outcomes_device",
+    "qmpc_sizeof_push_params",
+    "qmpc_loop_run_pushes",
+    "qmpc_loop_run_pushes_device",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
@@ -887,6 +916,61 @@ class Solver:
         if rc != OK:
             raise QmpcError(rc, "qmpc_loop_run_outcomes_device")
 
+    def loop_run_pushes(self, states: np.ndarray, ticks: int, push: np.ndarray | None, lp: LoopParams | None = None,
+                        ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
+                        outcomes: np.ndarray | None = None, trace: bool = False):
+        """qmpc_loop_run_pushes: loop_run_outcomes whose plant integrates under timed push windows per robot.  push:
+        [B][per_robot] (or [B]: one window each) PUSH_PARAMS_DTYPE records, push_params(); None: exactly loop_run_outcomes.
+        Returns what loop_run_outcomes returns; the arguments are not modified."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
+        B = st.shape[0]
+        if ctrl is not None:
+            ctrl = np.ascontiguousarray(ctrl, dtype=INSTANCE_PARAMS_DTYPE)
+            if ctrl.shape != (B,):
+                raise ValueError(f"ctrl: shape {ctrl.shape}, expected ({B},)")
+        if plant is not None:
+            plant = np.ascontiguousarray(plant, dtype=PLANT_PARAMS_DTYPE)
+            if plant.shape != (B,):
+                raise ValueError(f"plant: shape {plant.shape}, expected ({B},)")
+        per_robot = 0
+        if push is not None:
+            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
+            if push.ndim == 1:
+                push = push.reshape(-1, 1)
+            if push.ndim != 2 or push.shape[0] != B:
+                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
+            per_robot = push.shape[1]      # 0 or above QMPC_MAX_PUSHES: the library refuses (QMPC_BAD_ARGUMENT)
+            if per_robot == 0:
+                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
+        if outcomes is None:
+            oc = loop_outcomes(B, self.lib)
+        else:
+            oc = np.ascontiguousarray(outcomes, dtype=LOOP_OUTCOME_DTYPE).copy()
+            if oc.shape != (B,):
+                raise ValueError(f"outcomes: shape {oc.shape}, expected ({B},)")
+        tf = np.zeros((ticks, B, 12)) if trace else None
+        tc = np.zeros((ticks, B, 4)) if trace else None
+        rc = self.lib.qmpc_loop_run_pushes(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
+                                           C.byref(op), _ptr(oc), _ptr(push), int(per_robot))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_pushes")
+        return (st, oc, tf, tc) if trace else (st, oc)
+
+    def loop_run_pushes_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_push: int, pushes_per_robot: int,
+                               lp: LoopParams | None = None, op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0,
+                               d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_pushes_device: device pointers (ints; 0 = NULL), stream-ordered; d_push is read in place."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        rc = self.lib.qmpc_loop_run_pushes_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
+                                                  p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
+                                                  int(pushes_per_robot), p(stream))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_pushes_device")
+
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
         as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN).  Answers under the handle's
@@ -1122,5 +1206,5 @@ class Solver:
 
 
 from .scenarios import (go1_stand_input, quat_to_rot, random_go1_trot_states,  # noqa: E402,F401
-                        random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_plants)
+                        random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_plants, random_go1_pushes)
 from .sharding import StepPipeline, gather_forces, shard_range, solve_sharded  # noqa: E402,F401

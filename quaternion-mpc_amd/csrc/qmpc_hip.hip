@@ -96,6 +96,18 @@ hipError_t qmpc_loop_outcome_post_launch(hipStream_t s, const qmpc_loop_params* 
                                          const double* forces, const qmpc_info* info, double* trace_f, double* trace_c, const int* row,
                                          const void* plants, qmpc_loop_outcome* outcomes, int batch);
 
+// qmpc_loop_push.hip: the outcome loop under timed push windows per robot (qmpc_loop_run_pushes*)
+hipError_t qmpc_loop_push_set_lds();
+hipError_t qmpc_loop_push_check_launch(hipStream_t s, const qmpc_push_params* push, int per_robot, void* plants, int batch);
+hipError_t qmpc_loop_push_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,
+                                       const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st, qmpc_input* rec,
+                                       double* forces, qmpc_info* info, double* trace_f, double* trace_c, qmpc_loop_outcome* outcomes,
+                                       const qmpc_push_params* push, int per_robot, int ticks, double* gws);
+hipError_t qmpc_loop_push_post_launch(hipStream_t s, const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st,
+                                      const double* forces, const qmpc_info* info, double* trace_f, double* trace_c, const int* row,
+                                      const void* plants, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,
+                                      int batch);
+
 // qmpc_lane.hip (third translation unit): the lane-per-instance kernel of large batches
 size_t qmpc_lane_ws_bytes(int N, int nl, unsigned slots, int wide);
 size_t qmpc_lane_scratch_bytes(int batch);
@@ -175,6 +187,8 @@ struct qmpc_handle {
   unsigned char* d_plant;      // per-robot plants of qmpc_loop_run_instances*, on first use: [max_batch] PlantDev | [max_batch]
                                // qmpc_plant_params (staging of the host-buffer call)
   qmpc_loop_outcome* d_outcome;   // staging of qmpc_loop_run_outcomes (the host-buffer call), on its first use: [max_batch] records
+  qmpc_push_params* d_push;       // staging of qmpc_loop_run_pushes (the host-buffer call), on its first use: [max_batch][push_cap]
+  int push_cap;                   // ... windows per robot it holds (grown when a call brings more)
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -330,6 +344,7 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   HIP_TRY(qmpc_wform_set_lds());
   HIP_TRY(qmpc_loop_inst_set_lds());
   HIP_TRY(qmpc_loop_outcome_set_lds());
+  HIP_TRY(qmpc_loop_push_set_lds());
   HIP_TRY(qmpc_wform_inst_list_set_lds());
   HIP_TRY(hipMalloc(&h->d_gws, sizeof(double) * (size_t)N * (13 * nu + 21 * nl + 30 * nl) * (size_t)max_batch));
   return QMPC_OK;
@@ -397,6 +412,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_lane_prm) (void)hipFree(h->d_lane_prm);
   if (h->d_plant) (void)hipFree(h->d_plant);
   if (h->d_outcome) (void)hipFree(h->d_outcome);
+  if (h->d_push) (void)hipFree(h->d_push);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1017,6 +1033,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_lane_prm) b += qmpc_lane_inst_param_bytes(h->lane_slots);
       if (h->d_plant) b += plant_bytes(h->max_batch);
       if (h->d_outcome) b += sizeof(qmpc_loop_outcome) * (size_t)h->max_batch;
+      if (h->d_push) b += sizeof(qmpc_push_params) * (size_t)h->push_cap * (size_t)h->max_batch;
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
       return QMPC_OK;
@@ -1664,10 +1681,12 @@ void qmpc_loop_outcome_init(qmpc_loop_outcome* o, int32_t batch) {
 
 // The call of qmpc_loop_run_instances_device with the outcome kernels in place of its own.  Without records (both NULL) every
 // robot's plant block carries the handle's mass and inverse inertia: the call-level checks are those of a call with plant records.
-qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
-                                          int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
-                                          double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
-                                          qmpc_loop_outcome* d_outcomes, void* stream) {
+// d_push (qmpc_loop_run_pushes_device; NULL: qmpc_loop_run_outcomes_device, launch for launch): per_robot windows per robot,
+// checked once after the plant expansion, and the push kernels (qmpc_loop_push.hip) in place of the post step's.
+static qmpc_status loop_outcomes_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                        qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot, void* stream) {
   if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!d_states || !d_outcomes))) return QMPC_BAD_ARGUMENT;
   const qmpc_status cs = loop_instances_check(h, lp, batch, d_ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
@@ -1688,7 +1707,14 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
                                          plant_dev(h), (int)batch));
   else
     HIP_TRY(qmpc_loop_outcome_expand_base_launch(s, &h->dev, sizeof h->dev, bcast, plant_dev(h), (int)batch));
+  if (d_push) HIP_TRY(qmpc_loop_push_check_launch(s, d_push, (int)per_robot, plant_dev(h), (int)batch));
   if (lpp.fused) {
+    if (d_push) {
+      HIP_TRY(qmpc_loop_push_fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, &OP, d_states, h->d_in,
+                                          h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, d_outcomes, d_push, (int)per_robot,
+                                          (int)ticks, lpp.gws ? h->d_gws : nullptr));
+      return QMPC_OK;
+    }
     HIP_TRY(qmpc_loop_outcome_fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, &OP, d_states, h->d_in,
                                            h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, d_outcomes, (int)ticks,
                                            lpp.gws ? h->d_gws : nullptr));
@@ -1698,8 +1724,12 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
     HIP_TRY(qmpc_loop_outcome_front_launch(s, &LP, &OP, d_states, h->d_in, h->d_loop_row, plant_dev(h), d_outcomes, (int)batch));
     const qmpc_status st = d_ctrl ? loop_inst_tick_solve(h, lpp, batch, s) : loop_tick_solve(h, batch, s, warm, first, false);
     if (st != QMPC_OK) return st;
-    HIP_TRY(qmpc_loop_outcome_post_launch(s, &LP, &OP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts,
-                                          h->d_loop_row, plant_dev(h), d_outcomes, (int)batch));
+    if (d_push)
+      HIP_TRY(qmpc_loop_push_post_launch(s, &LP, &OP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, h->d_loop_row,
+                                         plant_dev(h), d_outcomes, d_push, (int)per_robot, (int)batch));
+    else
+      HIP_TRY(qmpc_loop_outcome_post_launch(s, &LP, &OP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts,
+                                            h->d_loop_row, plant_dev(h), d_outcomes, (int)batch));
     return QMPC_OK;
   };
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
@@ -1707,15 +1737,36 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
   return replay_ticks(h, lpp, s, ticks, warm, one_tick);
 }
 
-qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
-                                   const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
-                                   double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes) {
+qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                          int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                          double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                          qmpc_loop_outcome* d_outcomes, void* stream) {
+  return loop_outcomes_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, nullptr, 0,
+                              stream);
+}
+
+// the host-buffer call; push (qmpc_loop_run_pushes; NULL: qmpc_loop_run_outcomes): per_robot windows per robot, staged in h->d_push
+static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                      const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                      double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
+                                      const qmpc_push_params* push, int32_t per_robot) {
   if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!states || !outcomes))) return QMPC_BAD_ARGUMENT;
   const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
   HIP_TRY(hipSetDevice(h->device));
   const qmpc_status es = loop_instances_buffers(h, batch, ctrl != nullptr, lp->warm_start != 0.0, nullptr);
-  if (es != QMPC_OK || ticks == 0) return es;
+  if (es != QMPC_OK) return es;
+  if (push && h->push_cap < per_robot) {      // the windows' staging: before the ticks = 0 return, like every other buffer
+    if (h->d_push) (void)hipFree(h->d_push);
+    h->d_push = nullptr;
+    h->push_cap = 0;
+    HIP_TRY(hipMalloc(&h->d_push, sizeof(qmpc_push_params) * (size_t)per_robot * (size_t)h->max_batch));
+    h->push_cap = per_robot;
+  }
+  // (the push call's ticks = 0 allocates everything a later push call needs, the records' staging included; the outcome call's
+  // ticks = 0 stops before it, as it always did)
+  if (push && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
+  if (ticks == 0) return es;
   if (!h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
   // states and traces through the staging of qmpc_loop_run (loop_run_host), the records through their own
   const size_t B = (size_t)batch, T = (size_t)ticks;
@@ -1735,8 +1786,9 @@ qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, i
   HIP_TRY(hipMemcpyAsync(h->d_outcome, outcomes, sizeof(qmpc_loop_outcome) * B, hipMemcpyHostToDevice, h->stream));
   if (ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
   if (plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
-  const qmpc_status rs = qmpc_loop_run_outcomes_device(h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr,
-                                                       plant ? plant_rec(h) : nullptr, d_tf, d_tc, op, h->d_outcome, nullptr);
+  if (push) HIP_TRY(hipMemcpyAsync(h->d_push, push, sizeof(qmpc_push_params) * B * (size_t)per_robot, hipMemcpyHostToDevice, h->stream));
+  const qmpc_status rs = loop_outcomes_device(h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
+                                              d_tf, d_tc, op, h->d_outcome, push ? h->d_push : nullptr, per_robot, nullptr);
   if (rs != QMPC_OK) return rs;
   HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(outcomes, h->d_outcome, sizeof(qmpc_loop_outcome) * B, hipMemcpyDeviceToHost, h->stream));
@@ -1744,6 +1796,38 @@ qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, i
   if (d_tc) HIP_TRY(hipMemcpyAsync(trace_contacts, d_tc, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return QMPC_OK;
+}
+
+qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                   const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                   double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes) {
+  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, nullptr, 0);
+}
+
+// ---- the outcome loop under timed push windows per robot (qmpc_loop_push.hip) ------------------------------------------------
+static_assert(sizeof(qmpc_push_params) == 64, "qmpc_push_params is 8 doubles");
+int32_t qmpc_sizeof_push_params(void) { return (int32_t)sizeof(qmpc_push_params); }
+
+qmpc_status qmpc_loop_run_pushes_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                        qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                        void* stream) {
+  if (!d_push)
+    return qmpc_loop_run_outcomes_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
+                                         stream);
+  if (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES) return QMPC_BAD_ARGUMENT;
+  return loop_outcomes_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
+                              pushes_per_robot, stream);
+}
+
+qmpc_status qmpc_loop_run_pushes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                 const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                 double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
+                                 const qmpc_push_params* push, int32_t pushes_per_robot) {
+  if (!push) return qmpc_loop_run_outcomes(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes);
+  if (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES) return QMPC_BAD_ARGUMENT;
+  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot);
 }
 
 // Diagnostic: per-instance phase cycle counts (s_memtime) of one solve launch.

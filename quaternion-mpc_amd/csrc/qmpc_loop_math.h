@@ -198,6 +198,34 @@ QMPC_HD void loop_outcome_one(const qmpc_outcome_params& op, const qmpc_loop_sta
   if (!finite || height < op.down_height || upright < op.down_upright) o.down_tick = s.tick;
 }
 
+// The effective disturbance wrench of one tick under a robot's push windows (qmpc_loop_run_pushes*, include/qmpc.h): t is
+// state.tick BEFORE the tick, force / torque come in as the plant's constant disturbance and go out as the wrench of this tick.
+// Window k acts when t >= start_tick and t < start_tick + ticks (ticks <= 0: never).  Per component, in index order: an active
+// window's value that is not exactly zero replaces a running value that is exactly zero (either sign: the bits become the
+// window's) and is added to any other with one IEEE add; an inactive window or a zero component touches nothing -- the rule of
+// plant_rate_ext, so windows that never act leave the bytes of force / torque alone.
+// One source for the device kernels (qmpc_loop_push.hip), the host class (host/ClosedLoopHost.h) and the native test.
+QMPC_HD void loop_push_wrench(const qmpc_push_params* push, int n, double t, double* force, double* torque) {
+  QMPC_NO_CONTRACT
+  for (int k = 0; k < n; ++k) {
+    const qmpc_push_params& w = push[k];
+    if (!(w.ticks > 0.0) || !(t >= w.start_tick) || !(t < w.start_tick + w.ticks)) continue;
+    for (int a = 0; a < 3; ++a) {
+      if (w.force_world[a] != 0.0) force[a] = force[a] == 0.0 ? w.force_world[a] : force[a] + w.force_world[a];
+      if (w.torque_body[a] != 0.0) torque[a] = torque[a] == 0.0 ? w.torque_body[a] : torque[a] + w.torque_body[a];
+    }
+  }
+}
+
+// A push window is valid when its eight fields are finite (x - x is 0 only for a finite x); the robot of an invalid one is frozen
+QMPC_HD bool loop_push_valid(const qmpc_push_params& w) {
+  QMPC_NO_CONTRACT
+  bool ok = (w.start_tick - w.start_tick == 0.0) && (w.ticks - w.ticks == 0.0);
+  for (int a = 0; a < 3; ++a)
+    ok = ok && (w.force_world[a] - w.force_world[a] == 0.0) && (w.torque_body[a] - w.torque_body[a] == 0.0);
+  return ok;
+}
+
 // Condition matrix of the swing-foot quintic p(t) = sum_k a_k t^k (QuinticCurve::get_foot_swing_target,
 // Utils.cpp:236-293): rows p(0), p(T), p'(0), p'(T), p(T/2), p'(T/2).  Generated, with the reference's FLOAT
 // evaluation order so that every entry carries the same rounding as upstream's hand-written expressions: a power is

@@ -34,6 +34,8 @@ class ClosedLoopHostBase {
   // the robot's outcome record (qmpc_loop_run_outcomes*): fed by every tick, thresholds as set here (default: the ABI's)
   virtual void set_outcome_params(const qmpc_outcome_params& op) = 0;
   virtual const qmpc_loop_outcome& outcome() const = 0;
+  // the robot's push windows (qmpc_loop_run_pushes*): n <= QMPC_MAX_PUSHES records, copied; n = 0 or null: none
+  virtual void set_pushes(const qmpc_push_params* push, int n) = 0;
   State state;
 };
 
@@ -91,6 +93,10 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   void set_warm_start(bool on) override { warm(on); }
   void set_outcome_params(const qmpc_outcome_params& op) override { op_ = op; }
   const qmpc_loop_outcome& outcome() const override { return outcome_; }
+  void set_pushes(const qmpc_push_params* push, int n) override {
+    n_push_ = (push && n > 0) ? (n < QMPC_MAX_PUSHES ? n : QMPC_MAX_PUSHES) : 0;
+    for (int k = 0; k < n_push_; ++k) push_[k] = push[k];
+  }
   void reset_outcome() {                                    // qmpc_loop_outcome_init
     std::memset(&outcome_, 0, sizeof outcome_);
     outcome_.down_tick = outcome_.first_rejected_tick = -1.0;
@@ -140,7 +146,14 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     const bool ok = mpc->grf_update(state);
     double u[12];
     for (int a = 0; a < 12; ++a) u[a] = state.ctrl.optimized_input[a];
-    if (has_plant_)
+    if (n_push_ > 0) {   // the device's push tick: the plant's constant wrench (none without a plant record, on the handle's mass and
+                         // inverse inertia then) under the windows acting at state.tick = ticks_ (qmpc_loop_math.h: loop_push_wrench)
+      double f[3] = {0.0, 0.0, 0.0}, tq[3] = {0.0, 0.0, 0.0};
+      if (has_plant_)
+        for (int a = 0; a < 3; ++a) { f[a] = plant_.ext_force_world[a]; tq[a] = plant_.ext_torque_body[a]; }
+      qmpc_loop::loop_push_wrench(push_, n_push_, (double)ticks_, f, tq);
+      qmpc_loop::plant_step_ext(x_, u, feet_, NUM_LEG, has_plant_ ? plant_.mass : mpc->params().mass, Iinv_, f, tq, lp_.dt);
+    } else if (has_plant_)
       qmpc_loop::plant_step_ext(x_, u, feet_, NUM_LEG, plant_.mass, Iinv_, plant_.ext_force_world, plant_.ext_torque_body, lp_.dt);
     else
       qmpc_loop::plant_step(x_, u, feet_, NUM_LEG, mpc->params().mass, Iinv_, lp_.dt);
@@ -281,6 +294,8 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   bool has_plant_ = false;
   qmpc_outcome_params op_;
   qmpc_loop_outcome outcome_;
+  qmpc_push_params push_[QMPC_MAX_PUSHES];
+  int n_push_ = 0;
   long ticks_ = 0;
 };
 

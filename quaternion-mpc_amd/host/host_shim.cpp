@@ -264,6 +264,8 @@ void qh_loop_export(void* p, qmpc_loop_state* out) { static_cast<LoopHarness*>(p
 // the robot's outcome record (qmpc_loop_outcome) after the ticks made so far; its thresholds (default: qmpc_default_outcome_params)
 void qh_loop_outcome(void* p, qmpc_loop_outcome* out) { *out = static_cast<LoopHarness*>(p)->loop->outcome(); }
 void qh_loop_set_outcome_params(void* p, const qmpc_outcome_params* op) { static_cast<LoopHarness*>(p)->loop->set_outcome_params(*op); }
+// the robot's push windows (qmpc_push_params[n], n <= QMPC_MAX_PUSHES; n = 0: none) for the ticks to come
+void qh_loop_set_pushes(void* p, const qmpc_push_params* push, int n) { static_cast<LoopHarness*>(p)->loop->set_pushes(push, n); }
 void qh_loop_destroy(void* p) {
   LoopHarness* h = static_cast<LoopHarness*>(p);
   if (!h) return;

@@ -285,3 +285,25 @@ def random_go1_plants(batch: int, seed: int = 0, first: int = 0, base=None, payl
     rec["ext_force_world"][:, 0] = mag * np.cos(ang)
     rec["ext_force_world"][:, 1] = mag * np.sin(ang)
     return rec
+
+
+def random_go1_pushes(batch: int, seed: int = 0, first: int = 0, per_robot: int = 1, start=(0.0, 91.0), ticks=(4.0, 20.0),
+                      impulse=(0.0, 10.0), dt: float = 0.005) -> np.ndarray:
+    """`batch` x `per_robot` push windows (``struct qmpc_push_params``, for Solver.loop_run_pushes), robot indices
+    first .. first+batch-1, the counter-based generator of random_go1_plants (a shard equals its block of the whole): window k
+    of a robot starts at tick floor(U(start)), lasts max(1, floor(U(ticks))) ticks and carries an impulse of U(impulse) N s in
+    a horizontal, uniformly random direction -- a force of magnitude impulse / (ticks * dt) N at the CoM, no torque.  Four
+    uniforms per window, in the order start, ticks, impulse, direction."""
+    from . import push_params
+
+    rec = push_params(batch, per_robot)
+    idx = np.arange(first, first + batch, dtype=np.uint64)
+    u = _uniform(0x5EED3000 + int(seed), idx, 4 * int(per_robot)).reshape(batch, int(per_robot), 4)
+    rec["start_tick"] = np.floor(start[0] + (start[1] - start[0]) * u[:, :, 0])
+    n = np.maximum(1.0, np.floor(ticks[0] + (ticks[1] - ticks[0]) * u[:, :, 1]))
+    rec["ticks"] = n
+    mag = (impulse[0] + (impulse[1] - impulse[0]) * u[:, :, 2]) / (n * dt)
+    ang = 2.0 * np.pi * u[:, :, 3]
+    rec["force_world"][:, :, 0] = mag * np.cos(ang)
+    rec["force_world"][:, :, 1] = mag * np.sin(ang)
+    return rec

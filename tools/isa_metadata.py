@@ -12,7 +12,7 @@ CSRC = REPO / "quaternion-mpc_amd" / "csrc"
 print("ISA metadata of the final build (hipcc --offload-arch=gfx950 -O2 <per-unit flags of __graft_entry__.py> -S --cuda-device-only; .amdgpu_metadata notes), one row per kernel")
 print("columns: kernel | vgpr_count | agpr_count | sgpr_count | vgpr_spill_count | sgpr_spill_count | private_segment_fixed_size (scratch bytes) | group_segment_fixed_size (static LDS)")
 WAVE = ["-mllvm", "-disable-machine-licm", "-mllvm", "-disable-machine-sink"]
-for tu, extra in (("qmpc_hip.hip", WAVE), ("qmpc_loop_fused.hip", WAVE), ("qmpc_loop_inst.hip", WAVE), ("qmpc_loop_outcome.hip", WAVE), ("qmpc_wform.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
+for tu, extra in (("qmpc_hip.hip", WAVE), ("qmpc_loop_fused.hip", WAVE), ("qmpc_loop_inst.hip", WAVE), ("qmpc_loop_outcome.hip", WAVE), ("qmpc_loop_push.hip", WAVE), ("qmpc_wform.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
                   ("qmpc_lane.hip", ["-mllvm", "-disable-lsr", "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-DQL_UNIT=1"]),
                   ("qmpc_lane_ref.hip", ["-mllvm", "-disable-lsr", "-DQL_UNIT=2"]),
                   ("qmpc_lane_inst.hip", ["-mllvm", "-disable-lsr", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),

@@ -15,6 +15,9 @@ per-robot calls include their expansion kernels.
     (the lane kernel with per-lane parameters and its hand-off from the switch-over on), next to the plain loop's figure.  With
     --outcomes --stop the falling population runs with uniform controller records under each policy asked for (auto: e.g. with
     and without QMPC_LANE_SORT_IDLE=0 in the environment, the sort's class for robots that will not solve).
+--pushes [--per-robot K]: instead, same-job pairs of qmpc_loop_run_outcomes_device against qmpc_loop_run_pushes_device whose K
+    windows per robot never act (they lie beyond the run, with a wrench that is not zero): what reading the windows in every tick
+    costs, with plant records and with controller + plant records, on the walking fleet.  The two calls compute the same bytes.
 --records uniform|random: every robot carries the handle's values (default), or random_go1_variants / random_go1_plants."""
 import argparse
 import importlib.util
@@ -93,6 +96,74 @@ def falling(pkg, lib, torch, N, B, a, policy=None):
     return row
 
 
+def pushes(pkg, lib, torch, N, B, a):
+    """the outcome call against the push call whose windows never act (see the module docstring)"""
+    p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+    lp = pkg.default_loop_params(lib)
+    T, K = a.ticks, a.per_robot
+    rng = np.random.default_rng(5)
+    cmds = np.zeros((B, 7))
+    cmds[:, 0] = rng.uniform(-0.4, 0.4, B); cmds[:, 1] = rng.uniform(-0.15, 0.15, B)
+    cmds[:, 2] = rng.uniform(0.26, 0.32, B); cmds[:, 5] = rng.uniform(-0.4, 0.4, B)
+    cmds[:, 6] = (rng.random(B) < 0.85).astype(float)
+    stand = cmds.copy(); stand[:, 6] = 0.0
+    st = pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, B), lib=lib)
+    s = pkg.Solver(p, B, device=0, lib=lib)
+    s.set_instances_policy(a.policy if a.policy != "both" else "wave")
+    s.prepare(B)
+    s.prepare_instances()
+    st = s.loop_run(st, 6, lp)
+    st["movement_mode"] = cmds[:, 6]
+    if a.records == "random":
+        ctrl = pkg.random_go1_variants(B, seed=12, base=p)
+        ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
+        plant = pkg.random_go1_plants(B, seed=11, base=p, payload=(-1.0, 3.0), force=(0.0, 10.0))
+    else:
+        ctrl, plant = pkg.instance_params(p, B), pkg.plant_params(p, B)
+    push = pkg.random_go1_pushes(B, seed=13, per_robot=K, impulse=(1.0, 5.0), dt=lp.dt)
+    push["start_tick"] += 1e9      # beyond any run
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).cuda()      # noqa: E731
+    d_st0, d_oc0, d_ctrl, d_plant, d_push = dev(st), dev(pkg.loop_outcomes(B, lib)), dev(ctrl), dev(plant), dev(push)
+    d_st, d_oc = d_st0.clone(), d_oc0.clone()
+    op = pkg.default_outcome_params(lib)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    torch.cuda.synchronize()
+    calls = {}
+    for name, c in (("plant", 0), ("ctrl_plant", d_ctrl.data_ptr())):
+        calls[name + "_outcomes"] = lambda c=c: s.loop_run_outcomes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), lp, op, d_ctrl=c,
+                                                                          d_plant=d_plant.data_ptr(), stream=sp)
+        calls[name + "_pushes"] = lambda c=c: s.loop_run_pushes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), d_push.data_ptr(), K, lp, op,
+                                                                      d_ctrl=c, d_plant=d_plant.data_ptr(), stream=sp)
+    times, bits = {k: [] for k in calls}, {}
+    for r in range(a.warmup + a.reps):
+        for k, fn in calls.items():
+            with torch.cuda.stream(stream):
+                d_st.copy_(d_st0)
+                d_oc.copy_(d_oc0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            if r >= a.warmup:
+                times[k].append(e0.elapsed_time(e1))
+            bits[k] = (d_st.cpu().numpy().tobytes(), d_oc.cpu().numpy().tobytes())
+    forms = {"plant": s.loop_instances_plan(B, False, False), "ctrl_plant": s.loop_instances_plan(B, True, False)}
+    s.close()
+    ms = {k: float(np.median(v)) for k, v in times.items()}
+    row = {"N": N, "B": B, "ticks": T, "records": a.records, "pushes_per_robot": K}
+    for k in ("plant", "ctrl_plant"):
+        o, q = k + "_outcomes", k + "_pushes"
+        row.update({o + "_ms": ms[o], q + "_ms": ms[q], k + "_form": forms[k], k + "_pushes_ratio": ms[q] / ms[o],
+                    k + "_outcomes_spread": (max(times[o]) - min(times[o])) / ms[o], k + "_pushes_spread": (max(times[q]) - min(times[q])) / ms[q],
+                    k + "_same_bytes": bits[o] == bits[q]})
+        print(f"N={N:2d} B={B:6d} {k:10s} {forms[k]}: outcome call {ms[o]:9.3f} ms (min {min(times[o]):.3f}, max {max(times[o]):.3f})   push call, "
+              f"{K} idle window(s) per robot {ms[q]:9.3f} ms (min {min(times[q]):.3f}, max {max(times[q]):.3f})   push / outcome "
+              f"{row[k + '_pushes_ratio']:.4f}   same bytes: {row[k + '_same_bytes']}", flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -102,6 +173,8 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--outcomes", action="store_true")
     ap.add_argument("--stop", action="store_true")
+    ap.add_argument("--pushes", action="store_true")
+    ap.add_argument("--per-robot", type=int, default=1)
     ap.add_argument("--policy", choices=("wave", "auto", "both"), default="wave")
     ap.add_argument("--records", choices=("uniform", "random"), default="uniform")
     a = ap.parse_args()
@@ -115,6 +188,9 @@ def main():
     for item in a.sizes.split(","):
         N, B = (int(x) for x in item.split(":"))
         policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
+        if a.pushes:
+            rows.append(pushes(pkg, lib, torch, N, B, a))
+            continue
         if a.stop:
             if a.policy == "wave":      # (as before the policy existed: plant records only)
                 rows.append(falling(pkg, lib, torch, N, B, a))

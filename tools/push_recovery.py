@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Push recovery of the trotting Go1 on the device: a fleet under a grid of impulse magnitude x 8 directions x start tick over one
+gait period (91 ticks of 5 ms at 2.2 Hz), every robot shoved once (qmpc_loop_run_pushes, one window per robot), the share of robots
+still up per cell from the outcome records.  The robots of a cell differ in their true plant (random_go1_plants: payload and
+inertia); the controller is the handle's and is not told about the push.
+    python tools/push_recovery.py [--impulses 2,4,6,8,10] [--starts 13] [--length 10] [--per-cell 8] [--speed 0.3] [--settle 60]
+                                  [--recover 200] [--horizon 10] [--json FILE]
+Every robot stands for 6 ticks, trots at --speed for --settle ticks, is shoved at tick 6 + settle + start for --length ticks with
+force impulse / (length dt) in its cell's direction (0 degrees: ahead, 90: to its left), and trots on until --recover ticks after
+the last start.  Down: below 0.15 m or tilted beyond 60 degrees (qmpc_default_outcome_params); stop_when_down halts a fallen robot.
+Prints one table per impulse (rows: start tick in the gait period, columns: direction) and the marginals.  The figures are whatever
+the run gives."""
+import argparse
+import importlib.util
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+REPO = Path(__file__).resolve().parents[1]
+PERIOD = 91      # ticks of 5 ms in one gait period at 2.2 Hz
+
+
+def load_pkg():
+    spec = importlib.util.spec_from_file_location("quaternion_mpc_amd", REPO / "quaternion-mpc_amd" / "__init__.py",
+                                                  submodule_search_locations=[str(REPO / "quaternion-mpc_amd")])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules["quaternion_mpc_amd"] = mod
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--impulses", default="2,4,6,8,10", help="N s")
+    ap.add_argument("--starts", type=int, default=13, help="start ticks, evenly spread over the gait period")
+    ap.add_argument("--length", type=float, default=10.0, help="ticks the shove lasts")
+    ap.add_argument("--per-cell", type=int, default=8)
+    ap.add_argument("--speed", type=float, default=0.3)
+    ap.add_argument("--settle", type=int, default=60)
+    ap.add_argument("--recover", type=int, default=200)
+    ap.add_argument("--horizon", type=int, default=10)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    pkg = load_pkg()
+    lib = pkg.load_library()
+    impulses = [float(x) for x in a.impulses.split(",")]
+    starts = [int(round(k * PERIOD / a.starts)) for k in range(a.starts)]
+    angles = np.arange(8) * (np.pi / 4)
+    # the grid, robot index = ((impulse, start, direction), member of the cell)
+    gi, gs, gd, _ = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8), np.arange(a.per_cell),
+                                                    indexing="ij"))
+    B = gi.size
+    p = pkg.default_params(a.horizon, pkg.MODE_CONVERGED, lib)
+    lp = pkg.default_loop_params(lib)
+    assert abs(1.0 / (lp.gait_freq * lp.dt) - PERIOD) < 0.5, (lp.gait_freq, lp.dt)
+    cmd = [a.speed, 0.0, 0.30, 0.0, 0.0, 0.0, 0.0]
+    st = pkg.loop_states([cmd] * B, lp, height=0.3, yaw=0.0, lib=lib)
+    plant = pkg.random_go1_plants(B, seed=21, base=p, payload=(0.0, 3.0))
+    push = pkg.push_params(B)
+    t0 = 6 + a.settle
+    push["start_tick"][:, 0] = t0 + np.asarray(starts, dtype=np.float64)[gs]
+    push["ticks"][:, 0] = a.length
+    mag = np.asarray(impulses)[gi] / (a.length * lp.dt)
+    push["force_world"][:, 0, 0] = mag * np.cos(angles[gd])
+    push["force_world"][:, 0, 1] = mag * np.sin(angles[gd])
+    op = pkg.default_outcome_params(lib, stop_when_down=True)
+    s = pkg.Solver(p, B, device=0, lib=lib)
+    form = s.loop_instances_plan(B, False, False)
+    total = a.settle + PERIOD + a.recover
+    w0 = time.perf_counter()
+    st, oc = s.loop_run_pushes(st, 6, push, lp, plant=plant, op=op)
+    st["movement_mode"] = 1.0
+    st, oc = s.loop_run_pushes(st, total, push, lp, plant=plant, op=op, outcomes=oc)
+    wall = time.perf_counter() - w0
+    s.close()
+    up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, a.per_cell)
+    share = up.mean(axis=3)
+    fell_before = int(((oc["down_tick"] >= 0) & (oc["down_tick"] <= push["start_tick"][:, 0])).sum())
+    print(f"push recovery: {B} robots ({len(impulses)} impulses x {len(starts)} start ticks x 8 directions x {a.per_cell} plants), N={a.horizon}, "
+          f"trot at {a.speed} m/s, shove of {a.length:g} ticks from tick {t0} + start, {6 + total} ticks in all, launch {form}, "
+          f"{wall:.2f} s wall with the copies; {fell_before} robots were down before their shove began")
+    print(f"solves: {pkg.summarize_outcomes(oc)['mean_iterations']:.2f} iterations on average, "
+          f"{int(oc['rejected_ticks'].sum())} rejected, {int((oc['not_ok_ticks'] - oc['rejected_ticks']).sum())} at the iteration cap")
+    head = "start " + " ".join(f"{int(np.degrees(x)):4d}d" for x in angles) + "    all"
+    for i, imp in enumerate(impulses):
+        print(f"\nimpulse {imp:g} N s ({imp / (a.length * lp.dt):.0f} N for {a.length:g} ticks): share still up at the end")
+        print(head)
+        for j, t in enumerate(starts):
+            print(f"{t:5d} " + " ".join(f"{share[i, j, d]:5.2f}" for d in range(8)) + f"  {share[i, j].mean():5.2f}")
+        print("  all " + " ".join(f"{share[i, :, d].mean():5.2f}" for d in range(8)) + f"  {share[i].mean():5.2f}")
+    if a.json:
+        Path(a.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.json).write_text(json.dumps({"impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
+                                            "per_cell": a.per_cell, "length_ticks": a.length, "speed": a.speed, "form": form,
+                                            "share_up": share.tolist()}, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
