@@ -68,45 +68,44 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
                                         const qmpc_input* in, double* forces, qmpc_info* info, double* traj_u, double* traj_x,
                                         double* gws);
 
-// qmpc_loop_inst.hip (fifth translation unit): the closed loop with per-robot controller and plant records
-hipError_t qmpc_loop_inst_set_lds();
+// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip: the closed loop with per-robot records -- controller and plant
+// records (qmpc_loop_run_instances*), with the outcome step (qmpc_loop_run_outcomes*), under timed push windows
+// (qmpc_loop_run_pushes*).  Each unit defines the same entry points in its namespace (qmpc_loop_rec.inc) and ignores the
+// trailing arguments its kernels do not take; the push unit has no front kernel of its own.
+#define QMPC_REC_DECLARE(ns)                                                                                                         \
+  namespace ns {                                                                                                                     \
+  hipError_t rec_set_lds();                                                                                                          \
+  hipError_t rec_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,            \
+                              const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info,    \
+                              double* trace_f, double* trace_c, int ticks, double* gws, const qmpc_outcome_params* op,              \
+                              qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot);                            \
+  hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, int* row,            \
+                              const void* plants, int batch, const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes);     \
+  hipError_t rec_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, const double* forces,                  \
+                             const qmpc_info* info, double* trace_f, double* trace_c, const int* row, const void* plants, int batch, \
+                             const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push,              \
+                             int per_robot);                                                                                         \
+  }
+QMPC_REC_DECLARE(qmpc_inst_tu)
+QMPC_REC_DECLARE(qmpc_outc_tu)
+QMPC_REC_DECLARE(qmpc_push_tu)
+#undef QMPC_REC_DECLARE
+enum { REC_PLAIN = 0, REC_OUTCOME = 1, REC_PUSH = 2 };      // the kind of a call with records: QMPC_REC_EXT of its unit
+static const struct {
+  decltype(&qmpc_inst_tu::rec_set_lds) set_lds;
+  decltype(&qmpc_inst_tu::rec_fused_launch) fused_launch;
+  decltype(&qmpc_inst_tu::rec_front_launch) front_launch;
+  decltype(&qmpc_inst_tu::rec_post_launch) post_launch;
+} kRec[3] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
+             {qmpc_outc_tu::rec_set_lds, qmpc_outc_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_outc_tu::rec_post_launch},
+             {qmpc_push_tu::rec_set_lds, qmpc_push_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_push_tu::rec_post_launch}};
+// ... and the kernels each unit has beside them: the expansions of the plant blocks and the check of the windows
 hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, const qmpc_plant_params* plant,
                                         const qmpc_instance_params* ctrl, const int* ctrl_status, void* bcast_out, void* plants_out,
                                         int batch);
-hipError_t qmpc_loop_inst_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,
-                                       const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, double* forces,
-                                       qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws);
-hipError_t qmpc_loop_inst_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, int* row,
-                                       const void* plants, int batch);
-hipError_t qmpc_loop_inst_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, const double* forces,
-                                      const qmpc_info* info, double* trace_f, double* trace_c, const int* row, const void* plants,
-                                      int batch);
-
-// qmpc_loop_outcome.hip: the same closed loop accumulating per-robot outcome records (qmpc_loop_run_outcomes*)
-hipError_t qmpc_loop_outcome_set_lds();
 hipError_t qmpc_loop_outcome_expand_base_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, void* bcast_out,
                                                 void* plants_out, int batch);
-hipError_t qmpc_loop_outcome_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,
-                                          const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st,
-                                          qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f, double* trace_c,
-                                          qmpc_loop_outcome* outcomes, int ticks, double* gws);
-hipError_t qmpc_loop_outcome_front_launch(hipStream_t s, const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st,
-                                          qmpc_input* rec, int* row, const void* plants, const qmpc_loop_outcome* outcomes, int batch);
-hipError_t qmpc_loop_outcome_post_launch(hipStream_t s, const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st,
-                                         const double* forces, const qmpc_info* info, double* trace_f, double* trace_c, const int* row,
-                                         const void* plants, qmpc_loop_outcome* outcomes, int batch);
-
-// qmpc_loop_push.hip: the outcome loop under timed push windows per robot (qmpc_loop_run_pushes*)
-hipError_t qmpc_loop_push_set_lds();
 hipError_t qmpc_loop_push_check_launch(hipStream_t s, const qmpc_push_params* push, int per_robot, void* plants, int batch);
-hipError_t qmpc_loop_push_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,
-                                       const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st, qmpc_input* rec,
-                                       double* forces, qmpc_info* info, double* trace_f, double* trace_c, qmpc_loop_outcome* outcomes,
-                                       const qmpc_push_params* push, int per_robot, int ticks, double* gws);
-hipError_t qmpc_loop_push_post_launch(hipStream_t s, const qmpc_loop_params* lp, const qmpc_outcome_params* op, qmpc_loop_state* st,
-                                      const double* forces, const qmpc_info* info, double* trace_f, double* trace_c, const int* row,
-                                      const void* plants, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,
-                                      int batch);
 
 // qmpc_lane.hip (third translation unit): the lane-per-instance kernel of large batches
 size_t qmpc_lane_ws_bytes(int N, int nl, unsigned slots, int wide);
@@ -342,9 +341,7 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   HIP_TRY(set_max_lds(kDenseSolve, kDenseRef, kLinearize));
   HIP_TRY(qmpc_loop_fused_set_lds());
   HIP_TRY(qmpc_wform_set_lds());
-  HIP_TRY(qmpc_loop_inst_set_lds());
-  HIP_TRY(qmpc_loop_outcome_set_lds());
-  HIP_TRY(qmpc_loop_push_set_lds());
+  for (const auto& r : kRec) HIP_TRY(r.set_lds());
   HIP_TRY(qmpc_wform_inst_list_set_lds());
   HIP_TRY(hipMalloc(&h->d_gws, sizeof(double) * (size_t)N * (13 * nu + 21 * nl + 30 * nl) * (size_t)max_batch));
   return QMPC_OK;
@@ -1494,12 +1491,18 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
   return loop_run_impl(h, lp, batch, d_states, ticks, nullptr, nullptr, g, d_joint_pos, d_cmd, d_trace_cmd, stream);
 }
 
-// The host-buffer closed loop (qmpc_loop_run*, its arguments checked): states, the records given and the traces through the
-// handle's staging, which only grows -- [states | force trace | contact trace]; the records go to the staging halves of the
-// per-instance and plant buffers (allocated by the caller)
-static qmpc_status loop_run_host(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
-                                 const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
-                                 double* trace_contacts) {
+static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                       int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                       double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                       qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot, void* stream);
+
+// The host-buffer closed loop of every kind (qmpc_loop_run*, its arguments checked): states and traces through the handle's
+// staging, which only grows -- [states | force trace | contact trace]; the records given go to the staging halves of the
+// per-instance and plant buffers, outcome records and windows to h->d_outcome and h->d_push (all allocated by the caller)
+static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                     int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                     double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
+                                     const qmpc_push_params* push, int32_t per_robot) {
   const size_t B = (size_t)batch, T = (size_t)ticks;
   const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
                n_tc = trace_contacts ? 4 * B * T : 0;
@@ -1514,12 +1517,16 @@ static qmpc_status loop_run_host(qmpc_handle* h, const qmpc_loop_params* lp, int
   double* d_tf = trace_forces ? h->d_loop + n_st : nullptr;
   double* d_tc = trace_contacts ? h->d_loop + n_st + n_tf : nullptr;
   HIP_TRY(hipMemcpyAsync(d_st, states, sizeof(qmpc_loop_state) * B, hipMemcpyHostToDevice, h->stream));
+  if (outcomes) HIP_TRY(hipMemcpyAsync(h->d_outcome, outcomes, sizeof(qmpc_loop_outcome) * B, hipMemcpyHostToDevice, h->stream));
   if (ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
   if (plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
-  const qmpc_status rs = qmpc_loop_run_instances_device(h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
-                                                        d_tf, d_tc, nullptr);
+  if (push) HIP_TRY(hipMemcpyAsync(h->d_push, push, sizeof(qmpc_push_params) * B * (size_t)per_robot, hipMemcpyHostToDevice, h->stream));
+  const qmpc_status rs = loop_records_device(kind, h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
+                                             d_tf, d_tc, op, outcomes ? h->d_outcome : nullptr, push ? h->d_push : nullptr, per_robot,
+                                             nullptr);
   if (rs != QMPC_OK) return rs;
   HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
+  if (outcomes) HIP_TRY(hipMemcpyAsync(outcomes, h->d_outcome, sizeof(qmpc_loop_outcome) * B, hipMemcpyDeviceToHost, h->stream));
   if (d_tf) HIP_TRY(hipMemcpyAsync(trace_forces, d_tf, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream));
   if (d_tc) HIP_TRY(hipMemcpyAsync(trace_contacts, d_tc, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1533,7 +1540,7 @@ qmpc_status qmpc_loop_run(qmpc_handle* h, const qmpc_loop_params* lp, int32_t ba
   if (batch == 0 || ticks == 0) return QMPC_OK;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
   HIP_TRY(hipSetDevice(h->device));
-  return loop_run_host(h, lp, batch, states, ticks, nullptr, nullptr, trace_forces, trace_contacts);
+  return loop_records_host(REC_PLAIN, h, lp, batch, states, ticks, nullptr, nullptr, trace_forces, trace_contacts, nullptr, nullptr, nullptr, 0);
 }
 
 // ---- the closed loop with per-robot controller and plant records (qmpc_loop_inst.hip) -------------------------------------
@@ -1602,11 +1609,18 @@ static qmpc_status loop_inst_tick_solve(qmpc_handle* h, const qmpc_plan& p, int3
   return QMPC_OK;
 }
 
-qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
-                                           int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
-                                           double* d_trace_forces, double* d_trace_contacts, void* stream) {
+// The device-buffer closed loop of every kind with records.  kind REC_PLAIN (qmpc_loop_run_instances_device): the call without
+// records is the plain loop.  REC_OUTCOME / REC_PUSH (qmpc_loop_run_outcomes_device / qmpc_loop_run_pushes_device): the same call
+// with the kernels of the kind's unit in place of the plain unit's; without records (both NULL) every robot's plant block carries
+// the handle's mass and inverse inertia, and the call-level checks are those of a call with plant records.  d_push (REC_PUSH):
+// per_robot windows per robot, checked once after the plant expansion.
+static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                       int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                       double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                       qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot, void* stream) {
   if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !d_states)) return QMPC_BAD_ARGUMENT;
-  if (!d_ctrl && !d_plant)
+  if (kind != REC_PLAIN && (!op || (batch > 0 && !d_outcomes))) return QMPC_BAD_ARGUMENT;
+  if (kind == REC_PLAIN && !d_ctrl && !d_plant)
     return loop_run_impl(h, lp, batch, d_states, ticks, d_trace_forces, d_trace_contacts, nullptr, nullptr, nullptr, nullptr, stream);
   const qmpc_status cs = loop_instances_check(h, lp, batch, d_ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
@@ -1619,28 +1633,42 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
   const qmpc_status ss = loop_setup(h, s, warm && !lpp.fused);
   if (ss != QMPC_OK) return ss;
   const qmpc_loop_params LP = *lp;
+  const auto& R = kRec[kind];
   // the records are expanded once per call: the controllers' blocks (or, for the persistent kernel without controller records,
   // the handle's block per robot) and the plant blocks with each robot's verdict
   if (d_ctrl) HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_ctrl, inst_dev(h), inst_status(h)));
-  HIP_TRY(qmpc_loop_inst_expand_launch(s, &h->dev, sizeof h->dev, d_plant, d_ctrl, d_ctrl ? inst_status(h) : nullptr,
-                                       (!d_ctrl && lpp.fused) ? inst_dev(h) : nullptr, plant_dev(h), (int)batch));
+  void* bcast = (!d_ctrl && lpp.fused) ? inst_dev(h) : nullptr;
+  if (d_ctrl || d_plant)
+    HIP_TRY(qmpc_loop_inst_expand_launch(s, &h->dev, sizeof h->dev, d_plant, d_ctrl, d_ctrl ? inst_status(h) : nullptr, bcast,
+                                         plant_dev(h), (int)batch));
+  else
+    HIP_TRY(qmpc_loop_outcome_expand_base_launch(s, &h->dev, sizeof h->dev, bcast, plant_dev(h), (int)batch));
+  if (d_push) HIP_TRY(qmpc_loop_push_check_launch(s, d_push, (int)per_robot, plant_dev(h), (int)batch));
   if (lpp.fused) {
-    HIP_TRY(qmpc_loop_inst_fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, d_states, h->d_in, h->d_forces,
-                                        h->d_info, d_trace_forces, d_trace_contacts, (int)ticks, lpp.gws ? h->d_gws : nullptr));
+    HIP_TRY(R.fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, d_states, h->d_in, h->d_forces, h->d_info,
+                           d_trace_forces, d_trace_contacts, (int)ticks, lpp.gws ? h->d_gws : nullptr, op, d_outcomes, d_push,
+                           (int)per_robot));
     return QMPC_OK;
   }
   auto one_tick = [&](bool first) -> qmpc_status {
-    HIP_TRY(qmpc_loop_inst_front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch));
+    HIP_TRY(R.front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch, op, d_outcomes));
     // with controller records the solve on the blocks expanded above, without them the plain loop's
     const qmpc_status st = d_ctrl ? loop_inst_tick_solve(h, lpp, batch, s) : loop_tick_solve(h, batch, s, warm, first, false);
     if (st != QMPC_OK) return st;
-    HIP_TRY(qmpc_loop_inst_post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts,
-                                       h->d_loop_row, plant_dev(h), (int)batch));
+    HIP_TRY(R.post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, h->d_loop_row, plant_dev(h),
+                          (int)batch, op, d_outcomes, d_push, (int)per_robot));
     return QMPC_OK;
   };
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
   if (d_ctrl && lpp.variant == 4) HIP_TRY(qmpc_lane_inst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   return replay_ticks(h, lpp, s, ticks, warm, one_tick);
+}
+
+qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                           int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                           double* d_trace_forces, double* d_trace_contacts, void* stream) {
+  return loop_records_device(REC_PLAIN, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, nullptr, nullptr,
+                             nullptr, 0, stream);
 }
 
 qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -1653,7 +1681,7 @@ qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, 
   HIP_TRY(hipSetDevice(h->device));
   const qmpc_status es = loop_instances_buffers(h, batch, ctrl != nullptr, lp->warm_start != 0.0, nullptr);
   if (es != QMPC_OK || ticks == 0) return es;
-  return loop_run_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts);
+  return loop_records_host(REC_PLAIN, h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, nullptr, nullptr, nullptr, 0);
 }
 
 // ---- the same closed loop with per-robot outcome records (qmpc_loop_outcome.hip) -------------------------------------------
@@ -1679,73 +1707,16 @@ void qmpc_loop_outcome_init(qmpc_loop_outcome* o, int32_t batch) {
   }
 }
 
-// The call of qmpc_loop_run_instances_device with the outcome kernels in place of its own.  Without records (both NULL) every
-// robot's plant block carries the handle's mass and inverse inertia: the call-level checks are those of a call with plant records.
-// d_push (qmpc_loop_run_pushes_device; NULL: qmpc_loop_run_outcomes_device, launch for launch): per_robot windows per robot,
-// checked once after the plant expansion, and the push kernels (qmpc_loop_push.hip) in place of the post step's.
-static qmpc_status loop_outcomes_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
-                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
-                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
-                                        qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot, void* stream) {
-  if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!d_states || !d_outcomes))) return QMPC_BAD_ARGUMENT;
-  const qmpc_status cs = loop_instances_check(h, lp, batch, d_ctrl != nullptr);
-  if (cs != QMPC_OK || batch == 0) return cs;
-  const bool warm = lp->warm_start != 0.0;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  qmpc_plan lpp;
-  const qmpc_status es = loop_instances_buffers(h, batch, d_ctrl != nullptr, warm, &lpp);
-  if (es != QMPC_OK || ticks == 0) return es;      // ticks = 0: the buffers only
-  const qmpc_status ss = loop_setup(h, s, warm && !lpp.fused);
-  if (ss != QMPC_OK) return ss;
-  const qmpc_loop_params LP = *lp;
-  const qmpc_outcome_params OP = *op;
-  if (d_ctrl) HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_ctrl, inst_dev(h), inst_status(h)));
-  void* bcast = (!d_ctrl && lpp.fused) ? inst_dev(h) : nullptr;
-  if (d_ctrl || d_plant)
-    HIP_TRY(qmpc_loop_inst_expand_launch(s, &h->dev, sizeof h->dev, d_plant, d_ctrl, d_ctrl ? inst_status(h) : nullptr, bcast,
-                                         plant_dev(h), (int)batch));
-  else
-    HIP_TRY(qmpc_loop_outcome_expand_base_launch(s, &h->dev, sizeof h->dev, bcast, plant_dev(h), (int)batch));
-  if (d_push) HIP_TRY(qmpc_loop_push_check_launch(s, d_push, (int)per_robot, plant_dev(h), (int)batch));
-  if (lpp.fused) {
-    if (d_push) {
-      HIP_TRY(qmpc_loop_push_fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, &OP, d_states, h->d_in,
-                                          h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, d_outcomes, d_push, (int)per_robot,
-                                          (int)ticks, lpp.gws ? h->d_gws : nullptr));
-      return QMPC_OK;
-    }
-    HIP_TRY(qmpc_loop_outcome_fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, &OP, d_states, h->d_in,
-                                           h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, d_outcomes, (int)ticks,
-                                           lpp.gws ? h->d_gws : nullptr));
-    return QMPC_OK;
-  }
-  auto one_tick = [&](bool first) -> qmpc_status {
-    HIP_TRY(qmpc_loop_outcome_front_launch(s, &LP, &OP, d_states, h->d_in, h->d_loop_row, plant_dev(h), d_outcomes, (int)batch));
-    const qmpc_status st = d_ctrl ? loop_inst_tick_solve(h, lpp, batch, s) : loop_tick_solve(h, batch, s, warm, first, false);
-    if (st != QMPC_OK) return st;
-    if (d_push)
-      HIP_TRY(qmpc_loop_push_post_launch(s, &LP, &OP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, h->d_loop_row,
-                                         plant_dev(h), d_outcomes, d_push, (int)per_robot, (int)batch));
-    else
-      HIP_TRY(qmpc_loop_outcome_post_launch(s, &LP, &OP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts,
-                                            h->d_loop_row, plant_dev(h), d_outcomes, (int)batch));
-    return QMPC_OK;
-  };
-  // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
-  if (d_ctrl && lpp.variant == 4) HIP_TRY(qmpc_lane_inst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
-  return replay_ticks(h, lpp, s, ticks, warm, one_tick);
-}
-
 qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
                                           int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                           double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                           qmpc_loop_outcome* d_outcomes, void* stream) {
-  return loop_outcomes_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, nullptr, 0,
-                              stream);
+  return loop_records_device(REC_OUTCOME, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
+                             nullptr, 0, stream);
 }
 
-// the host-buffer call; push (qmpc_loop_run_pushes; NULL: qmpc_loop_run_outcomes): per_robot windows per robot, staged in h->d_push
+// the host-buffer call's checks and buffers (the staging itself: loop_records_host); push (qmpc_loop_run_pushes; NULL:
+// qmpc_loop_run_outcomes): per_robot windows per robot, staged in h->d_push
 static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
                                       const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                       double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
@@ -1768,34 +1739,8 @@ static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp
   if (push && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
   if (ticks == 0) return es;
   if (!h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
-  // states and traces through the staging of qmpc_loop_run (loop_run_host), the records through their own
-  const size_t B = (size_t)batch, T = (size_t)ticks;
-  const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
-               n_tc = trace_contacts ? 4 * B * T : 0;
-  if (h->loop_cap < n_st + n_tf + n_tc) {
-    if (h->d_loop) (void)hipFree(h->d_loop);
-    h->d_loop = nullptr;
-    h->loop_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_loop, sizeof(double) * (n_st + n_tf + n_tc)));
-    h->loop_cap = n_st + n_tf + n_tc;
-  }
-  qmpc_loop_state* d_st = reinterpret_cast<qmpc_loop_state*>(h->d_loop);
-  double* d_tf = trace_forces ? h->d_loop + n_st : nullptr;
-  double* d_tc = trace_contacts ? h->d_loop + n_st + n_tf : nullptr;
-  HIP_TRY(hipMemcpyAsync(d_st, states, sizeof(qmpc_loop_state) * B, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_outcome, outcomes, sizeof(qmpc_loop_outcome) * B, hipMemcpyHostToDevice, h->stream));
-  if (ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
-  if (plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
-  if (push) HIP_TRY(hipMemcpyAsync(h->d_push, push, sizeof(qmpc_push_params) * B * (size_t)per_robot, hipMemcpyHostToDevice, h->stream));
-  const qmpc_status rs = loop_outcomes_device(h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
-                                              d_tf, d_tc, op, h->d_outcome, push ? h->d_push : nullptr, per_robot, nullptr);
-  if (rs != QMPC_OK) return rs;
-  HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(outcomes, h->d_outcome, sizeof(qmpc_loop_outcome) * B, hipMemcpyDeviceToHost, h->stream));
-  if (d_tf) HIP_TRY(hipMemcpyAsync(trace_forces, d_tf, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream));
-  if (d_tc) HIP_TRY(hipMemcpyAsync(trace_contacts, d_tc, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return QMPC_OK;
+  return loop_records_host(push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes,
+                           push, per_robot);
 }
 
 qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -1817,8 +1762,8 @@ qmpc_status qmpc_loop_run_pushes_device(qmpc_handle* h, const qmpc_loop_params* 
     return qmpc_loop_run_outcomes_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
                                          stream);
   if (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES) return QMPC_BAD_ARGUMENT;
-  return loop_outcomes_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                              pushes_per_robot, stream);
+  return loop_records_device(REC_PUSH, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
+                             pushes_per_robot, stream);
 }
 
 qmpc_status qmpc_loop_run_pushes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,

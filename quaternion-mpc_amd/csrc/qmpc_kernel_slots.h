@@ -12,7 +12,7 @@
 
 namespace qmpc {
 
-// the wrench-form variants 3 / 5 / 6 -> 0 / 1 / 2 (qmpc_solve_w_inst_kernel, qmpc_loop_fused_inst_kernel: the slot itself)
+// the wrench-form variants 3 / 5 / 6 -> 0 / 1 / 2 (qmpc_solve_w_inst_kernel, qmpc_loop_rec_fused_kernel: the slot itself)
 constexpr int kWformVars = 3;
 static inline int wform_index(int var) { return var == 3 ? 0 : var == 5 ? 1 : var == 6 ? 2 : -1; }
 // the variants 0 1 2 3 5 6 of a body every launch form of the converged mode shares -> 0 .. 5

@@ -1,0 +1,243 @@
+// qmpc_loop_rec.inc -- the kernels of the closed loop with per-robot records and their launchers, defined once.  Included by
+// qmpc_loop_inst.hip, qmpc_loop_outcome.hip and qmpc_loop_push.hip inside the unit's namespace, after qmpc_loop.hip, with
+//   QMPC_REC_EXT 0   controller and plant records only                          (qmpc_loop_run_instances*)
+//                1   ... and the outcome step after the post step               (qmpc_loop_run_outcomes*)
+//                2   ... whose plant step integrates under timed push windows   (qmpc_loop_run_pushes*)
+// Textual inclusion, not a template over EXT: each unit compiles to the instructions it had as a file of its own (a shared
+// __forceinline__ function template moved the register assignment of every kernel; DESIGN.md).  The parameters a smaller EXT
+// does not have are written with the two macros below; a kernel's parameter list is that of its EXT and of no other.
+//   per tick    qmpc_loop_rec_front_kernel (EXT 0 / 1; the push call launches the outcome unit's) and qmpc_loop_rec_post_kernel
+//               around the solve the C entry point launches
+//   persistent  qmpc_loop_rec_fused_kernel<3|5|6>: qmpc_loop_fused_kernel<VAR, false, false, false> (QuatMpc's problem,
+//               converged mode, wrench-form body) with the robot's own controller and plant
+//   launchers   rec_set_lds, rec_fused_launch, rec_front_launch, rec_post_launch: one signature for the three units, the
+//               arguments beyond the unit's EXT ignored (declared for qmpc_hip.hip by its QMPC_REC_DECLARE)
+#if QMPC_REC_EXT >= 1
+#define QMPC_REC_OUTCOME(...) __VA_ARGS__
+#else
+#define QMPC_REC_OUTCOME(...)
+#endif
+#if QMPC_REC_EXT >= 2
+#define QMPC_REC_PUSH(...) __VA_ARGS__
+#else
+#define QMPC_REC_PUSH(...)
+#endif
+
+// the trace row of a robot that does not move in this tick
+__device__ inline void loop_zero_row(double* __restrict__ trace_f, double* __restrict__ trace_c) {
+  if (trace_f) for (int a = 0; a < 12; ++a) trace_f[a] = 0.0;
+  if (trace_c) for (int a = 0; a < 4; ++a) trace_c[a] = 0.0;
+}
+
+// A frozen robot (invalid record): its state untouched except status and iterations, its trace row of this tick zero
+__device__ inline void loop_freeze(qmpc_loop_state& s, double* __restrict__ trace_f, double* __restrict__ trace_c) {
+  s.status = (double)QMPC_BAD_PARAMS;
+  s.iterations = 0.0;
+  loop_zero_row(trace_f, trace_c);
+}
+
+#if QMPC_REC_EXT >= 1
+// the robot of record o is halted: it went down in an earlier tick (or call) and the caller asked to stop such robots
+__device__ inline bool outcome_halted(const qmpc_outcome_params& OP, const qmpc_loop_outcome& o) {
+  return OP.stop_when_down != 0.0 && o.down_tick >= 0.0;
+}
+#endif
+
+#if QMPC_REC_EXT >= 2
+// the robot's plant block with the effective wrench of the tick that starts at state.tick = t
+__device__ inline PlantDev push_plant(const PlantDev& pl, const qmpc_push_params* __restrict__ w, int per_robot, double t) {
+  PlantDev p = pl;
+  qmpc_loop::loop_push_wrench(w, per_robot, t, p.force, p.torque);
+  return p;
+}
+#endif
+
+// ---- per-tick form -----------------------------------------------------------------------------------------------------
+#if QMPC_REC_EXT <= 1
+// The front end of qmpc_loop_front_kernel; the record of a frozen robot, or of one halted under stop_when_down, gets a NaN
+// attitude instead, which every solve kernel rejects before its first iteration (QMPC_NAN_INPUT; the post kernel ignores it)
+__global__ __launch_bounds__(64) void qmpc_loop_rec_front_kernel(
+    qmpc_loop_params LP, QMPC_REC_OUTCOME(qmpc_outcome_params OP, ) qmpc_loop_state* __restrict__ st, qmpc_input* __restrict__ rec,
+    int* __restrict__ row, const PlantDev* __restrict__ pl, QMPC_REC_OUTCOME(const qmpc_loop_outcome* __restrict__ oc, ) int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0 && row) *row += 1;                         // trace row of this tick (stream order: after the last post)
+  if (i >= batch) return;
+  if (pl[i].status != QMPC_OK QMPC_REC_OUTCOME(|| outcome_halted(OP, oc[i]))) {
+    rec[i].quat[0] = __builtin_nan("");
+    return;
+  }
+  loop_front_one(LP, st[i], rec[i]);
+}
+#endif
+
+__global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
+    qmpc_loop_params LP, QMPC_REC_OUTCOME(qmpc_outcome_params OP, ) qmpc_loop_state* __restrict__ st,
+    const double* __restrict__ forces, const qmpc_info* __restrict__ info, double* __restrict__ trace_f, double* __restrict__ trace_c,
+    const int* __restrict__ row, const PlantDev* __restrict__ pl, QMPC_REC_OUTCOME(qmpc_loop_outcome* __restrict__ oc, )
+    QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, ) int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  const size_t slot = (trace_f || trace_c) ? (size_t)(*row) * batch + i : 0;
+  double* tf = trace_f ? trace_f + 12 * slot : nullptr;
+  double* tc = trace_c ? trace_c + 4 * slot : nullptr;
+  if (pl[i].status != QMPC_OK) {      // frozen; an outcome record stays as it is
+    loop_freeze(st[i], tf, tc);
+    return;
+  }
+#if QMPC_REC_EXT >= 1
+  qmpc_loop_outcome o = oc[i];
+  if (outcome_halted(OP, o)) {        // halted: state and record untouched, a zero trace row
+    loop_zero_row(tf, tc);
+    return;
+  }
+#endif
+#if QMPC_REC_EXT >= 2
+  const PlantDev p = push_plant(pl[i], push + (size_t)i * per_robot, per_robot, st[i].tick);
+  loop_post_plant_one(p, LP, st[i], forces + 12 * (size_t)i, info[i], tf, tc);
+#else
+  loop_post_plant_one(pl[i], LP, st[i], forces + 12 * (size_t)i, info[i], tf, tc);
+#endif
+#if QMPC_REC_EXT >= 1
+  qmpc_loop::loop_outcome_one(OP, st[i], o);
+  oc[i] = o;
+#endif
+}
+
+// ---- persistent form ---------------------------------------------------------------------------------------------------
+// P is bound to Pi[b] as in qmpc_solve_w_inst_kernel (the address depends on blockIdx.x only, the reads stay scalar loads), the
+// post step reads plants[b].  A frozen robot's wave writes its status and zero trace rows and leaves.  The warm start works as
+// in the plain kernel (warm_t; the entry point refuses it with controller records, whose per-tick form has no warm-started
+// kernel).
+// EXT >= 1: lane 0 holds the robot's outcome record from the first tick to the last and stores it once.  `halt` is lane 0's
+// verdict after the outcome step, made uniform with a readfirstlane (all lanes are active there): the wave zero-fills the trace
+// rows left and returns, which frees its SIMD slot for the next robot.  A robot halted by an earlier call leaves like a frozen
+// one, its state untouched.
+// EXT 2: lane 0 reads the robot's windows from global memory inside the post step of each tick: nothing of the push is live
+// across the solve (variants 5 / 6 sit at their 256-register limit).
+// (The two zero-fill loops stay written out: as calls of one inline function they compile to other instructions.)
+template <int VAR>
+__global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QuatModel, VAR)) void qmpc_loop_rec_fused_kernel(
+    const DevParams* __restrict__ Pi, const PlantDev* __restrict__ plants, qmpc_loop_params LP, QMPC_REC_OUTCOME(qmpc_outcome_params OP, )
+    qmpc_loop_state* __restrict__ st, qmpc_input* __restrict__ rec, double* __restrict__ forces, qmpc_info* __restrict__ info,
+    double* __restrict__ trace_f, double* __restrict__ trace_c, QMPC_REC_OUTCOME(qmpc_loop_outcome* __restrict__ outcomes, )
+    QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, ) int ticks, int batch, double* __restrict__ gws) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int b = blockIdx.x;
+  if (b >= batch) return;
+  const int lane = threadIdx.x;
+  typedef QuatModel MD;
+  constexpr bool PROF = false;
+  constexpr int OCC = QMPC_SOLVE_WAVES(QuatModel, VAR);
+  const qmpc_input* in_ = rec;
+  double *traj_u = nullptr, *traj_x = nullptr;
+  long long* prof_out = nullptr;
+  const bool frozen = plants[b].status != QMPC_OK;
+  if (frozen QMPC_REC_OUTCOME(|| outcome_halted(OP, outcomes[b]))) {      // uniform: every lane reads the same words
+    if (frozen && lane == 0) {
+      st[b].status = (double)QMPC_BAD_PARAMS;
+      st[b].iterations = 0.0;
+    }
+    for (int t = 0; t < ticks; ++t) {
+      const size_t slot = (size_t)t * batch + b;
+      if (trace_f && lane < 12) trace_f[12 * slot + lane] = 0.0;
+      if (trace_c && lane < 4) trace_c[4 * slot + lane] = 0.0;
+    }
+    return;
+  }
+  const DevParams& P = Pi[b];
+#if QMPC_REC_EXT >= 1
+  qmpc_loop_outcome oc;
+  if (lane == 0) oc = outcomes[b];
+#endif
+  bool prev_ok = false;
+  for (int t = 0; t < ticks; ++t) {
+    if (lane == 0) loop_front_one<OCC>(LP, st[b], rec[b]);
+    __syncthreads();                      // the record (global memory) is visible to the wave
+    [&]() {
+      const int warm_t = (LP.warm_start != 0.0 && prev_ok) ? t : 0;   // t > 0 and the last solve left a usable U in LDS
+      constexpr int WVAR = VAR;
+      const int wslot = b;
+      constexpr const double* resume = nullptr;
+#include "qmpc_wform_body.inc"
+    }();
+    __syncthreads();
+    prev_ok = info[b].status == QMPC_OK || info[b].status == QMPC_MAX_ITER;   // uniform: every lane reads the same word
+#if QMPC_REC_EXT >= 1
+    int halt = 0;
+#endif
+    if (lane == 0) {
+      const size_t slot = (size_t)t * batch + b;
+#if QMPC_REC_EXT >= 2
+      const PlantDev p = push_plant(plants[b], push + (size_t)b * per_robot, per_robot, st[b].tick);
+      loop_post_plant_one<OCC>(p, LP, st[b], forces + 12 * (size_t)b, info[b], trace_f ? trace_f + 12 * slot : nullptr,
+                               trace_c ? trace_c + 4 * slot : nullptr);
+#else
+      loop_post_plant_one<OCC>(plants[b], LP, st[b], forces + 12 * (size_t)b, info[b], trace_f ? trace_f + 12 * slot : nullptr,
+                               trace_c ? trace_c + 4 * slot : nullptr);
+#endif
+#if QMPC_REC_EXT >= 1
+      qmpc_loop::loop_outcome_one(OP, st[b], oc);
+      halt = outcome_halted(OP, oc) ? 1 : 0;
+#endif
+    }
+    __syncthreads();
+#if QMPC_REC_EXT >= 1
+    if (__builtin_amdgcn_readfirstlane(halt)) {
+      for (int u = t + 1; u < ticks; ++u) {
+        const size_t slot = (size_t)u * batch + b;
+        if (trace_f && lane < 12) trace_f[12 * slot + lane] = 0.0;
+        if (trace_c && lane < 4) trace_c[4 * slot + lane] = 0.0;
+      }
+      break;
+    }
+#endif
+  }
+#if QMPC_REC_EXT >= 1
+  if (lane == 0) outcomes[b] = oc;
+#endif
+}
+
+// ---- launchers (host; called from qmpc_hip.hip; hidden: not part of the C ABI) ------------------------------------------------
+// the launch table of this unit: the persistent kernels by wrench-form variant 3 / 5 / 6 (qmpc_kernel_slots.h: wform_index)
+static decltype(&qmpc_loop_rec_fused_kernel<3>) const kRecFused[] = {qmpc_loop_rec_fused_kernel<3>, qmpc_loop_rec_fused_kernel<5>, qmpc_loop_rec_fused_kernel<6>};
+static_assert(sizeof kRecFused / sizeof kRecFused[0] == qmpc::kWformVars, "qmpc_kernel_slots.h");
+
+__attribute__((visibility("hidden"))) hipError_t rec_set_lds() { return set_max_lds(kRecFused); }
+
+// one launch for all ticks: var 3 / 5 / 6 (qmpc_plan.h: plan_loop_instances)
+__attribute__((visibility("hidden"))) hipError_t rec_fused_launch(
+    int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants, const qmpc_loop_params* lp,
+    qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws,
+    const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot) {
+  const int k = qmpc::wform_index(var);
+  if (k < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kRecFused[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks),
+                     static_cast<const PlantDev*>(plants), *lp, QMPC_REC_OUTCOME(*op, ) st, rec, forces, info, trace_f, trace_c,
+                     QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_PUSH(push, per_robot, ) ticks, batch, gws);
+  return hipGetLastError();
+}
+
+#if QMPC_REC_EXT <= 1
+__attribute__((visibility("hidden"))) hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st,
+                                                                  qmpc_input* rec, int* row, const void* plants, int batch,
+                                                                  const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes) {
+  hipLaunchKernelGGL(qmpc_loop_rec_front_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, *lp, QMPC_REC_OUTCOME(*op, ) st, rec, row,
+                     static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, ) batch);
+  return hipGetLastError();
+}
+#endif
+
+__attribute__((visibility("hidden"))) hipError_t rec_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st,
+                                                                 const double* forces, const qmpc_info* info, double* trace_f,
+                                                                 double* trace_c, const int* row, const void* plants, int batch,
+                                                                 const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
+                                                                 const qmpc_push_params* push, int per_robot) {
+  hipLaunchKernelGGL(qmpc_loop_rec_post_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, *lp, QMPC_REC_OUTCOME(*op, ) st, forces, info,
+                     trace_f, trace_c, row, static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, )
+                     QMPC_REC_PUSH(push, per_robot, ) batch);
+  return hipGetLastError();
+}
+
+#undef QMPC_REC_OUTCOME
+#undef QMPC_REC_PUSH
+#undef QMPC_REC_EXT

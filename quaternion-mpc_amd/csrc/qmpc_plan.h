@@ -314,7 +314,7 @@ static inline qmpc_plan plan_instances(const qmpc_select& s, int batch, int poli
 // The plan of qmpc_loop_run_instances* (the closed loop with per-robot controller and / or plant records; qmpc_loop_inst.hip).
 // `has_ctrl`: controller records are given (their solve is the per-instance wrench-form kernel), `warm`: lp->warm_start.
 //   persistent  where the plain loop of this batch takes its persistent kernel (2048 robots, 4096 warm, or QMPC_LOOP_FUSED)
-//               on a wrench-form variant: that very variant (qmpc_loop_fused_inst_kernel<3|5|6>), fused = true;
+//               on a wrench-form variant: that very variant (qmpc_loop_rec_fused_kernel<3|5|6>), fused = true;
 //   per tick    otherwise: with controller records the plan of qmpc_solve_instances* (plan_instances), without them the
 //               plain loop's tick (lane kernel and hand-off included); fused = false.
 // NONE: not QuatMpc's problem in the converged mode, controller records with the warm start (the per-tick form has no

@@ -8,19 +8,20 @@ import tempfile
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(REPO))
+from __graft_entry__ import hip_units  # noqa: E402
+
 CSRC = REPO / "quaternion-mpc_amd" / "csrc"
 print("ISA metadata of the final build (hipcc --offload-arch=gfx950 -O2 <per-unit flags of __graft_entry__.py> -S --cuda-device-only; .amdgpu_metadata notes), one row per kernel")
 print("columns: kernel | vgpr_count | agpr_count | sgpr_count | vgpr_spill_count | sgpr_spill_count | private_segment_fixed_size (scratch bytes) | group_segment_fixed_size (static LDS)")
-WAVE = ["-mllvm", "-disable-machine-licm", "-mllvm", "-disable-machine-sink"]
-for tu, extra in (("qmpc_hip.hip", WAVE), ("qmpc_loop_fused.hip", WAVE), ("qmpc_loop_inst.hip", WAVE), ("qmpc_loop_outcome.hip", WAVE), ("qmpc_loop_push.hip", WAVE), ("qmpc_wform.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
-                  ("qmpc_lane.hip", ["-mllvm", "-disable-lsr", "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-DQL_UNIT=1"]),
-                  ("qmpc_lane_ref.hip", ["-mllvm", "-disable-lsr", "-DQL_UNIT=2"]),
-                  ("qmpc_lane_inst.hip", ["-mllvm", "-disable-lsr", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
-                  ("qmpc_wform_inst_list.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"])):
+# the units and their flags: the table the library is built from (the flags every unit has are not repeated in its header row)
+BASE = ["--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC"]
+for name, _, flags in hip_units():
+    tu, extra = name + ".hip", [f for f in flags if f not in BASE]
     with tempfile.TemporaryDirectory() as d:
         asm = Path(d) / "tu.s"
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", *extra, "-std=c++17", "-S", "--cuda-device-only", "-o", str(asm),
-                        str(CSRC / tu)], check=True, stderr=subprocess.DEVNULL)
+        subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-S", "--cuda-device-only", "-o", str(asm), str(CSRC / tu)], check=True,
+                       stderr=subprocess.DEVNULL)
         txt = asm.read_text()
     print(f"---- translation unit {tu} (extra flags: {' '.join(extra)})" + (" (the kernel calls its passes as functions: the per-function figures follow the kernel rows)" if "lane" in tu else ""))
     for m in re.finditer(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", txt, re.S):
