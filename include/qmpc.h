@@ -302,8 +302,11 @@ enum qmpc_query_what {
   QMPC_QUERY_LOOP_INSTANCES_PLAN  = 9,  /* arg = batch (bits 0-31) | 1 << 32 with controller records | 1 << 33 with
                                            lp->warm_start: the launch qmpc_loop_run_instances* takes, 16 * form + family --
                                            form 1 the persistent kernel, 2 the per-tick sequence; family the
-                                           qmpc_kernel_family of its solve.  0: the call is refused */
-  QMPC_QUERY_INSTANCES_POLICY     = 10  /* the handle's policy for qmpc_solve_instances*, a qmpc_instances_policy value */
+                                           qmpc_kernel_family of its solve.  0: the call is refused.  Bits 32 and 33 together
+                                           answer under the handle's qmpc_set_loop_warm_records setting (default: refused) */
+  QMPC_QUERY_INSTANCES_POLICY     = 10, /* the handle's policy for qmpc_solve_instances*, a qmpc_instances_policy value */
+  QMPC_QUERY_LOOP_WARM_RECORDS    = 11  /* 1: the closed loops with controller records accept lp->warm_start on this handle
+                                           (qmpc_set_loop_warm_records); 0 (default): they refuse it */
 };
 enum qmpc_kernel_family {
   QMPC_KERNEL_NONE         = 0,
@@ -622,7 +625,8 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
  *
  * Call level: QMPC_BAD_ARGUMENT for null pointers and for an 8-point handle (as qmpc_loop_run); QMPC_UNSUPPORTED, when
  * ctrl or plant is non-NULL, for a ConvexMpc or reference-mode handle; with ctrl non-NULL also for lp->warm_start != 0
- * and for a handle whose knobs leave no wrench-form kernel (QMPC_WFORM=0); QMPC_BATCH_TOO_LARGE above max_batch.  With
+ * unless the handle opted in (qmpc_set_loop_warm_records below; off by default) and for a handle whose knobs leave no
+ * wrench-form kernel (QMPC_WFORM=0); QMPC_BATCH_TOO_LARGE above max_batch.  With
  * plant only, everything the plain loop supports works, the warm start included, and the per-tick form keeps the plain
  * loop's solve (lane kernel and hand-off included).  The joint-level loop is not covered: run
  * qmpc_loop_joint_commands_device on the states afterwards.
@@ -644,7 +648,22 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
  * family's.  Below the switch-over, without ctrl and under the default policy nothing changes, bit for bit.  The lane
  * kernel's buffers (workspace, sort scratch, per-lane parameter rows, hand-off records) are allocated before the tick is
  * captured, by a call with ticks = 0 too, and by qmpc_prepare(h, batch) under AUTO when `batch` robots with ctrl take
- * this form; under the default policy no call allocates them. */
+ * this form; under the default policy no call allocates them.
+ *
+ * Warm start with controller records: qmpc_set_loop_warm_records(h, 1).  lp->warm_start != 0 is then accepted with ctrl by
+ * qmpc_loop_run_instances*, qmpc_loop_run_outcomes* and qmpc_loop_run_pushes*, with the plain loop's rule: the first tick of a
+ * call starts cold, every later solve of a robot starts from its previous solution shifted by one knot unless that solve
+ * failed (a robot that was frozen or halted never solved).  Launch: the persistent kernel up to 4096 robots, as with plant
+ * records only; beyond, the per-tick sequence whose later ticks run qmpc_solve_w_inst_warm_kernel on the variant of
+ * qmpc_solve_instances* -- the solution travels through the handle's trajectory buffer -- and, under QMPC_INSTANCES_AUTO from
+ * the larger of qmpc_solve_instances*' switch-over and the warm-started loop's on (18432 robots at N <= 12, 20480 at
+ * N = 13 ... 22), the stance sort, qmpc_lane_inst_warm_kernel to the warm ticks' iteration cap (qmpc_query QMPC_QUERY_LANE_CAP,
+ * arg 3) and the per-instance list kernel on the stragglers; the cold first tick of a call runs the lane kernel without cap and
+ * hand-off, so QMPC_QUERY_LAST_KERNEL after a call of one tick says QMPC_KERNEL_LANE where the plan says LANE_HANDOFF.  With uniform records every form gives the bytes of
+ * qmpc_loop_run_device with the same lp at the same size.  The buffers this adds (the trajectory buffer, 96 N bytes x
+ * max_batch; the lane kernel's under AUTO) are allocated before the tick is captured, by a call with ticks = 0 too, and by
+ * qmpc_prepare.  After such a call the device entry points may run inside a stream capture of the CALLER's (persistent form and
+ * per-tick wave form; the ticks become nodes of the caller's graph, and the library begins no capture of its own inside it); a handle that never opts in plans, refuses, computes and allocates as before. */
 typedef struct qmpc_plant_params {   /* 16 doubles, 128 B: the TRUE robot the plant integrates */
   double mass;
   double inertia[9];                 /* row-major, same convention as qmpc_params.inertia */
@@ -664,6 +683,11 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
                                            qmpc_loop_state* d_states, int32_t ticks,
                                            const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                            double* d_trace_forces, double* d_trace_contacts, void* stream);
+/* on = 1: the closed loops with controller records (the three pairs of entry points with ctrl) accept lp->warm_start on this
+ * handle; 0 (default): they refuse it with QMPC_UNSUPPORTED.  Holds until it is changed.  QMPC_BAD_ARGUMENT for a null handle
+ * or another value.  qmpc_query(QMPC_QUERY_LOOP_WARM_RECORDS) returns the setting, QMPC_QUERY_LOOP_INSTANCES_PLAN answers
+ * under it. */
+qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on);
 
 /* ---- per-robot outcome records of the closed loop (robustness sweeps) -------------------------------------------------
  * The other half of the question above: did robot i stay up, how far did it tilt, how well did it track its command, how
@@ -687,7 +711,8 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
  *
  * Scope and refusals: those of qmpc_loop_run_instances* with records -- a QuatMpc handle in the converged mode;
  * QMPC_UNSUPPORTED for a ConvexMpc or reference-mode handle, QMPC_BAD_ARGUMENT for an 8-point handle, with ctrl also
- * QMPC_UNSUPPORTED for lp->warm_start != 0 or a handle without a wrench-form kernel -- and QMPC_BAD_ARGUMENT for a NULL op
+ * QMPC_UNSUPPORTED for lp->warm_start != 0 (unless the handle opted in: qmpc_set_loop_warm_records) or a handle without a
+ * wrench-form kernel -- and QMPC_BAD_ARGUMENT for a NULL op
  * or outcomes.  ctrl and plant may both be NULL: plain robots on the handle's parameters (still a QuatMpc converged
  * handle).  Buffers: those of qmpc_loop_run_instances*; the host-buffer call adds a staging buffer for the records (128 B x
  * max_batch) on its first use.  No other call allocates it.  Under QMPC_INSTANCES_AUTO the ticks with ctrl take the lane

@@ -381,6 +381,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_pushes_device.restype = i32
     lib.qmpc_set_instances_policy.argtypes = [vp, i32]
     lib.qmpc_set_instances_policy.restype = i32
+    lib.qmpc_set_loop_warm_records.argtypes = [vp, i32]
+    lib.qmpc_set_loop_warm_records.restype = i32
     lib.qmpc_gather.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.qmpc_gather.restype = i32
     lib.qmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -541,6 +543,7 @@ EXPORTED_SYMBOLS = (
     "qmpc_loop_run_instances",
     "qmpc_loop_run_instances_device",
     "qmpc_set_instances_policy",
+    "qmpc_set_loop_warm_records",
     "qmpc_default_outcome_params",
     "qmpc_loop_outcome_init",
     "qmpc_sizeof_loop_outcome",
@@ -555,6 +558,7 @@ EXPORTED_SYMBOLS = (
 QUERY_HANDOFF_ACTIVE, QUERY_HANDOFF_ALLOC_FAILED, QUERY_KERNEL_FOR_BATCH, QUERY_LAST_KERNEL, QUERY_LANE_CAP, \
     QUERY_DEVICE_BYTES, QUERY_ZERO_COPY, QUERY_KERNEL_FOR_INSTANCES, QUERY_LOOP_INSTANCES_PLAN = 1, 2, 3, 4, 5, 6, 7, 8, 9
 QUERY_INSTANCES_POLICY = 10
+QUERY_LOOP_WARM_RECORDS = 11
 # enum qmpc_instances_policy
 INSTANCES_WAVE, INSTANCES_AUTO = 0, 1
 INSTANCES_POLICY = {"wave": INSTANCES_WAVE, "auto": INSTANCES_AUTO}
@@ -974,7 +978,8 @@ class Solver:
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
         as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN).  Answers under the handle's
-        instances policy: with ctrl under "auto" the per-tick form is ("per_tick", "lane_handoff" / "lane") from the switch-over on."""
+        instances policy: with ctrl under "auto" the per-tick form is ("per_tick", "lane_handoff" / "lane") from the switch-over on.
+        ctrl and warm together answer under set_loop_warm_records (default off: None)."""
         v = self.query(QUERY_LOOP_INSTANCES_PLAN, int(batch) | (int(bool(ctrl)) << 32) | (int(bool(warm)) << 33))
         if v == 0:
             return None
@@ -991,6 +996,16 @@ class Solver:
         st = self.lib.qmpc_set_instances_policy(self._h, value)
         if st != OK:
             raise QmpcError(st, "qmpc_set_instances_policy")
+
+    def set_loop_warm_records(self, on: bool = True):
+        """Let the loops with controller records (loop_run_instances* / loop_run_outcomes* / loop_run_pushes* with ctrl) accept
+        lp.warm_start on this handle (qmpc_set_loop_warm_records; default off: they refuse it).  Holds until it is changed."""
+        st = self.lib.qmpc_set_loop_warm_records(self._h, int(on))
+        if st != OK:
+            raise QmpcError(st, "qmpc_set_loop_warm_records")
+
+    def loop_warm_records(self) -> bool:
+        return bool(self.query(QUERY_LOOP_WARM_RECORDS))
 
     def instances_policy(self) -> str:
         return {v: k for k, v in INSTANCES_POLICY.items()}[self.query(QUERY_INSTANCES_POLICY)]

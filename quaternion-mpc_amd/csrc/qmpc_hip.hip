@@ -138,6 +138,19 @@ hipError_t qmpc_wform_inst_list_launch(int var, int grid, size_t lds, hipStream_
                                        double* forces, qmpc_info* info, double* traj_u, double* traj_x, const int* sel,
                                        const int* sel_count, double* gws, const double* hstate, int hcap);
 
+// qmpc_wform_inst_warm.hip / qmpc_lane_inst_warm.hip: the warm-started ticks of a closed loop with controller records
+// (qmpc_set_loop_warm_records) on the wave kernels and on the lane kernel
+hipError_t qmpc_wform_inst_warm_set_lds();
+hipError_t qmpc_loop_row_reset_launch(hipStream_t s, int* row);
+hipError_t qmpc_wform_inst_warm_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
+                                       const qmpc_input* in, const double* u_init, double* forces, qmpc_info* info, double* traj_u,
+                                       double* gws, int check_prev);
+hipError_t qmpc_lane_inst_warm_upload_params(int pslot, hipStream_t s, const void* dev_params, size_t dev_params_size);
+hipError_t qmpc_lane_inst_warm_launch_only(int pslot, int batch, hipStream_t s, const void* in, const void* dev_blocks, const int* status,
+                                           double* forces, qmpc_info* info, double* ws, double* prm, unsigned slots, const int* perm,
+                                           const double* u_init, double* traj_u, int check_prev, int iter_cap, int* hcount, int* hsel,
+                                           double* hstate, int hcap, int pair);
+
 struct qmpc_handle {
   qmpc_params params;
   DevParams dev;
@@ -188,6 +201,7 @@ struct qmpc_handle {
   qmpc_loop_outcome* d_outcome;   // staging of qmpc_loop_run_outcomes (the host-buffer call), on its first use: [max_batch] records
   qmpc_push_params* d_push;       // staging of qmpc_loop_run_pushes (the host-buffer call), on its first use: [max_batch][push_cap]
   int push_cap;                   // ... windows per robot it holds (grown when a call brings more)
+  int loop_warm_rec;              // qmpc_set_loop_warm_records: 1 the loops with controller records accept lp->warm_start (default 0)
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -343,6 +357,7 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   HIP_TRY(qmpc_wform_set_lds());
   for (const auto& r : kRec) HIP_TRY(r.set_lds());
   HIP_TRY(qmpc_wform_inst_list_set_lds());
+  HIP_TRY(qmpc_wform_inst_warm_set_lds());
   HIP_TRY(hipMalloc(&h->d_gws, sizeof(double) * (size_t)N * (13 * nu + 21 * nl + 30 * nl) * (size_t)max_batch));
   return QMPC_OK;
 }
@@ -834,6 +849,14 @@ qmpc_status qmpc_prepare(qmpc_handle* h, int32_t batch) {
     if (es == QMPC_OK) es = ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_LOOP_TICK, h->handoff_failed) != 0);
     if (es != QMPC_OK) return es;
   }
+  // ... and for their warm-started ticks on a handle that opted in (qmpc_set_loop_warm_records)
+  if (h->loop_warm_rec && h->inst_policy == QMPC_INSTANCES_AUTO &&
+      plan_loop_instances(h->sel, batch, true, true, h->inst_policy, h->handoff_failed, true).variant == 4) {
+    qmpc_status es = ensure_instance_buffers(h);
+    if (es == QMPC_OK) es = ensure_plant_buffers(h);
+    if (es == QMPC_OK) es = ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_WARM_LOOP_TICK, h->handoff_failed) != 0);
+    if (es != QMPC_OK) return es;
+  }
   // the pinned staging of the host-buffer calls: ALWAYS (a handle prepared for a lane-kernel batch may still be handed a smaller
   // batch on host buffers, which runs zero-copy), and the buffers the closed loops and the trajectory / warm-started calls
   // otherwise allocate on first use -- nothing of that may happen inside a caller's stream capture
@@ -1002,6 +1025,12 @@ qmpc_status qmpc_set_instances_policy(qmpc_handle* h, int32_t policy) {
   return QMPC_OK;
 }
 
+qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on) {
+  if (!h || (on != 0 && on != 1)) return QMPC_BAD_ARGUMENT;
+  h->loop_warm_rec = on;
+  return QMPC_OK;
+}
+
 qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value) {
   if (!h || !value) return QMPC_BAD_ARGUMENT;
   switch (what) {
@@ -1044,10 +1073,12 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
     case QMPC_QUERY_LOOP_INSTANCES_PLAN: {
       const int64_t b = arg & 0xffffffffLL;
       if (b < 1 || b > h->max_batch) return QMPC_BAD_ARGUMENT;
-      const qmpc_plan p = plan_loop_instances(h->sel, (int)b, (arg >> 32) & 1, (arg >> 33) & 1, h->inst_policy, h->handoff_failed);
+      const qmpc_plan p = plan_loop_instances(h->sel, (int)b, (arg >> 32) & 1, (arg >> 33) & 1, h->inst_policy, h->handoff_failed,
+                                              h->loop_warm_rec != 0);
       *value = p.family == QMPC_KERNEL_NONE ? 0 : 16 * (p.fused ? 1 : 2) + p.family;
       return QMPC_OK;
     }
+    case QMPC_QUERY_LOOP_WARM_RECORDS: *value = h->loop_warm_rec; return QMPC_OK;
     default: return QMPC_BAD_ARGUMENT;
   }
 }
@@ -1358,6 +1389,13 @@ static qmpc_status loop_tick_solve(qmpc_handle* h, int32_t batch, hipStream_t s,
   return launch_solve(h, batch, h->d_in, h->d_forces, h->d_info, nullptr, nullptr, s, QMPC_CALL_LOOP_TICK);
 }
 
+// the caller is capturing stream s into a graph of its own
+static bool stream_is_capturing(hipStream_t s) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return cs == hipStreamCaptureStatusActive;
+}
+
 // The per-tick form of the closed loop: `one_tick(first)` enqueues one tick (three kernels, four with the joint level); it is
 // captured once into a graph and replayed (the sequence is launch-bound for small batches); plain launches when capture is not
 // available on this stream.  tick_plan: the plan of the solve of the tick the loop repeats.
@@ -1382,7 +1420,9 @@ static qmpc_status replay_ticks(qmpc_handle* h, const qmpc_plan& tick_plan, hipS
     if (st != QMPC_OK) return st;
     t_start = 1;
   }
-  if (ticks - t_start > 1 && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+  // (a stream the CALLER is capturing takes the ticks as plain launches, which become nodes of the caller's graph: no capture
+  // is begun inside another)
+  if (ticks - t_start > 1 && !stream_is_capturing(s) && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
     const qmpc_status st = one_tick(false);
     const hipError_t ee = hipStreamEndCapture(s, &graph);
     if (st == QMPC_OK && ee == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess)
@@ -1410,11 +1450,21 @@ static qmpc_status replay_ticks(qmpc_handle* h, const qmpc_plan& tick_plan, hipS
 // The closed loop's set-up on stream s: the trace row counter, reset to -1 stream-ordered (no host staging), and for a warm start
 // in the per-tick form the handle's trajectory buffer, through which the solution travels from tick to tick (the persistent
 // kernel keeps it in LDS; the first tick of a call starts cold)
-static qmpc_status loop_setup(qmpc_handle* h, hipStream_t s, bool warm_ticks) {
+// (the buffers alone: also what a call with ticks = 0 allocates on a handle that opted in to warm starts with controller records)
+static qmpc_status ensure_loop_buffers(qmpc_handle* h, bool warm_ticks) {
   if (!h->d_loop_row) HIP_TRY(hipMalloc(&h->d_loop_row, sizeof(int)));
-  HIP_TRY(hipMemsetAsync(h->d_loop_row, 0xFF, sizeof(int), s));
   if (warm_ticks && !h->d_traj_u)
     HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * (size_t)h->params.horizon * (size_t)h->max_batch));
+  return QMPC_OK;
+}
+static qmpc_status loop_setup(qmpc_handle* h, hipStream_t s, bool warm_ticks) {
+  const qmpc_status es = ensure_loop_buffers(h, warm_ticks);
+  if (es != QMPC_OK) return es;
+  // inside a stream capture of the caller's the reset is a kernel node like the ticks that follow it, not a memset node
+  if (stream_is_capturing(s))
+    HIP_TRY(qmpc_loop_row_reset_launch(s, h->d_loop_row));
+  else
+    HIP_TRY(hipMemsetAsync(h->d_loop_row, 0xFF, sizeof(int), s));
   return QMPC_OK;
 }
 
@@ -1558,26 +1608,34 @@ void qmpc_plant_params_from(const qmpc_params* p, qmpc_plant_params* out) {
 static qmpc_status loop_instances_check(const qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, bool has_ctrl) {
   if (h->params.model != QMPC_MODEL_QUAT && h->params.model != QMPC_MODEL_CONVEX) return QMPC_BAD_ARGUMENT;
   if (h->params.model != QMPC_MODEL_QUAT || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
-  if (has_ctrl && (lp->warm_start != 0.0 || !h->sel.wform)) return QMPC_UNSUPPORTED;
+  // (controller records with the warm start: on a handle that opted in only, qmpc_set_loop_warm_records)
+  if (has_ctrl && ((lp->warm_start != 0.0 && !h->loop_warm_rec) || !h->sel.wform)) return QMPC_UNSUPPORTED;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
-  if (batch > 0 && plan_loop_instances(h->sel, batch, has_ctrl, lp->warm_start != 0.0, h->handoff_failed).family == QMPC_KERNEL_NONE)
+  if (batch > 0 && plan_loop_instances(h->sel, batch, has_ctrl, lp->warm_start != 0.0, QMPC_INSTANCES_WAVE, h->handoff_failed,
+                                       h->loop_warm_rec != 0).family == QMPC_KERNEL_NONE)
     return QMPC_UNSUPPORTED;
   return QMPC_OK;
 }
 
 // The buffers of a call with records, allocated before anything is launched or captured (a call with ticks = 0 stops after
 // this): the per-instance and plant blocks and, where the ticks' solve is the lane kernel with per-lane parameters
-// (QMPC_INSTANCES_AUTO), its workspace, sort scratch, parameter rows and hand-off records.  *lpp: the call's plan -- re-planned
-// without the hand-off where its records could not be allocated.
+// (QMPC_INSTANCES_AUTO), its workspace, sort scratch, parameter rows and hand-off records; for warm-started ticks with
+// controller records the trajectory buffer the solution travels through.  *lpp: the call's plan -- re-planned without the
+// hand-off where its records could not be allocated.
 static qmpc_status loop_instances_buffers(qmpc_handle* h, int32_t batch, bool has_ctrl, bool warm, qmpc_plan* lpp) {
   qmpc_status es = ensure_instance_buffers(h);
   if (es == QMPC_OK) es = ensure_plant_buffers(h);
   if (es != QMPC_OK) return es;
-  qmpc_plan p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed);
+  const bool wr = h->loop_warm_rec != 0;
+  qmpc_plan p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed, wr);
   if (has_ctrl && !p.fused && p.variant == 4) {
     es = ensure_lane_inst_buffers(h, false);
     if (es != QMPC_OK) return es;
-    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed);
+    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed, wr);
+  }
+  if (has_ctrl && warm && !p.fused) {      // (an opted-in handle: what loop_setup would allocate after a ticks = 0 return)
+    es = ensure_loop_buffers(h, true);
+    if (es != QMPC_OK) return es;
   }
   if (lpp) *lpp = p;
   return QMPC_OK;
@@ -1609,6 +1667,46 @@ static qmpc_status loop_inst_tick_solve(qmpc_handle* h, const qmpc_plan& p, int3
   return QMPC_OK;
 }
 
+// ... warm-started (lp->warm_start on a handle that opted in: qmpc_set_loop_warm_records).  p: the plan of THIS tick
+// (plan_loop_instances with `first`).  first: the cold first tick of the call -- the kernels above, under the lane plan without
+// cap and hand-off, leaving the solution in h->d_traj_u; later ticks: the warm-started
+// kernels of the plan start from it (a robot whose previous solve failed starts cold: check_prev) and leave theirs there.  The
+// lane form: the sort, qmpc_lane_inst_warm_kernel to the warm ticks' cap, the per-instance list kernel on what it leaves (its
+// records carry the rows' initial residuals).
+static qmpc_status loop_inst_warm_tick_solve(qmpc_handle* h, const qmpc_plan& p, int32_t batch, hipStream_t s, bool first) {
+  double* tu = h->d_traj_u;
+  if (p.variant == 4) {
+    const bool cap = p.iter_cap > 0;
+    const int* perm = h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr;
+    if (h->sel.lane_sort)
+      HIP_TRY(qmpc_lane_inst_sort_loop_launch((int)batch, s, h->d_in, p.order_prev ? h->d_info : nullptr, inst_status(h),
+                                              h->sel.lane_sort_idle, h->d_lane_scratch));
+    if (first)
+      HIP_TRY(qmpc_lane_inst_launch_only(h->lane_pslot, (int)batch, s, h->d_in, inst_dev(h), inst_status(h), h->d_forces, h->d_info,
+                                         h->d_lane_ws, h->d_lane_prm, h->lane_slots, perm, tu, nullptr, p.iter_cap,
+                                         cap ? h->d_handoff : nullptr, cap ? h->d_handoff + 64 : nullptr, cap ? h->d_hstate : nullptr,
+                                         h->hstate_cap, h->sel.lane_pair));
+    else
+      HIP_TRY(qmpc_lane_inst_warm_launch_only(h->lane_pslot, (int)batch, s, h->d_in, inst_dev(h), inst_status(h), h->d_forces, h->d_info,
+                                              h->d_lane_ws, h->d_lane_prm, h->lane_slots, perm, tu, tu, /*check_prev=*/1, p.iter_cap,
+                                              cap ? h->d_handoff : nullptr, cap ? h->d_handoff + 64 : nullptr, cap ? h->d_hstate : nullptr,
+                                              h->hstate_cap, h->sel.lane_pair));
+    if (cap)
+      HIP_TRY(qmpc_wform_inst_list_launch(p.handoff_variant, p.handoff_grid, p.lds, s, inst_dev(h), h->d_in, h->d_forces, h->d_info, tu,
+                                          nullptr, h->d_handoff + 64, h->d_handoff, p.gws ? h->d_gws : nullptr, h->d_hstate, h->hstate_cap));
+    h->last_kernel = p.family;
+    return QMPC_OK;
+  }
+  if (first)
+    HIP_TRY(qmpc_wform_inst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces, h->d_info, tu,
+                                         nullptr, p.gws ? h->d_gws : nullptr));
+  else
+    HIP_TRY(qmpc_wform_inst_warm_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), h->d_in, tu, h->d_forces, h->d_info,
+                                        tu, p.gws ? h->d_gws : nullptr, /*check_prev=*/1));
+  h->last_kernel = p.family;
+  return QMPC_OK;
+}
+
 // The device-buffer closed loop of every kind with records.  kind REC_PLAIN (qmpc_loop_run_instances_device): the call without
 // records is the plain loop.  REC_OUTCOME / REC_PUSH (qmpc_loop_run_outcomes_device / qmpc_loop_run_pushes_device): the same call
 // with the kernels of the kind's unit in place of the plain unit's; without records (both NULL) every robot's plant block carries
@@ -1632,6 +1730,10 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   if (es != QMPC_OK || ticks == 0) return es;      // ticks = 0: the buffers only (e.g. before the caller's stream capture)
   const qmpc_status ss = loop_setup(h, s, warm && !lpp.fused);
   if (ss != QMPC_OK) return ss;
+  // the cold first tick of a warm-started call with controller records has a plan of its own (the lane form: no cap, no hand-off)
+  const qmpc_plan lpp_first = (d_ctrl && warm && !lpp.fused) ? plan_loop_instances(h->sel, batch, true, true, h->inst_policy, h->handoff_failed,
+                                                                                 h->loop_warm_rec != 0, /*first=*/true)
+                                                             : lpp;
   const qmpc_loop_params LP = *lp;
   const auto& R = kRec[kind];
   // the records are expanded once per call: the controllers' blocks (or, for the persistent kernel without controller records,
@@ -1653,7 +1755,9 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   auto one_tick = [&](bool first) -> qmpc_status {
     HIP_TRY(R.front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch, op, d_outcomes));
     // with controller records the solve on the blocks expanded above, without them the plain loop's
-    const qmpc_status st = d_ctrl ? loop_inst_tick_solve(h, lpp, batch, s) : loop_tick_solve(h, batch, s, warm, first, false);
+    const qmpc_status st = !d_ctrl ? loop_tick_solve(h, batch, s, warm, first, false)
+                           : warm  ? loop_inst_warm_tick_solve(h, first ? lpp_first : lpp, batch, s, first)
+                                   : loop_inst_tick_solve(h, lpp, batch, s);
     if (st != QMPC_OK) return st;
     HIP_TRY(R.post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, h->d_loop_row, plant_dev(h),
                           (int)batch, op, d_outcomes, d_push, (int)per_robot));
@@ -1661,6 +1765,7 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   };
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
   if (d_ctrl && lpp.variant == 4) HIP_TRY(qmpc_lane_inst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
+  if (d_ctrl && warm && lpp.variant == 4) HIP_TRY(qmpc_lane_inst_warm_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   return replay_ticks(h, lpp, s, ticks, warm, one_tick);
 }
 

@@ -89,4 +89,9 @@ static inline int wform_list_slot(int var) { return var == 3 || var == 5 ? wform
 constexpr int kWformListInstSlots = 2;
 static inline int wform_list_inst_slot(int var) { return wform_list_slot(var); }
 
+// ---- qmpc_wform_inst_warm.hip -------------------------------------------------------------------------------------------
+// qmpc_solve_w_inst_warm_kernel<WVAR> (the warm-started ticks of a closed loop with controller records): 3 5 6
+constexpr int kWformInstWarmSlots = 3;
+static inline int wform_inst_warm_slot(int var) { return wform_index(var); }
+
 }  // namespace qmpc

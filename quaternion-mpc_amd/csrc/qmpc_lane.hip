@@ -33,8 +33,10 @@
 // strategy: max-ilp costs that kernel 5-8 %, profiles/HISTORY_r06.md).
 // QL_UNIT 3 (qmpc_lane_inst.hip includes this file): the converged mode's kernel with per-lane robot and cost parameters
 // (qmpc_solve_instances* under QMPC_INSTANCES_AUTO) -- what it shares with the two units above is the text up to the kernels.
-#if !defined(QL_UNIT) || (QL_UNIT != 1 && QL_UNIT != 2 && QL_UNIT != 3)
-#error "QL_UNIT must be 1 (the converged mode's unit), 2 (the reference mode's unit) or 3 (per-lane parameters)"
+// QL_UNIT 4 (qmpc_lane_inst_warm.hip includes this file): that kernel warm-started, the later ticks of a closed loop with
+// controller records under lp->warm_start.
+#if !defined(QL_UNIT) || (QL_UNIT != 1 && QL_UNIT != 2 && QL_UNIT != 3 && QL_UNIT != 4)
+#error "QL_UNIT must be 1 (the converged mode's unit), 2 (the reference mode's unit), 3 (per-lane parameters) or 4 (... warm-started)"
 #endif
 namespace qmpc {
 namespace lane {

@@ -10,18 +10,7 @@
 namespace qmpc {
 namespace lane {
 
-struct InstArgs {
-  PassArgs a;
-  unsigned pr_lo, pr_hi;     // this wave's parameter block
-};
-__device__ __forceinline__ QL_GLOBAL_AS const double* inst_prm(const InstArgs& a) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane(a.pr_lo), hi = __builtin_amdgcn_readfirstlane(a.pr_hi);
-  return reinterpret_cast<QL_GLOBAL_AS const double*>(((unsigned long long)hi << 32) | lo);
-}
-// U: the handle's block (scalar loads); P: the passes' parameter source
-#define QL_INST_PARAMS(a)                                                         \
-  const DevParams& U = ql_params[__builtin_amdgcn_readfirstlane((a).a.pslot)];    \
-  const LaneParams P(U, inst_prm(a), 8u * kLaneWave, (a).a.lane8)
+#include "qmpc_lane_inst_calls.inc"
 
 // pi: the instance's expanded block (qmpc_expand_instances_kernel); its instance fields become the lane's rows first
 __device__ __noinline__ void call_setup_inst(InstArgs a, unsigned long long rec, unsigned long long pi, QL_PRIV_AS LaneK<4>* Kp,
@@ -36,61 +25,6 @@ __device__ __noinline__ void call_setup_inst(InstArgs a, unsigned long long rec,
   priv_store(Kp, K);
   priv_store(sp, st);
 }
-template <bool PAIR>
-__device__ __noinline__ void call_A_inst(InstArgs a, QL_PRIV_AS const LaneK<4>* Kp, QL_PRIV_AS LaneState* sp) {
-  QL_INST_PARAMS(a);
-  const Ctx c = pass_ctx<4>(a.a);
-  const WsOff O = make_wsoff<4>(U.N);
-  LaneK<4> K;
-  priv_load(K, Kp);
-  LaneState st;
-  priv_load(st, (QL_PRIV_AS const LaneState*)sp);
-  st.it += 1;
-  pass_A<4, false, MD_QUAT, PAIR>(P, c, O, K, st, st.it == 1, (FootPtr)Kp->foot);
-  priv_store(sp, st);
-}
-template <bool PAIR>
-__device__ __noinline__ bool call_B_inst(InstArgs a, QL_PRIV_AS const LaneK<4>* Kp, QL_PRIV_AS LaneState* sp) {
-  QL_INST_PARAMS(a);
-  const Ctx c = pass_ctx<4>(a.a);
-  const WsOff O = make_wsoff<4>(U.N);
-  LaneK<4> K;
-  priv_load(K, Kp);
-  LaneState st;
-  priv_load(st, (QL_PRIV_AS const LaneState*)sp);
-  const bool ok = pass_B<4, false, MD_QUAT, false, PAIR>(P, c, O, K, st, (FootPtr)Kp->foot);
-#if defined(QL_PROFILE)
-  priv_store(sp, st);
-#endif
-  return ok;
-}
-template <bool PAIR>
-__device__ __noinline__ void call_C_inst(InstArgs a, QL_PRIV_AS const LaneK<4>* Kp, QL_PRIV_AS LaneState* sp) {
-  QL_INST_PARAMS(a);
-  const Ctx c = pass_ctx<4>(a.a);
-  const WsOff O = make_wsoff<4>(U.N);
-  LaneK<4> K;
-  priv_load(K, Kp);
-  LaneState st;
-  priv_load(st, (QL_PRIV_AS const LaneState*)sp);
-  pass_C<4, false, MD_QUAT, PAIR>(P, c, O, K, st, (FootPtr)Kp->foot);
-  if (!st.bad_step) st.iters = st.it;
-  priv_store(sp, st);
-}
-__device__ __noinline__ void call_finish_inst(InstArgs a, QL_PRIV_AS const LaneK<4>* Kp, QL_PRIV_AS const LaneState* sp,
-                                              unsigned long long forces, unsigned long long info, unsigned long long traj_u,
-                                              unsigned long long traj_x) {
-  QL_INST_PARAMS(a);
-  const Ctx c = pass_ctx<4>(a.a);
-  const WsOff O = make_wsoff<4>(U.N);
-  LaneK<4> K;
-  priv_load(K, Kp);
-  LaneState st;
-  priv_load(st, sp);
-  lane_finish<4, MD_QUAT>(P, c, O, K, st, reinterpret_cast<double*>(forces), reinterpret_cast<qmpc_info*>(info),
-                          reinterpret_cast<double*>(traj_u), reinterpret_cast<double*>(traj_x));
-}
-
 // qmpc_lane_kernel<4, MD_QUAT>'s cold launch with Pi[b] / pstatus[b] (the expanded block and the verdict of instance b) and prm,
 // the parameter blocks of the resident wavefronts (LPR_ROWS rows of 64 lanes each).  Same persistent wavefronts, same sort
 // (perm maps a position to b: the parameters are indexed by b), same 32 / 64 lanes and lane pairs, same cap and hand-off records.
@@ -137,7 +71,7 @@ __global__ __launch_bounds__(kLaneWave) void qmpc_lane_inst_kernel(int pslot, co
     while (__any(active)) {
       if (active) {
         // one interior-point iteration: the control flow of qmpc_lane_kernel's cold rounds
-        if (pairm) call_A_inst<true>(a, Kp, sp); else call_A_inst<false>(a, Kp, sp);
+        if (pairm) call_A_inst<false, true>(a, Kp, sp); else call_A_inst<false, false>(a, Kp, sp);
         const double resid = st.rho * st.rcmax;
         if (st.mu <= P.mu_final && resid <= P.tol_feas && st.last_step <= P.tol_step) { st.status = QMPC_OK; active = false; }
         else if (st.it > itmax) { st.status = QMPC_MAX_ITER; active = false; }
@@ -148,10 +82,10 @@ __global__ __launch_bounds__(kLaneWave) void qmpc_lane_inst_kernel(int pslot, co
           else if (st.it > 1 && amin < 0.2) sg = fmax(sg, 0.8);
           else if (st.it > 1 && amin < 0.5) sg = fmax(sg, 0.5);
           st.target = sg * st.mu;
-          const bool okB = pairm ? call_B_inst<true>(a, Kp, sp) : call_B_inst<false>(a, Kp, sp);
+          const bool okB = pairm ? call_B_inst<false, true>(a, Kp, sp) : call_B_inst<false, false>(a, Kp, sp);
           if (!okB) { st.status = QMPC_NOT_PD; active = false; }
           else {
-            if (pairm) call_C_inst<true>(a, Kp, sp); else call_C_inst<false>(a, Kp, sp);
+            if (pairm) call_C_inst<false, true>(a, Kp, sp); else call_C_inst<false, false>(a, Kp, sp);
             if (st.bad_step) { st.status = QMPC_NOT_PD; active = false; }
           }
         }

@@ -106,8 +106,8 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
 // ---- persistent form ---------------------------------------------------------------------------------------------------
 // P is bound to Pi[b] as in qmpc_solve_w_inst_kernel (the address depends on blockIdx.x only, the reads stay scalar loads), the
 // post step reads plants[b].  A frozen robot's wave writes its status and zero trace rows and leaves.  The warm start works as
-// in the plain kernel (warm_t; the entry point refuses it with controller records, whose per-tick form has no warm-started
-// kernel).
+// in the plain kernel (warm_t); with controller records the entry point accepts it on a handle that opted in
+// (qmpc_set_loop_warm_records; the per-tick form's kernels: qmpc_wform_inst_warm.hip, qmpc_lane_inst_warm.hip).
 // EXT >= 1: lane 0 holds the robot's outcome record from the first tick to the last and stores it once.  `halt` is lane 0's
 // verdict after the outcome step, made uniform with a readfirstlane (all lanes are active there): the wave zero-fills the trace
 // rows left and returns, which frees its SIMD slot for the next robot.  A robot halted by an earlier call leaves like a frozen

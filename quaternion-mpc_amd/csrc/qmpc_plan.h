@@ -317,8 +317,8 @@ static inline qmpc_plan plan_instances(const qmpc_select& s, int batch, int poli
 //               on a wrench-form variant: that very variant (qmpc_loop_rec_fused_kernel<3|5|6>), fused = true;
 //   per tick    otherwise: with controller records the plan of qmpc_solve_instances* (plan_instances), without them the
 //               plain loop's tick (lane kernel and hand-off included); fused = false.
-// NONE: not QuatMpc's problem in the converged mode, controller records with the warm start (the per-tick form has no
-// warm-started per-instance kernel) or with no wrench-form kernel for the batch (QMPC_WFORM=0, ...).
+// NONE: not QuatMpc's problem in the converged mode, controller records with the warm start (a handle opts in to those:
+// the last overload below) or with no wrench-form kernel for the batch (QMPC_WFORM=0, ...).
 static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, bool has_ctrl, bool warm, bool handoff_failed = false) {
   if (s.model != QMPC_MODEL_QUAT || s.mode != QMPC_MODE_CONVERGED) return qmpc_plan();
   if (has_ctrl && (warm || !s.wform)) return qmpc_plan();
@@ -344,6 +344,38 @@ static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, boo
   qmpc_select l = s;
   l.lane_min_loop_cold = 0;      // the switch-over is this call's own: the plain tick's plan only names the lane kernel's fields
   qmpc_plan p = plan(l, batch, QMPC_CALL_LOOP_TICK, true, handoff_failed);
+  if (p.variant != 4) return w;
+  p.fused = false;
+  return p;
+}
+
+// ... on a handle that may have opted in to warm-started loops with controller records (qmpc_set_loop_warm_records;
+// `warm_records`).  Off, or a call without controller records or without lp->warm_start: the overload above.  On, with both:
+//   persistent  where the warm-started plain loop of this batch takes its persistent kernel on a wrench-form variant (4096
+//               robots, or QMPC_LOOP_FUSED): that plan -- the rule of a call with plant records only;
+//   per tick    otherwise the plan of qmpc_solve_instances* (qmpc_solve_w_inst_warm_kernel on its variant), fused = false;
+//               under QMPC_INSTANCES_AUTO on a handle with a slot of the lane kernel's parameter table, from the larger of the
+//               two switch-overs the tick combines on (lane_min_inst and the warm-started loop's, lane_min_warm: 18432 robots
+//               with the defaults, 20480 at N = 13 ... 22), the lane fields of the plain loop's warm tick for this batch
+//               (qmpc_lane_inst_warm_kernel to lane_cap_warm, the per-instance list kernel on what it leaves, the batch ordered
+//               by the previous records, no upload inside the tick).  QMPC_VARIANT=4: the pure lane kernel wherever the
+//               per-tick form runs.
+// `first`: the cold first tick of the call instead of the tick it repeats -- the same wave variant, or the lane kernel without
+// cap and hand-off (the plain loop's QMPC_CALL_WARM_LOOP_FIRST).
+// NONE: not QuatMpc's problem in the converged mode, or no wrench-form kernel for the batch.
+static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, bool has_ctrl, bool warm, int policy, bool handoff_failed,
+                                            bool warm_records, bool first = false) {
+  if (!warm_records || !has_ctrl || !warm) return plan_loop_instances(s, batch, has_ctrl, warm, policy, handoff_failed);
+  if (s.model != QMPC_MODEL_QUAT || s.mode != QMPC_MODE_CONVERGED || !s.wform) return qmpc_plan();
+  const qmpc_plan f = plan(s, batch, QMPC_CALL_WARM_LOOP, true, handoff_failed);
+  if (f.fused && (f.variant == 3 || f.variant == 5 || f.variant == 6)) return f;
+  qmpc_plan w = plan_instances(s, batch);
+  w.fused = false;
+  if (policy != QMPC_INSTANCES_AUTO || w.family == QMPC_KERNEL_NONE || !s.lane_slot) return w;
+  if (s.variant != 4 && batch < (s.lane_min_inst > s.lane_min_warm ? s.lane_min_inst : s.lane_min_warm)) return w;
+  qmpc_select l = s;
+  l.lane_min_warm = 0;      // the switch-over is this call's own: the plain tick's plan only names the lane kernel's fields
+  qmpc_plan p = plan(l, batch, first ? QMPC_CALL_WARM_LOOP_FIRST : QMPC_CALL_WARM_LOOP_TICK, true, handoff_failed);
   if (p.variant != 4) return w;
   p.fused = false;
   return p;

@@ -18,7 +18,13 @@ per-robot calls include their expansion kernels.
 --pushes [--per-robot K]: instead, same-job pairs of qmpc_loop_run_outcomes_device against qmpc_loop_run_pushes_device whose K
     windows per robot never act (they lie beyond the run, with a wrench that is not zero): what reading the windows in every tick
     costs, with plant records and with controller + plant records, on the walking fleet.  The two calls compute the same bytes.
---records uniform|random: every robot carries the handle's values (default), or random_go1_variants / random_go1_plants."""
+--records uniform|random: every robot carries the handle's values (default), or random_go1_variants / random_go1_plants.
+--warm-records [--mu0 1e-6]: instead, the warm-started loop with controller + plant records (qmpc_set_loop_warm_records) as same-job
+    pairs: the plain loop and the call with records, each cold-started (a handle on the default barrier parameter) and
+    warm-started (lp.warm_start = 1 on a handle with ipm_mu0 = --mu0, the setting the plain warm loop's figures were taken
+    with), alternating on the same states.  Per size: robot-ticks/s of the four calls, warm / cold of the call with records, and
+    that ratio against the plain loop's own warm / cold -- with uniform records the plain warm loop is the ceiling.  --policy
+    both adds the calls with records under AUTO (the lane form from its switch-over on)."""
 import argparse
 import importlib.util
 import json
@@ -164,6 +170,103 @@ def pushes(pkg, lib, torch, N, B, a):
     return row
 
 
+def warm_records(pkg, lib, torch, N, B, a):
+    """cold against warm, the plain loop and the call with controller + plant records (see the module docstring)"""
+    lp_c = pkg.default_loop_params(lib)
+    lp_w = pkg.default_loop_params(lib)
+    lp_w.warm_start = 1.0
+    p_c = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+    p_w = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+    p_w.ipm_mu0 = a.mu0
+    T = a.ticks
+    rng = np.random.default_rng(5)
+    cmds = np.zeros((B, 7))
+    cmds[:, 0] = rng.uniform(-0.4, 0.4, B); cmds[:, 1] = rng.uniform(-0.15, 0.15, B)
+    cmds[:, 2] = rng.uniform(0.26, 0.32, B); cmds[:, 5] = rng.uniform(-0.4, 0.4, B)
+    cmds[:, 6] = (rng.random(B) < 0.85).astype(float)
+    stand = cmds.copy(); stand[:, 6] = 0.0
+    st = pkg.loop_states(stand, lp_c, height=0.3, yaw=rng.uniform(-3, 3, B), lib=lib)
+    policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
+    handles = {}
+    for kind, p in (("cold", p_c), ("warm", p_w)):
+        h = pkg.Solver(p, B, device=0, lib=lib)
+        if kind == "warm":
+            h.set_loop_warm_records(True)
+        for pol in policies:      # (the buffers of every policy asked for: allocated before anything is timed)
+            h.set_instances_policy(pol)
+            h.prepare(B)
+        h.prepare_instances()
+        handles[kind] = h
+    st = handles["cold"].loop_run(st, 6, lp_c)
+    st["movement_mode"] = cmds[:, 6]
+    if a.records == "random":
+        ctrl = pkg.random_go1_variants(B, seed=12, base=p_c)
+        ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
+        plant = pkg.random_go1_plants(B, seed=11, base=p_c, payload=(-1.0, 3.0), force=(0.0, 10.0))
+    else:
+        ctrl, plant = pkg.instance_params(p_c, B), pkg.plant_params(p_c, B)
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).cuda()      # noqa: E731
+    d_st0, d_ctrl, d_plant = dev(st), dev(ctrl), dev(plant)
+    d_st = d_st0.clone()
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    torch.cuda.synchronize()
+
+    def rec_call(kind, pol):
+        h = handles[kind]
+        h.set_instances_policy(pol)
+        h.loop_run_instances_device(B, d_st.data_ptr(), T, lp_w if kind == "warm" else lp_c, d_ctrl=d_ctrl.data_ptr(), d_plant=d_plant.data_ptr(),
+                                    stream=sp)
+
+    calls, forms = {}, {}
+    for kind, lp in (("cold", lp_c), ("warm", lp_w)):
+        calls["plain_" + kind] = lambda kind=kind, lp=lp: handles[kind].loop_run_device(B, d_st.data_ptr(), T, lp, stream=sp)
+        for pol in policies:
+            calls[f"records_{pol}_{kind}"] = lambda kind=kind, pol=pol: rec_call(kind, pol)
+            handles[kind].set_instances_policy(pol)
+            forms[f"records_{pol}_{kind}"] = handles[kind].loop_instances_plan(B, True, kind == "warm")
+    times, its = {k: [] for k in calls}, {}
+    for r in range(a.warmup + a.reps):
+        for k, fn in calls.items():
+            with torch.cuda.stream(stream):
+                d_st.copy_(d_st0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            if r >= a.warmup:
+                times[k].append(e0.elapsed_time(e1))
+            x = d_st.cpu().numpy().view(pkg.LOOP_STATE_DTYPE).reshape(B)
+            its[k] = (float(x["iterations"].mean()), int((x["status"] != 0).sum()))
+    for h in handles.values():
+        h.close()
+    ms = {k: float(np.median(v)) for k, v in times.items()}
+    row = {"N": N, "B": B, "ticks": T, "records": a.records, "mu0_warm": a.mu0}
+    for k in calls:
+        row[k + "_ms"] = ms[k]
+        row[k + "_Mrobot_ticks_s"] = B * T / ms[k] / 1e3
+        row[k + "_form"] = forms.get(k)
+        row[k + "_last_tick_iterations"] = its[k][0]
+    row["plain_warm_over_cold"] = ms["plain_cold"] / ms["plain_warm"]
+    print(f"N={N:2d} B={B:6d}  plain loop cold {row['plain_cold_Mrobot_ticks_s']:7.3f} M/s   warm {row['plain_warm_Mrobot_ticks_s']:7.3f} M/s   "
+          f"warm / cold x{row['plain_warm_over_cold']:.3f}   (ms min/median/max cold {min(times['plain_cold']):.3f} / {ms['plain_cold']:.3f} / "
+          f"{max(times['plain_cold']):.3f}, warm {min(times['plain_warm']):.3f} / {ms['plain_warm']:.3f} / {max(times['plain_warm']):.3f}; last tick's "
+          f"mean iterations {its['plain_cold'][0]:.2f} / {its['plain_warm'][0]:.2f})", flush=True)
+    for pol in policies:
+        c, w = f"records_{pol}_cold", f"records_{pol}_warm"
+        row[f"records_{pol}_warm_over_cold"] = ms[c] / ms[w]
+        row[f"records_{pol}_gain_over_plain_gain"] = row[f"records_{pol}_warm_over_cold"] / row["plain_warm_over_cold"]
+        row[f"records_{pol}_warm_over_plain_warm"] = ms["plain_warm"] / ms[w]
+        print(f"            {a.records} ctrl+plant records, {pol}: cold {row[c + '_Mrobot_ticks_s']:7.3f} M/s {forms[c]}   warm "
+              f"{row[w + '_Mrobot_ticks_s']:7.3f} M/s {forms[w]}   warm / cold x{row[f'records_{pol}_warm_over_cold']:.3f} "
+              f"({row[f'records_{pol}_gain_over_plain_gain']:.3f} of the plain loop's ratio; {row[f'records_{pol}_warm_over_plain_warm']:.3f} of the "
+              f"plain warm loop)   ms min/median/max cold {min(times[c]):.3f} / {ms[c]:.3f} / {max(times[c]):.3f}, warm {min(times[w]):.3f} / "
+              f"{ms[w]:.3f} / {max(times[w]):.3f}; last tick's mean iterations {its[c][0]:.2f} / {its[w][0]:.2f}, robots not OK {its[c][1]} / {its[w][1]}",
+              flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -177,6 +280,8 @@ def main():
     ap.add_argument("--per-robot", type=int, default=1)
     ap.add_argument("--policy", choices=("wave", "auto", "both"), default="wave")
     ap.add_argument("--records", choices=("uniform", "random"), default="uniform")
+    ap.add_argument("--warm-records", action="store_true")
+    ap.add_argument("--mu0", type=float, default=1e-6)
     a = ap.parse_args()
     import torch
 
@@ -190,6 +295,9 @@ def main():
         policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
         if a.pushes:
             rows.append(pushes(pkg, lib, torch, N, B, a))
+            continue
+        if a.warm_records:
+            rows.append(warm_records(pkg, lib, torch, N, B, a))
             continue
         if a.stop:
             if a.policy == "wave":      # (as before the policy existed: plant records only)
