@@ -305,8 +305,13 @@ enum qmpc_query_what {
                                            qmpc_kernel_family of its solve.  0: the call is refused.  Bits 32 and 33 together
                                            answer under the handle's qmpc_set_loop_warm_records setting (default: refused) */
   QMPC_QUERY_INSTANCES_POLICY     = 10, /* the handle's policy for qmpc_solve_instances*, a qmpc_instances_policy value */
-  QMPC_QUERY_LOOP_WARM_RECORDS    = 11  /* 1: the closed loops with controller records accept lp->warm_start on this handle
+  QMPC_QUERY_LOOP_WARM_RECORDS    = 11, /* 1: the closed loops with controller records accept lp->warm_start on this handle
                                            (qmpc_set_loop_warm_records); 0 (default): they refuse it */
+  QMPC_QUERY_KERNEL_FOR_CONVEX_INSTANCES = 12, /* arg = batch: the qmpc_kernel_family qmpc_convex_solve_instances* launches
+                                           for that size (QMPC_KERNEL_NONE, on a QuatMpc or 8-point handle too: the call is
+                                           refused).  QMPC_QUERY_KERNEL_FOR_INSTANCES keeps answering NONE on a ConvexMpc handle */
+  QMPC_QUERY_CONVEX_RECORDS       = 13  /* 1: the closed loops with per-robot records accept this ConvexMpc handle
+                                           (qmpc_set_convex_records); 0 (default): they refuse it */
 };
 enum qmpc_kernel_family {
   QMPC_KERNEL_NONE         = 0,
@@ -351,7 +356,8 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
  * qmpc_prepare_instances and qmpc_prepare allocate them, under WAVE they allocate what they always did.  A handle that
  * refuses the call under WAVE refuses it under AUTO.
  *
- * Not covered: the reference mode, ConvexMpc, the 8-point model, warm starts.  The closed loop has its own entry points
+ * Not covered: the reference mode, the 8-point model, warm starts.  ConvexMpc's problem has entry points of its own with
+ * the same records, qmpc_convex_solve_instances* below.  The closed loop has its own entry points
  * with these records, qmpc_loop_run_instances* below; with controller records it keeps the wave form under either policy.
  *
  * The handle's per-instance buffers (the records and one expanded parameter block per instance, about 760 B x max_batch)
@@ -391,6 +397,37 @@ typedef enum qmpc_instances_policy {
                                 qmpc_solve_instances* and in the closed loops' ticks with controller records */
 } qmpc_instances_policy;
 qmpc_status qmpc_set_instances_policy(qmpc_handle* h, int32_t policy);
+
+/* ---- per-instance robot and cost parameters for ConvexMpc's problem (ConvexMpc handle, converged mode) ------------------
+ * qmpc_solve_instances* for the sibling controller: qmpc_convex_input records, world-frame forces, and the same 304-byte
+ * qmpc_instance_params -- e.g. one fleet with its payload, inertia and friction spread, solved under both controllers.
+ * ConvexMpc reads mass, inertia, mu, fz_max, q_weights[0..11] (its state has 12 entries) and r_weights from a record;
+ * q_weights[12] and w are validated like the other fields and otherwise unused.  The handle's own values of those fields
+ * are ignored in this call.  A record is invalid by the rule above (QMPC_BAD_PARAMS for that instance: zero forces, zero
+ * trajectory rows, 0 iterations; its neighbours are unaffected).
+ *
+ * Kernel: qmpc_solve_cw_inst_kernel, the wrench-form ConvexMpc kernel with its parameters read per workgroup, on the
+ * variant (everything in LDS / gains / gains and slack arrays in the workspace) a plain qmpc_convex_solve of the size takes
+ * on the wrench form; results are then bit-identical to qmpc_convex_solve on a handle carrying the same values.  Where the
+ * plain solve takes the round-1 kernel or the lane kernel (there is no per-instance form of either for this problem) the
+ * call stays on a wrench-form variant and agrees with the plain solve to the rounding between ConvexMpc's kernel families
+ * (status words equal, forces within 1e-7 N).  qmpc_query(QMPC_QUERY_KERNEL_FOR_CONVEX_INSTANCES) names the family for a
+ * batch size, QMPC_QUERY_LAST_KERNEL the one the last call took.  qmpc_set_instances_policy does not change this call:
+ * there is no lane-per-instance form with per-lane parameters for ConvexMpc's problem.
+ *
+ * Call-level: QMPC_UNSUPPORTED on a QuatMpc or 8-point handle, a reference-mode handle, or a handle whose knobs leave no
+ * wrench-form kernel (QMPC_WFORM=0); QMPC_BATCH_TOO_LARGE above max_batch; QMPC_BAD_ARGUMENT for null pointers.  The
+ * buffers are those of qmpc_prepare_instances (which a ConvexMpc handle in the converged mode accepts too).
+ *
+ * Host buffers: in [batch], iparams [batch], forces_world [batch][12]; info, traj_u ([batch][N][12]) and traj_x
+ * ([batch][N+1][12]) may be NULL.  Synchronous. */
+qmpc_status qmpc_convex_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_convex_input* in,
+                                        const qmpc_instance_params* iparams, double* forces_world, qmpc_info* info,
+                                        double* traj_u, double* traj_x);
+/* Device buffers, stream-ordered (NULL stream = the handle's), nothing synchronised; d_info may be NULL. */
+qmpc_status qmpc_convex_solve_instances_device(qmpc_handle* h, int32_t batch, const qmpc_convex_input* d_in,
+                                               const qmpc_instance_params* d_iparams, double* d_forces_world,
+                                               qmpc_info* d_info, void* stream);
 
 /* Multi-GPU: the single collective of the path.  All-gathers `count` doubles per rank (e.g. the
  * [B/G][12] force block, or forces + qmpc_info records laid out in one buffer) from every rank's `d_local` into
@@ -624,7 +661,8 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
  * unaffected, bit for bit.
  *
  * Call level: QMPC_BAD_ARGUMENT for null pointers and for an 8-point handle (as qmpc_loop_run); QMPC_UNSUPPORTED, when
- * ctrl or plant is non-NULL, for a ConvexMpc or reference-mode handle; with ctrl non-NULL also for lp->warm_start != 0
+ * ctrl or plant is non-NULL, for a reference-mode handle and for a ConvexMpc handle that has not opted in
+ * (qmpc_set_convex_records below; off by default); with ctrl non-NULL also for lp->warm_start != 0
  * unless the handle opted in (qmpc_set_loop_warm_records below; off by default) and for a handle whose knobs leave no
  * wrench-form kernel (QMPC_WFORM=0); QMPC_BATCH_TOO_LARGE above max_batch.  With
  * plant only, everything the plain loop supports works, the warm start included, and the per-tick form keeps the plain
@@ -689,6 +727,30 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
  * under it. */
 qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on);
 
+/* Opt in to the closed loops with per-robot records on a ConvexMpc handle: on = 1 (0, the default, restores the refusal).
+ * qmpc_loop_run_instances*, qmpc_loop_run_outcomes* and qmpc_loop_run_pushes* then accept a ConvexMpc handle in the converged
+ * mode -- with ctrl and / or plant, with outcome records and stop_when_down, with push windows -- with the semantics, buffers
+ * and ticks = 0 behaviour they have on a QuatMpc handle: the same fleet, plants, pushes and outcome records under either
+ * controller.  A controller record is read as by qmpc_convex_solve_instances*; the plant step is the one of the QuatMpc calls,
+ * on the world-frame forces of ConvexMpc rotated into the body (optimized_input = R' u).  A handle that never opts in plans,
+ * refuses, computes and allocates as before; the setting does nothing on a handle of another model.
+ *
+ * Launch (QMPC_QUERY_LOOP_INSTANCES_PLAN answers under the setting): the persistent kernel where the plain ConvexMpc loop of
+ * the batch takes its own on a wrench-form variant (2048 robots, 4096 with lp->warm_start, or QMPC_LOOP_FUSED); otherwise per
+ * tick -- the front kernel, qmpc_solve_cw_inst_kernel with ctrl or the plain ConvexMpc tick (its lane kernel included) without,
+ * the post kernel.  With records equal to the handle's values both forms give the bytes of qmpc_loop_run* on the same handle
+ * (states, force and contact traces) wherever that loop solves on the same wrench-form variant, and the two forms agree with
+ * each other bit for bit on any records.  Under QMPC_INSTANCES_AUTO the ticks with ctrl stay on the wave kernels at every
+ * size: there is no lane-per-instance form with per-lane parameters for ConvexMpc's problem.
+ *
+ * Still QMPC_UNSUPPORTED with the setting on: the reference mode; ctrl together with lp->warm_start, whatever
+ * qmpc_set_loop_warm_records says (plant records alone follow the plain warm-started loop); a batch with no wrench-form kernel
+ * under the handle's knobs with ctrl; a handle whose knot spacing is not the controller period of 5 ms (as qmpc_loop_run*).
+ * Memory: the calls without outcome records run the outcome step on a scratch of 128 B x max_batch the handle allocates with
+ * their other buffers.  QMPC_BAD_ARGUMENT for a null handle or another value; qmpc_query(QMPC_QUERY_CONVEX_RECORDS) returns
+ * the setting. */
+qmpc_status qmpc_set_convex_records(qmpc_handle* h, int32_t on);
+
 /* ---- per-robot outcome records of the closed loop (robustness sweeps) -------------------------------------------------
  * The other half of the question above: did robot i stay up, how far did it tilt, how well did it track its command, how
  * often was its solve rejected?  qmpc_loop_run_outcomes* is qmpc_loop_run_instances* -- the same robots, launch forms
@@ -709,13 +771,16 @@ qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on);
  * A robot whose record comes in with down_tick >= 0 is halted from the first tick of the call.
  * The robot of an invalid controller or plant record (QMPC_BAD_PARAMS) leaves its outcome record untouched.
  *
- * Scope and refusals: those of qmpc_loop_run_instances* with records -- a QuatMpc handle in the converged mode;
- * QMPC_UNSUPPORTED for a ConvexMpc or reference-mode handle, QMPC_BAD_ARGUMENT for an 8-point handle, with ctrl also
+ * Scope and refusals: those of qmpc_loop_run_instances* with records -- a QuatMpc handle in the converged mode, or a
+ * ConvexMpc handle in the converged mode that opted in (qmpc_set_convex_records);
+ * QMPC_UNSUPPORTED for a reference-mode handle or a ConvexMpc handle that has not opted in (qmpc_set_convex_records),
+ * QMPC_BAD_ARGUMENT for an 8-point handle, with ctrl also
  * QMPC_UNSUPPORTED for lp->warm_start != 0 (unless the handle opted in: qmpc_set_loop_warm_records) or a handle without a
  * wrench-form kernel -- and QMPC_BAD_ARGUMENT for a NULL op
  * or outcomes.  ctrl and plant may both be NULL: plain robots on the handle's parameters (still a QuatMpc converged
- * handle).  Buffers: those of qmpc_loop_run_instances*; the host-buffer call adds a staging buffer for the records (128 B x
- * max_batch) on its first use.  No other call allocates it.  Under QMPC_INSTANCES_AUTO the ticks with ctrl take the lane
+ * handle, or an opted-in ConvexMpc one).  Buffers: those of qmpc_loop_run_instances*; the host-buffer call adds a staging
+ * buffer for the records (128 B x max_batch) on its first use.  No other call allocates it on a QuatMpc handle; an opted-in
+ * ConvexMpc handle allocates it with the buffers of any call with records (qmpc_set_convex_records).  Under QMPC_INSTANCES_AUTO the ticks with ctrl take the lane
  * form of qmpc_loop_run_instances* from the same switch-over on; a halted robot then sorts into the class that will not
  * solve, so a fleet of which many are down runs in fewer wavefronts. */
 typedef struct qmpc_outcome_params {   /* 4 doubles */

@@ -358,6 +358,10 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_solve_instances.restype = i32
     lib.qmpc_solve_instances_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.qmpc_solve_instances_device.restype = i32
+    lib.qmpc_convex_solve_instances.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.qmpc_convex_solve_instances.restype = i32
+    lib.qmpc_convex_solve_instances_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    lib.qmpc_convex_solve_instances_device.restype = i32
     lib.qmpc_prepare_instances.argtypes = [vp]
     lib.qmpc_plant_params_from.argtypes = [C.POINTER(Params), vp]
     lib.qmpc_plant_params_from.restype = None
@@ -383,6 +387,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_set_loop_warm_records.argtypes = [vp, i32]
     lib.qmpc_set_loop_warm_records.restype = i32
+    lib.qmpc_set_convex_records.argtypes = [vp, i32]
+    lib.qmpc_set_convex_records.restype = i32
     lib.qmpc_gather.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.qmpc_gather.restype = i32
     lib.qmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -537,6 +543,9 @@ EXPORTED_SYMBOLS = (
     "qmpc_sizeof_instance_params",
     "qmpc_solve_instances",
     "qmpc_solve_instances_device",
+    "qmpc_convex_solve_instances",
+    "qmpc_convex_solve_instances_device",
+    "qmpc_set_convex_records",
     "qmpc_prepare_instances",
     "qmpc_plant_params_from",
     "qmpc_sizeof_plant_params",
@@ -559,6 +568,8 @@ QUERY_HANDOFF_ACTIVE, QUERY_HANDOFF_ALLOC_FAILED, QUERY_KERNEL_FOR_BATCH, QUERY_
     QUERY_DEVICE_BYTES, QUERY_ZERO_COPY, QUERY_KERNEL_FOR_INSTANCES, QUERY_LOOP_INSTANCES_PLAN = 1, 2, 3, 4, 5, 6, 7, 8, 9
 QUERY_INSTANCES_POLICY = 10
 QUERY_LOOP_WARM_RECORDS = 11
+QUERY_KERNEL_FOR_CONVEX_INSTANCES = 12
+QUERY_CONVEX_RECORDS = 13
 # enum qmpc_instances_policy
 INSTANCES_WAVE, INSTANCES_AUTO = 0, 1
 INSTANCES_POLICY = {"wave": INSTANCES_WAVE, "auto": INSTANCES_AUTO}
@@ -1007,6 +1018,17 @@ class Solver:
     def loop_warm_records(self) -> bool:
         return bool(self.query(QUERY_LOOP_WARM_RECORDS))
 
+    def set_convex_records(self, on: bool = True):
+        """Let loop_run_instances* / loop_run_outcomes* / loop_run_pushes* accept this ConvexMpc handle (converged mode) with
+        per-robot controller and plant records, outcome records and push windows (qmpc_set_convex_records; default off: they
+        refuse it).  Holds until it is changed; does nothing on a handle of another model."""
+        st = self.lib.qmpc_set_convex_records(self._h, int(on))
+        if st != OK:
+            raise QmpcError(st, "qmpc_set_convex_records")
+
+    def convex_records(self) -> bool:
+        return bool(self.query(QUERY_CONVEX_RECORDS))
+
     def instances_policy(self) -> str:
         return {v: k for k, v in INSTANCES_POLICY.items()}[self.query(QUERY_INSTANCES_POLICY)]
 
@@ -1093,6 +1115,36 @@ class Solver:
                                                C.c_void_p(stream) if stream else None)
         if st != OK:
             raise QmpcError(st, "qmpc_convex_solve_device")
+
+    def convex_solve_instances(self, inputs: np.ndarray, iparams: np.ndarray, want_traj: bool = False):
+        """qmpc_convex_solve_instances: ConvexMpc's problem, instance i solved with the handle's parameters and the fields of
+        iparams[i] (INSTANCE_PARAMS_DTYPE; q_weights[12] and w are validated but unused).  Returns (forces_world [B,12], info) or,
+        with want_traj, also traj_u [B,N,12] and traj_x [B,N+1,12]."""
+        inputs = np.ascontiguousarray(inputs, dtype=CONVEX_INPUT_DTYPE)
+        iparams = np.ascontiguousarray(iparams, dtype=INSTANCE_PARAMS_DTYPE)
+        B, N = inputs.shape[0], self.params.horizon
+        if iparams.shape != (B,):
+            raise ValueError(f"iparams: shape {iparams.shape}, expected ({B},)")
+        forces = np.zeros((B, NU), dtype=np.float64)
+        info = np.zeros(B, dtype=INFO_DTYPE)
+        tu = np.zeros((B, N, NU)) if want_traj else None
+        tx = np.zeros((B, N + 1, 12)) if want_traj else None
+        st = self.lib.qmpc_convex_solve_instances(self._h, B, _ptr(inputs), _ptr(iparams), _ptr(forces), _ptr(info), _ptr(tu), _ptr(tx))
+        if st != OK:
+            raise QmpcError(st, "qmpc_convex_solve_instances")
+        return (forces, info, tu, tx) if want_traj else (forces, info)
+
+    def convex_solve_instances_device(self, batch: int, d_in: int, d_iparams: int, d_forces: int, d_info: int, stream: int = 0):
+        """qmpc_convex_solve_instances_device: device pointers (ints), stream-ordered, no synchronisation."""
+        st = self.lib.qmpc_convex_solve_instances_device(self._h, int(batch), C.c_void_p(d_in), C.c_void_p(d_iparams),
+                                                         C.c_void_p(d_forces), C.c_void_p(d_info) if d_info else None,
+                                                         C.c_void_p(stream) if stream else None)
+        if st != OK:
+            raise QmpcError(st, "qmpc_convex_solve_instances_device")
+
+    def kernel_for_convex_instances(self, batch: int) -> str:
+        """The kernel family convex_solve_instances* launches for a batch size ("none": the handle refuses the call)."""
+        return KERNEL_FAMILY[self.query(QUERY_KERNEL_FOR_CONVEX_INSTANCES, batch)]
 
     def convex_linearize(self, inputs: np.ndarray):
         inputs = np.ascontiguousarray(inputs, dtype=CONVEX_INPUT_DTYPE)
@@ -1221,5 +1273,6 @@ class Solver:
 
 
 from .scenarios import (go1_stand_input, quat_to_rot, random_go1_trot_states,  # noqa: E402,F401
-                        random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_plants, random_go1_pushes)
+                        random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_convex_variants, random_go1_plants,
+                        random_go1_pushes)
 from .sharding import StepPipeline, gather_forces, shard_range, solve_sharded  # noqa: E402,F401

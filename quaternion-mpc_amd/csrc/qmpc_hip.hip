@@ -89,16 +89,19 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
 QMPC_REC_DECLARE(qmpc_inst_tu)
 QMPC_REC_DECLARE(qmpc_outc_tu)
 QMPC_REC_DECLARE(qmpc_push_tu)
+QMPC_REC_DECLARE(qmpc_crec_tu)      // qmpc_loop_crec.hip: the three kinds on a ConvexMpc handle (qmpc_set_convex_records)
 #undef QMPC_REC_DECLARE
 enum { REC_PLAIN = 0, REC_OUTCOME = 1, REC_PUSH = 2 };      // the kind of a call with records: QMPC_REC_EXT of its unit
+enum { REC_CONVEX = 3 };                                    // ... the unit that serves every kind for ConvexMpc's problem
 static const struct {
   decltype(&qmpc_inst_tu::rec_set_lds) set_lds;
   decltype(&qmpc_inst_tu::rec_fused_launch) fused_launch;
   decltype(&qmpc_inst_tu::rec_front_launch) front_launch;
   decltype(&qmpc_inst_tu::rec_post_launch) post_launch;
-} kRec[3] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
+} kRec[4] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
              {qmpc_outc_tu::rec_set_lds, qmpc_outc_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_outc_tu::rec_post_launch},
-             {qmpc_push_tu::rec_set_lds, qmpc_push_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_push_tu::rec_post_launch}};
+             {qmpc_push_tu::rec_set_lds, qmpc_push_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_push_tu::rec_post_launch},
+             {qmpc_crec_tu::rec_set_lds, qmpc_crec_tu::rec_fused_launch, qmpc_crec_tu::rec_front_launch, qmpc_crec_tu::rec_post_launch}};
 // ... and the kernels each unit has beside them: the expansions of the plant blocks and the check of the windows
 hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, const qmpc_plant_params* plant,
                                         const qmpc_instance_params* ctrl, const int* ctrl_status, void* bcast_out, void* plants_out,
@@ -151,6 +154,12 @@ hipError_t qmpc_lane_inst_warm_launch_only(int pslot, int batch, hipStream_t s, 
                                            const double* u_init, double* traj_u, int check_prev, int iter_cap, int* hcount, int* hsel,
                                            double* hstate, int hcap, int pair);
 
+// qmpc_wform_cinst.hip: ConvexMpc's solve with per-instance parameters (qmpc_convex_solve_instances*)
+hipError_t qmpc_wform_cinst_set_lds();
+hipError_t qmpc_wform_cinst_solve_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
+                                         const qmpc_input* in, double* forces, qmpc_info* info, double* traj_u, double* traj_x,
+                                         double* gws);
+
 struct qmpc_handle {
   qmpc_params params;
   DevParams dev;
@@ -202,6 +211,8 @@ struct qmpc_handle {
   qmpc_push_params* d_push;       // staging of qmpc_loop_run_pushes (the host-buffer call), on its first use: [max_batch][push_cap]
   int push_cap;                   // ... windows per robot it holds (grown when a call brings more)
   int loop_warm_rec;              // qmpc_set_loop_warm_records: 1 the loops with controller records accept lp->warm_start (default 0)
+  int convex_rec;                 // qmpc_set_convex_records: 1 the loops with records accept this ConvexMpc handle (default 0); then
+                                  // d_outcome is also the scratch the outcome step of a call without outcome records runs on
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -358,6 +369,7 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   for (const auto& r : kRec) HIP_TRY(r.set_lds());
   HIP_TRY(qmpc_wform_inst_list_set_lds());
   HIP_TRY(qmpc_wform_inst_warm_set_lds());
+  HIP_TRY(qmpc_wform_cinst_set_lds());
   HIP_TRY(hipMalloc(&h->d_gws, sizeof(double) * (size_t)N * (13 * nu + 21 * nl + 30 * nl) * (size_t)max_batch));
   return QMPC_OK;
 }
@@ -1009,8 +1021,79 @@ qmpc_status qmpc_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_input
   return QMPC_OK;
 }
 
+// ---- ... for ConvexMpc's problem (converged mode; qmpc_wform_cinst.hip: qmpc_solve_cw_inst_kernel) ---------------------------
+// The records, the expansion kernel and the handle's per-instance buffers are those above: apply_instance_params writes the
+// record's fields into the handle's DevParams whatever the model.
+static qmpc_status convex_instances_check(const qmpc_handle* h, int32_t batch) {
+  if (h->params.model != QMPC_MODEL_CONVEX || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
+  if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
+  if (batch > 0 && plan_convex_instances(h->sel, batch).family == QMPC_KERNEL_NONE) return QMPC_UNSUPPORTED;
+  return QMPC_OK;
+}
+
+static qmpc_status launch_convex_instances(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_rec,
+                                           double* d_forces, qmpc_info* d_info, double* d_tu, double* d_tx, hipStream_t s) {
+  const qmpc_plan p = plan_convex_instances(h->sel, batch);
+  const qmpc_status es = ensure_instance_buffers(h);
+  if (es != QMPC_OK) return es;
+  HIP_TRY(hipEventRecord(h->ev0, s));
+  HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_rec, inst_dev(h), inst_status(h)));
+  HIP_TRY(qmpc_wform_cinst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, d_forces, d_info, d_tu, d_tx,
+                                        p.gws ? h->d_gws : nullptr));
+  h->last_kernel = p.family;
+  HIP_TRY(hipEventRecord(h->ev1, s));
+  h->timed = true;
+  return QMPC_OK;
+}
+
+qmpc_status qmpc_convex_solve_instances_device(qmpc_handle* h, int32_t batch, const qmpc_convex_input* d_in,
+                                               const qmpc_instance_params* d_iparams, double* d_forces_world, qmpc_info* d_info,
+                                               void* stream) {
+  if (!h || batch < 0 || (batch > 0 && (!d_in || !d_iparams || !d_forces_world))) return QMPC_BAD_ARGUMENT;
+  const qmpc_status cs = convex_instances_check(h, batch);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  HIP_TRY(hipSetDevice(h->device));
+  return launch_convex_instances(h, batch, reinterpret_cast<const qmpc_input*>(d_in), d_iparams, d_forces_world, d_info, nullptr, nullptr,
+                                 stream ? (hipStream_t)stream : h->stream);
+}
+
+qmpc_status qmpc_convex_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_convex_input* in, const qmpc_instance_params* iparams,
+                                        double* forces_world, qmpc_info* info, double* traj_u, double* traj_x) {
+  if (!h || batch < 0 || (batch > 0 && (!in || !iparams || !forces_world))) return QMPC_BAD_ARGUMENT;
+  const qmpc_status cs = convex_instances_check(h, batch);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  HIP_TRY(hipSetDevice(h->device));
+  // an earlier non-blocking call was never waited for: complete it first (it owes a pageable caller its copy-out)
+  if (h->pending.forces || h->pending.info || h->stage_in_busy) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    finish_pending(h);
+    h->stage_in_busy = 0;
+  }
+  const int N = h->params.horizon;
+  const qmpc_status es = ensure_instance_buffers(h);
+  if (es != QMPC_OK) return es;
+  // (the trajectory buffers are sized as every call of the handle sizes them: rows of 13 hold ConvexMpc's rows of 12)
+  if (traj_u && !h->d_traj_u) HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * N * (size_t)h->max_batch));
+  if (traj_x && !h->d_traj_x) HIP_TRY(hipMalloc(&h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch));
+  HIP_TRY(hipMemcpyAsync(h->d_in, in, sizeof(qmpc_input) * (size_t)batch, hipMemcpyDefault, h->stream));
+  HIP_TRY(hipMemcpyAsync(inst_rec(h), iparams, sizeof(qmpc_instance_params) * (size_t)batch, hipMemcpyDefault, h->stream));
+  const qmpc_status st = launch_convex_instances(h, batch, h->d_in, inst_rec(h), h->d_forces, h->d_info, traj_u ? h->d_traj_u : nullptr,
+                                                 traj_x ? h->d_traj_x : nullptr, h->stream);
+  if (st != QMPC_OK) return st;
+  HIP_TRY(hipMemcpyAsync(forces_world, h->d_forces, sizeof(double) * 12 * (size_t)batch, hipMemcpyDefault, h->stream));
+  if (info) HIP_TRY(hipMemcpyAsync(info, h->d_info, sizeof(qmpc_info) * (size_t)batch, hipMemcpyDefault, h->stream));
+  if (traj_u) HIP_TRY(hipMemcpyAsync(traj_u, h->d_traj_u, sizeof(double) * 12 * N * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  if (traj_x) HIP_TRY(hipMemcpyAsync(traj_x, h->d_traj_x, sizeof(double) * 12 * (N + 1) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return QMPC_OK;
+}
+
 qmpc_status qmpc_prepare_instances(qmpc_handle* h) {
   if (!h) return QMPC_BAD_ARGUMENT;
+  if (convex_instances_check(h, 0) == QMPC_OK) {      // ConvexMpc: the per-instance buffers (no lane form)
+    HIP_TRY(hipSetDevice(h->device));
+    return ensure_instance_buffers(h);
+  }
   const qmpc_status cs = instances_check(h, 0);
   if (cs != QMPC_OK) return cs;
   HIP_TRY(hipSetDevice(h->device));
@@ -1028,6 +1111,12 @@ qmpc_status qmpc_set_instances_policy(qmpc_handle* h, int32_t policy) {
 qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on) {
   if (!h || (on != 0 && on != 1)) return QMPC_BAD_ARGUMENT;
   h->loop_warm_rec = on;
+  return QMPC_OK;
+}
+
+qmpc_status qmpc_set_convex_records(qmpc_handle* h, int32_t on) {
+  if (!h || (on != 0 && on != 1)) return QMPC_BAD_ARGUMENT;
+  h->convex_rec = on;
   return QMPC_OK;
 }
 
@@ -1074,11 +1163,16 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       const int64_t b = arg & 0xffffffffLL;
       if (b < 1 || b > h->max_batch) return QMPC_BAD_ARGUMENT;
       const qmpc_plan p = plan_loop_instances(h->sel, (int)b, (arg >> 32) & 1, (arg >> 33) & 1, h->inst_policy, h->handoff_failed,
-                                              h->loop_warm_rec != 0);
+                                              h->loop_warm_rec != 0, false, h->convex_rec != 0);
       *value = p.family == QMPC_KERNEL_NONE ? 0 : 16 * (p.fused ? 1 : 2) + p.family;
       return QMPC_OK;
     }
     case QMPC_QUERY_LOOP_WARM_RECORDS: *value = h->loop_warm_rec; return QMPC_OK;
+    case QMPC_QUERY_CONVEX_RECORDS: *value = h->convex_rec; return QMPC_OK;
+    case QMPC_QUERY_KERNEL_FOR_CONVEX_INSTANCES:
+      if (arg < 1 || arg > h->max_batch) return QMPC_BAD_ARGUMENT;
+      *value = plan_convex_instances(h->sel, (int)arg).family;
+      return QMPC_OK;
     default: return QMPC_BAD_ARGUMENT;
   }
 }
@@ -1604,15 +1698,22 @@ void qmpc_plant_params_from(const qmpc_params* p, qmpc_plant_params* out) {
   std::memcpy(out->inertia, p->inertia, sizeof out->inertia);
 }
 
+// the handle is ConvexMpc's and opted in to the loops with records (qmpc_set_convex_records): the kernels of qmpc_loop_crec.hip
+static bool convex_records(const qmpc_handle* h) { return h->params.model == QMPC_MODEL_CONVEX && h->convex_rec != 0; }
+
 // the call-level checks of both entry points, for a call with at least one kind of record (QMPC_OK: go on)
 static qmpc_status loop_instances_check(const qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, bool has_ctrl) {
   if (h->params.model != QMPC_MODEL_QUAT && h->params.model != QMPC_MODEL_CONVEX) return QMPC_BAD_ARGUMENT;
-  if (h->params.model != QMPC_MODEL_QUAT || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
-  // (controller records with the warm start: on a handle that opted in only, qmpc_set_loop_warm_records)
-  if (has_ctrl && ((lp->warm_start != 0.0 && !h->loop_warm_rec) || !h->sel.wform)) return QMPC_UNSUPPORTED;
+  // (a ConvexMpc handle: one that opted in only, qmpc_set_convex_records)
+  const bool crec = convex_records(h);
+  if ((h->params.model != QMPC_MODEL_QUAT && !crec) || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
+  // (the device tick of ConvexMpc carries the controller period as the literal 5 ms: loop_run_impl)
+  if (crec && h->params.h != (float)(5.0 / 1000.0)) return QMPC_UNSUPPORTED;
+  // (controller records with the warm start: on a QuatMpc handle that opted in only, qmpc_set_loop_warm_records)
+  if (has_ctrl && ((lp->warm_start != 0.0 && (crec || !h->loop_warm_rec)) || !h->sel.wform)) return QMPC_UNSUPPORTED;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
   if (batch > 0 && plan_loop_instances(h->sel, batch, has_ctrl, lp->warm_start != 0.0, QMPC_INSTANCES_WAVE, h->handoff_failed,
-                                       h->loop_warm_rec != 0).family == QMPC_KERNEL_NONE)
+                                       h->loop_warm_rec != 0, false, crec).family == QMPC_KERNEL_NONE)
     return QMPC_UNSUPPORTED;
   return QMPC_OK;
 }
@@ -1626,12 +1727,20 @@ static qmpc_status loop_instances_buffers(qmpc_handle* h, int32_t batch, bool ha
   qmpc_status es = ensure_instance_buffers(h);
   if (es == QMPC_OK) es = ensure_plant_buffers(h);
   if (es != QMPC_OK) return es;
-  const bool wr = h->loop_warm_rec != 0;
-  qmpc_plan p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed, wr);
+  const bool wr = h->loop_warm_rec != 0, crec = convex_records(h);
+  // (ConvexMpc: the scratch the outcome step of a call without outcome records runs on)
+  if (crec && !h->d_outcome) {
+    HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
+    // (its contents never reach a result -- the parameters that go with it halt no robot -- zeroed once all the same)
+    HIP_TRY(hipMemsetAsync(h->d_outcome, 0, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  qmpc_plan p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed, wr, false, crec);
   if (has_ctrl && !p.fused && p.variant == 4) {
     es = ensure_lane_inst_buffers(h, false);
     if (es != QMPC_OK) return es;
-    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed, wr);
+    if (p.iter_cap && !ensure_handoff_buffers(h))
+      p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed, wr, false, crec);
   }
   if (has_ctrl && warm && !p.fused) {      // (an opted-in handle: what loop_setup would allocate after a ticks = 0 return)
     es = ensure_loop_buffers(h, true);
@@ -1663,6 +1772,14 @@ static qmpc_status loop_inst_tick_solve(qmpc_handle* h, const qmpc_plan& p, int3
     HIP_TRY(qmpc_wform_inst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces, h->d_info,
                                          nullptr, nullptr, p.gws ? h->d_gws : nullptr));
   }
+  h->last_kernel = p.family;
+  return QMPC_OK;
+}
+
+// ... on a ConvexMpc handle (qmpc_set_convex_records): qmpc_solve_cw_inst_kernel on the variant of plan_convex_instances
+static qmpc_status loop_convex_inst_tick_solve(qmpc_handle* h, const qmpc_plan& p, int32_t batch, hipStream_t s) {
+  HIP_TRY(qmpc_wform_cinst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces, h->d_info,
+                                        nullptr, nullptr, p.gws ? h->d_gws : nullptr));
   h->last_kernel = p.family;
   return QMPC_OK;
 }
@@ -1735,7 +1852,20 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
                                                                                  h->loop_warm_rec != 0, /*first=*/true)
                                                              : lpp;
   const qmpc_loop_params LP = *lp;
-  const auto& R = kRec[kind];
+  // a ConvexMpc handle (opted in): one unit for the three kinds -- a call without windows passes none (per_robot = 0), a call
+  // without outcome records the handle's scratch and parameters that never halt a robot
+  const bool crec = convex_records(h);
+  const auto& R = kRec[crec ? REC_CONVEX : kind];
+  qmpc_outcome_params op_none;
+  std::memset(&op_none, 0, sizeof op_none);
+  if (crec && kind == REC_PLAIN) {
+    op = &op_none;
+    d_outcomes = h->d_outcome;
+  }
+  if (crec && kind != REC_PUSH) {
+    d_push = nullptr;
+    per_robot = 0;
+  }
   // the records are expanded once per call: the controllers' blocks (or, for the persistent kernel without controller records,
   // the handle's block per robot) and the plant blocks with each robot's verdict
   if (d_ctrl) HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_ctrl, inst_dev(h), inst_status(h)));
@@ -1755,7 +1885,8 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   auto one_tick = [&](bool first) -> qmpc_status {
     HIP_TRY(R.front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch, op, d_outcomes));
     // with controller records the solve on the blocks expanded above, without them the plain loop's
-    const qmpc_status st = !d_ctrl ? loop_tick_solve(h, batch, s, warm, first, false)
+    const qmpc_status st = !d_ctrl ? loop_tick_solve(h, batch, s, warm, first, crec)
+                           : crec  ? loop_convex_inst_tick_solve(h, lpp, batch, s)
                            : warm  ? loop_inst_warm_tick_solve(h, first ? lpp_first : lpp, batch, s, first)
                                    : loop_inst_tick_solve(h, lpp, batch, s);
     if (st != QMPC_OK) return st;

@@ -94,4 +94,9 @@ static inline int wform_list_inst_slot(int var) { return wform_list_slot(var); }
 constexpr int kWformInstWarmSlots = 3;
 static inline int wform_inst_warm_slot(int var) { return wform_index(var); }
 
+// ---- qmpc_wform_cinst.hip -----------------------------------------------------------------------------------------------
+// qmpc_solve_cw_inst_kernel<WVAR> (qmpc_convex_solve_instances*: ConvexMpc's problem with per-instance parameters): 3 5 6
+constexpr int kWformConvexInstSlots = 3;
+static inline int wform_convex_inst_slot(int var) { return wform_index(var); }
+
 }  // namespace qmpc

@@ -3,6 +3,11 @@
 //   QMPC_REC_EXT 0   controller and plant records only                          (qmpc_loop_run_instances*)
 //                1   ... and the outcome step after the post step               (qmpc_loop_run_outcomes*)
 //                2   ... whose plant step integrates under timed push windows   (qmpc_loop_run_pushes*)
+// and, for the sibling controller (qmpc_loop_crec.hip; a handle opts in with qmpc_set_convex_records),
+//   QMPC_REC_CONVEX  defined: ConvexMpc's problem -- ConvexModel and the wrench-form body with QMPC_WMODEL WM_CONVEX, the front
+//                    end loop_front_convex_one on qmpc_convex_input records, the world-frame back end with the robot's plant
+//                    (loop_post_plant_world_one below).  That unit is built at EXT 2 and has a front kernel of its own; it serves
+//                    the three calls (the calls without windows pass per_robot = 0, the call without outcome records a scratch).
 // Textual inclusion, not a template over EXT: each unit compiles to the instructions it had as a file of its own (a shared
 // __forceinline__ function template moved the register assignment of every kernel; DESIGN.md).  The parameters a smaller EXT
 // does not have are written with the two macros below; a kernel's parameter list is that of its EXT and of no other.
@@ -12,6 +17,15 @@
 //               converged mode, wrench-form body) with the robot's own controller and plant
 //   launchers   rec_set_lds, rec_fused_launch, rec_front_launch, rec_post_launch: one signature for the three units, the
 //               arguments beyond the unit's EXT ignored (declared for qmpc_hip.hip by its QMPC_REC_DECLARE)
+#ifdef QMPC_REC_CONVEX
+#define QMPC_REC_MODEL ConvexModel
+#define QMPC_REC_FRONT(OCC_, LP_, s_, r_) loop_front_convex_one<OCC_>(LP_, s_, reinterpret_cast<qmpc_convex_input&>(r_))
+#define QMPC_REC_POST loop_post_plant_world_one
+#else
+#define QMPC_REC_MODEL QuatModel
+#define QMPC_REC_FRONT(OCC_, LP_, s_, r_) loop_front_one<OCC_>(LP_, s_, r_)
+#define QMPC_REC_POST loop_post_plant_one
+#endif
 #if QMPC_REC_EXT >= 1
 #define QMPC_REC_OUTCOME(...) __VA_ARGS__
 #else
@@ -52,8 +66,46 @@ __device__ inline PlantDev push_plant(const PlantDev& pl, const qmpc_push_params
 }
 #endif
 
+#ifdef QMPC_REC_CONVEX
+// The back end of ConvexMpc's tick with the robot's own TRUE plant: loop_post_one<true> (qmpc_loop.hip: the solve returns
+// WORLD-frame forces, optimized_input = R' u; converged mode) with pl's mass, inverse inertia and disturbance wrench in the plant
+// step, as loop_post_plant_one is loop_post_one<false> with them.  plant_step_ext with the handle's mass and inertia and a zero
+// wrench gives plant_step's bits, so such a plant gives loop_post_one<true>'s state and trace rows.
+template <int OCC = 1>
+QMPC_LOOP_FN void loop_post_plant_world_one(const PlantDev& pl, const qmpc_loop_params& LP, qmpc_loop_state& s,
+                                            const double* __restrict__ forces, const qmpc_info& inf, double* __restrict__ trace_f,
+                                            double* __restrict__ trace_c) {
+#pragma clang fp contract(off)
+  const int status = inf.status;
+  s.status = (double)status;
+  s.iterations = (double)inf.iterations;
+  const bool accepted = status == QMPC_OK || status == QMPC_MAX_ITER;     // (the converged mode only)
+  double R[9];
+  qmpc_loop::quat_to_rot(s.quat, R);
+  if (accepted)
+    for (int l = 0; l < 4; ++l)
+      for (int r = 0; r < 3; ++r) {
+        s.grf_world[3 * l + r] = forces[3 * l + r];
+        s.forces_body[3 * l + r] = R[r] * forces[3 * l] + R[3 + r] * forces[3 * l + 1] + R[6 + r] * forces[3 * l + 2];
+      }
+  if (trace_f) for (int a = 0; a < 12; ++a) trace_f[a] = s.forces_body[a];
+  if (trace_c) for (int a = 0; a < 4; ++a) trace_c[a] = s.contacts[a];
+  double x[13];
+  for (int a = 0; a < 3; ++a) { x[a] = s.pos_world[a]; x[7 + a] = s.lin_vel_world[a]; x[10 + a] = s.ang_vel_body[a]; }
+  for (int a = 0; a < 4; ++a) x[3 + a] = s.quat[a];
+  qmpc_loop::plant_step_ext(x, s.forces_body, s.foot_pos_world, 4, pl.mass, pl.Iinv, pl.force, pl.torque, LP.dt);
+  for (int a = 0; a < 3; ++a) { s.pos_world[a] = x[a]; s.lin_vel_world[a] = x[7 + a]; s.ang_vel_body[a] = x[10 + a]; }
+  for (int a = 0; a < 4; ++a) s.quat[a] = x[3 + a];
+  if (s.movement_mode != 0.0)
+    for (int l = 0; l < 4; ++l)
+      if (s.contacts[l] == 0.0)
+        for (int a = 0; a < 3; ++a) s.foot_pos_world[3 * l + a] = s.leg[l].fsm_pos[a];
+  s.tick += 1.0;
+}
+#endif
+
 // ---- per-tick form -----------------------------------------------------------------------------------------------------
-#if QMPC_REC_EXT <= 1
+#if QMPC_REC_EXT <= 1 || defined(QMPC_REC_CONVEX)
 // The front end of qmpc_loop_front_kernel; the record of a frozen robot, or of one halted under stop_when_down, gets a NaN
 // attitude instead, which every solve kernel rejects before its first iteration (QMPC_NAN_INPUT; the post kernel ignores it)
 __global__ __launch_bounds__(64) void qmpc_loop_rec_front_kernel(
@@ -63,10 +115,10 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_front_kernel(
   if (i == 0 && row) *row += 1;                         // trace row of this tick (stream order: after the last post)
   if (i >= batch) return;
   if (pl[i].status != QMPC_OK QMPC_REC_OUTCOME(|| outcome_halted(OP, oc[i]))) {
-    rec[i].quat[0] = __builtin_nan("");
+    rec[i].quat[0] = __builtin_nan("");      // (ConvexMpc's record: its first word, euler[0])
     return;
   }
-  loop_front_one(LP, st[i], rec[i]);
+  QMPC_REC_FRONT(1, LP, st[i], rec[i]);
 }
 #endif
 
@@ -93,9 +145,9 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
 #endif
 #if QMPC_REC_EXT >= 2
   const PlantDev p = push_plant(pl[i], push + (size_t)i * per_robot, per_robot, st[i].tick);
-  loop_post_plant_one(p, LP, st[i], forces + 12 * (size_t)i, info[i], tf, tc);
+  QMPC_REC_POST(p, LP, st[i], forces + 12 * (size_t)i, info[i], tf, tc);
 #else
-  loop_post_plant_one(pl[i], LP, st[i], forces + 12 * (size_t)i, info[i], tf, tc);
+  QMPC_REC_POST(pl[i], LP, st[i], forces + 12 * (size_t)i, info[i], tf, tc);
 #endif
 #if QMPC_REC_EXT >= 1
   qmpc_loop::loop_outcome_one(OP, st[i], o);
@@ -116,7 +168,7 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
 // across the solve (variants 5 / 6 sit at their 256-register limit).
 // (The two zero-fill loops stay written out: as calls of one inline function they compile to other instructions.)
 template <int VAR>
-__global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QuatModel, VAR)) void qmpc_loop_rec_fused_kernel(
+__global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmpc_loop_rec_fused_kernel(
     const DevParams* __restrict__ Pi, const PlantDev* __restrict__ plants, qmpc_loop_params LP, QMPC_REC_OUTCOME(qmpc_outcome_params OP, )
     qmpc_loop_state* __restrict__ st, qmpc_input* __restrict__ rec, double* __restrict__ forces, qmpc_info* __restrict__ info,
     double* __restrict__ trace_f, double* __restrict__ trace_c, QMPC_REC_OUTCOME(qmpc_loop_outcome* __restrict__ outcomes, )
@@ -125,9 +177,9 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QuatModel, VAR)) void qmpc_loo
   const int b = blockIdx.x;
   if (b >= batch) return;
   const int lane = threadIdx.x;
-  typedef QuatModel MD;
+  typedef QMPC_REC_MODEL MD;
   constexpr bool PROF = false;
-  constexpr int OCC = QMPC_SOLVE_WAVES(QuatModel, VAR);
+  constexpr int OCC = QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR);
   const qmpc_input* in_ = rec;
   double *traj_u = nullptr, *traj_x = nullptr;
   long long* prof_out = nullptr;
@@ -151,14 +203,20 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QuatModel, VAR)) void qmpc_loo
 #endif
   bool prev_ok = false;
   for (int t = 0; t < ticks; ++t) {
-    if (lane == 0) loop_front_one<OCC>(LP, st[b], rec[b]);
+    if (lane == 0) QMPC_REC_FRONT(OCC, LP, st[b], rec[b]);
     __syncthreads();                      // the record (global memory) is visible to the wave
     [&]() {
       const int warm_t = (LP.warm_start != 0.0 && prev_ok) ? t : 0;   // t > 0 and the last solve left a usable U in LDS
       constexpr int WVAR = VAR;
       const int wslot = b;
       constexpr const double* resume = nullptr;
+#ifdef QMPC_REC_CONVEX
+#define QMPC_WMODEL WM_CONVEX
+#endif
 #include "qmpc_wform_body.inc"
+#ifdef QMPC_REC_CONVEX
+#undef QMPC_WMODEL
+#endif
     }();
     __syncthreads();
     prev_ok = info[b].status == QMPC_OK || info[b].status == QMPC_MAX_ITER;   // uniform: every lane reads the same word
@@ -169,10 +227,10 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QuatModel, VAR)) void qmpc_loo
       const size_t slot = (size_t)t * batch + b;
 #if QMPC_REC_EXT >= 2
       const PlantDev p = push_plant(plants[b], push + (size_t)b * per_robot, per_robot, st[b].tick);
-      loop_post_plant_one<OCC>(p, LP, st[b], forces + 12 * (size_t)b, info[b], trace_f ? trace_f + 12 * slot : nullptr,
+      QMPC_REC_POST<OCC>(p, LP, st[b], forces + 12 * (size_t)b, info[b], trace_f ? trace_f + 12 * slot : nullptr,
                                trace_c ? trace_c + 4 * slot : nullptr);
 #else
-      loop_post_plant_one<OCC>(plants[b], LP, st[b], forces + 12 * (size_t)b, info[b], trace_f ? trace_f + 12 * slot : nullptr,
+      QMPC_REC_POST<OCC>(plants[b], LP, st[b], forces + 12 * (size_t)b, info[b], trace_f ? trace_f + 12 * slot : nullptr,
                                trace_c ? trace_c + 4 * slot : nullptr);
 #endif
 #if QMPC_REC_EXT >= 1
@@ -217,7 +275,7 @@ __attribute__((visibility("hidden"))) hipError_t rec_fused_launch(
   return hipGetLastError();
 }
 
-#if QMPC_REC_EXT <= 1
+#if QMPC_REC_EXT <= 1 || defined(QMPC_REC_CONVEX)
 __attribute__((visibility("hidden"))) hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st,
                                                                   qmpc_input* rec, int* row, const void* plants, int batch,
                                                                   const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes) {
@@ -241,3 +299,6 @@ __attribute__((visibility("hidden"))) hipError_t rec_post_launch(hipStream_t s, 
 #undef QMPC_REC_OUTCOME
 #undef QMPC_REC_PUSH
 #undef QMPC_REC_EXT
+#undef QMPC_REC_MODEL
+#undef QMPC_REC_FRONT
+#undef QMPC_REC_POST

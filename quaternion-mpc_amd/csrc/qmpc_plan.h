@@ -311,6 +311,32 @@ static inline qmpc_plan plan_instances(const qmpc_select& s, int batch, int poli
   return p.variant == 4 ? p : w;
 }
 
+// The plan of qmpc_convex_solve_instances* (ConvexMpc's problem with per-instance parameters; qmpc_wform_cinst.hip:
+// qmpc_solve_cw_inst_kernel<3|5|6>).  NONE unless the handle is ConvexMpc in the converged mode with the wrench form on.
+// Where a plain solve of `batch` instances on the wave kernels (lane_slot off: there is no lane form with per-lane parameters
+// for this problem, whatever the qmpc_instances_policy) takes a wrench-form variant: that variant, and the results are the plain
+// solve's bit for bit.  Where it falls to the round-1 family (beyond one resident round of the workspace form, QMPC_VARIANT
+// 2 / 3) there is no per-instance dense kernel, and the call keeps the wrench form: 6 (slack arrays in the workspace too: two
+// waves per SIMD) under plan()'s own condition for it, else 5 while its layout leaves a CU two instances (80 KB), else 3 if an
+// instance fits a CU at all; NONE otherwise.
+static inline qmpc_plan plan_convex_instances(const qmpc_select& s, int batch) {
+  if (s.model != QMPC_MODEL_CONVEX || s.mode != QMPC_MODE_CONVERGED || !s.wform) return qmpc_plan();
+  qmpc_select w = s;
+  w.lane_slot = false;
+  qmpc_plan p = plan(w, batch, QMPC_CALL_PLAIN, true, false);
+  if (p.family == QMPC_KERNEL_WFORM_LDS || p.family == QMPC_KERNEL_WFORM_WS) return p;
+  const size_t* lds = s.lds[0];
+  const bool w6 = s.horizon >= 4 && lds[6] <= 80 * 1024;      // plan(): WVAR 6 exists from four knots on, two waves per SIMD
+  const int var = w6 ? 6 : lds[5] <= 80 * 1024 ? 5 : lds[3] <= 160 * 1024 ? 3 : 0;
+  if (!var) return qmpc_plan();
+  p = qmpc_plan();
+  p.family = var == 3 ? QMPC_KERNEL_WFORM_LDS : QMPC_KERNEL_WFORM_WS;
+  p.variant = var;
+  p.lds = lds[var];
+  p.gws = var != 3;
+  return p;
+}
+
 // The plan of qmpc_loop_run_instances* (the closed loop with per-robot controller and / or plant records; qmpc_loop_inst.hip).
 // `has_ctrl`: controller records are given (their solve is the per-instance wrench-form kernel), `warm`: lp->warm_start.
 //   persistent  where the plain loop of this batch takes its persistent kernel (2048 robots, 4096 warm, or QMPC_LOOP_FUSED)
@@ -377,6 +403,29 @@ static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, boo
   l.lane_min_warm = 0;      // the switch-over is this call's own: the plain tick's plan only names the lane kernel's fields
   qmpc_plan p = plan(l, batch, first ? QMPC_CALL_WARM_LOOP_FIRST : QMPC_CALL_WARM_LOOP_TICK, true, handoff_failed);
   if (p.variant != 4) return w;
+  p.fused = false;
+  return p;
+}
+
+// ... on a handle that may have opted in to records on ConvexMpc's problem (qmpc_set_convex_records; `convex_records`).  Off, or
+// another model: the overload above, field for field.  On, for a ConvexMpc handle (qmpc_loop_crec.hip):
+//   persistent  where the plain ConvexMpc loop of this batch takes its persistent kernel on a wrench-form variant 3 / 5 / 6
+//               (2048 robots, 4096 warm, or QMPC_LOOP_FUSED): that plan (qmpc_loop_rec_fused_kernel<3|5|6> on the convex body);
+//   per tick    otherwise: with controller records the plan of qmpc_convex_solve_instances* (plan_convex_instances: the wave
+//               kernels at every size under either policy -- there is no lane form with per-lane parameters for this problem),
+//               without them the plain loop's tick (its lane kernel included); fused = false.
+// NONE: the reference mode, controller records with the warm start (whatever `warm_records` says) or with no wrench-form kernel
+// for the batch.
+static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, bool has_ctrl, bool warm, int policy, bool handoff_failed,
+                                            bool warm_records, bool first, bool convex_records) {
+  if (!convex_records || s.model != QMPC_MODEL_CONVEX)
+    return plan_loop_instances(s, batch, has_ctrl, warm, policy, handoff_failed, warm_records, first);
+  if (s.mode != QMPC_MODE_CONVERGED) return qmpc_plan();
+  if (has_ctrl && (warm || !s.wform)) return qmpc_plan();
+  const qmpc_plan f = plan(s, batch, warm ? QMPC_CALL_WARM_LOOP : QMPC_CALL_LOOP, true, handoff_failed);
+  if (f.fused && (f.variant == 3 || f.variant == 5 || f.variant == 6)) return f;
+  qmpc_plan p = has_ctrl ? plan_convex_instances(s, batch)
+                         : plan(s, batch, warm ? QMPC_CALL_WARM_LOOP_TICK : QMPC_CALL_LOOP_TICK, true, handoff_failed);
   p.fused = false;
   return p;
 }

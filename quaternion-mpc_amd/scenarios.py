@@ -261,6 +261,16 @@ def random_go1_variants(batch: int, seed: int = 0, first: int = 0, base=None) ->
     return rec
 
 
+def random_go1_convex_variants(batch: int, seed: int = 0, first: int = 0, base=None) -> np.ndarray:
+    """`batch` per-instance records for Solver.convex_solve_instances: the spread of random_go1_variants around `base`
+    (default: the ConvexMpc values of qmpc_default_convex_params).  The same generator and counters: with the same seed robot i
+    has the mass, the per-axis inertia factors, the friction, the force bound and the two cost factors of
+    random_go1_variants' robot i -- one fleet under both controllers."""
+    from . import default_convex_params
+
+    return random_go1_variants(batch, seed, first, default_convex_params(10) if base is None else base)
+
+
 def random_go1_plants(batch: int, seed: int = 0, first: int = 0, base=None, payload=(0.0, 4.0), inertia_scale=(0.8, 1.2),
                       force=(0.0, 0.0)) -> np.ndarray:
     """`batch` TRUE-plant records (``struct qmpc_plant_params``, for Solver.loop_run_instances) of Go1 robots around `base`

@@ -5,8 +5,13 @@ handle per size.  Columns: the plain solve, the per-instance call under QMPC_INS
 (random_go1_variants).  The calls alternate within a repetition, each timed with device events around the call on the same stream
 after warm-up; median of the repetitions.  The per-instance calls include their expansion kernel (one DevParams block per
 instance) and, under AUTO, the stance sort and the hand-off.
-    python tools/instance_params_bench.py [--policy wave|auto|both] [--reps 10] [--warmup 3] [--sizes 10:1024,...] [--json FILE]"""
+    python tools/instance_params_bench.py [--policy wave|auto|both] [--reps 10] [--warmup 3] [--sizes 10:1024,...] [--json FILE]
+--model convex: ConvexMpc's problem instead -- qmpc_convex_solve_device against qmpc_convex_solve_instances_device on
+    random_go1_convex_states, records from random_go1_convex_variants; the call has no lane form, so there is one policy column.
+--plain-lib FILE: another build of the library (e.g. the parent revision's) whose plain solve joins the alternation as
+    "base_plain", with a handle of its own on the same buffers: the per-instance call over THAT plain solve, in the same job."""
 import argparse
+import ctypes as C
 import importlib.util
 import json
 import sys
@@ -27,6 +32,32 @@ def load_pkg():
     return mod
 
 
+class BasePlain:
+    """the plain device solve of another build of the library, through its C ABI alone (the build may lack newer symbols)"""
+
+    def __init__(self, path, params, batch, convex):
+        self.lib = C.CDLL(str(path))
+        vp, i32 = C.c_void_p, C.c_int32
+        self.lib.qmpc_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
+        self.lib.qmpc_create.restype = i32
+        self.lib.qmpc_prepare.argtypes = [vp, i32]
+        self.lib.qmpc_prepare.restype = i32
+        self.lib.qmpc_destroy.argtypes = [vp]
+        self.fn = self.lib.qmpc_convex_solve_device if convex else self.lib.qmpc_solve_device
+        self.fn.argtypes = [vp, i32, vp, vp, vp, vp]
+        self.fn.restype = i32
+        self.h = vp()
+        rc = self.lib.qmpc_create(C.byref(params), batch, 0, C.byref(self.h))
+        assert rc == 0 and self.lib.qmpc_prepare(self.h, batch) == 0, rc
+
+    def solve(self, batch, d_in, d_f, d_info, stream):
+        rc = self.fn(self.h, batch, d_in, d_f, d_info, stream)
+        assert rc == 0, rc
+
+    def close(self):
+        self.lib.qmpc_destroy(self.h)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -34,6 +65,8 @@ def main():
     ap.add_argument("--sizes", default=DEFAULT_SIZES)
     ap.add_argument("--json", default=None)
     ap.add_argument("--policy", default="both", choices=("wave", "auto", "both"))
+    ap.add_argument("--model", default="quat", choices=("quat", "convex"))
+    ap.add_argument("--plain-lib", default=None)
     a = ap.parse_args()
     import torch
 
@@ -42,16 +75,22 @@ def main():
     rows = []
     for item in a.sizes.split(","):
         N, B = (int(x) for x in item.split(":"))
-        p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
-        rec = pkg.random_go1_trot_states(B, config_id=2)
+        convex = a.model == "convex"
+        if convex:
+            p = pkg.default_convex_params(N, pkg.MODE_CONVERGED, lib)
+            rec = pkg.random_go1_convex_states(B, config_id=13)
+        else:
+            p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+            rec = pkg.random_go1_trot_states(B, config_id=2)
         s = pkg.Solver(p, B, device=0, lib=lib)
-        policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
+        policies = ("wave",) if convex else ("wave", "auto") if a.policy == "both" else (a.policy,)
         if "auto" in policies:
             s.set_instances_policy("auto")      # the buffers of every call below are allocated here, not in a timed call
         s.prepare(B)
         s.prepare_instances()
         d_in = torch.from_numpy(rec.view(np.uint8).copy()).cuda()
-        records = {"uniform": pkg.instance_params(p, B), "variants": pkg.random_go1_variants(B, seed=13, base=p)}
+        records = {"uniform": pkg.instance_params(p, B),
+                   "variants": (pkg.random_go1_convex_variants if convex else pkg.random_go1_variants)(B, seed=13, base=p)}
         d_ip = {k: torch.from_numpy(v.view(np.uint8).copy()).cuda() for k, v in records.items()}
         d_f = torch.zeros((B, 12), dtype=torch.float64, device="cuda")
         d_info = torch.zeros(B * pkg.INFO_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
@@ -61,9 +100,14 @@ def main():
 
         def inst(policy, kind):
             s.set_instances_policy(policy)
-            s.solve_instances_device(B, d_in.data_ptr(), d_ip[kind].data_ptr(), d_f.data_ptr(), d_info.data_ptr(), stream=st)
+            (s.convex_solve_instances_device if convex else s.solve_instances_device)(B, d_in.data_ptr(), d_ip[kind].data_ptr(), d_f.data_ptr(),
+                                                                                      d_info.data_ptr(), stream=st)
 
-        calls = {"plain": lambda: s.solve_device(B, d_in.data_ptr(), d_f.data_ptr(), d_info.data_ptr(), stream=st)}
+        calls = {"plain": lambda: (s.convex_solve_device if convex else s.solve_device)(B, d_in.data_ptr(), d_f.data_ptr(), d_info.data_ptr(),
+                                                                                        stream=st)}
+        base = BasePlain(a.plain_lib, p, B, convex) if a.plain_lib else None
+        if base:
+            calls["base_plain"] = lambda: base.solve(B, d_in.data_ptr(), d_f.data_ptr(), d_info.data_ptr(), st)
         for pol in policies:
             for kind in records:
                 calls[f"{pol}_{kind}"] = (lambda pol=pol, kind=kind: inst(pol, kind))
@@ -77,11 +121,13 @@ def main():
                 e1.synchronize()
                 if r >= a.warmup:
                     times[k].append(e0.elapsed_time(e1))
-        row = {"N": N, "B": B, "plain_kernel": s.kernel_for_batch(B)}
+        row = {"N": N, "B": B, "model": a.model, "plain_kernel": s.kernel_for_batch(B)}
         for pol in policies:
             s.set_instances_policy(pol)
-            row[f"{pol}_kernel"] = s.kernel_for_instances(B)
+            row[f"{pol}_kernel"] = s.kernel_for_convex_instances(B) if convex else s.kernel_for_instances(B)
         s.close()
+        if base:
+            base.close()
         line = f"N={N:2d} B={B:6d}"
         for k, v in times.items():
             ms = float(np.median(v))
@@ -94,6 +140,12 @@ def main():
             line += f"  auto/wave variants x{row['wave_variants_ms'] / row['auto_variants_ms']:.3f}"
         if "auto" in policies:
             line += f"  auto/plain {row['auto_variants_ms'] / row['plain_ms']:.3f}"
+        if "wave" in policies:
+            row["wave_uniform_over_plain"] = row["wave_uniform_ms"] / row["plain_ms"]
+            line += f"  [plain: {row['plain_kernel']}]  wave_uniform/plain {row['wave_uniform_over_plain']:.3f}"
+            if base:
+                row["wave_uniform_over_base_plain"] = row["wave_uniform_ms"] / row["base_plain_ms"]
+                line += f"  wave_uniform/base_plain {row['wave_uniform_over_base_plain']:.3f}  plain/base_plain {row['plain_ms'] / row['base_plain_ms']:.3f}"
         rows.append(row)
         print(line, flush=True)
     if a.json:

@@ -24,7 +24,10 @@ per-robot calls include their expansion kernels.
     warm-started (lp.warm_start = 1 on a handle with ipm_mu0 = --mu0, the setting the plain warm loop's figures were taken
     with), alternating on the same states.  Per size: robot-ticks/s of the four calls, warm / cold of the call with records, and
     that ratio against the plain loop's own warm / cold -- with uniform records the plain warm loop is the ceiling.  --policy
-    both adds the calls with records under AUTO (the lane form from its switch-over on)."""
+    both adds the calls with records under AUTO (the lane form from its switch-over on).
+--model convex: the default comparison (plain / plant records / controller + plant records) on a ConvexMpc handle that opted in
+    with qmpc_set_convex_records, with the commands of the ConvexMpc loop tests and records around default_convex_params
+    (random_go1_convex_variants).  With ctrl the ticks stay on the wave kernels at every size under either policy."""
 import argparse
 import importlib.util
 import json
@@ -282,6 +285,7 @@ def main():
     ap.add_argument("--records", choices=("uniform", "random"), default="uniform")
     ap.add_argument("--warm-records", action="store_true")
     ap.add_argument("--mu0", type=float, default=1e-6)
+    ap.add_argument("--model", choices=("quat", "convex"), default="quat")
     a = ap.parse_args()
     import torch
 
@@ -290,6 +294,9 @@ def main():
     rows = []
     if a.stop and not a.outcomes:
         ap.error("--stop goes with --outcomes")
+    convex = a.model == "convex"
+    if convex and (a.pushes or a.warm_records or a.stop):
+        ap.error("--model convex goes with the default comparison and --outcomes")
     for item in a.sizes.split(","):
         N, B = (int(x) for x in item.split(":"))
         policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
@@ -305,16 +312,21 @@ def main():
             else:
                 rows.extend(falling(pkg, lib, torch, N, B, a, pol) for pol in policies)
             continue
-        p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+        p = (pkg.default_convex_params if convex else pkg.default_params)(N, pkg.MODE_CONVERGED, lib)
         lp = pkg.default_loop_params(lib)
         rng = np.random.default_rng(5)
         cmds = np.zeros((B, 7))
         cmds[:, 0] = rng.uniform(-0.4, 0.4, B); cmds[:, 1] = rng.uniform(-0.15, 0.15, B)
         cmds[:, 2] = rng.uniform(0.26, 0.32, B); cmds[:, 5] = rng.uniform(-0.4, 0.4, B)
         cmds[:, 6] = (rng.random(B) < 0.85).astype(float)
+        if convex:      # (this controller has no command for a robot that stands: tests/test_gpu_lane.py)
+            cmds[cmds[:, 6] == 0, :2] = 0.0
+            cmds[cmds[:, 6] == 0, 5] = 0.0
         stand = cmds.copy(); stand[:, 6] = 0.0
         st = pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, B), lib=lib)
         s = pkg.Solver(p, B, device=0, lib=lib)
+        if convex:
+            s.set_convex_records(True)
         for pol in policies:      # (the buffers of every policy asked for: allocated before anything is timed)
             s.set_instances_policy(pol)
             s.prepare(B)
@@ -324,11 +336,13 @@ def main():
         d_st0 = torch.from_numpy(st.view(np.uint8).copy()).cuda()
         d_st = d_st0.clone()
         if a.records == "random":
-            ctrl = pkg.random_go1_variants(B, seed=12, base=p)
+            ctrl = (pkg.random_go1_convex_variants if convex else pkg.random_go1_variants)(B, seed=12, base=p)
             ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
             plant = pkg.random_go1_plants(B, seed=11, base=p, payload=(-1.0, 3.0), force=(0.0, 10.0))
         else:
             ctrl, plant = pkg.instance_params(p, B), pkg.plant_params(p, B)
+        if convex:      # (the buffers of the calls with records, the outcome scratch included: before anything is timed)
+            s.loop_run_instances(st, 0, lp, ctrl=ctrl, plant=plant)
         d_ctrl = torch.from_numpy(ctrl.view(np.uint8).copy()).cuda()
         d_plant = torch.from_numpy(plant.view(np.uint8).copy()).cuda()
         stream = torch.cuda.Stream()
@@ -384,7 +398,7 @@ def main():
             forms["ctrl_plant" + suffix[pol]] = forms["ctrl_plant" + suffix[pol] + "_outcomes"] = s.loop_instances_plan(B, True, False)
         s.close()
         ms = {k: float(np.median(v)) for k, v in times.items()}
-        row = {"N": N, "B": B, "ticks": T, "records": a.records, "policy": policies[0]}
+        row = {"N": N, "B": B, "ticks": T, "records": a.records, "policy": policies[0], "model": a.model}
         for k in calls:
             row[k + "_ms"] = ms[k]
             row[k + "_Mrobot_ticks_s"] = B * T / ms[k] / 1e3

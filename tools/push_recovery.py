@@ -4,12 +4,14 @@ gait period (91 ticks of 5 ms at 2.2 Hz), every robot shoved once (qmpc_loop_run
 still up per cell from the outcome records.  The robots of a cell differ in their true plant (random_go1_plants: payload and
 inertia); the controller is the handle's and is not told about the push.
     python tools/push_recovery.py [--impulses 2,4,6,8,10] [--starts 13] [--length 10] [--per-cell 8] [--speed 0.3] [--settle 60]
-                                  [--recover 200] [--horizon 10] [--json FILE]
+                                  [--recover 200] [--horizon 10] [--controller quat|convex|both] [--json FILE]
 Every robot stands for 6 ticks, trots at --speed for --settle ticks, is shoved at tick 6 + settle + start for --length ticks with
 force impulse / (length dt) in its cell's direction (0 degrees: ahead, 90: to its left), and trots on until --recover ticks after
 the last start.  Down: below 0.15 m or tilted beyond 60 degrees (qmpc_default_outcome_params); stop_when_down halts a fallen robot.
 Prints one table per impulse (rows: start tick in the gait period, columns: direction) and the marginals.  The figures are whatever
-the run gives."""
+the run gives.
+--controller: QuatMpc (default), ConvexMpc (a handle that opted in with qmpc_set_convex_records), or both -- the same pushes,
+plants and commands under each controller, one summary per controller.  --horizon is then each controller's horizon."""
 import argparse
 import importlib.util
 import json
@@ -43,9 +45,17 @@ def main():
     ap.add_argument("--recover", type=int, default=200)
     ap.add_argument("--horizon", type=int, default=10)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--controller", choices=("quat", "convex", "both"), default="quat")
     a = ap.parse_args()
     pkg = load_pkg()
     lib = pkg.load_library()
+    results = [run(a, pkg, lib, c) for c in (("quat", "convex") if a.controller == "both" else (a.controller,))]
+    if a.json:
+        Path(a.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.json).write_text(json.dumps(results[0] if len(results) == 1 else results, indent=1) + "\n")
+
+
+def run(a, pkg, lib, controller):
     impulses = [float(x) for x in a.impulses.split(",")]
     starts = [int(round(k * PERIOD / a.starts)) for k in range(a.starts)]
     angles = np.arange(8) * (np.pi / 4)
@@ -53,12 +63,14 @@ def main():
     gi, gs, gd, _ = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8), np.arange(a.per_cell),
                                                     indexing="ij"))
     B = gi.size
-    p = pkg.default_params(a.horizon, pkg.MODE_CONVERGED, lib)
+    convex = controller == "convex"
+    p = (pkg.default_convex_params if convex else pkg.default_params)(a.horizon, pkg.MODE_CONVERGED, lib)
     lp = pkg.default_loop_params(lib)
     assert abs(1.0 / (lp.gait_freq * lp.dt) - PERIOD) < 0.5, (lp.gait_freq, lp.dt)
     cmd = [a.speed, 0.0, 0.30, 0.0, 0.0, 0.0, 0.0]
     st = pkg.loop_states([cmd] * B, lp, height=0.3, yaw=0.0, lib=lib)
-    plant = pkg.random_go1_plants(B, seed=21, base=p, payload=(0.0, 3.0))
+    # (the same plants under either controller: around QuatMpc's Go1, whose mass is ConvexMpc's too)
+    plant = pkg.random_go1_plants(B, seed=21, base=pkg.default_params(a.horizon, pkg.MODE_CONVERGED, lib), payload=(0.0, 3.0))
     push = pkg.push_params(B)
     t0 = 6 + a.settle
     push["start_tick"][:, 0] = t0 + np.asarray(starts, dtype=np.float64)[gs]
@@ -68,6 +80,8 @@ def main():
     push["force_world"][:, 0, 1] = mag * np.sin(angles[gd])
     op = pkg.default_outcome_params(lib, stop_when_down=True)
     s = pkg.Solver(p, B, device=0, lib=lib)
+    if convex:
+        s.set_convex_records(True)
     form = s.loop_instances_plan(B, False, False)
     total = a.settle + PERIOD + a.recover
     w0 = time.perf_counter()
@@ -79,7 +93,7 @@ def main():
     up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, a.per_cell)
     share = up.mean(axis=3)
     fell_before = int(((oc["down_tick"] >= 0) & (oc["down_tick"] <= push["start_tick"][:, 0])).sum())
-    print(f"push recovery: {B} robots ({len(impulses)} impulses x {len(starts)} start ticks x 8 directions x {a.per_cell} plants), N={a.horizon}, "
+    print(f"push recovery under {'ConvexMpc' if convex else 'QuatMpc'}: {B} robots ({len(impulses)} impulses x {len(starts)} start ticks x 8 directions x {a.per_cell} plants), N={a.horizon}, "
           f"trot at {a.speed} m/s, shove of {a.length:g} ticks from tick {t0} + start, {6 + total} ticks in all, launch {form}, "
           f"{wall:.2f} s wall with the copies; {fell_before} robots were down before their shove began")
     print(f"solves: {pkg.summarize_outcomes(oc)['mean_iterations']:.2f} iterations on average, "
@@ -91,11 +105,10 @@ def main():
         for j, t in enumerate(starts):
             print(f"{t:5d} " + " ".join(f"{share[i, j, d]:5.2f}" for d in range(8)) + f"  {share[i, j].mean():5.2f}")
         print("  all " + " ".join(f"{share[i, :, d].mean():5.2f}" for d in range(8)) + f"  {share[i].mean():5.2f}")
-    if a.json:
-        Path(a.json).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.json).write_text(json.dumps({"impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
-                                            "per_cell": a.per_cell, "length_ticks": a.length, "speed": a.speed, "form": form,
-                                            "share_up": share.tolist()}, indent=1) + "\n")
+    print(f"\nsummary, {'ConvexMpc' if convex else 'QuatMpc'}: share still up by impulse " +
+          "  ".join(f"{imp:g} N s: {share[i].mean():.3f}" for i, imp in enumerate(impulses)) + f"   all: {share.mean():.3f}\n")
+    return {"controller": controller, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
+            "per_cell": a.per_cell, "length_ticks": a.length, "speed": a.speed, "form": form, "share_up": share.tolist()}
 
 
 if __name__ == "__main__":
