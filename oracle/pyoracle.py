@@ -120,8 +120,9 @@ def solve(params: Params, inputs: np.ndarray, threads: int = 1, want_traj: bool 
     return forces, info
 
 
-def solve_warm(params: Params, inputs: np.ndarray, u_init):
-    """Every instance started from u_init [B][N][12] shifted by one knot (None: cold).  (forces, info, traj_u)"""
+def solve_warm(params: Params, inputs: np.ndarray, u_init, threads: int = 1):
+    """Every instance started from u_init [B][N][12] shifted by one knot (None: cold).  (forces, info, traj_u)
+    threads > 1: the instances on that many threads (the call keeps its state per thread; the results are the same bits)."""
     inputs = np.ascontiguousarray(inputs, dtype=INPUT_DTYPE)
     B, N = inputs.shape[0], params.horizon
     forces = np.zeros((B, 12))
@@ -130,9 +131,17 @@ def solve_warm(params: Params, inputs: np.ndarray, u_init):
     ui = None if u_init is None else np.ascontiguousarray(u_init, dtype=np.float64).reshape(B, N, 12)
     L = lib()
     L.qo_solve_one_warm.argtypes = [C.c_void_p] * 6
-    for b in range(B):
+    def one(b):
         L.qo_solve_one_warm(C.addressof(params), inputs[b:b + 1].ctypes.data, None if ui is None else ui[b].ctypes.data,
                             forces[b].ctypes.data, info[b:b + 1].ctypes.data, tu[b].ctypes.data)
+
+    if threads > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(threads) as pool:
+            list(pool.map(one, range(B)))
+    else:
+        for b in range(B):
+            one(b)
     return forces, info, tu
 
 

@@ -668,8 +668,10 @@ template <class PT>
 QL_FN void initial_rows(const PT& P, const double cr[18], double uz, double s0[6], double rc0[6]) {
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    double c0 = cr[3 * i + 2] * uz;
-    if (i == 4) c0 += -P.fz_max;
+    // (row 4 explicitly fused: whether `cr uz - fz_max` becomes one operation is otherwise the compiler's choice per instantiation,
+    // and the pair form of the backward pass chose differently from the plain form.  It shows where the row's residual is not 0 --
+    // with ONE stance leg, whose reference input carries the whole weight, above fz_max: the forms then parted by 1e-9 N)
+    const double c0 = (i == 4) ? fma(cr[3 * i + 2], uz, -P.fz_max) : cr[3 * i + 2] * uz;
     s0[i] = fmax(-c0, 1.0);
     rc0[i] = c0 + s0[i];
   }
@@ -1087,7 +1089,13 @@ QL_FN void pass_A(const PT& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K,
         if (2 * rd >= pcount) continue;       // wave-uniform
         bool exists;
         const int lm = pair_point(rd, exists);
-        const bool on_m = exists && ((st.con >> lm) & 1u);
+        // The partner lanes share one column of the workspace.  In the last round of an ODD number of stance points the upper
+        // lane has no point of its own and shadows the lower lane's: it must then form the lower lane's update too, so that the
+        // two stores of a row carry the same value -- storing back what it read would undo the lower lane's step whenever its
+        // store lands last (the iterate then never moves: every instance of such a wavefront ran into the iteration limit).
+        // on_p: this lane forms the point's update; on_m: ... and the point counts in this lane's share of the sums.
+        const bool on_p = (st.con >> lm) & 1u;
+        const bool on_m = exists && on_p;
         const unsigned pa_ = (plist >> (8 * rd)) & 0xFu, pb_ = (plist >> (8 * rd + 4)) & 0xFu;
         const bool on_lo = (st.con >> pa_) & 1u, on_hi = pb_ != 0xFu && ((st.con >> (pb_ & 3u)) & 1u);
         const bool more = 2 * (rd + 1) < pcount;      // another round of this knot follows
@@ -1122,7 +1130,7 @@ QL_FN void pass_A(const PT& P, const Ctx& c, const WsOff& O, const LaneK<NL>& K,
             bool ex;
             fetch_ahead<NL, true>(c, O, more ? k : kn, pair_point(more ? rd + 1 : 0, ex), R, fp, rcrows);
           }
-          if (on_m) {
+          if (on_p) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
               const double jd = cr[3 * i] * du[0] + cr[3 * i + 1] * du[1] + cr[3 * i + 2] * du[2];
