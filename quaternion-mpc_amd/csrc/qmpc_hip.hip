@@ -189,7 +189,12 @@ struct qmpc_handle {
   int* d_handoff;              // straggler hand-off: count | list of instances the capped lane launch left (on first use)
   double* d_hstate;            // ... and their state records (hstate_cap of them)
   int hstate_cap;
-  int handoff_failed;          // 1: the hand-off records could not be allocated -- this handle runs the pure lane kernel (qmpc_query)
+  qmpc_opts opts;              // the run-time settings the planners of the calls with records read (qmpc_plan.h): the policy of
+                               // qmpc_set_instances_policy (default WAVE), handoff_failed (the hand-off records could not be allocated --
+                               // this handle runs the pure lane kernel, qmpc_query), the opt-ins of qmpc_set_loop_warm_records (the loops
+                               // with controller records accept lp->warm_start) and qmpc_set_convex_records (the loops with records accept
+                               // this ConvexMpc handle; then d_outcome is also the scratch the outcome step of a call without outcome
+                               // records runs on)
   int last_kernel;             // QMPC_KERNEL_* of the most recent solve launch (qmpc_query)
   // host-buffer calls (qmpc_solve*, qmpc_solve_async): pinned staging owned by the handle.  Batches below the lane kernel's
   // threshold are solved ZERO-COPY: the wavefront of an instance reads its 384-byte record from pinned host memory with its
@@ -203,16 +208,12 @@ struct qmpc_handle {
                                // not refilled before the stream has drained (qmpc_solve_async with a pageable `in`, pinned outputs)
   unsigned char* d_inst;       // per-instance parameters (qmpc_solve_instances*), on first use: [max_batch] DevParams | [max_batch]
                                // qmpc_instance_params (staging of the host-buffer call) | [max_batch] int verdicts
-  int inst_policy;             // qmpc_instances_policy of qmpc_solve_instances* (qmpc_set_instances_policy; default WAVE)
-  double* d_lane_prm;          // ... under AUTO: the resident wavefronts' parameter blocks [LPR_ROWS][lane_slots], on first use
+  double* d_lane_prm;          // ... under QMPC_INSTANCES_AUTO: the resident wavefronts' parameter blocks [LPR_ROWS][lane_slots], on first use
   unsigned char* d_plant;      // per-robot plants of qmpc_loop_run_instances*, on first use: [max_batch] PlantDev | [max_batch]
                                // qmpc_plant_params (staging of the host-buffer call)
   qmpc_loop_outcome* d_outcome;   // staging of qmpc_loop_run_outcomes (the host-buffer call), on its first use: [max_batch] records
   qmpc_push_params* d_push;       // staging of qmpc_loop_run_pushes (the host-buffer call), on its first use: [max_batch][push_cap]
   int push_cap;                   // ... windows per robot it holds (grown when a call brings more)
-  int loop_warm_rec;              // qmpc_set_loop_warm_records: 1 the loops with controller records accept lp->warm_start (default 0)
-  int convex_rec;                 // qmpc_set_convex_records: 1 the loops with records accept this ConvexMpc handle (default 0); then
-                                  // d_outcome is also the scratch the outcome step of a call without outcome records runs on
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -390,6 +391,7 @@ qmpc_status qmpc_create(const qmpc_params* params, int32_t max_batch, int32_t de
   qmpc_handle* h = new (std::nothrow) qmpc_handle();
   if (!h) return QMPC_HIP_ERROR;
   std::memset(h, 0, sizeof *h);
+  h->opts = qmpc_opts();
   h->params = *params;
   h->dev = d;
   h->device = device;
@@ -472,7 +474,7 @@ static qmpc_status ensure_lane_buffers(qmpc_handle* h) {
 // qmpc_destroy, like the lane kernel's workspace).  If the memory is not there the hand-off is switched off for this handle.
 static bool ensure_handoff_buffers(qmpc_handle* h) {
   if (h->d_handoff) return true;
-  if (h->handoff_failed) return false;
+  if (h->opts.handoff_failed) return false;
   h->hstate_cap = h->max_batch;
   const size_t rec_bytes = sizeof(double) * qmpc_lane_handoff_record_doubles(h->params.horizon);
   if (hipMalloc(&h->d_handoff, qmpc_lane_handoff_list_bytes(h->max_batch)) != hipSuccess ||
@@ -484,7 +486,7 @@ static bool ensure_handoff_buffers(qmpc_handle* h) {
                  (rec_bytes * (size_t)h->hstate_cap) >> 20, hipGetErrorString(hipGetLastError()));
     if (h->d_handoff) (void)hipFree(h->d_handoff);
     h->d_handoff = nullptr; h->d_hstate = nullptr;
-    h->handoff_failed = 1;
+    h->opts.handoff_failed = true;
     return false;
   }
   return true;
@@ -516,14 +518,14 @@ static qmpc_status launch_solve(qmpc_handle* h, int32_t batch, const qmpc_input*
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;   // the gains workspace is sized by max_batch
   const bool timed = kind == QMPC_CALL_PLAIN;
   if (timed) HIP_TRY(hipEventRecord(h->ev0, s));
-  qmpc_plan p = plan(h->sel, batch, kind, d_info != nullptr, h->handoff_failed);
+  qmpc_plan p = plan(h->sel, batch, kind, d_info != nullptr, h->opts.handoff_failed);
   const bool ref = h->params.mode == QMPC_MODE_REFERENCE;
   double* gws = p.gws ? h->d_gws : nullptr;
   if (p.variant == 4) {
     const qmpc_status es = ensure_lane_buffers(h);
     if (es != QMPC_OK) return es;
     // (the hand-off records are allocated on first use; without them the pure lane kernel)
-    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan(h->sel, batch, kind, true, h->handoff_failed);
+    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan(h->sel, batch, kind, true, h->opts.handoff_failed);
     const qmpc_status ls = launch_lane(h, p, batch, d_in, d_forces, d_info, s, nullptr, d_tu, 0, d_tx, h->sel.handoff_restart);
     if (ls != QMPC_OK) return ls;
   } else if (p.variant >= 3) {      // the wrench-form kernels (qmpc_wform.hip)
@@ -657,7 +659,7 @@ static qmpc_status solve_host(qmpc_handle* h, int32_t batch, const qmpc_input* i
   const size_t fbytes = sizeof(double) * nu * (size_t)batch, ibytes = sizeof(qmpc_info) * (size_t)batch;
   if (traj_u && !h->d_traj_u) HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * nu * N * (size_t)h->max_batch));
   if (traj_x && !h->d_traj_x) HIP_TRY(hipMalloc(&h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch));
-  const bool lane = plan(h->sel, batch, QMPC_CALL_PLAIN, true, h->handoff_failed).variant == 4;
+  const bool lane = plan(h->sel, batch, QMPC_CALL_PLAIN, true, h->opts.handoff_failed).variant == 4;
   if (h->zero_copy && !lane) {
     void *din = nullptr, *df = nullptr, *di = nullptr;
     const int k_in = pointer_kind(in, &din), k_f = pointer_kind(forces_body, &df), k_i = info ? pointer_kind(info, &di) : 1;
@@ -710,7 +712,7 @@ qmpc_status qmpc_solve_warm_device(qmpc_handle* h, int32_t batch, const qmpc_inp
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const qmpc_plan p = plan(h->sel, batch, QMPC_CALL_WARM, true, h->handoff_failed);
+  const qmpc_plan p = plan(h->sel, batch, QMPC_CALL_WARM, true, h->opts.handoff_failed);
   if (p.variant == 4) {      // large batches: the lane-per-instance kernel, same start rule
     const qmpc_status es = ensure_lane_buffers(h);
     if (es != QMPC_OK) return es;
@@ -824,51 +826,45 @@ void qmpc_host_free(void* p) {
 
 // the handle hands the stragglers of capped lane launches over (plain solves, cold- or warm-started loops)
 static bool handoff_active(const qmpc_handle* h) {
-  return lane_cap(h->sel, QMPC_CALL_PLAIN, h->handoff_failed) || lane_cap(h->sel, QMPC_CALL_LOOP_TICK, h->handoff_failed) ||
-         lane_cap(h->sel, QMPC_CALL_WARM_LOOP_TICK, h->handoff_failed);
+  return lane_cap(h->sel, QMPC_CALL_PLAIN, h->opts.handoff_failed) || lane_cap(h->sel, QMPC_CALL_LOOP_TICK, h->opts.handoff_failed) ||
+         lane_cap(h->sel, QMPC_CALL_WARM_LOOP_TICK, h->opts.handoff_failed);
+}
+
+static qmpc_status ensure_instance_buffers(qmpc_handle* h);
+static qmpc_status ensure_lane_inst_buffers(qmpc_handle* h, bool handoff);
+static qmpc_status ensure_plant_buffers(qmpc_handle* h);
+// the buffers of a call with per-instance records where `p` plans it on the lane kernel (QMPC_INSTANCES_AUTO): the per-instance
+// blocks, for a loop the plant blocks, the lane kernel's buffers and, where the plan hands stragglers over, the hand-off records
+static qmpc_status prepare_lane_inst(qmpc_handle* h, const qmpc_plan& p, bool loop) {
+  if (p.variant != 4) return QMPC_OK;
+  qmpc_status es = ensure_instance_buffers(h);
+  if (es == QMPC_OK && loop) es = ensure_plant_buffers(h);
+  if (es == QMPC_OK) es = ensure_lane_inst_buffers(h, p.iter_cap != 0);
+  return es;
 }
 
 // Everything a solve of `batch` instances will need, allocated NOW: the lane kernel's workspace and sort scratch, the
 // hand-off records, the pinned staging of the host-buffer calls.  Afterwards no solve of up to `batch` instances allocates
 // (safe inside the caller's own stream capture) and qmpc_query(QMPC_QUERY_HANDOFF_ACTIVE) says which family of roundings
 // the handle's large-batch results belong to.
-static qmpc_status ensure_instance_buffers(qmpc_handle* h);
-static qmpc_status ensure_lane_inst_buffers(qmpc_handle* h, bool handoff);
-static qmpc_status ensure_plant_buffers(qmpc_handle* h);
 qmpc_status qmpc_prepare(qmpc_handle* h, int32_t batch) {
   if (!h || batch < 1) return QMPC_BAD_ARGUMENT;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
   HIP_TRY(hipSetDevice(h->device));
   // the lane kernel's buffers where a plain solve or a cold-started loop's tick of this size takes it; the hand-off records
   // wherever the handle hands stragglers over at all
-  if (plan(h->sel, batch, QMPC_CALL_PLAIN, true, h->handoff_failed).variant == 4 ||
-      plan(h->sel, batch, QMPC_CALL_LOOP_TICK, true, h->handoff_failed).variant == 4) {
+  if (plan(h->sel, batch, QMPC_CALL_PLAIN, true, h->opts.handoff_failed).variant == 4 ||
+      plan(h->sel, batch, QMPC_CALL_LOOP_TICK, true, h->opts.handoff_failed).variant == 4) {
     const qmpc_status es = ensure_lane_buffers(h);
     if (es != QMPC_OK) return es;
     if (handoff_active(h)) (void)ensure_handoff_buffers(h);
   }
-  // ... and for qmpc_solve_instances* of this size under QMPC_INSTANCES_AUTO, with the per-instance buffers
-  if (h->inst_policy == QMPC_INSTANCES_AUTO && plan_instances(h->sel, batch, h->inst_policy, true, h->handoff_failed).variant == 4) {
-    qmpc_status es = ensure_instance_buffers(h);
-    if (es == QMPC_OK) es = ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_PLAIN, h->handoff_failed) != 0);
-    if (es != QMPC_OK) return es;
-  }
-  // ... and for the ticks of qmpc_loop_run_instances* / qmpc_loop_run_outcomes* with controller records, with the plant blocks
-  if (h->inst_policy == QMPC_INSTANCES_AUTO &&
-      plan_loop_instances(h->sel, batch, true, false, h->inst_policy, h->handoff_failed).variant == 4) {
-    qmpc_status es = ensure_instance_buffers(h);
-    if (es == QMPC_OK) es = ensure_plant_buffers(h);
-    if (es == QMPC_OK) es = ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_LOOP_TICK, h->handoff_failed) != 0);
-    if (es != QMPC_OK) return es;
-  }
-  // ... and for their warm-started ticks on a handle that opted in (qmpc_set_loop_warm_records)
-  if (h->loop_warm_rec && h->inst_policy == QMPC_INSTANCES_AUTO &&
-      plan_loop_instances(h->sel, batch, true, true, h->inst_policy, h->handoff_failed, true).variant == 4) {
-    qmpc_status es = ensure_instance_buffers(h);
-    if (es == QMPC_OK) es = ensure_plant_buffers(h);
-    if (es == QMPC_OK) es = ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_WARM_LOOP_TICK, h->handoff_failed) != 0);
-    if (es != QMPC_OK) return es;
-  }
+  // ... and where qmpc_solve_instances* of this size or the ticks of qmpc_loop_run_instances* / qmpc_loop_run_outcomes* with
+  // controller records (cold-started; warm-started on a handle that opted in) take the lane kernel with per-lane parameters
+  qmpc_status ps = prepare_lane_inst(h, plan_instances(h->sel, h->opts, batch, /*has_info=*/true), false);
+  for (int warm = 0; warm < 2 && ps == QMPC_OK; ++warm)
+    ps = prepare_lane_inst(h, plan_loop_instances(h->sel, h->opts, batch, /*has_ctrl=*/true, warm != 0), true);
+  if (ps != QMPC_OK) return ps;
   // the pinned staging of the host-buffer calls: ALWAYS (a handle prepared for a lane-kernel batch may still be handed a smaller
   // batch on host buffers, which runs zero-copy), and the buffers the closed loops and the trajectory / warm-started calls
   // otherwise allocate on first use -- nothing of that may happen inside a caller's stream capture
@@ -926,11 +922,18 @@ static int* inst_status(qmpc_handle* h) {
   return reinterpret_cast<int*>(h->d_inst + (sizeof(DevParams) + sizeof(qmpc_instance_params)) * (size_t)h->max_batch);
 }
 
+// The solves with per-instance parameters come in two models, QuatMpc's (qmpc_solve_instances*) and ConvexMpc's
+// (qmpc_convex_solve_instances*; qmpc_wform_cinst.hip: qmpc_solve_cw_inst_kernel).  The records, the expansion kernel and the
+// handle's per-instance buffers are the same: apply_instance_params writes the record's fields into the handle's DevParams
+// whatever the model.  `convex` says which of the two a call is; the plan of a call:
+static qmpc_plan plan_inst_call(const qmpc_handle* h, bool convex, int batch, bool has_info) {
+  return convex ? plan_convex_instances(h->sel, batch) : plan_instances(h->sel, h->opts, batch, has_info);
+}
 // the call-level checks both entry points share (after the null-pointer ones)
-static qmpc_status instances_check(const qmpc_handle* h, int32_t batch) {
-  if (h->params.model != QMPC_MODEL_QUAT || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
+static qmpc_status instances_check(const qmpc_handle* h, bool convex, int32_t batch) {
+  if (h->params.model != (convex ? QMPC_MODEL_CONVEX : QMPC_MODEL_QUAT) || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
-  if (batch > 0 && plan_instances(h->sel, batch).family == QMPC_KERNEL_NONE) return QMPC_UNSUPPORTED;
+  if (batch > 0 && plan_inst_call(h, convex, batch, true).family == QMPC_KERNEL_NONE) return QMPC_UNSUPPORTED;
   return QMPC_OK;
 }
 
@@ -944,57 +947,97 @@ static qmpc_status ensure_lane_inst_buffers(qmpc_handle* h, bool handoff) {
   return QMPC_OK;
 }
 // some batch of the handle takes the lane kernel in qmpc_solve_instances* under its current policy
-static bool instances_lane_possible(const qmpc_handle* h) {
-  return plan_instances(h->sel, h->max_batch, h->inst_policy, true, h->handoff_failed).variant == 4;
+static bool instances_lane_possible(const qmpc_handle* h) { return plan_instances(h->sel, h->opts, h->max_batch, true).variant == 4; }
+
+// The solve of one call or tick with per-instance parameters, as `p` plans it (the blocks expanded and the buffers allocated
+// already): d_in -> d_forces, d_info, and the trajectories where tu / tx are given.  Nothing here but kernels, the plain call's
+// parameter upload and the hand-off counter's memset, so a tick can be captured.
+//   INST_CALL        qmpc_solve_instances* / qmpc_convex_solve_instances*
+//   INST_TICK_COLD   a tick of a cold-started loop with controller records
+//   INST_TICK_FIRST  the cold first tick of a warm-started one (p: the plan with `first`), leaving its solution in tu
+//   INST_TICK_WARM   ... its later ticks: the warm-started kernels start from tu (a robot whose previous solve failed starts cold:
+//                    check_prev) and leave theirs there
+// The wave form: the per-instance wrench-form kernel of the model.  The lane form (QuatMpc): the sort -- the plain call's by
+// stance mask, the loops' also by the previous records' iteration classes, robots that will not solve last --, the lane kernel
+// with per-lane parameters to the cap, the per-instance list kernel on what it leaves (a warm tick's records carry the rows'
+// initial residuals, so only the cold forms honour QMPC_HANDOFF_RESTART).  The plain call uploads the lane kernel's parameter
+// block just before its launch; the loops upload it once per call, outside the capture.
+enum inst_form { INST_CALL, INST_TICK_COLD, INST_TICK_FIRST, INST_TICK_WARM };
+static qmpc_status inst_solve(qmpc_handle* h, const qmpc_plan& p, bool convex, inst_form form, int32_t batch, const qmpc_input* d_in,
+                              double* d_forces, qmpc_info* d_info, double* tu, double* tx, hipStream_t s) {
+  const bool warm = form == INST_TICK_WARM;
+  double* gws = p.gws ? h->d_gws : nullptr;
+  if (p.variant == 4) {
+    const bool cap = p.iter_cap > 0;
+    const int* perm = h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr;
+    int *hcount = cap ? h->d_handoff : nullptr, *hsel = cap ? h->d_handoff + 64 : nullptr;
+    double* hstate = cap ? h->d_hstate : nullptr;
+    if (h->sel.lane_sort && form == INST_CALL) HIP_TRY(qmpc_lane_sort_launch((int)batch, s, d_in, h->d_lane_scratch));
+    if (h->sel.lane_sort && form != INST_CALL)
+      HIP_TRY(qmpc_lane_inst_sort_loop_launch((int)batch, s, d_in, p.order_prev ? d_info : nullptr, inst_status(h), h->sel.lane_sort_idle,
+                                              h->d_lane_scratch));
+    if (warm)
+      HIP_TRY(qmpc_lane_inst_warm_launch_only(h->lane_pslot, (int)batch, s, d_in, inst_dev(h), inst_status(h), d_forces, d_info, h->d_lane_ws,
+                                              h->d_lane_prm, h->lane_slots, perm, tu, tu, /*check_prev=*/1, p.iter_cap, hcount, hsel, hstate,
+                                              h->hstate_cap, h->sel.lane_pair));
+    else if (form == INST_CALL)
+      HIP_TRY(qmpc_lane_inst_launch(h->lane_pslot, (int)batch, s, &h->dev, sizeof h->dev, d_in, inst_dev(h), inst_status(h), d_forces, d_info,
+                                    h->d_lane_ws, h->d_lane_prm, h->lane_slots, perm, tu, tx, p.iter_cap, hcount, hsel, hstate, h->hstate_cap,
+                                    h->sel.lane_pair));
+    else
+      HIP_TRY(qmpc_lane_inst_launch_only(h->lane_pslot, (int)batch, s, d_in, inst_dev(h), inst_status(h), d_forces, d_info, h->d_lane_ws,
+                                         h->d_lane_prm, h->lane_slots, perm, tu, tx, p.iter_cap, hcount, hsel, hstate, h->hstate_cap,
+                                         h->sel.lane_pair));
+    if (cap)
+      HIP_TRY(qmpc_wform_inst_list_launch(p.handoff_variant, p.handoff_grid, p.lds, s, inst_dev(h), d_in, d_forces, d_info, tu, tx, hsel, hcount,
+                                          gws, (warm || !h->sel.handoff_restart) ? h->d_hstate : nullptr, h->hstate_cap));
+  } else if (convex) {
+    HIP_TRY(qmpc_wform_cinst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, d_forces, d_info, tu, tx, gws));
+  } else if (warm) {
+    HIP_TRY(qmpc_wform_inst_warm_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, tu, d_forces, d_info, tu, gws,
+                                        /*check_prev=*/1));
+  } else {
+    HIP_TRY(qmpc_wform_inst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, d_forces, d_info, tu, tx, gws));
+  }
+  h->last_kernel = p.family;
+  return QMPC_OK;
 }
 
-// expansion kernel + solve kernel on stream s; d_rec: the records in device-addressable memory
-static qmpc_status launch_instances(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_rec,
+// expansion kernel + solve on stream s; d_rec: the records in device-addressable memory
+static qmpc_status launch_instances(qmpc_handle* h, bool convex, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_rec,
                                     double* d_forces, qmpc_info* d_info, double* d_tu, double* d_tx, hipStream_t s) {
-  qmpc_plan p = plan_instances(h->sel, batch, h->inst_policy, d_info != nullptr, h->handoff_failed);
+  qmpc_plan p = plan_inst_call(h, convex, batch, d_info != nullptr);
   const qmpc_status es = ensure_instance_buffers(h);
   if (es != QMPC_OK) return es;
   if (p.variant == 4) {
     const qmpc_status ls = ensure_lane_inst_buffers(h, false);
     if (ls != QMPC_OK) return ls;
     // (the hand-off records are allocated on first use; without them the pure lane kernel)
-    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan_instances(h->sel, batch, h->inst_policy, true, h->handoff_failed);
+    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan_inst_call(h, convex, batch, true);
   }
   HIP_TRY(hipEventRecord(h->ev0, s));
   HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_rec, inst_dev(h), inst_status(h)));
-  if (p.variant == 4) {      // expansion, stance sort, the capped lane kernel, the per-instance list kernel: stream-ordered
-    const bool cap = p.iter_cap > 0;
-    if (h->sel.lane_sort) HIP_TRY(qmpc_lane_sort_launch((int)batch, s, d_in, h->d_lane_scratch));
-    HIP_TRY(qmpc_lane_inst_launch(h->lane_pslot, (int)batch, s, &h->dev, sizeof h->dev, d_in, inst_dev(h), inst_status(h), d_forces, d_info,
-                                  h->d_lane_ws, h->d_lane_prm, h->lane_slots, h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr, d_tu, d_tx,
-                                  p.iter_cap, cap ? h->d_handoff : nullptr, cap ? h->d_handoff + 64 : nullptr, cap ? h->d_hstate : nullptr,
-                                  h->hstate_cap, h->sel.lane_pair));
-    if (cap)
-      HIP_TRY(qmpc_wform_inst_list_launch(p.handoff_variant, p.handoff_grid, p.lds, s, inst_dev(h), d_in, d_forces, d_info, d_tu, d_tx,
-                                          h->d_handoff + 64, h->d_handoff, p.gws ? h->d_gws : nullptr,
-                                          h->sel.handoff_restart ? nullptr : h->d_hstate, h->hstate_cap));
-  } else
-  HIP_TRY(qmpc_wform_inst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, d_forces, d_info, d_tu, d_tx,
-                                       p.gws ? h->d_gws : nullptr));
-  h->last_kernel = p.family;
+  const qmpc_status st = inst_solve(h, p, convex, INST_CALL, batch, d_in, d_forces, d_info, d_tu, d_tx, s);
+  if (st != QMPC_OK) return st;
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
   return QMPC_OK;
 }
 
-qmpc_status qmpc_solve_instances_device(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_iparams,
-                                        double* d_forces_body, qmpc_info* d_info, void* stream) {
-  if (!h || batch < 0 || (batch > 0 && (!d_in || !d_iparams || !d_forces_body))) return QMPC_BAD_ARGUMENT;
-  const qmpc_status cs = instances_check(h, batch);
+// the device-buffer entry points after their null-pointer checks
+static qmpc_status solve_instances_device(qmpc_handle* h, bool convex, int32_t batch, const qmpc_input* d_in,
+                                          const qmpc_instance_params* d_iparams, double* d_forces, qmpc_info* d_info, void* stream) {
+  const qmpc_status cs = instances_check(h, convex, batch);
   if (cs != QMPC_OK || batch == 0) return cs;
   HIP_TRY(hipSetDevice(h->device));
-  return launch_instances(h, batch, d_in, d_iparams, d_forces_body, d_info, nullptr, nullptr, stream ? (hipStream_t)stream : h->stream);
+  return launch_instances(h, convex, batch, d_in, d_iparams, d_forces, d_info, nullptr, nullptr, stream ? (hipStream_t)stream : h->stream);
 }
 
-qmpc_status qmpc_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_input* in, const qmpc_instance_params* iparams,
-                                 double* forces_body, qmpc_info* info, double* traj_u, double* traj_x) {
-  if (!h || batch < 0 || (batch > 0 && (!in || !iparams || !forces_body))) return QMPC_BAD_ARGUMENT;
-  const qmpc_status cs = instances_check(h, batch);
+// ... and the host-buffer ones.  The trajectory buffers are sized as every call of the handle sizes them (rows of 13 hold
+// ConvexMpc's rows of 12); the copy-out of traj_x is the model's: 13 (N + 1) doubles per instance, ConvexMpc 12 (N + 1).
+static qmpc_status solve_instances_host(qmpc_handle* h, bool convex, int32_t batch, const qmpc_input* in, const qmpc_instance_params* iparams,
+                                        double* forces, qmpc_info* info, double* traj_u, double* traj_x) {
+  const qmpc_status cs = instances_check(h, convex, batch);
   if (cs != QMPC_OK || batch == 0) return cs;
   HIP_TRY(hipSetDevice(h->device));
   // an earlier qmpc_solve_async was never waited for: complete it first (it owes a pageable caller its copy-out)
@@ -1003,120 +1046,75 @@ qmpc_status qmpc_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_input
     finish_pending(h);
     h->stage_in_busy = 0;
   }
-  const int N = h->params.horizon;
+  const int N = h->params.horizon, nx = convex ? 12 : 13;
   const qmpc_status es = ensure_instance_buffers(h);
   if (es != QMPC_OK) return es;
   if (traj_u && !h->d_traj_u) HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * N * (size_t)h->max_batch));
   if (traj_x && !h->d_traj_x) HIP_TRY(hipMalloc(&h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch));
   HIP_TRY(hipMemcpyAsync(h->d_in, in, sizeof(qmpc_input) * (size_t)batch, hipMemcpyDefault, h->stream));
   HIP_TRY(hipMemcpyAsync(inst_rec(h), iparams, sizeof(qmpc_instance_params) * (size_t)batch, hipMemcpyDefault, h->stream));
-  const qmpc_status st = launch_instances(h, batch, h->d_in, inst_rec(h), h->d_forces, h->d_info, traj_u ? h->d_traj_u : nullptr,
+  const qmpc_status st = launch_instances(h, convex, batch, h->d_in, inst_rec(h), h->d_forces, h->d_info, traj_u ? h->d_traj_u : nullptr,
                                           traj_x ? h->d_traj_x : nullptr, h->stream);
   if (st != QMPC_OK) return st;
-  HIP_TRY(hipMemcpyAsync(forces_body, h->d_forces, sizeof(double) * 12 * (size_t)batch, hipMemcpyDefault, h->stream));
+  HIP_TRY(hipMemcpyAsync(forces, h->d_forces, sizeof(double) * 12 * (size_t)batch, hipMemcpyDefault, h->stream));
   if (info) HIP_TRY(hipMemcpyAsync(info, h->d_info, sizeof(qmpc_info) * (size_t)batch, hipMemcpyDefault, h->stream));
   if (traj_u) HIP_TRY(hipMemcpyAsync(traj_u, h->d_traj_u, sizeof(double) * 12 * N * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
-  if (traj_x) HIP_TRY(hipMemcpyAsync(traj_x, h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  if (traj_x) HIP_TRY(hipMemcpyAsync(traj_x, h->d_traj_x, sizeof(double) * nx * (N + 1) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return QMPC_OK;
 }
 
-// ---- ... for ConvexMpc's problem (converged mode; qmpc_wform_cinst.hip: qmpc_solve_cw_inst_kernel) ---------------------------
-// The records, the expansion kernel and the handle's per-instance buffers are those above: apply_instance_params writes the
-// record's fields into the handle's DevParams whatever the model.
-static qmpc_status convex_instances_check(const qmpc_handle* h, int32_t batch) {
-  if (h->params.model != QMPC_MODEL_CONVEX || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
-  if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
-  if (batch > 0 && plan_convex_instances(h->sel, batch).family == QMPC_KERNEL_NONE) return QMPC_UNSUPPORTED;
-  return QMPC_OK;
+qmpc_status qmpc_solve_instances_device(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_iparams,
+                                        double* d_forces_body, qmpc_info* d_info, void* stream) {
+  if (!h || batch < 0 || (batch > 0 && (!d_in || !d_iparams || !d_forces_body))) return QMPC_BAD_ARGUMENT;
+  return solve_instances_device(h, false, batch, d_in, d_iparams, d_forces_body, d_info, stream);
 }
 
-static qmpc_status launch_convex_instances(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_rec,
-                                           double* d_forces, qmpc_info* d_info, double* d_tu, double* d_tx, hipStream_t s) {
-  const qmpc_plan p = plan_convex_instances(h->sel, batch);
-  const qmpc_status es = ensure_instance_buffers(h);
-  if (es != QMPC_OK) return es;
-  HIP_TRY(hipEventRecord(h->ev0, s));
-  HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_rec, inst_dev(h), inst_status(h)));
-  HIP_TRY(qmpc_wform_cinst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, d_forces, d_info, d_tu, d_tx,
-                                        p.gws ? h->d_gws : nullptr));
-  h->last_kernel = p.family;
-  HIP_TRY(hipEventRecord(h->ev1, s));
-  h->timed = true;
-  return QMPC_OK;
+qmpc_status qmpc_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_input* in, const qmpc_instance_params* iparams,
+                                 double* forces_body, qmpc_info* info, double* traj_u, double* traj_x) {
+  if (!h || batch < 0 || (batch > 0 && (!in || !iparams || !forces_body))) return QMPC_BAD_ARGUMENT;
+  return solve_instances_host(h, false, batch, in, iparams, forces_body, info, traj_u, traj_x);
 }
 
 qmpc_status qmpc_convex_solve_instances_device(qmpc_handle* h, int32_t batch, const qmpc_convex_input* d_in,
                                                const qmpc_instance_params* d_iparams, double* d_forces_world, qmpc_info* d_info,
                                                void* stream) {
   if (!h || batch < 0 || (batch > 0 && (!d_in || !d_iparams || !d_forces_world))) return QMPC_BAD_ARGUMENT;
-  const qmpc_status cs = convex_instances_check(h, batch);
-  if (cs != QMPC_OK || batch == 0) return cs;
-  HIP_TRY(hipSetDevice(h->device));
-  return launch_convex_instances(h, batch, reinterpret_cast<const qmpc_input*>(d_in), d_iparams, d_forces_world, d_info, nullptr, nullptr,
-                                 stream ? (hipStream_t)stream : h->stream);
+  return solve_instances_device(h, true, batch, reinterpret_cast<const qmpc_input*>(d_in), d_iparams, d_forces_world, d_info, stream);
 }
 
 qmpc_status qmpc_convex_solve_instances(qmpc_handle* h, int32_t batch, const qmpc_convex_input* in, const qmpc_instance_params* iparams,
                                         double* forces_world, qmpc_info* info, double* traj_u, double* traj_x) {
   if (!h || batch < 0 || (batch > 0 && (!in || !iparams || !forces_world))) return QMPC_BAD_ARGUMENT;
-  const qmpc_status cs = convex_instances_check(h, batch);
-  if (cs != QMPC_OK || batch == 0) return cs;
-  HIP_TRY(hipSetDevice(h->device));
-  // an earlier non-blocking call was never waited for: complete it first (it owes a pageable caller its copy-out)
-  if (h->pending.forces || h->pending.info || h->stage_in_busy) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    finish_pending(h);
-    h->stage_in_busy = 0;
-  }
-  const int N = h->params.horizon;
-  const qmpc_status es = ensure_instance_buffers(h);
-  if (es != QMPC_OK) return es;
-  // (the trajectory buffers are sized as every call of the handle sizes them: rows of 13 hold ConvexMpc's rows of 12)
-  if (traj_u && !h->d_traj_u) HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * N * (size_t)h->max_batch));
-  if (traj_x && !h->d_traj_x) HIP_TRY(hipMalloc(&h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch));
-  HIP_TRY(hipMemcpyAsync(h->d_in, in, sizeof(qmpc_input) * (size_t)batch, hipMemcpyDefault, h->stream));
-  HIP_TRY(hipMemcpyAsync(inst_rec(h), iparams, sizeof(qmpc_instance_params) * (size_t)batch, hipMemcpyDefault, h->stream));
-  const qmpc_status st = launch_convex_instances(h, batch, h->d_in, inst_rec(h), h->d_forces, h->d_info, traj_u ? h->d_traj_u : nullptr,
-                                                 traj_x ? h->d_traj_x : nullptr, h->stream);
-  if (st != QMPC_OK) return st;
-  HIP_TRY(hipMemcpyAsync(forces_world, h->d_forces, sizeof(double) * 12 * (size_t)batch, hipMemcpyDefault, h->stream));
-  if (info) HIP_TRY(hipMemcpyAsync(info, h->d_info, sizeof(qmpc_info) * (size_t)batch, hipMemcpyDefault, h->stream));
-  if (traj_u) HIP_TRY(hipMemcpyAsync(traj_u, h->d_traj_u, sizeof(double) * 12 * N * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
-  if (traj_x) HIP_TRY(hipMemcpyAsync(traj_x, h->d_traj_x, sizeof(double) * 12 * (N + 1) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return QMPC_OK;
+  return solve_instances_host(h, true, batch, reinterpret_cast<const qmpc_input*>(in), iparams, forces_world, info, traj_u, traj_x);
 }
 
 qmpc_status qmpc_prepare_instances(qmpc_handle* h) {
   if (!h) return QMPC_BAD_ARGUMENT;
-  if (convex_instances_check(h, 0) == QMPC_OK) {      // ConvexMpc: the per-instance buffers (no lane form)
-    HIP_TRY(hipSetDevice(h->device));
-    return ensure_instance_buffers(h);
-  }
-  const qmpc_status cs = instances_check(h, 0);
+  const bool convex = h->params.model == QMPC_MODEL_CONVEX;      // ConvexMpc: the per-instance buffers (no lane form)
+  const qmpc_status cs = instances_check(h, convex, 0);
   if (cs != QMPC_OK) return cs;
   HIP_TRY(hipSetDevice(h->device));
   const qmpc_status es = ensure_instance_buffers(h);
   if (es != QMPC_OK || !instances_lane_possible(h)) return es;
-  return ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_PLAIN, h->handoff_failed) != 0);
+  return ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_PLAIN, h->opts.handoff_failed) != 0);
 }
 
 qmpc_status qmpc_set_instances_policy(qmpc_handle* h, int32_t policy) {
   if (!h || (policy != QMPC_INSTANCES_WAVE && policy != QMPC_INSTANCES_AUTO)) return QMPC_BAD_ARGUMENT;
-  h->inst_policy = policy;
+  h->opts.inst_policy = policy;
   return QMPC_OK;
 }
 
 qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on) {
   if (!h || (on != 0 && on != 1)) return QMPC_BAD_ARGUMENT;
-  h->loop_warm_rec = on;
+  h->opts.loop_warm_records = on != 0;
   return QMPC_OK;
 }
 
 qmpc_status qmpc_set_convex_records(qmpc_handle* h, int32_t on) {
   if (!h || (on != 0 && on != 1)) return QMPC_BAD_ARGUMENT;
-  h->convex_rec = on;
+  h->opts.convex_records = on != 0;
   return QMPC_OK;
 }
 
@@ -1126,14 +1124,14 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
     case QMPC_QUERY_HANDOFF_ACTIVE:      // 1: capped lane launches hand their stragglers over; 0: pure lane kernel (off, or allocation failed)
       *value = handoff_active(h) ? 1 : 0;
       return QMPC_OK;
-    case QMPC_QUERY_HANDOFF_ALLOC_FAILED: *value = h->handoff_failed; return QMPC_OK;
+    case QMPC_QUERY_HANDOFF_ALLOC_FAILED: *value = h->opts.handoff_failed; return QMPC_OK;
     case QMPC_QUERY_KERNEL_FOR_BATCH:
       if (arg < 1 || arg > h->max_batch) return QMPC_BAD_ARGUMENT;
-      *value = plan(h->sel, (int)arg, QMPC_CALL_PLAIN, true, h->handoff_failed).family;
+      *value = plan(h->sel, (int)arg, QMPC_CALL_PLAIN, true, h->opts.handoff_failed).family;
       return QMPC_OK;
     case QMPC_QUERY_LAST_KERNEL: *value = h->last_kernel; return QMPC_OK;
     case QMPC_QUERY_LANE_CAP:
-      *value = lane_cap(h->sel, arg == 3 ? QMPC_CALL_WARM_LOOP_TICK : (arg == 2 ? QMPC_CALL_LOOP_TICK : QMPC_CALL_PLAIN), h->handoff_failed);
+      *value = lane_cap(h->sel, arg == 3 ? QMPC_CALL_WARM_LOOP_TICK : (arg == 2 ? QMPC_CALL_LOOP_TICK : QMPC_CALL_PLAIN), h->opts.handoff_failed);
       return QMPC_OK;
     case QMPC_QUERY_DEVICE_BYTES: {      // device memory the handle holds right now
       const int N = h->params.horizon, nl = model_nl(h->params.model), nu = 3 * nl;
@@ -1156,19 +1154,18 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
     case QMPC_QUERY_ZERO_COPY: *value = h->zero_copy; return QMPC_OK;
     case QMPC_QUERY_KERNEL_FOR_INSTANCES:
       if (arg < 1 || arg > h->max_batch) return QMPC_BAD_ARGUMENT;
-      *value = plan_instances(h->sel, (int)arg, h->inst_policy, true, h->handoff_failed).family;
+      *value = plan_instances(h->sel, h->opts, (int)arg, true).family;
       return QMPC_OK;
-    case QMPC_QUERY_INSTANCES_POLICY: *value = h->inst_policy; return QMPC_OK;
+    case QMPC_QUERY_INSTANCES_POLICY: *value = h->opts.inst_policy; return QMPC_OK;
     case QMPC_QUERY_LOOP_INSTANCES_PLAN: {
       const int64_t b = arg & 0xffffffffLL;
       if (b < 1 || b > h->max_batch) return QMPC_BAD_ARGUMENT;
-      const qmpc_plan p = plan_loop_instances(h->sel, (int)b, (arg >> 32) & 1, (arg >> 33) & 1, h->inst_policy, h->handoff_failed,
-                                              h->loop_warm_rec != 0, false, h->convex_rec != 0);
+      const qmpc_plan p = plan_loop_instances(h->sel, h->opts, (int)b, (arg >> 32) & 1, (arg >> 33) & 1);
       *value = p.family == QMPC_KERNEL_NONE ? 0 : 16 * (p.fused ? 1 : 2) + p.family;
       return QMPC_OK;
     }
-    case QMPC_QUERY_LOOP_WARM_RECORDS: *value = h->loop_warm_rec; return QMPC_OK;
-    case QMPC_QUERY_CONVEX_RECORDS: *value = h->convex_rec; return QMPC_OK;
+    case QMPC_QUERY_LOOP_WARM_RECORDS: *value = h->opts.loop_warm_records; return QMPC_OK;
+    case QMPC_QUERY_CONVEX_RECORDS: *value = h->opts.convex_records; return QMPC_OK;
     case QMPC_QUERY_KERNEL_FOR_CONVEX_INSTANCES:
       if (arg < 1 || arg > h->max_batch) return QMPC_BAD_ARGUMENT;
       *value = plan_convex_instances(h->sel, (int)arg).family;
@@ -1467,7 +1464,7 @@ void qmpc_loop_state_init(qmpc_loop_state* s, const qmpc_loop_params* lp, const 
 // tick of a warm-started call
 static qmpc_status loop_tick_solve(qmpc_handle* h, int32_t batch, hipStream_t s, bool warm, bool first, bool convex) {
   if (warm) {
-    const qmpc_plan p = plan(h->sel, batch, first ? QMPC_CALL_WARM_LOOP_FIRST : QMPC_CALL_WARM_LOOP_TICK, true, h->handoff_failed);
+    const qmpc_plan p = plan(h->sel, batch, first ? QMPC_CALL_WARM_LOOP_FIRST : QMPC_CALL_WARM_LOOP_TICK, true, h->opts.handoff_failed);
     // the lane kernel hands the stragglers of the warm-started ticks over (not of the cold first one): the records carry the
     // rows' initial residuals
     if (p.variant == 4) {
@@ -1612,7 +1609,7 @@ static qmpc_status loop_run_impl(qmpc_handle* h, const qmpc_loop_params* lp, int
     return QMPC_OK;
   };
   // the persistent kernel (ONE launch for all ticks) or the per-tick launch sequence below (qmpc_plan.h)
-  const qmpc_plan lp_plan = plan(h->sel, batch, warm ? QMPC_CALL_WARM_LOOP : QMPC_CALL_LOOP, true, h->handoff_failed);
+  const qmpc_plan lp_plan = plan(h->sel, batch, warm ? QMPC_CALL_WARM_LOOP : QMPC_CALL_LOOP, true, h->opts.handoff_failed);
   if (lp_plan.fused) {
     HIP_TRY(qmpc_fused_launch(lp_plan.variant, h->params.mode == QMPC_MODE_REFERENCE ? 1 : 0, convex ? 1 : 0, (int)batch, lp_plan.lds, s, &h->dev,
                               sizeof h->dev, &LP, d_states, h->d_in, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, (int)ticks,
@@ -1699,7 +1696,7 @@ void qmpc_plant_params_from(const qmpc_params* p, qmpc_plant_params* out) {
 }
 
 // the handle is ConvexMpc's and opted in to the loops with records (qmpc_set_convex_records): the kernels of qmpc_loop_crec.hip
-static bool convex_records(const qmpc_handle* h) { return h->params.model == QMPC_MODEL_CONVEX && h->convex_rec != 0; }
+static bool convex_records(const qmpc_handle* h) { return h->params.model == QMPC_MODEL_CONVEX && h->opts.convex_records; }
 
 // the call-level checks of both entry points, for a call with at least one kind of record (QMPC_OK: go on)
 static qmpc_status loop_instances_check(const qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, bool has_ctrl) {
@@ -1710,10 +1707,10 @@ static qmpc_status loop_instances_check(const qmpc_handle* h, const qmpc_loop_pa
   // (the device tick of ConvexMpc carries the controller period as the literal 5 ms: loop_run_impl)
   if (crec && h->params.h != (float)(5.0 / 1000.0)) return QMPC_UNSUPPORTED;
   // (controller records with the warm start: on a QuatMpc handle that opted in only, qmpc_set_loop_warm_records)
-  if (has_ctrl && ((lp->warm_start != 0.0 && (crec || !h->loop_warm_rec)) || !h->sel.wform)) return QMPC_UNSUPPORTED;
+  if (has_ctrl && ((lp->warm_start != 0.0 && (crec || !h->opts.loop_warm_records)) || !h->sel.wform)) return QMPC_UNSUPPORTED;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
-  if (batch > 0 && plan_loop_instances(h->sel, batch, has_ctrl, lp->warm_start != 0.0, QMPC_INSTANCES_WAVE, h->handoff_failed,
-                                       h->loop_warm_rec != 0, false, crec).family == QMPC_KERNEL_NONE)
+  // (the handle's policy refuses no call: a plan is NONE under QMPC_INSTANCES_AUTO exactly where it is under QMPC_INSTANCES_WAVE)
+  if (batch > 0 && plan_loop_instances(h->sel, h->opts, batch, has_ctrl, lp->warm_start != 0.0).family == QMPC_KERNEL_NONE)
     return QMPC_UNSUPPORTED;
   return QMPC_OK;
 }
@@ -1727,100 +1724,24 @@ static qmpc_status loop_instances_buffers(qmpc_handle* h, int32_t batch, bool ha
   qmpc_status es = ensure_instance_buffers(h);
   if (es == QMPC_OK) es = ensure_plant_buffers(h);
   if (es != QMPC_OK) return es;
-  const bool wr = h->loop_warm_rec != 0, crec = convex_records(h);
   // (ConvexMpc: the scratch the outcome step of a call without outcome records runs on)
-  if (crec && !h->d_outcome) {
+  if (convex_records(h) && !h->d_outcome) {
     HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
     // (its contents never reach a result -- the parameters that go with it halt no robot -- zeroed once all the same)
     HIP_TRY(hipMemsetAsync(h->d_outcome, 0, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
-  qmpc_plan p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed, wr, false, crec);
+  qmpc_plan p = plan_loop_instances(h->sel, h->opts, batch, has_ctrl, warm);
   if (has_ctrl && !p.fused && p.variant == 4) {
     es = ensure_lane_inst_buffers(h, false);
     if (es != QMPC_OK) return es;
-    if (p.iter_cap && !ensure_handoff_buffers(h))
-      p = plan_loop_instances(h->sel, batch, has_ctrl, warm, h->inst_policy, h->handoff_failed, wr, false, crec);
+    if (p.iter_cap && !ensure_handoff_buffers(h)) p = plan_loop_instances(h->sel, h->opts, batch, has_ctrl, warm);
   }
   if (has_ctrl && warm && !p.fused) {      // (an opted-in handle: what loop_setup would allocate after a ticks = 0 return)
     es = ensure_loop_buffers(h, true);
     if (es != QMPC_OK) return es;
   }
   if (lpp) *lpp = p;
-  return QMPC_OK;
-}
-
-// The solve of one tick with controller records, as `p` plans it (h->d_in -> h->d_forces, h->d_info; the blocks expanded and the
-// buffers allocated already, the lane kernel's parameter block uploaded: nothing here but kernels and the hand-off counter's
-// memset, so the tick can be captured).  The lane form: the sort (stance mask, the previous records' iteration classes, robots
-// that will not solve last), qmpc_lane_inst_kernel to the cap, the per-instance list kernel on what it leaves.
-static qmpc_status loop_inst_tick_solve(qmpc_handle* h, const qmpc_plan& p, int32_t batch, hipStream_t s) {
-  if (p.variant == 4) {
-    const bool cap = p.iter_cap > 0;
-    if (h->sel.lane_sort)
-      HIP_TRY(qmpc_lane_inst_sort_loop_launch((int)batch, s, h->d_in, p.order_prev ? h->d_info : nullptr, inst_status(h),
-                                              h->sel.lane_sort_idle, h->d_lane_scratch));
-    HIP_TRY(qmpc_lane_inst_launch_only(h->lane_pslot, (int)batch, s, h->d_in, inst_dev(h), inst_status(h), h->d_forces, h->d_info,
-                                       h->d_lane_ws, h->d_lane_prm, h->lane_slots, h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr,
-                                       nullptr, nullptr, p.iter_cap, cap ? h->d_handoff : nullptr, cap ? h->d_handoff + 64 : nullptr,
-                                       cap ? h->d_hstate : nullptr, h->hstate_cap, h->sel.lane_pair));
-    if (cap)
-      HIP_TRY(qmpc_wform_inst_list_launch(p.handoff_variant, p.handoff_grid, p.lds, s, inst_dev(h), h->d_in, h->d_forces, h->d_info, nullptr,
-                                          nullptr, h->d_handoff + 64, h->d_handoff, p.gws ? h->d_gws : nullptr,
-                                          h->sel.handoff_restart ? nullptr : h->d_hstate, h->hstate_cap));
-  } else {      // the per-instance wrench-form kernel
-    HIP_TRY(qmpc_wform_inst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces, h->d_info,
-                                         nullptr, nullptr, p.gws ? h->d_gws : nullptr));
-  }
-  h->last_kernel = p.family;
-  return QMPC_OK;
-}
-
-// ... on a ConvexMpc handle (qmpc_set_convex_records): qmpc_solve_cw_inst_kernel on the variant of plan_convex_instances
-static qmpc_status loop_convex_inst_tick_solve(qmpc_handle* h, const qmpc_plan& p, int32_t batch, hipStream_t s) {
-  HIP_TRY(qmpc_wform_cinst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces, h->d_info,
-                                        nullptr, nullptr, p.gws ? h->d_gws : nullptr));
-  h->last_kernel = p.family;
-  return QMPC_OK;
-}
-
-// ... warm-started (lp->warm_start on a handle that opted in: qmpc_set_loop_warm_records).  p: the plan of THIS tick
-// (plan_loop_instances with `first`).  first: the cold first tick of the call -- the kernels above, under the lane plan without
-// cap and hand-off, leaving the solution in h->d_traj_u; later ticks: the warm-started
-// kernels of the plan start from it (a robot whose previous solve failed starts cold: check_prev) and leave theirs there.  The
-// lane form: the sort, qmpc_lane_inst_warm_kernel to the warm ticks' cap, the per-instance list kernel on what it leaves (its
-// records carry the rows' initial residuals).
-static qmpc_status loop_inst_warm_tick_solve(qmpc_handle* h, const qmpc_plan& p, int32_t batch, hipStream_t s, bool first) {
-  double* tu = h->d_traj_u;
-  if (p.variant == 4) {
-    const bool cap = p.iter_cap > 0;
-    const int* perm = h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr;
-    if (h->sel.lane_sort)
-      HIP_TRY(qmpc_lane_inst_sort_loop_launch((int)batch, s, h->d_in, p.order_prev ? h->d_info : nullptr, inst_status(h),
-                                              h->sel.lane_sort_idle, h->d_lane_scratch));
-    if (first)
-      HIP_TRY(qmpc_lane_inst_launch_only(h->lane_pslot, (int)batch, s, h->d_in, inst_dev(h), inst_status(h), h->d_forces, h->d_info,
-                                         h->d_lane_ws, h->d_lane_prm, h->lane_slots, perm, tu, nullptr, p.iter_cap,
-                                         cap ? h->d_handoff : nullptr, cap ? h->d_handoff + 64 : nullptr, cap ? h->d_hstate : nullptr,
-                                         h->hstate_cap, h->sel.lane_pair));
-    else
-      HIP_TRY(qmpc_lane_inst_warm_launch_only(h->lane_pslot, (int)batch, s, h->d_in, inst_dev(h), inst_status(h), h->d_forces, h->d_info,
-                                              h->d_lane_ws, h->d_lane_prm, h->lane_slots, perm, tu, tu, /*check_prev=*/1, p.iter_cap,
-                                              cap ? h->d_handoff : nullptr, cap ? h->d_handoff + 64 : nullptr, cap ? h->d_hstate : nullptr,
-                                              h->hstate_cap, h->sel.lane_pair));
-    if (cap)
-      HIP_TRY(qmpc_wform_inst_list_launch(p.handoff_variant, p.handoff_grid, p.lds, s, inst_dev(h), h->d_in, h->d_forces, h->d_info, tu,
-                                          nullptr, h->d_handoff + 64, h->d_handoff, p.gws ? h->d_gws : nullptr, h->d_hstate, h->hstate_cap));
-    h->last_kernel = p.family;
-    return QMPC_OK;
-  }
-  if (first)
-    HIP_TRY(qmpc_wform_inst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), h->d_in, h->d_forces, h->d_info, tu,
-                                         nullptr, p.gws ? h->d_gws : nullptr));
-  else
-    HIP_TRY(qmpc_wform_inst_warm_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), h->d_in, tu, h->d_forces, h->d_info,
-                                        tu, p.gws ? h->d_gws : nullptr, /*check_prev=*/1));
-  h->last_kernel = p.family;
   return QMPC_OK;
 }
 
@@ -1848,9 +1769,7 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   const qmpc_status ss = loop_setup(h, s, warm && !lpp.fused);
   if (ss != QMPC_OK) return ss;
   // the cold first tick of a warm-started call with controller records has a plan of its own (the lane form: no cap, no hand-off)
-  const qmpc_plan lpp_first = (d_ctrl && warm && !lpp.fused) ? plan_loop_instances(h->sel, batch, true, true, h->inst_policy, h->handoff_failed,
-                                                                                 h->loop_warm_rec != 0, /*first=*/true)
-                                                             : lpp;
+  const qmpc_plan lpp_first = (d_ctrl && warm && !lpp.fused) ? plan_loop_instances(h->sel, h->opts, batch, true, warm, /*first=*/true) : lpp;
   const qmpc_loop_params LP = *lp;
   // a ConvexMpc handle (opted in): one unit for the three kinds -- a call without windows passes none (per_robot = 0), a call
   // without outcome records the handle's scratch and parameters that never halt a robot
@@ -1884,11 +1803,11 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   }
   auto one_tick = [&](bool first) -> qmpc_status {
     HIP_TRY(R.front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch, op, d_outcomes));
-    // with controller records the solve on the blocks expanded above, without them the plain loop's
+    // with controller records the solve on the blocks expanded above (a warm-started call's solution travels through
+    // h->d_traj_u), without them the plain loop's
     const qmpc_status st = !d_ctrl ? loop_tick_solve(h, batch, s, warm, first, crec)
-                           : crec  ? loop_convex_inst_tick_solve(h, lpp, batch, s)
-                           : warm  ? loop_inst_warm_tick_solve(h, first ? lpp_first : lpp, batch, s, first)
-                                   : loop_inst_tick_solve(h, lpp, batch, s);
+                                   : inst_solve(h, first ? lpp_first : lpp, crec, !warm ? INST_TICK_COLD : first ? INST_TICK_FIRST : INST_TICK_WARM,
+                                                batch, h->d_in, h->d_forces, h->d_info, warm ? h->d_traj_u : nullptr, nullptr, s);
     if (st != QMPC_OK) return st;
     HIP_TRY(R.post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, h->d_loop_row, plant_dev(h),
                           (int)batch, op, d_outcomes, d_push, (int)per_robot));
@@ -2024,7 +1943,7 @@ qmpc_status qmpc_debug_profile(qmpc_handle* h, int32_t batch, const qmpc_input* 
   HIP_TRY(hipMalloc(&d_prof, sizeof(long long) * 16 * (size_t)batch));
   HIP_TRY(hipMemsetAsync(d_prof, 0, sizeof(long long) * 16 * (size_t)batch, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_in, in, sizeof(qmpc_input) * (size_t)batch, hipMemcpyHostToDevice, h->stream));
-  const qmpc_plan p = plan(h->sel, batch, QMPC_CALL_PROFILE, true, h->handoff_failed);
+  const qmpc_plan p = plan(h->sel, batch, QMPC_CALL_PROFILE, true, h->opts.handoff_failed);
   if (p.variant >= 3) {
     HIP_TRY(qmpc_wform_launch(QMPC_MODEL_QUAT, 0, p.variant, 1, (int)batch, p.lds, h->stream, &h->dev, sizeof h->dev, h->d_in, h->d_forces, h->d_info,
                               nullptr, nullptr, d_prof, p.gws ? h->d_gws : nullptr));

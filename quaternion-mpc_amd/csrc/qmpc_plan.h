@@ -1,6 +1,7 @@
 // qmpc_plan.h -- which kernel a launch of the library takes: the handle's selection state (filled once in qmpc_create,
 // qmpc_plan_fill.h), the facts of one call, and the plan of that call.  Pure host C++: no HIP call, nothing read from the
-// environment, so the choice can be enumerated and checked without a device (tests/native/plan_host.cpp).
+// environment, so the choice can be enumerated and checked without a device (tests/native/plan_host.cpp; the planners of the
+// calls with per-instance records, which also read the handle's qmpc_opts: tests/native/records_plan_host.cpp).
 //
 // Every launch form of a model (plain solve, warm-started solve, per-tick and persistent closed loop) includes the same body, so
 // ONE rule names the variant for all of them -- they are bit-identical only then.
@@ -283,38 +284,44 @@ static inline qmpc_plan plan(const qmpc_select& s, int batch, qmpc_call kind, bo
   return wave(body());
 }
 
-// The plan of qmpc_solve_instances* (per-instance parameters, qmpc_wform.hip: qmpc_solve_w_inst_kernel): the wrench-form
-// variant (3 / 5 / 6, with its LDS and workspace) that a plain solve of `batch` instances takes on the wave kernels -- also
-// where a plain solve would go to the lane kernel (the default policy QMPC_INSTANCES_WAVE; the lane form: the overload below).  NONE: not QuatMpc's problem in the
-// converged mode, or no wrench-form kernel for this batch under the handle's knobs (QMPC_WFORM=0, QMPC_WFORM=3 beyond the
-// all-LDS sizes, ...).
-static inline qmpc_plan plan_instances(const qmpc_select& s, int batch) {
-  if (s.model != QMPC_MODEL_QUAT || s.mode != QMPC_MODE_CONVERGED || !s.wform) return qmpc_plan();
-  qmpc_select w = s;
-  w.lane_slot = false;      // no lane kernel to go to: plan() keeps the wave kernels' own rule at every batch size
-  const qmpc_plan p = plan(w, batch, QMPC_CALL_PLAIN, true, false);
-  return (p.family == QMPC_KERNEL_WFORM_LDS || p.family == QMPC_KERNEL_WFORM_WS) ? p : qmpc_plan();
-}
+// A handle's run-time settings (qmpc_set_instances_policy, qmpc_set_loop_warm_records, qmpc_set_convex_records, and what became of
+// its hand-off records): what the planners of the calls with per-instance records read besides the selection state.  The
+// handle holds one and passes it whole.
+struct qmpc_opts {
+  int inst_policy = QMPC_INSTANCES_WAVE;      // qmpc_instances_policy of the solves and ticks with per-instance parameters
+  bool handoff_failed = false;                // the hand-off records could not be allocated: the pure lane kernel
+  bool loop_warm_records = false;             // the loops with controller records accept lp->warm_start (QuatMpc)
+  bool convex_records = false;                // the loops with records accept a ConvexMpc handle
+};
 
-// ... under the handle's qmpc_instances_policy.  WAVE: the rule above.  AUTO: the same where it refuses the call, on a handle
-// without a slot of the lane kernel's parameter table and below the switch-over lane_min_inst; from there on the lane fields
-// of the plain solve's plan for this batch (qmpc_lane_inst_kernel to the plain solve's cap and qmpc_solve_w_list_inst_kernel
-// on what it leaves: LANE_HANDOFF; LANE where the plain solve does not hand off).  QMPC_VARIANT=4: the pure lane kernel at
-// every batch size, as for plain solves.
-static inline qmpc_plan plan_instances(const qmpc_select& s, int batch, int policy, bool has_info, bool handoff_failed) {
-  const qmpc_plan w = plan_instances(s, batch);
-  if (policy != QMPC_INSTANCES_AUTO || w.family == QMPC_KERNEL_NONE || !s.lane_slot) return w;
+// The plan of qmpc_solve_instances* (per-instance parameters, qmpc_wform.hip: qmpc_solve_w_inst_kernel).  `has_info`: the call
+// passes status records.
+//   QMPC_INSTANCES_WAVE (the default)  the wrench-form variant (3 / 5 / 6, with its LDS and workspace) that a plain solve of
+//       `batch` instances takes on the wave kernels -- also where a plain solve would go to the lane kernel.
+//   QMPC_INSTANCES_AUTO  the same on a handle without a slot of the lane kernel's parameter table and below the switch-over
+//       lane_min_inst; from there on the lane fields of the plain solve's plan for this batch (qmpc_lane_inst_kernel to the plain
+//       solve's cap and qmpc_solve_w_list_inst_kernel on what it leaves: LANE_HANDOFF; LANE where the plain solve does not hand
+//       off).  QMPC_VARIANT=4: the pure lane kernel at every batch size, as for plain solves.
+// NONE under either policy: not QuatMpc's problem in the converged mode, or no wrench-form kernel for this batch under the
+// handle's knobs (QMPC_WFORM=0, QMPC_WFORM=3 beyond the all-LDS sizes, ...).
+static inline qmpc_plan plan_instances(const qmpc_select& s, const qmpc_opts& o, int batch, bool has_info) {
+  if (s.model != QMPC_MODEL_QUAT || s.mode != QMPC_MODE_CONVERGED || !s.wform) return qmpc_plan();
+  qmpc_select t = s;
+  t.lane_slot = false;      // no lane kernel to go to: plan() keeps the wave kernels' own rule at every batch size
+  const qmpc_plan w = plan(t, batch, QMPC_CALL_PLAIN, true, false);
+  if (w.family != QMPC_KERNEL_WFORM_LDS && w.family != QMPC_KERNEL_WFORM_WS) return qmpc_plan();
+  if (o.inst_policy != QMPC_INSTANCES_AUTO || !s.lane_slot) return w;
   if (s.variant != 4 && batch < s.lane_min_inst) return w;
-  qmpc_select l = s;
-  l.lane_min_batch = 0;      // the switch-over is this call's own: the plain plan only names the lane kernel's fields
-  const qmpc_plan p = plan(l, batch, QMPC_CALL_PLAIN, has_info, handoff_failed);
+  t = s;
+  t.lane_min_batch = 0;      // the switch-over is this call's own: the plain plan only names the lane kernel's fields
+  const qmpc_plan p = plan(t, batch, QMPC_CALL_PLAIN, has_info, o.handoff_failed);
   return p.variant == 4 ? p : w;
 }
 
 // The plan of qmpc_convex_solve_instances* (ConvexMpc's problem with per-instance parameters; qmpc_wform_cinst.hip:
 // qmpc_solve_cw_inst_kernel<3|5|6>).  NONE unless the handle is ConvexMpc in the converged mode with the wrench form on.
 // Where a plain solve of `batch` instances on the wave kernels (lane_slot off: there is no lane form with per-lane parameters
-// for this problem, whatever the qmpc_instances_policy) takes a wrench-form variant: that variant, and the results are the plain
+// for this problem, whatever the handle's qmpc_opts) takes a wrench-form variant: that variant, and the results are the plain
 // solve's bit for bit.  Where it falls to the round-1 family (beyond one resident round of the workspace form, QMPC_VARIANT
 // 2 / 3) there is no per-instance dense kernel, and the call keeps the wrench form: 6 (slack arrays in the workspace too: two
 // waves per SIMD) under plan()'s own condition for it, else 5 while its layout leaves a CU two instances (80 KB), else 3 if an
@@ -337,95 +344,50 @@ static inline qmpc_plan plan_convex_instances(const qmpc_select& s, int batch) {
   return p;
 }
 
-// The plan of qmpc_loop_run_instances* (the closed loop with per-robot controller and / or plant records; qmpc_loop_inst.hip).
-// `has_ctrl`: controller records are given (their solve is the per-instance wrench-form kernel), `warm`: lp->warm_start.
-//   persistent  where the plain loop of this batch takes its persistent kernel (2048 robots, 4096 warm, or QMPC_LOOP_FUSED)
-//               on a wrench-form variant: that very variant (qmpc_loop_rec_fused_kernel<3|5|6>), fused = true;
-//   per tick    otherwise: with controller records the plan of qmpc_solve_instances* (plan_instances), without them the
-//               plain loop's tick (lane kernel and hand-off included); fused = false.
-// NONE: not QuatMpc's problem in the converged mode, controller records with the warm start (a handle opts in to those:
-// the last overload below) or with no wrench-form kernel for the batch (QMPC_WFORM=0, ...).
-static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, bool has_ctrl, bool warm, bool handoff_failed = false) {
-  if (s.model != QMPC_MODEL_QUAT || s.mode != QMPC_MODE_CONVERGED) return qmpc_plan();
-  if (has_ctrl && (warm || !s.wform)) return qmpc_plan();
-  const qmpc_plan f = plan(s, batch, warm ? QMPC_CALL_WARM_LOOP : QMPC_CALL_LOOP, true, handoff_failed);
+// The plan of the closed loops with per-robot controller and / or plant records (qmpc_loop_run_instances*, _outcomes*,
+// _pushes*; qmpc_loop_inst.hip and its siblings, on a ConvexMpc handle qmpc_loop_crec.hip).  `has_ctrl`: controller records are
+// given (their solve is a kernel with per-instance parameters), `warm`: lp->warm_start, `first`: the cold first tick of a
+// warm-started call instead of the tick it repeats.
+//   persistent  where the plain loop of this batch takes its persistent kernel (2048 robots, 4096 warm, or QMPC_LOOP_FUSED) on a
+//               wrench-form variant: that very plan (qmpc_loop_rec_fused_kernel<3|5|6> on the model's body), fused = true --
+//               the rule of a call with plant records only, whatever the policy.  Never with variant 4.
+//   per tick    otherwise, fused = false.  Without controller records the plain loop's tick (lane kernel and hand-off
+//               included).  With them the plan of the model's solve with per-instance parameters under the default settings
+//               (plan_instances: qmpc_solve_w_inst_kernel, warm-started qmpc_solve_w_inst_warm_kernel; ConvexMpc:
+//               plan_convex_instances -- the wave kernels at every size under either policy, there is no lane form with per-lane
+//               parameters for that problem).
+//   lane form   of QuatMpc's per-tick solve with controller records, under QMPC_INSTANCES_AUTO on a handle with a slot of the
+//               lane kernel's parameter table: from the LARGER of the two switch-overs the tick combines on -- that of
+//               qmpc_solve_instances* (lane_min_inst; QMPC_LANE_INST_MIN moves it) and the plain loop's own (cold-started:
+//               lane_min_loop_cold, warm-started: lane_min_warm; QMPC_LANE_MIN moves both) -- the lane fields of the plain loop's
+//               tick for this batch: qmpc_lane_inst_kernel to lane_cap_loop (warm: qmpc_lane_inst_warm_kernel to lane_cap_warm),
+//               the per-instance list kernel on what it leaves, the batch ordered by the previous records too, the parameter
+//               block uploaded once per call and not inside the tick.  With the defaults the cold switch-over is 16384 robots
+//               (16384 and 14336 / 14848), the warm one 18432, 20480 at N = 13 ... 22.  QMPC_VARIANT=4: the pure lane kernel
+//               wherever the per-tick form runs, as for the plain loop.  `first`: the lane kernel without cap and hand-off (the
+//               plain loop's QMPC_CALL_WARM_LOOP_FIRST); on the wave kernels the first tick's variant is the tick's.
+// NONE: the reference mode; a model other than QuatMpc and, on a handle that opted in (convex_records), ConvexMpc; controller
+// records without a wrench-form kernel for the batch (QMPC_WFORM=0, ...); controller records with the warm start unless a
+// QuatMpc handle opted in (loop_warm_records; never on ConvexMpc).
+static inline qmpc_plan plan_loop_instances(const qmpc_select& s, const qmpc_opts& o, int batch, bool has_ctrl, bool warm,
+                                            bool first = false) {
+  const bool convex = s.model == QMPC_MODEL_CONVEX && o.convex_records;
+  if ((s.model != QMPC_MODEL_QUAT && !convex) || s.mode != QMPC_MODE_CONVERGED) return qmpc_plan();
+  if (has_ctrl && (!s.wform || (warm && (convex || !o.loop_warm_records)))) return qmpc_plan();
+  const qmpc_plan f = plan(s, batch, warm ? QMPC_CALL_WARM_LOOP : QMPC_CALL_LOOP, true, o.handoff_failed);
   if (f.fused && (f.variant == 3 || f.variant == 5 || f.variant == 6)) return f;
-  qmpc_plan p = has_ctrl ? plan_instances(s, batch)
-                         : plan(s, batch, warm ? QMPC_CALL_WARM_LOOP_TICK : QMPC_CALL_LOOP_TICK, true, handoff_failed);
-  p.fused = false;
-  return p;
-}
-
-// ... under the handle's qmpc_instances_policy.  WAVE: the rule above.  AUTO: the same without controller records, where it
-// refuses the call, where it takes the persistent kernel, on a handle without a slot of the lane kernel's parameter table and
-// below the switch-over -- the larger of the two switch-overs the tick combines, qmpc_solve_instances*' (lane_min_inst) and the
-// cold-started loop's (lane_min_loop_cold): 16384 robots with the defaults (16384 and 14336 / 14848).  From there on the lane fields of the plain loop's
-// cold tick for this batch (qmpc_lane_inst_kernel to the loop's cap, the per-instance list kernel on what it leaves, the batch
-// ordered by the previous records too, the parameter block uploaded once per call).  QMPC_VARIANT=4: the pure lane kernel
-// wherever the per-tick form runs, as for the plain loop.
-static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, bool has_ctrl, bool warm, int policy, bool handoff_failed) {
-  const qmpc_plan w = plan_loop_instances(s, batch, has_ctrl, warm, handoff_failed);
-  if (!has_ctrl || policy != QMPC_INSTANCES_AUTO || w.family == QMPC_KERNEL_NONE || w.fused || !s.lane_slot) return w;
-  if (s.variant != 4 && batch < (s.lane_min_inst > s.lane_min_loop_cold ? s.lane_min_inst : s.lane_min_loop_cold)) return w;
-  qmpc_select l = s;
-  l.lane_min_loop_cold = 0;      // the switch-over is this call's own: the plain tick's plan only names the lane kernel's fields
-  qmpc_plan p = plan(l, batch, QMPC_CALL_LOOP_TICK, true, handoff_failed);
-  if (p.variant != 4) return w;
-  p.fused = false;
-  return p;
-}
-
-// ... on a handle that may have opted in to warm-started loops with controller records (qmpc_set_loop_warm_records;
-// `warm_records`).  Off, or a call without controller records or without lp->warm_start: the overload above.  On, with both:
-//   persistent  where the warm-started plain loop of this batch takes its persistent kernel on a wrench-form variant (4096
-//               robots, or QMPC_LOOP_FUSED): that plan -- the rule of a call with plant records only;
-//   per tick    otherwise the plan of qmpc_solve_instances* (qmpc_solve_w_inst_warm_kernel on its variant), fused = false;
-//               under QMPC_INSTANCES_AUTO on a handle with a slot of the lane kernel's parameter table, from the larger of the
-//               two switch-overs the tick combines on (lane_min_inst and the warm-started loop's, lane_min_warm: 18432 robots
-//               with the defaults, 20480 at N = 13 ... 22), the lane fields of the plain loop's warm tick for this batch
-//               (qmpc_lane_inst_warm_kernel to lane_cap_warm, the per-instance list kernel on what it leaves, the batch ordered
-//               by the previous records, no upload inside the tick).  QMPC_VARIANT=4: the pure lane kernel wherever the
-//               per-tick form runs.
-// `first`: the cold first tick of the call instead of the tick it repeats -- the same wave variant, or the lane kernel without
-// cap and hand-off (the plain loop's QMPC_CALL_WARM_LOOP_FIRST).
-// NONE: not QuatMpc's problem in the converged mode, or no wrench-form kernel for the batch.
-static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, bool has_ctrl, bool warm, int policy, bool handoff_failed,
-                                            bool warm_records, bool first = false) {
-  if (!warm_records || !has_ctrl || !warm) return plan_loop_instances(s, batch, has_ctrl, warm, policy, handoff_failed);
-  if (s.model != QMPC_MODEL_QUAT || s.mode != QMPC_MODE_CONVERGED || !s.wform) return qmpc_plan();
-  const qmpc_plan f = plan(s, batch, QMPC_CALL_WARM_LOOP, true, handoff_failed);
-  if (f.fused && (f.variant == 3 || f.variant == 5 || f.variant == 6)) return f;
-  qmpc_plan w = plan_instances(s, batch);
+  const qmpc_call tick = !warm ? QMPC_CALL_LOOP_TICK : (has_ctrl && first ? QMPC_CALL_WARM_LOOP_FIRST : QMPC_CALL_WARM_LOOP_TICK);
+  qmpc_plan w = !has_ctrl ? plan(s, batch, tick, true, o.handoff_failed)
+                : convex  ? plan_convex_instances(s, batch)
+                          : plan_instances(s, qmpc_opts(), batch, true);
   w.fused = false;
-  if (policy != QMPC_INSTANCES_AUTO || w.family == QMPC_KERNEL_NONE || !s.lane_slot) return w;
-  if (s.variant != 4 && batch < (s.lane_min_inst > s.lane_min_warm ? s.lane_min_inst : s.lane_min_warm)) return w;
+  if (!has_ctrl || convex || o.inst_policy != QMPC_INSTANCES_AUTO || w.family == QMPC_KERNEL_NONE || !s.lane_slot) return w;
   qmpc_select l = s;
-  l.lane_min_warm = 0;      // the switch-over is this call's own: the plain tick's plan only names the lane kernel's fields
-  qmpc_plan p = plan(l, batch, first ? QMPC_CALL_WARM_LOOP_FIRST : QMPC_CALL_WARM_LOOP_TICK, true, handoff_failed);
+  int& own = warm ? l.lane_min_warm : l.lane_min_loop_cold;
+  if (s.variant != 4 && batch < (s.lane_min_inst > own ? s.lane_min_inst : own)) return w;
+  own = 0;      // the switch-over is this call's own: the plain tick's plan only names the lane kernel's fields
+  qmpc_plan p = plan(l, batch, tick, true, o.handoff_failed);
   if (p.variant != 4) return w;
-  p.fused = false;
-  return p;
-}
-
-// ... on a handle that may have opted in to records on ConvexMpc's problem (qmpc_set_convex_records; `convex_records`).  Off, or
-// another model: the overload above, field for field.  On, for a ConvexMpc handle (qmpc_loop_crec.hip):
-//   persistent  where the plain ConvexMpc loop of this batch takes its persistent kernel on a wrench-form variant 3 / 5 / 6
-//               (2048 robots, 4096 warm, or QMPC_LOOP_FUSED): that plan (qmpc_loop_rec_fused_kernel<3|5|6> on the convex body);
-//   per tick    otherwise: with controller records the plan of qmpc_convex_solve_instances* (plan_convex_instances: the wave
-//               kernels at every size under either policy -- there is no lane form with per-lane parameters for this problem),
-//               without them the plain loop's tick (its lane kernel included); fused = false.
-// NONE: the reference mode, controller records with the warm start (whatever `warm_records` says) or with no wrench-form kernel
-// for the batch.
-static inline qmpc_plan plan_loop_instances(const qmpc_select& s, int batch, bool has_ctrl, bool warm, int policy, bool handoff_failed,
-                                            bool warm_records, bool first, bool convex_records) {
-  if (!convex_records || s.model != QMPC_MODEL_CONVEX)
-    return plan_loop_instances(s, batch, has_ctrl, warm, policy, handoff_failed, warm_records, first);
-  if (s.mode != QMPC_MODE_CONVERGED) return qmpc_plan();
-  if (has_ctrl && (warm || !s.wform)) return qmpc_plan();
-  const qmpc_plan f = plan(s, batch, warm ? QMPC_CALL_WARM_LOOP : QMPC_CALL_LOOP, true, handoff_failed);
-  if (f.fused && (f.variant == 3 || f.variant == 5 || f.variant == 6)) return f;
-  qmpc_plan p = has_ctrl ? plan_convex_instances(s, batch)
-                         : plan(s, batch, warm ? QMPC_CALL_WARM_LOOP_TICK : QMPC_CALL_LOOP_TICK, true, handoff_failed);
   p.fused = false;
   return p;
 }

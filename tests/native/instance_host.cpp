@@ -1,12 +1,9 @@
 // Host-only checks of the per-instance parameter path (qmpc_solve_instances*), built like plan_host.cpp
 // (hipcc -x hip --offload-host-only; no device code, no device needed):
-//   (a) plan_instances (quaternion-mpc_amd/csrc/qmpc_plan.h) over every model, mode, horizon 1..32, the knob sets of plan_host.cpp
-//       and the batch sizes around every switch-over: QuatMpc's problem in the converged mode takes a wave wrench-form kernel
-//       (never the lane kernel), the very variant, LDS and workspace of a plain solve wherever that solve is a wave kernel, and
-//       NONE where the plain solve would take no wrench-form kernel; every other handle gets NONE.
-//   (b) apply_instance_params (qmpc_params_dev.h), the helper the expansion kernel runs, against fill_dev_params on a qmpc_params
-//       carrying the same seven fields: byte for byte on 10000 random valid records; every kind of invalid record is rejected.
-// Prints one summary line per part; exit status 0 when nothing failed.
+//   apply_instance_params (qmpc_params_dev.h), the helper the expansion kernel runs, against fill_dev_params on a qmpc_params
+//   carrying the same seven fields: byte for byte on 10000 random valid records; every kind of invalid record is rejected.
+// (The planner of the call: records_plan_host.cpp --check instances.)
+// Prints one summary line; exit status 0 when nothing failed.
 #define QMPC_FUSED_TU 1      // the templates of the kernel headers only: no kernel is instantiated here
 #include "../../quaternion-mpc_amd/csrc/qmpc_kernels.hip"
 #include "../../quaternion-mpc_amd/csrc/qmpc_wform.h"
@@ -17,31 +14,8 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
-#include <set>
 
 namespace {
-
-struct Knobs {
-  const char* name;
-  const char* var;
-  const char* value;
-  bool no_slot;
-  int handoff_failed;
-};
-const Knobs kKnobs[] = {
-    {"default", nullptr, nullptr, false, 0},       {"QMPC_VARIANT=1", "QMPC_VARIANT", "1", false, 0},
-    {"QMPC_VARIANT=2", "QMPC_VARIANT", "2", false, 0}, {"QMPC_VARIANT=3", "QMPC_VARIANT", "3", false, 0},
-    {"QMPC_VARIANT=4", "QMPC_VARIANT", "4", false, 0}, {"QMPC_WFORM=0", "QMPC_WFORM", "0", false, 0},
-    {"QMPC_WFORM=3", "QMPC_WFORM", "3", false, 0},     {"no-lane-slot", nullptr, nullptr, true, 0},
-    {"handoff-failed", nullptr, nullptr, false, 1},
-    {"QMPC_VARIANT=4 handoff-failed", "QMPC_VARIANT", "4", false, 1},
-    {"QMPC_LANE_MIN=8192", "QMPC_LANE_MIN", "8192", false, 0},
-    {"QMPC_LANE_REF_MIN=8192", "QMPC_LANE_REF_MIN", "8192", false, 0},
-    {"QMPC_LANE_CAP=0", "QMPC_LANE_CAP", "0", false, 0},     {"QMPC_LANE_CAP=12", "QMPC_LANE_CAP", "12", false, 0},
-    {"QMPC_LANE_CAP_LOOP=0", "QMPC_LANE_CAP_LOOP", "0", false, 0}, {"QMPC_LANE_CAP_WARM=0", "QMPC_LANE_CAP_WARM", "0", false, 0},
-    {"QMPC_LOOP_FUSED=0", "QMPC_LOOP_FUSED", "0", false, 0}, {"QMPC_LOOP_FUSED=1", "QMPC_LOOP_FUSED", "1", false, 0},
-    {"QMPC_REF_WFORM_MAXN=12", "QMPC_REF_WFORM_MAXN", "12", false, 0},
-};
 
 int failures = 0;
 #define CHECK(cond, ...)                          \
@@ -55,72 +29,6 @@ int failures = 0;
       ++failures;                                 \
     }                                             \
   } while (0)
-
-bool wform_family(int f) { return f == QMPC_KERNEL_WFORM_LDS || f == QMPC_KERNEL_WFORM_WS; }
-bool lane_family(int f) { return f == QMPC_KERNEL_LANE || f == QMPC_KERNEL_LANE_HANDOFF; }
-
-void check_planner() {
-  long cases = 0, wave_equal = 0, above_lane = 0, none = 0;
-  for (int model = 0; model < 3; ++model)
-    for (int mode = 0; mode < 2; ++mode)
-      for (int N = 1; N <= QMPC_MAX_HORIZON; ++N)
-        for (const Knobs& k : kKnobs) {
-          qmpc_params params;
-          std::memset(&params, 0, sizeof params);
-          params.model = model;
-          params.mode = mode;
-          params.horizon = N;
-          params.iterations_max = mode == QMPC_MODE_REFERENCE ? (model == QMPC_MODEL_CONVEX ? 5 : 10) : 120;
-          auto env = [&k](const char* name) -> const char* { return (k.var && std::strcmp(name, k.var) == 0) ? k.value : nullptr; };
-          qmpc::qmpc_select sel;
-          if (!qmpc::qmpc_fill_select(&sel, &params, env, !k.no_slot)) continue;
-          std::set<int> batches = {1, 2, 255, 256, 257, 512, 513, 768, 769, 1023, 1024, 1025, 2048, 2049, 4096, 4097,
-                                   8192, 14335, 14336, 16384, 32768, 65536, 262144};
-          for (const auto& table : sel.lds)
-            for (size_t lds : table)
-              if (lds > 0)
-                for (int d = -1; d <= 1; ++d) batches.insert(256 * (int)((160 * 1024) / lds) + d);
-          for (int t : {sel.lane_min_batch, sel.lane_min_loop_cold, sel.lane_min_warm, sel.lane_ref_min, qmpc::kLaneRefMinLoop})
-            for (int d = -1; d <= 1; ++d) batches.insert(t + d);
-          const bool supported = model == QMPC_MODEL_QUAT && mode == QMPC_MODE_CONVERGED && sel.wform;
-          for (int b : batches) {
-            if (b < 1) continue;
-            ++cases;
-            const qmpc::qmpc_plan r = qmpc::plan_instances(sel, b);
-            const qmpc::qmpc_plan pp = qmpc::plan(sel, b, qmpc::QMPC_CALL_PLAIN, true, k.handoff_failed);
-            CHECK(!lane_family(r.family) && r.family != QMPC_KERNEL_DENSE_LDS && r.family != QMPC_KERNEL_DENSE_WS,
-                  "model %d mode %d N=%d %s B=%d: family %d", model, mode, N, k.name, b, r.family);
-            if (!supported) {
-              CHECK(r.family == QMPC_KERNEL_NONE, "model %d mode %d N=%d %s B=%d: family %d, want none", model, mode, N, k.name, b,
-                    r.family);
-              continue;
-            }
-            if (r.family == QMPC_KERNEL_NONE) {
-              ++none;
-            } else {
-              CHECK(r.variant == 3 || r.variant == 5 || r.variant == 6, "N=%d %s B=%d: variant %d", N, k.name, b, r.variant);
-              CHECK(r.family == (r.variant == 3 ? QMPC_KERNEL_WFORM_LDS : QMPC_KERNEL_WFORM_WS), "N=%d %s B=%d", N, k.name, b);
-              CHECK(r.lds == sel.lds[0][r.variant] && r.gws == (r.variant != 3), "N=%d %s B=%d: lds %zu gws %d", N, k.name, b, r.lds,
-                    (int)r.gws);
-              CHECK(r.handoff_variant == 0 && r.iter_cap == 0 && !r.fused, "N=%d %s B=%d", N, k.name, b);
-            }
-            if (lane_family(pp.family)) {
-              ++above_lane;
-              // the default knobs leave the wrench form at every batch size: the workspace form beyond the lane switch-over
-              if (!k.var) CHECK(wform_family(r.family), "N=%d %s B=%d: none above the lane switch-over", N, k.name, b);
-            } else if (wform_family(pp.family)) {
-              ++wave_equal;
-              CHECK(r.family == pp.family && r.variant == pp.variant && r.lds == pp.lds && r.gws == pp.gws,
-                    "N=%d %s B=%d: variant %d, plain solve %d", N, k.name, b, r.variant, pp.variant);
-            } else {
-              CHECK(r.family == QMPC_KERNEL_NONE, "N=%d %s B=%d: family %d where the plain solve takes family %d", N, k.name, b,
-                    r.family, pp.family);
-            }
-          }
-        }
-  std::printf("planner: %ld cases, %ld equal to a plain wave-kernel solve, %ld beyond the lane switch-over, %ld none\n", cases,
-              wave_equal, above_lane, none);
-}
 
 // counter-based uniform draws in [0, 1)
 uint64_t mix(uint64_t z) {
@@ -249,7 +157,6 @@ void check_helper() {
 }  // namespace
 
 int main() {
-  check_planner();
   check_helper();
   std::printf("%s: %d failures\n", failures ? "FAILED" : "passed", failures);
   return failures ? 1 : 0;

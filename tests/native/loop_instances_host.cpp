@@ -4,9 +4,7 @@
 //       of invalid record (non-finite field, mass <= 0, singular inertia) is rejected.
 //   (b) plant_step_ext (qmpc_loop_math.h) with a zero disturbance against plant_step on random states and forces: bit for bit,
 //       -0.0 components included; a non-zero component changes the step.
-//   (c) plan_loop_instances (qmpc_plan.h) over every model, mode, horizon, the knob sets below and the batch sizes around every
-//       switch-over: refusals, the persistent / per-tick threshold of the plain loop, and the variant of the plain loop's
-//       persistent kernel where the persistent form is taken.
+// (The planner of the call: records_plan_host.cpp --check loop.)
 // Prints one summary line per part; exit status 0 when nothing failed.
 #define QMPC_FUSED_TU 1      // the templates of the kernel headers only: no kernel is instantiated here
 #include "../../quaternion-mpc_amd/csrc/qmpc_kernels.hip"
@@ -19,7 +17,6 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
-#include <set>
 
 namespace {
 
@@ -173,86 +170,11 @@ void check_plant_step() {
   std::printf("plant step: %ld of %d zero-disturbance steps equal plant_step bit for bit; %ld disturbed steps moved\n", same, n, moved);
 }
 
-struct Knobs {
-  const char* name;
-  const char* var;
-  const char* value;
-  bool no_slot;
-  int handoff_failed;
-};
-const Knobs kKnobs[] = {
-    {"default", nullptr, nullptr, false, 0},       {"QMPC_VARIANT=1", "QMPC_VARIANT", "1", false, 0},
-    {"QMPC_VARIANT=3", "QMPC_VARIANT", "3", false, 0}, {"QMPC_VARIANT=4", "QMPC_VARIANT", "4", false, 0},
-    {"QMPC_WFORM=0", "QMPC_WFORM", "0", false, 0},     {"QMPC_WFORM=3", "QMPC_WFORM", "3", false, 0},
-    {"no-lane-slot", nullptr, nullptr, true, 0},       {"handoff-failed", nullptr, nullptr, false, 1},
-    {"QMPC_LOOP_FUSED=0", "QMPC_LOOP_FUSED", "0", false, 0}, {"QMPC_LOOP_FUSED=1", "QMPC_LOOP_FUSED", "1", false, 0},
-};
-
-void check_planner() {
-  long cases = 0, persistent = 0, per_tick = 0, none = 0;
-  for (int model = 0; model < 3; ++model)
-    for (int mode = 0; mode < 2; ++mode)
-      for (int N = 1; N <= QMPC_MAX_HORIZON; ++N)
-        for (const Knobs& k : kKnobs) {
-          qmpc_params params;
-          std::memset(&params, 0, sizeof params);
-          params.model = model;
-          params.mode = mode;
-          params.horizon = N;
-          params.iterations_max = mode == QMPC_MODE_REFERENCE ? (model == QMPC_MODEL_CONVEX ? 5 : 10) : 120;
-          auto env = [&k](const char* name) -> const char* { return (k.var && std::strcmp(name, k.var) == 0) ? k.value : nullptr; };
-          qmpc::qmpc_select sel;
-          if (!qmpc::qmpc_fill_select(&sel, &params, env, !k.no_slot)) continue;
-          const std::set<int> batches = {1, 2, 96, 1024, 1025, 2047, 2048, 2049, 3000, 4095, 4096, 4097, 8192, 14336, 32768, 65536};
-          const bool quat = model == QMPC_MODEL_QUAT && mode == QMPC_MODE_CONVERGED;
-          for (int b : batches)
-            for (int has_ctrl = 0; has_ctrl < 2; ++has_ctrl)
-              for (int warm = 0; warm < 2; ++warm) {
-                ++cases;
-                const bool hf = k.handoff_failed != 0;
-                const qmpc::qmpc_plan r = qmpc::plan_loop_instances(sel, b, has_ctrl, warm, hf);
-                const char* what = k.name;
-                if (!quat || (has_ctrl && (warm || !sel.wform))) {
-                  CHECK(r.family == QMPC_KERNEL_NONE, "model %d mode %d N=%d %s B=%d ctrl %d warm %d: family %d, want none", model,
-                        mode, N, what, b, has_ctrl, warm, r.family);
-                  ++none;
-                  continue;
-                }
-                // the plain loop of the same batch
-                const qmpc::qmpc_plan pl = qmpc::plan(sel, b, warm ? qmpc::QMPC_CALL_WARM_LOOP : qmpc::QMPC_CALL_LOOP, true, hf);
-                const bool threshold = k.var && std::strcmp(k.var, "QMPC_LOOP_FUSED") == 0 ? k.value[0] == '1' : b <= (warm ? 4096 : 2048);
-                CHECK(pl.fused == threshold, "N=%d %s B=%d warm %d: plain loop fused %d", N, what, b, warm, (int)pl.fused);
-                const bool wv = pl.variant == 3 || pl.variant == 5 || pl.variant == 6;
-                if (pl.fused && wv) {
-                  ++persistent;
-                  CHECK(r.fused && r.variant == pl.variant && r.lds == pl.lds && r.gws == pl.gws && r.family == pl.family,
-                        "N=%d %s B=%d ctrl %d warm %d: persistent variant %d, plain loop %d", N, what, b, has_ctrl, warm, r.variant,
-                        pl.variant);
-                  continue;
-                }
-                CHECK(!r.fused, "N=%d %s B=%d: persistent form without a wrench-form variant", N, what, b);
-                if (has_ctrl) {
-                  const qmpc::qmpc_plan pi = qmpc::plan_instances(sel, b);
-                  CHECK(r.family == pi.family && r.variant == pi.variant && r.lds == pi.lds, "N=%d %s B=%d: per-tick %d vs instances %d",
-                        N, what, b, r.variant, pi.variant);
-                } else {
-                  const qmpc::qmpc_plan pt = qmpc::plan(sel, b, warm ? qmpc::QMPC_CALL_WARM_LOOP_TICK : qmpc::QMPC_CALL_LOOP_TICK, true, hf);
-                  CHECK(r.family == pt.family && r.variant == pt.variant && r.iter_cap == pt.iter_cap,
-                        "N=%d %s B=%d warm %d: per-tick %d vs the plain tick %d", N, what, b, warm, r.variant, pt.variant);
-                }
-                if (r.family == QMPC_KERNEL_NONE) ++none;
-                else ++per_tick;
-              }
-        }
-  std::printf("planner: %ld cases, %ld persistent, %ld per tick, %ld refused\n", cases, persistent, per_tick, none);
-}
-
 }  // namespace
 
 int main() {
   check_plant_rule();
   check_plant_step();
-  check_planner();
   std::printf("passed: %d failures\n", failures);
   return failures ? 1 : 0;
 }

@@ -7,8 +7,10 @@
 // headers as the library's, and the selection state from the same filler as qmpc_create's.
 //   plan_host              the table on stdout
 //   plan_host --write F    ... into F
-//   plan_host --kernels    check that every plan of the enumeration, and of qmpc_solve_instances* and qmpc_loop_run_instances*
-//                          on the same configurations, names a kernel of its unit's launch table (qmpc_kernel_slots.h)
+//   plan_host --kernels    check that every plan of the enumeration names a kernel of its unit's launch table
+//                          (qmpc_kernel_slots.h)
+// The planners of the calls with per-instance records (plan_instances, plan_convex_instances, plan_loop_instances) have a
+// program of their own with the same three modes, records_plan_host.cpp.
 #define QMPC_FUSED_TU 1      // the templates of the kernel headers only: no kernel is instantiated here
 #include "../../quaternion-mpc_amd/csrc/qmpc_kernels.hip"
 #include "../../quaternion-mpc_amd/csrc/qmpc_wform.h"
@@ -58,15 +60,13 @@ std::string row(const qmpc::qmpc_plan& p) {
 }
 
 // Whether the launch table slot the launchers take for plan p of a call of kind `call` exists (qmpc_hip.hip: launch_solve,
-// loop_tick_solve, qmpc_solve_warm_device, qmpc_debug_profile, loop_run_impl, launch_lane, launch_instances,
-// qmpc_loop_run_instances_device); joint: the JOINT half of the persistent kernels; inst: a per-instance kernel (per-instance
-// solve, persistent loop with per-robot records).  A plan of no wave kernel (NONE, the lane kernel) needs none.
-bool has_kernel(const qmpc::qmpc_select& s, const qmpc::qmpc_plan& p, qmpc::qmpc_call call, int batch, bool joint, bool inst) {
+// loop_tick_solve, qmpc_solve_warm_device, qmpc_debug_profile, loop_run_impl, launch_lane); joint: the JOINT half of the
+// persistent kernels.  A plan of no wave kernel (NONE, the lane kernel) needs none.
+bool has_kernel(const qmpc::qmpc_select& s, const qmpc::qmpc_plan& p, qmpc::qmpc_call call, int batch, bool joint) {
   using namespace qmpc;
   const bool ref = s.mode == QMPC_MODE_REFERENCE, convex = s.model == QMPC_MODEL_CONVEX;
   const bool warm = call == QMPC_CALL_WARM || call == QMPC_CALL_WARM_LOOP_FIRST || call == QMPC_CALL_WARM_LOOP_TICK || call == QMPC_CALL_WARM_LOOP;
   if (p.family == QMPC_KERNEL_NONE || p.family == QMPC_KERNEL_LANE) return true;
-  if (inst) return wform_index(p.variant) >= 0;
   if (p.family == QMPC_KERNEL_LANE_HANDOFF) return wform_list_slot(p.handoff_variant) >= 0;
   if (p.fused) return fused_slot(p.variant, ref, convex, joint) >= 0;
   if (warm) return warm_slot(p.variant, convex) >= 0;
@@ -86,12 +86,11 @@ int main(int argc, char** argv) {
   else if (argc != 1 && !kernels) { std::fprintf(stderr, "usage: plan_host [--write FILE | --kernels]\n"); return 2; }
   if (!out) return 1;
   long checked = 0, missing = 0;
-  auto check = [&](const qmpc::qmpc_select& sel, const qmpc::qmpc_plan& p, qmpc::qmpc_call call, int b, const char* cfg, bool inst) {
-    for (int joint = 0; joint < (p.fused && !inst ? 2 : 1); ++joint) {
+  auto check = [&](const qmpc::qmpc_select& sel, const qmpc::qmpc_plan& p, qmpc::qmpc_call call, int b, const char* cfg) {
+    for (int joint = 0; joint < (p.fused ? 2 : 1); ++joint) {
       ++checked;
-      if (!has_kernel(sel, p, call, b, joint, inst) && ++missing <= 20)
-        std::fprintf(stderr, "no kernel: %s, call %d%s batch %d: family %d variant %d joint %d\n", cfg, (int)call, inst ? " (per instance)" : "",
-                     b, p.family, p.variant, joint);
+      if (!has_kernel(sel, p, call, b, joint) && ++missing <= 20)
+        std::fprintf(stderr, "no kernel: %s, call %d batch %d: family %d variant %d joint %d\n", cfg, (int)call, b, p.family, p.variant, joint);
     }
   };
   if (!kernels)
@@ -130,23 +129,13 @@ int main(int argc, char** argv) {
               if (b < 1) continue;
               const qmpc::qmpc_plan p = qmpc::plan(sel, b, call, has_info, k.handoff_failed);
               if (kernels) {
-                check(sel, p, call, b, cfg, false);
+                check(sel, p, call, b, cfg);
                 continue;
               }
               const std::string r = row(p);
               if (r == prev) continue;
               std::fprintf(out, "%s%s %d %s\n", kKind[call], has_info ? "" : "-noinfo", b, r.c_str());
               prev = r;
-            }
-          }
-          if (!kernels) continue;
-          for (int b : batches) {      // the per-instance solve and the closed loop with per-robot records (controller / plant)
-            if (b < 1) continue;
-            check(sel, qmpc::plan_instances(sel, b), qmpc::QMPC_CALL_PLAIN, b, cfg, true);
-            for (int rec = 0; rec < 4; ++rec) {
-              const bool ctrl = rec & 1, warm = rec & 2;
-              const qmpc::qmpc_plan pl = qmpc::plan_loop_instances(sel, b, ctrl, warm, k.handoff_failed);
-              check(sel, pl, warm ? qmpc::QMPC_CALL_WARM_LOOP_TICK : qmpc::QMPC_CALL_LOOP_TICK, b, cfg, pl.fused || ctrl);
             }
           }
         }

@@ -1,7 +1,7 @@
 """CPU suite: per-robot controller and plant records for ConvexMpc solves and loops (qmpc_convex_solve_instances*,
 qmpc_set_convex_records; include/qmpc.h) without a device.
 
-tests/native/convex_records_plan_host.cpp enumerates plan_convex_instances and the planner overload that takes the setting over
+tests/native/records_plan_host.cpp (--check convex) enumerates plan_convex_instances and the loop planner under the setting over
 the planner's whole input space; the ABI: the symbols are exported, a null handle is refused, the header and the binding agree
 on the queries' numbers, the build's unit table carries the two new translation units, the record generator of the fleet
 under the sibling controller, and the oracle's own not-OK rate on the sample of the GPU parity test.  What needs a handle -- the
@@ -17,7 +17,7 @@ import pytest
 
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
-PLAN_SRC = HERE / "native" / "convex_records_plan_host.cpp"
+PLAN_SRC = HERE / "native" / "records_plan_host.cpp"
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
@@ -30,9 +30,9 @@ def lib(pkg):
 
 
 def test_planner_of_the_convex_calls(tmp_path):
-    exe = tmp_path / "convex_records_plan_host"
+    exe = tmp_path / "records_plan_host"
     subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-o", str(exe), str(PLAN_SRC)], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = subprocess.run([str(exe), "--check", "convex"], capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "convex records planner:" in r.stdout and "passed: 0 failures" in r.stdout

@@ -8,7 +8,7 @@ handle carrying the instance's values, bit for bit; where the plain solve takes 
 between ConvexMpc's wave families (status words equal, forces within 1e-7 N: the bound of tests/test_gpu_parity.py between
 those families), and against the CPU oracle to 1e-6 N (the project's ConvexMpc parity bound).
 
-Batch sizes, from the enumeration of tests/native/convex_records_plan_host.cpp (default knobs): the smallest batch on variant
+Batch sizes, from the enumeration of tests/native/records_plan_host.cpp --check convex (default knobs): the smallest batch on variant
 3 / 5 / 6 is 1 / 513 / 1025 at N = 20 (the plain solve takes the same variants there) and 1 / 769 / 2049 at N = 10 (where the
 plain solve of 2049 instances takes the round-1 kernel)."""
 import numpy as np

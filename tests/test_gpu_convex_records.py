@@ -7,7 +7,7 @@ qmpc_loop_run on the same handle in both launch forms; the two forms agree with 
 controller sets are the plain loops of handles carrying each set; a permuted fleet gives the permuted result; outcome records,
 stop_when_down, push windows and the freeze of an invalid record behave as DESIGN.md sections 3l - 3n define them.
 
-Sizes, from the enumeration of tests/native/convex_records_plan_host.cpp: up to 2048 robots the call takes the persistent kernel
+Sizes, from the enumeration of tests/native/records_plan_host.cpp --check convex: up to 2048 robots the call takes the persistent kernel
 on the plain loop's variant (3 up to 768 robots at N = 10 and 512 at N = 20); under QMPC_LOOP_FUSED=0 the per-tick solve with
 controller records is qmpc_solve_cw_inst_kernel on the variant of qmpc_convex_solve_instances* (3 / 5 / 6 from 1 / 769 / 2049
 instances at N = 10, 1 / 513 / 1025 at N = 20).  Launch forms other than the default are run in worker processes

@@ -5,7 +5,7 @@ tests/native/lane_inst_host.cpp is a g++ build of the lane core's per-lane-param
 qmpc_lane_inst_kernel): the instance fields of the parameters come from the lane's rows of a parameter block, everything else
 from the handle's block.  Host arithmetic uses the same expressions whatever the source, so its results must equal, byte for
 byte, the plain core's on a handle that carries the instance's values -- a difference is a field read from the wrong place.
-tests/native/instance_lane_plan_host.cpp enumerates the policy-aware planner over the planner's whole input space."""
+tests/native/records_plan_host.cpp (--check instances-policy) enumerates the planner under either policy over the planner's whole input space."""
 import ctypes as C
 import subprocess
 from pathlib import Path
@@ -18,7 +18,7 @@ from instance_lane_sets import SETS, input_set, plant_bad, sample, BAD_RECORDS
 HERE = Path(__file__).resolve().parent
 SRC = HERE / "native" / "lane_inst_host.cpp"
 LIB = HERE / "native" / "liblane_inst_host.so"
-PLAN_SRC = HERE / "native" / "instance_lane_plan_host.cpp"
+PLAN_SRC = HERE / "native" / "records_plan_host.cpp"
 CORE = HERE.parent / "quaternion-mpc_amd" / "csrc"
 HIPCC = "/opt/rocm/bin/hipcc"
 SAMPLES = {"S1": 1024, "S2": 1024, "S3": 512, "S4": 512}
@@ -135,9 +135,9 @@ def test_bad_records_are_flagged_alone(pkg, lib, host):
 
 
 def test_planner_under_the_policy(tmp_path):
-    exe = tmp_path / "instance_lane_plan_host"
+    exe = tmp_path / "records_plan_host"
     subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-o", str(exe), str(PLAN_SRC)], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = subprocess.run([str(exe), "--check", "instances-policy"], capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "instance lane planner:" in r.stdout and "passed: 0 failures" in r.stdout

@@ -1,9 +1,9 @@
 """CPU suite: per-instance robot and cost parameters (qmpc_solve_instances*, include/qmpc.h) without a device.
 
 The record's ABI (size, the seven fields qmpc_instance_params_from copies), the call-level argument checks that need no
-handle, and tests/native/instance_host.cpp: the planner rule of the per-instance call over the planner's whole input space,
-and the shared helper of the expansion kernel against the host's fill_dev_params, byte for byte.  The harness is compiled
-host-only by hipcc, like tests/native/plan_host.cpp."""
+handle, the planner rule of the per-instance call over the planner's whole input space (tests/native/records_plan_host.cpp
+--check instances), and tests/native/instance_host.cpp: the shared helper of the expansion kernel against the host's
+fill_dev_params, byte for byte.  The harnesses are compiled host-only by hipcc, like tests/native/plan_host.cpp."""
 import ctypes as C
 import subprocess
 from pathlib import Path
@@ -13,6 +13,7 @@ import pytest
 
 HERE = Path(__file__).resolve().parent
 SRC = HERE / "native" / "instance_host.cpp"
+PLAN_SRC = HERE / "native" / "records_plan_host.cpp"
 CSRC = HERE.parent / "quaternion-mpc_amd" / "csrc"
 HIPCC = "/opt/rocm/bin/hipcc"
 
@@ -61,12 +62,13 @@ def test_status_string(lib, pkg):
 
 
 def test_planner_rule_and_shared_helper(tmp_path):
-    exe = tmp_path / "instance_host"
-    subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-o", str(exe), str(SRC)], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "10000 valid records equal" in r.stdout and "passed: 0 failures" in r.stdout
+    for src, args, line in ((PLAN_SRC, ["--check", "instances"], "instances planner:"), (SRC, [], "10000 valid records equal")):
+        exe = tmp_path / src.stem
+        subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-o", str(exe), str(src)], check=True)
+        r = subprocess.run([str(exe), *args], capture_output=True, text=True)
+        print(r.stdout)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert line in r.stdout and "passed: 0 failures" in r.stdout
 
 
 def test_params_header_stays_gpp_compilable(tmp_path):

@@ -1,9 +1,10 @@
 """CPU suite: the closed loop with per-robot controller and plant records (qmpc_loop_run_instances*, include/qmpc.h) without
 a device.
 
-The plant record's ABI, the call-level argument checks that need no handle, and tests/native/loop_instances_host.cpp: the
-plant validity rule, the disturbed plant step against the plain one (bit for bit with a zero disturbance) and the planner rule
-of the call over the planner's input space.  The harness is compiled host-only by hipcc, like tests/native/instance_host.cpp."""
+The plant record's ABI, the call-level argument checks that need no handle, tests/native/loop_instances_host.cpp: the
+plant validity rule and the disturbed plant step against the plain one (bit for bit with a zero disturbance), and the planner
+rule of the call over the planner's input space (tests/native/records_plan_host.cpp --check loop).  The harnesses are compiled
+host-only by hipcc, like tests/native/instance_host.cpp."""
 import ctypes as C
 import subprocess
 from pathlib import Path
@@ -13,6 +14,7 @@ import pytest
 
 HERE = Path(__file__).resolve().parent
 SRC = HERE / "native" / "loop_instances_host.cpp"
+PLAN_SRC = HERE / "native" / "records_plan_host.cpp"
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
@@ -73,10 +75,13 @@ def test_random_go1_plants(lib, pkg):
 
 
 def test_plant_rule_step_and_planner(tmp_path):
-    exe = tmp_path / "loop_instances_host"
-    subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-o", str(exe), str(SRC)], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "10000 valid records equal fill_dev_params' blocks (10000)" in r.stdout
-    assert "20000 of 20000 zero-disturbance steps equal plant_step" in r.stdout and "passed: 0 failures" in r.stdout
+    out = ""
+    for src, args in ((SRC, []), (PLAN_SRC, ["--check", "loop"])):
+        exe = tmp_path / src.stem
+        subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-o", str(exe), str(src)], check=True)
+        r = subprocess.run([str(exe), *args], capture_output=True, text=True)
+        print(r.stdout)
+        assert r.returncode == 0 and "passed: 0 failures" in r.stdout, r.stdout + r.stderr
+        out += r.stdout
+    assert "10000 valid records equal fill_dev_params' blocks (10000)" in out
+    assert "20000 of 20000 zero-disturbance steps equal plant_step" in out and "loop records planner:" in out

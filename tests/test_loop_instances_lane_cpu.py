@@ -1,7 +1,7 @@
 """CPU suite: the lane-kernel ticks of the closed loop with per-robot controller records (qmpc_loop_run_instances* /
 qmpc_loop_run_outcomes* under QMPC_INSTANCES_AUTO, include/qmpc.h) without a device.
 
-tests/native/loop_instances_lane_plan_host.cpp enumerates the policy-aware overload of plan_loop_instances over the planner's
+tests/native/records_plan_host.cpp (--check loop-policy) enumerates plan_loop_instances under either policy over the planner's
 whole input space; the ABI's constants and null-handle answers stay as they are."""
 import ctypes as C
 import subprocess
@@ -10,7 +10,7 @@ from pathlib import Path
 import pytest
 
 HERE = Path(__file__).resolve().parent
-PLAN_SRC = HERE / "native" / "loop_instances_lane_plan_host.cpp"
+PLAN_SRC = HERE / "native" / "records_plan_host.cpp"
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
@@ -23,9 +23,9 @@ def lib(pkg):
 
 
 def test_loop_planner_under_the_policy(tmp_path):
-    exe = tmp_path / "loop_instances_lane_plan_host"
+    exe = tmp_path / "records_plan_host"
     subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-o", str(exe), str(PLAN_SRC)], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = subprocess.run([str(exe), "--check", "loop-policy"], capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "loop instance lane planner:" in r.stdout and "passed: 0 failures" in r.stdout

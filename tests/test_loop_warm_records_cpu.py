@@ -1,7 +1,7 @@
 """CPU suite: warm-started closed loops with per-robot controller records (qmpc_set_loop_warm_records, include/qmpc.h) without
 a device.
 
-tests/native/loop_warm_records_plan_host.cpp enumerates the planner overload that takes the opt-in flag over the planner's
+tests/native/records_plan_host.cpp (--check loop-warm) enumerates the loop planner with the opt-in setting over the planner's
 whole input space; the ABI: the symbol is exported, a null handle is refused, the header and the binding agree on the query's
 number, and the build's unit table carries the two new translation units."""
 import ctypes as C
@@ -13,7 +13,7 @@ import pytest
 
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
-PLAN_SRC = HERE / "native" / "loop_warm_records_plan_host.cpp"
+PLAN_SRC = HERE / "native" / "records_plan_host.cpp"
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
@@ -26,9 +26,9 @@ def lib(pkg):
 
 
 def test_planner_with_the_opt_in_flag(tmp_path):
-    exe = tmp_path / "loop_warm_records_plan_host"
+    exe = tmp_path / "records_plan_host"
     subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-o", str(exe), str(PLAN_SRC)], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = subprocess.run([str(exe), "--check", "loop-warm"], capture_output=True, text=True)
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "loop warm records planner:" in r.stdout and "passed: 0 failures" in r.stdout

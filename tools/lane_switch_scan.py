@@ -7,7 +7,7 @@ QMPC_INSTANCES_AUTO with QMPC_LANE_INST_MIN=1 on one handle per horizon, batches
 (the switch-over lane_min_inst of qmpc_plan_fill.h is the smallest size from which the lane path wins at every larger one).
 --loop-instances: the same for the ticks of qmpc_loop_run_instances_device with random-variant controller and plant records -- WAVE
 against AUTO with QMPC_LANE_INST_MIN=1 and QMPC_LANE_MIN=1 on one handle per horizon, robots walking with different commands,
---ticks ticks per call timed with device events (the switch-over of plan_loop_instances' policy overload, qmpc_plan.h)."""
+--ticks ticks per call timed with device events (the switch-over of plan_loop_instances under QMPC_INSTANCES_AUTO, qmpc_plan.h)."""
 import argparse, os, sys
 from pathlib import Path
 import numpy as np
