@@ -310,8 +310,10 @@ enum qmpc_query_what {
   QMPC_QUERY_KERNEL_FOR_CONVEX_INSTANCES = 12, /* arg = batch: the qmpc_kernel_family qmpc_convex_solve_instances* launches
                                            for that size (QMPC_KERNEL_NONE, on a QuatMpc or 8-point handle too: the call is
                                            refused).  QMPC_QUERY_KERNEL_FOR_INSTANCES keeps answering NONE on a ConvexMpc handle */
-  QMPC_QUERY_CONVEX_RECORDS       = 13  /* 1: the closed loops with per-robot records accept this ConvexMpc handle
+  QMPC_QUERY_CONVEX_RECORDS       = 13, /* 1: the closed loops with per-robot records accept this ConvexMpc handle
                                            (qmpc_set_convex_records); 0 (default): they refuse it */
+  QMPC_QUERY_CONVEX_LANE_RECORDS  = 14  /* 1: ConvexMpc's calls with per-instance records may take the lane kernel with per-lane
+                                           parameters under QMPC_INSTANCES_AUTO (qmpc_set_convex_lane_records); 0 (default) */
 };
 enum qmpc_kernel_family {
   QMPC_KERNEL_NONE         = 0,
@@ -412,8 +414,8 @@ qmpc_status qmpc_set_instances_policy(qmpc_handle* h, int32_t policy);
  * plain solve takes the round-1 kernel or the lane kernel (there is no per-instance form of either for this problem) the
  * call stays on a wrench-form variant and agrees with the plain solve to the rounding between ConvexMpc's kernel families
  * (status words equal, forces within 1e-7 N).  qmpc_query(QMPC_QUERY_KERNEL_FOR_CONVEX_INSTANCES) names the family for a
- * batch size, QMPC_QUERY_LAST_KERNEL the one the last call took.  qmpc_set_instances_policy does not change this call:
- * there is no lane-per-instance form with per-lane parameters for ConvexMpc's problem.
+ * batch size, QMPC_QUERY_LAST_KERNEL the one the last call took.  By default qmpc_set_instances_policy does not change this
+ * call; the lane-per-instance form with per-lane parameters is a setting of the handle, qmpc_set_convex_lane_records below.
  *
  * Call-level: QMPC_UNSUPPORTED on a QuatMpc or 8-point handle, a reference-mode handle, or a handle whose knobs leave no
  * wrench-form kernel (QMPC_WFORM=0); QMPC_BATCH_TOO_LARGE above max_batch; QMPC_BAD_ARGUMENT for null pointers.  The
@@ -741,7 +743,7 @@ qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on);
  * the post kernel.  With records equal to the handle's values both forms give the bytes of qmpc_loop_run* on the same handle
  * (states, force and contact traces) wherever that loop solves on the same wrench-form variant, and the two forms agree with
  * each other bit for bit on any records.  Under QMPC_INSTANCES_AUTO the ticks with ctrl stay on the wave kernels at every
- * size: there is no lane-per-instance form with per-lane parameters for ConvexMpc's problem.
+ * size unless the handle also opted in to the lane form (qmpc_set_convex_lane_records below).
  *
  * Still QMPC_UNSUPPORTED with the setting on: the reference mode; ctrl together with lp->warm_start, whatever
  * qmpc_set_loop_warm_records says (plant records alone follow the plain warm-started loop); a batch with no wrench-form kernel
@@ -750,6 +752,31 @@ qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on);
  * their other buffers.  QMPC_BAD_ARGUMENT for a null handle or another value; qmpc_query(QMPC_QUERY_CONVEX_RECORDS) returns
  * the setting. */
 qmpc_status qmpc_set_convex_records(qmpc_handle* h, int32_t on);
+
+/* Opt in to the lane-per-instance form of ConvexMpc's calls with per-instance records: on = 1 (0, the default, restores the
+ * wave form at every size).  It holds until changed and takes effect only under qmpc_set_instances_policy(h,
+ * QMPC_INSTANCES_AUTO), on a ConvexMpc handle in the converged mode that has a slot of the lane kernel's parameter table; the
+ * setting does nothing on a handle of another model.
+ *   qmpc_convex_solve_instances*: from the measured switch-over on (24576 instances at N <= 12, 26624 beyond; the knob
+ *     QMPC_LANE_CINST_MIN overrides it, QMPC_VARIANT=4 takes the lane form at every size) the call runs
+ *     qmpc_lane_cinst_kernel -- the passes of the plain ConvexMpc lane kernel with the record's fields read per LANE from a
+ *     parameter block laid out like the lane workspace.  No lane pairs, no iteration cap, no hand-off: QMPC_KERNEL_LANE.  The
+ *     results belong to the lane kernel's rounding family: bit-identical to qmpc_convex_solve's lane results on a handle that
+ *     carries the same values (forces, info, trajectories), within 1e-7 N of the wave form's, status words equal.  Below the
+ *     switch-over the wave form, bit for bit.  Measured at N=10, random records: 3.5 M solves/s at 32768 and 5.8 M at 65536
+ *     instances, where the wave form does 2.7 / 2.8 M and the plain lane solve 3.9 / 6.5 M.
+ *   qmpc_loop_run_instances* / _outcomes* / _pushes* with ctrl, on a handle that also opted in with qmpc_set_convex_records:
+ *     cold-started per-tick calls from the larger of that switch-over and the plain cold loop's own take the lane form in every
+ *     tick -- the sort (stance mask, the previous record's iteration class, robots that will not solve last) and
+ *     qmpc_lane_cinst_kernel; with records equal to the handle's values the bytes of the plain ConvexMpc loop's lane tick.
+ *     Persistent-kernel sizes stay persistent; ctrl with lp->warm_start, the reference mode and a knot spacing other than 5 ms
+ *     stay refused.
+ * qmpc_query(QMPC_QUERY_KERNEL_FOR_CONVEX_INSTANCES / QMPC_QUERY_LOOP_INSTANCES_PLAN / QMPC_QUERY_LAST_KERNEL /
+ * QMPC_QUERY_DEVICE_BYTES) answer under the setting and the policy, and qmpc_prepare_instances / qmpc_prepare allocate the
+ * lane workspace, the sort scratch and 312 B per resident lane of parameter rows where the lane form is possible, so that a
+ * caller's stream capture allocates nothing.  QMPC_BAD_ARGUMENT for a null handle or another value;
+ * qmpc_query(QMPC_QUERY_CONVEX_LANE_RECORDS) returns the setting. */
+qmpc_status qmpc_set_convex_lane_records(qmpc_handle* h, int32_t on);
 
 /* ---- per-robot outcome records of the closed loop (robustness sweeps) -------------------------------------------------
  * The other half of the question above: did robot i stay up, how far did it tilt, how well did it track its command, how

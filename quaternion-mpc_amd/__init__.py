@@ -389,6 +389,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_set_loop_warm_records.restype = i32
     lib.qmpc_set_convex_records.argtypes = [vp, i32]
     lib.qmpc_set_convex_records.restype = i32
+    lib.qmpc_set_convex_lane_records.argtypes = [vp, i32]
+    lib.qmpc_set_convex_lane_records.restype = i32
     lib.qmpc_gather.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.qmpc_gather.restype = i32
     lib.qmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -546,6 +548,7 @@ EXPORTED_SYMBOLS = (
     "qmpc_convex_solve_instances",
     "qmpc_convex_solve_instances_device",
     "qmpc_set_convex_records",
+    "qmpc_set_convex_lane_records",
     "qmpc_prepare_instances",
     "qmpc_plant_params_from",
     "qmpc_sizeof_plant_params",
@@ -570,6 +573,7 @@ QUERY_INSTANCES_POLICY = 10
 QUERY_LOOP_WARM_RECORDS = 11
 QUERY_KERNEL_FOR_CONVEX_INSTANCES = 12
 QUERY_CONVEX_RECORDS = 13
+QUERY_CONVEX_LANE_RECORDS = 14
 # enum qmpc_instances_policy
 INSTANCES_WAVE, INSTANCES_AUTO = 0, 1
 INSTANCES_POLICY = {"wave": INSTANCES_WAVE, "auto": INSTANCES_AUTO}
@@ -1028,6 +1032,18 @@ class Solver:
 
     def convex_records(self) -> bool:
         return bool(self.query(QUERY_CONVEX_RECORDS))
+
+    def set_convex_lane_records(self, on: bool = True):
+        """Let ConvexMpc's calls with per-instance records (convex_solve_instances*, and with set_convex_records the ticks of the
+        record loops with ctrl) take the lane-per-instance kernel with per-lane parameters from the switch-over on, under
+        set_instances_policy(INSTANCES_AUTO) (qmpc_set_convex_lane_records; default off: the wave kernels at every size).  It
+        does nothing on a handle of another model."""
+        st = self.lib.qmpc_set_convex_lane_records(self._h, int(on))
+        if st != OK:
+            raise QmpcError(st, "qmpc_set_convex_lane_records")
+
+    def convex_lane_records(self) -> bool:
+        return bool(self.query(QUERY_CONVEX_LANE_RECORDS))
 
     def instances_policy(self) -> str:
         return {v: k for k, v in INSTANCES_POLICY.items()}[self.query(QUERY_INSTANCES_POLICY)]

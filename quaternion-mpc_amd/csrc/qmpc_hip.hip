@@ -141,6 +141,16 @@ hipError_t qmpc_wform_inst_list_launch(int var, int grid, size_t lds, hipStream_
                                        double* forces, qmpc_info* info, double* traj_u, double* traj_x, const int* sel,
                                        const int* sel_count, double* gws, const double* hstate, int hcap);
 
+// qmpc_lane_cinst.hip: ConvexMpc's per-instance parameters on the lane kernel (qmpc_set_convex_lane_records under QMPC_INSTANCES_AUTO)
+hipError_t qmpc_lane_cinst_upload_params(int pslot, hipStream_t s, const void* dev_params, size_t dev_params_size);
+hipError_t qmpc_lane_cinst_launch_only(int pslot, int batch, hipStream_t s, const void* in, const void* dev_blocks, const int* status,
+                                       double* forces, qmpc_info* info, double* ws, double* prm, unsigned slots, const int* perm,
+                                       double* traj_u, double* traj_x);
+hipError_t qmpc_lane_cinst_launch(int pslot, int batch, hipStream_t s, const void* dev_params, size_t dev_params_size, const void* in,
+                                  const void* dev_blocks, const int* status, double* forces, qmpc_info* info, double* ws, double* prm,
+                                  unsigned slots, const int* perm, double* traj_u, double* traj_x);
+hipError_t qmpc_lane_cinst_sort_launch(int batch, hipStream_t s, const void* in, const qmpc_info* prev, const int* status, int idle_last,
+                                       int* scratch);
 // qmpc_wform_inst_warm.hip / qmpc_lane_inst_warm.hip: the warm-started ticks of a closed loop with controller records
 // (qmpc_set_loop_warm_records) on the wave kernels and on the lane kernel
 hipError_t qmpc_wform_inst_warm_set_lds();
@@ -862,6 +872,8 @@ qmpc_status qmpc_prepare(qmpc_handle* h, int32_t batch) {
   // ... and where qmpc_solve_instances* of this size or the ticks of qmpc_loop_run_instances* / qmpc_loop_run_outcomes* with
   // controller records (cold-started; warm-started on a handle that opted in) take the lane kernel with per-lane parameters
   qmpc_status ps = prepare_lane_inst(h, plan_instances(h->sel, h->opts, batch, /*has_info=*/true), false);
+  // (ConvexMpc: on a handle that opted in to the lane form, qmpc_set_convex_lane_records)
+  if (ps == QMPC_OK) ps = prepare_lane_inst(h, plan_convex_instances(h->sel, h->opts, batch, /*has_info=*/true), false);
   for (int warm = 0; warm < 2 && ps == QMPC_OK; ++warm)
     ps = prepare_lane_inst(h, plan_loop_instances(h->sel, h->opts, batch, /*has_ctrl=*/true, warm != 0), true);
   if (ps != QMPC_OK) return ps;
@@ -927,7 +939,7 @@ static int* inst_status(qmpc_handle* h) {
 // handle's per-instance buffers are the same: apply_instance_params writes the record's fields into the handle's DevParams
 // whatever the model.  `convex` says which of the two a call is; the plan of a call:
 static qmpc_plan plan_inst_call(const qmpc_handle* h, bool convex, int batch, bool has_info) {
-  return convex ? plan_convex_instances(h->sel, batch) : plan_instances(h->sel, h->opts, batch, has_info);
+  return convex ? plan_convex_instances(h->sel, h->opts, batch, has_info) : plan_instances(h->sel, h->opts, batch, has_info);
 }
 // the call-level checks both entry points share (after the null-pointer ones)
 static qmpc_status instances_check(const qmpc_handle* h, bool convex, int32_t batch) {
@@ -946,8 +958,11 @@ static qmpc_status ensure_lane_inst_buffers(qmpc_handle* h, bool handoff) {
   if (handoff) (void)ensure_handoff_buffers(h);
   return QMPC_OK;
 }
-// some batch of the handle takes the lane kernel in qmpc_solve_instances* under its current policy
-static bool instances_lane_possible(const qmpc_handle* h) { return plan_instances(h->sel, h->opts, h->max_batch, true).variant == 4; }
+// some batch of the handle takes the lane kernel in qmpc_solve_instances* (ConvexMpc: qmpc_convex_solve_instances*) under its
+// current settings
+static bool instances_lane_possible(const qmpc_handle* h) {
+  return plan_inst_call(h, h->params.model == QMPC_MODEL_CONVEX, h->max_batch, true).variant == 4;
+}
 
 // The solve of one call or tick with per-instance parameters, as `p` plans it (the blocks expanded and the buffers allocated
 // already): d_in -> d_forces, d_info, and the trajectories where tu / tx are given.  Nothing here but kernels, the plain call's
@@ -957,17 +972,31 @@ static bool instances_lane_possible(const qmpc_handle* h) { return plan_instance
 //   INST_TICK_FIRST  the cold first tick of a warm-started one (p: the plan with `first`), leaving its solution in tu
 //   INST_TICK_WARM   ... its later ticks: the warm-started kernels start from tu (a robot whose previous solve failed starts cold:
 //                    check_prev) and leave theirs there
-// The wave form: the per-instance wrench-form kernel of the model.  The lane form (QuatMpc): the sort -- the plain call's by
+// The wave form: the per-instance wrench-form kernel of the model.  The lane form of QuatMpc: the sort -- the plain call's by
 // stance mask, the loops' also by the previous records' iteration classes, robots that will not solve last --, the lane kernel
 // with per-lane parameters to the cap, the per-instance list kernel on what it leaves (a warm tick's records carry the rows'
 // initial residuals, so only the cold forms honour QMPC_HANDOFF_RESTART).  The plain call uploads the lane kernel's parameter
-// block just before its launch; the loops upload it once per call, outside the capture.
+// block just before its launch; the loops upload it once per call, outside the capture.  The lane form of ConvexMpc (cold forms
+// only; qmpc_lane_cinst.hip): its sort -- contacts at the convex record's offset, a tick's also by the previous records' iteration
+// classes, robots that will not solve last -- and qmpc_lane_cinst_kernel, which has neither cap nor hand-off.
 enum inst_form { INST_CALL, INST_TICK_COLD, INST_TICK_FIRST, INST_TICK_WARM };
 static qmpc_status inst_solve(qmpc_handle* h, const qmpc_plan& p, bool convex, inst_form form, int32_t batch, const qmpc_input* d_in,
                               double* d_forces, qmpc_info* d_info, double* tu, double* tx, hipStream_t s) {
   const bool warm = form == INST_TICK_WARM;
   double* gws = p.gws ? h->d_gws : nullptr;
-  if (p.variant == 4) {
+  if (p.variant == 4 && convex) {
+    if (form != INST_CALL && form != INST_TICK_COLD) return QMPC_UNSUPPORTED;
+    const int* perm = h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr;
+    if (h->sel.lane_sort)
+      HIP_TRY(qmpc_lane_cinst_sort_launch((int)batch, s, d_in, (form != INST_CALL && p.order_prev) ? d_info : nullptr, inst_status(h),
+                                          form != INST_CALL ? h->sel.lane_sort_idle : 0, h->d_lane_scratch));
+    if (form == INST_CALL)
+      HIP_TRY(qmpc_lane_cinst_launch(h->lane_pslot, (int)batch, s, &h->dev, sizeof h->dev, d_in, inst_dev(h), inst_status(h), d_forces, d_info,
+                                     h->d_lane_ws, h->d_lane_prm, h->lane_slots, perm, tu, tx));
+    else
+      HIP_TRY(qmpc_lane_cinst_launch_only(h->lane_pslot, (int)batch, s, d_in, inst_dev(h), inst_status(h), d_forces, d_info, h->d_lane_ws,
+                                          h->d_lane_prm, h->lane_slots, perm, tu, tx));
+  } else if (p.variant == 4) {
     const bool cap = p.iter_cap > 0;
     const int* perm = h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr;
     int *hcount = cap ? h->d_handoff : nullptr, *hsel = cap ? h->d_handoff + 64 : nullptr;
@@ -1091,7 +1120,7 @@ qmpc_status qmpc_convex_solve_instances(qmpc_handle* h, int32_t batch, const qmp
 
 qmpc_status qmpc_prepare_instances(qmpc_handle* h) {
   if (!h) return QMPC_BAD_ARGUMENT;
-  const bool convex = h->params.model == QMPC_MODEL_CONVEX;      // ConvexMpc: the per-instance buffers (no lane form)
+  const bool convex = h->params.model == QMPC_MODEL_CONVEX;      // (ConvexMpc: the lane form on a handle that opted in only)
   const qmpc_status cs = instances_check(h, convex, 0);
   if (cs != QMPC_OK) return cs;
   HIP_TRY(hipSetDevice(h->device));
@@ -1115,6 +1144,12 @@ qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on) {
 qmpc_status qmpc_set_convex_records(qmpc_handle* h, int32_t on) {
   if (!h || (on != 0 && on != 1)) return QMPC_BAD_ARGUMENT;
   h->opts.convex_records = on != 0;
+  return QMPC_OK;
+}
+
+qmpc_status qmpc_set_convex_lane_records(qmpc_handle* h, int32_t on) {
+  if (!h || (on != 0 && on != 1)) return QMPC_BAD_ARGUMENT;
+  h->opts.convex_lane = on != 0;
   return QMPC_OK;
 }
 
@@ -1168,8 +1203,9 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
     case QMPC_QUERY_CONVEX_RECORDS: *value = h->opts.convex_records; return QMPC_OK;
     case QMPC_QUERY_KERNEL_FOR_CONVEX_INSTANCES:
       if (arg < 1 || arg > h->max_batch) return QMPC_BAD_ARGUMENT;
-      *value = plan_convex_instances(h->sel, (int)arg).family;
+      *value = plan_convex_instances(h->sel, h->opts, (int)arg, true).family;
       return QMPC_OK;
+    case QMPC_QUERY_CONVEX_LANE_RECORDS: *value = h->opts.convex_lane; return QMPC_OK;
     default: return QMPC_BAD_ARGUMENT;
   }
 }
@@ -1814,7 +1850,8 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
     return QMPC_OK;
   };
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
-  if (d_ctrl && lpp.variant == 4) HIP_TRY(qmpc_lane_inst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
+  if (d_ctrl && lpp.variant == 4 && crec) HIP_TRY(qmpc_lane_cinst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
+  if (d_ctrl && lpp.variant == 4 && !crec) HIP_TRY(qmpc_lane_inst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   if (d_ctrl && warm && lpp.variant == 4) HIP_TRY(qmpc_lane_inst_warm_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   return replay_ticks(h, lpp, s, ticks, warm, one_tick);
 }

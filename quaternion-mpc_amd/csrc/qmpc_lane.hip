@@ -35,8 +35,10 @@
 // (qmpc_solve_instances* under QMPC_INSTANCES_AUTO) -- what it shares with the two units above is the text up to the kernels.
 // QL_UNIT 4 (qmpc_lane_inst_warm.hip includes this file): that kernel warm-started, the later ticks of a closed loop with
 // controller records under lp->warm_start.
-#if !defined(QL_UNIT) || (QL_UNIT != 1 && QL_UNIT != 2 && QL_UNIT != 3 && QL_UNIT != 4)
-#error "QL_UNIT must be 1 (the converged mode's unit), 2 (the reference mode's unit), 3 (per-lane parameters) or 4 (... warm-started)"
+// QL_UNIT 5 (qmpc_lane_cinst.hip includes this file): ConvexMpc's converged-mode kernel with per-lane parameters
+// (qmpc_convex_solve_instances* and the record loops on a handle that opted in: qmpc_set_convex_lane_records).
+#if !defined(QL_UNIT) || (QL_UNIT != 1 && QL_UNIT != 2 && QL_UNIT != 3 && QL_UNIT != 4 && QL_UNIT != 5)
+#error "QL_UNIT must be 1 (the converged mode's unit), 2 (the reference mode's unit), 3 (per-lane parameters), 4 (... warm-started) or 5 (... ConvexMpc)"
 #endif
 namespace qmpc {
 namespace lane {

@@ -546,7 +546,8 @@ QL_FN void srbd_step_fw(const PT& P, const double gb[3], const double* x, const 
 enum { MD_QUAT = 0, MD_CONVEX = 1 };
 enum { CVR_YAW = 0, CVR_RATE, CVR_POS, CVR_VX = 5, CVR_VY = 6 };      // refp of the convex model (qmpc_device.h CR_*)
 // Iw(yaw)^-1 = Rz diag(1/I) Rz': W = {w00, w01, w11, wzz}
-QL_FN void cv_winv(const DevParams& P, double c, double s, double W[4]) {
+template <class PT>
+QL_FN void cv_winv(const PT& P, double c, double s, double W[4]) {
   const double a = P.Iinv[0], b = P.Iinv[4];
   W[0] = c * c * a + s * s * b;
   W[1] = c * s * (a - b);
@@ -569,7 +570,8 @@ QL_FN void cv_cross_acc(const double r[3], const double u[3], double t[3]) {    
   t[2] += r[0] * u[1] - r[1] * u[0];
 }
 // explicit midpoint of ct_srb_dynamics (AltroUtils.cpp:9-22 on :224-293) given the force sum F and the torque sum tau
-QL_FN void cv_step_fw(const DevParams& P, const double* x, const double F[3], const double tau[3], double* xn) {
+template <class PT>
+QL_FN void cv_step_fw(const PT& P, const double* x, const double F[3], const double tau[3], double* xn) {
   double s0, c0, W[4];
   sincos(x[2], &s0, &c0);
   cv_winv(P, c0, s0, W);
@@ -593,7 +595,8 @@ QL_FN void cv_step_fw(const DevParams& P, const double* x, const double F[3], co
   xn[12] = 0.0;
 }
 // reference state of knot k (ConvexMpc.cpp:95-106)
-QL_FN void cv_xref_at(const DevParams& P, const double rp[13], int k, double* xr) {
+template <class PT>
+QL_FN void cv_xref_at(const PT& P, const double rp[13], int k, double* xr) {
   const double h_ms = P.h_ref * 1000.0;
 #pragma unroll
   for (int i = 0; i < 13; ++i) xr[i] = 0.0;
@@ -603,13 +606,15 @@ QL_FN void cv_xref_at(const DevParams& P, const double rp[13], int k, double* xr
   xr[9] = rp[CVR_VX]; xr[10] = rp[CVR_VY];
 }
 // Iw(yaw_m)^-1 of knot state x (the per-point map of the linearisation at that knot)
-QL_FN void cv_winv_mid(const DevParams& P, double yaw, double wz, double W[4]) {
+template <class PT>
+QL_FN void cv_winv_mid(const PT& P, double yaw, double wz, double W[4]) {
   double sm_, cm_;
   sincos(yaw + P.hh * wz, &sm_, &cm_);
   cv_winv(P, cm_, sm_, W);
 }
 // A1, A3, Wt of a knot from its state and torque sum (AltroUtils.cpp:295-359 through the midpoint rule :78-110)
-QL_FN void cv_expansion(const DevParams& P, const double* x, const double tau[3], double A1[9], double A3[9], double Wt[9]) {
+template <class PT>
+QL_FN void cv_expansion(const PT& P, const double* x, const double tau[3], double A1[9], double A3[9], double Wt[9]) {
   double s0, c0, W0[4], Wm[4];
   sincos(x[2], &s0, &c0);
   cv_winv(P, c0, s0, W0);

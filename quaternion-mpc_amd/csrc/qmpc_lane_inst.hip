@@ -10,6 +10,7 @@
 namespace qmpc {
 namespace lane {
 
+#define QL_INST_MD MD_QUAT
 #include "qmpc_lane_inst_calls.inc"
 
 // pi: the instance's expanded block (qmpc_expand_instances_kernel); its instance fields become the lane's rows first

@@ -12,6 +12,7 @@
 namespace qmpc {
 namespace lane {
 
+#define QL_INST_MD MD_QUAT
 #include "qmpc_lane_inst_calls.inc"
 
 // pi: the instance's expanded block (its instance fields become the lane's rows first, in every tick: which lane a robot takes

@@ -23,6 +23,9 @@ namespace qmpc {
 //   QMPC_LANE_INST_MIN    ... of qmpc_solve_instances* under QMPC_INSTANCES_AUTO (per-instance parameters on the lane kernel); the
 //                         ticks of qmpc_loop_run_instances* / qmpc_loop_run_outcomes* with controller records switch over at the
 //                         larger of this and the cold-started loop's own switch-over (QMPC_LANE_MIN moves that one)
+//   QMPC_LANE_CINST_MIN   ... of qmpc_convex_solve_instances* under QMPC_INSTANCES_AUTO on a handle that opted in with
+//                         qmpc_set_convex_lane_records (ConvexMpc's lane kernel with per-lane parameters); the ticks of its record
+//                         loops with controller records switch over at the larger of this and the cold-started loop's own
 //   QMPC_LANE_CAP, QMPC_LANE_CAP_LOOP, QMPC_LANE_CAP_WARM
 //                         iteration cap of the lane kernel before the straggler hand-off: cold plain solves, cold-started
 //                         loops, warm-started loop ticks (0: no hand-off)
@@ -52,6 +55,7 @@ struct qmpc_select {
   bool handoff_restart;
   int lane_sort, lane_pair, loop_fused, ref_wform_maxn, zero_copy;
   int lane_sort_idle;     // loop ticks with controller records on the lane kernel: robots that will not solve sort last
+  int lane_min_cinst;     // ... in qmpc_convex_solve_instances* under QMPC_INSTANCES_AUTO on a handle that opted in (qmpc_opts::convex_lane)
 };
 
 static inline int model_nl(int model) { return model == QMPC_MODEL_QUAT8 ? 8 : 4; }
@@ -284,14 +288,15 @@ static inline qmpc_plan plan(const qmpc_select& s, int batch, qmpc_call kind, bo
   return wave(body());
 }
 
-// A handle's run-time settings (qmpc_set_instances_policy, qmpc_set_loop_warm_records, qmpc_set_convex_records, and what became of
-// its hand-off records): what the planners of the calls with per-instance records read besides the selection state.  The
+// A handle's run-time settings (qmpc_set_instances_policy, qmpc_set_loop_warm_records, qmpc_set_convex_records,
+// qmpc_set_convex_lane_records, and what became of its hand-off records): what the planners of the calls with per-instance records read besides the selection state.  The
 // handle holds one and passes it whole.
 struct qmpc_opts {
   int inst_policy = QMPC_INSTANCES_WAVE;      // qmpc_instances_policy of the solves and ticks with per-instance parameters
   bool handoff_failed = false;                // the hand-off records could not be allocated: the pure lane kernel
   bool loop_warm_records = false;             // the loops with controller records accept lp->warm_start (QuatMpc)
   bool convex_records = false;                // the loops with records accept a ConvexMpc handle
+  bool convex_lane = false;                   // ConvexMpc's calls with per-instance records may take the lane kernel (under AUTO)
 };
 
 // The plan of qmpc_solve_instances* (per-instance parameters, qmpc_wform.hip: qmpc_solve_w_inst_kernel).  `has_info`: the call
@@ -320,9 +325,9 @@ static inline qmpc_plan plan_instances(const qmpc_select& s, const qmpc_opts& o,
 
 // The plan of qmpc_convex_solve_instances* (ConvexMpc's problem with per-instance parameters; qmpc_wform_cinst.hip:
 // qmpc_solve_cw_inst_kernel<3|5|6>).  NONE unless the handle is ConvexMpc in the converged mode with the wrench form on.
-// Where a plain solve of `batch` instances on the wave kernels (lane_slot off: there is no lane form with per-lane parameters
-// for this problem, whatever the handle's qmpc_opts) takes a wrench-form variant: that variant, and the results are the plain
-// solve's bit for bit.  Where it falls to the round-1 family (beyond one resident round of the workspace form, QMPC_VARIANT
+// This is the wave form: the plan of every handle that did not opt in to the lane form (the overload below).
+// Where a plain solve of `batch` instances on the wave kernels (lane_slot off) takes a wrench-form variant: that variant, and the
+// results are the plain solve's bit for bit.  Where it falls to the round-1 family (beyond one resident round of the workspace form, QMPC_VARIANT
 // 2 / 3) there is no per-instance dense kernel, and the call keeps the wrench form: 6 (slack arrays in the workspace too: two
 // waves per SIMD) under plan()'s own condition for it, else 5 while its layout leaves a CU two instances (80 KB), else 3 if an
 // instance fits a CU at all; NONE otherwise.
@@ -343,6 +348,20 @@ static inline qmpc_plan plan_convex_instances(const qmpc_select& s, int batch) {
   p.gws = var != 3;
   return p;
 }
+// ... with the handle's settings.  The lane form (qmpc_lane_cinst.hip: qmpc_lane_cinst_kernel) is opt-in per handle
+// (qmpc_set_convex_lane_records -> convex_lane) and taken only under QMPC_INSTANCES_AUTO, on a handle with a slot of the lane
+// kernel's parameter table, where the wave plan above is not NONE: from the switch-over lane_min_cinst on (QMPC_LANE_CINST_MIN
+// moves it; QMPC_VARIANT=4: at every size) the lane fields of the plain ConvexMpc solve's plan for this batch -- variant 4,
+// QMPC_KERNEL_LANE (ConvexMpc's lane kernel has neither cap nor hand-off), upload_params.  Everywhere else the wave plan.
+static inline qmpc_plan plan_convex_instances(const qmpc_select& s, const qmpc_opts& o, int batch, bool has_info) {
+  const qmpc_plan w = plan_convex_instances(s, batch);
+  if (!o.convex_lane || o.inst_policy != QMPC_INSTANCES_AUTO || !s.lane_slot || w.family == QMPC_KERNEL_NONE) return w;
+  if (s.variant != 4 && batch < s.lane_min_cinst) return w;
+  qmpc_select t = s;
+  t.lane_min_batch = 0;      // the switch-over is this call's own: the plain plan only names the lane kernel's fields
+  const qmpc_plan p = plan(t, batch, QMPC_CALL_PLAIN, has_info, o.handoff_failed);
+  return p.variant == 4 ? p : w;
+}
 
 // The plan of the closed loops with per-robot controller and / or plant records (qmpc_loop_run_instances*, _outcomes*,
 // _pushes*; qmpc_loop_inst.hip and its siblings, on a ConvexMpc handle qmpc_loop_crec.hip).  `has_ctrl`: controller records are
@@ -354,8 +373,7 @@ static inline qmpc_plan plan_convex_instances(const qmpc_select& s, int batch) {
 //   per tick    otherwise, fused = false.  Without controller records the plain loop's tick (lane kernel and hand-off
 //               included).  With them the plan of the model's solve with per-instance parameters under the default settings
 //               (plan_instances: qmpc_solve_w_inst_kernel, warm-started qmpc_solve_w_inst_warm_kernel; ConvexMpc:
-//               plan_convex_instances -- the wave kernels at every size under either policy, there is no lane form with per-lane
-//               parameters for that problem).
+//               plan_convex_instances(s, batch): the wave kernels).
 //   lane form   of QuatMpc's per-tick solve with controller records, under QMPC_INSTANCES_AUTO on a handle with a slot of the
 //               lane kernel's parameter table: from the LARGER of the two switch-overs the tick combines on -- that of
 //               qmpc_solve_instances* (lane_min_inst; QMPC_LANE_INST_MIN moves it) and the plain loop's own (cold-started:
@@ -366,6 +384,9 @@ static inline qmpc_plan plan_convex_instances(const qmpc_select& s, int batch) {
 //               (16384 and 14336 / 14848), the warm one 18432, 20480 at N = 13 ... 22.  QMPC_VARIANT=4: the pure lane kernel
 //               wherever the per-tick form runs, as for the plain loop.  `first`: the lane kernel without cap and hand-off (the
 //               plain loop's QMPC_CALL_WARM_LOOP_FIRST); on the wave kernels the first tick's variant is the tick's.
+//               ConvexMpc's per-tick solve with controller records takes it on a handle that opted in to BOTH convex_records and
+//               convex_lane, under the same policy: from the larger of lane_min_cinst and lane_min_loop_cold the lane fields of the
+//               plain cold tick (qmpc_lane_cinst_kernel: no cap, no hand-off; order_prev, no upload inside the tick).
 // NONE: the reference mode; a model other than QuatMpc and, on a handle that opted in (convex_records), ConvexMpc; controller
 // records without a wrench-form kernel for the batch (QMPC_WFORM=0, ...); controller records with the warm start unless a
 // QuatMpc handle opted in (loop_warm_records; never on ConvexMpc).
@@ -381,10 +402,12 @@ static inline qmpc_plan plan_loop_instances(const qmpc_select& s, const qmpc_opt
                 : convex  ? plan_convex_instances(s, batch)
                           : plan_instances(s, qmpc_opts(), batch, true);
   w.fused = false;
-  if (!has_ctrl || convex || o.inst_policy != QMPC_INSTANCES_AUTO || w.family == QMPC_KERNEL_NONE || !s.lane_slot) return w;
+  if (!has_ctrl || (convex && !o.convex_lane) || o.inst_policy != QMPC_INSTANCES_AUTO || w.family == QMPC_KERNEL_NONE || !s.lane_slot)
+    return w;
   qmpc_select l = s;
   int& own = warm ? l.lane_min_warm : l.lane_min_loop_cold;
-  if (s.variant != 4 && batch < (s.lane_min_inst > own ? s.lane_min_inst : own)) return w;
+  const int inst_min = convex ? s.lane_min_cinst : s.lane_min_inst;
+  if (s.variant != 4 && batch < (inst_min > own ? inst_min : own)) return w;
   own = 0;      // the switch-over is this call's own: the plain tick's plan only names the lane kernel's fields
   qmpc_plan p = plan(l, batch, tick, true, o.handoff_failed);
   if (p.variant != 4) return w;

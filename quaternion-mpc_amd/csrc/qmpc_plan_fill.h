@@ -97,6 +97,18 @@ constexpr int kLaneRefMinBatchConvexLong = 19456;
 // 14336 / 14848: this call also pays the expansion kernel and the per-lane rows.)
 constexpr int kLaneMinInst = 16384;           // horizons up to 12
 constexpr int kLaneMinInstLong = 16384;       // longer horizons
+// qmpc_convex_solve_instances* under QMPC_INSTANCES_AUTO on a handle that opted in (qmpc_set_convex_lane_records): ConvexMpc's lane
+// kernel with per-lane parameters (qmpc_lane_cinst.hip) against the per-instance wave kernel (qmpc_solve_cw_inst_kernel), random-variant
+// records, batches 8192 ... 65536 in steps of 2048 (tools/lane_switch_scan.py --instances --model convex and --loop-instances
+// --model convex, profiles/r16_convex_lane_records.txt).  One switch-over serves the solve and the loops' ticks, so it is the
+// smallest scanned size from which the lane path is faster at every larger one in BOTH scans.  Solves, N=10 20480: wave 8.28 vs
+// lane 9.01 ms, 22528: 9.05 vs 8.90, 24576: 9.70 vs 8.68, 65536: 24.0 vs 10.9; N=20 22528: 18.5 vs 19.4, 24576: 20.0 vs 19.4,
+// 26624: 21.7 vs 19.9, 65536: 49.8 vs 28.7.  Loop ticks (20 ticks), N=10 22528: 97.0 vs 98.1 ms, 24576: 105.5 vs 101.3, 65536:
+// 269.7 vs 127.1; N=20 24576: 199.3 vs 210.8, 26624: 215.5 vs 210.6, 65536: 509.4 vs 261.8.  (Later than the plain ConvexMpc
+// solve's 18432 / 22528: without lane pairs a launch below 32769 instances costs what 32768 cost, and this call also pays the
+// expansion kernel and the per-lane rows.)
+constexpr int kLaneMinCinst = 24576;          // horizons up to 12
+constexpr int kLaneMinCinstLong = 26624;      // longer horizons
 // env(name): the knob's value as a string, or null (qmpc_create passes std::getenv; qmpc_plan.h lists the knobs);
 // lane_slot: qmpc_create obtained a slot of the lane kernel's parameter table.  false: qmpc_create refuses the horizon (the
 // round-1 workspace layout does not fit a CU).
@@ -132,6 +144,7 @@ inline bool qmpc_fill_select(qmpc_select* h, const qmpc_params* params, Env env,
   h->lane_min_warm = (lm || params->model != QMPC_MODEL_QUAT) ? h->lane_min_batch
                                                               : (N <= 12 ? kLaneMinWarm : (N <= 22 ? kLaneMinWarmLong : kLaneMinWarmVeryLong));
   h->lane_min_inst = knob("QMPC_LANE_INST_MIN", N <= 12 ? kLaneMinInst : kLaneMinInstLong);
+  h->lane_min_cinst = knob("QMPC_LANE_CINST_MIN", N <= 12 ? kLaneMinCinst : kLaneMinCinstLong);
   // Straggler hand-off (cold plain solves of QuatMpc's problem on the lane kernel): a launch of the lane kernel lasts as
   // long as its slowest instance -- 23 interior-point iterations at N=10 (mean 13.6), 31 at N=20 (mean 14.6) -- while
   // only 8 % / 10 % of the instances are still running after 16 / 17.  The lane kernel stops there, leaves the state of

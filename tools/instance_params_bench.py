@@ -7,7 +7,9 @@ after warm-up; median of the repetitions.  The per-instance calls include their 
 instance) and, under AUTO, the stance sort and the hand-off.
     python tools/instance_params_bench.py [--policy wave|auto|both] [--reps 10] [--warmup 3] [--sizes 10:1024,...] [--json FILE]
 --model convex: ConvexMpc's problem instead -- qmpc_convex_solve_device against qmpc_convex_solve_instances_device on
-    random_go1_convex_states, records from random_go1_convex_variants; the call has no lane form, so there is one policy column.
+    random_go1_convex_states, records from random_go1_convex_variants; the handle opts in to the lane form
+    (qmpc_set_convex_lane_records), so the AUTO column is qmpc_lane_cinst_kernel from the switch-over on and the WAVE column the
+    wave form, as for QuatMpc.
 --plain-lib FILE: another build of the library (e.g. the parent revision's) whose plain solve joins the alternation as
     "base_plain", with a handle of its own on the same buffers: the per-instance call over THAT plain solve, in the same job."""
 import argparse
@@ -83,7 +85,9 @@ def main():
             p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
             rec = pkg.random_go1_trot_states(B, config_id=2)
         s = pkg.Solver(p, B, device=0, lib=lib)
-        policies = ("wave",) if convex else ("wave", "auto") if a.policy == "both" else (a.policy,)
+        policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
+        if convex:
+            s.set_convex_lane_records(True)      # (takes effect under AUTO only)
         if "auto" in policies:
             s.set_instances_policy("auto")      # the buffers of every call below are allocated here, not in a timed call
         s.prepare(B)

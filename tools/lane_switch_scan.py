@@ -7,7 +7,10 @@ QMPC_INSTANCES_AUTO with QMPC_LANE_INST_MIN=1 on one handle per horizon, batches
 (the switch-over lane_min_inst of qmpc_plan_fill.h is the smallest size from which the lane path wins at every larger one).
 --loop-instances: the same for the ticks of qmpc_loop_run_instances_device with random-variant controller and plant records -- WAVE
 against AUTO with QMPC_LANE_INST_MIN=1 and QMPC_LANE_MIN=1 on one handle per horizon, robots walking with different commands,
---ticks ticks per call timed with device events (the switch-over of plan_loop_instances under QMPC_INSTANCES_AUTO, qmpc_plan.h)."""
+--ticks ticks per call timed with device events (the switch-over of plan_loop_instances under QMPC_INSTANCES_AUTO, qmpc_plan.h).
+--model convex (with --instances or --loop-instances): ConvexMpc's calls on a handle that opted in to the lane form
+(qmpc_set_convex_lane_records; for the loops also qmpc_set_convex_records), QMPC_LANE_CINST_MIN=1 in place of QMPC_LANE_INST_MIN:
+the switch-over lane_min_cinst of qmpc_plan_fill.h."""
 import argparse, os, sys
 from pathlib import Path
 import numpy as np
@@ -22,15 +25,23 @@ ap.add_argument("--loop-instances", action="store_true")
 ap.add_argument("--ticks", type=int, default=20)
 ap.add_argument("--step", type=int, default=2048)
 ap.add_argument("--horizons", default="10,20")
+ap.add_argument("--model", default="quat", choices=("quat", "convex"))
+ap.add_argument("--start", type=int, default=8192)
 a = ap.parse_args()
 pkg = g._load_pkg(); lib = pkg.load_library()
+convex = a.model == "convex"
+default_params = pkg.default_convex_params if convex else pkg.default_params
+variants = pkg.random_go1_convex_variants if convex else pkg.random_go1_variants
+def opt_in(s):      # noqa: E302
+    if convex:
+        s.set_convex_records(True); s.set_convex_lane_records(True)
 import torch  # noqa: E402
 if a.loop_instances:
-    os.environ["QMPC_LANE_INST_MIN"] = "1"
+    os.environ["QMPC_LANE_CINST_MIN" if convex else "QMPC_LANE_INST_MIN"] = "1"
     os.environ["QMPC_LANE_MIN"] = "1"      # (the tick's switch-over is the larger of the two)
     BMAX, T = 65536, a.ticks
     for N in (int(x) for x in a.horizons.split(",")):
-        p = pkg.default_params(N, 0, lib)
+        p = default_params(N, 0, lib)
         lp = pkg.default_loop_params(lib)
         rng = np.random.default_rng(5)
         cmds = np.zeros((BMAX, 7))
@@ -39,9 +50,10 @@ if a.loop_instances:
         cmds[:, 6] = (rng.random(BMAX) < 0.85).astype(float)
         stand = cmds.copy(); stand[:, 6] = 0.0
         st = pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, BMAX), lib=lib)
-        ctrl = pkg.random_go1_variants(BMAX, seed=13, base=p); ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
+        ctrl = variants(BMAX, seed=13, base=p); ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
         plant = pkg.random_go1_plants(BMAX, seed=11, base=p, payload=(-1.0, 3.0), force=(0.0, 10.0))
         s = pkg.Solver(p, BMAX, 0, lib)
+        opt_in(s)
         s.set_instances_policy("auto"); s.prepare(BMAX); s.prepare_instances()
         st = s.loop_run_instances(st, 6, lp, ctrl=ctrl, plant=plant)
         st["movement_mode"] = cmds[:, 6]
@@ -51,7 +63,7 @@ if a.loop_instances:
         d_st = d_st0.clone()
         stream = torch.cuda.Stream(); torch.cuda.synchronize()
         first, wins = None, []
-        for B in range(8192, BMAX + 1, a.step):
+        for B in range(a.start, BMAX + 1, a.step):
             ms = {"wave": [], "auto": []}
             for r in range(a.reps + 1):
                 for pol in ms:
@@ -77,28 +89,31 @@ if a.loop_instances:
         print(f"N={N}: the lane ticks are faster at every scanned size from {first} on", flush=True)
     sys.exit(0)
 if a.instances:
-    os.environ["QMPC_LANE_INST_MIN"] = "1"
+    os.environ["QMPC_LANE_CINST_MIN" if convex else "QMPC_LANE_INST_MIN"] = "1"
     BMAX = 65536
     for N in (int(x) for x in a.horizons.split(",")):
-        p = pkg.default_params(N, 0, lib)
-        rec = pkg.random_go1_trot_states(BMAX, config_id=3 if N == 20 else 2)
-        ip = pkg.random_go1_variants(BMAX, seed=13, base=p)
+        p = default_params(N, 0, lib)
+        rec = pkg.random_go1_convex_states(BMAX, config_id=13) if convex else pkg.random_go1_trot_states(BMAX, config_id=3 if N == 20 else 2)
+        ip = variants(BMAX, seed=13, base=p)
         d_in = torch.from_numpy(rec.view(np.uint8).copy()).cuda(); d_ip = torch.from_numpy(ip.view(np.uint8).copy()).cuda()
         d_f = torch.zeros(BMAX, 12, dtype=torch.float64, device="cuda"); d_i = torch.zeros(BMAX, 5, dtype=torch.float64, device="cuda")
         s = pkg.Solver(p, BMAX, 0, lib)
+        opt_in(s)
         s.set_instances_policy("auto"); s.prepare(BMAX); s.prepare_instances()
+        solve_dev = s.convex_solve_instances_device if convex else s.solve_instances_device
+        kernel_for = s.kernel_for_convex_instances if convex else s.kernel_for_instances
         first = None
         wins = []
-        for B in range(8192, BMAX + 1, 2048):
+        for B in range(a.start, BMAX + 1, a.step):
             ms = {"wave": [], "auto": []}
             for r in range(a.reps + 2):
                 for pol in ms:
                     s.set_instances_policy(pol)
-                    s.solve_instances_device(B, d_in.data_ptr(), d_ip.data_ptr(), d_f.data_ptr(), d_i.data_ptr()); s.wait()
+                    solve_dev(B, d_in.data_ptr(), d_ip.data_ptr(), d_f.data_ptr(), d_i.data_ptr()); s.wait()
                     if r >= 2: ms[pol].append(s.last_kernel_ms())
             kern = {}
             for pol in ms:
-                s.set_instances_policy(pol); kern[pol] = s.kernel_for_instances(B)
+                s.set_instances_policy(pol); kern[pol] = kernel_for(B)
             mw, ml = float(np.median(ms["wave"])), float(np.median(ms["auto"]))
             wins.append((B, ml < mw))
             print(f"N={N} B={B}: wave {kern['wave']} {mw:.3f} ms ({B / mw / 1e3:.3f} M/s) vs auto {kern['auto']} {ml:.3f} ms ({B / ml / 1e3:.3f} M/s)  "

@@ -27,7 +27,8 @@ per-robot calls include their expansion kernels.
     both adds the calls with records under AUTO (the lane form from its switch-over on).
 --model convex: the default comparison (plain / plant records / controller + plant records) on a ConvexMpc handle that opted in
     with qmpc_set_convex_records, with the commands of the ConvexMpc loop tests and records around default_convex_params
-    (random_go1_convex_variants).  With ctrl the ticks stay on the wave kernels at every size under either policy."""
+    (random_go1_convex_variants).  The handle also opts in to the lane form (qmpc_set_convex_lane_records): with ctrl the ticks
+    take qmpc_lane_cinst_kernel from the switch-over on under AUTO and stay on the wave kernels under WAVE."""
 import argparse
 import importlib.util
 import json
@@ -327,6 +328,7 @@ def main():
         s = pkg.Solver(p, B, device=0, lib=lib)
         if convex:
             s.set_convex_records(True)
+            s.set_convex_lane_records(True)      # (takes effect under AUTO only)
         for pol in policies:      # (the buffers of every policy asked for: allocated before anything is timed)
             s.set_instances_policy(pol)
             s.prepare(B)

@@ -4,14 +4,17 @@ gait period (91 ticks of 5 ms at 2.2 Hz), every robot shoved once (qmpc_loop_run
 still up per cell from the outcome records.  The robots of a cell differ in their true plant (random_go1_plants: payload and
 inertia); the controller is the handle's and is not told about the push.
     python tools/push_recovery.py [--impulses 2,4,6,8,10] [--starts 13] [--length 10] [--per-cell 8] [--speed 0.3] [--settle 60]
-                                  [--recover 200] [--horizon 10] [--controller quat|convex|both] [--json FILE]
+                                  [--recover 200] [--horizon 10] [--controller quat|convex|both] [--ctrl-records] [--json FILE]
 Every robot stands for 6 ticks, trots at --speed for --settle ticks, is shoved at tick 6 + settle + start for --length ticks with
 force impulse / (length dt) in its cell's direction (0 degrees: ahead, 90: to its left), and trots on until --recover ticks after
 the last start.  Down: below 0.15 m or tilted beyond 60 degrees (qmpc_default_outcome_params); stop_when_down halts a fallen robot.
 Prints one table per impulse (rows: start tick in the gait period, columns: direction) and the marginals.  The figures are whatever
 the run gives.
 --controller: QuatMpc (default), ConvexMpc (a handle that opted in with qmpc_set_convex_records), or both -- the same pushes,
-plants and commands under each controller, one summary per controller.  --horizon is then each controller's horizon."""
+plants and commands under each controller, one summary per controller.  --horizon is then each controller's horizon.
+--ctrl-records: every robot also carries a controller record (the handle's values: the same controller) and the handle takes
+QMPC_INSTANCES_AUTO, a ConvexMpc handle with qmpc_set_convex_lane_records as well -- the launch a sweep over per-robot controllers
+takes: from the switch-over on the lane kernel with per-lane parameters under either controller."""
 import argparse
 import importlib.util
 import json
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--horizon", type=int, default=10)
     ap.add_argument("--json", default=None)
     ap.add_argument("--controller", choices=("quat", "convex", "both"), default="quat")
+    ap.add_argument("--ctrl-records", action="store_true")
     a = ap.parse_args()
     pkg = load_pkg()
     lib = pkg.load_library()
@@ -82,12 +86,18 @@ def run(a, pkg, lib, controller):
     s = pkg.Solver(p, B, device=0, lib=lib)
     if convex:
         s.set_convex_records(True)
-    form = s.loop_instances_plan(B, False, False)
+    ctrl = None
+    if a.ctrl_records:
+        ctrl = pkg.instance_params(p, B)
+        s.set_instances_policy("auto")
+        if convex:
+            s.set_convex_lane_records(True)
+    form = s.loop_instances_plan(B, ctrl is not None, False)
     total = a.settle + PERIOD + a.recover
     w0 = time.perf_counter()
-    st, oc = s.loop_run_pushes(st, 6, push, lp, plant=plant, op=op)
+    st, oc = s.loop_run_pushes(st, 6, push, lp, ctrl=ctrl, plant=plant, op=op)
     st["movement_mode"] = 1.0
-    st, oc = s.loop_run_pushes(st, total, push, lp, plant=plant, op=op, outcomes=oc)
+    st, oc = s.loop_run_pushes(st, total, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc)
     wall = time.perf_counter() - w0
     s.close()
     up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, a.per_cell)
