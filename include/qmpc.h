@@ -303,7 +303,8 @@ enum qmpc_query_what {
                                            lp->warm_start: the launch qmpc_loop_run_instances* takes, 16 * form + family --
                                            form 1 the persistent kernel, 2 the per-tick sequence; family the
                                            qmpc_kernel_family of its solve.  0: the call is refused.  Bits 32 and 33 together
-                                           answer under the handle's qmpc_set_loop_warm_records setting (default: refused) */
+                                           answer under the handle's qmpc_set_loop_warm_records setting (default: refused;
+                                           a ConvexMpc handle: under qmpc_set_convex_warm_records) */
   QMPC_QUERY_INSTANCES_POLICY     = 10, /* the handle's policy for qmpc_solve_instances*, a qmpc_instances_policy value */
   QMPC_QUERY_LOOP_WARM_RECORDS    = 11, /* 1: the closed loops with controller records accept lp->warm_start on this handle
                                            (qmpc_set_loop_warm_records); 0 (default): they refuse it */
@@ -312,8 +313,10 @@ enum qmpc_query_what {
                                            refused).  QMPC_QUERY_KERNEL_FOR_INSTANCES keeps answering NONE on a ConvexMpc handle */
   QMPC_QUERY_CONVEX_RECORDS       = 13, /* 1: the closed loops with per-robot records accept this ConvexMpc handle
                                            (qmpc_set_convex_records); 0 (default): they refuse it */
-  QMPC_QUERY_CONVEX_LANE_RECORDS  = 14  /* 1: ConvexMpc's calls with per-instance records may take the lane kernel with per-lane
+  QMPC_QUERY_CONVEX_LANE_RECORDS  = 14, /* 1: ConvexMpc's calls with per-instance records may take the lane kernel with per-lane
                                            parameters under QMPC_INSTANCES_AUTO (qmpc_set_convex_lane_records); 0 (default) */
+  QMPC_QUERY_CONVEX_WARM_RECORDS  = 15  /* 1: the closed loops with controller records accept lp->warm_start on this ConvexMpc
+                                           handle (qmpc_set_convex_warm_records, with qmpc_set_convex_records); 0 (default) */
 };
 enum qmpc_kernel_family {
   QMPC_KERNEL_NONE         = 0,
@@ -746,7 +749,8 @@ qmpc_status qmpc_set_loop_warm_records(qmpc_handle* h, int32_t on);
  * size unless the handle also opted in to the lane form (qmpc_set_convex_lane_records below).
  *
  * Still QMPC_UNSUPPORTED with the setting on: the reference mode; ctrl together with lp->warm_start, whatever
- * qmpc_set_loop_warm_records says (plant records alone follow the plain warm-started loop); a batch with no wrench-form kernel
+ * qmpc_set_loop_warm_records says, unless the handle also opted in with qmpc_set_convex_warm_records below (plant records alone
+ * follow the plain warm-started loop); a batch with no wrench-form kernel
  * under the handle's knobs with ctrl; a handle whose knot spacing is not the controller period of 5 ms (as qmpc_loop_run*).
  * Memory: the calls without outcome records run the outcome step on a scratch of 128 B x max_batch the handle allocates with
  * their other buffers.  QMPC_BAD_ARGUMENT for a null handle or another value; qmpc_query(QMPC_QUERY_CONVEX_RECORDS) returns
@@ -769,14 +773,38 @@ qmpc_status qmpc_set_convex_records(qmpc_handle* h, int32_t on);
  *     cold-started per-tick calls from the larger of that switch-over and the plain cold loop's own take the lane form in every
  *     tick -- the sort (stance mask, the previous record's iteration class, robots that will not solve last) and
  *     qmpc_lane_cinst_kernel; with records equal to the handle's values the bytes of the plain ConvexMpc loop's lane tick.
- *     Persistent-kernel sizes stay persistent; ctrl with lp->warm_start, the reference mode and a knot spacing other than 5 ms
- *     stay refused.
+ *     Persistent-kernel sizes stay persistent; the reference mode and a knot spacing other than 5 ms stay refused, and so
+ *     does ctrl with lp->warm_start unless the handle opted in with qmpc_set_convex_warm_records below.
  * qmpc_query(QMPC_QUERY_KERNEL_FOR_CONVEX_INSTANCES / QMPC_QUERY_LOOP_INSTANCES_PLAN / QMPC_QUERY_LAST_KERNEL /
  * QMPC_QUERY_DEVICE_BYTES) answer under the setting and the policy, and qmpc_prepare_instances / qmpc_prepare allocate the
  * lane workspace, the sort scratch and 312 B per resident lane of parameter rows where the lane form is possible, so that a
  * caller's stream capture allocates nothing.  QMPC_BAD_ARGUMENT for a null handle or another value;
  * qmpc_query(QMPC_QUERY_CONVEX_LANE_RECORDS) returns the setting. */
 qmpc_status qmpc_set_convex_lane_records(qmpc_handle* h, int32_t on);
+
+/* Opt in to warm-started closed loops with controller records on a ConvexMpc handle: on = 1 (0, the default, restores the
+ * refusal).  It holds until changed and takes effect only on a ConvexMpc handle in the converged mode that also opted in with
+ * qmpc_set_convex_records; the setting does nothing on a handle of another model, and qmpc_set_loop_warm_records keeps having no
+ * effect on ConvexMpc.  With both on, qmpc_loop_run_instances*, qmpc_loop_run_outcomes* and qmpc_loop_run_pushes* accept ctrl
+ * together with lp->warm_start != 0, with the plain loop's rule: the first tick of a call starts cold, every later solve of a
+ * robot starts from its previous solution shifted by one knot unless that solve failed (a frozen, halted or rejected robot never
+ * solved).  Every other refusal keeps its code: the reference mode, a knot spacing other than 5 ms, no wrench-form kernel for
+ * the batch, an 8-point handle.
+ *   Launch (QMPC_QUERY_LOOP_INSTANCES_PLAN with bits 32 and 33 answers under the setting): the persistent kernel where the
+ *     plain warm-started ConvexMpc loop takes its own on a wrench-form variant (up to 4096 robots, or QMPC_LOOP_FUSED);
+ *     otherwise per tick -- the first tick qmpc_solve_cw_inst_kernel, the later ones qmpc_solve_cw_inst_warm_kernel, on the
+ *     variant of qmpc_convex_solve_instances* for the batch.  On a handle that also opted in with qmpc_set_convex_lane_records,
+ *     under QMPC_INSTANCES_AUTO, the per-tick calls take the lane form from the larger of its switch-over and the plain
+ *     warm-started loop's own (QMPC_LANE_CINST_MIN / QMPC_LANE_MIN move them; QMPC_VARIANT=4: at every size): the sort and
+ *     qmpc_lane_cinst_warm_kernel, after a first tick on qmpc_lane_cinst_kernel.  No lane pairs, no cap, no hand-off.
+ *   With records equal to the handle's values every form gives the bytes of qmpc_loop_run* under the same lp (states, force and
+ *     contact traces) wherever that loop solves in the same family on the same variant; the persistent and per-tick wave forms
+ *     agree bit for bit on any records; wave and lane forms agree on status words and within 1e-7 N on forces.
+ *   Memory: the per-tick forms carry the solution through a buffer of 96 N bytes per robot of max_batch.  qmpc_prepare,
+ *     qmpc_prepare_instances and a call with ticks = 0 allocate it (and the lane buffers where the lane form is planned), so that
+ *     a caller's stream capture allocates nothing; the persistent and per-tick wave forms run inside a caller's capture.
+ * QMPC_BAD_ARGUMENT for a null handle or another value; qmpc_query(QMPC_QUERY_CONVEX_WARM_RECORDS) returns the setting. */
+qmpc_status qmpc_set_convex_warm_records(qmpc_handle* h, int32_t on);
 
 /* ---- per-robot outcome records of the closed loop (robustness sweeps) -------------------------------------------------
  * The other half of the question above: did robot i stay up, how far did it tilt, how well did it track its command, how
@@ -802,7 +830,7 @@ qmpc_status qmpc_set_convex_lane_records(qmpc_handle* h, int32_t on);
  * ConvexMpc handle in the converged mode that opted in (qmpc_set_convex_records);
  * QMPC_UNSUPPORTED for a reference-mode handle or a ConvexMpc handle that has not opted in (qmpc_set_convex_records),
  * QMPC_BAD_ARGUMENT for an 8-point handle, with ctrl also
- * QMPC_UNSUPPORTED for lp->warm_start != 0 (unless the handle opted in: qmpc_set_loop_warm_records) or a handle without a
+ * QMPC_UNSUPPORTED for lp->warm_start != 0 (unless the handle opted in: qmpc_set_loop_warm_records, ConvexMpc: qmpc_set_convex_warm_records) or a handle without a
  * wrench-form kernel -- and QMPC_BAD_ARGUMENT for a NULL op
  * or outcomes.  ctrl and plant may both be NULL: plain robots on the handle's parameters (still a QuatMpc converged
  * handle, or an opted-in ConvexMpc one).  Buffers: those of qmpc_loop_run_instances*; the host-buffer call adds a staging

@@ -391,6 +391,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_set_convex_records.restype = i32
     lib.qmpc_set_convex_lane_records.argtypes = [vp, i32]
     lib.qmpc_set_convex_lane_records.restype = i32
+    lib.qmpc_set_convex_warm_records.argtypes = [vp, i32]
+    lib.qmpc_set_convex_warm_records.restype = i32
     lib.qmpc_gather.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     lib.qmpc_gather.restype = i32
     lib.qmpc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -549,6 +551,7 @@ EXPORTED_SYMBOLS = (
     "qmpc_convex_solve_instances_device",
     "qmpc_set_convex_records",
     "qmpc_set_convex_lane_records",
+    "qmpc_set_convex_warm_records",
     "qmpc_prepare_instances",
     "qmpc_plant_params_from",
     "qmpc_sizeof_plant_params",
@@ -574,6 +577,7 @@ QUERY_LOOP_WARM_RECORDS = 11
 QUERY_KERNEL_FOR_CONVEX_INSTANCES = 12
 QUERY_CONVEX_RECORDS = 13
 QUERY_CONVEX_LANE_RECORDS = 14
+QUERY_CONVEX_WARM_RECORDS = 15
 # enum qmpc_instances_policy
 INSTANCES_WAVE, INSTANCES_AUTO = 0, 1
 INSTANCES_POLICY = {"wave": INSTANCES_WAVE, "auto": INSTANCES_AUTO}
@@ -994,7 +998,8 @@ class Solver:
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
         as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN).  Answers under the handle's
         instances policy: with ctrl under "auto" the per-tick form is ("per_tick", "lane_handoff" / "lane") from the switch-over on.
-        ctrl and warm together answer under set_loop_warm_records (default off: None)."""
+        ctrl and warm together answer under set_loop_warm_records (default off: None; a ConvexMpc
+        handle: under set_convex_warm_records)."""
         v = self.query(QUERY_LOOP_INSTANCES_PLAN, int(batch) | (int(bool(ctrl)) << 32) | (int(bool(warm)) << 33))
         if v == 0:
             return None
@@ -1044,6 +1049,17 @@ class Solver:
 
     def convex_lane_records(self) -> bool:
         return bool(self.query(QUERY_CONVEX_LANE_RECORDS))
+
+    def set_convex_warm_records(self, on: bool = True):
+        """Let the loops with controller records accept lp.warm_start on this ConvexMpc handle (qmpc_set_convex_warm_records;
+        default off: they refuse it).  Takes effect only together with set_convex_records; set_loop_warm_records keeps having
+        no effect on ConvexMpc, and this setting does nothing on a handle of another model."""
+        st = self.lib.qmpc_set_convex_warm_records(self._h, int(on))
+        if st != OK:
+            raise QmpcError(st, "qmpc_set_convex_warm_records")
+
+    def convex_warm_records(self) -> bool:
+        return bool(self.query(QUERY_CONVEX_WARM_RECORDS))
 
     def instances_policy(self) -> str:
         return {v: k for k, v in INSTANCES_POLICY.items()}[self.query(QUERY_INSTANCES_POLICY)]

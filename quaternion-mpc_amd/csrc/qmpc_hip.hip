@@ -164,6 +164,17 @@ hipError_t qmpc_lane_inst_warm_launch_only(int pslot, int batch, hipStream_t s, 
                                            const double* u_init, double* traj_u, int check_prev, int iter_cap, int* hcount, int* hsel,
                                            double* hstate, int hcap, int pair);
 
+// qmpc_wform_cinst_warm.hip / qmpc_lane_cinst_warm.hip: the warm-started ticks of a ConvexMpc closed loop with controller records
+// (qmpc_set_convex_warm_records) on the wave kernels and on the lane kernel
+hipError_t qmpc_wform_cinst_warm_set_lds();
+hipError_t qmpc_wform_cinst_warm_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
+                                        const qmpc_input* in, const double* u_init, double* forces, qmpc_info* info, double* traj_u,
+                                        double* gws, int check_prev);
+hipError_t qmpc_lane_cinst_warm_upload_params(int pslot, hipStream_t s, const void* dev_params, size_t dev_params_size);
+hipError_t qmpc_lane_cinst_warm_launch_only(int pslot, int batch, hipStream_t s, const void* in, const void* dev_blocks, const int* status,
+                                            double* forces, qmpc_info* info, double* ws, double* prm, unsigned slots, const int* perm,
+                                            const double* u_init, double* traj_u, int check_prev);
+
 // qmpc_wform_cinst.hip: ConvexMpc's solve with per-instance parameters (qmpc_convex_solve_instances*)
 hipError_t qmpc_wform_cinst_set_lds();
 hipError_t qmpc_wform_cinst_solve_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
@@ -202,8 +213,8 @@ struct qmpc_handle {
   qmpc_opts opts;              // the run-time settings the planners of the calls with records read (qmpc_plan.h): the policy of
                                // qmpc_set_instances_policy (default WAVE), handoff_failed (the hand-off records could not be allocated --
                                // this handle runs the pure lane kernel, qmpc_query), the opt-ins of qmpc_set_loop_warm_records (the loops
-                               // with controller records accept lp->warm_start) and qmpc_set_convex_records (the loops with records accept
-                               // this ConvexMpc handle; then d_outcome is also the scratch the outcome step of a call without outcome
+                               // with controller records accept lp->warm_start; ConvexMpc: qmpc_set_convex_warm_records) and
+                               // qmpc_set_convex_records (the loops with records accept this ConvexMpc handle; then d_outcome is also the scratch the outcome step of a call without outcome
                                // records runs on)
   int last_kernel;             // QMPC_KERNEL_* of the most recent solve launch (qmpc_query)
   // host-buffer calls (qmpc_solve*, qmpc_solve_async): pinned staging owned by the handle.  Batches below the lane kernel's
@@ -381,6 +392,7 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   HIP_TRY(qmpc_wform_inst_list_set_lds());
   HIP_TRY(qmpc_wform_inst_warm_set_lds());
   HIP_TRY(qmpc_wform_cinst_set_lds());
+  HIP_TRY(qmpc_wform_cinst_warm_set_lds());
   HIP_TRY(hipMalloc(&h->d_gws, sizeof(double) * (size_t)N * (13 * nu + 21 * nl + 30 * nl) * (size_t)max_batch));
   return QMPC_OK;
 }
@@ -976,21 +988,24 @@ static bool instances_lane_possible(const qmpc_handle* h) {
 // stance mask, the loops' also by the previous records' iteration classes, robots that will not solve last --, the lane kernel
 // with per-lane parameters to the cap, the per-instance list kernel on what it leaves (a warm tick's records carry the rows'
 // initial residuals, so only the cold forms honour QMPC_HANDOFF_RESTART).  The plain call uploads the lane kernel's parameter
-// block just before its launch; the loops upload it once per call, outside the capture.  The lane form of ConvexMpc (cold forms
-// only; qmpc_lane_cinst.hip): its sort -- contacts at the convex record's offset, a tick's also by the previous records' iteration
-// classes, robots that will not solve last -- and qmpc_lane_cinst_kernel, which has neither cap nor hand-off.
+// block just before its launch; the loops upload it once per call, outside the capture.  The lane form of ConvexMpc
+// (qmpc_lane_cinst.hip): its sort -- contacts at the convex record's offset, a tick's also by the previous records' iteration
+// classes, robots that will not solve last -- and qmpc_lane_cinst_kernel, which has neither cap nor hand-off; a warm tick:
+// qmpc_lane_cinst_warm_kernel (qmpc_lane_cinst_warm.hip) behind the same sort.
 enum inst_form { INST_CALL, INST_TICK_COLD, INST_TICK_FIRST, INST_TICK_WARM };
 static qmpc_status inst_solve(qmpc_handle* h, const qmpc_plan& p, bool convex, inst_form form, int32_t batch, const qmpc_input* d_in,
                               double* d_forces, qmpc_info* d_info, double* tu, double* tx, hipStream_t s) {
   const bool warm = form == INST_TICK_WARM;
   double* gws = p.gws ? h->d_gws : nullptr;
   if (p.variant == 4 && convex) {
-    if (form != INST_CALL && form != INST_TICK_COLD) return QMPC_UNSUPPORTED;
     const int* perm = h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr;
     if (h->sel.lane_sort)
       HIP_TRY(qmpc_lane_cinst_sort_launch((int)batch, s, d_in, (form != INST_CALL && p.order_prev) ? d_info : nullptr, inst_status(h),
                                           form != INST_CALL ? h->sel.lane_sort_idle : 0, h->d_lane_scratch));
-    if (form == INST_CALL)
+    if (warm)
+      HIP_TRY(qmpc_lane_cinst_warm_launch_only(h->lane_pslot, (int)batch, s, d_in, inst_dev(h), inst_status(h), d_forces, d_info, h->d_lane_ws,
+                                               h->d_lane_prm, h->lane_slots, perm, tu, tu, /*check_prev=*/1));
+    else if (form == INST_CALL)
       HIP_TRY(qmpc_lane_cinst_launch(h->lane_pslot, (int)batch, s, &h->dev, sizeof h->dev, d_in, inst_dev(h), inst_status(h), d_forces, d_info,
                                      h->d_lane_ws, h->d_lane_prm, h->lane_slots, perm, tu, tx));
     else
@@ -1020,6 +1035,9 @@ static qmpc_status inst_solve(qmpc_handle* h, const qmpc_plan& p, bool convex, i
     if (cap)
       HIP_TRY(qmpc_wform_inst_list_launch(p.handoff_variant, p.handoff_grid, p.lds, s, inst_dev(h), d_in, d_forces, d_info, tu, tx, hsel, hcount,
                                           gws, (warm || !h->sel.handoff_restart) ? h->d_hstate : nullptr, h->hstate_cap));
+  } else if (convex && warm) {
+    HIP_TRY(qmpc_wform_cinst_warm_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, tu, d_forces, d_info, tu, gws,
+                                         /*check_prev=*/1));
   } else if (convex) {
     HIP_TRY(qmpc_wform_cinst_solve_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, d_forces, d_info, tu, tx, gws));
   } else if (warm) {
@@ -1125,6 +1143,10 @@ qmpc_status qmpc_prepare_instances(qmpc_handle* h) {
   if (cs != QMPC_OK) return cs;
   HIP_TRY(hipSetDevice(h->device));
   const qmpc_status es = ensure_instance_buffers(h);
+  // (a ConvexMpc handle that opted in to warm-started loops with controller records: the buffer the solution travels through in
+  // the per-tick forms, 96 N bytes per robot)
+  if (es == QMPC_OK && convex && h->opts.convex_records && h->opts.convex_warm && !h->d_traj_u)
+    HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * (size_t)h->params.horizon * (size_t)h->max_batch));
   if (es != QMPC_OK || !instances_lane_possible(h)) return es;
   return ensure_lane_inst_buffers(h, lane_cap(h->sel, QMPC_CALL_PLAIN, h->opts.handoff_failed) != 0);
 }
@@ -1150,6 +1172,12 @@ qmpc_status qmpc_set_convex_records(qmpc_handle* h, int32_t on) {
 qmpc_status qmpc_set_convex_lane_records(qmpc_handle* h, int32_t on) {
   if (!h || (on != 0 && on != 1)) return QMPC_BAD_ARGUMENT;
   h->opts.convex_lane = on != 0;
+  return QMPC_OK;
+}
+
+qmpc_status qmpc_set_convex_warm_records(qmpc_handle* h, int32_t on) {
+  if (!h || (on != 0 && on != 1)) return QMPC_BAD_ARGUMENT;
+  h->opts.convex_warm = on != 0;
   return QMPC_OK;
 }
 
@@ -1206,6 +1234,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       *value = plan_convex_instances(h->sel, h->opts, (int)arg, true).family;
       return QMPC_OK;
     case QMPC_QUERY_CONVEX_LANE_RECORDS: *value = h->opts.convex_lane; return QMPC_OK;
+    case QMPC_QUERY_CONVEX_WARM_RECORDS: *value = h->opts.convex_warm; return QMPC_OK;
     default: return QMPC_BAD_ARGUMENT;
   }
 }
@@ -1742,8 +1771,10 @@ static qmpc_status loop_instances_check(const qmpc_handle* h, const qmpc_loop_pa
   if ((h->params.model != QMPC_MODEL_QUAT && !crec) || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
   // (the device tick of ConvexMpc carries the controller period as the literal 5 ms: loop_run_impl)
   if (crec && h->params.h != (float)(5.0 / 1000.0)) return QMPC_UNSUPPORTED;
-  // (controller records with the warm start: on a QuatMpc handle that opted in only, qmpc_set_loop_warm_records)
-  if (has_ctrl && ((lp->warm_start != 0.0 && (crec || !h->opts.loop_warm_records)) || !h->sel.wform)) return QMPC_UNSUPPORTED;
+  // (controller records with the warm start: on a handle that opted in only -- QuatMpc: qmpc_set_loop_warm_records, ConvexMpc:
+  // qmpc_set_convex_warm_records)
+  if (has_ctrl && ((lp->warm_start != 0.0 && !(crec ? h->opts.convex_warm : h->opts.loop_warm_records)) || !h->sel.wform))
+    return QMPC_UNSUPPORTED;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
   // (the handle's policy refuses no call: a plan is NONE under QMPC_INSTANCES_AUTO exactly where it is under QMPC_INSTANCES_WAVE)
   if (batch > 0 && plan_loop_instances(h->sel, h->opts, batch, has_ctrl, lp->warm_start != 0.0).family == QMPC_KERNEL_NONE)
@@ -1852,7 +1883,8 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
   if (d_ctrl && lpp.variant == 4 && crec) HIP_TRY(qmpc_lane_cinst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   if (d_ctrl && lpp.variant == 4 && !crec) HIP_TRY(qmpc_lane_inst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
-  if (d_ctrl && warm && lpp.variant == 4) HIP_TRY(qmpc_lane_inst_warm_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
+  if (d_ctrl && warm && lpp.variant == 4 && crec) HIP_TRY(qmpc_lane_cinst_warm_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
+  if (d_ctrl && warm && lpp.variant == 4 && !crec) HIP_TRY(qmpc_lane_inst_warm_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   return replay_ticks(h, lpp, s, ticks, warm, one_tick);
 }
 

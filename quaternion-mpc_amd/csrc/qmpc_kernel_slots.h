@@ -99,4 +99,9 @@ static inline int wform_inst_warm_slot(int var) { return wform_index(var); }
 constexpr int kWformConvexInstSlots = 3;
 static inline int wform_convex_inst_slot(int var) { return wform_index(var); }
 
+// ---- qmpc_wform_cinst_warm.hip ------------------------------------------------------------------------------------------
+// qmpc_solve_cw_inst_warm_kernel<WVAR> (the warm-started ticks of a ConvexMpc closed loop with controller records): 3 5 6
+constexpr int kWformConvexInstWarmSlots = 3;
+static inline int wform_convex_inst_warm_slot(int var) { return wform_index(var); }
+
 }  // namespace qmpc

@@ -37,8 +37,10 @@
 // controller records under lp->warm_start.
 // QL_UNIT 5 (qmpc_lane_cinst.hip includes this file): ConvexMpc's converged-mode kernel with per-lane parameters
 // (qmpc_convex_solve_instances* and the record loops on a handle that opted in: qmpc_set_convex_lane_records).
-#if !defined(QL_UNIT) || (QL_UNIT != 1 && QL_UNIT != 2 && QL_UNIT != 3 && QL_UNIT != 4 && QL_UNIT != 5)
-#error "QL_UNIT must be 1 (the converged mode's unit), 2 (the reference mode's unit), 3 (per-lane parameters), 4 (... warm-started) or 5 (... ConvexMpc)"
+// QL_UNIT 6 (qmpc_lane_cinst_warm.hip includes this file): that kernel warm-started, the later ticks of a ConvexMpc closed loop
+// with controller records under lp->warm_start (qmpc_set_convex_warm_records).
+#if !defined(QL_UNIT) || (QL_UNIT != 1 && QL_UNIT != 2 && QL_UNIT != 3 && QL_UNIT != 4 && QL_UNIT != 5 && QL_UNIT != 6)
+#error "QL_UNIT must be 1 (the converged mode's unit), 2 (the reference mode's unit), 3 (per-lane parameters), 4 (... warm-started), 5 (... ConvexMpc) or 6 (... ConvexMpc warm-started)"
 #endif
 namespace qmpc {
 namespace lane {

@@ -2,7 +2,7 @@
 // qmpc_lane_kernel<4, QL_INST_MD> instantiated on LaneParams (qmpc_lane_core.h) as separate functions, and the arguments they are
 // called with.  QL_INST_MD is the including unit's model: MD_QUAT in qmpc_lane_inst.hip (QL_UNIT 3: the cold kernel, WARM = false
 // throughout) and qmpc_lane_inst_warm.hip (QL_UNIT 4), MD_CONVEX in qmpc_lane_cinst.hip (QL_UNIT 5: ConvexMpc's cold kernel, which
-// has no pair forms).  Included inside namespace qmpc::lane, after qmpc_lane.hip.  Textual inclusion: each unit instantiates what
+// has no pair forms) and qmpc_lane_cinst_warm.hip (QL_UNIT 6: that kernel warm-started).  Included inside namespace qmpc::lane, after qmpc_lane.hip.  Textual inclusion: each unit instantiates what
 // it calls and keeps its own code object (tools/isa_same.py states unit 3's against a revision).  The set-up differs between the
 // units (cold: no previous solution) and stays with its unit.
 #if !defined(QL_INST_MD)

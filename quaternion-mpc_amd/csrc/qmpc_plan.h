@@ -26,6 +26,7 @@ namespace qmpc {
 //   QMPC_LANE_CINST_MIN   ... of qmpc_convex_solve_instances* under QMPC_INSTANCES_AUTO on a handle that opted in with
 //                         qmpc_set_convex_lane_records (ConvexMpc's lane kernel with per-lane parameters); the ticks of its record
 //                         loops with controller records switch over at the larger of this and the cold-started loop's own
+//                         (warm-started, on a handle that opted in with qmpc_set_convex_warm_records: the warm-started loop's own)
 //   QMPC_LANE_CAP, QMPC_LANE_CAP_LOOP, QMPC_LANE_CAP_WARM
 //                         iteration cap of the lane kernel before the straggler hand-off: cold plain solves, cold-started
 //                         loops, warm-started loop ticks (0: no hand-off)
@@ -289,7 +290,7 @@ static inline qmpc_plan plan(const qmpc_select& s, int batch, qmpc_call kind, bo
 }
 
 // A handle's run-time settings (qmpc_set_instances_policy, qmpc_set_loop_warm_records, qmpc_set_convex_records,
-// qmpc_set_convex_lane_records, and what became of its hand-off records): what the planners of the calls with per-instance records read besides the selection state.  The
+// qmpc_set_convex_lane_records, qmpc_set_convex_warm_records, and what became of its hand-off records): what the planners of the calls with per-instance records read besides the selection state.  The
 // handle holds one and passes it whole.
 struct qmpc_opts {
   int inst_policy = QMPC_INSTANCES_WAVE;      // qmpc_instances_policy of the solves and ticks with per-instance parameters
@@ -297,6 +298,8 @@ struct qmpc_opts {
   bool loop_warm_records = false;             // the loops with controller records accept lp->warm_start (QuatMpc)
   bool convex_records = false;                // the loops with records accept a ConvexMpc handle
   bool convex_lane = false;                   // ConvexMpc's calls with per-instance records may take the lane kernel (under AUTO)
+  bool convex_warm = false;                   // the loops with controller records accept lp->warm_start on a ConvexMpc handle
+                                              // that opted in with convex_records (qmpc_set_convex_warm_records)
 };
 
 // The plan of qmpc_solve_instances* (per-instance parameters, qmpc_wform.hip: qmpc_solve_w_inst_kernel).  `has_info`: the call
@@ -387,14 +390,21 @@ static inline qmpc_plan plan_convex_instances(const qmpc_select& s, const qmpc_o
 //               ConvexMpc's per-tick solve with controller records takes it on a handle that opted in to BOTH convex_records and
 //               convex_lane, under the same policy: from the larger of lane_min_cinst and lane_min_loop_cold the lane fields of the
 //               plain cold tick (qmpc_lane_cinst_kernel: no cap, no hand-off; order_prev, no upload inside the tick).
+//   ConvexMpc, warm-started with controller records: on a handle that opted in to convex_records AND convex_warm
+//               (loop_warm_records has no effect on ConvexMpc).  Persistent where the plain warm-started loop is (up to 4096
+//               robots; qmpc_loop_rec_fused_kernel carries the warm start); per tick otherwise: plan_convex_instances(s, batch)
+//               (qmpc_solve_cw_inst_warm_kernel; `first`: the cold qmpc_solve_cw_inst_kernel on the same variant); the lane form
+//               under the conditions above from the larger of lane_min_cinst and lane_min_warm, with the lane fields of the plain
+//               warm ConvexMpc tick (qmpc_lane_cinst_warm_kernel; `first`: qmpc_lane_cinst_kernel) -- QMPC_KERNEL_LANE,
+//               order_prev, no upload inside the tick; no cap, no hand-off, no pairs.
 // NONE: the reference mode; a model other than QuatMpc and, on a handle that opted in (convex_records), ConvexMpc; controller
-// records without a wrench-form kernel for the batch (QMPC_WFORM=0, ...); controller records with the warm start unless a
-// QuatMpc handle opted in (loop_warm_records; never on ConvexMpc).
+// records without a wrench-form kernel for the batch (QMPC_WFORM=0, ...); controller records with the warm start unless the
+// handle opted in (QuatMpc: loop_warm_records; ConvexMpc: convex_warm).
 static inline qmpc_plan plan_loop_instances(const qmpc_select& s, const qmpc_opts& o, int batch, bool has_ctrl, bool warm,
                                             bool first = false) {
   const bool convex = s.model == QMPC_MODEL_CONVEX && o.convex_records;
   if ((s.model != QMPC_MODEL_QUAT && !convex) || s.mode != QMPC_MODE_CONVERGED) return qmpc_plan();
-  if (has_ctrl && (!s.wform || (warm && (convex || !o.loop_warm_records)))) return qmpc_plan();
+  if (has_ctrl && (!s.wform || (warm && !(convex ? o.convex_warm : o.loop_warm_records)))) return qmpc_plan();
   const qmpc_plan f = plan(s, batch, warm ? QMPC_CALL_WARM_LOOP : QMPC_CALL_LOOP, true, o.handoff_failed);
   if (f.fused && (f.variant == 3 || f.variant == 5 || f.variant == 6)) return f;
   const qmpc_call tick = !warm ? QMPC_CALL_LOOP_TICK : (has_ctrl && first ? QMPC_CALL_WARM_LOOP_FIRST : QMPC_CALL_WARM_LOOP_TICK);

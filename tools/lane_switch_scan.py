@@ -10,7 +10,9 @@ against AUTO with QMPC_LANE_INST_MIN=1 and QMPC_LANE_MIN=1 on one handle per hor
 --ticks ticks per call timed with device events (the switch-over of plan_loop_instances under QMPC_INSTANCES_AUTO, qmpc_plan.h).
 --model convex (with --instances or --loop-instances): ConvexMpc's calls on a handle that opted in to the lane form
 (qmpc_set_convex_lane_records; for the loops also qmpc_set_convex_records), QMPC_LANE_CINST_MIN=1 in place of QMPC_LANE_INST_MIN:
-the switch-over lane_min_cinst of qmpc_plan_fill.h."""
+the switch-over lane_min_cinst of qmpc_plan_fill.h.
+--warm (with --loop-instances): the warm-started ticks (lp.warm_start = 1, ipm_mu0 = 1e-6) on a handle that opted in -- QuatMpc:
+qmpc_set_loop_warm_records, ConvexMpc: qmpc_set_convex_warm_records -- the warm switch-over of plan_loop_instances."""
 import argparse, os, sys
 from pathlib import Path
 import numpy as np
@@ -27,6 +29,7 @@ ap.add_argument("--step", type=int, default=2048)
 ap.add_argument("--horizons", default="10,20")
 ap.add_argument("--model", default="quat", choices=("quat", "convex"))
 ap.add_argument("--start", type=int, default=8192)
+ap.add_argument("--warm", action="store_true")
 a = ap.parse_args()
 pkg = g._load_pkg(); lib = pkg.load_library()
 convex = a.model == "convex"
@@ -34,7 +37,9 @@ default_params = pkg.default_convex_params if convex else pkg.default_params
 variants = pkg.random_go1_convex_variants if convex else pkg.random_go1_variants
 def opt_in(s):      # noqa: E302
     if convex:
-        s.set_convex_records(True); s.set_convex_lane_records(True)
+        s.set_convex_records(True); s.set_convex_lane_records(True); s.set_convex_warm_records(a.warm)
+    elif a.warm:
+        s.set_loop_warm_records(True)
 import torch  # noqa: E402
 if a.loop_instances:
     os.environ["QMPC_LANE_CINST_MIN" if convex else "QMPC_LANE_INST_MIN"] = "1"
@@ -43,11 +48,16 @@ if a.loop_instances:
     for N in (int(x) for x in a.horizons.split(",")):
         p = default_params(N, 0, lib)
         lp = pkg.default_loop_params(lib)
+        if a.warm:
+            p.ipm_mu0 = 1e-6
+            lp.warm_start = 1.0
         rng = np.random.default_rng(5)
         cmds = np.zeros((BMAX, 7))
         cmds[:, 0] = rng.uniform(-0.4, 0.4, BMAX); cmds[:, 1] = rng.uniform(-0.15, 0.15, BMAX)
         cmds[:, 2] = rng.uniform(0.26, 0.32, BMAX); cmds[:, 5] = rng.uniform(-0.4, 0.4, BMAX)
         cmds[:, 6] = (rng.random(BMAX) < 0.85).astype(float)
+        if convex:      # (this controller has no command for a robot that stands)
+            cmds[cmds[:, 6] == 0, :2] = 0.0; cmds[cmds[:, 6] == 0, 5] = 0.0
         stand = cmds.copy(); stand[:, 6] = 0.0
         st = pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, BMAX), lib=lib)
         ctrl = variants(BMAX, seed=13, base=p); ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
@@ -77,7 +87,7 @@ if a.loop_instances:
                     if r >= 1: ms[pol].append(e0.elapsed_time(e1))
             form = {}
             for pol in ms:
-                s.set_instances_policy(pol); form[pol] = s.loop_instances_plan(B, True, False)[1]
+                s.set_instances_policy(pol); form[pol] = s.loop_instances_plan(B, True, a.warm)[1]
             mw, ml = float(np.median(ms["wave"])), float(np.median(ms["auto"]))
             wins.append((B, ml < mw))
             print(f"N={N} B={B}: wave {form['wave']} {mw:.3f} ms ({B * T / mw / 1e3:.3f} M robot-ticks/s) vs auto {form['auto']} {ml:.3f} ms "
@@ -86,7 +96,7 @@ if a.loop_instances:
         for B, w in reversed(wins):
             if not w: break
             first = B
-        print(f"N={N}: the lane ticks are faster at every scanned size from {first} on", flush=True)
+        print(f"N={N}{' warm' if a.warm else ''}: the lane ticks are faster at every scanned size from {first} on", flush=True)
     sys.exit(0)
 if a.instances:
     os.environ["QMPC_LANE_CINST_MIN" if convex else "QMPC_LANE_INST_MIN"] = "1"

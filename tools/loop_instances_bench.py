@@ -28,7 +28,9 @@ per-robot calls include their expansion kernels.
 --model convex: the default comparison (plain / plant records / controller + plant records) on a ConvexMpc handle that opted in
     with qmpc_set_convex_records, with the commands of the ConvexMpc loop tests and records around default_convex_params
     (random_go1_convex_variants).  The handle also opts in to the lane form (qmpc_set_convex_lane_records): with ctrl the ticks
-    take qmpc_lane_cinst_kernel from the switch-over on under AUTO and stay on the wave kernels under WAVE."""
+    take qmpc_lane_cinst_kernel from the switch-over on under AUTO and stay on the wave kernels under WAVE.  With --warm-records:
+    the cold / warm pairs above on ConvexMpc handles, the warm one opted in with qmpc_set_convex_warm_records (under AUTO its warm
+    ticks take qmpc_lane_cinst_warm_kernel from the warm switch-over on)."""
 import argparse
 import importlib.util
 import json
@@ -179,8 +181,10 @@ def warm_records(pkg, lib, torch, N, B, a):
     lp_c = pkg.default_loop_params(lib)
     lp_w = pkg.default_loop_params(lib)
     lp_w.warm_start = 1.0
-    p_c = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
-    p_w = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+    convex = a.model == "convex"
+    defaults = pkg.default_convex_params if convex else pkg.default_params
+    p_c = defaults(N, pkg.MODE_CONVERGED, lib)
+    p_w = defaults(N, pkg.MODE_CONVERGED, lib)
     p_w.ipm_mu0 = a.mu0
     T = a.ticks
     rng = np.random.default_rng(5)
@@ -188,13 +192,20 @@ def warm_records(pkg, lib, torch, N, B, a):
     cmds[:, 0] = rng.uniform(-0.4, 0.4, B); cmds[:, 1] = rng.uniform(-0.15, 0.15, B)
     cmds[:, 2] = rng.uniform(0.26, 0.32, B); cmds[:, 5] = rng.uniform(-0.4, 0.4, B)
     cmds[:, 6] = (rng.random(B) < 0.85).astype(float)
+    if convex:      # (this controller has no command for a robot that stands: tests/test_gpu_lane.py)
+        cmds[cmds[:, 6] == 0, :2] = 0.0
+        cmds[cmds[:, 6] == 0, 5] = 0.0
     stand = cmds.copy(); stand[:, 6] = 0.0
     st = pkg.loop_states(stand, lp_c, height=0.3, yaw=rng.uniform(-3, 3, B), lib=lib)
     policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
     handles = {}
     for kind, p in (("cold", p_c), ("warm", p_w)):
         h = pkg.Solver(p, B, device=0, lib=lib)
-        if kind == "warm":
+        if convex:
+            h.set_convex_records(True)
+            h.set_convex_lane_records(True)      # (takes effect under AUTO only)
+            h.set_convex_warm_records(kind == "warm")
+        elif kind == "warm":
             h.set_loop_warm_records(True)
         for pol in policies:      # (the buffers of every policy asked for: allocated before anything is timed)
             h.set_instances_policy(pol)
@@ -204,7 +215,7 @@ def warm_records(pkg, lib, torch, N, B, a):
     st = handles["cold"].loop_run(st, 6, lp_c)
     st["movement_mode"] = cmds[:, 6]
     if a.records == "random":
-        ctrl = pkg.random_go1_variants(B, seed=12, base=p_c)
+        ctrl = (pkg.random_go1_convex_variants if convex else pkg.random_go1_variants)(B, seed=12, base=p_c)
         ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
         plant = pkg.random_go1_plants(B, seed=11, base=p_c, payload=(-1.0, 3.0), force=(0.0, 10.0))
     else:
@@ -246,7 +257,7 @@ def warm_records(pkg, lib, torch, N, B, a):
     for h in handles.values():
         h.close()
     ms = {k: float(np.median(v)) for k, v in times.items()}
-    row = {"N": N, "B": B, "ticks": T, "records": a.records, "mu0_warm": a.mu0}
+    row = {"N": N, "B": B, "ticks": T, "records": a.records, "mu0_warm": a.mu0, "model": a.model}
     for k in calls:
         row[k + "_ms"] = ms[k]
         row[k + "_Mrobot_ticks_s"] = B * T / ms[k] / 1e3
@@ -296,8 +307,8 @@ def main():
     if a.stop and not a.outcomes:
         ap.error("--stop goes with --outcomes")
     convex = a.model == "convex"
-    if convex and (a.pushes or a.warm_records or a.stop):
-        ap.error("--model convex goes with the default comparison and --outcomes")
+    if convex and (a.pushes or a.stop):
+        ap.error("--model convex goes with the default comparison, --outcomes and --warm-records")
     for item in a.sizes.split(","):
         N, B = (int(x) for x in item.split(":"))
         policies = ("wave", "auto") if a.policy == "both" else (a.policy,)

@@ -4,7 +4,7 @@ gait period (91 ticks of 5 ms at 2.2 Hz), every robot shoved once (qmpc_loop_run
 still up per cell from the outcome records.  The robots of a cell differ in their true plant (random_go1_plants: payload and
 inertia); the controller is the handle's and is not told about the push.
     python tools/push_recovery.py [--impulses 2,4,6,8,10] [--starts 13] [--length 10] [--per-cell 8] [--speed 0.3] [--settle 60]
-                                  [--recover 200] [--horizon 10] [--controller quat|convex|both] [--ctrl-records] [--json FILE]
+                                  [--recover 200] [--horizon 10] [--controller quat|convex|both] [--ctrl-records] [--warm] [--json FILE]
 Every robot stands for 6 ticks, trots at --speed for --settle ticks, is shoved at tick 6 + settle + start for --length ticks with
 force impulse / (length dt) in its cell's direction (0 degrees: ahead, 90: to its left), and trots on until --recover ticks after
 the last start.  Down: below 0.15 m or tilted beyond 60 degrees (qmpc_default_outcome_params); stop_when_down halts a fallen robot.
@@ -14,7 +14,9 @@ the run gives.
 plants and commands under each controller, one summary per controller.  --horizon is then each controller's horizon.
 --ctrl-records: every robot also carries a controller record (the handle's values: the same controller) and the handle takes
 QMPC_INSTANCES_AUTO, a ConvexMpc handle with qmpc_set_convex_lane_records as well -- the launch a sweep over per-robot controllers
-takes: from the switch-over on the lane kernel with per-lane parameters under either controller."""
+takes: from the switch-over on the lane kernel with per-lane parameters under either controller.
+--warm: the loops run warm-started (lp.warm_start = 1, ipm_mu0 = 1e-6).  With --ctrl-records the handle opts in to warm starts with
+controller records: a QuatMpc handle with qmpc_set_loop_warm_records, a ConvexMpc handle with qmpc_set_convex_warm_records."""
 import argparse
 import importlib.util
 import json
@@ -50,6 +52,7 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--controller", choices=("quat", "convex", "both"), default="quat")
     ap.add_argument("--ctrl-records", action="store_true")
+    ap.add_argument("--warm", action="store_true")
     a = ap.parse_args()
     pkg = load_pkg()
     lib = pkg.load_library()
@@ -70,6 +73,9 @@ def run(a, pkg, lib, controller):
     convex = controller == "convex"
     p = (pkg.default_convex_params if convex else pkg.default_params)(a.horizon, pkg.MODE_CONVERGED, lib)
     lp = pkg.default_loop_params(lib)
+    if a.warm:
+        p.ipm_mu0 = 1e-6
+        lp.warm_start = 1.0
     assert abs(1.0 / (lp.gait_freq * lp.dt) - PERIOD) < 0.5, (lp.gait_freq, lp.dt)
     cmd = [a.speed, 0.0, 0.30, 0.0, 0.0, 0.0, 0.0]
     st = pkg.loop_states([cmd] * B, lp, height=0.3, yaw=0.0, lib=lib)
@@ -92,7 +98,9 @@ def run(a, pkg, lib, controller):
         s.set_instances_policy("auto")
         if convex:
             s.set_convex_lane_records(True)
-    form = s.loop_instances_plan(B, ctrl is not None, False)
+        if a.warm:
+            (s.set_convex_warm_records if convex else s.set_loop_warm_records)(True)
+    form = s.loop_instances_plan(B, ctrl is not None, a.warm)
     total = a.settle + PERIOD + a.recover
     w0 = time.perf_counter()
     st, oc = s.loop_run_pushes(st, 6, push, lp, ctrl=ctrl, plant=plant, op=op)
