@@ -956,19 +956,26 @@ __device__ __forceinline__ void roll_load_c(const Layout& L, const LayoutW& LW, 
 #pragma unroll
   for (int i = 0; i < 4; ++i) r.iw[i] = sm[L.CV + 8 * k + 4 + i];
 }
-__device__ __forceinline__ void roll_load_w(const Layout& L, const LayoutW& LW, const double* sm, const double* KD, int k,
-                                            int row, int wi, RollLoadsW& r) {
+// the operands of the rollout's knot in two parts: the old state and the Jacobian blocks ...
+__device__ __forceinline__ void roll_load_state(const Layout& L, const double* sm, int k, RollLoadsW& r) {
 #pragma unroll
   for (int i = 0; i < 13; ++i) r.xo[i] = sm[L.X + 13 * k + i];
 #pragma unroll
   for (int i = 0; i < 18; ++i) r.ab[i] = sm[L.AB + kAB * k + i];
+}
+// ... and the lane's gain row (`row`) and wrench component (`wi`)
+__device__ __forceinline__ void roll_load_gains(const LayoutW& LW, const double* sm, const double* KD, int k, int row, int wi,
+                                                RollLoadsW& r) {
   const double* kd = KD + 156 * k + 13 * row;
 #pragma unroll
   for (int i = 0; i < 13; ++i) r.kd[i] = kd[i];
   r.wk = sm[LW.WR + 6 * k + wi];
 }
-// PF: the next knot's gains / old state / Jacobian blocks are loaded one knot ahead into a second register set (90 more
-// registers: the one-wave-per-SIMD form); without it the loads sit at the top of the knot (two waves per SIMD hide them)
+// PF: the next knot's gain row and wrench component are loaded one knot ahead into a second register set (28 more
+// registers: the one-wave-per-SIMD form); the old state and the Jacobian blocks are loaded at the head of their own knot,
+// as everything is without PF (two waves per SIMD hide the loads).  With xo and ab prefetched too (62 registers more per
+// set) the two sets did not fit beside what is live across the rollout, and the compiler parked about 90 registers in
+// AGPRs in front of the rollout and fetched them back behind it, in every iteration (profiles/HISTORY_r18.md).
 template <bool PROF, bool PF, int NL = 4, int MD = WM_QUAT>
 __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, const LayoutW& LW, double* sm,
                                         const double* KD, double* ROT, int lane, Prof<PROF>& prof, double alpha = 1.0) {
@@ -986,10 +993,11 @@ __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, con
   if (lane == 0)
 #pragma unroll
     for (int i = 0; i < 13; ++i) sm[L.Xc + i] = xc[i];
-  // one knot: gains / old state / Jacobian blocks in `cur`, the next knot's loaded into `nxt` meanwhile (the loop body is
-  // instantiated twice with the roles swapped: no register copies)
+  // one knot: its operands in `cur`, the next knot's gain row loaded into `nxt` meanwhile (the loop body is instantiated
+  // twice with the roles swapped: no register copies)
   auto knot = [&](int k, RollLoadsW& cur, RollLoadsW& nxt) {
-    if (!PF) roll_load_w(L, LW, sm, KD, k, row, wi, cur);
+    roll_load_state(L, sm, k, cur);
+    if (!PF) roll_load_gains(LW, sm, KD, k, row, wi, cur);
     double dx[12], e[12];
     if (MD == WM_CONVEX) {
 #pragma unroll
@@ -1015,7 +1023,7 @@ __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, con
     if (zlane) ROT[zeta_slot<NL>(k, lane - 6)] = s;      // the costate of the contact points, for the input recovery
     double wn = (MD == WM_CONVEX) ? s : cur.wk + s;      // (ConvexMpc: the increment alone; the torque part changes frame below)
     tick_dep1(prof, PH_R_GAIN, wn);
-    if (PF && k + 1 < N) roll_load_w(L, LW, sm, KD, k + 1, row, wi, nxt);      // one knot ahead
+    if (PF && k + 1 < N) roll_load_gains(LW, sm, KD, k + 1, row, wi, nxt);      // one knot ahead
     double w[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) w[i] = read_lane(wn, i);
@@ -1038,7 +1046,7 @@ __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, con
   };
   if (PF) {
     RollLoadsW ra, rb;
-    roll_load_w(L, LW, sm, KD, 0, row, wi, ra);
+    roll_load_gains(LW, sm, KD, 0, row, wi, ra);
     for (int k = 0; k < N; k += 2) {
       knot(k, ra, rb);
       if (k + 1 < N) knot(k + 1, rb, ra);
@@ -1335,7 +1343,8 @@ __device__ inline double rollout_trials_w(const DevParams& P, const Layout& L, c
   double Jx = TM::knot_cost(P, sm + L.refp, sm + L.uref, 0, xc, nullptr);
   // one knot: its gains / old state / Jacobian blocks are loaded at its top
   auto knot = [&](int k, RollLoadsW& cur) {
-    roll_load_w(L, LW, sm, KD, k, row, wi, cur);
+    roll_load_state(L, sm, k, cur);
+    roll_load_gains(LW, sm, KD, k, row, wi, cur);
     double dx[12], e[12];
     if (MD == WM_CONVEX) {
 #pragma unroll
