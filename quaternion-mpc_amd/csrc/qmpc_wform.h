@@ -150,6 +150,16 @@ __device__ __forceinline__ void cv_winv_mul(const double* W, const double t[3], 
   y[1] = W[1] * t[0] + W[2] * t[1];
   y[2] = W[3] * t[2];
 }
+// the same product with its two contracted sums written out, in the pairing the compiler gives cv_winv_mul where the
+// directions load W at its use (read from the listing of qmpc_solve_cw_kernel<3>: y0 = fma(W1, t1, W0 t0), y1 = fma(W1, t0,
+// W2 t1)).  With W in registers ahead of the sum (recover_directions_w<ONEW>) it pairs y0 the other way round and ConvexMpc's
+// forces change in the last bits (profiles/HISTORY_r19.md); contraction is off inside, the sums are exactly these.
+__device__ __forceinline__ void cv_winv_mul_dirs(const double* W, const double t[3], double y[3]) {
+#pragma clang fp contract(off)
+  y[0] = fma(W[1], t[1], W[0] * t[0]);
+  y[1] = fma(W[1], t[0], W[2] * t[1]);
+  y[2] = W[3] * t[2];
+}
 
 // ---- pre-pass over (knot, contact point), one lane each: barrier weights, rotated frame, L D L' of the 3 x 3 block,
 // and the point's share of G = sum V D^-1 V', r6 = sum V D^-1 g (the arithmetic of rotation_prepass in
@@ -761,16 +771,33 @@ __device__ __forceinline__ void srbd_step_w(const DevParams& P, const double gb[
 }
 
 // wrench of every knot from the inputs U (WITH_DU: U + dU), lane (k, i), i < 6
-template <bool WITH_DU, int NL = 4>
+// ONEW (the all-LDS form, one wave per SIMD: nothing hides a wait): the lane's inputs and its point-map row are loaded
+// up front into registers of their own, so that the sums wait for LDS once instead of once per register quad
+// (profiles/HISTORY_r19.md); the sums are the same statements in the same order.  Two waves per SIMD hide the loads
+// already and the registers are not free there: every other form keeps the loads where they are used.
+template <bool WITH_DU, int NL = 4, bool ONEW = false>
 __device__ inline void wrench_from_inputs(const DevParams& P, const Layout& L, const LayoutW& LW, double* sm, int lane) {
   const int N = P.N;
   constexpr int NU = 3 * NL;
   for (int q = lane; q < 6 * N; q += kWave) {
     const int k = q / 6, i = q - 6 * k;
     double u[NU];
+    double u0[NU], du0[NU], b0[NU];
+    if constexpr (ONEW) {
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        u0[j] = sm[L.U + NU * k + j];
+        if (WITH_DU) du0[j] = sm[L.dU + NU * k + j];
+        b0[j] = sm[L.bw0 + ((i >= 3) ? NU * (i - 3) : 0) + j];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < NU; ++j) u[j] = u0[j] + (WITH_DU ? du0[j] : 0.0);
+    } else {
 #pragma unroll
     for (int j = 0; j < NU; ++j) u[j] = sm[L.U + NU * k + j] + (WITH_DU ? sm[L.dU + NU * k + j] : 0.0);
-    const double* b = sm + L.bw0 + ((i >= 3) ? NU * (i - 3) : 0);
+    }
+    const double* b = ONEW ? b0 : sm + L.bw0 + ((i >= 3) ? NU * (i - 3) : 0);
     if (NL == 4) {
       double s0 = 0.0, s1 = 0.0, f0 = 0.0, f1 = 0.0;
 #pragma unroll
@@ -796,14 +823,14 @@ __device__ inline void wrench_from_inputs(const DevParams& P, const Layout& L, c
 }
 
 // shortened primal step: scale the trial increment and re-roll the states open loop from the knots' wrenches
-template <int NL = 4, int MD = WM_QUAT>
+template <int NL = 4, int MD = WM_QUAT, bool ONEW = false>
 __device__ inline void rollout_scaled_w(const DevParams& P, const Layout& L, const LayoutW& LW, double* sm, double ap, int lane) {
   typedef Dim<NL> D;
   const int N = P.N;
   const double* cst = sm + L.cst;
   for (int i = lane; i < N * D::NU; i += kWave) sm[L.dU + i] *= ap;
   QSYNC();
-  wrench_from_inputs<true, NL>(P, L, LW, sm, lane);
+  wrench_from_inputs<true, NL, ONEW>(P, L, LW, sm, lane);
   double gb[3], wd0[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) { gb[a] = cst[D::C_GB + a]; wd0[a] = cst[D::C_WD0 + a]; }
@@ -976,7 +1003,7 @@ __device__ __forceinline__ void roll_load_gains(const LayoutW& LW, const double*
 // as everything is without PF (two waves per SIMD hide the loads).  With xo and ab prefetched too (62 registers more per
 // set) the two sets did not fit beside what is live across the rollout, and the compiler parked about 90 registers in
 // AGPRs in front of the rollout and fetched them back behind it, in every iteration (profiles/HISTORY_r18.md).
-template <bool PROF, bool PF, int NL = 4, int MD = WM_QUAT>
+template <bool PROF, bool PF, int NL = 4, int MD = WM_QUAT, bool BC = false>
 __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, const LayoutW& LW, double* sm,
                                         const double* KD, double* ROT, int lane, Prof<PROF>& prof, double alpha = 1.0) {
   typedef Dim<NL> D;
@@ -1025,8 +1052,16 @@ __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, con
     tick_dep1(prof, PH_R_GAIN, wn);
     if (PF && k + 1 < N) roll_load_gains(LW, sm, KD, k + 1, row, wi, nxt);      // one knot ahead
     double w[6];
+    if (BC) {
+      // lanes 0..11, the only ones whose results are stored, sit in DPP row 0: six moves inside the row instead of twelve
+      // v_readlane_b32; rows 1..3 then advance a state of their own (every lane there holds row 0 of the gains; it may
+      // become non-finite: nothing reads it, no lane there stores, and nothing branches on it)
+      w[0] = row_bcast<0>(wn); w[1] = row_bcast<1>(wn); w[2] = row_bcast<2>(wn);
+      w[3] = row_bcast<3>(wn); w[4] = row_bcast<4>(wn); w[5] = row_bcast<5>(wn);
+    } else {
 #pragma unroll
     for (int i = 0; i < 6; ++i) w[i] = read_lane(wn, i);
+    }
     tick_dep(prof, PH_R_BCAST, w[0], w[5]);
     if (MD == WM_CONVEX) {
       RollLoadsC rc;
@@ -1165,7 +1200,14 @@ __device__ inline int recover_inputs_w(const DevParams& P, const Layout& L, doub
 // (compared by cross-multiplication): one division per lane instead of two per row.  `kapbits` returns the weakly-active
 // flags of the lane's rows (bit 6 j + i: row i of the lane's j-th (knot, point)), read from the DS slot before the
 // directions overwrite it; apply_w consumes them.  Returns nonzero (wave-uniform) when an increment is not finite.
-template <int NL = 4, int MD = WM_QUAT, bool LEAN = (NL == 8)>
+// ONEW (the all-LDS form, one wave per SIMD): the lane's point map bw[9] is read with the record's loads and the cone rows
+// cr[18] once, behind the increment and ahead of the loop over the six rows, instead of row by row inside it; same arithmetic.
+// (cr in front with the record as well: 150 registers of loads in flight, and the compiler parks registers in AGPRs around
+// the phase in every iteration -- profiles/HISTORY_r19.md.)  Of the contracted sums only ConvexMpc's Winv product is written
+// out (cv_winv_mul_dirs); that the others (the bw and T products, the rows' cr . du) pair as in the forms that load at the use
+// is what tests/test_gpu_wave_batched_loads.py and test_gpu_wave_phase_loads.py hold: a compiler update that fails them calls
+// for pinning those sums in the same way.
+template <int NL = 4, int MD = WM_QUAT, bool LEAN = (NL == 8), bool ONEW = false>
 __device__ inline int recover_directions_w(const DevParams& P, const Layout& L, double* sm, double* sl, const double* ROT,
                                            double target, int lane, double* alpha_p, double* alpha_d, double* full_step,
                                            unsigned& kapbits) {
@@ -1173,7 +1215,8 @@ __device__ inline int recover_directions_w(const DevParams& P, const Layout& L, 
   constexpr int LSH = (NL == 8) ? 3 : 2;
   const int N = P.N;
   const double* cst = sm + L.cst;
-  const double* cr = cst + D::C_CR;
+  double cr0[18], bw0[2 * D::NU + 3];      // (bw0: the three rows as far apart as in LDS, so that the sums below index both alike)
+  const double* cr = ONEW ? cr0 : cst + D::C_CR;
   bool bad = false;
   double pn = 1.0, pd = 0.0, dn = 1.0, dd = 0.0;      // smallest s / (-ds), lam / (-dlam) so far, as fractions (den 0: none)
   double stp = 0.0;
@@ -1191,6 +1234,8 @@ __device__ inline int recover_directions_w(const DevParams& P, const Layout& L, 
     for (int i = 0; i < 6; ++i) z[i] = ROT[zeta_slot<NL>(k, i)];
     if (MD == WM_CONVEX) {
       double y[3];
+      if (ONEW) cv_winv_mul_dirs(sm + L.CV + 8 * k, z + 3, y);
+      else
       cv_winv_mul(sm + L.CV + 8 * k, z + 3, y);
       z[3] = y[0]; z[4] = y[1]; z[5] = y[2];
     }
@@ -1202,6 +1247,14 @@ __device__ inline int recover_directions_w(const DevParams& P, const Layout& L, 
       kap[i] = LEAN ? (((kapbits >> (6 * j + i)) & 1u) ? 1.0 : 0.0) : sl[L.DS + i0 + i];
     }
     const double* bw = sm + L.bw0 + 3 * l;
+    if constexpr (ONEW) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) bw0[D::NU * a + b] = bw[D::NU * a + b];
+      __builtin_amdgcn_sched_barrier(0);
+      bw = bw0;
+    }
     double du[3] = {0.0, 0.0, 0.0};
     if (stance) {
       double f[3];
@@ -1217,10 +1270,15 @@ __device__ inline int recover_directions_w(const DevParams& P, const Layout& L, 
 #pragma unroll
       for (int a = 0; a < 3; ++a) du[a] = -(T[3 * a] * x0 + T[3 * a + 1] * x1 + T[3 * a + 2] * x2);
     }
+    if constexpr (ONEW) {
+#pragma unroll
+      for (int i = 0; i < 18; ++i) cr0[i] = cst[D::C_CR + i];
+    }
     double* o = sm + L.dU + D::NU * k + 3 * l;
     o[0] = du[0]; o[1] = du[1]; o[2] = du[2];
     bad = bad || !(isfinite(du[0]) && isfinite(du[1]) && isfinite(du[2]));
     stp = fmax(stp, fmax(fabs(du[0]), fmax(fabs(du[1]), fabs(du[2]))));
+    if constexpr (ONEW) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       const double jd = cr[3 * i] * du[0] + cr[3 * i + 1] * du[1] + cr[3 * i + 2] * du[2];

@@ -72,7 +72,7 @@
   }
   QSYNC();
   rollout_open<WMD, false>(P, L, sm, lane);
-  wrench_from_inputs<false, WNL>(P, L, LW, sm, lane);
+  wrench_from_inputs<false, WNL, !KDG>(P, L, LW, sm, lane);
   expansions_w<WNL, WMT>(P, L, LW, sm, lane);
   double sl_part = 0.0, rc_part = 0.0;
   unsigned kapbits = 0;
@@ -142,17 +142,17 @@
     if (backward_pass_w<PROF, false, WMT>(P, L, bp, sm, KD, GK, lane, prof)) { status = QMPC_NOT_PD; break; }
     QSYNC();
     double ap, ad;
-    rollout_closed_w<PROF, !KDG, WNL, WMT>(P, L, LW, sm, KD, ROT, lane, prof);      // trial step
+    rollout_closed_w<PROF, !KDG, WNL, WMT, !KDG>(P, L, LW, sm, KD, ROT, lane, prof);      // trial step
     prof.tick(PH_ROLL);
     {      // input recovery + directions, one lane per (knot, contact point)
       double stp_;      // a non-finite trial step is not applied and must not become the reported step
-      if (recover_directions_w<WNL, WMT, LEAN>(P, L, sm, sl, ROT, target, lane, &ap, &ad, &stp_, kapbits)) { status = QMPC_NOT_PD; break; }
+      if (recover_directions_w<WNL, WMT, LEAN, !KDG>(P, L, sm, sl, ROT, target, lane, &ap, &ad, &stp_, kapbits)) { status = QMPC_NOT_PD; break; }
       last_step = stp_;
     }
     last_ap = ap; last_ad = ad;
     prof.tick(PH_DIRS);
     if (LEAN) apply_w<WNL, true>(P, L, sl, ap, ad, conmask, lane, kapbits, sl_part, rc_part, sm, target);   // (before dU is scaled)
-    if (ap < 1.0) rollout_scaled_w<WNL, WMT>(P, L, LW, sm, ap, lane);    // shortened primal step
+    if (ap < 1.0) rollout_scaled_w<WNL, WMT, !KDG>(P, L, LW, sm, ap, lane);    // shortened primal step
     prof.tick(PH_ROLL);
     if (!LEAN) apply_w<WNL, false>(P, L, sl, ap, ad, conmask, lane, kapbits, sl_part, rc_part);
     prof.tick(PH_APPLY);
@@ -168,7 +168,7 @@
     // after a shortened step rollout_scaled_w has left the wrenches of U + dU in place: the same numbers as those of the
     // stored sum (every sum of wrench_from_inputs starts from +0.0, which absorbs a zero of either sign: the u + 0.0
     // of this form and the u + du of that one cannot give different wrenches)
-    if (!(ap < 1.0)) wrench_from_inputs<false, WNL>(P, L, LW, sm, lane);
+    if (!(ap < 1.0)) wrench_from_inputs<false, WNL, !KDG>(P, L, LW, sm, lane);
     prof.tick(PH_MISC);
     expansions_w<WNL, WMT>(P, L, LW, sm, lane);
     prof.tick(PH_EXPAND);
