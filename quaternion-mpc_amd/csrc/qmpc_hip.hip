@@ -123,57 +123,55 @@ size_t qmpc_lane_handoff_list_bytes(int batch);
 size_t qmpc_lane_handoff_record_doubles(int N);
 hipError_t qmpc_lane_sort_launch(int batch, hipStream_t s, const void* in, int* scratch);
 
-// qmpc_lane_inst.hip / qmpc_wform_inst_list.hip: per-instance parameters on the lane kernel and its hand-off (QMPC_INSTANCES_AUTO)
+// qmpc_lane_inst.hip, qmpc_lane_inst_warm.hip, qmpc_lane_cinst.hip, qmpc_lane_cinst_warm.hip: per-instance parameters on the lane
+// kernel (QMPC_INSTANCES_AUTO; ConvexMpc: qmpc_set_convex_lane_records) -- cold and warm-started, QuatMpc's and ConvexMpc's.  Each
+// unit defines the same two entry points (qmpc_lane_inst_kernel.inc) and ignores the trailing arguments its kernel does not take;
+// the cold units also define the sort of their model's ticks.
 size_t qmpc_lane_inst_param_bytes(unsigned slots);
-hipError_t qmpc_lane_inst_launch(int pslot, int batch, hipStream_t s, const void* dev_params, size_t dev_params_size, const void* in,
-                                 const void* dev_blocks, const int* status, double* forces, qmpc_info* info, double* ws, double* prm,
-                                 unsigned slots, const int* perm, double* traj_u, double* traj_x, int iter_cap, int* hcount, int* hsel,
-                                 double* hstate, int hcap, int pair);
-hipError_t qmpc_lane_inst_upload_params(int pslot, hipStream_t s, const void* dev_params, size_t dev_params_size);
-hipError_t qmpc_lane_inst_launch_only(int pslot, int batch, hipStream_t s, const void* in, const void* dev_blocks, const int* status,
-                                      double* forces, qmpc_info* info, double* ws, double* prm, unsigned slots, const int* perm,
-                                      double* traj_u, double* traj_x, int iter_cap, int* hcount, int* hsel, double* hstate, int hcap,
-                                      int pair);
-hipError_t qmpc_lane_inst_sort_loop_launch(int batch, hipStream_t s, const void* in, const qmpc_info* prev, const int* status,
-                                           int idle_last, int* scratch);
+#define QMPC_LANE_INST_DECLARE(name)                                                                                                  \
+  hipError_t name##_upload_params(int pslot, hipStream_t s, const void* dev_params, size_t dev_params_size);                         \
+  hipError_t name##_launch_only(int pslot, int batch, hipStream_t s, const void* in, const void* dev_blocks, const int* status,      \
+                                double* forces, qmpc_info* info, double* ws, double* prm, unsigned slots, const int* perm,           \
+                                const double* u_init, double* traj_u, double* traj_x, int check_prev, int iter_cap, int* hcount,     \
+                                int* hsel, double* hstate, int hcap, int pair);
+#define QMPC_LANE_INST_DECLARE_SORT(name)                                                                                             \
+  hipError_t name##_sort_launch(int batch, hipStream_t s, const void* in, const qmpc_info* prev, const int* status, int idle_last,   \
+                                int* scratch);
+QMPC_LANE_INST_DECLARE(qmpc_lane_inst)
+QMPC_LANE_INST_DECLARE(qmpc_lane_inst_warm)
+QMPC_LANE_INST_DECLARE(qmpc_lane_cinst)
+QMPC_LANE_INST_DECLARE(qmpc_lane_cinst_warm)
+QMPC_LANE_INST_DECLARE_SORT(qmpc_lane_inst)
+QMPC_LANE_INST_DECLARE_SORT(qmpc_lane_cinst)
+#undef QMPC_LANE_INST_DECLARE
+#undef QMPC_LANE_INST_DECLARE_SORT
+static const struct {
+  decltype(&qmpc_lane_inst_sort_launch) sort_launch;      // the model's idle-last sort
+  struct {
+    decltype(&qmpc_lane_inst_upload_params) upload_params;
+    decltype(&qmpc_lane_inst_launch_only) launch_only;
+  } start[2];
+} kLaneInst[2] = {      // [convex].start[warm]
+    {qmpc_lane_inst_sort_launch,
+     {{qmpc_lane_inst_upload_params, qmpc_lane_inst_launch_only}, {qmpc_lane_inst_warm_upload_params, qmpc_lane_inst_warm_launch_only}}},
+    {qmpc_lane_cinst_sort_launch,
+     {{qmpc_lane_cinst_upload_params, qmpc_lane_cinst_launch_only}, {qmpc_lane_cinst_warm_upload_params, qmpc_lane_cinst_warm_launch_only}}}};
+// qmpc_wform_inst_list.hip: the lane kernel's hand-off with per-instance parameters
 hipError_t qmpc_wform_inst_list_set_lds();
 hipError_t qmpc_wform_inst_list_launch(int var, int grid, size_t lds, hipStream_t s, const void* dev_blocks, const qmpc_input* in,
                                        double* forces, qmpc_info* info, double* traj_u, double* traj_x, const int* sel,
                                        const int* sel_count, double* gws, const double* hstate, int hcap);
-
-// qmpc_lane_cinst.hip: ConvexMpc's per-instance parameters on the lane kernel (qmpc_set_convex_lane_records under QMPC_INSTANCES_AUTO)
-hipError_t qmpc_lane_cinst_upload_params(int pslot, hipStream_t s, const void* dev_params, size_t dev_params_size);
-hipError_t qmpc_lane_cinst_launch_only(int pslot, int batch, hipStream_t s, const void* in, const void* dev_blocks, const int* status,
-                                       double* forces, qmpc_info* info, double* ws, double* prm, unsigned slots, const int* perm,
-                                       double* traj_u, double* traj_x);
-hipError_t qmpc_lane_cinst_launch(int pslot, int batch, hipStream_t s, const void* dev_params, size_t dev_params_size, const void* in,
-                                  const void* dev_blocks, const int* status, double* forces, qmpc_info* info, double* ws, double* prm,
-                                  unsigned slots, const int* perm, double* traj_u, double* traj_x);
-hipError_t qmpc_lane_cinst_sort_launch(int batch, hipStream_t s, const void* in, const qmpc_info* prev, const int* status, int idle_last,
-                                       int* scratch);
-// qmpc_wform_inst_warm.hip / qmpc_lane_inst_warm.hip: the warm-started ticks of a closed loop with controller records
-// (qmpc_set_loop_warm_records) on the wave kernels and on the lane kernel
+// qmpc_wform_inst_warm.hip, qmpc_wform_cinst_warm.hip: the warm-started ticks of a closed loop with controller records on the wave
+// kernels (qmpc_set_loop_warm_records; ConvexMpc: qmpc_set_convex_warm_records)
 hipError_t qmpc_wform_inst_warm_set_lds();
 hipError_t qmpc_loop_row_reset_launch(hipStream_t s, int* row);
 hipError_t qmpc_wform_inst_warm_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
                                        const qmpc_input* in, const double* u_init, double* forces, qmpc_info* info, double* traj_u,
                                        double* gws, int check_prev);
-hipError_t qmpc_lane_inst_warm_upload_params(int pslot, hipStream_t s, const void* dev_params, size_t dev_params_size);
-hipError_t qmpc_lane_inst_warm_launch_only(int pslot, int batch, hipStream_t s, const void* in, const void* dev_blocks, const int* status,
-                                           double* forces, qmpc_info* info, double* ws, double* prm, unsigned slots, const int* perm,
-                                           const double* u_init, double* traj_u, int check_prev, int iter_cap, int* hcount, int* hsel,
-                                           double* hstate, int hcap, int pair);
-
-// qmpc_wform_cinst_warm.hip / qmpc_lane_cinst_warm.hip: the warm-started ticks of a ConvexMpc closed loop with controller records
-// (qmpc_set_convex_warm_records) on the wave kernels and on the lane kernel
 hipError_t qmpc_wform_cinst_warm_set_lds();
 hipError_t qmpc_wform_cinst_warm_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
                                         const qmpc_input* in, const double* u_init, double* forces, qmpc_info* info, double* traj_u,
                                         double* gws, int check_prev);
-hipError_t qmpc_lane_cinst_warm_upload_params(int pslot, hipStream_t s, const void* dev_params, size_t dev_params_size);
-hipError_t qmpc_lane_cinst_warm_launch_only(int pslot, int batch, hipStream_t s, const void* in, const void* dev_blocks, const int* status,
-                                            double* forces, qmpc_info* info, double* ws, double* prm, unsigned slots, const int* perm,
-                                            const double* u_init, double* traj_u, int check_prev);
 
 // qmpc_wform_cinst.hip: ConvexMpc's solve with per-instance parameters (qmpc_convex_solve_instances*)
 hipError_t qmpc_wform_cinst_set_lds();
@@ -984,54 +982,32 @@ static bool instances_lane_possible(const qmpc_handle* h) {
 //   INST_TICK_FIRST  the cold first tick of a warm-started one (p: the plan with `first`), leaving its solution in tu
 //   INST_TICK_WARM   ... its later ticks: the warm-started kernels start from tu (a robot whose previous solve failed starts cold:
 //                    check_prev) and leave theirs there
-// The wave form: the per-instance wrench-form kernel of the model.  The lane form of QuatMpc: the sort -- the plain call's by
-// stance mask, the loops' also by the previous records' iteration classes, robots that will not solve last --, the lane kernel
-// with per-lane parameters to the cap, the per-instance list kernel on what it leaves (a warm tick's records carry the rows'
-// initial residuals, so only the cold forms honour QMPC_HANDOFF_RESTART).  The plain call uploads the lane kernel's parameter
-// block just before its launch; the loops upload it once per call, outside the capture.  The lane form of ConvexMpc
-// (qmpc_lane_cinst.hip): its sort -- contacts at the convex record's offset, a tick's also by the previous records' iteration
-// classes, robots that will not solve last -- and qmpc_lane_cinst_kernel, which has neither cap nor hand-off; a warm tick:
-// qmpc_lane_cinst_warm_kernel (qmpc_lane_cinst_warm.hip) behind the same sort.
+// The wave form: the per-instance wrench-form kernel of the model.  The lane form, one path through kLaneInst[convex]: the sort --
+// the plain call's by stance mask (QuatMpc: unit 1's, ConvexMpc: its unit's with the contacts at the convex record's offset), a
+// tick's also by the previous records' iteration classes, robots that will not solve last --, the plain call's upload of the
+// lane kernel's parameter block (the loops upload it once per call, outside the capture), the lane kernel with per-lane
+// parameters of the model and start and, for QuatMpc with a cap, the per-instance list kernel on what it leaves (a warm tick's
+// records carry the rows' initial residuals, so only the cold forms honour QMPC_HANDOFF_RESTART).  ConvexMpc's kernels have
+// neither cap nor hand-off.
 enum inst_form { INST_CALL, INST_TICK_COLD, INST_TICK_FIRST, INST_TICK_WARM };
 static qmpc_status inst_solve(qmpc_handle* h, const qmpc_plan& p, bool convex, inst_form form, int32_t batch, const qmpc_input* d_in,
                               double* d_forces, qmpc_info* d_info, double* tu, double* tx, hipStream_t s) {
   const bool warm = form == INST_TICK_WARM;
   double* gws = p.gws ? h->d_gws : nullptr;
-  if (p.variant == 4 && convex) {
-    const int* perm = h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr;
-    if (h->sel.lane_sort)
-      HIP_TRY(qmpc_lane_cinst_sort_launch((int)batch, s, d_in, (form != INST_CALL && p.order_prev) ? d_info : nullptr, inst_status(h),
-                                          form != INST_CALL ? h->sel.lane_sort_idle : 0, h->d_lane_scratch));
-    if (warm)
-      HIP_TRY(qmpc_lane_cinst_warm_launch_only(h->lane_pslot, (int)batch, s, d_in, inst_dev(h), inst_status(h), d_forces, d_info, h->d_lane_ws,
-                                               h->d_lane_prm, h->lane_slots, perm, tu, tu, /*check_prev=*/1));
-    else if (form == INST_CALL)
-      HIP_TRY(qmpc_lane_cinst_launch(h->lane_pslot, (int)batch, s, &h->dev, sizeof h->dev, d_in, inst_dev(h), inst_status(h), d_forces, d_info,
-                                     h->d_lane_ws, h->d_lane_prm, h->lane_slots, perm, tu, tx));
-    else
-      HIP_TRY(qmpc_lane_cinst_launch_only(h->lane_pslot, (int)batch, s, d_in, inst_dev(h), inst_status(h), d_forces, d_info, h->d_lane_ws,
-                                          h->d_lane_prm, h->lane_slots, perm, tu, tx));
-  } else if (p.variant == 4) {
-    const bool cap = p.iter_cap > 0;
+  if (p.variant == 4) {
+    const auto& L = kLaneInst[convex].start[warm];
+    const bool cap = !convex && p.iter_cap > 0;
     const int* perm = h->sel.lane_sort ? h->d_lane_scratch + 512 : nullptr;
     int *hcount = cap ? h->d_handoff : nullptr, *hsel = cap ? h->d_handoff + 64 : nullptr;
     double* hstate = cap ? h->d_hstate : nullptr;
-    if (h->sel.lane_sort && form == INST_CALL) HIP_TRY(qmpc_lane_sort_launch((int)batch, s, d_in, h->d_lane_scratch));
-    if (h->sel.lane_sort && form != INST_CALL)
-      HIP_TRY(qmpc_lane_inst_sort_loop_launch((int)batch, s, d_in, p.order_prev ? d_info : nullptr, inst_status(h), h->sel.lane_sort_idle,
-                                              h->d_lane_scratch));
-    if (warm)
-      HIP_TRY(qmpc_lane_inst_warm_launch_only(h->lane_pslot, (int)batch, s, d_in, inst_dev(h), inst_status(h), d_forces, d_info, h->d_lane_ws,
-                                              h->d_lane_prm, h->lane_slots, perm, tu, tu, /*check_prev=*/1, p.iter_cap, hcount, hsel, hstate,
-                                              h->hstate_cap, h->sel.lane_pair));
-    else if (form == INST_CALL)
-      HIP_TRY(qmpc_lane_inst_launch(h->lane_pslot, (int)batch, s, &h->dev, sizeof h->dev, d_in, inst_dev(h), inst_status(h), d_forces, d_info,
-                                    h->d_lane_ws, h->d_lane_prm, h->lane_slots, perm, tu, tx, p.iter_cap, hcount, hsel, hstate, h->hstate_cap,
-                                    h->sel.lane_pair));
-    else
-      HIP_TRY(qmpc_lane_inst_launch_only(h->lane_pslot, (int)batch, s, d_in, inst_dev(h), inst_status(h), d_forces, d_info, h->d_lane_ws,
-                                         h->d_lane_prm, h->lane_slots, perm, tu, tx, p.iter_cap, hcount, hsel, hstate, h->hstate_cap,
-                                         h->sel.lane_pair));
+    if (h->sel.lane_sort && form == INST_CALL && !convex) HIP_TRY(qmpc_lane_sort_launch((int)batch, s, d_in, h->d_lane_scratch));
+    else if (h->sel.lane_sort)
+      HIP_TRY(kLaneInst[convex].sort_launch((int)batch, s, d_in, (form != INST_CALL && p.order_prev) ? d_info : nullptr, inst_status(h),
+                                            form != INST_CALL ? h->sel.lane_sort_idle : 0, h->d_lane_scratch));
+    if (form == INST_CALL) HIP_TRY(L.upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
+    HIP_TRY(L.launch_only(h->lane_pslot, (int)batch, s, d_in, inst_dev(h), inst_status(h), d_forces, d_info, h->d_lane_ws, h->d_lane_prm,
+                          h->lane_slots, perm, warm ? tu : nullptr, tu, tx, /*check_prev=*/1, p.iter_cap, hcount, hsel, hstate,
+                          h->hstate_cap, h->sel.lane_pair));
     if (cap)
       HIP_TRY(qmpc_wform_inst_list_launch(p.handoff_variant, p.handoff_grid, p.lds, s, inst_dev(h), d_in, d_forces, d_info, tu, tx, hsel, hcount,
                                           gws, (warm || !h->sel.handoff_restart) ? h->d_hstate : nullptr, h->hstate_cap));
@@ -1881,10 +1857,8 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
     return QMPC_OK;
   };
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
-  if (d_ctrl && lpp.variant == 4 && crec) HIP_TRY(qmpc_lane_cinst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
-  if (d_ctrl && lpp.variant == 4 && !crec) HIP_TRY(qmpc_lane_inst_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
-  if (d_ctrl && warm && lpp.variant == 4 && crec) HIP_TRY(qmpc_lane_cinst_warm_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
-  if (d_ctrl && warm && lpp.variant == 4 && !crec) HIP_TRY(qmpc_lane_inst_warm_upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
+  if (d_ctrl && lpp.variant == 4)
+    for (int w = 0; w <= (warm ? 1 : 0); ++w) HIP_TRY(kLaneInst[crec].start[w].upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   return replay_ticks(h, lpp, s, ticks, warm, one_tick);
 }
 

@@ -31,8 +31,8 @@
 // kernels and the launcher (qmpc_lane.hip itself, scheduling strategy max-ilp: +3 % for the pair forms, nothing for the plain
 // ones) -- and QL_UNIT 2 -- the reference mode's kernel with its own launcher (qmpc_lane_ref.hip includes this file; the default
 // strategy: max-ilp costs that kernel 5-8 %, profiles/HISTORY_r06.md).
-// QL_UNIT 3 (qmpc_lane_inst.hip includes this file): the converged mode's kernel with per-lane robot and cost parameters
-// (qmpc_solve_instances* under QMPC_INSTANCES_AUTO) -- what it shares with the two units above is the text up to the kernels.
+// QL_UNIT 3 (qmpc_lane_inst.hip includes this file for the text up to the kernels, then qmpc_lane_inst_kernel.inc; so do 4 .. 6):
+// the converged mode's kernel with per-lane robot and cost parameters (qmpc_solve_instances* under QMPC_INSTANCES_AUTO).
 // QL_UNIT 4 (qmpc_lane_inst_warm.hip includes this file): that kernel warm-started, the later ticks of a closed loop with
 // controller records under lp->warm_start.
 // QL_UNIT 5 (qmpc_lane_cinst.hip includes this file): ConvexMpc's converged-mode kernel with per-lane parameters

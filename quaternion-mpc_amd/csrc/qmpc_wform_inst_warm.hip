@@ -5,84 +5,33 @@
 // sm[L.U], warm_t).  Same sources, same flags as qmpc_wform.hip; a unit of its own so that the kernels of every other unit keep
 // their code to the byte (qmpc_kernel_slots.h).
 #define QMPC_FUSED_TU 1
-#define qmpc qmpc_winstw_tu
+#define QMPC_WINST_TU qmpc_winstw_tu
+#define qmpc QMPC_WINST_TU
 #include "qmpc_kernels.hip"
 #include "qmpc_ref.hip"
 #include "qmpc_wform.h"
 
 namespace qmpc {
 
-// u_init: the previous solutions [batch][N][12] (it may be the buffer traj_u is written to); nullptr: a cold solve.
-// check_prev: info[b] still holds the record of the robot's previous solve; a failed one left no usable solution behind, so
-// this one starts cold -- the rule of qmpc_solve_warm_kernel and of the persistent kernel.
-template <int WVAR>
-__global__ __launch_bounds__(64, (WVAR == 5 || WVAR == 6) ? 2 : 1) void qmpc_solve_w_inst_warm_kernel(
-    const DevParams* __restrict__ Pi, const qmpc_input* __restrict__ in_, const double* u_init, double* __restrict__ forces,
-    qmpc_info* __restrict__ info, double* traj_u, int batch, double* __restrict__ gws, const int* __restrict__ pstatus, int check_prev) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int b = blockIdx.x;
-  if (b >= batch) return;
-  const int wslot = b;
-  const int lane = threadIdx.x;
-  constexpr bool PROF = false;
-  double* traj_x = nullptr;
-  long long* prof_out = nullptr;
-  constexpr const double* resume = nullptr;
-  if (pstatus[b] != QMPC_OK) {      // a rejected record: zero forces and trajectory rows, no iteration
-    const int N = Pi[b].N;
-    if (lane < 12) forces[12 * (size_t)b + lane] = 0.0;
-    if (lane == 0 && info) {
-      qmpc_info r = {QMPC_BAD_PARAMS, 0, 0.0, 0.0, 0.0, 0.0};
-      info[b] = r;
-    }
-    if (traj_u) for (int i = lane; i < N * 12; i += kWave) traj_u[(size_t)b * N * 12 + i] = 0.0;
-    return;
-  }
-  const DevParams& P = Pi[b];
-  const bool usable = u_init && (!check_prev || info[b].status == QMPC_OK || info[b].status == QMPC_MAX_ITER);
-  const int warm_t = usable ? 1 : 0;
-  if (usable) {
-    LayoutW LWw;
-    const Layout Lw = make_layout_w(P.N, &LWw, WVAR == 5 || WVAR == 6, WVAR == 6);
-    for (int i = lane; i < P.N * 12; i += kWave) sm[Lw.U + i] = u_init[(size_t)b * P.N * 12 + i];
-    __syncthreads();
-  }
-#include "qmpc_wform_body.inc"
-}
-
 // The closed loop's trace row counter back to -1 (the tick's front kernel counts it up to the row it writes).  The per-tick loops
 // reset it with a 4-byte memset; inside a stream capture of the CALLER's the reset is this kernel instead, a kernel node like the
-// ticks it precedes (qmpc_hip.hip: loop_setup).  Here because this unit is new: no other unit's code object changes.
+// ticks it precedes (qmpc_hip.hip: loop_setup).  Here because this unit was new with it: no other unit's code object changed.
 __global__ __launch_bounds__(64) void qmpc_loop_row_reset_kernel(int* __restrict__ row) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *row = -1;
 }
 
 }  // namespace qmpc
-#undef qmpc
 
-#include "qmpc_kernel_slots.h"
+#define QMPC_WINST_KERNEL qmpc_solve_w_inst_warm_kernel
+#define QMPC_WINST_CONVEX 0
+#define QMPC_WINST_WARM 1
+#define QMPC_WINST_SLOT wform_inst_warm_slot
+#define QMPC_WINST_SLOTS kWformInstWarmSlots
+#define QMPC_WINST_SET_LDS qmpc_wform_inst_warm_set_lds
+#define QMPC_WINST_LAUNCH qmpc_wform_inst_warm_launch
+#include "qmpc_wform_inst_kernel.inc"
 
-using namespace qmpc_winstw_tu;
-using namespace qmpc;
-
-static decltype(&qmpc_solve_w_inst_warm_kernel<3>) const kWformInstWarm[] = {
-    qmpc_solve_w_inst_warm_kernel<3>, qmpc_solve_w_inst_warm_kernel<5>, qmpc_solve_w_inst_warm_kernel<6>};
-static_assert(sizeof kWformInstWarm / sizeof kWformInstWarm[0] == kWformInstWarmSlots, "qmpc_kernel_slots.h");
-
-// called from qmpc_hip.hip (declared there); hidden: not part of the C ABI
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_warm_set_lds() { return set_max_lds(kWformInstWarm); }
 __attribute__((visibility("hidden"))) hipError_t qmpc_loop_row_reset_launch(hipStream_t s, int* row) {
   hipLaunchKernelGGL(qmpc_loop_row_reset_kernel, dim3(1), dim3(kWave), 0, s, row);
-  return hipGetLastError();
-}
-// variant var (3 / 5 / 6) on the expanded blocks and verdicts (dev_blocks / status) of qmpc_wform_inst_expand_launch
-__attribute__((visibility("hidden"))) hipError_t qmpc_wform_inst_warm_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks,
-                                                                             const int* status, const qmpc_input* in, const double* u_init,
-                                                                             double* forces, qmpc_info* info, double* traj_u, double* gws,
-                                                                             int check_prev) {
-  const int k = wform_inst_warm_slot(var);
-  if (k < 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kWformInstWarm[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks), in, u_init,
-                     forces, info, traj_u, batch, gws, status, check_prev);
   return hipGetLastError();
 }

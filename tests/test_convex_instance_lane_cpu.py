@@ -163,7 +163,7 @@ def test_abi_without_a_device(pkg, lib):
     assert pkg.QUERY_CONVEX_RECORDS == 13 and pkg.QUERY_KERNEL_FOR_CONVEX_INSTANCES == 12
     nm = subprocess.run(["nm", "-D", "--defined-only", str(CORE / "libqmpc_hip.so")], check=True, capture_output=True, text=True).stdout
     assert "qmpc_set_convex_lane_records" in pkg.EXPORTED_SYMBOLS and re.search(r" T qmpc_set_convex_lane_records$", nm, re.M)
-    for hidden in ("qmpc_lane_cinst_launch", "qmpc_lane_cinst_upload_params", "qmpc_lane_cinst_sort_launch"):
+    for hidden in ("qmpc_lane_cinst_launch_only", "qmpc_lane_cinst_upload_params", "qmpc_lane_cinst_sort_launch"):
         assert hidden not in nm, hidden      # (the unit's launchers are hidden: not part of the C ABI)
     assert lib.qmpc_set_convex_lane_records.argtypes == [C.c_void_p, C.c_int32] and lib.qmpc_set_convex_lane_records.restype == C.c_int32
     for on in (0, 1, 2, -1):

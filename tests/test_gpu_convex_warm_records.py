@@ -23,6 +23,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from records_fleet import convex_fleet as _fleet, same as _same, walk as _walk
+
 pytestmark = pytest.mark.gpu
 
 T0 = 6      # standing ticks before the robots walk
@@ -40,36 +42,12 @@ def _params(pkg, lib, N, mode=None):
     return p
 
 
-def _same(a, b):
-    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
-
-
 def _all_same(got, want):
     return len(got) == len(want) and all(_same(a, b) for a, b in zip(got, want))
 
 
 def _last(pkg, s):
     return pkg.KERNEL_FAMILY[s.query(pkg.QUERY_LAST_KERNEL)]
-
-
-def _fleet(pkg, lib, B, seed=29):
-    """the fleet and commands of tests/test_gpu_convex_loop_instance_lane.py, with lp.warm_start set"""
-    rng = np.random.default_rng(seed)
-    lp = pkg.default_loop_params(lib)
-    lp.warm_start = 1.0
-    cmds = np.zeros((B, 7))
-    cmds[:, 0] = 0.6 * rng.uniform(-0.5, 0.5, B); cmds[:, 1] = rng.uniform(-0.2, 0.2, B); cmds[:, 2] = rng.uniform(0.26, 0.32, B)
-    cmds[:, 5] = rng.uniform(-0.5, 0.5, B); cmds[:, 6] = (rng.random(B) < 0.9).astype(float)
-    cmds[cmds[:, 6] == 0, :2] = 0.0
-    cmds[cmds[:, 6] == 0, 5] = 0.0
-    stand = cmds.copy(); stand[:, 6] = 0.0
-    return lp, pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, B), lib=lib), cmds
-
-
-def _walk(run, st, cmds, t0, t):
-    st0 = run(st, t0, False)
-    st0["movement_mode"] = cmds[:, 6]
-    return run(st0, t, True)
 
 
 def _solver(pkg, lib, p, B, lane=False):

@@ -16,16 +16,9 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from records_fleet import quat_fleet as _fleet, same as _same, walk as _walk
 
-COMMANDS = [   # joy.{velx, vely, body_height, roll_rate, pitch_rate, yaw_rate}, movement_mode
-    [0.0, 0.0, 0.30, 0.0, 0.0, 0.0, 0.0],
-    [0.3, 0.0, 0.30, 0.0, 0.0, 0.0, 1.0],
-    [0.2, -0.1, 0.28, 0.0, 0.0, 0.3, 1.0],
-    [0.0, 0.0, 0.30, 0.1, -0.1, 0.0, 1.0],
-    [-0.2, 0.05, 0.32, 0.0, 0.0, -0.2, 1.0],
-    [0.0, 0.0, 0.27, 0.0, 0.0, 0.0, 0.0],
-]
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -37,29 +30,6 @@ def _params(pkg, lib, N):
     p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
     p.ipm_mu0 = 1e-6
     return p
-
-
-def _fleet(pkg, lib, B, seed=1, trot=False):
-    """B robots standing at their initial poses (movement 0) and the commands they walk with afterwards (the fleet of
-    tests/test_gpu_loop_instances.py); trot: every robot walks"""
-    lp = pkg.default_loop_params(lib)
-    lp.warm_start = 1.0
-    rng = np.random.default_rng(seed)
-    cmds = np.array([COMMANDS[1 + i % 4] if trot else COMMANDS[i % len(COMMANDS)] for i in range(B)])
-    cmds[:, 0] += rng.uniform(-0.1, 0.1, B) * cmds[:, 6]
-    stand = cmds.copy(); stand[:, 6] = 0.0
-    st = pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, B), lib=lib)
-    return lp, st, cmds
-
-
-def _walk(run, st, cmds, t0, t):
-    st0 = run(st, t0, False)
-    st0["movement_mode"] = cmds[:, 6]
-    return run(st0, t, True)
-
-
-def _same(a, b):
-    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
 
 
 def _last(pkg, s):
