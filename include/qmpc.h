@@ -922,6 +922,68 @@ qmpc_status qmpc_loop_run_pushes_device(qmpc_handle* h, const qmpc_loop_params* 
                                         const qmpc_outcome_params* op, qmpc_loop_outcome* d_outcomes,
                                         const qmpc_push_params* d_push, int32_t pushes_per_robot, void* stream);
 
+/* ---- per-robot ground friction and force limits in the plant (the true ground under each foot) -------------------------
+ * The controller records carry a friction coefficient and a normal-force bound; the plant above delivers whatever force the
+ * solve returns.  qmpc_loop_run_ground* is qmpc_loop_run_pushes* -- the same robots, launch forms
+ * (QMPC_QUERY_LOOP_INSTANCES_PLAN answers for it too), refusals, ticks = 0 behaviour, freezing and halting -- whose plant
+ * integrates under the force the robot's TRUE ground delivers.  The controller is not told.
+ *
+ * In the back end of a tick, after grf_world has been formed as always (QuatMpc: R forces_body; ConvexMpc: the solve's
+ * world-frame forces), every leg with contacts[l] != 0 of a robot whose record has at least one finite field is clamped on
+ * its world-frame force f = (fx, fy, fz), in this order (loop_ground_leg, csrc/qmpc_loop_math.h: one source for the device,
+ * the host class and the tests):
+ *   1. fz < 0: f = 0 (the ground does not pull); counted as normal
+ *   2. fz > fz_max[l]: fz = fz_max[l]; counted as normal
+ *   3. t = sqrt(fx fx + fy fy) > mu[l] fz: fx and fy are multiplied by s = (mu[l] fz) / t; counted as friction (mu = 0 gives
+ *      zeros of either sign)
+ * A leg no rule changed keeps its bytes -- no arithmetic, no `+ 0.0`; swing legs are not looked at.  The plant step takes the
+ * delivered body-frame force R' f of a changed leg and the commanded forces_body bytes of an unchanged one, under the tick's
+ * effective wrench (pushes compose).  state.grf_world holds the DELIVERED force; state.forces_body and trace_forces stay
+ * the controller's COMMAND (what tau = -J' f and the outcome record's max_force_z read, what a warm start continues from).
+ * (A ConvexMpc tick whose solve was rejected clamps R forces_body, the command the plant keeps applying.)
+ * So ground == NULL, an all-+inf record and a finite record that never binds give the bytes of qmpc_loop_run_pushes*.
+ * (Never binds is a statement about the forces too: a stance leg whose command is the solver's zero arrives as +-1e-15 N per
+ * component, and a finite record binds there on a negative fz or on |f_xy| > mu fz; an all-+inf record looks at no leg.)
+ *
+ * tally (may be NULL) accumulates over calls like the outcome records, from the same verdicts; a robot that is frozen or
+ * halted leaves its tally untouched.  Start from qmpc_ground_tally_init.
+ *
+ * A record with a NaN field, a mu < 0 or an fz_max <= 0 makes its robot the robot of an invalid plant record
+ * (QMPC_BAD_PARAMS: state untouched except status and iterations, zero trace rows, outcome record and tally untouched, every
+ * other robot unaffected bit for bit).  ground == NULL: the call IS qmpc_loop_run_pushes* and tally is not touched.  push may be
+ * NULL (no windows; pushes_per_robot ignored).  Buffers: those of the push call; the device call reads d_ground in place;
+ * the host-buffer call stages records and tallies in a buffer of its own ((64 + 32) B x max_batch), allocated on its first
+ * use -- a call with ticks = 0 included.  No other call allocates it. */
+typedef struct qmpc_ground_params {   /* 8 doubles, 64 B: the TRUE ground / actuator under each foot */
+  double mu[4];       /* Coulomb coefficient under leg l; +inf: no limit; 0 legal (ice) */
+  double fz_max[4];   /* largest normal force leg l can receive [N]; +inf: no limit */
+} qmpc_ground_params;
+typedef struct qmpc_ground_tally {    /* 4 doubles, 32 B; in/out: accumulates over calls */
+  double clipped_ticks;          /* ticks in which the delivered force of >= 1 stance leg differs from the command */
+  double first_clipped_tick;     /* state.tick after the first such tick; -1: never */
+  double friction_leg_ticks;     /* (leg, tick) pairs whose tangential force was scaled down */
+  double normal_leg_ticks;       /* (leg, tick) pairs whose normal force was cut (above fz_max, or negative) */
+} qmpc_ground_tally;
+/* Host-side; every byte is written: every field +inf / 0, -1, 0, 0 */
+void    qmpc_ground_params_init(qmpc_ground_params* g, int32_t batch);
+void    qmpc_ground_tally_init(qmpc_ground_tally* t, int32_t batch);
+int32_t qmpc_sizeof_ground_params(void);
+int32_t qmpc_sizeof_ground_tally(void);
+/* Host buffers: qmpc_loop_run_pushes' arguments, then ground [batch] and tally [batch] in/out (or NULL).  Synchronous. */
+qmpc_status qmpc_loop_run_ground(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                 int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant,
+                                 double* trace_forces, double* trace_contacts, const qmpc_outcome_params* op,
+                                 qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int32_t pushes_per_robot,
+                                 const qmpc_ground_params* ground, qmpc_ground_tally* tally);
+/* Device buffers (op is a host pointer, read during the call), stream-ordered (NULL stream = the handle's). */
+qmpc_status qmpc_loop_run_ground_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch,
+                                        qmpc_loop_state* d_states, int32_t ticks,
+                                        const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                        double* d_trace_forces, double* d_trace_contacts,
+                                        const qmpc_outcome_params* op, qmpc_loop_outcome* d_outcomes,
+                                        const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                        const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally, void* stream);
+
 /* Stand-pose joint angles (0, 0.67, -1.3 per leg: the reference's Gazebo start pose) for `batch`
  * robots, host buffer [batch][12]. */
 void qmpc_loop_joint_init(double* joint_pos, int32_t batch);

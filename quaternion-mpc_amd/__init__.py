@@ -280,6 +280,37 @@ def push_params(batch: int, per_robot: int = 1) -> np.ndarray:
     return np.zeros((int(batch), int(per_robot)), dtype=PUSH_PARAMS_DTYPE)
 
 
+# struct qmpc_ground_params (qmpc_loop_run_ground*): the TRUE ground / actuator under each foot of one robot, 8 doubles = 64 B
+GROUND_PARAMS_DTYPE = np.dtype([("mu", "<f8", (4,)), ("fz_max", "<f8", (4,))], align=False)
+# struct qmpc_ground_tally: what the ground cut of one robot's commands, 4 doubles = 32 B (in/out: accumulates over calls)
+GROUND_TALLY_DTYPE = np.dtype(
+    [
+        ("clipped_ticks", "<f8"),
+        ("first_clipped_tick", "<f8"),
+        ("friction_leg_ticks", "<f8"),
+        ("normal_leg_ticks", "<f8"),
+    ],
+    align=False,
+)
+assert GROUND_PARAMS_DTYPE.itemsize == 8 * 8 and GROUND_TALLY_DTYPE.itemsize == 4 * 8
+
+
+def ground_params(batch: int) -> np.ndarray:
+    """[batch] ground records that limit nothing: every field +inf, the bytes of qmpc_ground_params_init (set mu / fz_max per
+    robot and leg)."""
+    out = np.zeros(int(batch), dtype=GROUND_PARAMS_DTYPE)
+    out["mu"] = np.inf
+    out["fz_max"] = np.inf
+    return out
+
+
+def ground_tallies(batch: int) -> np.ndarray:
+    """[batch] empty tallies: 0, -1, 0, 0, the bytes of qmpc_ground_tally_init."""
+    out = np.zeros(int(batch), dtype=GROUND_TALLY_DTYPE)
+    out["first_clipped_tick"] = -1.0
+    return out
+
+
 # struct qmpc_info: 2 x int32 + 4 doubles = 40 B
 INFO_DTYPE = np.dtype(
     [
@@ -383,6 +414,15 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_pushes_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
                                                 i32, vp]
     lib.qmpc_loop_run_pushes_device.restype = i32
+    lib.qmpc_ground_params_init.argtypes = [vp, i32]
+    lib.qmpc_ground_params_init.restype = None
+    lib.qmpc_ground_tally_init.argtypes = [vp, i32]
+    lib.qmpc_ground_tally_init.restype = None
+    lib.qmpc_loop_run_ground.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp]
+    lib.qmpc_loop_run_ground.restype = i32
+    lib.qmpc_loop_run_ground_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
+                                                i32, vp, vp, vp]
+    lib.qmpc_loop_run_ground_device.restype = i32
     lib.qmpc_set_instances_policy.argtypes = [vp, i32]
     lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_set_loop_warm_records.argtypes = [vp, i32]
@@ -463,7 +503,7 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_device.restype = i32
     for name in ("qmpc_sizeof_input", "qmpc_sizeof_params", "qmpc_sizeof_info", "qmpc_sizeof_convex_input",
                  "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params", "qmpc_sizeof_plant_params",
-                 "qmpc_sizeof_loop_outcome", "qmpc_sizeof_push_params"):
+                 "qmpc_sizeof_loop_outcome", "qmpc_sizeof_push_params", "qmpc_sizeof_ground_params", "qmpc_sizeof_ground_tally"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = i32
     if lib.qmpc_sizeof_input() != INPUT_DTYPE.itemsize:
@@ -486,6 +526,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         raise RuntimeError("qmpc_loop_outcome ABI size mismatch")
     if lib.qmpc_sizeof_push_params() != PUSH_PARAMS_DTYPE.itemsize:
         raise RuntimeError("qmpc_push_params ABI size mismatch")
+    if lib.qmpc_sizeof_ground_params() != GROUND_PARAMS_DTYPE.itemsize or lib.qmpc_sizeof_ground_tally() != GROUND_TALLY_DTYPE.itemsize:
+        raise RuntimeError("qmpc_ground_params / qmpc_ground_tally ABI size mismatch")
     return lib
 
 
@@ -567,6 +609,12 @@ EXPORTED_SYMBOLS = (
     "qmpc_sizeof_push_params",
     "qmpc_loop_run_pushes",
     "qmpc_loop_run_pushes_device",
+    "qmpc_ground_params_init",
+    "qmpc_ground_tally_init",
+    "qmpc_sizeof_ground_params",
+    "qmpc_sizeof_ground_tally",
+    "qmpc_loop_run_ground",
+    "qmpc_loop_run_ground_device",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
@@ -994,6 +1042,75 @@ class Solver:
         if rc != OK:
             raise QmpcError(rc, "qmpc_loop_run_pushes_device")
 
+    def loop_run_ground(self, states: np.ndarray, ticks: int, ground: np.ndarray | None, push: np.ndarray | None = None,
+                        lp: LoopParams | None = None, ctrl: np.ndarray | None = None, plant: np.ndarray | None = None,
+                        op: OutcomeParams | None = None, outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None,
+                        trace: bool = False):
+        """qmpc_loop_run_ground: loop_run_pushes whose plant integrates under the force the robot's TRUE ground delivers.
+        ground: [B] GROUND_PARAMS_DTYPE records, ground_params(); None: exactly loop_run_pushes (the tallies come back as given).
+        tallies: the GROUND_TALLY_DTYPE records to go on accumulating into (None: empty ones).  Returns (states, outcomes,
+        tallies[, forces, contacts]); the arguments are not modified."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
+        B = st.shape[0]
+        if ctrl is not None:
+            ctrl = np.ascontiguousarray(ctrl, dtype=INSTANCE_PARAMS_DTYPE)
+            if ctrl.shape != (B,):
+                raise ValueError(f"ctrl: shape {ctrl.shape}, expected ({B},)")
+        if plant is not None:
+            plant = np.ascontiguousarray(plant, dtype=PLANT_PARAMS_DTYPE)
+            if plant.shape != (B,):
+                raise ValueError(f"plant: shape {plant.shape}, expected ({B},)")
+        per_robot = 0
+        if push is not None:
+            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
+            if push.ndim == 1:
+                push = push.reshape(-1, 1)
+            if push.ndim != 2 or push.shape[0] != B:
+                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
+            per_robot = push.shape[1]
+            if per_robot == 0:
+                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
+        if ground is not None:
+            ground = np.ascontiguousarray(ground, dtype=GROUND_PARAMS_DTYPE)
+            if ground.shape != (B,):
+                raise ValueError(f"ground: shape {ground.shape}, expected ({B},)")
+        if outcomes is None:
+            oc = loop_outcomes(B, self.lib)
+        else:
+            oc = np.ascontiguousarray(outcomes, dtype=LOOP_OUTCOME_DTYPE).copy()
+            if oc.shape != (B,):
+                raise ValueError(f"outcomes: shape {oc.shape}, expected ({B},)")
+        if tallies is None:
+            ta = ground_tallies(B)
+        else:
+            ta = np.ascontiguousarray(tallies, dtype=GROUND_TALLY_DTYPE).copy()
+            if ta.shape != (B,):
+                raise ValueError(f"tallies: shape {ta.shape}, expected ({B},)")
+        tf = np.zeros((ticks, B, 12)) if trace else None
+        tc = np.zeros((ticks, B, 4)) if trace else None
+        rc = self.lib.qmpc_loop_run_ground(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
+                                           C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_ground")
+        return (st, oc, ta, tf, tc) if trace else (st, oc, ta)
+
+    def loop_run_ground_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_ground: int, d_tally: int = 0,
+                               d_push: int = 0, pushes_per_robot: int = 0, lp: LoopParams | None = None,
+                               op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0,
+                               d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_ground_device: device pointers (ints; 0 = NULL), stream-ordered; d_ground and d_push are read in place,
+        d_tally (or 0) is read and written."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        rc = self.lib.qmpc_loop_run_ground_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
+                                                  p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
+                                                  int(pushes_per_robot), p(d_ground), p(d_tally), p(stream))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_ground_device")
+
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
         as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN).  Answers under the handle's
@@ -1306,5 +1423,5 @@ class Solver:
 
 from .scenarios import (go1_stand_input, quat_to_rot, random_go1_trot_states,  # noqa: E402,F401
                         random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_convex_variants, random_go1_plants,
-                        random_go1_pushes)
+                        random_go1_pushes, random_go1_grounds)
 from .sharding import StepPipeline, gather_forces, shard_range, solve_sharded  # noqa: E402,F401

@@ -68,40 +68,47 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
                                         const qmpc_input* in, double* forces, qmpc_info* info, double* traj_u, double* traj_x,
                                         double* gws);
 
-// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip: the closed loop with per-robot records -- controller and plant
-// records (qmpc_loop_run_instances*), with the outcome step (qmpc_loop_run_outcomes*), under timed push windows
-// (qmpc_loop_run_pushes*).  Each unit defines the same entry points in its namespace (qmpc_loop_rec.inc) and ignores the
-// trailing arguments its kernels do not take; the push unit has no front kernel of its own.
+// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip, qmpc_loop_ground.hip: the closed loop with per-robot records --
+// controller and plant records (qmpc_loop_run_instances*), with the outcome step (qmpc_loop_run_outcomes*), under timed push
+// windows (qmpc_loop_run_pushes*), on the robot's true ground (qmpc_loop_run_ground*).  Each unit defines the same entry points in
+// its namespace (qmpc_loop_rec.inc) and ignores the trailing arguments its kernels do not take; the push and ground units have no
+// front kernel of their own.
 #define QMPC_REC_DECLARE(ns)                                                                                                         \
   namespace ns {                                                                                                                     \
   hipError_t rec_set_lds();                                                                                                          \
   hipError_t rec_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,            \
                               const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info,    \
                               double* trace_f, double* trace_c, int ticks, double* gws, const qmpc_outcome_params* op,              \
-                              qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot);                            \
+                              qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,                             \
+                              const qmpc_ground_params* ground, qmpc_ground_tally* tally);                                          \
   hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, int* row,            \
                               const void* plants, int batch, const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes);     \
   hipError_t rec_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, const double* forces,                  \
                              const qmpc_info* info, double* trace_f, double* trace_c, const int* row, const void* plants, int batch, \
                              const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push,              \
-                             int per_robot);                                                                                         \
+                             int per_robot, const qmpc_ground_params* ground, qmpc_ground_tally* tally);                             \
   }
 QMPC_REC_DECLARE(qmpc_inst_tu)
 QMPC_REC_DECLARE(qmpc_outc_tu)
 QMPC_REC_DECLARE(qmpc_push_tu)
 QMPC_REC_DECLARE(qmpc_crec_tu)      // qmpc_loop_crec.hip: the three kinds on a ConvexMpc handle (qmpc_set_convex_records)
+QMPC_REC_DECLARE(qmpc_ground_tu)    // qmpc_loop_ground.hip
+QMPC_REC_DECLARE(qmpc_cground_tu)   // qmpc_loop_cground.hip: the ground call on such a ConvexMpc handle
 #undef QMPC_REC_DECLARE
 enum { REC_PLAIN = 0, REC_OUTCOME = 1, REC_PUSH = 2 };      // the kind of a call with records: QMPC_REC_EXT of its unit
-enum { REC_CONVEX = 3 };                                    // ... the unit that serves every kind for ConvexMpc's problem
+enum { REC_CONVEX = 3 };                                    // ... the unit that serves those three kinds for ConvexMpc's problem
+enum { REC_GROUND = 4, REC_CGROUND = 5 };                   // the ground call's kind (EXT 3), and its unit for ConvexMpc's problem
 static const struct {
   decltype(&qmpc_inst_tu::rec_set_lds) set_lds;
   decltype(&qmpc_inst_tu::rec_fused_launch) fused_launch;
   decltype(&qmpc_inst_tu::rec_front_launch) front_launch;
   decltype(&qmpc_inst_tu::rec_post_launch) post_launch;
-} kRec[4] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
+} kRec[6] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
              {qmpc_outc_tu::rec_set_lds, qmpc_outc_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_outc_tu::rec_post_launch},
              {qmpc_push_tu::rec_set_lds, qmpc_push_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_push_tu::rec_post_launch},
-             {qmpc_crec_tu::rec_set_lds, qmpc_crec_tu::rec_fused_launch, qmpc_crec_tu::rec_front_launch, qmpc_crec_tu::rec_post_launch}};
+             {qmpc_crec_tu::rec_set_lds, qmpc_crec_tu::rec_fused_launch, qmpc_crec_tu::rec_front_launch, qmpc_crec_tu::rec_post_launch},
+             {qmpc_ground_tu::rec_set_lds, qmpc_ground_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_ground_tu::rec_post_launch},
+             {qmpc_cground_tu::rec_set_lds, qmpc_cground_tu::rec_fused_launch, qmpc_cground_tu::rec_front_launch, qmpc_cground_tu::rec_post_launch}};
 // ... and the kernels each unit has beside them: the expansions of the plant blocks and the check of the windows
 hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, const qmpc_plant_params* plant,
                                         const qmpc_instance_params* ctrl, const int* ctrl_status, void* bcast_out, void* plants_out,
@@ -109,6 +116,9 @@ hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, s
 hipError_t qmpc_loop_outcome_expand_base_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, void* bcast_out,
                                                 void* plants_out, int batch);
 hipError_t qmpc_loop_push_check_launch(hipStream_t s, const qmpc_push_params* push, int per_robot, void* plants, int batch);
+namespace qmpc_ground_tu {
+hipError_t rec_ground_check_launch(hipStream_t s, const qmpc_ground_params* ground, void* plants, int batch);
+}
 
 // qmpc_lane.hip (third translation unit): the lane-per-instance kernel of large batches
 size_t qmpc_lane_ws_bytes(int N, int nl, unsigned slots, int wide);
@@ -233,6 +243,8 @@ struct qmpc_handle {
   qmpc_loop_outcome* d_outcome;   // staging of qmpc_loop_run_outcomes (the host-buffer call), on its first use: [max_batch] records
   qmpc_push_params* d_push;       // staging of qmpc_loop_run_pushes (the host-buffer call), on its first use: [max_batch][push_cap]
   int push_cap;                   // ... windows per robot it holds (grown when a call brings more)
+  void* d_ground;                 // staging of qmpc_loop_run_ground (the host-buffer call), on its first use: max_batch ground
+                                  // records (64 B each), then max_batch tallies (32 B each)
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -459,6 +471,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_plant) (void)hipFree(h->d_plant);
   if (h->d_outcome) (void)hipFree(h->d_outcome);
   if (h->d_push) (void)hipFree(h->d_push);
+  if (h->d_ground) (void)hipFree(h->d_ground);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1186,6 +1199,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_plant) b += plant_bytes(h->max_batch);
       if (h->d_outcome) b += sizeof(qmpc_loop_outcome) * (size_t)h->max_batch;
       if (h->d_push) b += sizeof(qmpc_push_params) * (size_t)h->push_cap * (size_t)h->max_batch;
+      if (h->d_ground) b += (sizeof(qmpc_ground_params) + sizeof(qmpc_ground_tally)) * (size_t)h->max_batch;
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
       return QMPC_OK;
@@ -1676,15 +1690,18 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
 static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
-                                       qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot, void* stream);
+                                       qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot,
+                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally, void* stream);
 
 // The host-buffer closed loop of every kind (qmpc_loop_run*, its arguments checked): states and traces through the handle's
 // staging, which only grows -- [states | force trace | contact trace]; the records given go to the staging halves of the
-// per-instance and plant buffers, outcome records and windows to h->d_outcome and h->d_push (all allocated by the caller)
+// per-instance and plant buffers, outcome records and windows to h->d_outcome and h->d_push, ground records and tallies to
+// h->d_ground (all allocated by the caller)
 static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
                                      int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                      double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
-                                     const qmpc_push_params* push, int32_t per_robot) {
+                                     const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
+                                     qmpc_ground_tally* tally) {
   const size_t B = (size_t)batch, T = (size_t)ticks;
   const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
                n_tc = trace_contacts ? 4 * B * T : 0;
@@ -1703,10 +1720,15 @@ static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_p
   if (ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
   if (plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
   if (push) HIP_TRY(hipMemcpyAsync(h->d_push, push, sizeof(qmpc_push_params) * B * (size_t)per_robot, hipMemcpyHostToDevice, h->stream));
+  qmpc_ground_params* d_gr = ground ? static_cast<qmpc_ground_params*>(h->d_ground) : nullptr;
+  qmpc_ground_tally* d_ta = (ground && tally) ? reinterpret_cast<qmpc_ground_tally*>(static_cast<qmpc_ground_params*>(h->d_ground) + h->max_batch) : nullptr;
+  if (d_gr) HIP_TRY(hipMemcpyAsync(d_gr, ground, sizeof(qmpc_ground_params) * B, hipMemcpyHostToDevice, h->stream));
+  if (d_ta) HIP_TRY(hipMemcpyAsync(d_ta, tally, sizeof(qmpc_ground_tally) * B, hipMemcpyHostToDevice, h->stream));
   const qmpc_status rs = loop_records_device(kind, h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
                                              d_tf, d_tc, op, outcomes ? h->d_outcome : nullptr, push ? h->d_push : nullptr, per_robot,
-                                             nullptr);
+                                             d_gr, d_ta, nullptr);
   if (rs != QMPC_OK) return rs;
+  if (d_ta) HIP_TRY(hipMemcpyAsync(tally, d_ta, sizeof(qmpc_ground_tally) * B, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
   if (outcomes) HIP_TRY(hipMemcpyAsync(outcomes, h->d_outcome, sizeof(qmpc_loop_outcome) * B, hipMemcpyDeviceToHost, h->stream));
   if (d_tf) HIP_TRY(hipMemcpyAsync(trace_forces, d_tf, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream));
@@ -1722,7 +1744,7 @@ qmpc_status qmpc_loop_run(qmpc_handle* h, const qmpc_loop_params* lp, int32_t ba
   if (batch == 0 || ticks == 0) return QMPC_OK;
   if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
   HIP_TRY(hipSetDevice(h->device));
-  return loop_records_host(REC_PLAIN, h, lp, batch, states, ticks, nullptr, nullptr, trace_forces, trace_contacts, nullptr, nullptr, nullptr, 0);
+  return loop_records_host(REC_PLAIN, h, lp, batch, states, ticks, nullptr, nullptr, trace_forces, trace_contacts, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
 }
 
 // ---- the closed loop with per-robot controller and plant records (qmpc_loop_inst.hip) -------------------------------------
@@ -1792,11 +1814,13 @@ static qmpc_status loop_instances_buffers(qmpc_handle* h, int32_t batch, bool ha
 // records is the plain loop.  REC_OUTCOME / REC_PUSH (qmpc_loop_run_outcomes_device / qmpc_loop_run_pushes_device): the same call
 // with the kernels of the kind's unit in place of the plain unit's; without records (both NULL) every robot's plant block carries
 // the handle's mass and inverse inertia, and the call-level checks are those of a call with plant records.  d_push (REC_PUSH):
-// per_robot windows per robot, checked once after the plant expansion.
+// per_robot windows per robot, checked once after the plant expansion.  REC_GROUND (qmpc_loop_run_ground_device): d_push may be
+// NULL (no windows), d_ground is checked after the windows, d_tally may be NULL.
 static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
-                                       qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot, void* stream) {
+                                       qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot,
+                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally, void* stream) {
   if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !d_states)) return QMPC_BAD_ARGUMENT;
   if (kind != REC_PLAIN && (!op || (batch > 0 && !d_outcomes))) return QMPC_BAD_ARGUMENT;
   if (kind == REC_PLAIN && !d_ctrl && !d_plant)
@@ -1817,14 +1841,14 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   // a ConvexMpc handle (opted in): one unit for the three kinds -- a call without windows passes none (per_robot = 0), a call
   // without outcome records the handle's scratch and parameters that never halt a robot
   const bool crec = convex_records(h);
-  const auto& R = kRec[crec ? REC_CONVEX : kind];
+  const auto& R = kRec[kind == REC_GROUND ? (crec ? REC_CGROUND : REC_GROUND) : crec ? REC_CONVEX : kind];
   qmpc_outcome_params op_none;
   std::memset(&op_none, 0, sizeof op_none);
   if (crec && kind == REC_PLAIN) {
     op = &op_none;
     d_outcomes = h->d_outcome;
   }
-  if (crec && kind != REC_PUSH) {
+  if ((crec && kind != REC_PUSH && kind != REC_GROUND) || !d_push) {
     d_push = nullptr;
     per_robot = 0;
   }
@@ -1838,10 +1862,11 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   else
     HIP_TRY(qmpc_loop_outcome_expand_base_launch(s, &h->dev, sizeof h->dev, bcast, plant_dev(h), (int)batch));
   if (d_push) HIP_TRY(qmpc_loop_push_check_launch(s, d_push, (int)per_robot, plant_dev(h), (int)batch));
+  if (kind == REC_GROUND) HIP_TRY(qmpc_ground_tu::rec_ground_check_launch(s, d_ground, plant_dev(h), (int)batch));
   if (lpp.fused) {
     HIP_TRY(R.fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, d_states, h->d_in, h->d_forces, h->d_info,
                            d_trace_forces, d_trace_contacts, (int)ticks, lpp.gws ? h->d_gws : nullptr, op, d_outcomes, d_push,
-                           (int)per_robot));
+                           (int)per_robot, d_ground, d_tally));
     return QMPC_OK;
   }
   auto one_tick = [&](bool first) -> qmpc_status {
@@ -1853,7 +1878,7 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
                                                 batch, h->d_in, h->d_forces, h->d_info, warm ? h->d_traj_u : nullptr, nullptr, s);
     if (st != QMPC_OK) return st;
     HIP_TRY(R.post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, h->d_loop_row, plant_dev(h),
-                          (int)batch, op, d_outcomes, d_push, (int)per_robot));
+                          (int)batch, op, d_outcomes, d_push, (int)per_robot, d_ground, d_tally));
     return QMPC_OK;
   };
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
@@ -1866,7 +1891,7 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
                                            int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                            double* d_trace_forces, double* d_trace_contacts, void* stream) {
   return loop_records_device(REC_PLAIN, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, nullptr, nullptr,
-                             nullptr, 0, stream);
+                             nullptr, 0, nullptr, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -1879,7 +1904,7 @@ qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, 
   HIP_TRY(hipSetDevice(h->device));
   const qmpc_status es = loop_instances_buffers(h, batch, ctrl != nullptr, lp->warm_start != 0.0, nullptr);
   if (es != QMPC_OK || ticks == 0) return es;
-  return loop_records_host(REC_PLAIN, h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, nullptr, nullptr, nullptr, 0);
+  return loop_records_host(REC_PLAIN, h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
 }
 
 // ---- the same closed loop with per-robot outcome records (qmpc_loop_outcome.hip) -------------------------------------------
@@ -1910,15 +1935,17 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
                                           double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                           qmpc_loop_outcome* d_outcomes, void* stream) {
   return loop_records_device(REC_OUTCOME, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
-                             nullptr, 0, stream);
+                             nullptr, 0, nullptr, nullptr, stream);
 }
 
 // the host-buffer call's checks and buffers (the staging itself: loop_records_host); push (qmpc_loop_run_pushes; NULL:
-// qmpc_loop_run_outcomes): per_robot windows per robot, staged in h->d_push
+// qmpc_loop_run_outcomes): per_robot windows per robot, staged in h->d_push; ground (qmpc_loop_run_ground, with or without push)
+// and tally (or NULL): staged in h->d_ground
 static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
                                       const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                       double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
-                                      const qmpc_push_params* push, int32_t per_robot) {
+                                      const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
+                                      qmpc_ground_tally* tally) {
   if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!states || !outcomes))) return QMPC_BAD_ARGUMENT;
   const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
@@ -1934,17 +1961,19 @@ static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp
   }
   // (the push call's ticks = 0 allocates everything a later push call needs, the records' staging included; the outcome call's
   // ticks = 0 stops before it, as it always did)
-  if (push && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
+  if ((push || ground) && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
+  if (ground && !h->d_ground)
+    HIP_TRY(hipMalloc(&h->d_ground, (sizeof(qmpc_ground_params) + sizeof(qmpc_ground_tally)) * (size_t)h->max_batch));
   if (ticks == 0) return es;
   if (!h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
-  return loop_records_host(push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes,
-                           push, per_robot);
+  return loop_records_host(ground ? REC_GROUND : push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant, trace_forces,
+                           trace_contacts, op, outcomes, push, per_robot, ground, tally);
 }
 
 qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
                                    const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                    double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes) {
-  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, nullptr, 0);
+  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, nullptr, 0, nullptr, nullptr);
 }
 
 // ---- the outcome loop under timed push windows per robot (qmpc_loop_push.hip) ------------------------------------------------
@@ -1961,7 +1990,7 @@ qmpc_status qmpc_loop_run_pushes_device(qmpc_handle* h, const qmpc_loop_params* 
                                          stream);
   if (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES) return QMPC_BAD_ARGUMENT;
   return loop_records_device(REC_PUSH, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             pushes_per_robot, stream);
+                             pushes_per_robot, nullptr, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_pushes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -1970,7 +1999,53 @@ qmpc_status qmpc_loop_run_pushes(qmpc_handle* h, const qmpc_loop_params* lp, int
                                  const qmpc_push_params* push, int32_t pushes_per_robot) {
   if (!push) return qmpc_loop_run_outcomes(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes);
   if (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES) return QMPC_BAD_ARGUMENT;
-  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot);
+  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot, nullptr,
+                            nullptr);
+}
+
+// ---- the push loop on the robot's true ground: friction and normal-force limits per leg (qmpc_loop_ground.hip, qmpc_loop_cground.hip) ----
+static_assert(sizeof(qmpc_ground_params) == 64 && sizeof(qmpc_ground_tally) == 32, "qmpc_ground_params is 8 doubles, qmpc_ground_tally 4");
+int32_t qmpc_sizeof_ground_params(void) { return (int32_t)sizeof(qmpc_ground_params); }
+int32_t qmpc_sizeof_ground_tally(void) { return (int32_t)sizeof(qmpc_ground_tally); }
+
+void qmpc_ground_params_init(qmpc_ground_params* g, int32_t batch) {
+  if (!g) return;
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int32_t i = 0; i < batch; ++i)
+    for (int l = 0; l < 4; ++l) g[i].mu[l] = g[i].fz_max[l] = inf;
+}
+
+void qmpc_ground_tally_init(qmpc_ground_tally* t, int32_t batch) {
+  if (!t) return;
+  for (int32_t i = 0; i < batch; ++i) {
+    t[i].clipped_ticks = t[i].friction_leg_ticks = t[i].normal_leg_ticks = 0.0;
+    t[i].first_clipped_tick = -1.0;
+  }
+}
+
+qmpc_status qmpc_loop_run_ground_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                        qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                        const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally, void* stream) {
+  if (!d_ground)
+    return qmpc_loop_run_pushes_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
+                                       pushes_per_robot, stream);
+  if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
+  return loop_records_device(REC_GROUND, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
+                             d_push ? pushes_per_robot : 0, d_ground, d_tally, stream);
+}
+
+qmpc_status qmpc_loop_run_ground(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                 const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                 double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
+                                 const qmpc_push_params* push, int32_t pushes_per_robot, const qmpc_ground_params* ground,
+                                 qmpc_ground_tally* tally) {
+  if (!ground)
+    return qmpc_loop_run_pushes(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot);
+  if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
+  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
+                            push ? pushes_per_robot : 0, ground, tally);
 }
 
 // Diagnostic: per-instance phase cycle counts (s_memtime) of one solve launch.

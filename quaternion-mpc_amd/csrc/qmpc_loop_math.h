@@ -226,6 +226,83 @@ QMPC_HD bool loop_push_valid(const qmpc_push_params& w) {
   return ok;
 }
 
+// What the TRUE ground under one stance foot delivers of a commanded world-frame force f (qmpc_loop_run_ground*, include/qmpc.h),
+// in this order: fz < 0 -> f = 0 (the ground does not pull); fz > fz_max -> fz = fz_max; t = |f_xy| > mu fz -> f_xy scaled by
+// (mu fz) / t.  Returns the verdict: LOOP_GROUND_NORMAL and / or LOOP_GROUND_FRICTION, 0 for a leg no rule changed -- whose
+// bytes are then untouched: no arithmetic reaches f, no `+ 0.0` (the rule of plant_rate_ext and loop_push_wrench).  A +inf
+// limit never binds (mu = +inf with fz = 0 compares against NaN: false).  mu = 0 leaves zeros of either sign in f_xy.
+enum { LOOP_GROUND_NORMAL = 1, LOOP_GROUND_FRICTION = 2 };
+QMPC_HD int loop_ground_leg(double mu, double fz_max, double* f) {
+  QMPC_NO_CONTRACT
+  int v = 0;
+  if (f[2] < 0.0) {
+    f[0] = 0.0; f[1] = 0.0; f[2] = 0.0;
+    v |= LOOP_GROUND_NORMAL;
+  }
+  if (f[2] > fz_max) {
+    f[2] = fz_max;
+    v |= LOOP_GROUND_NORMAL;
+  }
+  const double t = sqrt(f[0] * f[0] + f[1] * f[1]);
+  const double cap = mu * f[2];
+  if (t > cap) {
+    const double s = cap / t;
+    f[0] *= s; f[1] *= s;
+    v |= LOOP_GROUND_FRICTION;
+  }
+  return v;
+}
+
+// A ground record limits something when at least one of its eight fields is finite (x - x is 0 only for a finite x); the legs
+// of an all-+inf record are not looked at
+QMPC_HD bool loop_ground_active(const qmpc_ground_params& g) {
+  QMPC_NO_CONTRACT
+  bool any = false;
+  for (int l = 0; l < 4; ++l) any = any || (g.mu[l] - g.mu[l] == 0.0) || (g.fz_max[l] - g.fz_max[l] == 0.0);
+  return any;
+}
+
+// ... and is valid when no field is NaN, every mu >= 0 and every fz_max > 0 (+inf passes both); the robot of an invalid one is
+// frozen like that of an invalid plant record
+QMPC_HD bool loop_ground_valid(const qmpc_ground_params& g) {
+  bool ok = true;
+  for (int l = 0; l < 4; ++l) ok = ok && (g.mu[l] >= 0.0) && (g.fz_max[l] > 0.0);      // (a NaN fails either comparison)
+  return ok;
+}
+
+// The ground's part of one tick: grf (12, world frame, as the back end formed it) is clamped leg by leg where
+// contacts[l] != 0 (swing legs are not looked at), verdict[l] gets loop_ground_leg's word (0 for a swing leg).  Returns the OR
+// of the four.  An inactive record leaves everything alone.
+QMPC_HD int loop_ground_clamp(const qmpc_ground_params& g, const double* contacts, double* grf, int* verdict) {
+  int any = 0;
+  const bool active = loop_ground_active(g);
+  for (int l = 0; l < 4; ++l) {
+    verdict[l] = (active && contacts[l] != 0.0) ? loop_ground_leg(g.mu[l], g.fz_max[l], grf + 3 * l) : 0;
+    any |= verdict[l];
+  }
+  return any;
+}
+
+// The tally of a tick with these verdicts; tick_after is state.tick AFTER the tick
+QMPC_HD void loop_ground_tally_one(const int* verdict, double tick_after, qmpc_ground_tally& t) {
+  int any = 0;
+  for (int l = 0; l < 4; ++l) {
+    any |= verdict[l];
+    if (verdict[l] & LOOP_GROUND_FRICTION) t.friction_leg_ticks += 1.0;
+    if (verdict[l] & LOOP_GROUND_NORMAL) t.normal_leg_ticks += 1.0;
+  }
+  if (any) {
+    t.clipped_ticks += 1.0;
+    if (t.first_clipped_tick < 0.0) t.first_clipped_tick = tick_after;
+  }
+}
+
+// The delivered body-frame force of a clamped leg: R' f, in the expression shape of the ConvexMpc back end's R' u
+QMPC_HD void loop_ground_to_body(const double* R, const double* f, double* fb) {
+  QMPC_NO_CONTRACT
+  for (int r = 0; r < 3; ++r) fb[r] = R[r] * f[0] + R[3 + r] * f[1] + R[6 + r] * f[2];
+}
+
 // Condition matrix of the swing-foot quintic p(t) = sum_k a_k t^k (QuinticCurve::get_foot_swing_target,
 // Utils.cpp:236-293): rows p(0), p(T), p'(0), p'(T), p(T/2), p'(T/2).  Generated, with the reference's FLOAT
 // evaluation order so that every entry carries the same rounding as upstream's hand-written expressions: a power is

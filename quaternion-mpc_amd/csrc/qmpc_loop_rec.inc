@@ -1,8 +1,11 @@
 // qmpc_loop_rec.inc -- the kernels of the closed loop with per-robot records and their launchers, defined once.  Included by
-// qmpc_loop_inst.hip, qmpc_loop_outcome.hip and qmpc_loop_push.hip inside the unit's namespace, after qmpc_loop.hip, with
+// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip and qmpc_loop_ground.hip inside the unit's namespace, after
+// qmpc_loop.hip, with
 //   QMPC_REC_EXT 0   controller and plant records only                          (qmpc_loop_run_instances*)
 //                1   ... and the outcome step after the post step               (qmpc_loop_run_outcomes*)
 //                2   ... whose plant step integrates under timed push windows   (qmpc_loop_run_pushes*)
+//                3   ... under the force the robot's true ground delivers       (qmpc_loop_run_ground*; qmpc_loop_cground.hip: the
+//                    same with QMPC_REC_CONVEX, beside qmpc_loop_crec.hip, which stays at EXT 2)
 // and, for the sibling controller (qmpc_loop_crec.hip; a handle opts in with qmpc_set_convex_records),
 //   QMPC_REC_CONVEX  defined: ConvexMpc's problem -- ConvexModel and the wrench-form body with QMPC_WMODEL WM_CONVEX, the front
 //                    end loop_front_convex_one on qmpc_convex_input records, the world-frame back end with the robot's plant
@@ -20,11 +23,20 @@
 #ifdef QMPC_REC_CONVEX
 #define QMPC_REC_MODEL ConvexModel
 #define QMPC_REC_FRONT(OCC_, LP_, s_, r_) loop_front_convex_one<OCC_>(LP_, s_, reinterpret_cast<qmpc_convex_input&>(r_))
-#define QMPC_REC_POST loop_post_plant_world_one
 #else
 #define QMPC_REC_MODEL QuatModel
 #define QMPC_REC_FRONT(OCC_, LP_, s_, r_) loop_front_one<OCC_>(LP_, s_, r_)
+#endif
+// the post step and, at EXT 3, the two arguments it has beyond the plant block: robot i_'s ground record and tally
+#if QMPC_REC_EXT >= 3
+#define QMPC_REC_POST loop_post_ground_one
+#define QMPC_REC_POST_GROUND(i_) , ground + (size_t)(i_), tally ? tally + (size_t)(i_) : nullptr
+#elif defined(QMPC_REC_CONVEX)
+#define QMPC_REC_POST loop_post_plant_world_one
+#define QMPC_REC_POST_GROUND(i_)
+#else
 #define QMPC_REC_POST loop_post_plant_one
+#define QMPC_REC_POST_GROUND(i_)
 #endif
 #if QMPC_REC_EXT >= 1
 #define QMPC_REC_OUTCOME(...) __VA_ARGS__
@@ -35,6 +47,11 @@
 #define QMPC_REC_PUSH(...) __VA_ARGS__
 #else
 #define QMPC_REC_PUSH(...)
+#endif
+#if QMPC_REC_EXT >= 3
+#define QMPC_REC_GROUND(...) __VA_ARGS__
+#else
+#define QMPC_REC_GROUND(...)
 #endif
 
 // the trace row of a robot that does not move in this tick
@@ -66,7 +83,82 @@ __device__ inline PlantDev push_plant(const PlantDev& pl, const qmpc_push_params
 }
 #endif
 
+#if QMPC_REC_EXT >= 3
+// The back end of a tick on the robot's TRUE ground (qmpc_loop_run_ground*): loop_post_plant_one (QMPC_REC_CONVEX:
+// loop_post_plant_world_one) whose plant step takes the DELIVERED forces.  After grf_world has been formed as there, the stance
+// legs are clamped in the world frame (qmpc_loop::loop_ground_clamp); a changed leg hands the plant R' f, an unchanged one the
+// commanded forces_body bytes, so a record that changes no leg gives that function's state, bit for bit.  grf_world holds the
+// delivered force, forces_body and the trace row the command.  g and tally point into global memory: the record is read and the
+// tally read-modify-written here, inside the post step -- nothing of either is live across the solve, and no block is copied.
+// ConvexMpc, solve rejected: grf_world still holds the last accepted tick's entry, so the clamp runs on R forces_body, the
+// command the plant keeps applying; only a leg it changes is written.
+template <int OCC = 1>
+QMPC_LOOP_FN void loop_post_ground_one(const PlantDev& pl, const qmpc_loop_params& LP, qmpc_loop_state& s,
+                                       const double* __restrict__ forces, const qmpc_info& inf, double* __restrict__ trace_f,
+                                       double* __restrict__ trace_c, const qmpc_ground_params* __restrict__ g,
+                                       qmpc_ground_tally* __restrict__ tally) {
+#pragma clang fp contract(off)
+  const int status = inf.status;
+  s.status = (double)status;
+  s.iterations = (double)inf.iterations;
+  const bool accepted = status == QMPC_OK || status == QMPC_MAX_ITER;     // (the converged mode only)
+  double R[9];
+  qmpc_loop::quat_to_rot(s.quat, R);
+  int verdict[4];
+  int any;
 #ifdef QMPC_REC_CONVEX
+  if (accepted) {
+    for (int l = 0; l < 4; ++l)
+      for (int r = 0; r < 3; ++r) {
+        s.grf_world[3 * l + r] = forces[3 * l + r];
+        s.forces_body[3 * l + r] = R[r] * forces[3 * l] + R[3 + r] * forces[3 * l + 1] + R[6 + r] * forces[3 * l + 2];
+      }
+    any = qmpc_loop::loop_ground_clamp(*g, s.contacts, s.grf_world, verdict);
+  } else {
+    double fw[12];
+    for (int l = 0; l < 4; ++l)
+      for (int r = 0; r < 3; ++r)
+        fw[3 * l + r] = R[3 * r] * s.forces_body[3 * l] + R[3 * r + 1] * s.forces_body[3 * l + 1] + R[3 * r + 2] * s.forces_body[3 * l + 2];
+    any = qmpc_loop::loop_ground_clamp(*g, s.contacts, fw, verdict);
+    for (int l = 0; l < 4; ++l)
+      if (verdict[l])
+        for (int r = 0; r < 3; ++r) s.grf_world[3 * l + r] = fw[3 * l + r];
+  }
+#else
+  if (accepted)
+    for (int a = 0; a < 12; ++a) s.forces_body[a] = forces[a];
+  for (int l = 0; l < 4; ++l)
+    for (int r = 0; r < 3; ++r)
+      s.grf_world[3 * l + r] = R[3 * r] * s.forces_body[3 * l] + R[3 * r + 1] * s.forces_body[3 * l + 1] +
+                               R[3 * r + 2] * s.forces_body[3 * l + 2];
+  any = qmpc_loop::loop_ground_clamp(*g, s.contacts, s.grf_world, verdict);
+#endif
+  if (trace_f) for (int a = 0; a < 12; ++a) trace_f[a] = s.forces_body[a];
+  if (trace_c) for (int a = 0; a < 4; ++a) trace_c[a] = s.contacts[a];
+  double u[12];      // what the plant receives
+  for (int l = 0; l < 4; ++l) {
+    if (verdict[l]) qmpc_loop::loop_ground_to_body(R, s.grf_world + 3 * l, u + 3 * l);
+    else
+      for (int r = 0; r < 3; ++r) u[3 * l + r] = s.forces_body[3 * l + r];
+  }
+  double x[13];
+  for (int a = 0; a < 3; ++a) { x[a] = s.pos_world[a]; x[7 + a] = s.lin_vel_world[a]; x[10 + a] = s.ang_vel_body[a]; }
+  for (int a = 0; a < 4; ++a) x[3 + a] = s.quat[a];
+  qmpc_loop::plant_step_ext(x, u, s.foot_pos_world, 4, pl.mass, pl.Iinv, pl.force, pl.torque, LP.dt);
+  for (int a = 0; a < 3; ++a) { s.pos_world[a] = x[a]; s.lin_vel_world[a] = x[7 + a]; s.ang_vel_body[a] = x[10 + a]; }
+  for (int a = 0; a < 4; ++a) s.quat[a] = x[3 + a];
+  if (s.movement_mode != 0.0)
+    for (int l = 0; l < 4; ++l)
+      if (s.contacts[l] == 0.0)
+        for (int a = 0; a < 3; ++a) s.foot_pos_world[3 * l + a] = s.leg[l].fsm_pos[a];
+  s.tick += 1.0;
+  if (tally && any) {
+    qmpc_ground_tally t = *tally;
+    qmpc_loop::loop_ground_tally_one(verdict, s.tick, t);
+    *tally = t;
+  }
+}
+#elif defined(QMPC_REC_CONVEX)
 // The back end of ConvexMpc's tick with the robot's own TRUE plant: loop_post_one<true> (qmpc_loop.hip: the solve returns
 // WORLD-frame forces, optimized_input = R' u; converged mode) with pl's mass, inverse inertia and disturbance wrench in the plant
 // step, as loop_post_plant_one is loop_post_one<false> with them.  plant_step_ext with the handle's mass and inertia and a zero
@@ -126,7 +218,8 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
     qmpc_loop_params LP, QMPC_REC_OUTCOME(qmpc_outcome_params OP, ) qmpc_loop_state* __restrict__ st,
     const double* __restrict__ forces, const qmpc_info* __restrict__ info, double* __restrict__ trace_f, double* __restrict__ trace_c,
     const int* __restrict__ row, const PlantDev* __restrict__ pl, QMPC_REC_OUTCOME(qmpc_loop_outcome* __restrict__ oc, )
-    QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, ) int batch) {
+    QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, )
+    QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, ) int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
   const size_t slot = (trace_f || trace_c) ? (size_t)(*row) * batch + i : 0;
@@ -145,7 +238,7 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
 #endif
 #if QMPC_REC_EXT >= 2
   const PlantDev p = push_plant(pl[i], push + (size_t)i * per_robot, per_robot, st[i].tick);
-  QMPC_REC_POST(p, LP, st[i], forces + 12 * (size_t)i, info[i], tf, tc);
+  QMPC_REC_POST(p, LP, st[i], forces + 12 * (size_t)i, info[i], tf, tc QMPC_REC_POST_GROUND(i));
 #else
   QMPC_REC_POST(pl[i], LP, st[i], forces + 12 * (size_t)i, info[i], tf, tc);
 #endif
@@ -166,13 +259,17 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
 // one, its state untouched.
 // EXT 2: lane 0 reads the robot's windows from global memory inside the post step of each tick: nothing of the push is live
 // across the solve (variants 5 / 6 sit at their 256-register limit).
+// EXT 3: lane 0's post step also reads the robot's 64 B ground record and read-modify-writes its 32 B tally, by pointer, in each
+// tick -- the same rule: nothing live across the solve, no block copied.
 // (The two zero-fill loops stay written out: as calls of one inline function they compile to other instructions.)
 template <int VAR>
 __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmpc_loop_rec_fused_kernel(
     const DevParams* __restrict__ Pi, const PlantDev* __restrict__ plants, qmpc_loop_params LP, QMPC_REC_OUTCOME(qmpc_outcome_params OP, )
     qmpc_loop_state* __restrict__ st, qmpc_input* __restrict__ rec, double* __restrict__ forces, qmpc_info* __restrict__ info,
     double* __restrict__ trace_f, double* __restrict__ trace_c, QMPC_REC_OUTCOME(qmpc_loop_outcome* __restrict__ outcomes, )
-    QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, ) int ticks, int batch, double* __restrict__ gws) {
+    QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, )
+    QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, ) int ticks, int batch,
+    double* __restrict__ gws) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int b = blockIdx.x;
   if (b >= batch) return;
@@ -228,7 +325,7 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
 #if QMPC_REC_EXT >= 2
       const PlantDev p = push_plant(plants[b], push + (size_t)b * per_robot, per_robot, st[b].tick);
       QMPC_REC_POST<OCC>(p, LP, st[b], forces + 12 * (size_t)b, info[b], trace_f ? trace_f + 12 * slot : nullptr,
-                               trace_c ? trace_c + 4 * slot : nullptr);
+                               trace_c ? trace_c + 4 * slot : nullptr QMPC_REC_POST_GROUND(b));
 #else
       QMPC_REC_POST<OCC>(plants[b], LP, st[b], forces + 12 * (size_t)b, info[b], trace_f ? trace_f + 12 * slot : nullptr,
                                trace_c ? trace_c + 4 * slot : nullptr);
@@ -255,6 +352,24 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
 #endif
 }
 
+#if QMPC_REC_EXT >= 3 && !defined(QMPC_REC_CONVEX)
+// ---- the check of the ground records (QuatMpc's unit only: it does not depend on the model) -------------------------------
+// One thread per robot: the verdict of the robot's ground record into its plant block (a verdict already there stays)
+__global__ __launch_bounds__(256) void qmpc_ground_check_kernel(const qmpc_ground_params* __restrict__ ground, PlantDev* __restrict__ pl,
+                                                                int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  if (!qmpc_loop::loop_ground_valid(ground[i])) pl[i].status = QMPC_BAD_PARAMS;
+}
+
+__attribute__((visibility("hidden"))) hipError_t rec_ground_check_launch(hipStream_t s, const qmpc_ground_params* ground, void* plants,
+                                                                         int batch) {
+  hipLaunchKernelGGL(qmpc_ground_check_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, ground,
+                     static_cast<PlantDev*>(plants), batch);
+  return hipGetLastError();
+}
+#endif
+
 // ---- launchers (host; called from qmpc_hip.hip; hidden: not part of the C ABI) ------------------------------------------------
 // the launch table of this unit: the persistent kernels by wrench-form variant 3 / 5 / 6 (qmpc_kernel_slots.h: wform_index)
 static decltype(&qmpc_loop_rec_fused_kernel<3>) const kRecFused[] = {qmpc_loop_rec_fused_kernel<3>, qmpc_loop_rec_fused_kernel<5>, qmpc_loop_rec_fused_kernel<6>};
@@ -266,12 +381,13 @@ __attribute__((visibility("hidden"))) hipError_t rec_set_lds() { return set_max_
 __attribute__((visibility("hidden"))) hipError_t rec_fused_launch(
     int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants, const qmpc_loop_params* lp,
     qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws,
-    const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot) {
+    const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,
+    const qmpc_ground_params* ground, qmpc_ground_tally* tally) {
   const int k = qmpc::wform_index(var);
   if (k < 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kRecFused[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks),
                      static_cast<const PlantDev*>(plants), *lp, QMPC_REC_OUTCOME(*op, ) st, rec, forces, info, trace_f, trace_c,
-                     QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_PUSH(push, per_robot, ) ticks, batch, gws);
+                     QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, ) ticks, batch, gws);
   return hipGetLastError();
 }
 
@@ -289,15 +405,18 @@ __attribute__((visibility("hidden"))) hipError_t rec_post_launch(hipStream_t s, 
                                                                  const double* forces, const qmpc_info* info, double* trace_f,
                                                                  double* trace_c, const int* row, const void* plants, int batch,
                                                                  const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
-                                                                 const qmpc_push_params* push, int per_robot) {
+                                                                 const qmpc_push_params* push, int per_robot,
+                                                                 const qmpc_ground_params* ground, qmpc_ground_tally* tally) {
   hipLaunchKernelGGL(qmpc_loop_rec_post_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, *lp, QMPC_REC_OUTCOME(*op, ) st, forces, info,
                      trace_f, trace_c, row, static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, )
-                     QMPC_REC_PUSH(push, per_robot, ) batch);
+                     QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, ) batch);
   return hipGetLastError();
 }
 
 #undef QMPC_REC_OUTCOME
 #undef QMPC_REC_PUSH
+#undef QMPC_REC_GROUND
+#undef QMPC_REC_POST_GROUND
 #undef QMPC_REC_EXT
 #undef QMPC_REC_MODEL
 #undef QMPC_REC_FRONT

@@ -36,6 +36,10 @@ class ClosedLoopHostBase {
   virtual const qmpc_loop_outcome& outcome() const = 0;
   // the robot's push windows (qmpc_loop_run_pushes*): n <= QMPC_MAX_PUSHES records, copied; n = 0 or null: none
   virtual void set_pushes(const qmpc_push_params* push, int n) = 0;
+  // the robot's TRUE ground (qmpc_loop_run_ground*): one record, copied (null: none -- the plant delivers every command), and the
+  // tally its ticks accumulate into (starts empty; set_ground leaves it)
+  virtual void set_ground(const qmpc_ground_params* ground) = 0;
+  virtual const qmpc_ground_tally& ground_tally() const = 0;
   State state;
 };
 
@@ -97,6 +101,11 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     n_push_ = (push && n > 0) ? (n < QMPC_MAX_PUSHES ? n : QMPC_MAX_PUSHES) : 0;
     for (int k = 0; k < n_push_; ++k) push_[k] = push[k];
   }
+  void set_ground(const qmpc_ground_params* ground) override {
+    has_ground_ = ground != nullptr;
+    if (ground) ground_ = *ground;
+  }
+  const qmpc_ground_tally& ground_tally() const override { return tally_; }
   void reset_outcome() {                                    // qmpc_loop_outcome_init
     std::memset(&outcome_, 0, sizeof outcome_);
     outcome_.down_tick = outcome_.first_rejected_tick = -1.0;
@@ -146,7 +155,22 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     const bool ok = mpc->grf_update(state);
     double u[12];
     for (int a = 0; a < 12; ++a) u[a] = state.ctrl.optimized_input[a];
-    if (n_push_ > 0) {   // the device's push tick: the plant's constant wrench (none without a plant record, on the handle's mass and
+    int verdict[4] = {0, 0, 0, 0};
+    if (has_ground_) {   // the device's ground tick (qmpc_loop_math.h: loop_ground_clamp): the stance legs' world-frame forces are
+                         // clamped, a changed leg hands the plant R' f and mpc_grf_world the delivered force; optimized_input stays
+                         // the command
+      double R[9], grf[12], con[4];
+      qmpc_loop::quat_to_rot(&x_[3], R);
+      for (int a = 0; a < 12; ++a) grf[a] = state.ctrl.mpc_grf_world[a];
+      for (int l = 0; l < NUM_LEG; ++l) con[l] = state.ctrl.plan_contacts[l] ? 1.0 : 0.0;
+      qmpc_loop::loop_ground_clamp(ground_, con, grf, verdict);
+      for (int l = 0; l < NUM_LEG; ++l)
+        if (verdict[l]) {
+          qmpc_loop::loop_ground_to_body(R, grf + 3 * l, u + 3 * l);
+          for (int a = 0; a < 3; ++a) state.ctrl.mpc_grf_world[3 * l + a] = grf[3 * l + a];
+        }
+    }
+    if (n_push_ > 0 || has_ground_) {   // the device's push tick: the plant's constant wrench (none without a plant record, on the handle's mass and
                          // inverse inertia then) under the windows acting at state.tick = ticks_ (qmpc_loop_math.h: loop_push_wrench)
       double f[3] = {0.0, 0.0, 0.0}, tq[3] = {0.0, 0.0, 0.0};
       if (has_plant_)
@@ -162,6 +186,7 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
         if (!state.ctrl.plan_contacts[l])
           for (int a = 0; a < 3; ++a) feet_[3 * l + a] = mpc->leg_FSM[l].FSM_foot_pos_target_world[a];
     ticks_ += 1;
+    if (verdict[0] | verdict[1] | verdict[2] | verdict[3]) qmpc_loop::loop_ground_tally_one(verdict, (double)ticks_, tally_);
     {   // the outcome step of the device tick, on the same record layout: the arithmetic is the device's (qmpc_loop_math.h).
         // The host robot goes on ticking when it is down (stop_when_down is the device loop's); its record is frozen then.
       qmpc_loop_state after;
@@ -296,6 +321,9 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   qmpc_loop_outcome outcome_;
   qmpc_push_params push_[QMPC_MAX_PUSHES];
   int n_push_ = 0;
+  qmpc_ground_params ground_;
+  bool has_ground_ = false;
+  qmpc_ground_tally tally_ = {0.0, -1.0, 0.0, 0.0};      // qmpc_ground_tally_init
   long ticks_ = 0;
 };
 

@@ -266,6 +266,9 @@ void qh_loop_outcome(void* p, qmpc_loop_outcome* out) { *out = static_cast<LoopH
 void qh_loop_set_outcome_params(void* p, const qmpc_outcome_params* op) { static_cast<LoopHarness*>(p)->loop->set_outcome_params(*op); }
 // the robot's push windows (qmpc_push_params[n], n <= QMPC_MAX_PUSHES; n = 0: none) for the ticks to come
 void qh_loop_set_pushes(void* p, const qmpc_push_params* push, int n) { static_cast<LoopHarness*>(p)->loop->set_pushes(push, n); }
+// ... and its true ground (qmpc_loop_run_ground*; null: none) with the tally its ticks accumulate
+void qh_loop_set_ground(void* p, const qmpc_ground_params* ground) { static_cast<LoopHarness*>(p)->loop->set_ground(ground); }
+void qh_loop_ground_tally(void* p, qmpc_ground_tally* out) { *out = static_cast<LoopHarness*>(p)->loop->ground_tally(); }
 void qh_loop_destroy(void* p) {
   LoopHarness* h = static_cast<LoopHarness*>(p);
   if (!h) return;

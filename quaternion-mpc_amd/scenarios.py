@@ -317,3 +317,19 @@ def random_go1_pushes(batch: int, seed: int = 0, first: int = 0, per_robot: int 
     rec["force_world"][:, :, 0] = mag * np.cos(ang)
     rec["force_world"][:, :, 1] = mag * np.sin(ang)
     return rec
+
+
+def random_go1_grounds(batch: int, seed: int = 0, first: int = 0, mu=(0.1, 0.9), fz_max=None) -> np.ndarray:
+    """`batch` ground records (``struct qmpc_ground_params``, for Solver.loop_run_ground), robot indices first .. first+batch-1,
+    the counter-based generator of random_go1_pushes (a shard equals its block of the whole): one true friction coefficient
+    U(mu) per robot, copied to its four legs, and -- with fz_max = (lo, hi) -- one normal-force limit U(fz_max) N per robot,
+    copied likewise (None: +inf, no limit).  Two uniforms per robot, in the order mu, fz_max."""
+    from . import ground_params
+
+    rec = ground_params(batch)
+    idx = np.arange(first, first + batch, dtype=np.uint64)
+    u = _uniform(0x5EED4000 + int(seed), idx, 2)
+    rec["mu"] = (mu[0] + (mu[1] - mu[0]) * u[:, 0])[:, None]
+    if fz_max is not None:
+        rec["fz_max"] = (fz_max[0] + (fz_max[1] - fz_max[0]) * u[:, 1])[:, None]
+    return rec

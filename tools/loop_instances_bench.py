@@ -18,6 +18,11 @@ per-robot calls include their expansion kernels.
 --pushes [--per-robot K]: instead, same-job pairs of qmpc_loop_run_outcomes_device against qmpc_loop_run_pushes_device whose K
     windows per robot never act (they lie beyond the run, with a wrench that is not zero): what reading the windows in every tick
     costs, with plant records and with controller + plant records, on the walking fleet.  The two calls compute the same bytes.
+--ground: instead, same-job pairs of qmpc_loop_run_pushes_device (one idle window per robot) against qmpc_loop_run_ground_device on the
+    same windows, first with ground records that never bind (mu = 10, fz_max = 1e4: what reading the record and clamping in
+    every tick costs; the same bytes up to the robots a zero-force leg binds on, counted in the row) and then with
+    mu_true = 0.5 mu_ctrl on every robot (the clamp binds: the robots compute something else), with plant records and with
+    controller + plant records, on the walking fleet.  Median, minimum and maximum of the repetitions beside each ratio.
 --records uniform|random: every robot carries the handle's values (default), or random_go1_variants / random_go1_plants.
 --warm-records [--mu0 1e-6]: instead, the warm-started loop with controller + plant records (qmpc_set_loop_warm_records) as same-job
     pairs: the plain loop and the call with records, each cold-started (a handle on the default barrier parameter) and
@@ -176,6 +181,88 @@ def pushes(pkg, lib, torch, N, B, a):
     return row
 
 
+def ground(pkg, lib, torch, N, B, a):
+    """the push call against the ground call, with records that never bind and with binding ones (see the module docstring)"""
+    p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+    lp = pkg.default_loop_params(lib)
+    T = a.ticks
+    rng = np.random.default_rng(5)
+    cmds = np.zeros((B, 7))
+    cmds[:, 0] = rng.uniform(-0.4, 0.4, B); cmds[:, 1] = rng.uniform(-0.15, 0.15, B)
+    cmds[:, 2] = rng.uniform(0.26, 0.32, B); cmds[:, 5] = rng.uniform(-0.4, 0.4, B)
+    cmds[:, 6] = (rng.random(B) < 0.85).astype(float)
+    stand = cmds.copy(); stand[:, 6] = 0.0
+    st = pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, B), lib=lib)
+    s = pkg.Solver(p, B, device=0, lib=lib)
+    s.set_instances_policy(a.policy if a.policy != "both" else "wave")
+    s.prepare(B)
+    s.prepare_instances()
+    st = s.loop_run(st, 6, lp)
+    st["movement_mode"] = cmds[:, 6]
+    if a.records == "random":
+        ctrl = pkg.random_go1_variants(B, seed=12, base=p)
+        ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
+        plant = pkg.random_go1_plants(B, seed=11, base=p, payload=(-1.0, 3.0), force=(0.0, 10.0))
+    else:
+        ctrl, plant = pkg.instance_params(p, B), pkg.plant_params(p, B)
+    push = pkg.random_go1_pushes(B, seed=13, per_robot=1, impulse=(1.0, 5.0), dt=lp.dt)
+    push["start_tick"] += 1e9      # beyond any run
+    loose, tight = pkg.ground_params(B), pkg.ground_params(B)
+    loose["mu"], loose["fz_max"] = 10.0, 1e4
+    tight["mu"] = 0.5 * ctrl["mu"][:, None]
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).cuda()      # noqa: E731
+    d_st0, d_oc0, d_ta0, d_ctrl, d_plant, d_push = dev(st), dev(pkg.loop_outcomes(B, lib)), dev(pkg.ground_tallies(B)), dev(ctrl), dev(plant), dev(push)
+    d_loose, d_tight = dev(loose), dev(tight)
+    d_st, d_oc, d_ta = d_st0.clone(), d_oc0.clone(), d_ta0.clone()
+    op = pkg.default_outcome_params(lib)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    torch.cuda.synchronize()
+    calls = {}
+    for name, c in (("plant", 0), ("ctrl_plant", d_ctrl.data_ptr())):
+        calls[name + "_pushes"] = lambda c=c: s.loop_run_pushes_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), d_push.data_ptr(), 1, lp, op,
+                                                                      d_ctrl=c, d_plant=d_plant.data_ptr(), stream=sp)
+        for kind, d_g in (("loose", d_loose), ("tight", d_tight)):
+            calls[name + "_" + kind] = lambda c=c, d_g=d_g: s.loop_run_ground_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), d_g.data_ptr(), d_ta.data_ptr(),
+                                                                                     d_push.data_ptr(), 1, lp, op, d_ctrl=c, d_plant=d_plant.data_ptr(),
+                                                                                     stream=sp)
+    times, bits, tallies = {k: [] for k in calls}, {}, {}
+    for r in range(a.warmup + a.reps):
+        for k, fn in calls.items():
+            with torch.cuda.stream(stream):
+                d_st.copy_(d_st0)
+                d_oc.copy_(d_oc0)
+                d_ta.copy_(d_ta0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            if r >= a.warmup:
+                times[k].append(e0.elapsed_time(e1))
+            bits[k] = (d_st.cpu().numpy().view(pkg.LOOP_STATE_DTYPE), d_oc.cpu().numpy().view(pkg.LOOP_OUTCOME_DTYPE))
+            tallies[k] = d_ta.cpu().numpy().view(pkg.GROUND_TALLY_DTYPE).reshape(B)
+    forms = {"plant": s.loop_instances_plan(B, False, False), "ctrl_plant": s.loop_instances_plan(B, True, False)}
+    s.close()
+    ms = {k: float(np.median(v)) for k, v in times.items()}
+    row = {"N": N, "B": B, "ticks": T, "records": a.records}
+    for k in ("plant", "ctrl_plant"):
+        q = k + "_pushes"
+        row.update({q + "_ms": ms[q], k + "_form": forms[k], q + "_spread": (max(times[q]) - min(times[q])) / ms[q]})
+        print(f"N={N:2d} B={B:6d} {k:10s} {forms[k]}: push call {ms[q]:9.3f} ms (min {min(times[q]):.3f}, max {max(times[q]):.3f})", flush=True)
+        for kind, what in (("loose", "mu = 10, fz_max = 1e4"), ("tight", "mu_true = 0.5 mu_ctrl")):
+            g = k + "_" + kind
+            ta = tallies[g]
+            quiet = ta["clipped_ticks"] == 0
+            same = all(x.reshape(B)[quiet].tobytes() == y.reshape(B)[quiet].tobytes() for x, y in zip(bits[g], bits[q]))
+            row.update({g + "_ms": ms[g], g + "_ratio": ms[g] / ms[q], g + "_spread": (max(times[g]) - min(times[g])) / ms[g],
+                        g + "_robots_clipped": int((~quiet).sum()), g + "_unclipped_same_bytes": same})
+            print(f"    ground call, {what:22s} {ms[g]:9.3f} ms (min {min(times[g]):.3f}, max {max(times[g]):.3f})   ground / push {row[g + '_ratio']:.4f}   "
+                  f"robots clipped {int((~quiet).sum())} (clipped ticks {int(ta['clipped_ticks'].sum())}, friction leg-ticks {int(ta['friction_leg_ticks'].sum())}, "
+                  f"normal {int(ta['normal_leg_ticks'].sum())}); robots never clipped have the push call's bytes: {same}", flush=True)
+    return row
+
+
 def warm_records(pkg, lib, torch, N, B, a):
     """cold against warm, the plain loop and the call with controller + plant records (see the module docstring)"""
     lp_c = pkg.default_loop_params(lib)
@@ -293,6 +380,7 @@ def main():
     ap.add_argument("--stop", action="store_true")
     ap.add_argument("--pushes", action="store_true")
     ap.add_argument("--per-robot", type=int, default=1)
+    ap.add_argument("--ground", action="store_true")
     ap.add_argument("--policy", choices=("wave", "auto", "both"), default="wave")
     ap.add_argument("--records", choices=("uniform", "random"), default="uniform")
     ap.add_argument("--warm-records", action="store_true")
@@ -307,13 +395,16 @@ def main():
     if a.stop and not a.outcomes:
         ap.error("--stop goes with --outcomes")
     convex = a.model == "convex"
-    if convex and (a.pushes or a.stop):
+    if convex and (a.pushes or a.stop or a.ground):
         ap.error("--model convex goes with the default comparison, --outcomes and --warm-records")
     for item in a.sizes.split(","):
         N, B = (int(x) for x in item.split(":"))
         policies = ("wave", "auto") if a.policy == "both" else (a.policy,)
         if a.pushes:
             rows.append(pushes(pkg, lib, torch, N, B, a))
+            continue
+        if a.ground:
+            rows.append(ground(pkg, lib, torch, N, B, a))
             continue
         if a.warm_records:
             rows.append(warm_records(pkg, lib, torch, N, B, a))

@@ -5,6 +5,7 @@ still up per cell from the outcome records.  The robots of a cell differ in thei
 inertia); the controller is the handle's and is not told about the push.
     python tools/push_recovery.py [--impulses 2,4,6,8,10] [--starts 13] [--length 10] [--per-cell 8] [--speed 0.3] [--settle 60]
                                   [--recover 200] [--horizon 10] [--controller quat|convex|both] [--ctrl-records] [--warm] [--json FILE]
+                                  [--mu-true LO HI [--mu-steps 5]]
 Every robot stands for 6 ticks, trots at --speed for --settle ticks, is shoved at tick 6 + settle + start for --length ticks with
 force impulse / (length dt) in its cell's direction (0 degrees: ahead, 90: to its left), and trots on until --recover ticks after
 the last start.  Down: below 0.15 m or tilted beyond 60 degrees (qmpc_default_outcome_params); stop_when_down halts a fallen robot.
@@ -12,6 +13,9 @@ Prints one table per impulse (rows: start tick in the gait period, columns: dire
 the run gives.
 --controller: QuatMpc (default), ConvexMpc (a handle that opted in with qmpc_set_convex_records), or both -- the same pushes,
 plants and commands under each controller, one summary per controller.  --horizon is then each controller's horizon.
+--mu-true LO HI: the true-friction axis.  The grid is repeated on --mu-steps grounds whose Coulomb coefficient runs from LO to HI
+(qmpc_loop_run_ground: the plant delivers what that ground allows, the controller keeps assuming its own mu), and a table of falls
+per (impulse, mu_true) cell with the ground tallies is printed after the tables above, which then pool the grounds.
 --ctrl-records: every robot also carries a controller record (the handle's values: the same controller) and the handle takes
 QMPC_INSTANCES_AUTO, a ConvexMpc handle with qmpc_set_convex_lane_records as well -- the launch a sweep over per-robot controllers
 takes: from the switch-over on the lane kernel with per-lane parameters under either controller.
@@ -53,6 +57,8 @@ def main():
     ap.add_argument("--controller", choices=("quat", "convex", "both"), default="quat")
     ap.add_argument("--ctrl-records", action="store_true")
     ap.add_argument("--warm", action="store_true")
+    ap.add_argument("--mu-true", type=float, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--mu-steps", type=int, default=5)
     a = ap.parse_args()
     pkg = load_pkg()
     lib = pkg.load_library()
@@ -67,8 +73,9 @@ def run(a, pkg, lib, controller):
     starts = [int(round(k * PERIOD / a.starts)) for k in range(a.starts)]
     angles = np.arange(8) * (np.pi / 4)
     # the grid, robot index = ((impulse, start, direction), member of the cell)
-    gi, gs, gd, _ = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8), np.arange(a.per_cell),
-                                                    indexing="ij"))
+    mus = np.linspace(a.mu_true[0], a.mu_true[1], a.mu_steps) if a.mu_true else np.array([np.inf])
+    gi, gs, gd, gm, _ = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8), np.arange(len(mus)),
+                                                        np.arange(a.per_cell), indexing="ij"))
     B = gi.size
     convex = controller == "convex"
     p = (pkg.default_convex_params if convex else pkg.default_params)(a.horizon, pkg.MODE_CONVERGED, lib)
@@ -80,6 +87,10 @@ def run(a, pkg, lib, controller):
     cmd = [a.speed, 0.0, 0.30, 0.0, 0.0, 0.0, 0.0]
     st = pkg.loop_states([cmd] * B, lp, height=0.3, yaw=0.0, lib=lib)
     # (the same plants under either controller: around QuatMpc's Go1, whose mass is ConvexMpc's too)
+    ground = None
+    if a.mu_true:
+        ground = pkg.ground_params(B)
+        ground["mu"] = mus[gm][:, None]
     plant = pkg.random_go1_plants(B, seed=21, base=pkg.default_params(a.horizon, pkg.MODE_CONVERGED, lib), payload=(0.0, 3.0))
     push = pkg.push_params(B)
     t0 = 6 + a.settle
@@ -103,15 +114,15 @@ def run(a, pkg, lib, controller):
     form = s.loop_instances_plan(B, ctrl is not None, a.warm)
     total = a.settle + PERIOD + a.recover
     w0 = time.perf_counter()
-    st, oc = s.loop_run_pushes(st, 6, push, lp, ctrl=ctrl, plant=plant, op=op)
+    st, oc, ta = s.loop_run_ground(st, 6, ground, push, lp, ctrl=ctrl, plant=plant, op=op)      # (ground = None: the push call)
     st["movement_mode"] = 1.0
-    st, oc = s.loop_run_pushes(st, total, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc)
+    st, oc, ta = s.loop_run_ground(st, total, ground, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc, tallies=ta)
     wall = time.perf_counter() - w0
     s.close()
-    up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, a.per_cell)
+    up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, len(mus) * a.per_cell)
     share = up.mean(axis=3)
     fell_before = int(((oc["down_tick"] >= 0) & (oc["down_tick"] <= push["start_tick"][:, 0])).sum())
-    print(f"push recovery under {'ConvexMpc' if convex else 'QuatMpc'}: {B} robots ({len(impulses)} impulses x {len(starts)} start ticks x 8 directions x {a.per_cell} plants), N={a.horizon}, "
+    print(f"push recovery under {'ConvexMpc' if convex else 'QuatMpc'}: {B} robots ({len(impulses)} impulses x {len(starts)} start ticks x 8 directions x {len(mus) * a.per_cell} plants), N={a.horizon}, "
           f"trot at {a.speed} m/s, shove of {a.length:g} ticks from tick {t0} + start, {6 + total} ticks in all, launch {form}, "
           f"{wall:.2f} s wall with the copies; {fell_before} robots were down before their shove began")
     print(f"solves: {pkg.summarize_outcomes(oc)['mean_iterations']:.2f} iterations on average, "
@@ -125,8 +136,25 @@ def run(a, pkg, lib, controller):
         print("  all " + " ".join(f"{share[i, :, d].mean():5.2f}" for d in range(8)) + f"  {share[i].mean():5.2f}")
     print(f"\nsummary, {'ConvexMpc' if convex else 'QuatMpc'}: share still up by impulse " +
           "  ".join(f"{imp:g} N s: {share[i].mean():.3f}" for i, imp in enumerate(impulses)) + f"   all: {share.mean():.3f}\n")
-    return {"controller": controller, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
-            "per_cell": a.per_cell, "length_ticks": a.length, "speed": a.speed, "form": form, "share_up": share.tolist()}
+    by_mu = None
+    if a.mu_true:
+        shape = (len(impulses), len(starts), 8, len(mus), a.per_cell)
+        down = (oc["down_tick"] >= 0).reshape(shape)
+        cell = down.shape[1] * down.shape[2] * down.shape[4]
+        print(f"true friction: robots down per (impulse, mu_true) cell, of {cell} (the controller assumes mu = {p.mu:g})")
+        print("impulse " + " ".join(f"mu={m:5.2f}" for m in mus))
+        for i, imp in enumerate(impulses):
+            print(f"{imp:5g}   " + " ".join(f"{int(down[i, :, :, m].sum()):8d}" for m in range(len(mus))))
+        print("ground tallies by mu_true, mean per robot (robots that went down stop counting at their down tick):")
+        for k in ("clipped_ticks", "friction_leg_ticks", "normal_leg_ticks"):
+            v = ta[k].reshape(shape)
+            print(f"{k:>20s} " + " ".join(f"{v[:, :, :, m].mean():8.1f}" for m in range(len(mus))))
+        first = ta["first_clipped_tick"].reshape(shape)
+        print(f"{'never clipped':>20s} " + " ".join(f"{int((first[:, :, :, m] < 0).sum()):8d}" for m in range(len(mus))) + "\n")
+        by_mu = {"mu_true": mus.tolist(), "down": down.sum(axis=(1, 2, 4)).tolist(), "cell": cell,
+                 "clipped_ticks_mean": ta["clipped_ticks"].reshape(shape).mean(axis=(0, 1, 2, 4)).tolist()}
+    return {"controller": controller, "by_mu_true": by_mu, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
+            "per_cell": len(mus) * a.per_cell, "length_ticks": a.length, "speed": a.speed, "form": form, "share_up": share.tolist()}
 
 
 if __name__ == "__main__":
