@@ -887,6 +887,53 @@ static void ipm_apply(solver_ws* ws, double alpha_p, double alpha_d) {
     }
 }
 
+/* Multipliers for the certificate (qo_options.dual_out: the oracle-only calls qo_solve*_one_dual; the iterate U, X is not
+ * touched, so the primal answer stays the plain call's).
+ * The step test is the last one to be met, and where the Newton steps converge linearly (large attitude errors: the
+ * Hessian term w |q_ref'q| is small) that takes 6 to 8 iterations more than the barrier test, each dividing mu by 100: the
+ * slacks of the active rows end at 1e-21 ... 1e-25 N, below the rounding of the row increments Ju dU, and the update
+ * lam += (target - s lam - lam ds) / s loses the multipliers digit by digit while the primal point keeps improving
+ * (measured: stationarity with the iterate's own multipliers 8e-10 at mu = 7e-18, 1.2e-4 at mu = 7e-26, with re-derived
+ * ones 5e-13).  So the multipliers handed out are those of one more Newton step of the same KKT system at the returned
+ * point with the slacks of the rows below 1e-9 N lifted to 1e-9 N (rc takes the difference) and the barrier target at 0,
+ * where lam / s is a well-defined number again: lam + dlam, the step's estimate, not applied to anything else.
+ * (tests/golden/kkt_fixtures.npz and stance_fixtures.npz were recorded with the iteration's own multipliers; on their
+ * records -- small attitude errors, quadratic tails -- both kinds meet the certificate's tolerances by five orders.) */
+static void dual_polish(solver_ws* ws, const qo_options* o) {
+  const qo_problem* p = ws->prob;
+  const double s_floor = 1e-9;
+  for (int k = 0; k <= ws->N; ++k)
+    for (int ci = 0; ci < p->ncon; ++ci) {
+      const qo_constraint* cn = &p->con[ci];
+      if (!con_active_at(cn, k) || cn->type != QO_INEQUALITY) continue;
+      knot_ws* kw = &ws->kn[k];
+      for (int i = 0; i < cn->p; ++i) {
+        if (!row_on(cn, i)) continue;
+        kw->kap[ci][i] = 0.0;
+        if (kw->s[ci][i] < s_floor) {
+          kw->rc[ci][i] += s_floor - kw->s[ci][i];
+          kw->s[ci][i] = s_floor;
+        }
+      }
+    }
+  ws->ipm_target = 0.0;
+  ws->ipm = 1;
+  if (backward_pass(ws) == QO_STATUS_OK) {
+    double ap, ad;
+    rollout_closed_loop(ws, 1.0);
+    ipm_directions(ws, o->ipm_tau, &ap, &ad);
+    for (int k = 0; k < ws->N; ++k)
+      for (int ci = 0; ci < p->ncon; ++ci) {
+        const qo_constraint* cn = &p->con[ci];
+        if (!con_active_at(cn, k) || cn->type != QO_INEQUALITY) continue;
+        knot_ws* kw = &ws->kn[k];
+        for (int i = 0; i < cn->p; ++i)
+          if (row_on(cn, i)) kw->lam[ci][i] = fmax(kw->lam[ci][i] + kw->dlam[ci][i], 0.0);
+      }
+  }
+  ws->ipm = 0;
+}
+
 static const double* p_x0(const solver_ws* ws) { return ws->prob->x0; }
 
 static int ipm_phase(solver_ws* ws, const qo_options* o, qo_result* r) {
@@ -1031,15 +1078,17 @@ int qo_altro_solve(const qo_problem* prob, const qo_options* opts, double* X, do
       r.status = st;
       r.penalty = r.ipm_mu;
       if (res) *res = r;
-      if (opts->dual_out || opts->slack_out) {
+      for (int pass = 0; pass < 2; ++pass) {      /* the slacks as the iteration left them, then the multipliers */
+        double* out = pass ? opts->dual_out : opts->slack_out;
+        if (!out) continue;
+        if (pass && st == QO_STATUS_OK) dual_polish(&ws, opts);
         size_t o = 0;
         for (int k = 0; k < N; ++k)
           for (int ci = 0; ci < prob->ncon; ++ci) {
             const qo_constraint* cn = &prob->con[ci];
             for (int i = 0; i < cn->p; ++i, ++o) {
               const int on = con_active_at(cn, k) && cn->type == QO_INEQUALITY && row_on(cn, i);
-              if (opts->dual_out) opts->dual_out[o] = on ? ws.kn[k].lam[ci][i] : 0.0;
-              if (opts->slack_out) opts->slack_out[o] = on ? ws.kn[k].s[ci][i] : 0.0;
+              out[o] = !on ? 0.0 : (pass ? ws.kn[k].lam[ci][i] : ws.kn[k].s[ci][i]);
             }
           }
       }
