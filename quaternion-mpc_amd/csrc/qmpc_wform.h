@@ -1196,8 +1196,12 @@ __device__ inline int recover_inputs_w(const DevParams& P, const Layout& L, doub
 // ---- converged mode, one lane per (knot, contact point): the input increments of the trial step (recover_inputs_w), then
 // the slack / multiplier directions of the point's six rows and its share of the step lengths (ipm_directions of
 // qmpc_kernels.hip: ds = -(a_i . dU_l + rc), dlam = (target - (1 + kappa) s lam - lam ds) / s, fraction to the boundary).
-// The rows' loads are issued together, nothing branches, and the ratio tests keep the smallest s / (-ds) as a fraction
-// (compared by cross-multiplication): one division per lane instead of two per row.  `kapbits` returns the weakly-active
+// The rows' loads are issued together and the ratio tests keep the smallest s / (-ds) as a fraction (compared by
+// cross-multiplication): one division per lane instead of two per row.  The six rows of a point are straight-line code: the
+// ratio tests are written with `&` / `|` on the comparisons' values (as `&&` / `||` each compiled to two nested exec-mask
+// regions: 25 s_and_saveexec and 15 s_cbranch_execz per trip of the lane loop, every row ending a basic block).  What a trip
+// still branches on is `stance` around the increment (one region) and its own back edge (tools/isa_regions.py,
+// profiles/HISTORY_r20.md).  `kapbits` returns the weakly-active
 // flags of the lane's rows (bit 6 j + i: row i of the lane's j-th (knot, point)), read from the DS slot before the
 // directions overwrite it; apply_w consumes them.  Returns nonzero (wave-uniform) when an increment is not finite.
 // ONEW (the all-LDS form, one wave per SIMD): the lane's point map bw[9] is read with the record's loads and the cone rows
@@ -1287,9 +1291,10 @@ __device__ inline int recover_directions_w(const DevParams& P, const Layout& L, 
       dsv = stance ? dsv : 0.0;
       dlv = stance ? dlv : 0.0;
       // sv / (-dsv) < pn / pd  <=>  sv pd < pn (-dsv)   (pd = 0: nothing yet, any candidate wins)
-      const bool up = (dsv < 0.0) && (pd == 0.0 || sv[i] * pd < pn * (-dsv));
+      // (`&`, `|` on the comparisons' values, not `&&`, `||`: every operand is evaluated, no exec-mask region per row)
+      const bool up = (int)(dsv < 0.0) & ((int)(pd == 0.0) | (int)(sv[i] * pd < pn * (-dsv)));
       pn = up ? sv[i] : pn; pd = up ? -dsv : pd;
-      const bool ud = (dlv < 0.0) && (dd == 0.0 || lv[i] * dd < dn * (-dlv));
+      const bool ud = (int)(dlv < 0.0) & ((int)(dd == 0.0) | (int)(lv[i] * dd < dn * (-dlv)));
       dn = ud ? lv[i] : dn; dd = ud ? -dlv : dd;
       if (!LEAN) {
         sl[L.DS + i0 + i] = dsv;
