@@ -984,6 +984,77 @@ qmpc_status qmpc_loop_run_ground_device(qmpc_handle* h, const qmpc_loop_params* 
                                         const qmpc_push_params* d_push, int32_t pushes_per_robot,
                                         const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally, void* stream);
 
+/* ---- actuation delay and actuator lag per robot (time between the solve and the force under the feet) -------------------
+ * In every loop above the force solved from the state at tick t acts on the plant during tick t: no compute latency, infinite
+ * actuator bandwidth.  qmpc_loop_run_actuation* is qmpc_loop_run_ground* -- the same robots, launch forms
+ * (QMPC_QUERY_LOOP_INSTANCES_PLAN answers for it too), refusals, ticks = 0 behaviour, freezing, halting and ConvexMpc opt-ins
+ * -- whose plant receives the command of delay_ticks ticks ago through a first-order actuator.  The controller is not told.
+ *
+ * The rule (loop_actuation_one, csrc/qmpc_loop_math.h: one source for the device, the host class and the tests) runs in the
+ * back end of a tick, after state.forces_body holds this tick's command c by the accept / reject rule of every loop (a
+ * rejected solve keeps the last accepted command, and that command is what is pushed):
+ *   1. push     line.cmd[count mod QMPC_MAX_DELAY] = c, copied as bytes
+ *   2. target   y = the slot of command number count - delay_ticks when that number is >= 0; otherwise the line predates the
+ *               first command and y is slot (count - delay_ticks) mod QMPC_MAX_DELAY taken non-negative, which still holds
+ *               the initial force qmpc_actuation_line_init wrote.  delay_ticks = 0: y is the bytes of c.  (delay_ticks =
+ *               QMPC_MAX_DELAY reads the slot before step 1 overwrites it.)
+ *   3. lag      per component: alpha == 1: a = y as bytes, no arithmetic; otherwise a = applied + alpha * (y - applied) --
+ *               one subtract, one multiply, one add, in that order
+ *   4. swing    a leg with contacts[l] == 0 delivers exactly +0.0 in all three components and its applied becomes +0.0: an
+ *               unloaded leg cannot push, and its actuator starts from rest at touchdown
+ *   5. store    applied = a, then count += 1
+ * A robot whose record is the identity (delay_ticks = 0, alpha = 1) takes the ground call's post step as it stands (QuatMpc:
+ * grf_world = R forces_body; ConvexMpc: the solve's world-frame bytes); steps 1 and 5 still keep its line current, so its
+ * state, traces, outcome record and tally are the bytes of qmpc_loop_run_ground*.  Any other robot forms grf_world = R a (in
+ * the expression shape of R forces_body; a swing leg's entry is +0.0) and passes through the ground clamp unchanged: a
+ * changed leg hands the plant R' f, an unchanged one a.  The plant steps under those twelve values and the tick's effective
+ * wrench, so pushes and ground compose.  state.forces_body and trace_forces stay the controller's COMMAND (what a warm start
+ * continues from, what tau = -J' f and the outcome record's max_force_z read); state.grf_world holds the DELIVERED force.
+ *
+ * act == NULL: the call IS qmpc_loop_run_ground* and line is not touched.  act != NULL with line == NULL: QMPC_BAD_ARGUMENT.
+ * ground == NULL with act != NULL: no clamp -- the bytes an all-+inf ground record gives; tally is untouched and no ground
+ * record is read.  A record with a non-finite field, a delay_ticks that is not an integer in 0 .. QMPC_MAX_DELAY, an alpha
+ * outside (0, 1], or a line whose count is negative, non-integer, non-finite or beyond 2^53 makes its robot the robot of an
+ * invalid plant record (QMPC_BAD_PARAMS, marked by a check kernel before the first tick: state untouched except status and
+ * iterations, zero trace rows, outcome record, tally and line untouched, every other robot unaffected bit for bit).  A frozen
+ * or halted robot leaves its line untouched.  Buffers: those of the ground call; the device call reads d_act and works on
+ * d_line in place; the host-buffer call stages records and lines in a buffer of its own ((32 + 896) B x max_batch), allocated
+ * on its first use -- a call with ticks = 0 included.  No other call allocates it. */
+#define QMPC_MAX_DELAY 8
+typedef struct qmpc_actuation_params {   /* 4 doubles, 32 B */
+  double delay_ticks;   /* 0 .. QMPC_MAX_DELAY, integer-valued: the plant receives the command of delay_ticks ticks ago */
+  double alpha;         /* first-order actuator response per tick, in (0, 1]; exactly 1: none.  alpha = 1 - exp(-dt / tau) */
+  double reserved[2];   /* 0 */
+} qmpc_actuation_params;
+typedef struct qmpc_actuation_line {     /* 112 doubles, 896 B; in/out: the robot's delay line, carries over calls */
+  double cmd[QMPC_MAX_DELAY][12];  /* ring of body-frame commands; the command number c sits in slot c mod QMPC_MAX_DELAY */
+  double applied[12];              /* body-frame force the actuators produced in the last tick (the lag's state) */
+  double count;                    /* commands pushed so far (integer-valued, >= 0) */
+  double reserved[3];
+} qmpc_actuation_line;
+/* Host-side; every byte is written.  The identity record (delay_ticks = 0, alpha = 1); every ring slot and applied hold
+ * initial_forces_body ([12], or NULL = zeros), count = 0 */
+void    qmpc_actuation_params_init(qmpc_actuation_params* act, int32_t batch);
+void    qmpc_actuation_line_init(qmpc_actuation_line* line, int32_t batch, const double* initial_forces_body);
+int32_t qmpc_sizeof_actuation_params(void);
+int32_t qmpc_sizeof_actuation_line(void);
+/* Host buffers: qmpc_loop_run_ground's arguments, then act [batch] and line [batch] in/out.  Synchronous. */
+qmpc_status qmpc_loop_run_actuation(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                    int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant,
+                                    double* trace_forces, double* trace_contacts, const qmpc_outcome_params* op,
+                                    qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int32_t pushes_per_robot,
+                                    const qmpc_ground_params* ground, qmpc_ground_tally* tally,
+                                    const qmpc_actuation_params* act, qmpc_actuation_line* line);
+/* Device buffers (op is a host pointer, read during the call), stream-ordered (NULL stream = the handle's). */
+qmpc_status qmpc_loop_run_actuation_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch,
+                                           qmpc_loop_state* d_states, int32_t ticks,
+                                           const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                           double* d_trace_forces, double* d_trace_contacts,
+                                           const qmpc_outcome_params* op, qmpc_loop_outcome* d_outcomes,
+                                           const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                           const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
+                                           const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line, void* stream);
+
 /* Stand-pose joint angles (0, 0.67, -1.3 per leg: the reference's Gazebo start pose) for `batch`
  * robots, host buffer [batch][12]. */
 void qmpc_loop_joint_init(double* joint_pos, int32_t batch);

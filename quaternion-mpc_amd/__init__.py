@@ -311,6 +311,47 @@ def ground_tallies(batch: int) -> np.ndarray:
     return out
 
 
+# struct qmpc_actuation_params (qmpc_loop_run_actuation*): the time between one robot's solve and the force under its feet, 4 doubles
+MAX_DELAY = 8
+ACTUATION_PARAMS_DTYPE = np.dtype([("delay_ticks", "<f8"), ("alpha", "<f8"), ("reserved", "<f8", (2,))], align=False)
+# struct qmpc_actuation_line: the robot's delay line, 112 doubles = 896 B (in/out: carries over calls)
+ACTUATION_LINE_DTYPE = np.dtype(
+    [("cmd", "<f8", (MAX_DELAY, 12)), ("applied", "<f8", (12,)), ("count", "<f8"), ("reserved", "<f8", (3,))], align=False)
+assert ACTUATION_PARAMS_DTYPE.itemsize == 4 * 8 and ACTUATION_LINE_DTYPE.itemsize == 112 * 8
+
+
+def actuation_params(batch: int, delay_ticks=0, tau=None, dt: float = 0.005) -> np.ndarray:
+    """[batch] actuation records: the plant receives the command of delay_ticks ticks ago (an integer in 0 .. MAX_DELAY, or one
+    per robot) through a first-order actuator of time constant tau seconds (None or 0: no lag; or one per robot) sampled at
+    the loop's tick dt: alpha = 1 - exp(-dt / tau).  The defaults give the bytes of qmpc_actuation_params_init."""
+    out = np.zeros(int(batch), dtype=ACTUATION_PARAMS_DTYPE)
+    out["delay_ticks"] = delay_ticks
+    out["alpha"] = 1.0
+    if tau is not None:
+        tau = np.broadcast_to(np.asarray(tau, dtype=np.float64), (int(batch),))
+        lag = tau > 0.0
+        out["alpha"][lag] = -np.expm1(-float(dt) / tau[lag])
+    return out
+
+
+def stand_forces_body(mass: float) -> np.ndarray:
+    """[12] the body-frame force of a level robot standing still: m g / 4 on each leg's fz (g = 9.81, the plant's)."""
+    f = np.zeros(12)
+    f[2::3] = float(mass) * 9.81 / 4.0
+    return f
+
+
+def actuation_lines(batch: int, initial=None) -> np.ndarray:
+    """[batch] delay lines before the first command: every ring slot and applied hold `initial` ([12] body-frame forces, e.g.
+    stand_forces_body(params.mass), or [batch, 12]; None: zeros), count = 0 -- the bytes of qmpc_actuation_line_init."""
+    out = np.zeros(int(batch), dtype=ACTUATION_LINE_DTYPE)
+    if initial is not None:
+        f = np.broadcast_to(np.asarray(initial, dtype=np.float64), (int(batch), 12))
+        out["cmd"] = f[:, None, :]
+        out["applied"] = f
+    return out
+
+
 # struct qmpc_info: 2 x int32 + 4 doubles = 40 B
 INFO_DTYPE = np.dtype(
     [
@@ -423,6 +464,16 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_ground_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
                                                 i32, vp, vp, vp]
     lib.qmpc_loop_run_ground_device.restype = i32
+    lib.qmpc_actuation_params_init.argtypes = [vp, i32]
+    lib.qmpc_actuation_params_init.restype = None
+    lib.qmpc_actuation_line_init.argtypes = [vp, i32, vp]
+    lib.qmpc_actuation_line_init.restype = None
+    lib.qmpc_loop_run_actuation.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp,
+                                            vp, vp]
+    lib.qmpc_loop_run_actuation.restype = i32
+    lib.qmpc_loop_run_actuation_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
+                                                   i32, vp, vp, vp, vp, vp]
+    lib.qmpc_loop_run_actuation_device.restype = i32
     lib.qmpc_set_instances_policy.argtypes = [vp, i32]
     lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_set_loop_warm_records.argtypes = [vp, i32]
@@ -503,7 +554,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_device.restype = i32
     for name in ("qmpc_sizeof_input", "qmpc_sizeof_params", "qmpc_sizeof_info", "qmpc_sizeof_convex_input",
                  "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params", "qmpc_sizeof_plant_params",
-                 "qmpc_sizeof_loop_outcome", "qmpc_sizeof_push_params", "qmpc_sizeof_ground_params", "qmpc_sizeof_ground_tally"):
+                 "qmpc_sizeof_loop_outcome", "qmpc_sizeof_push_params", "qmpc_sizeof_ground_params", "qmpc_sizeof_ground_tally",
+                 "qmpc_sizeof_actuation_params", "qmpc_sizeof_actuation_line"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = i32
     if lib.qmpc_sizeof_input() != INPUT_DTYPE.itemsize:
@@ -528,6 +580,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         raise RuntimeError("qmpc_push_params ABI size mismatch")
     if lib.qmpc_sizeof_ground_params() != GROUND_PARAMS_DTYPE.itemsize or lib.qmpc_sizeof_ground_tally() != GROUND_TALLY_DTYPE.itemsize:
         raise RuntimeError("qmpc_ground_params / qmpc_ground_tally ABI size mismatch")
+    if (lib.qmpc_sizeof_actuation_params() != ACTUATION_PARAMS_DTYPE.itemsize
+            or lib.qmpc_sizeof_actuation_line() != ACTUATION_LINE_DTYPE.itemsize):
+        raise RuntimeError("qmpc_actuation_params / qmpc_actuation_line ABI size mismatch")
     return lib
 
 
@@ -615,6 +670,12 @@ EXPORTED_SYMBOLS = (
     "qmpc_sizeof_ground_tally",
     "qmpc_loop_run_ground",
     "qmpc_loop_run_ground_device",
+    "qmpc_actuation_params_init",
+    "qmpc_actuation_line_init",
+    "qmpc_sizeof_actuation_params",
+    "qmpc_sizeof_actuation_line",
+    "qmpc_loop_run_actuation",
+    "qmpc_loop_run_actuation_device",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
@@ -1111,6 +1172,69 @@ class Solver:
         if rc != OK:
             raise QmpcError(rc, "qmpc_loop_run_ground_device")
 
+    def loop_run_actuation(self, states: np.ndarray, ticks: int, act: np.ndarray | None, lines: np.ndarray | None = None,
+                           ground: np.ndarray | None = None, push: np.ndarray | None = None, lp: LoopParams | None = None,
+                           ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
+                           outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None, trace: bool = False):
+        """qmpc_loop_run_actuation: loop_run_ground whose plant receives each robot's command of delay_ticks ticks ago through
+        its first-order actuator.  act: [B] ACTUATION_PARAMS_DTYPE records, actuation_params(); None: exactly loop_run_ground
+        (the lines come back as given).  lines: the ACTUATION_LINE_DTYPE records to go on from (None: actuation_lines(B), zeros).
+        ground may be None (no clamp).  Returns (states, outcomes, tallies, lines[, forces, contacts]); the arguments are not
+        modified."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
+        B = st.shape[0]
+
+        def records(a, dtype, name, copy=False):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.shape != (B,):
+                raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
+            return a.copy() if copy else a
+
+        ctrl = records(ctrl, INSTANCE_PARAMS_DTYPE, "ctrl")
+        plant = records(plant, PLANT_PARAMS_DTYPE, "plant")
+        ground = records(ground, GROUND_PARAMS_DTYPE, "ground")
+        act = records(act, ACTUATION_PARAMS_DTYPE, "act")
+        per_robot = 0
+        if push is not None:
+            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
+            if push.ndim == 1:
+                push = push.reshape(-1, 1)
+            if push.ndim != 2 or push.shape[0] != B:
+                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
+            per_robot = push.shape[1]
+            if per_robot == 0:
+                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
+        oc = loop_outcomes(B, self.lib) if outcomes is None else records(outcomes, LOOP_OUTCOME_DTYPE, "outcomes", copy=True)
+        ta = ground_tallies(B) if tallies is None else records(tallies, GROUND_TALLY_DTYPE, "tallies", copy=True)
+        li = actuation_lines(B) if lines is None else records(lines, ACTUATION_LINE_DTYPE, "lines", copy=True)
+        tf = np.zeros((ticks, B, 12)) if trace else None
+        tc = np.zeros((ticks, B, 4)) if trace else None
+        rc = self.lib.qmpc_loop_run_actuation(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
+                                              C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta), _ptr(act),
+                                              _ptr(li))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_actuation")
+        return (st, oc, ta, li, tf, tc) if trace else (st, oc, ta, li)
+
+    def loop_run_actuation_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_act: int, d_line: int,
+                                  d_ground: int = 0, d_tally: int = 0, d_push: int = 0, pushes_per_robot: int = 0,
+                                  lp: LoopParams | None = None, op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0,
+                                  d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_actuation_device: device pointers (ints; 0 = NULL), stream-ordered; d_act, d_ground and d_push are read in
+        place, d_line and d_tally (or 0) are read and written."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        rc = self.lib.qmpc_loop_run_actuation_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
+                                                     p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
+                                                     int(pushes_per_robot), p(d_ground), p(d_tally), p(d_act), p(d_line), p(stream))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_actuation_device")
+
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
         as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN).  Answers under the handle's
@@ -1423,5 +1547,5 @@ class Solver:
 
 from .scenarios import (go1_stand_input, quat_to_rot, random_go1_trot_states,  # noqa: E402,F401
                         random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_convex_variants, random_go1_plants,
-                        random_go1_pushes, random_go1_grounds)
+                        random_go1_pushes, random_go1_grounds, random_go1_actuations)
 from .sharding import StepPipeline, gather_forces, shard_range, solve_sharded  # noqa: E402,F401

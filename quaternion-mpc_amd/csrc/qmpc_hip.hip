@@ -72,7 +72,8 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
 // controller and plant records (qmpc_loop_run_instances*), with the outcome step (qmpc_loop_run_outcomes*), under timed push
 // windows (qmpc_loop_run_pushes*), on the robot's true ground (qmpc_loop_run_ground*).  Each unit defines the same entry points in
 // its namespace (qmpc_loop_rec.inc) and ignores the trailing arguments its kernels do not take; the push and ground units have no
-// front kernel of their own.
+// front kernel of their own.  qmpc_loop_act.hip: the ground loop behind the robot's delay line and actuator lag
+// (qmpc_loop_run_actuation*), the same entry points once more, no front kernel either.
 #define QMPC_REC_DECLARE(ns)                                                                                                         \
   namespace ns {                                                                                                                     \
   hipError_t rec_set_lds();                                                                                                          \
@@ -80,13 +81,15 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
                               const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info,    \
                               double* trace_f, double* trace_c, int ticks, double* gws, const qmpc_outcome_params* op,              \
                               qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,                             \
-                              const qmpc_ground_params* ground, qmpc_ground_tally* tally);                                          \
+                              const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act,         \
+                              qmpc_actuation_line* line);                                                                            \
   hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, int* row,            \
                               const void* plants, int batch, const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes);     \
   hipError_t rec_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, const double* forces,                  \
                              const qmpc_info* info, double* trace_f, double* trace_c, const int* row, const void* plants, int batch, \
                              const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push,              \
-                             int per_robot, const qmpc_ground_params* ground, qmpc_ground_tally* tally);                             \
+                             int per_robot, const qmpc_ground_params* ground, qmpc_ground_tally* tally,                              \
+                             const qmpc_actuation_params* act, qmpc_actuation_line* line);                                           \
   }
 QMPC_REC_DECLARE(qmpc_inst_tu)
 QMPC_REC_DECLARE(qmpc_outc_tu)
@@ -94,21 +97,26 @@ QMPC_REC_DECLARE(qmpc_push_tu)
 QMPC_REC_DECLARE(qmpc_crec_tu)      // qmpc_loop_crec.hip: the three kinds on a ConvexMpc handle (qmpc_set_convex_records)
 QMPC_REC_DECLARE(qmpc_ground_tu)    // qmpc_loop_ground.hip
 QMPC_REC_DECLARE(qmpc_cground_tu)   // qmpc_loop_cground.hip: the ground call on such a ConvexMpc handle
+QMPC_REC_DECLARE(qmpc_act_tu)       // qmpc_loop_act.hip
+QMPC_REC_DECLARE(qmpc_cact_tu)      // qmpc_loop_cact.hip: the actuation call on such a ConvexMpc handle
 #undef QMPC_REC_DECLARE
 enum { REC_PLAIN = 0, REC_OUTCOME = 1, REC_PUSH = 2 };      // the kind of a call with records: QMPC_REC_EXT of its unit
 enum { REC_CONVEX = 3 };                                    // ... the unit that serves those three kinds for ConvexMpc's problem
 enum { REC_GROUND = 4, REC_CGROUND = 5 };                   // the ground call's kind (EXT 3), and its unit for ConvexMpc's problem
+enum { REC_ACT = 6, REC_CACT = 7 };                         // the actuation call's kind (EXT 4), and its unit for ConvexMpc's problem
 static const struct {
   decltype(&qmpc_inst_tu::rec_set_lds) set_lds;
   decltype(&qmpc_inst_tu::rec_fused_launch) fused_launch;
   decltype(&qmpc_inst_tu::rec_front_launch) front_launch;
   decltype(&qmpc_inst_tu::rec_post_launch) post_launch;
-} kRec[6] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
+} kRec[8] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
              {qmpc_outc_tu::rec_set_lds, qmpc_outc_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_outc_tu::rec_post_launch},
              {qmpc_push_tu::rec_set_lds, qmpc_push_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_push_tu::rec_post_launch},
              {qmpc_crec_tu::rec_set_lds, qmpc_crec_tu::rec_fused_launch, qmpc_crec_tu::rec_front_launch, qmpc_crec_tu::rec_post_launch},
              {qmpc_ground_tu::rec_set_lds, qmpc_ground_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_ground_tu::rec_post_launch},
-             {qmpc_cground_tu::rec_set_lds, qmpc_cground_tu::rec_fused_launch, qmpc_cground_tu::rec_front_launch, qmpc_cground_tu::rec_post_launch}};
+             {qmpc_cground_tu::rec_set_lds, qmpc_cground_tu::rec_fused_launch, qmpc_cground_tu::rec_front_launch, qmpc_cground_tu::rec_post_launch},
+             {qmpc_act_tu::rec_set_lds, qmpc_act_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_act_tu::rec_post_launch},
+             {qmpc_cact_tu::rec_set_lds, qmpc_cact_tu::rec_fused_launch, qmpc_cact_tu::rec_front_launch, qmpc_cact_tu::rec_post_launch}};
 // ... and the kernels each unit has beside them: the expansions of the plant blocks and the check of the windows
 hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, const qmpc_plant_params* plant,
                                         const qmpc_instance_params* ctrl, const int* ctrl_status, void* bcast_out, void* plants_out,
@@ -118,6 +126,9 @@ hipError_t qmpc_loop_outcome_expand_base_launch(hipStream_t s, const void* dev_p
 hipError_t qmpc_loop_push_check_launch(hipStream_t s, const qmpc_push_params* push, int per_robot, void* plants, int batch);
 namespace qmpc_ground_tu {
 hipError_t rec_ground_check_launch(hipStream_t s, const qmpc_ground_params* ground, void* plants, int batch);
+}
+namespace qmpc_act_tu {
+hipError_t rec_act_check_launch(hipStream_t s, const qmpc_actuation_params* act, const qmpc_actuation_line* line, void* plants, int batch);
 }
 
 // qmpc_lane.hip (third translation unit): the lane-per-instance kernel of large batches
@@ -245,6 +256,8 @@ struct qmpc_handle {
   int push_cap;                   // ... windows per robot it holds (grown when a call brings more)
   void* d_ground;                 // staging of qmpc_loop_run_ground (the host-buffer call), on its first use: max_batch ground
                                   // records (64 B each), then max_batch tallies (32 B each)
+  void* d_act;                    // staging of qmpc_loop_run_actuation (the host-buffer call), on its first use: max_batch delay
+                                  // lines (896 B each), then max_batch actuation records (32 B each)
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -472,6 +485,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_outcome) (void)hipFree(h->d_outcome);
   if (h->d_push) (void)hipFree(h->d_push);
   if (h->d_ground) (void)hipFree(h->d_ground);
+  if (h->d_act) (void)hipFree(h->d_act);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1200,6 +1214,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_outcome) b += sizeof(qmpc_loop_outcome) * (size_t)h->max_batch;
       if (h->d_push) b += sizeof(qmpc_push_params) * (size_t)h->push_cap * (size_t)h->max_batch;
       if (h->d_ground) b += (sizeof(qmpc_ground_params) + sizeof(qmpc_ground_tally)) * (size_t)h->max_batch;
+      if (h->d_act) b += (sizeof(qmpc_actuation_params) + sizeof(qmpc_actuation_line)) * (size_t)h->max_batch;
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
       return QMPC_OK;
@@ -1691,17 +1706,19 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                        qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot,
-                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally, void* stream);
+                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
+                                       const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line, void* stream);
 
 // The host-buffer closed loop of every kind (qmpc_loop_run*, its arguments checked): states and traces through the handle's
 // staging, which only grows -- [states | force trace | contact trace]; the records given go to the staging halves of the
 // per-instance and plant buffers, outcome records and windows to h->d_outcome and h->d_push, ground records and tallies to
-// h->d_ground (all allocated by the caller)
+// h->d_ground, actuation records and delay lines to h->d_act (all allocated by the caller)
 static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
                                      int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                      double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                      const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
-                                     qmpc_ground_tally* tally) {
+                                     qmpc_ground_tally* tally, const qmpc_actuation_params* act = nullptr,
+                                     qmpc_actuation_line* line = nullptr) {
   const size_t B = (size_t)batch, T = (size_t)ticks;
   const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
                n_tc = trace_contacts ? 4 * B * T : 0;
@@ -1724,10 +1741,15 @@ static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_p
   qmpc_ground_tally* d_ta = (ground && tally) ? reinterpret_cast<qmpc_ground_tally*>(static_cast<qmpc_ground_params*>(h->d_ground) + h->max_batch) : nullptr;
   if (d_gr) HIP_TRY(hipMemcpyAsync(d_gr, ground, sizeof(qmpc_ground_params) * B, hipMemcpyHostToDevice, h->stream));
   if (d_ta) HIP_TRY(hipMemcpyAsync(d_ta, tally, sizeof(qmpc_ground_tally) * B, hipMemcpyHostToDevice, h->stream));
+  qmpc_actuation_line* d_li = act ? static_cast<qmpc_actuation_line*>(h->d_act) : nullptr;
+  qmpc_actuation_params* d_ac = act ? reinterpret_cast<qmpc_actuation_params*>(static_cast<qmpc_actuation_line*>(h->d_act) + h->max_batch) : nullptr;
+  if (d_ac) HIP_TRY(hipMemcpyAsync(d_ac, act, sizeof(qmpc_actuation_params) * B, hipMemcpyHostToDevice, h->stream));
+  if (d_li) HIP_TRY(hipMemcpyAsync(d_li, line, sizeof(qmpc_actuation_line) * B, hipMemcpyHostToDevice, h->stream));
   const qmpc_status rs = loop_records_device(kind, h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
                                              d_tf, d_tc, op, outcomes ? h->d_outcome : nullptr, push ? h->d_push : nullptr, per_robot,
-                                             d_gr, d_ta, nullptr);
+                                             d_gr, d_ta, d_ac, d_li, nullptr);
   if (rs != QMPC_OK) return rs;
+  if (d_li) HIP_TRY(hipMemcpyAsync(line, d_li, sizeof(qmpc_actuation_line) * B, hipMemcpyDeviceToHost, h->stream));
   if (d_ta) HIP_TRY(hipMemcpyAsync(tally, d_ta, sizeof(qmpc_ground_tally) * B, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
   if (outcomes) HIP_TRY(hipMemcpyAsync(outcomes, h->d_outcome, sizeof(qmpc_loop_outcome) * B, hipMemcpyDeviceToHost, h->stream));
@@ -1815,12 +1837,14 @@ static qmpc_status loop_instances_buffers(qmpc_handle* h, int32_t batch, bool ha
 // with the kernels of the kind's unit in place of the plain unit's; without records (both NULL) every robot's plant block carries
 // the handle's mass and inverse inertia, and the call-level checks are those of a call with plant records.  d_push (REC_PUSH):
 // per_robot windows per robot, checked once after the plant expansion.  REC_GROUND (qmpc_loop_run_ground_device): d_push may be
-// NULL (no windows), d_ground is checked after the windows, d_tally may be NULL.
+// NULL (no windows), d_ground is checked after the windows, d_tally may be NULL.  REC_ACT (qmpc_loop_run_actuation_device): d_ground
+// may be NULL too (no clamp; checked when given), d_act and the count of d_line are checked last.
 static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                        qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot,
-                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally, void* stream) {
+                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
+                                       const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line, void* stream) {
   if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !d_states)) return QMPC_BAD_ARGUMENT;
   if (kind != REC_PLAIN && (!op || (batch > 0 && !d_outcomes))) return QMPC_BAD_ARGUMENT;
   if (kind == REC_PLAIN && !d_ctrl && !d_plant)
@@ -1841,14 +1865,14 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   // a ConvexMpc handle (opted in): one unit for the three kinds -- a call without windows passes none (per_robot = 0), a call
   // without outcome records the handle's scratch and parameters that never halt a robot
   const bool crec = convex_records(h);
-  const auto& R = kRec[kind == REC_GROUND ? (crec ? REC_CGROUND : REC_GROUND) : crec ? REC_CONVEX : kind];
+  const auto& R = kRec[kind == REC_ACT ? (crec ? REC_CACT : REC_ACT) : kind == REC_GROUND ? (crec ? REC_CGROUND : REC_GROUND) : crec ? REC_CONVEX : kind];
   qmpc_outcome_params op_none;
   std::memset(&op_none, 0, sizeof op_none);
   if (crec && kind == REC_PLAIN) {
     op = &op_none;
     d_outcomes = h->d_outcome;
   }
-  if ((crec && kind != REC_PUSH && kind != REC_GROUND) || !d_push) {
+  if ((crec && kind != REC_PUSH && kind != REC_GROUND && kind != REC_ACT) || !d_push) {
     d_push = nullptr;
     per_robot = 0;
   }
@@ -1862,11 +1886,13 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   else
     HIP_TRY(qmpc_loop_outcome_expand_base_launch(s, &h->dev, sizeof h->dev, bcast, plant_dev(h), (int)batch));
   if (d_push) HIP_TRY(qmpc_loop_push_check_launch(s, d_push, (int)per_robot, plant_dev(h), (int)batch));
-  if (kind == REC_GROUND) HIP_TRY(qmpc_ground_tu::rec_ground_check_launch(s, d_ground, plant_dev(h), (int)batch));
+  if (kind == REC_GROUND || (kind == REC_ACT && d_ground))
+    HIP_TRY(qmpc_ground_tu::rec_ground_check_launch(s, d_ground, plant_dev(h), (int)batch));
+  if (kind == REC_ACT) HIP_TRY(qmpc_act_tu::rec_act_check_launch(s, d_act, d_line, plant_dev(h), (int)batch));
   if (lpp.fused) {
     HIP_TRY(R.fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, d_states, h->d_in, h->d_forces, h->d_info,
                            d_trace_forces, d_trace_contacts, (int)ticks, lpp.gws ? h->d_gws : nullptr, op, d_outcomes, d_push,
-                           (int)per_robot, d_ground, d_tally));
+                           (int)per_robot, d_ground, d_tally, d_act, d_line));
     return QMPC_OK;
   }
   auto one_tick = [&](bool first) -> qmpc_status {
@@ -1878,7 +1904,7 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
                                                 batch, h->d_in, h->d_forces, h->d_info, warm ? h->d_traj_u : nullptr, nullptr, s);
     if (st != QMPC_OK) return st;
     HIP_TRY(R.post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, h->d_loop_row, plant_dev(h),
-                          (int)batch, op, d_outcomes, d_push, (int)per_robot, d_ground, d_tally));
+                          (int)batch, op, d_outcomes, d_push, (int)per_robot, d_ground, d_tally, d_act, d_line));
     return QMPC_OK;
   };
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
@@ -1891,7 +1917,7 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
                                            int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                            double* d_trace_forces, double* d_trace_contacts, void* stream) {
   return loop_records_device(REC_PLAIN, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, nullptr, nullptr,
-                             nullptr, 0, nullptr, nullptr, stream);
+                             nullptr, 0, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -1935,17 +1961,18 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
                                           double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                           qmpc_loop_outcome* d_outcomes, void* stream) {
   return loop_records_device(REC_OUTCOME, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
-                             nullptr, 0, nullptr, nullptr, stream);
+                             nullptr, 0, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // the host-buffer call's checks and buffers (the staging itself: loop_records_host); push (qmpc_loop_run_pushes; NULL:
 // qmpc_loop_run_outcomes): per_robot windows per robot, staged in h->d_push; ground (qmpc_loop_run_ground, with or without push)
-// and tally (or NULL): staged in h->d_ground
+// and tally (or NULL): staged in h->d_ground; act and line (qmpc_loop_run_actuation, with or without ground): staged in h->d_act
 static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
                                       const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                       double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                       const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
-                                      qmpc_ground_tally* tally) {
+                                      qmpc_ground_tally* tally, const qmpc_actuation_params* act = nullptr,
+                                      qmpc_actuation_line* line = nullptr) {
   if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!states || !outcomes))) return QMPC_BAD_ARGUMENT;
   const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
@@ -1961,13 +1988,15 @@ static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp
   }
   // (the push call's ticks = 0 allocates everything a later push call needs, the records' staging included; the outcome call's
   // ticks = 0 stops before it, as it always did)
-  if ((push || ground) && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
+  if ((push || ground || act) && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
   if (ground && !h->d_ground)
     HIP_TRY(hipMalloc(&h->d_ground, (sizeof(qmpc_ground_params) + sizeof(qmpc_ground_tally)) * (size_t)h->max_batch));
+  if (act && !h->d_act)
+    HIP_TRY(hipMalloc(&h->d_act, (sizeof(qmpc_actuation_params) + sizeof(qmpc_actuation_line)) * (size_t)h->max_batch));
   if (ticks == 0) return es;
   if (!h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
-  return loop_records_host(ground ? REC_GROUND : push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant, trace_forces,
-                           trace_contacts, op, outcomes, push, per_robot, ground, tally);
+  return loop_records_host(act ? REC_ACT : ground ? REC_GROUND : push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant,
+                           trace_forces, trace_contacts, op, outcomes, push, per_robot, ground, tally, act, line);
 }
 
 qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -1990,7 +2019,7 @@ qmpc_status qmpc_loop_run_pushes_device(qmpc_handle* h, const qmpc_loop_params* 
                                          stream);
   if (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES) return QMPC_BAD_ARGUMENT;
   return loop_records_device(REC_PUSH, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             pushes_per_robot, nullptr, nullptr, stream);
+                             pushes_per_robot, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_pushes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2033,7 +2062,7 @@ qmpc_status qmpc_loop_run_ground_device(qmpc_handle* h, const qmpc_loop_params* 
                                        pushes_per_robot, stream);
   if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
   return loop_records_device(REC_GROUND, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             d_push ? pushes_per_robot : 0, d_ground, d_tally, stream);
+                             d_push ? pushes_per_robot : 0, d_ground, d_tally, nullptr, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_ground(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2046,6 +2075,62 @@ qmpc_status qmpc_loop_run_ground(qmpc_handle* h, const qmpc_loop_params* lp, int
   if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
   return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
                             push ? pushes_per_robot : 0, ground, tally);
+}
+
+// ---- the ground loop behind the robot's delay line and actuator lag (qmpc_loop_act.hip, qmpc_loop_cact.hip) ----------------------
+static_assert(sizeof(qmpc_actuation_params) == 32 && sizeof(qmpc_actuation_line) == 896, "qmpc_actuation_params is 4 doubles, qmpc_actuation_line 112");
+int32_t qmpc_sizeof_actuation_params(void) { return (int32_t)sizeof(qmpc_actuation_params); }
+int32_t qmpc_sizeof_actuation_line(void) { return (int32_t)sizeof(qmpc_actuation_line); }
+
+void qmpc_actuation_params_init(qmpc_actuation_params* act, int32_t batch) {
+  if (!act) return;
+  for (int32_t i = 0; i < batch; ++i) {
+    act[i].delay_ticks = 0.0;
+    act[i].alpha = 1.0;
+    act[i].reserved[0] = act[i].reserved[1] = 0.0;
+  }
+}
+
+void qmpc_actuation_line_init(qmpc_actuation_line* line, int32_t batch, const double* initial_forces_body) {
+  if (!line) return;
+  for (int32_t i = 0; i < batch; ++i) {
+    for (int k = 0; k < 12; ++k) {
+      const double f = initial_forces_body ? initial_forces_body[k] : 0.0;
+      for (int c = 0; c < QMPC_MAX_DELAY; ++c) line[i].cmd[c][k] = f;
+      line[i].applied[k] = f;
+    }
+    line[i].count = 0.0;
+    line[i].reserved[0] = line[i].reserved[1] = line[i].reserved[2] = 0.0;
+  }
+}
+
+qmpc_status qmpc_loop_run_actuation_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                           int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                           double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                           qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                           const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
+                                           const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line, void* stream) {
+  if (!d_act)
+    return qmpc_loop_run_ground_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
+                                       pushes_per_robot, d_ground, d_tally, stream);
+  if (!d_line) return QMPC_BAD_ARGUMENT;
+  if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
+  return loop_records_device(REC_ACT, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
+                             d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_line, stream);
+}
+
+qmpc_status qmpc_loop_run_actuation(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                    const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                    double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
+                                    const qmpc_push_params* push, int32_t pushes_per_robot, const qmpc_ground_params* ground,
+                                    qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line) {
+  if (!act)
+    return qmpc_loop_run_ground(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot,
+                                ground, tally);
+  if (!line) return QMPC_BAD_ARGUMENT;
+  if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
+  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
+                            push ? pushes_per_robot : 0, ground, ground ? tally : nullptr, act, line);
 }
 
 // Diagnostic: per-instance phase cycle counts (s_memtime) of one solve launch.

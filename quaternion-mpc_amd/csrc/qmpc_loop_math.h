@@ -303,6 +303,58 @@ QMPC_HD void loop_ground_to_body(const double* R, const double* f, double* fb) {
   for (int r = 0; r < 3; ++r) fb[r] = R[r] * f[0] + R[3 + r] * f[1] + R[6 + r] * f[2];
 }
 
+// The time between the solve and the force under the feet (qmpc_loop_run_actuation*, include/qmpc.h): a record is the identity
+// when it neither delays nor lags -- its robot takes the ground call's post step as it stands
+QMPC_HD bool loop_actuation_identity(const qmpc_actuation_params& p) { return p.delay_ticks == 0.0 && p.alpha == 1.0; }
+
+// ... and is valid when delay_ticks is an integer in 0 .. QMPC_MAX_DELAY, alpha lies in (0, 1] and the reserved words are
+// finite (a NaN fails every comparison; x - x is 0 only for a finite x); a line when its count is a non-negative integer
+// that `+ 1.0` still advances (below 2^53).  The robot of an invalid one is frozen like that of an invalid plant record.
+QMPC_HD bool loop_actuation_valid(const qmpc_actuation_params& p, const qmpc_actuation_line& line) {
+  QMPC_NO_CONTRACT
+  bool ok = p.delay_ticks >= 0.0 && p.delay_ticks <= (double)QMPC_MAX_DELAY && p.delay_ticks == (double)(int)p.delay_ticks;
+  ok = ok && p.alpha > 0.0 && p.alpha <= 1.0;
+  ok = ok && (p.reserved[0] - p.reserved[0] == 0.0) && (p.reserved[1] - p.reserved[1] == 0.0);
+  const double n = line.count;
+  ok = ok && n >= 0.0 && n < 9007199254740992.0 && n == (double)(long long)n;
+  return ok;
+}
+
+// One tick of a robot's actuation (the rule of include/qmpc.h in full): c (12) is the tick's body-frame command, contacts (4)
+// its stance flags, a (12) receives the body-frame force the actuators produce.  Push c into slot count mod 8; the target y is
+// the slot of command count - delay_ticks (before the first command: the slot that still holds the initial force; `& 7` of a
+// negative two's-complement number is its non-negative remainder).  Each word of the target's slot is read before the
+// command's word is written, since with delay_ticks = QMPC_MAX_DELAY the two are one slot; with delay_ticks = 0 y is c itself.
+// alpha == 1: a = y as bytes; otherwise a = applied + alpha * (y - applied).  A swing leg delivers +0.0 and its applied becomes
+// +0.0.  Then applied = a, count += 1.  The ring is indexed in the line's own memory (global memory on the device): one slot
+// read, one written, applied read-modify-written, no local copy of the line.  p and line must be valid (loop_actuation_valid).
+QMPC_HD void loop_actuation_one(const qmpc_actuation_params& p, qmpc_actuation_line& line, const double* c, const double* contacts,
+                                double* a) {
+  QMPC_NO_CONTRACT
+  const long long n = (long long)line.count;
+  const int d = (int)p.delay_ticks;
+  const double alpha = p.alpha;
+  double* wr = line.cmd[(int)(n & (QMPC_MAX_DELAY - 1))];
+  const double* rd = line.cmd[(int)((n - d) & (QMPC_MAX_DELAY - 1))];
+  for (int l = 0; l < 4; ++l)
+    for (int r = 0; r < 3; ++r) {
+      const int k = 3 * l + r;
+      const double old = rd[k];
+      wr[k] = c[k];
+      const double y = d == 0 ? c[k] : old;
+      double v;
+      if (contacts[l] == 0.0) v = 0.0;
+      else if (alpha == 1.0) v = y;
+      else {
+        const double ap = line.applied[k];
+        v = ap + alpha * (y - ap);
+      }
+      a[k] = v;
+      line.applied[k] = v;
+    }
+  line.count = (double)(n + 1);
+}
+
 // Condition matrix of the swing-foot quintic p(t) = sum_k a_k t^k (QuinticCurve::get_foot_swing_target,
 // Utils.cpp:236-293): rows p(0), p(T), p'(0), p'(T), p(T/2), p'(T/2).  Generated, with the reference's FLOAT
 // evaluation order so that every entry carries the same rounding as upstream's hand-written expressions: a power is

@@ -1,11 +1,13 @@
 // qmpc_loop_rec.inc -- the kernels of the closed loop with per-robot records and their launchers, defined once.  Included by
-// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip and qmpc_loop_ground.hip inside the unit's namespace, after
-// qmpc_loop.hip, with
+// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip, qmpc_loop_ground.hip and qmpc_loop_act.hip inside the unit's
+// namespace, after qmpc_loop.hip, with
 //   QMPC_REC_EXT 0   controller and plant records only                          (qmpc_loop_run_instances*)
 //                1   ... and the outcome step after the post step               (qmpc_loop_run_outcomes*)
 //                2   ... whose plant step integrates under timed push windows   (qmpc_loop_run_pushes*)
 //                3   ... under the force the robot's true ground delivers       (qmpc_loop_run_ground*; qmpc_loop_cground.hip: the
 //                    same with QMPC_REC_CONVEX, beside qmpc_loop_crec.hip, which stays at EXT 2)
+//                4   ... through the robot's delay line and actuator lag         (qmpc_loop_run_actuation*; qmpc_loop_cact.hip: the
+//                    same with QMPC_REC_CONVEX; the ground record may be absent)
 // and, for the sibling controller (qmpc_loop_crec.hip; a handle opts in with qmpc_set_convex_records),
 //   QMPC_REC_CONVEX  defined: ConvexMpc's problem -- ConvexModel and the wrench-form body with QMPC_WMODEL WM_CONVEX, the front
 //                    end loop_front_convex_one on qmpc_convex_input records, the world-frame back end with the robot's plant
@@ -18,7 +20,7 @@
 //               around the solve the C entry point launches
 //   persistent  qmpc_loop_rec_fused_kernel<3|5|6>: qmpc_loop_fused_kernel<VAR, false, false, false> (QuatMpc's problem,
 //               converged mode, wrench-form body) with the robot's own controller and plant
-//   launchers   rec_set_lds, rec_fused_launch, rec_front_launch, rec_post_launch: one signature for the three units, the
+//   launchers   rec_set_lds, rec_fused_launch, rec_front_launch, rec_post_launch: one signature for all units, the
 //               arguments beyond the unit's EXT ignored (declared for qmpc_hip.hip by its QMPC_REC_DECLARE)
 #ifdef QMPC_REC_CONVEX
 #define QMPC_REC_MODEL ConvexModel
@@ -27,8 +29,13 @@
 #define QMPC_REC_MODEL QuatModel
 #define QMPC_REC_FRONT(OCC_, LP_, s_, r_) loop_front_one<OCC_>(LP_, s_, r_)
 #endif
-// the post step and, at EXT 3, the two arguments it has beyond the plant block: robot i_'s ground record and tally
-#if QMPC_REC_EXT >= 3
+// the post step and, at EXT 3, the two arguments it has beyond the plant block: robot i_'s ground record and tally; at EXT 4
+// (where there may be no ground record) the robot's actuation record and delay line after them
+#if QMPC_REC_EXT >= 4
+#define QMPC_REC_POST loop_post_actuation_one
+#define QMPC_REC_POST_GROUND(i_) \
+  , ground ? ground + (size_t)(i_) : nullptr, tally ? tally + (size_t)(i_) : nullptr, act + (size_t)(i_), line + (size_t)(i_)
+#elif QMPC_REC_EXT >= 3
 #define QMPC_REC_POST loop_post_ground_one
 #define QMPC_REC_POST_GROUND(i_) , ground + (size_t)(i_), tally ? tally + (size_t)(i_) : nullptr
 #elif defined(QMPC_REC_CONVEX)
@@ -52,6 +59,11 @@
 #define QMPC_REC_GROUND(...) __VA_ARGS__
 #else
 #define QMPC_REC_GROUND(...)
+#endif
+#if QMPC_REC_EXT >= 4
+#define QMPC_REC_ACT(...) __VA_ARGS__
+#else
+#define QMPC_REC_ACT(...)
 #endif
 
 // the trace row of a robot that does not move in this tick
@@ -83,7 +95,96 @@ __device__ inline PlantDev push_plant(const PlantDev& pl, const qmpc_push_params
 }
 #endif
 
-#if QMPC_REC_EXT >= 3
+#if QMPC_REC_EXT >= 4
+// The back end of a tick whose force reaches the feet through the robot's delay line and actuator lag
+// (qmpc_loop_run_actuation*), a sibling of loop_post_ground_one below.  After forces_body holds the tick's command,
+// qmpc_loop::loop_actuation_one pushes it into the line and returns a, the body-frame force the actuators produce.  A robot whose
+// record is the identity then goes through loop_post_ground_one's text as it stands (a is not looked at; the line stays
+// current), so it gets that function's state, bit for bit.  Any other robot forms grf_world = R a (a swing leg: +0.0), the
+// stance legs are clamped as there, a changed leg hands the plant R' f and an unchanged one a.  g may be null: no clamp, the
+// tally untouched.  grf_world holds the delivered force, forces_body and the trace row the command.  act, line, g and tally
+// point into global memory: one ring slot is read, one written and applied read-modify-written here, inside the post step --
+// nothing of the feature is live across the solve, no block is copied, the ring is indexed in global memory.
+template <int OCC = 1>
+QMPC_LOOP_FN void loop_post_actuation_one(const PlantDev& pl, const qmpc_loop_params& LP, qmpc_loop_state& s,
+                                          const double* __restrict__ forces, const qmpc_info& inf, double* __restrict__ trace_f,
+                                          double* __restrict__ trace_c, const qmpc_ground_params* __restrict__ g,
+                                          qmpc_ground_tally* __restrict__ tally, const qmpc_actuation_params* __restrict__ act,
+                                          qmpc_actuation_line* __restrict__ line) {
+#pragma clang fp contract(off)
+  const int status = inf.status;
+  s.status = (double)status;
+  s.iterations = (double)inf.iterations;
+  const bool accepted = status == QMPC_OK || status == QMPC_MAX_ITER;     // (the converged mode only)
+  double R[9];
+  qmpc_loop::quat_to_rot(s.quat, R);
+  int verdict[4] = {0, 0, 0, 0};
+  int any = 0;
+  const bool ident = qmpc_loop::loop_actuation_identity(*act);
+#ifdef QMPC_REC_CONVEX
+  if (accepted)
+    for (int l = 0; l < 4; ++l)
+      for (int r = 0; r < 3; ++r) {
+        s.grf_world[3 * l + r] = forces[3 * l + r];
+        s.forces_body[3 * l + r] = R[r] * forces[3 * l] + R[3 + r] * forces[3 * l + 1] + R[6 + r] * forces[3 * l + 2];
+      }
+#else
+  if (accepted)
+    for (int a = 0; a < 12; ++a) s.forces_body[a] = forces[a];
+#endif
+  double u[12];      // what the plant receives
+  qmpc_loop::loop_actuation_one(*act, *line, s.forces_body, s.contacts, u);
+  if (ident) {
+#ifdef QMPC_REC_CONVEX
+    if (accepted) {
+      if (g) any = qmpc_loop::loop_ground_clamp(*g, s.contacts, s.grf_world, verdict);
+    } else if (g) {
+      double fw[12];
+      for (int l = 0; l < 4; ++l)
+        for (int r = 0; r < 3; ++r)
+          fw[3 * l + r] = R[3 * r] * s.forces_body[3 * l] + R[3 * r + 1] * s.forces_body[3 * l + 1] + R[3 * r + 2] * s.forces_body[3 * l + 2];
+      any = qmpc_loop::loop_ground_clamp(*g, s.contacts, fw, verdict);
+      for (int l = 0; l < 4; ++l)
+        if (verdict[l])
+          for (int r = 0; r < 3; ++r) s.grf_world[3 * l + r] = fw[3 * l + r];
+    }
+#else
+    for (int l = 0; l < 4; ++l)
+      for (int r = 0; r < 3; ++r)
+        s.grf_world[3 * l + r] = R[3 * r] * s.forces_body[3 * l] + R[3 * r + 1] * s.forces_body[3 * l + 1] +
+                                 R[3 * r + 2] * s.forces_body[3 * l + 2];
+    if (g) any = qmpc_loop::loop_ground_clamp(*g, s.contacts, s.grf_world, verdict);
+#endif
+    for (int a = 0; a < 12; ++a) u[a] = s.forces_body[a];
+  } else {
+    for (int l = 0; l < 4; ++l)
+      for (int r = 0; r < 3; ++r)
+        s.grf_world[3 * l + r] = s.contacts[l] == 0.0 ? 0.0
+                                                      : R[3 * r] * u[3 * l] + R[3 * r + 1] * u[3 * l + 1] + R[3 * r + 2] * u[3 * l + 2];
+    if (g) any = qmpc_loop::loop_ground_clamp(*g, s.contacts, s.grf_world, verdict);
+  }
+  if (trace_f) for (int a = 0; a < 12; ++a) trace_f[a] = s.forces_body[a];
+  if (trace_c) for (int a = 0; a < 4; ++a) trace_c[a] = s.contacts[a];
+  for (int l = 0; l < 4; ++l)
+    if (verdict[l]) qmpc_loop::loop_ground_to_body(R, s.grf_world + 3 * l, u + 3 * l);
+  double x[13];
+  for (int a = 0; a < 3; ++a) { x[a] = s.pos_world[a]; x[7 + a] = s.lin_vel_world[a]; x[10 + a] = s.ang_vel_body[a]; }
+  for (int a = 0; a < 4; ++a) x[3 + a] = s.quat[a];
+  qmpc_loop::plant_step_ext(x, u, s.foot_pos_world, 4, pl.mass, pl.Iinv, pl.force, pl.torque, LP.dt);
+  for (int a = 0; a < 3; ++a) { s.pos_world[a] = x[a]; s.lin_vel_world[a] = x[7 + a]; s.ang_vel_body[a] = x[10 + a]; }
+  for (int a = 0; a < 4; ++a) s.quat[a] = x[3 + a];
+  if (s.movement_mode != 0.0)
+    for (int l = 0; l < 4; ++l)
+      if (s.contacts[l] == 0.0)
+        for (int a = 0; a < 3; ++a) s.foot_pos_world[3 * l + a] = s.leg[l].fsm_pos[a];
+  s.tick += 1.0;
+  if (tally && any) {
+    qmpc_ground_tally t = *tally;
+    qmpc_loop::loop_ground_tally_one(verdict, s.tick, t);
+    *tally = t;
+  }
+}
+#elif QMPC_REC_EXT >= 3
 // The back end of a tick on the robot's TRUE ground (qmpc_loop_run_ground*): loop_post_plant_one (QMPC_REC_CONVEX:
 // loop_post_plant_world_one) whose plant step takes the DELIVERED forces.  After grf_world has been formed as there, the stance
 // legs are clamped in the world frame (qmpc_loop::loop_ground_clamp); a changed leg hands the plant R' f, an unchanged one the
@@ -219,7 +320,8 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
     const double* __restrict__ forces, const qmpc_info* __restrict__ info, double* __restrict__ trace_f, double* __restrict__ trace_c,
     const int* __restrict__ row, const PlantDev* __restrict__ pl, QMPC_REC_OUTCOME(qmpc_loop_outcome* __restrict__ oc, )
     QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, )
-    QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, ) int batch) {
+    QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, )
+    QMPC_REC_ACT(const qmpc_actuation_params* __restrict__ act, qmpc_actuation_line* __restrict__ line, ) int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
   const size_t slot = (trace_f || trace_c) ? (size_t)(*row) * batch + i : 0;
@@ -261,6 +363,8 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
 // across the solve (variants 5 / 6 sit at their 256-register limit).
 // EXT 3: lane 0's post step also reads the robot's 64 B ground record and read-modify-writes its 32 B tally, by pointer, in each
 // tick -- the same rule: nothing live across the solve, no block copied.
+// EXT 4: ... and reaches the robot's actuation record and delay line by pointer there: one 96 B ring slot read, one written, the
+// 96 B applied read-modify-written, the ring indexed in global memory with the run-time slot number (no local array, no scratch).
 // (The two zero-fill loops stay written out: as calls of one inline function they compile to other instructions.)
 template <int VAR>
 __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmpc_loop_rec_fused_kernel(
@@ -268,7 +372,8 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
     qmpc_loop_state* __restrict__ st, qmpc_input* __restrict__ rec, double* __restrict__ forces, qmpc_info* __restrict__ info,
     double* __restrict__ trace_f, double* __restrict__ trace_c, QMPC_REC_OUTCOME(qmpc_loop_outcome* __restrict__ outcomes, )
     QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, )
-    QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, ) int ticks, int batch,
+    QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, )
+    QMPC_REC_ACT(const qmpc_actuation_params* __restrict__ act, qmpc_actuation_line* __restrict__ line, ) int ticks, int batch,
     double* __restrict__ gws) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int b = blockIdx.x;
@@ -352,7 +457,27 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
 #endif
 }
 
-#if QMPC_REC_EXT >= 3 && !defined(QMPC_REC_CONVEX)
+#if QMPC_REC_EXT == 4 && !defined(QMPC_REC_CONVEX)
+// ---- the check of the actuation records and delay lines (QuatMpc's unit only: it does not depend on the model) ------------
+// One thread per robot: the verdict of the robot's record and of its line's count into its plant block (a verdict already there
+// stays); the line is read, never written
+__global__ __launch_bounds__(256) void qmpc_act_check_kernel(const qmpc_actuation_params* __restrict__ act,
+                                                             const qmpc_actuation_line* __restrict__ line, PlantDev* __restrict__ pl,
+                                                             int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  if (!qmpc_loop::loop_actuation_valid(act[i], line[i])) pl[i].status = QMPC_BAD_PARAMS;
+}
+
+__attribute__((visibility("hidden"))) hipError_t rec_act_check_launch(hipStream_t s, const qmpc_actuation_params* act,
+                                                                      const qmpc_actuation_line* line, void* plants, int batch) {
+  hipLaunchKernelGGL(qmpc_act_check_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, act, line,
+                     static_cast<PlantDev*>(plants), batch);
+  return hipGetLastError();
+}
+#endif
+
+#if QMPC_REC_EXT == 3 && !defined(QMPC_REC_CONVEX)
 // ---- the check of the ground records (QuatMpc's unit only: it does not depend on the model) -------------------------------
 // One thread per robot: the verdict of the robot's ground record into its plant block (a verdict already there stays)
 __global__ __launch_bounds__(256) void qmpc_ground_check_kernel(const qmpc_ground_params* __restrict__ ground, PlantDev* __restrict__ pl,
@@ -382,12 +507,13 @@ __attribute__((visibility("hidden"))) hipError_t rec_fused_launch(
     int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants, const qmpc_loop_params* lp,
     qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws,
     const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,
-    const qmpc_ground_params* ground, qmpc_ground_tally* tally) {
+    const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line) {
   const int k = qmpc::wform_index(var);
   if (k < 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kRecFused[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks),
                      static_cast<const PlantDev*>(plants), *lp, QMPC_REC_OUTCOME(*op, ) st, rec, forces, info, trace_f, trace_c,
-                     QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, ) ticks, batch, gws);
+                     QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, )
+                     QMPC_REC_ACT(act, line, ) ticks, batch, gws);
   return hipGetLastError();
 }
 
@@ -406,16 +532,18 @@ __attribute__((visibility("hidden"))) hipError_t rec_post_launch(hipStream_t s, 
                                                                  double* trace_c, const int* row, const void* plants, int batch,
                                                                  const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                                                  const qmpc_push_params* push, int per_robot,
-                                                                 const qmpc_ground_params* ground, qmpc_ground_tally* tally) {
+                                                                 const qmpc_ground_params* ground, qmpc_ground_tally* tally,
+                                                                 const qmpc_actuation_params* act, qmpc_actuation_line* line) {
   hipLaunchKernelGGL(qmpc_loop_rec_post_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, *lp, QMPC_REC_OUTCOME(*op, ) st, forces, info,
                      trace_f, trace_c, row, static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, )
-                     QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, ) batch);
+                     QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, ) QMPC_REC_ACT(act, line, ) batch);
   return hipGetLastError();
 }
 
 #undef QMPC_REC_OUTCOME
 #undef QMPC_REC_PUSH
 #undef QMPC_REC_GROUND
+#undef QMPC_REC_ACT
 #undef QMPC_REC_POST_GROUND
 #undef QMPC_REC_EXT
 #undef QMPC_REC_MODEL

@@ -40,6 +40,10 @@ class ClosedLoopHostBase {
   // tally its ticks accumulate into (starts empty; set_ground leaves it)
   virtual void set_ground(const qmpc_ground_params* ground) = 0;
   virtual const qmpc_ground_tally& ground_tally() const = 0;
+  // the robot's actuation record and delay line (qmpc_loop_run_actuation*): both copied (act null: none -- the plant receives
+  // every command in its own tick); the line the ticks advance is read back with actuation_line, to carry it over runs
+  virtual void set_actuation(const qmpc_actuation_params* act, const qmpc_actuation_line* line) = 0;
+  virtual const qmpc_actuation_line& actuation_line() const = 0;
   State state;
 };
 
@@ -106,6 +110,11 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     if (ground) ground_ = *ground;
   }
   const qmpc_ground_tally& ground_tally() const override { return tally_; }
+  void set_actuation(const qmpc_actuation_params* act, const qmpc_actuation_line* line) override {
+    has_act_ = act != nullptr && line != nullptr;
+    if (has_act_) { act_ = *act; line_ = *line; }
+  }
+  const qmpc_actuation_line& actuation_line() const override { return line_; }
   void reset_outcome() {                                    // qmpc_loop_outcome_init
     std::memset(&outcome_, 0, sizeof outcome_);
     outcome_.down_tick = outcome_.first_rejected_tick = -1.0;
@@ -156,7 +165,28 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     double u[12];
     for (int a = 0; a < 12; ++a) u[a] = state.ctrl.optimized_input[a];
     int verdict[4] = {0, 0, 0, 0};
-    if (has_ground_) {   // the device's ground tick (qmpc_loop_math.h: loop_ground_clamp): the stance legs' world-frame forces are
+    bool shaped = false;
+    if (has_act_) {      // the device's actuation tick (qmpc_loop_math.h: loop_actuation_one): the command enters the robot's delay
+                         // line; an identity record goes on as below, any other hands on a, what the actuators produce:
+                         // mpc_grf_world = R a (a swing leg: +0.0), clamped on the ground when there is one
+      double R[9], a[12], c[12], con[4];
+      qmpc_loop::quat_to_rot(&x_[3], R);
+      for (int k = 0; k < 12; ++k) c[k] = state.ctrl.optimized_input[k];
+      for (int l = 0; l < NUM_LEG; ++l) con[l] = state.ctrl.plan_contacts[l] ? 1.0 : 0.0;
+      qmpc_loop::loop_actuation_one(act_, line_, c, con, a);
+      if (!qmpc_loop::loop_actuation_identity(act_)) {
+        shaped = true;
+        double grf[12];
+        for (int l = 0; l < NUM_LEG; ++l)
+          for (int r = 0; r < 3; ++r)
+            grf[3 * l + r] = con[l] == 0.0 ? 0.0 : R[3 * r] * a[3 * l] + R[3 * r + 1] * a[3 * l + 1] + R[3 * r + 2] * a[3 * l + 2];
+        if (has_ground_) qmpc_loop::loop_ground_clamp(ground_, con, grf, verdict);
+        for (int k = 0; k < 12; ++k) { u[k] = a[k]; state.ctrl.mpc_grf_world[k] = grf[k]; }
+        for (int l = 0; l < NUM_LEG; ++l)
+          if (verdict[l]) qmpc_loop::loop_ground_to_body(R, grf + 3 * l, u + 3 * l);
+      }
+    }
+    if (has_ground_ && !shaped) {   // the device's ground tick (qmpc_loop_math.h: loop_ground_clamp): the stance legs' world-frame forces are
                          // clamped, a changed leg hands the plant R' f and mpc_grf_world the delivered force; optimized_input stays
                          // the command
       double R[9], grf[12], con[4];
@@ -170,7 +200,7 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
           for (int a = 0; a < 3; ++a) state.ctrl.mpc_grf_world[3 * l + a] = grf[3 * l + a];
         }
     }
-    if (n_push_ > 0 || has_ground_) {   // the device's push tick: the plant's constant wrench (none without a plant record, on the handle's mass and
+    if (n_push_ > 0 || has_ground_ || has_act_) {   // the device's push tick: the plant's constant wrench (none without a plant record, on the handle's mass and
                          // inverse inertia then) under the windows acting at state.tick = ticks_ (qmpc_loop_math.h: loop_push_wrench)
       double f[3] = {0.0, 0.0, 0.0}, tq[3] = {0.0, 0.0, 0.0};
       if (has_plant_)
@@ -324,6 +354,9 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   qmpc_ground_params ground_;
   bool has_ground_ = false;
   qmpc_ground_tally tally_ = {0.0, -1.0, 0.0, 0.0};      // qmpc_ground_tally_init
+  qmpc_actuation_params act_;
+  qmpc_actuation_line line_ = {};                        // qmpc_actuation_line_init with no initial force
+  bool has_act_ = false;
   long ticks_ = 0;
 };
 

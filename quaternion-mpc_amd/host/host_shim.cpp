@@ -269,6 +269,11 @@ void qh_loop_set_pushes(void* p, const qmpc_push_params* push, int n) { static_c
 // ... and its true ground (qmpc_loop_run_ground*; null: none) with the tally its ticks accumulate
 void qh_loop_set_ground(void* p, const qmpc_ground_params* ground) { static_cast<LoopHarness*>(p)->loop->set_ground(ground); }
 void qh_loop_ground_tally(void* p, qmpc_ground_tally* out) { *out = static_cast<LoopHarness*>(p)->loop->ground_tally(); }
+// ... and its actuation record with the delay line its ticks advance (qmpc_loop_run_actuation*; act null: none)
+void qh_loop_set_actuation(void* p, const qmpc_actuation_params* act, const qmpc_actuation_line* line) {
+  static_cast<LoopHarness*>(p)->loop->set_actuation(act, line);
+}
+void qh_loop_actuation_line(void* p, qmpc_actuation_line* out) { *out = static_cast<LoopHarness*>(p)->loop->actuation_line(); }
 void qh_loop_destroy(void* p) {
   LoopHarness* h = static_cast<LoopHarness*>(p);
   if (!h) return;

@@ -333,3 +333,17 @@ def random_go1_grounds(batch: int, seed: int = 0, first: int = 0, mu=(0.1, 0.9),
     if fz_max is not None:
         rec["fz_max"] = (fz_max[0] + (fz_max[1] - fz_max[0]) * u[:, 1])[:, None]
     return rec
+
+
+def random_go1_actuations(batch: int, seed: int = 0, first: int = 0, delay=(0, 4), tau=None, dt: float = 0.005) -> np.ndarray:
+    """`batch` actuation records (``struct qmpc_actuation_params``, for Solver.loop_run_actuation), robot indices first ..
+    first+batch-1, the counter-based generator of random_go1_pushes (a shard equals its block of the whole): one delay per robot,
+    an integer uniform on delay[0] .. delay[1] ticks, and -- with tau = (lo, hi) -- one actuator time constant U(tau) seconds per
+    robot, sampled at the tick dt (None: no lag, alpha = 1).  Two uniforms per robot, in the order delay, tau."""
+    from . import actuation_params
+
+    idx = np.arange(first, first + batch, dtype=np.uint64)
+    u = _uniform(0x5EED5000 + int(seed), idx, 2)
+    d = np.minimum(np.floor(delay[0] + (delay[1] - delay[0] + 1) * u[:, 0]), delay[1])
+    t = None if tau is None else tau[0] + (tau[1] - tau[0]) * u[:, 1]
+    return actuation_params(batch, delay_ticks=d, tau=t, dt=dt)

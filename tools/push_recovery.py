@@ -5,7 +5,7 @@ still up per cell from the outcome records.  The robots of a cell differ in thei
 inertia); the controller is the handle's and is not told about the push.
     python tools/push_recovery.py [--impulses 2,4,6,8,10] [--starts 13] [--length 10] [--per-cell 8] [--speed 0.3] [--settle 60]
                                   [--recover 200] [--horizon 10] [--controller quat|convex|both] [--ctrl-records] [--warm] [--json FILE]
-                                  [--mu-true LO HI [--mu-steps 5]]
+                                  [--mu-true LO HI [--mu-steps 5]] [--delay LO HI] [--tau LO HI [--tau-steps 3]]
 Every robot stands for 6 ticks, trots at --speed for --settle ticks, is shoved at tick 6 + settle + start for --length ticks with
 force impulse / (length dt) in its cell's direction (0 degrees: ahead, 90: to its left), and trots on until --recover ticks after
 the last start.  Down: below 0.15 m or tilted beyond 60 degrees (qmpc_default_outcome_params); stop_when_down halts a fallen robot.
@@ -16,6 +16,10 @@ plants and commands under each controller, one summary per controller.  --horizo
 --mu-true LO HI: the true-friction axis.  The grid is repeated on --mu-steps grounds whose Coulomb coefficient runs from LO to HI
 (qmpc_loop_run_ground: the plant delivers what that ground allows, the controller keeps assuming its own mu), and a table of falls
 per (impulse, mu_true) cell with the ground tallies is printed after the tables above, which then pool the grounds.
+--delay LO HI, --tau LO HI: the time axes.  The grid is repeated for every actuation delay of LO .. HI ticks (integers, at most 8) and
+for --tau-steps actuator time constants from LO to HI seconds (qmpc_loop_run_actuation: the plant receives the command of `delay`
+ticks ago through a first-order lag, alpha = 1 - exp(-dt / tau); the controller is not told; the delay lines start from the stand
+force m g / 4 per leg), and a table of falls per (impulse, delay, tau) cell is printed after the tables above, which then pool them.
 --ctrl-records: every robot also carries a controller record (the handle's values: the same controller) and the handle takes
 QMPC_INSTANCES_AUTO, a ConvexMpc handle with qmpc_set_convex_lane_records as well -- the launch a sweep over per-robot controllers
 takes: from the switch-over on the lane kernel with per-lane parameters under either controller.
@@ -59,6 +63,9 @@ def main():
     ap.add_argument("--warm", action="store_true")
     ap.add_argument("--mu-true", type=float, nargs=2, default=None, metavar=("LO", "HI"))
     ap.add_argument("--mu-steps", type=int, default=5)
+    ap.add_argument("--delay", type=int, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--tau", type=float, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--tau-steps", type=int, default=3)
     a = ap.parse_args()
     pkg = load_pkg()
     lib = pkg.load_library()
@@ -74,8 +81,13 @@ def run(a, pkg, lib, controller):
     angles = np.arange(8) * (np.pi / 4)
     # the grid, robot index = ((impulse, start, direction), member of the cell)
     mus = np.linspace(a.mu_true[0], a.mu_true[1], a.mu_steps) if a.mu_true else np.array([np.inf])
-    gi, gs, gd, gm, _ = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8), np.arange(len(mus)),
-                                                        np.arange(a.per_cell), indexing="ij"))
+    delays = np.arange(a.delay[0], a.delay[1] + 1) if a.delay else np.array([0])
+    taus = np.linspace(a.tau[0], a.tau[1], a.tau_steps) if a.tau else np.array([0.0])
+    timed = bool(a.delay or a.tau)
+    gi, gs, gd, gm, gl, gt, _ = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8),
+                                                                np.arange(len(mus)), np.arange(len(delays)), np.arange(len(taus)),
+                                                                np.arange(a.per_cell), indexing="ij"))
+    members = len(mus) * len(delays) * len(taus) * a.per_cell
     B = gi.size
     convex = controller == "convex"
     p = (pkg.default_convex_params if convex else pkg.default_params)(a.horizon, pkg.MODE_CONVERGED, lib)
@@ -99,6 +111,10 @@ def run(a, pkg, lib, controller):
     mag = np.asarray(impulses)[gi] / (a.length * lp.dt)
     push["force_world"][:, 0, 0] = mag * np.cos(angles[gd])
     push["force_world"][:, 0, 1] = mag * np.sin(angles[gd])
+    act = line = None
+    if timed:
+        act = pkg.actuation_params(B, delay_ticks=delays[gl], tau=taus[gt], dt=lp.dt)
+        line = pkg.actuation_lines(B, pkg.stand_forces_body(p.mass))
     op = pkg.default_outcome_params(lib, stop_when_down=True)
     s = pkg.Solver(p, B, device=0, lib=lib)
     if convex:
@@ -114,15 +130,16 @@ def run(a, pkg, lib, controller):
     form = s.loop_instances_plan(B, ctrl is not None, a.warm)
     total = a.settle + PERIOD + a.recover
     w0 = time.perf_counter()
-    st, oc, ta = s.loop_run_ground(st, 6, ground, push, lp, ctrl=ctrl, plant=plant, op=op)      # (ground = None: the push call)
+    # (act = None: the ground call; ground = None: the push call)
+    st, oc, ta, line = s.loop_run_actuation(st, 6, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op)
     st["movement_mode"] = 1.0
-    st, oc, ta = s.loop_run_ground(st, total, ground, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc, tallies=ta)
+    st, oc, ta, line = s.loop_run_actuation(st, total, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc, tallies=ta)
     wall = time.perf_counter() - w0
     s.close()
-    up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, len(mus) * a.per_cell)
+    up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, members)
     share = up.mean(axis=3)
     fell_before = int(((oc["down_tick"] >= 0) & (oc["down_tick"] <= push["start_tick"][:, 0])).sum())
-    print(f"push recovery under {'ConvexMpc' if convex else 'QuatMpc'}: {B} robots ({len(impulses)} impulses x {len(starts)} start ticks x 8 directions x {len(mus) * a.per_cell} plants), N={a.horizon}, "
+    print(f"push recovery under {'ConvexMpc' if convex else 'QuatMpc'}: {B} robots ({len(impulses)} impulses x {len(starts)} start ticks x 8 directions x {members} plants), N={a.horizon}, "
           f"trot at {a.speed} m/s, shove of {a.length:g} ticks from tick {t0} + start, {6 + total} ticks in all, launch {form}, "
           f"{wall:.2f} s wall with the copies; {fell_before} robots were down before their shove began")
     print(f"solves: {pkg.summarize_outcomes(oc)['mean_iterations']:.2f} iterations on average, "
@@ -138,7 +155,7 @@ def run(a, pkg, lib, controller):
           "  ".join(f"{imp:g} N s: {share[i].mean():.3f}" for i, imp in enumerate(impulses)) + f"   all: {share.mean():.3f}\n")
     by_mu = None
     if a.mu_true:
-        shape = (len(impulses), len(starts), 8, len(mus), a.per_cell)
+        shape = (len(impulses), len(starts), 8, len(mus), len(delays) * len(taus) * a.per_cell)
         down = (oc["down_tick"] >= 0).reshape(shape)
         cell = down.shape[1] * down.shape[2] * down.shape[4]
         print(f"true friction: robots down per (impulse, mu_true) cell, of {cell} (the controller assumes mu = {p.mu:g})")
@@ -153,8 +170,24 @@ def run(a, pkg, lib, controller):
         print(f"{'never clipped':>20s} " + " ".join(f"{int((first[:, :, :, m] < 0).sum()):8d}" for m in range(len(mus))) + "\n")
         by_mu = {"mu_true": mus.tolist(), "down": down.sum(axis=(1, 2, 4)).tolist(), "cell": cell,
                  "clipped_ticks_mean": ta["clipped_ticks"].reshape(shape).mean(axis=(0, 1, 2, 4)).tolist()}
-    return {"controller": controller, "by_mu_true": by_mu, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
-            "per_cell": len(mus) * a.per_cell, "length_ticks": a.length, "speed": a.speed, "form": form, "share_up": share.tolist()}
+    by_time = None
+    if timed:
+        shape = (len(impulses), len(starts), 8, len(mus), len(delays), len(taus), a.per_cell)
+        down = (oc["down_tick"] >= 0).reshape(shape)
+        cell = down[0, :, :, :, 0, 0].size
+        alphas = pkg.actuation_params(len(taus), tau=taus, dt=lp.dt)["alpha"]
+        print(f"actuation: robots down per (impulse, delay, tau) cell, of {cell}; delay in ticks of {lp.dt * 1e3:g} ms, tau in ms (alpha)")
+        print("impulse delay " + " ".join(f"tau={1e3 * t:4.1f} ({al:.3f})" for t, al in zip(taus, alphas)))
+        for i, imp in enumerate(impulses):
+            for l, d in enumerate(delays):
+                print(f"{imp:5g}   {int(d):5d} " + " ".join(f"{int(down[i, :, :, :, l, t].sum()):16d}" for t in range(len(taus))))
+        before = ((oc["down_tick"] >= 0) & (oc["down_tick"] <= push["start_tick"][:, 0])).reshape(shape)
+        print("  ... of them down before their shove began, by delay: " +
+              " ".join(f"{int(d)}: {int(before[:, :, :, :, l].sum())}" for l, d in enumerate(delays)) + "\n")
+        by_time = {"delay_ticks": delays.tolist(), "tau_s": taus.tolist(), "alpha": alphas.tolist(), "cell": cell,
+                   "down": down.sum(axis=(1, 2, 3, 6)).tolist()}
+    return {"controller": controller, "by_mu_true": by_mu, "by_actuation": by_time, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
+            "per_cell": members, "length_ticks": a.length, "speed": a.speed, "form": form, "share_up": share.tolist()}
 
 
 if __name__ == "__main__":
