@@ -1055,6 +1055,80 @@ qmpc_status qmpc_loop_run_actuation_device(qmpc_handle* h, const qmpc_loop_param
                                            const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
                                            const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line, void* stream);
 
+/* ---- state-estimate bias and noise per robot (what the controller reads is not what the plant is) -----------------------
+ * In every loop above the controller reads the plant's true state to the last bit.  qmpc_loop_run_sensing* is
+ * qmpc_loop_run_actuation* -- the same robots, launch forms (QMPC_QUERY_LOOP_INSTANCES_PLAN answers for it too), refusals,
+ * ticks = 0 behaviour, freezing, halting, ConvexMpc and warm-record opt-ins -- whose controller reads a MEASURED state: the
+ * true pos_world, quat, lin_vel_world and ang_vel_body plus a per-robot bias and per-robot, per-tick, reproducible bounded
+ * noise.  The plant, the outcome record, pushes, ground and actuation keep working on the truth.
+ *
+ * The rule (loop_sense_one, csrc/qmpc_loop_math.h: one source for the device, the host class and the tests), in the front
+ * end of the tick that starts at t = (uint64) state.tick:
+ *   noise    for channel c in 0 .. 11:  z = mix(seed + 0x9E3779B97F4A7C15 * (12 t + c + 1)), wrapping in 64 bits, mix the
+ *            splitmix64 finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *            z ^= z >> 31);  S = the sum of the four 16-bit fields of z;  n = (double)(int)(S - 131070) * 0x1.bb67ae86627e7p-16
+ *            (the constant is 1 / sqrt((2^32 - 1) / 3)).  n is an Irwin-Hall(4) variate: mean 0, variance 1, close to a normal
+ *            one in the middle and BOUNDED by +-3.4641 (2 sqrt 3) -- for a robustness sweep the bound is a feature: no run is
+ *            decided by one sample from a far tail.  Integer-only up to one conversion and one multiply: no libm call, the same
+ *            bits everywhere.  It is keyed on state.tick, not on the call: a run split over calls draws the same noise.
+ *   error    e_c = bias[c] + sigma[c] * n_c.  A channel with sigma == 0 evaluates no hash (e_c = bias[c]); a channel with
+ *            bias == 0 and sigma == 0 is inactive: it contributes no arithmetic, its field is copied as bytes.
+ *   measure  position, velocity, body rate: m = x + e.  Attitude, if any of channels 3-5 is active: q_m = normalize(q (x)
+ *            (1, phi / 2)), phi = e_3..5 (an inactive channel's entry 0), scalar first, Hamilton product with its terms summed
+ *            left to right, the norm the sqrt of the four squares summed left to right, then four divisions.  That rotates by
+ *            2 atan(|phi| / 2) about phi in the body frame -- |phi| to within |phi|^3 / 12 -- without sin or cos.  Otherwise
+ *            the quaternion is copied as bytes.
+ * foot_pos_world and the contact flags are not touched (the stance feet are what leg odometry anchors on, the flags come from
+ * the feet): the controller's foot_pos_body becomes R_m' (foot - p_m).
+ *
+ * A robot whose record is the identity (all of bias and sigma zero; seed ignored) runs the front end as it stands; its seen
+ * is untouched.  Any other robot saves the 13 true doubles, writes the measured ones into the state, runs the front end
+ * unchanged, restores the 13 true doubles as bytes and writes seen when given.  Nothing else in the tick changes: the post step
+ * (grf_world = R forces_body with the TRUE R), the plant, the outcome record, the ground clamp and the delay line see the truth.
+ * Frozen and halted robots leave seen untouched.
+ *
+ * sense == NULL: the call IS qmpc_loop_run_actuation* and seen is not touched.  act may be NULL with sense given (line is then
+ * ignored): every command reaches the plant in its own tick.  A record with a non-finite field, a sigma < 0 or a seed that is
+ * not an integer in [0, 2^53) makes its robot the robot of an invalid plant record (QMPC_BAD_PARAMS, marked by a check kernel
+ * before the first tick; every other robot unaffected bit for bit).  Buffers: those of the actuation call; the device call reads
+ * d_sense and works on d_seen in place; the host-buffer call stages records and seen in a buffer of its own ((256 + 128) B x
+ * max_batch), allocated on its first use -- a call with ticks = 0 included.  No other call allocates it. */
+typedef struct qmpc_sense_params {   /* 32 doubles, 256 B: what robot i's estimator gets wrong */
+  double bias[12];     /* channels 0-2 pos_world [m], 3-5 attitude error phi, body frame [rad],
+                          6-8 lin_vel_world [m/s], 9-11 ang_vel_body [rad/s] (gyro bias) */
+  double sigma[12];    /* standard deviation of the per-tick noise on the same channels, >= 0 */
+  double seed;         /* integer-valued, 0 .. 2^53 - 1 */
+  double reserved[7];  /* 0 */
+} qmpc_sense_params;
+typedef struct qmpc_sense_seen {     /* 16 doubles, 128 B; in/out, may be NULL */
+  double meas[13];     /* pos[3] quat[4] lin_vel_world[3] ang_vel_body[3] the controller read in the robot's last tick */
+  double ticks;        /* ticks in which a non-identity measurement was formed; accumulates over calls */
+  double reserved[2];
+} qmpc_sense_seen;
+/* Host-side; every byte is written: the identity record (all zero), an empty seen (all zero) */
+void    qmpc_sense_params_init(qmpc_sense_params* sense, int32_t batch);
+void    qmpc_sense_seen_init(qmpc_sense_seen* seen, int32_t batch);
+int32_t qmpc_sizeof_sense_params(void);
+int32_t qmpc_sizeof_sense_seen(void);
+/* Host buffers: qmpc_loop_run_actuation's arguments, then sense [batch] and seen [batch] in/out (or NULL).  Synchronous. */
+qmpc_status qmpc_loop_run_sensing(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                  int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant,
+                                  double* trace_forces, double* trace_contacts, const qmpc_outcome_params* op,
+                                  qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int32_t pushes_per_robot,
+                                  const qmpc_ground_params* ground, qmpc_ground_tally* tally,
+                                  const qmpc_actuation_params* act, qmpc_actuation_line* line,
+                                  const qmpc_sense_params* sense, qmpc_sense_seen* seen);
+/* Device buffers (op is a host pointer, read during the call), stream-ordered (NULL stream = the handle's). */
+qmpc_status qmpc_loop_run_sensing_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch,
+                                         qmpc_loop_state* d_states, int32_t ticks,
+                                         const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                         double* d_trace_forces, double* d_trace_contacts,
+                                         const qmpc_outcome_params* op, qmpc_loop_outcome* d_outcomes,
+                                         const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                         const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
+                                         const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
+                                         const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, void* stream);
+
 /* Stand-pose joint angles (0, 0.67, -1.3 per leg: the reference's Gazebo start pose) for `batch`
  * robots, host buffer [batch][12]. */
 void qmpc_loop_joint_init(double* joint_pos, int32_t batch);

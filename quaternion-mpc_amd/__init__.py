@@ -352,6 +352,37 @@ def actuation_lines(batch: int, initial=None) -> np.ndarray:
     return out
 
 
+# struct qmpc_sense_params (qmpc_loop_run_sensing*): what one robot's state estimator gets wrong, 32 doubles = 256 B.  Channels
+# 0-2 pos_world [m], 3-5 attitude error phi in the body frame [rad], 6-8 lin_vel_world [m/s], 9-11 ang_vel_body [rad/s]
+SENSE_PARAMS_DTYPE = np.dtype([("bias", "<f8", (12,)), ("sigma", "<f8", (12,)), ("seed", "<f8"), ("reserved", "<f8", (7,))], align=False)
+# struct qmpc_sense_seen: what the controller read in the robot's last tick, 16 doubles = 128 B (in/out: ticks accumulates)
+SENSE_SEEN_DTYPE = np.dtype([("meas", "<f8", (13,)), ("ticks", "<f8"), ("reserved", "<f8", (2,))], align=False)
+assert SENSE_PARAMS_DTYPE.itemsize == 32 * 8 and SENSE_SEEN_DTYPE.itemsize == 16 * 8
+SENSE_GROUPS = {"pos": slice(0, 3), "att": slice(3, 6), "vel": slice(6, 9), "gyro": slice(9, 12)}
+
+
+def sense_params(batch: int, seed=0, pos_bias=0.0, att_bias=0.0, vel_bias=0.0, gyro_bias=0.0, pos_noise=0.0, att_noise=0.0,
+                 vel_noise=0.0, gyro_noise=0.0) -> np.ndarray:
+    """[batch] sensing records: the controller reads the true state plus a bias and per-tick noise of standard deviation *_noise
+    on position [m], attitude (a rotation vector in the body frame [rad]), world-frame velocity [m/s] and body rate [rad/s] (the
+    gyro bias).  Every argument is a scalar, a 3-vector or [batch, 3] (a scalar applies to the three axes); seed an integer in
+    0 .. 2^53 - 1 or one per robot -- robots that share a seed draw the same noise.  The defaults give the bytes of
+    qmpc_sense_params_init."""
+    B = int(batch)
+    out = np.zeros(B, dtype=SENSE_PARAMS_DTYPE)
+    out["seed"] = seed
+    for key, b, n in (("pos", pos_bias, pos_noise), ("att", att_bias, att_noise), ("vel", vel_bias, vel_noise),
+                      ("gyro", gyro_bias, gyro_noise)):
+        for field, v in (("bias", b), ("sigma", n)):
+            out[field][:, SENSE_GROUPS[key]] = np.broadcast_to(np.asarray(v, dtype=np.float64), (B, 3))
+    return out
+
+
+def sense_seen(batch: int) -> np.ndarray:
+    """[batch] empty seen records: all zero, the bytes of qmpc_sense_seen_init."""
+    return np.zeros(int(batch), dtype=SENSE_SEEN_DTYPE)
+
+
 # struct qmpc_info: 2 x int32 + 4 doubles = 40 B
 INFO_DTYPE = np.dtype(
     [
@@ -474,6 +505,16 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_actuation_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
                                                    i32, vp, vp, vp, vp, vp]
     lib.qmpc_loop_run_actuation_device.restype = i32
+    lib.qmpc_sense_params_init.argtypes = [vp, i32]
+    lib.qmpc_sense_params_init.restype = None
+    lib.qmpc_sense_seen_init.argtypes = [vp, i32]
+    lib.qmpc_sense_seen_init.restype = None
+    lib.qmpc_loop_run_sensing.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp,
+                                          vp, vp, vp, vp]
+    lib.qmpc_loop_run_sensing.restype = i32
+    lib.qmpc_loop_run_sensing_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
+                                                 i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.qmpc_loop_run_sensing_device.restype = i32
     lib.qmpc_set_instances_policy.argtypes = [vp, i32]
     lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_set_loop_warm_records.argtypes = [vp, i32]
@@ -555,7 +596,7 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     for name in ("qmpc_sizeof_input", "qmpc_sizeof_params", "qmpc_sizeof_info", "qmpc_sizeof_convex_input",
                  "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params", "qmpc_sizeof_plant_params",
                  "qmpc_sizeof_loop_outcome", "qmpc_sizeof_push_params", "qmpc_sizeof_ground_params", "qmpc_sizeof_ground_tally",
-                 "qmpc_sizeof_actuation_params", "qmpc_sizeof_actuation_line"):
+                 "qmpc_sizeof_actuation_params", "qmpc_sizeof_actuation_line", "qmpc_sizeof_sense_params", "qmpc_sizeof_sense_seen"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = i32
     if lib.qmpc_sizeof_input() != INPUT_DTYPE.itemsize:
@@ -583,6 +624,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if (lib.qmpc_sizeof_actuation_params() != ACTUATION_PARAMS_DTYPE.itemsize
             or lib.qmpc_sizeof_actuation_line() != ACTUATION_LINE_DTYPE.itemsize):
         raise RuntimeError("qmpc_actuation_params / qmpc_actuation_line ABI size mismatch")
+    if lib.qmpc_sizeof_sense_params() != SENSE_PARAMS_DTYPE.itemsize or lib.qmpc_sizeof_sense_seen() != SENSE_SEEN_DTYPE.itemsize:
+        raise RuntimeError("qmpc_sense_params / qmpc_sense_seen ABI size mismatch")
     return lib
 
 
@@ -676,6 +719,12 @@ EXPORTED_SYMBOLS = (
     "qmpc_sizeof_actuation_line",
     "qmpc_loop_run_actuation",
     "qmpc_loop_run_actuation_device",
+    "qmpc_sense_params_init",
+    "qmpc_sense_seen_init",
+    "qmpc_sizeof_sense_params",
+    "qmpc_sizeof_sense_seen",
+    "qmpc_loop_run_sensing",
+    "qmpc_loop_run_sensing_device",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
@@ -1235,6 +1284,74 @@ class Solver:
         if rc != OK:
             raise QmpcError(rc, "qmpc_loop_run_actuation_device")
 
+    def loop_run_sensing(self, states: np.ndarray, ticks: int, sense: np.ndarray | None, seen: np.ndarray | None = None,
+                         act: np.ndarray | None = None, lines: np.ndarray | None = None, ground: np.ndarray | None = None,
+                         push: np.ndarray | None = None, lp: LoopParams | None = None, ctrl: np.ndarray | None = None,
+                         plant: np.ndarray | None = None, op: OutcomeParams | None = None, outcomes: np.ndarray | None = None,
+                         tallies: np.ndarray | None = None, trace: bool = False, want_seen: bool = True):
+        """qmpc_loop_run_sensing: loop_run_actuation whose controller reads each robot's MEASURED state -- the true one plus the
+        record's bias and reproducible bounded noise -- while plant, outcome record, pushes, ground and actuation work on the
+        truth.  sense: [B] SENSE_PARAMS_DTYPE records, sense_params(); None: exactly loop_run_actuation (seen comes back as
+        given).  seen: the SENSE_SEEN_DTYPE records to go on from (None: sense_seen(B)); want_seen=False passes NULL.  act may be
+        None (every command acts in its own tick; the lines come back as given), ground may be None (no clamp).  Returns (states,
+        outcomes, tallies, lines, seen[, forces, contacts]); the arguments are not modified."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
+        B = st.shape[0]
+
+        def records(a, dtype, name, copy=False):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.shape != (B,):
+                raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
+            return a.copy() if copy else a
+
+        ctrl = records(ctrl, INSTANCE_PARAMS_DTYPE, "ctrl")
+        plant = records(plant, PLANT_PARAMS_DTYPE, "plant")
+        ground = records(ground, GROUND_PARAMS_DTYPE, "ground")
+        act = records(act, ACTUATION_PARAMS_DTYPE, "act")
+        sense = records(sense, SENSE_PARAMS_DTYPE, "sense")
+        per_robot = 0
+        if push is not None:
+            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
+            if push.ndim == 1:
+                push = push.reshape(-1, 1)
+            if push.ndim != 2 or push.shape[0] != B:
+                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
+            per_robot = push.shape[1]
+            if per_robot == 0:
+                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
+        oc = loop_outcomes(B, self.lib) if outcomes is None else records(outcomes, LOOP_OUTCOME_DTYPE, "outcomes", copy=True)
+        ta = ground_tallies(B) if tallies is None else records(tallies, GROUND_TALLY_DTYPE, "tallies", copy=True)
+        li = actuation_lines(B) if lines is None else records(lines, ACTUATION_LINE_DTYPE, "lines", copy=True)
+        sn = sense_seen(B) if seen is None else records(seen, SENSE_SEEN_DTYPE, "seen", copy=True)
+        tf = np.zeros((ticks, B, 12)) if trace else None
+        tc = np.zeros((ticks, B, 4)) if trace else None
+        rc = self.lib.qmpc_loop_run_sensing(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
+                                            C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta), _ptr(act),
+                                            _ptr(li), _ptr(sense), _ptr(sn) if want_seen else None)
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_sensing")
+        return (st, oc, ta, li, sn, tf, tc) if trace else (st, oc, ta, li, sn)
+
+    def loop_run_sensing_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_sense: int, d_seen: int = 0,
+                                d_act: int = 0, d_line: int = 0, d_ground: int = 0, d_tally: int = 0, d_push: int = 0,
+                                pushes_per_robot: int = 0, lp: LoopParams | None = None, op: OutcomeParams | None = None,
+                                d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_sensing_device: device pointers (ints; 0 = NULL), stream-ordered; d_sense, d_act, d_ground and d_push are
+        read in place, d_seen (or 0), d_line and d_tally (or 0) are read and written."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        rc = self.lib.qmpc_loop_run_sensing_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
+                                                   p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
+                                                   int(pushes_per_robot), p(d_ground), p(d_tally), p(d_act), p(d_line), p(d_sense),
+                                                   p(d_seen), p(stream))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_sensing_device")
+
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
         as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN).  Answers under the handle's
@@ -1547,5 +1664,5 @@ class Solver:
 
 from .scenarios import (go1_stand_input, quat_to_rot, random_go1_trot_states,  # noqa: E402,F401
                         random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_convex_variants, random_go1_plants,
-                        random_go1_pushes, random_go1_grounds, random_go1_actuations)
+                        random_go1_pushes, random_go1_grounds, random_go1_actuations, random_go1_senses)
 from .sharding import StepPipeline, gather_forces, shard_range, solve_sharded  # noqa: E402,F401

@@ -355,6 +355,77 @@ QMPC_HD void loop_actuation_one(const qmpc_actuation_params& p, qmpc_actuation_l
   line.count = (double)(n + 1);
 }
 
+// What the controller reads instead of the plant's state (qmpc_loop_run_sensing*, include/qmpc.h): a record is the identity
+// when all of bias and sigma are zero (either sign; the seed is not looked at) -- its robot takes the front end as it stands
+QMPC_HD bool loop_sense_identity(const qmpc_sense_params& p) {
+  bool id = true;
+  for (int c = 0; c < 12; ++c) id = id && p.bias[c] == 0.0 && p.sigma[c] == 0.0;
+  return id;
+}
+
+// ... and is valid when every field is finite (a NaN fails every comparison; x - x is 0 only for a finite x), no sigma is
+// negative and the seed is an integer in [0, 2^53).  The robot of an invalid one is frozen like that of an invalid plant record.
+QMPC_HD bool loop_sense_valid(const qmpc_sense_params& p) {
+  QMPC_NO_CONTRACT
+  bool ok = true;
+  for (int c = 0; c < 12; ++c) ok = ok && (p.bias[c] - p.bias[c] == 0.0) && (p.sigma[c] - p.sigma[c] == 0.0) && p.sigma[c] >= 0.0;
+  for (int c = 0; c < 7; ++c) ok = ok && (p.reserved[c] - p.reserved[c] == 0.0);
+  const double sd = p.seed;
+  ok = ok && sd >= 0.0 && sd < 9007199254740992.0 && sd == (double)(long long)sd;
+  return ok;
+}
+
+// S of channel c in the tick that starts at t, for an integer seed: the sum of the four 16-bit fields of
+// mix(seed + 0x9E3779B97F4A7C15 * (12 t + c + 1)), mix the splitmix64 finaliser; 64-bit wrapping integer arithmetic only
+QMPC_HD unsigned loop_sense_sum(unsigned long long seed, unsigned long long t, int c) {
+  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (12ull * t + (unsigned long long)c + 1ull);
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (unsigned)(z & 0xFFFFull) + (unsigned)((z >> 16) & 0xFFFFull) + (unsigned)((z >> 32) & 0xFFFFull) + (unsigned)(z >> 48);
+}
+
+// ... and n of it: an Irwin-Hall(4) variate, mean 0, variance 1, |n| <= 131070 / sqrt((2^32 - 1) / 3) = 3.4641 (2 sqrt 3) --
+// bounded on purpose.  One conversion and one multiply by 1 / sqrt((2^32 - 1) / 3): no libm, the same bits on every side.
+QMPC_HD double loop_sense_noise(unsigned long long seed, unsigned long long t, int c) {
+  QMPC_NO_CONTRACT
+  return (double)(int)(loop_sense_sum(seed, t, c) - 131070u) * 0x1.bb67ae86627e7p-16;
+}
+
+// One tick's measurement (the rule of include/qmpc.h in full): x (13) = pos_world[3] quat[4] lin_vel_world[3] ang_vel_body[3]
+// of the true state, tick = state.tick, m (13) receives what the controller reads.  Per channel e = bias + sigma * n, the
+// hash evaluated only where sigma != 0; a channel with bias == 0 and sigma == 0 copies its field as bytes.  Position, velocity
+// and body rate: m = x + e.  Attitude, when one of channels 3-5 is active: q_m = normalize(q (x) (1, phi / 2)), scalar first,
+// the norm written as the front end writes quat_d's (sqrt of the four squares summed left to right, four divisions): a
+// rotation by 2 atan(|phi| / 2) about phi, no sin / cos; otherwise the quaternion is copied as bytes.  p must be valid
+// (loop_sense_valid).  x and m must not overlap.
+QMPC_HD void loop_sense_one(const qmpc_sense_params& p, double tick, const double* x, double* m) {
+  QMPC_NO_CONTRACT
+  const unsigned long long seed = (unsigned long long)(long long)p.seed, t = (unsigned long long)(long long)tick;
+  double e[12];
+  bool on[12];
+  for (int c = 0; c < 12; ++c) {
+    on[c] = !(p.bias[c] == 0.0 && p.sigma[c] == 0.0);
+    e[c] = 0.0;
+    if (on[c]) e[c] = p.sigma[c] == 0.0 ? p.bias[c] : p.bias[c] + p.sigma[c] * loop_sense_noise(seed, t, c);
+  }
+  for (int a = 0; a < 3; ++a) {
+    m[a] = on[a] ? x[a] + e[a] : x[a];
+    m[7 + a] = on[6 + a] ? x[7 + a] + e[6 + a] : x[7 + a];
+    m[10 + a] = on[9 + a] ? x[10 + a] + e[9 + a] : x[10 + a];
+  }
+  if (on[3] || on[4] || on[5]) {
+    const double w = x[3], qx = x[4], qy = x[5], qz = x[6];
+    const double a = 0.5 * e[3], b = 0.5 * e[4], c = 0.5 * e[5];
+    double q[4] = {w - qx * a - qy * b - qz * c, w * a + qx + qy * c - qz * b, w * b - qx * c + qy + qz * a,
+                   w * c + qx * b - qy * a + qz};
+    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int k = 0; k < 4; ++k) m[3 + k] = q[k] / n;
+  } else {
+    for (int k = 0; k < 4; ++k) m[3 + k] = x[3 + k];
+  }
+}
+
 // Condition matrix of the swing-foot quintic p(t) = sum_k a_k t^k (QuinticCurve::get_foot_swing_target,
 // Utils.cpp:236-293): rows p(0), p(T), p'(0), p'(T), p(T/2), p'(T/2).  Generated, with the reference's FLOAT
 // evaluation order so that every entry carries the same rounding as upstream's hand-written expressions: a power is

@@ -1,6 +1,6 @@
 // qmpc_loop_rec.inc -- the kernels of the closed loop with per-robot records and their launchers, defined once.  Included by
-// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip, qmpc_loop_ground.hip and qmpc_loop_act.hip inside the unit's
-// namespace, after qmpc_loop.hip, with
+// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip, qmpc_loop_ground.hip, qmpc_loop_act.hip and qmpc_loop_sense.hip
+// inside the unit's namespace, after qmpc_loop.hip, with
 //   QMPC_REC_EXT 0   controller and plant records only                          (qmpc_loop_run_instances*)
 //                1   ... and the outcome step after the post step               (qmpc_loop_run_outcomes*)
 //                2   ... whose plant step integrates under timed push windows   (qmpc_loop_run_pushes*)
@@ -8,6 +8,8 @@
 //                    same with QMPC_REC_CONVEX, beside qmpc_loop_crec.hip, which stays at EXT 2)
 //                4   ... through the robot's delay line and actuator lag         (qmpc_loop_run_actuation*; qmpc_loop_cact.hip: the
 //                    same with QMPC_REC_CONVEX; the ground record may be absent)
+//                5   ... whose controller reads a measured state                 (qmpc_loop_run_sensing*; qmpc_loop_csense.hip: the
+//                    same with QMPC_REC_CONVEX; the actuation record may be absent too).  The one layer in the FRONT end
 // and, for the sibling controller (qmpc_loop_crec.hip; a handle opts in with qmpc_set_convex_records),
 //   QMPC_REC_CONVEX  defined: ConvexMpc's problem -- ConvexModel and the wrench-form body with QMPC_WMODEL WM_CONVEX, the front
 //                    end loop_front_convex_one on qmpc_convex_input records, the world-frame back end with the robot's plant
@@ -16,7 +18,7 @@
 // Textual inclusion, not a template over EXT: each unit compiles to the instructions it had as a file of its own (a shared
 // __forceinline__ function template moved the register assignment of every kernel; DESIGN.md).  The parameters a smaller EXT
 // does not have are written with the two macros below; a kernel's parameter list is that of its EXT and of no other.
-//   per tick    qmpc_loop_rec_front_kernel (EXT 0 / 1; the push call launches the outcome unit's) and qmpc_loop_rec_post_kernel
+//   per tick    qmpc_loop_rec_front_kernel (EXT 0 / 1 / 5; the calls of EXT 2-4 launch the outcome unit's) and qmpc_loop_rec_post_kernel
 //               around the solve the C entry point launches
 //   persistent  qmpc_loop_rec_fused_kernel<3|5|6>: qmpc_loop_fused_kernel<VAR, false, false, false> (QuatMpc's problem,
 //               converged mode, wrench-form body) with the robot's own controller and plant
@@ -30,8 +32,13 @@
 #define QMPC_REC_FRONT(OCC_, LP_, s_, r_) loop_front_one<OCC_>(LP_, s_, r_)
 #endif
 // the post step and, at EXT 3, the two arguments it has beyond the plant block: robot i_'s ground record and tally; at EXT 4
-// (where there may be no ground record) the robot's actuation record and delay line after them
-#if QMPC_REC_EXT >= 4
+// (where there may be no ground record) the robot's actuation record and delay line after them; at EXT 5 those may be absent too
+#if QMPC_REC_EXT >= 5
+#define QMPC_REC_POST loop_post_actuation_one
+#define QMPC_REC_POST_GROUND(i_)                                                                                               \
+  , ground ? ground + (size_t)(i_) : nullptr, tally ? tally + (size_t)(i_) : nullptr, act ? act + (size_t)(i_) : nullptr, \
+      line ? line + (size_t)(i_) : nullptr
+#elif QMPC_REC_EXT >= 4
 #define QMPC_REC_POST loop_post_actuation_one
 #define QMPC_REC_POST_GROUND(i_) \
   , ground ? ground + (size_t)(i_) : nullptr, tally ? tally + (size_t)(i_) : nullptr, act + (size_t)(i_), line + (size_t)(i_)
@@ -64,6 +71,11 @@
 #define QMPC_REC_ACT(...) __VA_ARGS__
 #else
 #define QMPC_REC_ACT(...)
+#endif
+#if QMPC_REC_EXT >= 5
+#define QMPC_REC_SENSE(...) __VA_ARGS__
+#else
+#define QMPC_REC_SENSE(...)
 #endif
 
 // the trace row of a robot that does not move in this tick
@@ -120,7 +132,11 @@ QMPC_LOOP_FN void loop_post_actuation_one(const PlantDev& pl, const qmpc_loop_pa
   qmpc_loop::quat_to_rot(s.quat, R);
   int verdict[4] = {0, 0, 0, 0};
   int any = 0;
+#if QMPC_REC_EXT >= 5
+  const bool ident = !act || qmpc_loop::loop_actuation_identity(*act);     // (no record: every command acts in its own tick)
+#else
   const bool ident = qmpc_loop::loop_actuation_identity(*act);
+#endif
 #ifdef QMPC_REC_CONVEX
   if (accepted)
     for (int l = 0; l < 4; ++l)
@@ -133,6 +149,9 @@ QMPC_LOOP_FN void loop_post_actuation_one(const PlantDev& pl, const qmpc_loop_pa
     for (int a = 0; a < 12; ++a) s.forces_body[a] = forces[a];
 #endif
   double u[12];      // what the plant receives
+#if QMPC_REC_EXT >= 5
+  if (act)
+#endif
   qmpc_loop::loop_actuation_one(*act, *line, s.forces_body, s.contacts, u);
   if (ident) {
 #ifdef QMPC_REC_CONVEX
@@ -297,13 +316,45 @@ QMPC_LOOP_FN void loop_post_plant_world_one(const PlantDev& pl, const qmpc_loop_
 }
 #endif
 
+#if QMPC_REC_EXT >= 5
+// The front end of a tick whose controller reads a MEASURED state (qmpc_loop_run_sensing*).  A robot without a record, or whose
+// record is the identity, runs the front end as it stands and its seen stays untouched.  Any other robot: the 13 true doubles
+// at the head of the state (pos_world, quat, lin_vel_world, ang_vel_body) are saved, qmpc_loop::loop_sense_one's measurement of
+// them is written in their place, the front end runs unchanged -- it writes none of the 13 --, the true doubles are put back as
+// bytes and seen, when given, takes the measurement.  sense and seen point into global memory and are reached here, inside
+// the front step: the 13 saved doubles live across the front end's call only, nothing of the feature across the solve.
+template <int OCC = 1>
+QMPC_LOOP_FN void loop_front_sense_one(const qmpc_loop_params& LP, qmpc_loop_state& s, qmpc_input& in,
+                                       const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen) {
+#pragma clang fp contract(off)
+  if (!sense || qmpc_loop::loop_sense_identity(*sense)) {
+    QMPC_REC_FRONT(OCC, LP, s, in);
+    return;
+  }
+  double x[13], m[13];
+  for (int a = 0; a < 3; ++a) { x[a] = s.pos_world[a]; x[7 + a] = s.lin_vel_world[a]; x[10 + a] = s.ang_vel_body[a]; }
+  for (int a = 0; a < 4; ++a) x[3 + a] = s.quat[a];
+  qmpc_loop::loop_sense_one(*sense, s.tick, x, m);
+  for (int a = 0; a < 3; ++a) { s.pos_world[a] = m[a]; s.lin_vel_world[a] = m[7 + a]; s.ang_vel_body[a] = m[10 + a]; }
+  for (int a = 0; a < 4; ++a) s.quat[a] = m[3 + a];
+  if (seen) {      // (before the call: m is not live across it)
+    for (int a = 0; a < 13; ++a) seen->meas[a] = m[a];
+    seen->ticks += 1.0;
+  }
+  QMPC_REC_FRONT(OCC, LP, s, in);
+  for (int a = 0; a < 3; ++a) { s.pos_world[a] = x[a]; s.lin_vel_world[a] = x[7 + a]; s.ang_vel_body[a] = x[10 + a]; }
+  for (int a = 0; a < 4; ++a) s.quat[a] = x[3 + a];
+}
+#endif
+
 // ---- per-tick form -----------------------------------------------------------------------------------------------------
-#if QMPC_REC_EXT <= 1 || defined(QMPC_REC_CONVEX)
+#if QMPC_REC_EXT <= 1 || QMPC_REC_EXT >= 5 || defined(QMPC_REC_CONVEX)
 // The front end of qmpc_loop_front_kernel; the record of a frozen robot, or of one halted under stop_when_down, gets a NaN
 // attitude instead, which every solve kernel rejects before its first iteration (QMPC_NAN_INPUT; the post kernel ignores it)
 __global__ __launch_bounds__(64) void qmpc_loop_rec_front_kernel(
     qmpc_loop_params LP, QMPC_REC_OUTCOME(qmpc_outcome_params OP, ) qmpc_loop_state* __restrict__ st, qmpc_input* __restrict__ rec,
-    int* __restrict__ row, const PlantDev* __restrict__ pl, QMPC_REC_OUTCOME(const qmpc_loop_outcome* __restrict__ oc, ) int batch) {
+    int* __restrict__ row, const PlantDev* __restrict__ pl, QMPC_REC_OUTCOME(const qmpc_loop_outcome* __restrict__ oc, )
+    QMPC_REC_SENSE(const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen, ) int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0 && row) *row += 1;                         // trace row of this tick (stream order: after the last post)
   if (i >= batch) return;
@@ -311,7 +362,11 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_front_kernel(
     rec[i].quat[0] = __builtin_nan("");      // (ConvexMpc's record: its first word, euler[0])
     return;
   }
+#if QMPC_REC_EXT >= 5
+  loop_front_sense_one<1>(LP, st[i], rec[i], sense ? sense + (size_t)i : nullptr, seen ? seen + (size_t)i : nullptr);
+#else
   QMPC_REC_FRONT(1, LP, st[i], rec[i]);
+#endif
 }
 #endif
 
@@ -365,6 +420,8 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
 // tick -- the same rule: nothing live across the solve, no block copied.
 // EXT 4: ... and reaches the robot's actuation record and delay line by pointer there: one 96 B ring slot read, one written, the
 // 96 B applied read-modify-written, the ring indexed in global memory with the run-time slot number (no local array, no scratch).
+// EXT 5: lane 0's FRONT step reaches the robot's 256 B sensing record and its 128 B seen by pointer (loop_front_sense_one): the 13
+// true doubles it saves live across the front end's call only -- the same rule, nothing of the feature is live across the solve.
 // (The two zero-fill loops stay written out: as calls of one inline function they compile to other instructions.)
 template <int VAR>
 __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmpc_loop_rec_fused_kernel(
@@ -373,7 +430,8 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
     double* __restrict__ trace_f, double* __restrict__ trace_c, QMPC_REC_OUTCOME(qmpc_loop_outcome* __restrict__ outcomes, )
     QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, )
     QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, )
-    QMPC_REC_ACT(const qmpc_actuation_params* __restrict__ act, qmpc_actuation_line* __restrict__ line, ) int ticks, int batch,
+    QMPC_REC_ACT(const qmpc_actuation_params* __restrict__ act, qmpc_actuation_line* __restrict__ line, )
+    QMPC_REC_SENSE(const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen, ) int ticks, int batch,
     double* __restrict__ gws) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int b = blockIdx.x;
@@ -405,7 +463,11 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
 #endif
   bool prev_ok = false;
   for (int t = 0; t < ticks; ++t) {
+#if QMPC_REC_EXT >= 5
+    if (lane == 0) loop_front_sense_one<OCC>(LP, st[b], rec[b], sense ? sense + (size_t)b : nullptr, seen ? seen + (size_t)b : nullptr);
+#else
     if (lane == 0) QMPC_REC_FRONT(OCC, LP, st[b], rec[b]);
+#endif
     __syncthreads();                      // the record (global memory) is visible to the wave
     [&]() {
       const int warm_t = (LP.warm_start != 0.0 && prev_ok) ? t : 0;   // t > 0 and the last solve left a usable U in LDS
@@ -457,6 +519,24 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
 #endif
 }
 
+#if QMPC_REC_EXT == 5 && !defined(QMPC_REC_CONVEX)
+// ---- the check of the sensing records (QuatMpc's unit only: it does not depend on the model) -------------------------------
+// One thread per robot: the verdict of the robot's sensing record into its plant block (a verdict already there stays)
+__global__ __launch_bounds__(256) void qmpc_sense_check_kernel(const qmpc_sense_params* __restrict__ sense, PlantDev* __restrict__ pl,
+                                                               int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  if (!qmpc_loop::loop_sense_valid(sense[i])) pl[i].status = QMPC_BAD_PARAMS;
+}
+
+__attribute__((visibility("hidden"))) hipError_t rec_sense_check_launch(hipStream_t s, const qmpc_sense_params* sense, void* plants,
+                                                                        int batch) {
+  hipLaunchKernelGGL(qmpc_sense_check_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, sense,
+                     static_cast<PlantDev*>(plants), batch);
+  return hipGetLastError();
+}
+#endif
+
 #if QMPC_REC_EXT == 4 && !defined(QMPC_REC_CONVEX)
 // ---- the check of the actuation records and delay lines (QuatMpc's unit only: it does not depend on the model) ------------
 // One thread per robot: the verdict of the robot's record and of its line's count into its plant block (a verdict already there
@@ -507,22 +587,24 @@ __attribute__((visibility("hidden"))) hipError_t rec_fused_launch(
     int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants, const qmpc_loop_params* lp,
     qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws,
     const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,
-    const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line) {
+    const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line,
+    const qmpc_sense_params* sense, qmpc_sense_seen* seen) {
   const int k = qmpc::wform_index(var);
   if (k < 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kRecFused[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks),
                      static_cast<const PlantDev*>(plants), *lp, QMPC_REC_OUTCOME(*op, ) st, rec, forces, info, trace_f, trace_c,
                      QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, )
-                     QMPC_REC_ACT(act, line, ) ticks, batch, gws);
+                     QMPC_REC_ACT(act, line, ) QMPC_REC_SENSE(sense, seen, ) ticks, batch, gws);
   return hipGetLastError();
 }
 
-#if QMPC_REC_EXT <= 1 || defined(QMPC_REC_CONVEX)
+#if QMPC_REC_EXT <= 1 || QMPC_REC_EXT >= 5 || defined(QMPC_REC_CONVEX)
 __attribute__((visibility("hidden"))) hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st,
                                                                   qmpc_input* rec, int* row, const void* plants, int batch,
-                                                                  const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes) {
+                                                                  const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes,
+                                                                  const qmpc_sense_params* sense, qmpc_sense_seen* seen) {
   hipLaunchKernelGGL(qmpc_loop_rec_front_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, *lp, QMPC_REC_OUTCOME(*op, ) st, rec, row,
-                     static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, ) batch);
+                     static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_SENSE(sense, seen, ) batch);
   return hipGetLastError();
 }
 #endif
@@ -544,6 +626,7 @@ __attribute__((visibility("hidden"))) hipError_t rec_post_launch(hipStream_t s, 
 #undef QMPC_REC_PUSH
 #undef QMPC_REC_GROUND
 #undef QMPC_REC_ACT
+#undef QMPC_REC_SENSE
 #undef QMPC_REC_POST_GROUND
 #undef QMPC_REC_EXT
 #undef QMPC_REC_MODEL

@@ -44,6 +44,10 @@ class ClosedLoopHostBase {
   // every command in its own tick); the line the ticks advance is read back with actuation_line, to carry it over runs
   virtual void set_actuation(const qmpc_actuation_params* act, const qmpc_actuation_line* line) = 0;
   virtual const qmpc_actuation_line& actuation_line() const = 0;
+  // the robot's sensing record (qmpc_loop_run_sensing*): copied (null: none -- the controller reads the true state); what the
+  // controller read in the last tick and the count of such ticks are read back with sense_seen (it starts empty; set_sense leaves it)
+  virtual void set_sense(const qmpc_sense_params* sense) = 0;
+  virtual const qmpc_sense_seen& sense_seen() const = 0;
   State state;
 };
 
@@ -115,6 +119,11 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     if (has_act_) { act_ = *act; line_ = *line; }
   }
   const qmpc_actuation_line& actuation_line() const override { return line_; }
+  void set_sense(const qmpc_sense_params* sense) override {
+    has_sense_ = sense != nullptr;
+    if (sense) sense_ = *sense;
+  }
+  const qmpc_sense_seen& sense_seen() const override { return seen_; }
   void reset_outcome() {                                    // qmpc_loop_outcome_init
     std::memset(&outcome_, 0, sizeof outcome_);
     outcome_.down_tick = outcome_.first_rejected_tick = -1.0;
@@ -157,11 +166,38 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   }
 
   bool tick() override {
+    // the device's sensing tick (qmpc_loop_math.h: loop_sense_one): a robot with a non-identity record hands its controller the
+    // measurement of the state at state.tick = ticks_ -- feedback, Raibert targets, goal, feet and the solve read it -- and
+    // everything after the solve works on the true state again
+    double true_x[13];
+    const bool sensed = has_sense_ && !qmpc_loop::loop_sense_identity(sense_);
+    if (sensed) {
+      for (int a = 0; a < 13; ++a) true_x[a] = x_[a];
+      qmpc_loop::loop_sense_one(sense_, (double)ticks_, true_x, x_);
+      for (int a = 0; a < 13; ++a) seen_.meas[a] = x_[a];
+      seen_.ticks += 1.0;
+    }
     refresh_feedback();
     raibert_foot_targets(state);
     mpc->goal_update(state);
     mpc->foot_update(state);
     const bool ok = mpc->grf_update(state);
+    if (sensed) {
+      for (int a = 0; a < 13; ++a) x_[a] = true_x[a];
+      if (ok) {      // the device's post step works with the TRUE R: QuatMpc's mpc_grf_world = R u, ConvexMpc's optimized_input = R' u
+        double R[9];
+        qmpc_loop::quat_to_rot(&x_[3], R);
+        for (int l = 0; l < NUM_LEG; ++l)
+          for (int r = 0; r < 3; ++r) {
+            if (kConvex)
+              state.ctrl.optimized_input[3 * l + r] = R[r] * state.ctrl.mpc_grf_world[3 * l] + R[3 + r] * state.ctrl.mpc_grf_world[3 * l + 1] +
+                                                      R[6 + r] * state.ctrl.mpc_grf_world[3 * l + 2];
+            else
+              state.ctrl.mpc_grf_world[3 * l + r] = R[3 * r] * state.ctrl.optimized_input[3 * l] + R[3 * r + 1] * state.ctrl.optimized_input[3 * l + 1] +
+                                                    R[3 * r + 2] * state.ctrl.optimized_input[3 * l + 2];
+          }
+      }
+    }
     double u[12];
     for (int a = 0; a < 12; ++a) u[a] = state.ctrl.optimized_input[a];
     int verdict[4] = {0, 0, 0, 0};
@@ -357,6 +393,9 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   qmpc_actuation_params act_;
   qmpc_actuation_line line_ = {};                        // qmpc_actuation_line_init with no initial force
   bool has_act_ = false;
+  qmpc_sense_params sense_;
+  qmpc_sense_seen seen_ = {};                            // qmpc_sense_seen_init
+  bool has_sense_ = false;
   long ticks_ = 0;
 };
 

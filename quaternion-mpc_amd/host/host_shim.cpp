@@ -274,6 +274,18 @@ void qh_loop_set_actuation(void* p, const qmpc_actuation_params* act, const qmpc
   static_cast<LoopHarness*>(p)->loop->set_actuation(act, line);
 }
 void qh_loop_actuation_line(void* p, qmpc_actuation_line* out) { *out = static_cast<LoopHarness*>(p)->loop->actuation_line(); }
+// ... and its sensing record with what its controller read in the last tick (qmpc_loop_run_sensing*; sense null: none)
+void qh_loop_set_sense(void* p, const qmpc_sense_params* sense) { static_cast<LoopHarness*>(p)->loop->set_sense(sense); }
+void qh_loop_sense_seen(void* p, qmpc_sense_seen* out) { *out = static_cast<LoopHarness*>(p)->loop->sense_seen(); }
+// the rule itself on caller buffers (qmpc_loop_math.h: loop_sense_one, the one source the device compiles too): x [13] = pos_world,
+// quat, lin_vel_world, ang_vel_body of the state at `tick`, m [13] receives what the controller reads; an identity record copies.
+// Returns 0 for an invalid record (m untouched), 1 otherwise.
+int qh_sense_one(const qmpc_sense_params* sense, double tick, const double* x, double* m) {
+  if (!qmpc_loop::loop_sense_valid(*sense)) return 0;
+  if (qmpc_loop::loop_sense_identity(*sense)) std::memcpy(m, x, 13 * sizeof(double));
+  else qmpc_loop::loop_sense_one(*sense, tick, x, m);
+  return 1;
+}
 void qh_loop_destroy(void* p) {
   LoopHarness* h = static_cast<LoopHarness*>(p);
   if (!h) return;

@@ -347,3 +347,26 @@ def random_go1_actuations(batch: int, seed: int = 0, first: int = 0, delay=(0, 4
     d = np.minimum(np.floor(delay[0] + (delay[1] - delay[0] + 1) * u[:, 0]), delay[1])
     t = None if tau is None else tau[0] + (tau[1] - tau[0]) * u[:, 1]
     return actuation_params(batch, delay_ticks=d, tau=t, dt=dt)
+
+
+def random_go1_senses(batch: int, seed: int = 0, first: int = 0, pos_noise=(0.0, 0.01), att_noise=(0.0, 0.01), vel_noise=(0.0, 0.05),
+                      gyro_noise=(0.0, 0.02), gyro_bias=(0.0, 0.02), pos_bias=(0.0, 0.02)) -> np.ndarray:
+    """`batch` sensing records (``struct qmpc_sense_params``, for Solver.loop_run_sensing), robot indices first .. first+batch-1,
+    the counter-based generator of random_go1_pushes (a shard equals its block of the whole).  Per robot one noise level per
+    channel group, U(*_noise), copied to the group's three axes -- position [m], attitude [rad], world-frame velocity [m/s], body
+    rate [rad/s] -- and per axis a gyro bias and a position bias, uniform on +-U-range: magnitude U(*_bias) with a random sign.
+    The noise seed of robot i is seed * 2^32 + i, so no two robots of a sweep share their noise.  The default ranges are
+    ASSUMPTIONS about a small quadruped's leg-odometry / IMU estimator (a centimetre of position noise, a degree of attitude,
+    centimetres per second of velocity, a degree per second of gyro noise and bias), not measurements of a Go1: sweep them.
+    Sixteen uniforms per robot, in the order pos, att, vel, gyro noise, gyro bias magnitude x 3, its sign x 3, position bias
+    magnitude x 3, its sign x 3."""
+    from . import sense_params
+
+    idx = np.arange(first, first + batch, dtype=np.uint64)
+    u = _uniform(0x5EED6000 + int(seed), idx, 16)
+    lin = lambda r, v: r[0] + (r[1] - r[0]) * v      # noqa: E731
+    sign = lambda v: np.where(v < 0.5, -1.0, 1.0)      # noqa: E731
+    return sense_params(batch, seed=(int(seed) % (1 << 21)) * float(1 << 32) + idx.astype(np.float64),
+                        pos_noise=lin(pos_noise, u[:, 0])[:, None] * np.ones(3), att_noise=lin(att_noise, u[:, 1])[:, None] * np.ones(3),
+                        vel_noise=lin(vel_noise, u[:, 2])[:, None] * np.ones(3), gyro_noise=lin(gyro_noise, u[:, 3])[:, None] * np.ones(3),
+                        gyro_bias=lin(gyro_bias, u[:, 4:7]) * sign(u[:, 7:10]), pos_bias=lin(pos_bias, u[:, 10:13]) * sign(u[:, 13:16]))

@@ -6,6 +6,7 @@ inertia); the controller is the handle's and is not told about the push.
     python tools/push_recovery.py [--impulses 2,4,6,8,10] [--starts 13] [--length 10] [--per-cell 8] [--speed 0.3] [--settle 60]
                                   [--recover 200] [--horizon 10] [--controller quat|convex|both] [--ctrl-records] [--warm] [--json FILE]
                                   [--mu-true LO HI [--mu-steps 5]] [--delay LO HI] [--tau LO HI [--tau-steps 3]]
+                                  [--gyro-bias LO HI] [--pos-noise LO HI] [--att-noise LO HI] [--vel-noise LO HI] [--sense-steps 3]
 Every robot stands for 6 ticks, trots at --speed for --settle ticks, is shoved at tick 6 + settle + start for --length ticks with
 force impulse / (length dt) in its cell's direction (0 degrees: ahead, 90: to its left), and trots on until --recover ticks after
 the last start.  Down: below 0.15 m or tilted beyond 60 degrees (qmpc_default_outcome_params); stop_when_down halts a fallen robot.
@@ -20,6 +21,13 @@ per (impulse, mu_true) cell with the ground tallies is printed after the tables 
 for --tau-steps actuator time constants from LO to HI seconds (qmpc_loop_run_actuation: the plant receives the command of `delay`
 ticks ago through a first-order lag, alpha = 1 - exp(-dt / tau); the controller is not told; the delay lines start from the stand
 force m g / 4 per leg), and a table of falls per (impulse, delay, tau) cell is printed after the tables above, which then pool them.
+--gyro-bias LO HI, --pos-noise LO HI, --att-noise LO HI, --vel-noise LO HI: the estimator axes (qmpc_loop_run_sensing: the
+controller reads the true state plus a bias and reproducible bounded noise; the plant works on the truth).  The grid is repeated
+for --sense-steps gyro biases from LO to HI rad/s (on all three body axes, the signs by the robot's place in its cell) and for
+--sense-steps noise levels: level j takes the j-th of --sense-steps values from LO to HI of each noise given -- position [m],
+attitude [rad], world-frame velocity [m/s], standard deviation per axis -- so the noises rise together.  Every robot draws its own
+noise (seed = its index).  A table of falls per (impulse, gyro bias, noise level) cell is printed after the tables above, which
+then pool them.
 --ctrl-records: every robot also carries a controller record (the handle's values: the same controller) and the handle takes
 QMPC_INSTANCES_AUTO, a ConvexMpc handle with qmpc_set_convex_lane_records as well -- the launch a sweep over per-robot controllers
 takes: from the switch-over on the lane kernel with per-lane parameters under either controller.
@@ -66,6 +74,11 @@ def main():
     ap.add_argument("--delay", type=int, nargs=2, default=None, metavar=("LO", "HI"))
     ap.add_argument("--tau", type=float, nargs=2, default=None, metavar=("LO", "HI"))
     ap.add_argument("--tau-steps", type=int, default=3)
+    ap.add_argument("--gyro-bias", type=float, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--pos-noise", type=float, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--att-noise", type=float, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--vel-noise", type=float, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--sense-steps", type=int, default=3)
     a = ap.parse_args()
     pkg = load_pkg()
     lib = pkg.load_library()
@@ -84,10 +97,16 @@ def run(a, pkg, lib, controller):
     delays = np.arange(a.delay[0], a.delay[1] + 1) if a.delay else np.array([0])
     taus = np.linspace(a.tau[0], a.tau[1], a.tau_steps) if a.tau else np.array([0.0])
     timed = bool(a.delay or a.tau)
-    gi, gs, gd, gm, gl, gt, _ = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8),
-                                                                np.arange(len(mus)), np.arange(len(delays)), np.arange(len(taus)),
-                                                                np.arange(a.per_cell), indexing="ij"))
-    members = len(mus) * len(delays) * len(taus) * a.per_cell
+    noises = {k: v for k, v in (("pos", a.pos_noise), ("att", a.att_noise), ("vel", a.vel_noise)) if v}
+    gbs = np.linspace(a.gyro_bias[0], a.gyro_bias[1], a.sense_steps) if a.gyro_bias else np.array([0.0])
+    levels = np.arange(a.sense_steps) if noises else np.array([0])
+    sensed = bool(a.gyro_bias or noises)
+    gi, gs, gd, gm, gl, gt, gb, gn, gk = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8),
+                                                                         np.arange(len(mus)), np.arange(len(delays)), np.arange(len(taus)),
+                                                                         np.arange(len(gbs)), np.arange(len(levels)), np.arange(a.per_cell),
+                                                                         indexing="ij"))
+    tail = len(gbs) * len(levels) * a.per_cell      # the robots of one (impulse, start, direction, mu, delay, tau) cell
+    members = len(mus) * len(delays) * len(taus) * tail
     B = gi.size
     convex = controller == "convex"
     p = (pkg.default_convex_params if convex else pkg.default_params)(a.horizon, pkg.MODE_CONVERGED, lib)
@@ -115,6 +134,12 @@ def run(a, pkg, lib, controller):
     if timed:
         act = pkg.actuation_params(B, delay_ticks=delays[gl], tau=taus[gt], dt=lp.dt)
         line = pkg.actuation_lines(B, pkg.stand_forces_body(p.mass))
+    sense = None
+    if sensed:
+        signs = np.stack([np.where((gk >> b) & 1, -1.0, 1.0) for b in range(3)], axis=1)
+        level = lambda r: np.linspace(r[0], r[1], a.sense_steps)[gn][:, None] * np.ones(3)      # noqa: E731
+        sense = pkg.sense_params(B, seed=np.arange(B, dtype=np.float64), gyro_bias=gbs[gb][:, None] * signs,
+                                 **{k + "_noise": level(r) for k, r in noises.items()})
     op = pkg.default_outcome_params(lib, stop_when_down=True)
     s = pkg.Solver(p, B, device=0, lib=lib)
     if convex:
@@ -130,10 +155,11 @@ def run(a, pkg, lib, controller):
     form = s.loop_instances_plan(B, ctrl is not None, a.warm)
     total = a.settle + PERIOD + a.recover
     w0 = time.perf_counter()
-    # (act = None: the ground call; ground = None: the push call)
-    st, oc, ta, line = s.loop_run_actuation(st, 6, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op)
+    # (sense = None: the actuation call; act = None: the ground call; ground = None: the push call)
+    st, oc, ta, line, seen = s.loop_run_sensing(st, 6, sense, None, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op)
     st["movement_mode"] = 1.0
-    st, oc, ta, line = s.loop_run_actuation(st, total, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc, tallies=ta)
+    st, oc, ta, line, seen = s.loop_run_sensing(st, total, sense, seen, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc,
+                                                tallies=ta)
     wall = time.perf_counter() - w0
     s.close()
     up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, members)
@@ -155,7 +181,7 @@ def run(a, pkg, lib, controller):
           "  ".join(f"{imp:g} N s: {share[i].mean():.3f}" for i, imp in enumerate(impulses)) + f"   all: {share.mean():.3f}\n")
     by_mu = None
     if a.mu_true:
-        shape = (len(impulses), len(starts), 8, len(mus), len(delays) * len(taus) * a.per_cell)
+        shape = (len(impulses), len(starts), 8, len(mus), len(delays) * len(taus) * tail)
         down = (oc["down_tick"] >= 0).reshape(shape)
         cell = down.shape[1] * down.shape[2] * down.shape[4]
         print(f"true friction: robots down per (impulse, mu_true) cell, of {cell} (the controller assumes mu = {p.mu:g})")
@@ -172,7 +198,7 @@ def run(a, pkg, lib, controller):
                  "clipped_ticks_mean": ta["clipped_ticks"].reshape(shape).mean(axis=(0, 1, 2, 4)).tolist()}
     by_time = None
     if timed:
-        shape = (len(impulses), len(starts), 8, len(mus), len(delays), len(taus), a.per_cell)
+        shape = (len(impulses), len(starts), 8, len(mus), len(delays), len(taus), tail)
         down = (oc["down_tick"] >= 0).reshape(shape)
         cell = down[0, :, :, :, 0, 0].size
         alphas = pkg.actuation_params(len(taus), tau=taus, dt=lp.dt)["alpha"]
@@ -186,7 +212,25 @@ def run(a, pkg, lib, controller):
               " ".join(f"{int(d)}: {int(before[:, :, :, :, l].sum())}" for l, d in enumerate(delays)) + "\n")
         by_time = {"delay_ticks": delays.tolist(), "tau_s": taus.tolist(), "alpha": alphas.tolist(), "cell": cell,
                    "down": down.sum(axis=(1, 2, 3, 6)).tolist()}
-    return {"controller": controller, "by_mu_true": by_mu, "by_actuation": by_time, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
+    by_sense = None
+    if sensed:
+        shape = (len(impulses), len(starts), 8, len(mus) * len(delays) * len(taus), len(gbs), len(levels), a.per_cell)
+        down = (oc["down_tick"] >= 0).reshape(shape)
+        cell = down[0, :, :, :, 0, 0].size
+        what = ", ".join(f"{k} {r[0]:g} .. {r[1]:g}" for k, r in noises.items()) or "none"
+        print(f"sensing: robots down per (impulse, gyro bias, noise level) cell, of {cell}; gyro bias in rad/s on every body axis, noise "
+              f"levels 0 .. {len(levels) - 1} of: {what}")
+        print("impulse gyro_bias " + " ".join(f"level {int(j):d}" for j in levels))
+        for i, imp in enumerate(impulses):
+            for b, g in enumerate(gbs):
+                print(f"{imp:5g}   {g:9.4f} " + " ".join(f"{int(down[i, :, :, :, b, j].sum()):7d}" for j in range(len(levels))))
+        before = ((oc["down_tick"] >= 0) & (oc["down_tick"] <= push["start_tick"][:, 0])).reshape(shape)
+        print("  ... of them down before their shove began, by gyro bias: " +
+              " ".join(f"{g:g}: {int(before[:, :, :, :, b].sum())}" for b, g in enumerate(gbs)) + "; by noise level: " +
+              " ".join(f"{int(j)}: {int(before[:, :, :, :, :, j].sum())}" for j in range(len(levels))) + "\n")
+        by_sense = {"gyro_bias": gbs.tolist(), "noise": {k: np.linspace(r[0], r[1], a.sense_steps).tolist() for k, r in noises.items()},
+                    "cell": cell, "down": down.sum(axis=(1, 2, 3, 6)).tolist(), "measurements": int(seen["ticks"].sum())}
+    return {"controller": controller, "by_mu_true": by_mu, "by_actuation": by_time, "by_sensing": by_sense, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
             "per_cell": members, "length_ticks": a.length, "speed": a.speed, "form": form, "share_up": share.tolist()}
 
 
