@@ -1129,6 +1129,80 @@ qmpc_status qmpc_loop_run_sensing_device(qmpc_handle* h, const qmpc_loop_params*
                                          const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
                                          const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, void* stream);
 
+/* ---- gait frequency and contact pattern per robot (which gait and cadence survives this shove?) -------------------------
+ * In every loop above all robots of a call walk the reference's trot at lp->gait_freq.  qmpc_loop_run_gaits* is
+ * qmpc_loop_run_sensing* -- the same arguments in their order, robots, launch forms (QMPC_QUERY_LOOP_INSTANCES_PLAN answers for
+ * it too), refusals, ticks = 0 behaviour, freezing, halting, ConvexMpc and warm-record opt-ins, the lane tick under
+ * QMPC_INSTANCES_AUTO -- with one more record per robot before `stream`: its gait.  It adds no in/out record: the schedule
+ * lives in qmpc_loop_state::leg[], contacts and gait_counter, as it always did.
+ *
+ * The reference's FSM holds a pattern of states and switch times per leg; its update() toggles the state on every transition
+ * instead of reading the pattern, so only two-entry patterns work as written.  A robot's gait here is therefore, per leg, a
+ * two-entry pattern -- [STANCE, SWING] or [SWING, STANCE] with switch times split and 1.0 -- plus the phase the leg starts at.
+ *
+ * The rule (loop_gait_* in csrc/qmpc_loop_math.h: one source for the device, the host classes and the tests):
+ *   pattern   pattern(leg, idx) = ((idx == 0) == (first_stance[leg] != 0)) ? STANCE : SWING; switch_time(leg, idx) = idx == 0 ?
+ *             split[leg] : 1.0.
+ *   update    the reference's update / common_enter (LeggedContactFSM.cpp:33-78,208-223) with gait_freq and the switch times of
+ *             the record; the early-contact branch (percent > 0.9 and the contact flag) is unchanged.
+ *   reset     every tick while movement_mode == 0, and in qmpc_loop_state_set_gait:  gait_phase = phase0;  idx = phase0 < split ?
+ *             0 : 1;  pattern_index = idx, prev_pattern_index = 1 - idx;  start_time = idx ? split : 0, end_time = idx ? 1 : split;
+ *             state = pattern(idx); everything else as the reference's reset().  With phase0 = 0 these are the trot's bytes.
+ *   swing     the reference's literal 0.5 in the swing curve's times is the trot's swing fraction; a leg uses its own,
+ *             w = first_stance ? 1 - split : split:  swing target at (float)(w t / f) of (float)(w / f).
+ *   Raibert   the literal (1 / f) / 2 is the trot's stance time; a leg uses (1 / f) (1 - w), the +-0.5 / +-0.3 clamps per leg.
+ *             At w = 1/2 both give the trot's bits (a scaling by a power of two is exact).
+ *
+ * A record is the IDENTITY when gait_freq == lp->gait_freq, first_stance == {1, 0, 0, 1}, every split == 0.5 and every
+ * phase0 == 0: its robot, and every robot when gait == NULL, runs the front end of the sensing call as it stands -- every byte
+ * equals that call's.  gait == NULL: the call IS qmpc_loop_run_sensing*.  Every other record may be NULL as in that call.
+ *
+ * A record is VALID when every field is finite and the reserved words are 0; gait_freq > 0 and gait_freq * lp->dt <= 1/16 (every
+ * arc lasts at least two ticks); first_stance is 0 or 1; split is a multiple of 2^-8 in [1/8, 7/8]; phase0 a multiple of 2^-8 in
+ * [0, 1); and the schedule plans no flight: with the leg's stance arc in the robot's phase starting at A = frac(a - phase0 + 1)
+ * (a = 0 or split) with length len (split or 1 - split), the end frac(A + len) of every leg's arc lies in some leg's arc
+ * (frac(E - A_m + 1) < len_m) -- exact arithmetic on dyadic numbers.  Pronk and every gait with a flight phase are refused.  An
+ * invalid record makes its robot the robot of an invalid plant record (QMPC_BAD_PARAMS, marked by a check kernel after the
+ * sensing check; every other robot unaffected bit for bit).  A tick without a stance leg can still happen by a rounding
+ * coincidence of two legs' phase accumulators, as in the trot after an early contact: it ends as there (QMPC_NO_CONTACT, the
+ * last forces stay).
+ *
+ * Between calls: split and gait_freq take effect at each leg's next transition, phase0 only at a reset -- a run split into
+ * calls with different records is a gait transition.  Buffers: those of the sensing call; the host-buffer call stages the
+ * records in a buffer of its own (128 B x max_batch), allocated on its first use.  No other call allocates it. */
+typedef struct qmpc_gait_params {   /* 16 doubles, 128 B */
+  double gait_freq;        /* cycles per second, replaces lp->gait_freq for this robot */
+  double first_stance[4];  /* 1: the leg's pattern is [STANCE, SWING]; 0: [SWING, STANCE] */
+  double split[4];         /* the leg's first switch time; the second is 1.0 */
+  double phase0[4];        /* the leg's gait_phase at an FSM reset */
+  double reserved[3];      /* must be 0 */
+} qmpc_gait_params;
+int32_t qmpc_sizeof_gait_params(void);
+/* Host-side; every byte is written: the identity record of lp (the reference's trot at lp->gait_freq) */
+void    qmpc_default_gait_params(const qmpc_loop_params* lp, qmpc_gait_params* out);
+/* Host-side: the reset rule above on the four legs of s, and contacts = the legs' states.  After qmpc_loop_state_init, for a
+ * robot that walks (movement_mode != 0) from tick 0 in the gait's own pattern.  The record is not checked. */
+void    qmpc_loop_state_set_gait(qmpc_loop_state* s, const qmpc_gait_params* gait);
+/* Host buffers: qmpc_loop_run_sensing's arguments, then gait [batch] (or NULL).  Synchronous. */
+qmpc_status qmpc_loop_run_gaits(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant,
+                                double* trace_forces, double* trace_contacts, const qmpc_outcome_params* op,
+                                qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int32_t pushes_per_robot,
+                                const qmpc_ground_params* ground, qmpc_ground_tally* tally,
+                                const qmpc_actuation_params* act, qmpc_actuation_line* line,
+                                const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait);
+/* Device buffers (op is a host pointer, read during the call), stream-ordered (NULL stream = the handle's). */
+qmpc_status qmpc_loop_run_gaits_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch,
+                                       qmpc_loop_state* d_states, int32_t ticks,
+                                       const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                       double* d_trace_forces, double* d_trace_contacts,
+                                       const qmpc_outcome_params* op, qmpc_loop_outcome* d_outcomes,
+                                       const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
+                                       const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
+                                       const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen,
+                                       const qmpc_gait_params* d_gait, void* stream);
+
 /* Stand-pose joint angles (0, 0.67, -1.3 per leg: the reference's Gazebo start pose) for `batch`
  * robots, host buffer [batch][12]. */
 void qmpc_loop_joint_init(double* joint_pos, int32_t batch);

@@ -383,6 +383,54 @@ def sense_seen(batch: int) -> np.ndarray:
     return np.zeros(int(batch), dtype=SENSE_SEEN_DTYPE)
 
 
+# struct qmpc_gait_params (qmpc_loop_run_gaits*): one robot's gait, 16 doubles = 128 B.  Legs in the order FL, FR, RL, RR
+GAIT_PARAMS_DTYPE = np.dtype([("gait_freq", "<f8"), ("first_stance", "<f8", (4,)), ("split", "<f8", (4,)), ("phase0", "<f8", (4,)),
+                              ("reserved", "<f8", (3,))], align=False)
+assert GAIT_PARAMS_DTYPE.itemsize == 16 * 8
+# the named gaits: (first_stance, split, phase0) per leg FL, FR, RL, RR.  Every one is valid (no planned flight); trot is the
+# reference's set_default_gait_pattern -- at the call's gait_freq it is the identity record
+GAITS = {
+    "trot": ((1, 0, 0, 1), (0.5,) * 4, (0.0,) * 4),
+    "pace": ((1, 0, 1, 0), (0.5,) * 4, (0.0,) * 4),
+    "bound": ((1, 1, 0, 0), (0.5,) * 4, (0.0,) * 4),
+    "trot_overlap": ((1, 0, 0, 1), (0.625, 0.375, 0.375, 0.625), (0.0, 0.875, 0.875, 0.0)),
+    "crawl": ((0, 0, 0, 0), (0.25,) * 4, (0.0, 0.75, 0.5, 0.25)),
+    "amble": ((0, 0, 0, 0), (0.375,) * 4, (0.0, 0.5, 0.75, 0.25)),
+}
+
+
+def gait_params(batch: int, gait="trot", gait_freq=None, lp: "LoopParams | None" = None) -> np.ndarray:
+    """[batch] gait records: gait a name of GAITS or one per robot, gait_freq [Hz] a scalar or one per robot (None: lp's, the
+    library's default loop parameters when lp is None too).  gait_params(B) is the identity record of qmpc_default_gait_params:
+    the reference's trot at the call's frequency."""
+    B = int(batch)
+    out = np.zeros(B, dtype=GAIT_PARAMS_DTYPE)
+    if gait_freq is None:
+        gait_freq = (lp or default_loop_params()).gait_freq
+    out["gait_freq"] = np.broadcast_to(np.asarray(gait_freq, dtype=np.float64), (B,))
+    names = [gait] * B if isinstance(gait, str) else list(gait)
+    if len(names) != B:
+        raise ValueError(f"gait: {len(names)} names for {B} robots")
+    for i, n in enumerate(names):
+        if n not in GAITS:
+            raise ValueError(f"gait: unknown name {n!r} (one of {', '.join(GAITS)})")
+        out["first_stance"][i], out["split"][i], out["phase0"][i] = GAITS[n]
+    return out
+
+
+def loop_states_set_gait(states: np.ndarray, gait: np.ndarray, lib: "C.CDLL | None" = None) -> np.ndarray:
+    """qmpc_loop_state_set_gait on a copy of `states`: every robot's four legs at their gait's starting phase, in their pattern's
+    state, contacts to match -- for robots that walk (movement_mode != 0) from tick 0."""
+    lib = lib or load_library()
+    st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
+    g = np.ascontiguousarray(gait, dtype=GAIT_PARAMS_DTYPE)
+    if g.shape != st.shape:
+        raise ValueError(f"gait: shape {g.shape}, expected {st.shape}")
+    for i in range(st.shape[0]):
+        lib.qmpc_loop_state_set_gait(C.c_void_p(st[i:i + 1].ctypes.data), C.c_void_p(g[i:i + 1].ctypes.data))
+    return st
+
+
 # struct qmpc_info: 2 x int32 + 4 doubles = 40 B
 INFO_DTYPE = np.dtype(
     [
@@ -515,6 +563,16 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_sensing_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
                                                  i32, vp, vp, vp, vp, vp, vp, vp]
     lib.qmpc_loop_run_sensing_device.restype = i32
+    lib.qmpc_default_gait_params.argtypes = [C.POINTER(LoopParams), vp]
+    lib.qmpc_default_gait_params.restype = None
+    lib.qmpc_loop_state_set_gait.argtypes = [vp, vp]
+    lib.qmpc_loop_state_set_gait.restype = None
+    lib.qmpc_loop_run_gaits.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp,
+                                        vp, vp, vp, vp, vp]
+    lib.qmpc_loop_run_gaits.restype = i32
+    lib.qmpc_loop_run_gaits_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
+                                               i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.qmpc_loop_run_gaits_device.restype = i32
     lib.qmpc_set_instances_policy.argtypes = [vp, i32]
     lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_set_loop_warm_records.argtypes = [vp, i32]
@@ -596,7 +654,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     for name in ("qmpc_sizeof_input", "qmpc_sizeof_params", "qmpc_sizeof_info", "qmpc_sizeof_convex_input",
                  "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params", "qmpc_sizeof_plant_params",
                  "qmpc_sizeof_loop_outcome", "qmpc_sizeof_push_params", "qmpc_sizeof_ground_params", "qmpc_sizeof_ground_tally",
-                 "qmpc_sizeof_actuation_params", "qmpc_sizeof_actuation_line", "qmpc_sizeof_sense_params", "qmpc_sizeof_sense_seen"):
+                 "qmpc_sizeof_actuation_params", "qmpc_sizeof_actuation_line", "qmpc_sizeof_sense_params", "qmpc_sizeof_sense_seen",
+                 "qmpc_sizeof_gait_params"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = i32
     if lib.qmpc_sizeof_input() != INPUT_DTYPE.itemsize:
@@ -626,6 +685,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         raise RuntimeError("qmpc_actuation_params / qmpc_actuation_line ABI size mismatch")
     if lib.qmpc_sizeof_sense_params() != SENSE_PARAMS_DTYPE.itemsize or lib.qmpc_sizeof_sense_seen() != SENSE_SEEN_DTYPE.itemsize:
         raise RuntimeError("qmpc_sense_params / qmpc_sense_seen ABI size mismatch")
+    if lib.qmpc_sizeof_gait_params() != GAIT_PARAMS_DTYPE.itemsize:
+        raise RuntimeError("qmpc_gait_params ABI size mismatch")
     return lib
 
 
@@ -725,6 +786,11 @@ EXPORTED_SYMBOLS = (
     "qmpc_sizeof_sense_seen",
     "qmpc_loop_run_sensing",
     "qmpc_loop_run_sensing_device",
+    "qmpc_sizeof_gait_params",
+    "qmpc_default_gait_params",
+    "qmpc_loop_state_set_gait",
+    "qmpc_loop_run_gaits",
+    "qmpc_loop_run_gaits_device",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
@@ -1352,6 +1418,75 @@ class Solver:
         if rc != OK:
             raise QmpcError(rc, "qmpc_loop_run_sensing_device")
 
+    def loop_run_gaits(self, states: np.ndarray, ticks: int, gait: np.ndarray | None, sense: np.ndarray | None = None,
+                       seen: np.ndarray | None = None, act: np.ndarray | None = None, lines: np.ndarray | None = None,
+                       ground: np.ndarray | None = None, push: np.ndarray | None = None, lp: LoopParams | None = None,
+                       ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
+                       outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None, trace: bool = False,
+                       want_seen: bool = True):
+        """qmpc_loop_run_gaits: loop_run_sensing in which every robot walks its own gait -- frequency, contact pattern, split and
+        starting phase per leg.  gait: [B] GAIT_PARAMS_DTYPE records, gait_params(); None: exactly loop_run_sensing.  Every other
+        record may be None as there.  The schedule lives in the states (leg, contacts, gait_counter): there is no record to carry
+        over calls, and a record changed between calls takes effect at each leg's next transition (phase0 at the next reset).
+        Returns (states, outcomes, tallies, lines, seen[, forces, contacts]); the arguments are not modified."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
+        B = st.shape[0]
+
+        def records(a, dtype, name, copy=False):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.shape != (B,):
+                raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
+            return a.copy() if copy else a
+
+        ctrl = records(ctrl, INSTANCE_PARAMS_DTYPE, "ctrl")
+        plant = records(plant, PLANT_PARAMS_DTYPE, "plant")
+        ground = records(ground, GROUND_PARAMS_DTYPE, "ground")
+        act = records(act, ACTUATION_PARAMS_DTYPE, "act")
+        sense = records(sense, SENSE_PARAMS_DTYPE, "sense")
+        gait = records(gait, GAIT_PARAMS_DTYPE, "gait")
+        per_robot = 0
+        if push is not None:
+            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
+            if push.ndim == 1:
+                push = push.reshape(-1, 1)
+            if push.ndim != 2 or push.shape[0] != B:
+                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
+            per_robot = push.shape[1]
+            if per_robot == 0:
+                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
+        oc = loop_outcomes(B, self.lib) if outcomes is None else records(outcomes, LOOP_OUTCOME_DTYPE, "outcomes", copy=True)
+        ta = ground_tallies(B) if tallies is None else records(tallies, GROUND_TALLY_DTYPE, "tallies", copy=True)
+        li = actuation_lines(B) if lines is None else records(lines, ACTUATION_LINE_DTYPE, "lines", copy=True)
+        sn = sense_seen(B) if seen is None else records(seen, SENSE_SEEN_DTYPE, "seen", copy=True)
+        tf = np.zeros((ticks, B, 12)) if trace else None
+        tc = np.zeros((ticks, B, 4)) if trace else None
+        rc = self.lib.qmpc_loop_run_gaits(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
+                                          C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta), _ptr(act),
+                                          _ptr(li), _ptr(sense), _ptr(sn) if want_seen else None, _ptr(gait))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_gaits")
+        return (st, oc, ta, li, sn, tf, tc) if trace else (st, oc, ta, li, sn)
+
+    def loop_run_gaits_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_gait: int, d_sense: int = 0,
+                              d_seen: int = 0, d_act: int = 0, d_line: int = 0, d_ground: int = 0, d_tally: int = 0, d_push: int = 0,
+                              pushes_per_robot: int = 0, lp: LoopParams | None = None, op: OutcomeParams | None = None,
+                              d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_gaits_device: device pointers (ints; 0 = NULL), stream-ordered; d_gait, d_sense, d_act, d_ground and
+        d_push are read in place, d_seen (or 0), d_line and d_tally (or 0) are read and written."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        rc = self.lib.qmpc_loop_run_gaits_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
+                                                 p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
+                                                 int(pushes_per_robot), p(d_ground), p(d_tally), p(d_act), p(d_line), p(d_sense),
+                                                 p(d_seen), p(d_gait), p(stream))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_gaits_device")
+
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
         as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN).  Answers under the handle's
@@ -1664,5 +1799,5 @@ class Solver:
 
 from .scenarios import (go1_stand_input, quat_to_rot, random_go1_trot_states,  # noqa: E402,F401
                         random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_convex_variants, random_go1_plants,
-                        random_go1_pushes, random_go1_grounds, random_go1_actuations, random_go1_senses)
+                        random_go1_pushes, random_go1_grounds, random_go1_actuations, random_go1_senses, random_go1_gaits)
 from .sharding import StepPipeline, gather_forces, shard_range, solve_sharded  # noqa: E402,F401

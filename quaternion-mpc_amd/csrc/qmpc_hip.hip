@@ -74,7 +74,9 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
 // its namespace (qmpc_loop_rec.inc) and ignores the trailing arguments its kernels do not take; the push and ground units have no
 // front kernel of their own.  qmpc_loop_act.hip: the ground loop behind the robot's delay line and actuator lag
 // (qmpc_loop_run_actuation*), the same entry points once more, no front kernel either.  qmpc_loop_sense.hip: the actuation loop
-// whose controller reads a measured state (qmpc_loop_run_sensing*), with a front kernel of its own that takes the last two arguments.
+// whose controller reads a measured state (qmpc_loop_run_sensing*), with a front kernel of its own that takes the sensing arguments.
+// qmpc_loop_gait.hip: the sensing loop in which every robot walks a gait of its own (qmpc_loop_run_gaits*); its front kernel takes
+// the last argument too.
 #define QMPC_REC_DECLARE(ns)                                                                                                         \
   namespace ns {                                                                                                                     \
   hipError_t rec_set_lds();                                                                                                          \
@@ -83,10 +85,11 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
                               double* trace_f, double* trace_c, int ticks, double* gws, const qmpc_outcome_params* op,              \
                               qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,                             \
                               const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act,         \
-                              qmpc_actuation_line* line, const qmpc_sense_params* sense, qmpc_sense_seen* seen);                     \
+                              qmpc_actuation_line* line, const qmpc_sense_params* sense, qmpc_sense_seen* seen,                      \
+                              const qmpc_gait_params* gait);                                                                         \
   hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, int* row,            \
                               const void* plants, int batch, const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes,      \
-                              const qmpc_sense_params* sense, qmpc_sense_seen* seen);                                                \
+                              const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait);                 \
   hipError_t rec_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, const double* forces,                  \
                              const qmpc_info* info, double* trace_f, double* trace_c, const int* row, const void* plants, int batch, \
                              const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push,              \
@@ -103,18 +106,21 @@ QMPC_REC_DECLARE(qmpc_act_tu)       // qmpc_loop_act.hip
 QMPC_REC_DECLARE(qmpc_cact_tu)      // qmpc_loop_cact.hip: the actuation call on such a ConvexMpc handle
 QMPC_REC_DECLARE(qmpc_sense_tu)     // qmpc_loop_sense.hip
 QMPC_REC_DECLARE(qmpc_csense_tu)    // qmpc_loop_csense.hip: the sensing call on such a ConvexMpc handle
+QMPC_REC_DECLARE(qmpc_gait_tu)      // qmpc_loop_gait.hip
+QMPC_REC_DECLARE(qmpc_cgait_tu)     // qmpc_loop_cgait.hip: the gait call on such a ConvexMpc handle
 #undef QMPC_REC_DECLARE
 enum { REC_PLAIN = 0, REC_OUTCOME = 1, REC_PUSH = 2 };      // the kind of a call with records: QMPC_REC_EXT of its unit
 enum { REC_CONVEX = 3 };                                    // ... the unit that serves those three kinds for ConvexMpc's problem
 enum { REC_GROUND = 4, REC_CGROUND = 5 };                   // the ground call's kind (EXT 3), and its unit for ConvexMpc's problem
 enum { REC_ACT = 6, REC_CACT = 7 };                         // the actuation call's kind (EXT 4), and its unit for ConvexMpc's problem
 enum { REC_SENSE = 8, REC_CSENSE = 9 };                     // the sensing call's kind (EXT 5), and its unit for ConvexMpc's problem
+enum { REC_GAIT = 10, REC_CGAIT = 11 };                     // the gait call's kind (EXT 6), and its unit for ConvexMpc's problem
 static const struct {
   decltype(&qmpc_inst_tu::rec_set_lds) set_lds;
   decltype(&qmpc_inst_tu::rec_fused_launch) fused_launch;
   decltype(&qmpc_inst_tu::rec_front_launch) front_launch;
   decltype(&qmpc_inst_tu::rec_post_launch) post_launch;
-} kRec[10] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
+} kRec[12] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
              {qmpc_outc_tu::rec_set_lds, qmpc_outc_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_outc_tu::rec_post_launch},
              {qmpc_push_tu::rec_set_lds, qmpc_push_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_push_tu::rec_post_launch},
              {qmpc_crec_tu::rec_set_lds, qmpc_crec_tu::rec_fused_launch, qmpc_crec_tu::rec_front_launch, qmpc_crec_tu::rec_post_launch},
@@ -123,7 +129,9 @@ static const struct {
              {qmpc_act_tu::rec_set_lds, qmpc_act_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_act_tu::rec_post_launch},
              {qmpc_cact_tu::rec_set_lds, qmpc_cact_tu::rec_fused_launch, qmpc_cact_tu::rec_front_launch, qmpc_cact_tu::rec_post_launch},
              {qmpc_sense_tu::rec_set_lds, qmpc_sense_tu::rec_fused_launch, qmpc_sense_tu::rec_front_launch, qmpc_sense_tu::rec_post_launch},
-             {qmpc_csense_tu::rec_set_lds, qmpc_csense_tu::rec_fused_launch, qmpc_csense_tu::rec_front_launch, qmpc_csense_tu::rec_post_launch}};
+             {qmpc_csense_tu::rec_set_lds, qmpc_csense_tu::rec_fused_launch, qmpc_csense_tu::rec_front_launch, qmpc_csense_tu::rec_post_launch},
+             {qmpc_gait_tu::rec_set_lds, qmpc_gait_tu::rec_fused_launch, qmpc_gait_tu::rec_front_launch, qmpc_gait_tu::rec_post_launch},
+             {qmpc_cgait_tu::rec_set_lds, qmpc_cgait_tu::rec_fused_launch, qmpc_cgait_tu::rec_front_launch, qmpc_cgait_tu::rec_post_launch}};
 // ... and the kernels each unit has beside them: the expansions of the plant blocks and the check of the windows
 hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, const qmpc_plant_params* plant,
                                         const qmpc_instance_params* ctrl, const int* ctrl_status, void* bcast_out, void* plants_out,
@@ -139,6 +147,9 @@ hipError_t rec_act_check_launch(hipStream_t s, const qmpc_actuation_params* act,
 }
 namespace qmpc_sense_tu {
 hipError_t rec_sense_check_launch(hipStream_t s, const qmpc_sense_params* sense, void* plants, int batch);
+}
+namespace qmpc_gait_tu {
+hipError_t rec_gait_check_launch(hipStream_t s, const qmpc_gait_params* gait, void* plants, double dt, int batch);
 }
 
 // qmpc_lane.hip (third translation unit): the lane-per-instance kernel of large batches
@@ -270,6 +281,8 @@ struct qmpc_handle {
                                   // lines (896 B each), then max_batch actuation records (32 B each)
   void* d_sense;                  // staging of qmpc_loop_run_sensing (the host-buffer call), on its first use: max_batch sensing
                                   // records (256 B each), then max_batch seen records (128 B each)
+  void* d_gait;                   // staging of qmpc_loop_run_gaits (the host-buffer call), on its first use: max_batch gait records
+                                  // (128 B each)
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -499,6 +512,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_ground) (void)hipFree(h->d_ground);
   if (h->d_act) (void)hipFree(h->d_act);
   if (h->d_sense) (void)hipFree(h->d_sense);
+  if (h->d_gait) (void)hipFree(h->d_gait);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1229,6 +1243,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_ground) b += (sizeof(qmpc_ground_params) + sizeof(qmpc_ground_tally)) * (size_t)h->max_batch;
       if (h->d_act) b += (sizeof(qmpc_actuation_params) + sizeof(qmpc_actuation_line)) * (size_t)h->max_batch;
       if (h->d_sense) b += (sizeof(qmpc_sense_params) + sizeof(qmpc_sense_seen)) * (size_t)h->max_batch;
+      if (h->d_gait) b += sizeof(qmpc_gait_params) * (size_t)h->max_batch;
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
       return QMPC_OK;
@@ -1722,19 +1737,21 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
                                        qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot,
                                        const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
                                        const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
-                                       const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, void* stream);
+                                       const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
+                                       void* stream);
 
 // The host-buffer closed loop of every kind (qmpc_loop_run*, its arguments checked): states and traces through the handle's
 // staging, which only grows -- [states | force trace | contact trace]; the records given go to the staging halves of the
 // per-instance and plant buffers, outcome records and windows to h->d_outcome and h->d_push, ground records and tallies to
-// h->d_ground, actuation records and delay lines to h->d_act, sensing records and seen to h->d_sense (all allocated by the caller)
+// h->d_ground, actuation records and delay lines to h->d_act, sensing records and seen to h->d_sense, gait records to h->d_gait
+// (all allocated by the caller)
 static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
                                      int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                      double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                      const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
                                      qmpc_ground_tally* tally, const qmpc_actuation_params* act = nullptr,
                                      qmpc_actuation_line* line = nullptr, const qmpc_sense_params* sense = nullptr,
-                                     qmpc_sense_seen* seen = nullptr) {
+                                     qmpc_sense_seen* seen = nullptr, const qmpc_gait_params* gait = nullptr) {
   const size_t B = (size_t)batch, T = (size_t)ticks;
   const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
                n_tc = trace_contacts ? 4 * B * T : 0;
@@ -1765,9 +1782,11 @@ static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_p
   qmpc_sense_seen* d_sn = (sense && seen) ? reinterpret_cast<qmpc_sense_seen*>(static_cast<qmpc_sense_params*>(h->d_sense) + h->max_batch) : nullptr;
   if (d_se) HIP_TRY(hipMemcpyAsync(d_se, sense, sizeof(qmpc_sense_params) * B, hipMemcpyHostToDevice, h->stream));
   if (d_sn) HIP_TRY(hipMemcpyAsync(d_sn, seen, sizeof(qmpc_sense_seen) * B, hipMemcpyHostToDevice, h->stream));
+  qmpc_gait_params* d_ga = gait ? static_cast<qmpc_gait_params*>(h->d_gait) : nullptr;
+  if (d_ga) HIP_TRY(hipMemcpyAsync(d_ga, gait, sizeof(qmpc_gait_params) * B, hipMemcpyHostToDevice, h->stream));
   const qmpc_status rs = loop_records_device(kind, h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
                                              d_tf, d_tc, op, outcomes ? h->d_outcome : nullptr, push ? h->d_push : nullptr, per_robot,
-                                             d_gr, d_ta, d_ac, d_li, d_se, d_sn, nullptr);
+                                             d_gr, d_ta, d_ac, d_li, d_se, d_sn, d_ga, nullptr);
   if (rs != QMPC_OK) return rs;
   if (d_sn) HIP_TRY(hipMemcpyAsync(seen, d_sn, sizeof(qmpc_sense_seen) * B, hipMemcpyDeviceToHost, h->stream));
   if (d_li) HIP_TRY(hipMemcpyAsync(line, d_li, sizeof(qmpc_actuation_line) * B, hipMemcpyDeviceToHost, h->stream));
@@ -1861,13 +1880,15 @@ static qmpc_status loop_instances_buffers(qmpc_handle* h, int32_t batch, bool ha
 // NULL (no windows), d_ground is checked after the windows, d_tally may be NULL.  REC_ACT (qmpc_loop_run_actuation_device): d_ground
 // may be NULL too (no clamp; checked when given), d_act and the count of d_line are checked last.  REC_SENSE
 // (qmpc_loop_run_sensing_device): d_act may be NULL too (checked when given), d_sense is checked last, d_seen may be NULL.
+// REC_GAIT (qmpc_loop_run_gaits_device): d_sense may be NULL too (checked when given), d_gait is checked last.
 static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                        qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot,
                                        const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
                                        const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
-                                       const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, void* stream) {
+                                       const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
+                                       void* stream) {
   if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !d_states)) return QMPC_BAD_ARGUMENT;
   if (kind != REC_PLAIN && (!op || (batch > 0 && !d_outcomes))) return QMPC_BAD_ARGUMENT;
   if (kind == REC_PLAIN && !d_ctrl && !d_plant)
@@ -1888,14 +1909,14 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   // a ConvexMpc handle (opted in): one unit for the three kinds -- a call without windows passes none (per_robot = 0), a call
   // without outcome records the handle's scratch and parameters that never halt a robot
   const bool crec = convex_records(h);
-  const auto& R = kRec[kind == REC_SENSE ? (crec ? REC_CSENSE : REC_SENSE) : kind == REC_ACT ? (crec ? REC_CACT : REC_ACT) : kind == REC_GROUND ? (crec ? REC_CGROUND : REC_GROUND) : crec ? REC_CONVEX : kind];
+  const auto& R = kRec[kind == REC_GAIT ? (crec ? REC_CGAIT : REC_GAIT) : kind == REC_SENSE ? (crec ? REC_CSENSE : REC_SENSE) : kind == REC_ACT ? (crec ? REC_CACT : REC_ACT) : kind == REC_GROUND ? (crec ? REC_CGROUND : REC_GROUND) : crec ? REC_CONVEX : kind];
   qmpc_outcome_params op_none;
   std::memset(&op_none, 0, sizeof op_none);
   if (crec && kind == REC_PLAIN) {
     op = &op_none;
     d_outcomes = h->d_outcome;
   }
-  if ((crec && kind != REC_PUSH && kind != REC_GROUND && kind != REC_ACT && kind != REC_SENSE) || !d_push) {
+  if ((crec && kind != REC_PUSH && kind != REC_GROUND && kind != REC_ACT && kind != REC_SENSE && kind != REC_GAIT) || !d_push) {
     d_push = nullptr;
     per_robot = 0;
   }
@@ -1909,18 +1930,19 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   else
     HIP_TRY(qmpc_loop_outcome_expand_base_launch(s, &h->dev, sizeof h->dev, bcast, plant_dev(h), (int)batch));
   if (d_push) HIP_TRY(qmpc_loop_push_check_launch(s, d_push, (int)per_robot, plant_dev(h), (int)batch));
-  if (kind == REC_GROUND || ((kind == REC_ACT || kind == REC_SENSE) && d_ground))
+  if (kind == REC_GROUND || ((kind == REC_ACT || kind == REC_SENSE || kind == REC_GAIT) && d_ground))
     HIP_TRY(qmpc_ground_tu::rec_ground_check_launch(s, d_ground, plant_dev(h), (int)batch));
-  if (kind == REC_ACT || (kind == REC_SENSE && d_act)) HIP_TRY(qmpc_act_tu::rec_act_check_launch(s, d_act, d_line, plant_dev(h), (int)batch));
-  if (kind == REC_SENSE) HIP_TRY(qmpc_sense_tu::rec_sense_check_launch(s, d_sense, plant_dev(h), (int)batch));
+  if (kind == REC_ACT || ((kind == REC_SENSE || kind == REC_GAIT) && d_act)) HIP_TRY(qmpc_act_tu::rec_act_check_launch(s, d_act, d_line, plant_dev(h), (int)batch));
+  if (kind == REC_SENSE || (kind == REC_GAIT && d_sense)) HIP_TRY(qmpc_sense_tu::rec_sense_check_launch(s, d_sense, plant_dev(h), (int)batch));
+  if (kind == REC_GAIT) HIP_TRY(qmpc_gait_tu::rec_gait_check_launch(s, d_gait, plant_dev(h), lp->dt, (int)batch));
   if (lpp.fused) {
     HIP_TRY(R.fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, d_states, h->d_in, h->d_forces, h->d_info,
                            d_trace_forces, d_trace_contacts, (int)ticks, lpp.gws ? h->d_gws : nullptr, op, d_outcomes, d_push,
-                           (int)per_robot, d_ground, d_tally, d_act, d_line, d_sense, d_seen));
+                           (int)per_robot, d_ground, d_tally, d_act, d_line, d_sense, d_seen, d_gait));
     return QMPC_OK;
   }
   auto one_tick = [&](bool first) -> qmpc_status {
-    HIP_TRY(R.front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch, op, d_outcomes, d_sense, d_seen));
+    HIP_TRY(R.front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch, op, d_outcomes, d_sense, d_seen, d_gait));
     // with controller records the solve on the blocks expanded above (a warm-started call's solution travels through
     // h->d_traj_u), without them the plain loop's
     const qmpc_status st = !d_ctrl ? loop_tick_solve(h, batch, s, warm, first, crec)
@@ -1941,7 +1963,7 @@ qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_param
                                            int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                            double* d_trace_forces, double* d_trace_contacts, void* stream) {
   return loop_records_device(REC_PLAIN, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, nullptr, nullptr,
-                             nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+                             nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -1985,20 +2007,21 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
                                           double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                           qmpc_loop_outcome* d_outcomes, void* stream) {
   return loop_records_device(REC_OUTCOME, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
-                             nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+                             nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // the host-buffer call's checks and buffers (the staging itself: loop_records_host); push (qmpc_loop_run_pushes; NULL:
 // qmpc_loop_run_outcomes): per_robot windows per robot, staged in h->d_push; ground (qmpc_loop_run_ground, with or without push)
 // and tally (or NULL): staged in h->d_ground; act and line (qmpc_loop_run_actuation, with or without ground): staged in h->d_act;
-// sense and seen (or NULL) (qmpc_loop_run_sensing, with or without act): staged in h->d_sense
+// sense and seen (or NULL) (qmpc_loop_run_sensing, with or without act): staged in h->d_sense; gait (qmpc_loop_run_gaits, with or
+// without sense): staged in h->d_gait
 static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
                                       const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                       double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                       const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
                                       qmpc_ground_tally* tally, const qmpc_actuation_params* act = nullptr,
                                       qmpc_actuation_line* line = nullptr, const qmpc_sense_params* sense = nullptr,
-                                      qmpc_sense_seen* seen = nullptr) {
+                                      qmpc_sense_seen* seen = nullptr, const qmpc_gait_params* gait = nullptr) {
   if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!states || !outcomes))) return QMPC_BAD_ARGUMENT;
   const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
@@ -2014,17 +2037,18 @@ static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp
   }
   // (the push call's ticks = 0 allocates everything a later push call needs, the records' staging included; the outcome call's
   // ticks = 0 stops before it, as it always did)
-  if ((push || ground || act || sense) && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
+  if ((push || ground || act || sense || gait) && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
   if (ground && !h->d_ground)
     HIP_TRY(hipMalloc(&h->d_ground, (sizeof(qmpc_ground_params) + sizeof(qmpc_ground_tally)) * (size_t)h->max_batch));
   if (act && !h->d_act)
     HIP_TRY(hipMalloc(&h->d_act, (sizeof(qmpc_actuation_params) + sizeof(qmpc_actuation_line)) * (size_t)h->max_batch));
   if (sense && !h->d_sense)
     HIP_TRY(hipMalloc(&h->d_sense, (sizeof(qmpc_sense_params) + sizeof(qmpc_sense_seen)) * (size_t)h->max_batch));
+  if (gait && !h->d_gait) HIP_TRY(hipMalloc(&h->d_gait, sizeof(qmpc_gait_params) * (size_t)h->max_batch));
   if (ticks == 0) return es;
   if (!h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
-  return loop_records_host(sense ? REC_SENSE : act ? REC_ACT : ground ? REC_GROUND : push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant,
-                           trace_forces, trace_contacts, op, outcomes, push, per_robot, ground, tally, act, line, sense, seen);
+  return loop_records_host(gait ? REC_GAIT : sense ? REC_SENSE : act ? REC_ACT : ground ? REC_GROUND : push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant,
+                           trace_forces, trace_contacts, op, outcomes, push, per_robot, ground, tally, act, line, sense, seen, gait);
 }
 
 qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2047,7 +2071,7 @@ qmpc_status qmpc_loop_run_pushes_device(qmpc_handle* h, const qmpc_loop_params* 
                                          stream);
   if (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES) return QMPC_BAD_ARGUMENT;
   return loop_records_device(REC_PUSH, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             pushes_per_robot, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+                             pushes_per_robot, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_pushes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2090,7 +2114,7 @@ qmpc_status qmpc_loop_run_ground_device(qmpc_handle* h, const qmpc_loop_params* 
                                        pushes_per_robot, stream);
   if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
   return loop_records_device(REC_GROUND, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             d_push ? pushes_per_robot : 0, d_ground, d_tally, nullptr, nullptr, nullptr, nullptr, stream);
+                             d_push ? pushes_per_robot : 0, d_ground, d_tally, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_ground(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2144,7 +2168,7 @@ qmpc_status qmpc_loop_run_actuation_device(qmpc_handle* h, const qmpc_loop_param
   if (!d_line) return QMPC_BAD_ARGUMENT;
   if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
   return loop_records_device(REC_ACT, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_line, nullptr, nullptr, stream);
+                             d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_line, nullptr, nullptr, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_actuation(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2198,7 +2222,7 @@ qmpc_status qmpc_loop_run_sensing_device(qmpc_handle* h, const qmpc_loop_params*
   if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
   return loop_records_device(REC_SENSE, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
                              d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_act ? d_line : nullptr, d_sense,
-                             d_seen, stream);
+                             d_seen, nullptr, stream);
 }
 
 qmpc_status qmpc_loop_run_sensing(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2214,6 +2238,63 @@ qmpc_status qmpc_loop_run_sensing(qmpc_handle* h, const qmpc_loop_params* lp, in
   if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
   return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
                             push ? pushes_per_robot : 0, ground, ground ? tally : nullptr, act, act ? line : nullptr, sense, seen);
+}
+
+// ---- the sensing loop in which every robot walks a gait of its own (qmpc_loop_gait.hip, qmpc_loop_cgait.hip) ---------------------
+static_assert(sizeof(qmpc_gait_params) == 128, "qmpc_gait_params is 16 doubles");
+int32_t qmpc_sizeof_gait_params(void) { return (int32_t)sizeof(qmpc_gait_params); }
+
+void qmpc_default_gait_params(const qmpc_loop_params* lp, qmpc_gait_params* out) {
+  if (!lp || !out) return;
+  out->gait_freq = lp->gait_freq;
+  for (int l = 0; l < 4; ++l) {
+    out->first_stance[l] = (l == 0 || l == 3) ? 1.0 : 0.0;
+    out->split[l] = 0.5;
+    out->phase0[l] = 0.0;
+  }
+  for (int c = 0; c < 3; ++c) out->reserved[c] = 0.0;
+}
+
+void qmpc_loop_state_set_gait(qmpc_loop_state* s, const qmpc_gait_params* gait) {
+  if (!s || !gait) return;
+  for (int l = 0; l < 4; ++l) {
+    qmpc_loop::loop_gait_reset(*gait, l, s->leg[l]);
+    s->contacts[l] = s->leg[l].state;
+  }
+}
+
+qmpc_status qmpc_loop_run_gaits_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                       int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                       double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                       qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
+                                       const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
+                                       const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
+                                       void* stream) {
+  if (!d_gait)
+    return qmpc_loop_run_sensing_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
+                                        d_push, pushes_per_robot, d_ground, d_tally, d_act, d_line, d_sense, d_seen, stream);
+  if (d_act && !d_line) return QMPC_BAD_ARGUMENT;
+  if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
+  return loop_records_device(REC_GAIT, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
+                             d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_act ? d_line : nullptr, d_sense,
+                             d_sense ? d_seen : nullptr, d_gait, stream);
+}
+
+qmpc_status qmpc_loop_run_gaits(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
+                                const qmpc_push_params* push, int32_t pushes_per_robot, const qmpc_ground_params* ground,
+                                qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line,
+                                const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait) {
+  if (!gait)
+    return qmpc_loop_run_sensing(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
+                                 pushes_per_robot, ground, tally, act, line, sense, seen);
+  if (act && !line) return QMPC_BAD_ARGUMENT;
+  if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
+  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
+                            push ? pushes_per_robot : 0, ground, ground ? tally : nullptr, act, act ? line : nullptr, sense,
+                            sense ? seen : nullptr, gait);
 }
 
 // Diagnostic: per-instance phase cycle counts (s_memtime) of one solve launch.

@@ -229,6 +229,51 @@ __device__ inline void loop_foot_update(const qmpc_loop_params& LP, qmpc_loop_st
     for (int a = 0; a < 3; ++a) s.foot_target_world[3 * l + a] = s.leg[l].fsm_pos[a];
 }
 
+// ---- the same three steps for a robot with a gait of its own (qmpc_loop_run_gaits*; the rule: loop_gait_* of qmpc_loop_math.h) ----
+// Raibert targets with the leg's own stance time: loop_raibert with the offset d formed and clamped per leg
+__device__ inline void loop_raibert_gait(const qmpc_loop_params& LP, const qmpc_gait_params& G, const qmpc_loop_state& s,
+                                         const double* Rz, double* tgt_world) {
+#pragma clang fp contract(off)
+  double vrel[3];
+  for (int r = 0; r < 3; ++r) vrel[r] = Rz[r] * s.lin_vel_world[0] + Rz[3 + r] * s.lin_vel_world[1] + Rz[6 + r] * s.lin_vel_world[2];
+  const double k = sqrt(fabs(s.pos_world[2]) / 9.81);
+  for (int l = 0; l < 4; ++l) {
+    double d[3], dabs[3], ab[3];
+    qmpc_loop::loop_gait_raibert_delta(G, l, k, vrel, s.lin_vel_d_rel, d);
+    for (int r = 0; r < 3; ++r) dabs[r] = Rz[3 * r] * d[0] + Rz[3 * r + 1] * d[1] + Rz[3 * r + 2] * d[2];
+    for (int r = 0; r < 3; ++r)
+      ab[r] = Rz[3 * r] * LP.default_foot_pos_rel[3 * l] + Rz[3 * r + 1] * LP.default_foot_pos_rel[3 * l + 1] +
+              Rz[3 * r + 2] * LP.default_foot_pos_rel[3 * l + 2];
+    ab[0] += dabs[0];
+    ab[1] += dabs[1];
+    for (int r = 0; r < 3; ++r) tgt_world[3 * l + r] = ab[r] + s.pos_world[r];
+  }
+}
+// the reset of the four legs (every tick of movement_mode 0): the record's pattern at the legs' own starting phases
+__device__ inline void loop_fsm_reset_gait(const qmpc_gait_params& G, qmpc_loop_state& s) {
+  for (int l = 0; l < 4; ++l) {
+    qmpc_loop::loop_gait_reset(G, l, s.leg[l]);
+    s.contacts[l] = 1.0;
+  }
+}
+// foot_update with the record's frequency, pattern and swing fraction
+__device__ inline void loop_foot_update_gait(const qmpc_gait_params& G, qmpc_loop_state& s, const double* tgt_world, const double* flag) {
+#pragma clang fp contract(off)
+  if (s.movement_mode == 0.0) {
+    loop_fsm_reset_gait(G, s);
+  } else {
+    for (int l = 0; l < 4; ++l)
+      s.gait_counter[l] = qmpc_loop::loop_gait_update(G, l, s.leg[l], 5.0 / 1000.0, &s.foot_pos_world[3 * l], &tgt_world[3 * l],
+                                                      flag[l] != 0.0,
+                                                      [](float t, float T, const double* start, const double* fin, double* out) {
+                                                        loop_swing_target(t, T, start, fin, out);
+                                                      });
+    for (int l = 0; l < 4; ++l) s.contacts[l] = s.leg[l].state;
+  }
+  for (int l = 0; l < 4; ++l)
+    for (int a = 0; a < 3; ++a) s.foot_target_world[3 * l + a] = s.leg[l].fsm_pos[a];
+}
+
 template <int OCC = 1>
 QMPC_LOOP_FN void loop_front_one(const qmpc_loop_params& LP, qmpc_loop_state& s, qmpc_input& in) {
 #pragma clang fp contract(off)
@@ -312,6 +357,101 @@ QMPC_LOOP_FN void loop_front_convex_one(const qmpc_loop_params& LP, qmpc_loop_st
     vw[r] = Rz[3 * r] * s.lin_vel_d_rel[0] + Rz[3 * r + 1] * s.lin_vel_d_rel[1] + Rz[3 * r + 2] * s.lin_vel_d_rel[2];
   loop_foot_update(LP, s, tgt_world, flag);
   // record (ConvexMpc.cpp:92-118,156-167)
+  qmpc_loop::quat_to_euler(s.quat, in.euler);
+  for (int r = 0; r < 3; ++r) {
+    in.pos_world[r] = s.pos_world[r];
+    in.ang_vel_world[r] = R[3 * r] * s.ang_vel_body[0] + R[3 * r + 1] * s.ang_vel_body[1] + R[3 * r + 2] * s.ang_vel_body[2];
+    in.lin_vel_world[r] = s.lin_vel_world[r];
+    in.pos_d_world[r] = s.pos_d_world[r];
+    in.lin_vel_d_world[r] = vw[r];
+  }
+  for (int l = 0; l < 4; ++l) {
+    for (int r = 0; r < 3; ++r)
+      in.foot_pos_abs_com[3 * l + r] = R[3 * r] * foot_body[3 * l] + R[3 * r + 1] * foot_body[3 * l + 1] + R[3 * r + 2] * foot_body[3 * l + 2];
+    in.contacts[l] = (s.contacts[l] != 0.0) ? 1.0 : 0.0;
+  }
+  in.yaw_rate_d = s.joy[5];
+  for (int a = 0; a < 13; ++a) in.reserved[a] = 0.0;
+}
+
+// ---- the two front ends for a robot with a gait of its own (qmpc_loop_run_gaits*, a non-identity record G) -------------------
+// loop_front_one / loop_front_convex_one with loop_raibert_gait and loop_foot_update_gait in the place of loop_raibert and
+// loop_foot_update; every other line is theirs.  Instantiated in qmpc_loop_gait.hip / qmpc_loop_cgait.hip only.
+template <int OCC = 1>
+QMPC_LOOP_FN void loop_front_gait_one(const qmpc_loop_params& LP, qmpc_loop_state& s, qmpc_input& in, const qmpc_gait_params& G) {
+#pragma clang fp contract(off)
+  double R[9], Rz[9], foot_body[12], flag[4], tgt_world[12];
+  loop_feedback(LP, s, R, Rz, foot_body, flag);
+  loop_raibert_gait(LP, G, s, Rz, tgt_world);
+  double vel_f[3], pos_f[3], wd[3];
+  {
+    if (s.pos_d_init == 0.0) {
+      for (int a = 0; a < 3; ++a) s.pos_d_world[a] = s.pos_world[a];
+      s.pos_d_init = 1.0;
+    }
+    s.lin_vel_d_rel[0] = s.joy[0];
+    s.lin_vel_d_rel[1] = s.joy[1];
+    s.lin_vel_d_rel[2] = 0.0;
+    double vw[3], vb[3];
+    for (int r = 0; r < 3; ++r)
+      vw[r] = Rz[3 * r] * s.lin_vel_d_rel[0] + Rz[3 * r + 1] * s.lin_vel_d_rel[1] + Rz[3 * r + 2] * s.lin_vel_d_rel[2];
+    for (int r = 0; r < 3; ++r) vb[r] = R[r] * vw[0] + R[3 + r] * vw[1] + R[6 + r] * vw[2];
+    for (int a = 0; a < 3; ++a) vel_f[a] = loop_filter(s.vel_filter[a], vb[a]);
+    wd[0] = s.joy[3]; wd[1] = s.joy[4]; wd[2] = s.joy[5];
+    s.pos_d_world[0] += vw[0] * 5.0 / 1000.0;
+    s.pos_d_world[1] += vw[1] * 5.0 / 1000.0;
+    s.pos_d_world[2] = s.joy[2];
+    double dp[3], pb[3];
+    for (int a = 0; a < 3; ++a) dp[a] = s.pos_d_world[a] - s.pos_world[a];
+    for (int r = 0; r < 3; ++r) pb[r] = R[r] * dp[0] + R[3 + r] * dp[1] + R[6 + r] * dp[2];
+    for (int a = 0; a < 3; ++a) pos_f[a] = loop_filter(s.pos_filter[a], pb[a]);
+  }
+  loop_foot_update_gait(G, s, tgt_world, flag);
+  {
+    double* qd = s.quat_d;
+    const double gw[4] = {-qd[1] * wd[0] - qd[2] * wd[1] - qd[3] * wd[2], qd[0] * wd[0] - qd[3] * wd[1] + qd[2] * wd[2],
+                          qd[3] * wd[0] + qd[0] * wd[1] - qd[1] * wd[2], -qd[2] * wd[0] + qd[1] * wd[1] + qd[0] * wd[2]};
+    for (int a = 0; a < 4; ++a) qd[a] += 0.5 * gw[a] * 5.0 / 1000.0;
+    const double n = sqrt(qd[0] * qd[0] + qd[1] * qd[1] + qd[2] * qd[2] + qd[3] * qd[3]);
+    for (int a = 0; a < 4; ++a) qd[a] = qd[a] / n;
+    if (s.sin_ang_vel != 0.0) {
+      const double e = 3.14 / 8 * sin(2 * 3.14 / 900 * s.attitude_traj_count);
+      s.attitude_traj_count += 1.0;
+      const double hr = e / 2;
+      const double c = cos(hr), sn = sin(hr);
+      qd[0] = c * c * c + sn * sn * sn;
+      qd[1] = c * c * sn - sn * sn * c;
+      qd[2] = c * sn * c + sn * c * sn;
+      qd[3] = sn * c * c - c * sn * sn;
+    }
+  }
+  for (int a = 0; a < 4; ++a) { in.quat[a] = s.quat[a]; in.quat_d[a] = s.quat_d[a]; in.contacts[a] = (s.contacts[a] != 0.0) ? 1.0 : 0.0; }
+  for (int a = 0; a < 9; ++a) in.rot[a] = R[a];
+  for (int r = 0; r < 3; ++r) {
+    in.lin_vel_body[r] = R[r] * s.lin_vel_world[0] + R[3 + r] * s.lin_vel_world[1] + R[6 + r] * s.lin_vel_world[2];
+    in.ang_vel_body[r] = s.ang_vel_body[r];
+    in.pos_ref_body[r] = pos_f[r];
+    in.vel_ref_body[r] = vel_f[r];
+    in.acc_ref_body[r] = 0.0;
+  }
+  for (int a = 0; a < 12; ++a) in.foot_pos_body[a] = foot_body[a];
+}
+template <int OCC = 1>
+QMPC_LOOP_FN void loop_front_convex_gait_one(const qmpc_loop_params& LP, qmpc_loop_state& s, qmpc_convex_input& in,
+                                             const qmpc_gait_params& G) {
+#pragma clang fp contract(off)
+  double R[9], Rz[9], foot_body[12], flag[4], tgt_world[12];
+  loop_feedback(LP, s, R, Rz, foot_body, flag);
+  loop_raibert_gait(LP, G, s, Rz, tgt_world);
+  s.pos_d_world[2] = s.joy[2];
+  if (s.lin_vel_d_rel[0] < s.joy[0]) s.lin_vel_d_rel[0] += 1.0 * 5.0 / 1000.0;
+  else if (s.lin_vel_d_rel[0] > s.joy[0]) s.lin_vel_d_rel[0] -= 1.0 * 5.0 / 1000.0;
+  s.lin_vel_d_rel[1] = s.joy[1];
+  s.lin_vel_d_rel[2] = 0.0;
+  double vw[3];
+  for (int r = 0; r < 3; ++r)
+    vw[r] = Rz[3 * r] * s.lin_vel_d_rel[0] + Rz[3 * r + 1] * s.lin_vel_d_rel[1] + Rz[3 * r + 2] * s.lin_vel_d_rel[2];
+  loop_foot_update_gait(G, s, tgt_world, flag);
   qmpc_loop::quat_to_euler(s.quat, in.euler);
   for (int r = 0; r < 3; ++r) {
     in.pos_world[r] = s.pos_world[r];

@@ -426,6 +426,149 @@ QMPC_HD void loop_sense_one(const qmpc_sense_params& p, double tick, const doubl
   }
 }
 
+// ---- a robot's own gait (qmpc_loop_run_gaits*, include/qmpc.h): the rule, for the kernels, the host classes and the tests ----
+// The leg's two-entry pattern and its switch times
+QMPC_HD double loop_gait_pattern(const qmpc_gait_params& g, int leg, int idx) {
+  return (idx == 0) == (g.first_stance[leg] != 0.0) ? 1.0 : 0.0;
+}
+QMPC_HD double loop_gait_switch_time(const qmpc_gait_params& g, int leg, int idx) { return idx == 0 ? g.split[leg] : 1.0; }
+// the fraction of a cycle the leg swings (the trot's 0.5 in the reference's swing times and Raibert stance time)
+QMPC_HD double loop_gait_swing_fraction(const qmpc_gait_params& g, int leg) {
+  QMPC_NO_CONTRACT
+  return g.first_stance[leg] != 0.0 ? 1.0 - g.split[leg] : g.split[leg];
+}
+
+// A record is the identity when it is the reference's trot at the call's frequency: its robot takes the front end as it stands
+QMPC_HD bool loop_gait_identity(const qmpc_gait_params& g, double lp_gait_freq) {
+  bool id = g.gait_freq == lp_gait_freq;
+  for (int l = 0; l < 4; ++l)
+    id = id && g.first_stance[l] == ((l == 0 || l == 3) ? 1.0 : 0.0) && g.split[l] == 0.5 && g.phase0[l] == 0.0;
+  return id;
+}
+
+// x in [0, 2) -> its fractional part; exact
+QMPC_HD double loop_gait_frac(double x) {
+  QMPC_NO_CONTRACT
+  return x >= 1.0 ? x - 1.0 : x;
+}
+
+// ... and valid when (include/qmpc.h) every field is finite and the reserved words are 0, 0 < gait_freq and gait_freq * dt <= 1/16,
+// first_stance is 0 or 1, split is a multiple of 2^-8 in [1/8, 7/8], phase0 a multiple of 2^-8 in [0, 1), and no flight is
+// planned: the end of every leg's stance arc, in the robot's phase, lies in some leg's stance arc.  All of the arc arithmetic is
+// exact: sums and differences of multiples of 2^-8 below 2.
+QMPC_HD bool loop_gait_valid(const qmpc_gait_params& g, double dt) {
+  QMPC_NO_CONTRACT
+  bool ok = (g.gait_freq - g.gait_freq == 0.0) && g.gait_freq > 0.0 && g.gait_freq * dt <= 0.0625;
+  for (int c = 0; c < 3; ++c) ok = ok && g.reserved[c] == 0.0;
+  for (int l = 0; l < 4; ++l) {
+    const double fs = g.first_stance[l], sp = g.split[l], ph = g.phase0[l];
+    ok = ok && (fs == 0.0 || fs == 1.0);
+    ok = ok && sp >= 0.125 && sp <= 0.875 && sp * 256.0 == (double)(int)(sp * 256.0);
+    ok = ok && ph >= 0.0 && ph < 1.0 && ph * 256.0 == (double)(int)(ph * 256.0);
+  }
+  if (!ok) return false;
+  double A[4], len[4];
+  for (int l = 0; l < 4; ++l) {
+    const bool fs = g.first_stance[l] != 0.0;
+    const double a = fs ? 0.0 : g.split[l];
+    len[l] = fs ? g.split[l] : 1.0 - g.split[l];
+    A[l] = loop_gait_frac(a - g.phase0[l] + 1.0);
+  }
+  for (int l = 0; l < 4; ++l) {
+    const double E = loop_gait_frac(A[l] + len[l]);
+    bool covered = false;
+    for (int m = 0; m < 4; ++m) covered = covered || loop_gait_frac(E - A[m] + 1.0) < len[m];
+    ok = ok && covered;
+  }
+  return ok;
+}
+
+// The reset of one leg (LeggedContactFSM.cpp:11-31 with the record's pattern and the leg's own starting phase)
+QMPC_HD void loop_gait_reset(const qmpc_gait_params& g, int leg, qmpc_loop_leg& L) {
+  const double ph = g.phase0[leg], sp = g.split[leg];
+  const int idx = ph < sp ? 0 : 1;
+  L.gait_phase = ph;
+  L.pattern_index = (double)idx;
+  L.prev_pattern_index = (double)(1 - idx);
+  L.start_time = idx ? sp : 0.0;
+  L.end_time = idx ? 1.0 : sp;
+  if (L.state == 0.0) {
+    for (int a = 0; a < 3; ++a) { L.fsm_pos[a] = L.swing_end[a]; L.fsm_vel[a] = 0.0; }
+  }
+  L.state = loop_gait_pattern(g, leg, idx);
+  L.not_first_call = 0.0;
+}
+QMPC_HD void loop_gait_common_enter(const qmpc_gait_params& g, int leg, qmpc_loop_leg& L) {   // :208-223
+  QMPC_NO_CONTRACT
+  const int prev = (int)L.pattern_index;
+  const int idx = (prev + 1) % 2;
+  L.prev_pattern_index = (double)prev;
+  L.pattern_index = (double)idx;
+  if (idx < prev) L.gait_phase -= 1.0;
+  L.start_time = L.gait_phase;
+  L.end_time = loop_gait_switch_time(g, leg, idx);
+}
+QMPC_HD double loop_gait_percent(const qmpc_loop_leg& L) {   // :261-270
+  QMPC_NO_CONTRACT
+  double percent = (L.gait_phase - L.start_time) / (L.end_time - L.start_time);
+  if (percent < 0.0) percent = 0.0;
+  else if (percent > 1.0) percent = 1.0;
+  return percent;
+}
+// One update of one leg (:33-78): the schedule step and the foot targets of the state entered / held.  swing(t, T, start, fin,
+// out) is the side's swing-foot quintic (the device's loop_swing_target, the host's QuinticCurveHip).
+template <class Swing>
+QMPC_HD double loop_gait_update(const qmpc_gait_params& g, int leg, qmpc_loop_leg& L, double dt, const double* cur, const double* tgt,
+                                bool flag, Swing swing) {
+  QMPC_NO_CONTRACT
+  if (L.not_first_call == 0.0) {
+    for (int a = 0; a < 3; ++a) {
+      L.swing_start[a] = cur[a];
+      L.swing_end[a] = tgt[a];
+      L.fsm_pos[a] = tgt[a];
+      L.fsm_vel[a] = 0.0;
+    }
+    L.not_first_call = 1.0;
+  }
+  L.gait_phase += g.gait_freq * dt;
+  if (L.state == 1.0) {
+    if (L.gait_phase >= L.end_time) {
+      L.terrain_height = cur[2];                        // stance_exit
+      loop_gait_common_enter(g, leg, L);                // swing_enter
+      for (int a = 0; a < 3; ++a) { L.swing_start[a] = cur[a]; L.swing_extend[a] = 0.0; }
+      L.state = 0.0;
+    }
+  } else {
+    if ((loop_gait_percent(L) > 0.9 && flag) || loop_gait_percent(L) >= 1.0) {
+      L.state = 1.0;
+      loop_gait_common_enter(g, leg, L);                // stance_enter
+      for (int a = 0; a < 3; ++a) { L.fsm_pos[a] = cur[a]; L.fsm_vel[a] = 0.0; }
+    }
+  }
+  if (L.state == 0.0) {                                 // swing_update
+    const double t = loop_gait_percent(L);
+    const double w = loop_gait_swing_fraction(g, leg);
+    double fin[3], out[9];
+    for (int a = 0; a < 3; ++a) fin[a] = tgt[a] + L.swing_extend[a];
+    swing((float)(w * t / g.gait_freq), (float)(w / g.gait_freq), L.swing_start, fin, out);
+    for (int a = 0; a < 3; ++a) { L.fsm_pos[a] = out[a]; L.fsm_vel[a] = out[3 + a]; L.fsm_acc[a] = out[6 + a]; }
+  }
+  return L.gait_phase;
+}
+// Raibert foothold offset of one leg in the yaw frame (BaseInterface.cpp:266-288 with the leg's own stance time (1 / f)(1 - w)):
+// vrel = R_z' v, vd = last tick's torso_lin_vel_d_rel, k = sqrt(|z| / 9.81); d (3) receives the clamped offset, d[2] = 0
+QMPC_HD void loop_gait_raibert_delta(const qmpc_gait_params& g, int leg, double k, const double* vrel, const double* vd, double* d) {
+  QMPC_NO_CONTRACT
+  const double w = loop_gait_swing_fraction(g, leg);
+  d[0] = k * (vrel[0] - vd[0]) + (1.0 / g.gait_freq) * (1.0 - w) * vd[0];
+  if (d[0] < -0.5) d[0] = -0.5;
+  if (d[0] > 0.5) d[0] = 0.5;
+  d[1] = k * (vrel[1] - vd[1]) + (1.0 / g.gait_freq) * (1.0 - w) * vd[1];
+  if (d[1] < -0.3) d[1] = -0.3;
+  if (d[1] > 0.3) d[1] = 0.3;
+  d[2] = 0.0;
+}
+
 // Condition matrix of the swing-foot quintic p(t) = sum_k a_k t^k (QuinticCurve::get_foot_swing_target,
 // Utils.cpp:236-293): rows p(0), p(T), p'(0), p'(T), p(T/2), p'(T/2).  Generated, with the reference's FLOAT
 // evaluation order so that every entry carries the same rounding as upstream's hand-written expressions: a power is

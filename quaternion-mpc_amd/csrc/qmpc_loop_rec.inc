@@ -1,6 +1,6 @@
 // qmpc_loop_rec.inc -- the kernels of the closed loop with per-robot records and their launchers, defined once.  Included by
-// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip, qmpc_loop_ground.hip, qmpc_loop_act.hip and qmpc_loop_sense.hip
-// inside the unit's namespace, after qmpc_loop.hip, with
+// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip, qmpc_loop_ground.hip, qmpc_loop_act.hip, qmpc_loop_sense.hip and
+// qmpc_loop_gait.hip inside the unit's namespace, after qmpc_loop.hip, with
 //   QMPC_REC_EXT 0   controller and plant records only                          (qmpc_loop_run_instances*)
 //                1   ... and the outcome step after the post step               (qmpc_loop_run_outcomes*)
 //                2   ... whose plant step integrates under timed push windows   (qmpc_loop_run_pushes*)
@@ -9,7 +9,9 @@
 //                4   ... through the robot's delay line and actuator lag         (qmpc_loop_run_actuation*; qmpc_loop_cact.hip: the
 //                    same with QMPC_REC_CONVEX; the ground record may be absent)
 //                5   ... whose controller reads a measured state                 (qmpc_loop_run_sensing*; qmpc_loop_csense.hip: the
-//                    same with QMPC_REC_CONVEX; the actuation record may be absent too).  The one layer in the FRONT end
+//                    same with QMPC_REC_CONVEX; the actuation record may be absent too).  The first layer in the FRONT end
+//                6   ... and walks the robot's own gait                          (qmpc_loop_run_gaits*; qmpc_loop_cgait.hip: the
+//                    same with QMPC_REC_CONVEX; the sensing record may be absent too)
 // and, for the sibling controller (qmpc_loop_crec.hip; a handle opts in with qmpc_set_convex_records),
 //   QMPC_REC_CONVEX  defined: ConvexMpc's problem -- ConvexModel and the wrench-form body with QMPC_WMODEL WM_CONVEX, the front
 //                    end loop_front_convex_one on qmpc_convex_input records, the world-frame back end with the robot's plant
@@ -18,7 +20,7 @@
 // Textual inclusion, not a template over EXT: each unit compiles to the instructions it had as a file of its own (a shared
 // __forceinline__ function template moved the register assignment of every kernel; DESIGN.md).  The parameters a smaller EXT
 // does not have are written with the two macros below; a kernel's parameter list is that of its EXT and of no other.
-//   per tick    qmpc_loop_rec_front_kernel (EXT 0 / 1 / 5; the calls of EXT 2-4 launch the outcome unit's) and qmpc_loop_rec_post_kernel
+//   per tick    qmpc_loop_rec_front_kernel (EXT 0 / 1 / 5 / 6; the calls of EXT 2-4 launch the outcome unit's) and qmpc_loop_rec_post_kernel
 //               around the solve the C entry point launches
 //   persistent  qmpc_loop_rec_fused_kernel<3|5|6>: qmpc_loop_fused_kernel<VAR, false, false, false> (QuatMpc's problem,
 //               converged mode, wrench-form body) with the robot's own controller and plant
@@ -76,6 +78,17 @@
 #define QMPC_REC_SENSE(...) __VA_ARGS__
 #else
 #define QMPC_REC_SENSE(...)
+#endif
+#if QMPC_REC_EXT >= 6
+#define QMPC_REC_GAIT(...) __VA_ARGS__
+// the front end of a robot with a non-identity gait record g_
+#ifdef QMPC_REC_CONVEX
+#define QMPC_REC_FRONT_GAIT(OCC_, LP_, s_, r_, g_) loop_front_convex_gait_one<OCC_>(LP_, s_, reinterpret_cast<qmpc_convex_input&>(r_), g_)
+#else
+#define QMPC_REC_FRONT_GAIT(OCC_, LP_, s_, r_, g_) loop_front_gait_one<OCC_>(LP_, s_, r_, g_)
+#endif
+#else
+#define QMPC_REC_GAIT(...)
 #endif
 
 // the trace row of a robot that does not move in this tick
@@ -323,12 +336,26 @@ QMPC_LOOP_FN void loop_post_plant_world_one(const PlantDev& pl, const qmpc_loop_
 // them is written in their place, the front end runs unchanged -- it writes none of the 13 --, the true doubles are put back as
 // bytes and seen, when given, takes the measurement.  sense and seen point into global memory and are reached here, inside
 // the front step: the 13 saved doubles live across the front end's call only, nothing of the feature across the solve.
+// EXT 6 (qmpc_loop_run_gaits*): gait points at the robot's 128 B gait record in global memory, or is null.  Where this text says
+// "the front end" a robot with a non-identity record runs loop_front_gait_one / loop_front_convex_gait_one on that record, read
+// by reference inside that call; a robot without one, or with the identity, the fixed front end.  Nothing else changes.
 template <int OCC = 1>
 QMPC_LOOP_FN void loop_front_sense_one(const qmpc_loop_params& LP, qmpc_loop_state& s, qmpc_input& in,
-                                       const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen) {
+                                       const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen
+                                       QMPC_REC_GAIT(, const qmpc_gait_params* __restrict__ gait)) {
 #pragma clang fp contract(off)
+#if QMPC_REC_EXT >= 6
+  const bool walk = gait && !qmpc_loop::loop_gait_identity(*gait, LP.gait_freq);
+#define QMPC_REC_FRONT_PICK()                              \
+  do {                                                     \
+    if (walk) QMPC_REC_FRONT_GAIT(OCC, LP, s, in, *gait);  \
+    else QMPC_REC_FRONT(OCC, LP, s, in);                   \
+  } while (0)
+#else
+#define QMPC_REC_FRONT_PICK() QMPC_REC_FRONT(OCC, LP, s, in)
+#endif
   if (!sense || qmpc_loop::loop_sense_identity(*sense)) {
-    QMPC_REC_FRONT(OCC, LP, s, in);
+    QMPC_REC_FRONT_PICK();
     return;
   }
   double x[13], m[13];
@@ -341,9 +368,10 @@ QMPC_LOOP_FN void loop_front_sense_one(const qmpc_loop_params& LP, qmpc_loop_sta
     for (int a = 0; a < 13; ++a) seen->meas[a] = m[a];
     seen->ticks += 1.0;
   }
-  QMPC_REC_FRONT(OCC, LP, s, in);
+  QMPC_REC_FRONT_PICK();
   for (int a = 0; a < 3; ++a) { s.pos_world[a] = x[a]; s.lin_vel_world[a] = x[7 + a]; s.ang_vel_body[a] = x[10 + a]; }
   for (int a = 0; a < 4; ++a) s.quat[a] = x[3 + a];
+#undef QMPC_REC_FRONT_PICK
 }
 #endif
 
@@ -354,7 +382,8 @@ QMPC_LOOP_FN void loop_front_sense_one(const qmpc_loop_params& LP, qmpc_loop_sta
 __global__ __launch_bounds__(64) void qmpc_loop_rec_front_kernel(
     qmpc_loop_params LP, QMPC_REC_OUTCOME(qmpc_outcome_params OP, ) qmpc_loop_state* __restrict__ st, qmpc_input* __restrict__ rec,
     int* __restrict__ row, const PlantDev* __restrict__ pl, QMPC_REC_OUTCOME(const qmpc_loop_outcome* __restrict__ oc, )
-    QMPC_REC_SENSE(const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen, ) int batch) {
+    QMPC_REC_SENSE(const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen, )
+    QMPC_REC_GAIT(const qmpc_gait_params* __restrict__ gait, ) int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0 && row) *row += 1;                         // trace row of this tick (stream order: after the last post)
   if (i >= batch) return;
@@ -363,7 +392,8 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_front_kernel(
     return;
   }
 #if QMPC_REC_EXT >= 5
-  loop_front_sense_one<1>(LP, st[i], rec[i], sense ? sense + (size_t)i : nullptr, seen ? seen + (size_t)i : nullptr);
+  loop_front_sense_one<1>(LP, st[i], rec[i], sense ? sense + (size_t)i : nullptr, seen ? seen + (size_t)i : nullptr
+                          QMPC_REC_GAIT(, gait ? gait + (size_t)i : nullptr));
 #else
   QMPC_REC_FRONT(1, LP, st[i], rec[i]);
 #endif
@@ -422,6 +452,7 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
 // 96 B applied read-modify-written, the ring indexed in global memory with the run-time slot number (no local array, no scratch).
 // EXT 5: lane 0's FRONT step reaches the robot's 256 B sensing record and its 128 B seen by pointer (loop_front_sense_one): the 13
 // true doubles it saves live across the front end's call only -- the same rule, nothing of the feature is live across the solve.
+// EXT 6: ... and the robot's 128 B gait record, read inside the front end it selects -- the same rule once more.
 // (The two zero-fill loops stay written out: as calls of one inline function they compile to other instructions.)
 template <int VAR>
 __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmpc_loop_rec_fused_kernel(
@@ -431,8 +462,8 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
     QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, )
     QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, )
     QMPC_REC_ACT(const qmpc_actuation_params* __restrict__ act, qmpc_actuation_line* __restrict__ line, )
-    QMPC_REC_SENSE(const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen, ) int ticks, int batch,
-    double* __restrict__ gws) {
+    QMPC_REC_SENSE(const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen, )
+    QMPC_REC_GAIT(const qmpc_gait_params* __restrict__ gait, ) int ticks, int batch, double* __restrict__ gws) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int b = blockIdx.x;
   if (b >= batch) return;
@@ -464,7 +495,9 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
   bool prev_ok = false;
   for (int t = 0; t < ticks; ++t) {
 #if QMPC_REC_EXT >= 5
-    if (lane == 0) loop_front_sense_one<OCC>(LP, st[b], rec[b], sense ? sense + (size_t)b : nullptr, seen ? seen + (size_t)b : nullptr);
+    if (lane == 0)
+      loop_front_sense_one<OCC>(LP, st[b], rec[b], sense ? sense + (size_t)b : nullptr, seen ? seen + (size_t)b : nullptr
+                                QMPC_REC_GAIT(, gait ? gait + (size_t)b : nullptr));
 #else
     if (lane == 0) QMPC_REC_FRONT(OCC, LP, st[b], rec[b]);
 #endif
@@ -518,6 +551,25 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
   if (lane == 0) outcomes[b] = oc;
 #endif
 }
+
+#if QMPC_REC_EXT == 6 && !defined(QMPC_REC_CONVEX)
+// ---- the check of the gait records (QuatMpc's unit only: it does not depend on the model) ----------------------------------
+// One thread per robot: the verdict of the robot's gait record (qmpc_loop::loop_gait_valid, with the call's tick dt) into its
+// plant block (a verdict already there stays)
+__global__ __launch_bounds__(256) void qmpc_gait_check_kernel(const qmpc_gait_params* __restrict__ gait, PlantDev* __restrict__ pl,
+                                                              double dt, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  if (!qmpc_loop::loop_gait_valid(gait[i], dt)) pl[i].status = QMPC_BAD_PARAMS;
+}
+
+__attribute__((visibility("hidden"))) hipError_t rec_gait_check_launch(hipStream_t s, const qmpc_gait_params* gait, void* plants,
+                                                                       double dt, int batch) {
+  hipLaunchKernelGGL(qmpc_gait_check_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, gait,
+                     static_cast<PlantDev*>(plants), dt, batch);
+  return hipGetLastError();
+}
+#endif
 
 #if QMPC_REC_EXT == 5 && !defined(QMPC_REC_CONVEX)
 // ---- the check of the sensing records (QuatMpc's unit only: it does not depend on the model) -------------------------------
@@ -588,13 +640,13 @@ __attribute__((visibility("hidden"))) hipError_t rec_fused_launch(
     qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws,
     const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,
     const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line,
-    const qmpc_sense_params* sense, qmpc_sense_seen* seen) {
+    const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait) {
   const int k = qmpc::wform_index(var);
   if (k < 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kRecFused[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks),
                      static_cast<const PlantDev*>(plants), *lp, QMPC_REC_OUTCOME(*op, ) st, rec, forces, info, trace_f, trace_c,
                      QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, )
-                     QMPC_REC_ACT(act, line, ) QMPC_REC_SENSE(sense, seen, ) ticks, batch, gws);
+                     QMPC_REC_ACT(act, line, ) QMPC_REC_SENSE(sense, seen, ) QMPC_REC_GAIT(gait, ) ticks, batch, gws);
   return hipGetLastError();
 }
 
@@ -602,9 +654,10 @@ __attribute__((visibility("hidden"))) hipError_t rec_fused_launch(
 __attribute__((visibility("hidden"))) hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st,
                                                                   qmpc_input* rec, int* row, const void* plants, int batch,
                                                                   const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes,
-                                                                  const qmpc_sense_params* sense, qmpc_sense_seen* seen) {
+                                                                  const qmpc_sense_params* sense, qmpc_sense_seen* seen,
+                                                                  const qmpc_gait_params* gait) {
   hipLaunchKernelGGL(qmpc_loop_rec_front_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, *lp, QMPC_REC_OUTCOME(*op, ) st, rec, row,
-                     static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_SENSE(sense, seen, ) batch);
+                     static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_SENSE(sense, seen, ) QMPC_REC_GAIT(gait, ) batch);
   return hipGetLastError();
 }
 #endif
@@ -627,6 +680,10 @@ __attribute__((visibility("hidden"))) hipError_t rec_post_launch(hipStream_t s, 
 #undef QMPC_REC_GROUND
 #undef QMPC_REC_ACT
 #undef QMPC_REC_SENSE
+#undef QMPC_REC_GAIT
+#ifdef QMPC_REC_FRONT_GAIT
+#undef QMPC_REC_FRONT_GAIT
+#endif
 #undef QMPC_REC_POST_GROUND
 #undef QMPC_REC_EXT
 #undef QMPC_REC_MODEL

@@ -48,6 +48,10 @@ class ClosedLoopHostBase {
   // controller read in the last tick and the count of such ticks are read back with sense_seen (it starts empty; set_sense leaves it)
   virtual void set_sense(const qmpc_sense_params* sense) = 0;
   virtual const qmpc_sense_seen& sense_seen() const = 0;
+  // the robot's gait record (qmpc_loop_run_gaits*): copied (null or the identity of lp: the reference's trot at lp.gait_freq,
+  // the fixed text).  Legs that have not walked yet are reset to their starting phase; walking legs take the new split and
+  // frequency at their next transition
+  virtual void set_gait(const qmpc_gait_params* gait) = 0;
   State state;
 };
 
@@ -124,6 +128,15 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     if (sense) sense_ = *sense;
   }
   const qmpc_sense_seen& sense_seen() const override { return seen_; }
+  void set_gait(const qmpc_gait_params* gait) override {
+    has_gait_ = gait != nullptr && !qmpc_loop::loop_gait_identity(*gait, lp_.gait_freq);
+    if (has_gait_) gait_ = *gait;
+    state.param.gait_freq = has_gait_ ? gait_.gait_freq : lp_.gait_freq;
+    for (int l = 0; l < NUM_LEG; ++l) {
+      if (has_gait_) mpc->leg_FSM[l].set_gait(gait_.first_stance[l], gait_.split[l], gait_.phase0[l]);
+      else mpc->leg_FSM[l].clear_gait();
+    }
+  }
   void reset_outcome() {                                    // qmpc_loop_outcome_init
     std::memset(&outcome_, 0, sizeof outcome_);
     outcome_.down_tick = outcome_.first_rejected_tick = -1.0;
@@ -178,7 +191,8 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
       seen_.ticks += 1.0;
     }
     refresh_feedback();
-    raibert_foot_targets(state);
+    if (has_gait_) raibert_foot_targets_gait(state, gait_);      // the leg's own stance time (qmpc_loop_run_gaits*)
+    else raibert_foot_targets(state);
     mpc->goal_update(state);
     mpc->foot_update(state);
     const bool ok = mpc->grf_update(state);
@@ -396,6 +410,8 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   qmpc_sense_params sense_;
   qmpc_sense_seen seen_ = {};                            // qmpc_sense_seen_init
   bool has_sense_ = false;
+  qmpc_gait_params gait_;
+  bool has_gait_ = false;
   long ticks_ = 0;
 };
 

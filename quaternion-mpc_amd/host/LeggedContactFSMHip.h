@@ -17,6 +17,9 @@
 //   swing_enter / stance_enter / stance_exit   :80-86,225-235
 //   swing_update (quintic foot target)         :237-246
 // It leaves the schedule arithmetic untouched.
+// set_gait() replaces the trot table by a two-entry pattern of the leg's own (qmpc_loop_run_gaits*, include/qmpc.h): pattern,
+// switch times, swing fraction and the reset to the leg's starting phase come from csrc/qmpc_loop_math.h (loop_gait_*), the
+// source the device compiles; the update and common_enter above walk it unchanged.
 #pragma once
 
 #include "SwingTrajectoryHip.h"
@@ -42,16 +45,37 @@ class LeggedContactFSMHip {
     slot_end = table[slot].ends_at;
   }
 
+  // The leg's own pattern: [STANCE, SWING] (first_stance != 0) or [SWING, STANCE], switch times split and 1.0, gait_phase =
+  // phase0 at a reset.  A leg that has not walked since its last reset is reset to it at once; a walking leg keeps its
+  // phase and its current slot's end -- the new split takes effect at its next transition, phase0 at the next reset.
+  void set_gait(double first_stance, double split, double phase0) {
+    has_gait = true;
+    gait.first_stance[leg_id & 3] = first_stance;
+    gait.split[leg_id & 3] = split;
+    gait.phase0[leg_id & 3] = phase0;
+    if (!not_first_call) reset();
+  }
+  void clear_gait() { has_gait = false; }               // back to the trot table, from the leg's next transition or reset on
+
   void reset() {                                        // :11-31
+    if (has_gait) {                                     // the reset rule of qmpc_loop_math.h: loop_gait_reset
+      const double ph = gait.phase0[leg_id & 3], sp = gait.split[leg_id & 3];
+      gait_phase = ph;
+      slot = ph < sp ? 0 : 1;
+      prev_slot = 1 - slot;
+      slot_begin = slot ? sp : 0.0;
+      slot_end = slot ? 1.0 : sp;
+    } else {
     gait_phase = 0;
     slot = 0;
     prev_slot = kSlots - 1;
     slot_begin = 0;
     slot_end = table[slot].ends_at;
+    }
     if (s == SWING_HIP) {                               // :20-25 a swing foot goes to its saved target
       for (int a = 0; a < 3; ++a) { FSM_foot_pos_target_world[a] = swing_end_foot_pos_world[a]; FSM_foot_vel_target_world[a] = 0.0; }
     }
-    s = table[slot].state;
+    s = state_at(slot);
     not_first_call = false;                             // :30 the next update() re-seeds the targets
   }
 
@@ -107,6 +131,11 @@ class LeggedContactFSMHip {
       const double t = percent_in_state();
       double fin[3], out[9];
       for (int a = 0; a < 3; ++a) fin[a] = foot_pos_target_world[a] + swing_extend_foot_pos_world[a];
+      if (has_gait) {                                   // the leg's own swing fraction in the place of the trot's 0.5
+        const double w = qmpc_loop::loop_gait_swing_fraction(gait, leg_id & 3);
+        quintic_curve.get_foot_swing_target(static_cast<float>(w * t / gait_freq_now), static_cast<float>(w / gait_freq_now),
+                                            swing_start_foot_pos_world, fin, out);
+      } else
       quintic_curve.get_foot_swing_target(static_cast<float>(0.5 * t / gait_freq_now),
                                           static_cast<float>(0.5 / gait_freq_now), swing_start_foot_pos_world, fin, out);
       for (int a = 0; a < 3; ++a) {
@@ -140,7 +169,11 @@ class LeggedContactFSMHip {
     slot = (slot + 1) % kSlots;
     if (slot < prev_slot) gait_phase -= 1.0;
     slot_begin = gait_phase;
-    slot_end = table[slot].ends_at;
+    slot_end = ends_at(slot);
+  }
+  double ends_at(int i) const { return has_gait ? qmpc_loop::loop_gait_switch_time(gait, leg_id & 3, i) : table[i].ends_at; }
+  LeggedContactStateHip state_at(int i) const {
+    return has_gait ? (qmpc_loop::loop_gait_pattern(gait, leg_id & 3, i) != 0.0 ? STANCE_HIP : SWING_HIP) : table[i].state;
   }
   // fraction of the current slot that has elapsed, clamped to [0, 1] (:261-270)
   double percent_in_state() const {
@@ -165,6 +198,8 @@ class LeggedContactFSMHip {
   double gait_phase = 0.0;
   double gait_freq = 0.0;
   const GaitSlot* table = kTrotDiagonal;
+  qmpc_gait_params gait = {};                           // this leg's entries only (set_gait)
+  bool has_gait = false;
   int slot = 0, prev_slot = kSlots - 1;
   double slot_begin = 0.0, slot_end = 0.5;
 };

@@ -115,4 +115,35 @@ void raibert_foot_targets(State& s) {
   }
 }
 
+// The same for a robot with a gait of its own (qmpc_loop_run_gaits*, a non-identity record): the offset is formed and clamped
+// per leg with the leg's own stance time (qmpc_loop_math.h: loop_gait_raibert_delta, the device's source)
+template <class State>
+void raibert_foot_targets_gait(State& s, const qmpc_gait_params& g) {
+  for (int r = 0; r < 3; ++r)
+    s.fbk.torso_lin_vel_rel[r] = s.fbk.torso_rot_mat_z(0, r) * s.fbk.torso_lin_vel_world[0] +
+                                 s.fbk.torso_rot_mat_z(1, r) * s.fbk.torso_lin_vel_world[1] +
+                                 s.fbk.torso_rot_mat_z(2, r) * s.fbk.torso_lin_vel_world[2];
+  const double k = std::sqrt(std::fabs(s.fbk.torso_pos_world[2]) / 9.81);
+  const double vrel[3] = {s.fbk.torso_lin_vel_rel[0], s.fbk.torso_lin_vel_rel[1], s.fbk.torso_lin_vel_rel[2]};
+  const double vd[3] = {s.ctrl.torso_lin_vel_d_rel[0], s.ctrl.torso_lin_vel_d_rel[1], s.ctrl.torso_lin_vel_d_rel[2]};
+  for (int i = 0; i < 4; ++i) {
+    double d[3], dabs[3], abs_[3];
+    qmpc_loop::loop_gait_raibert_delta(g, i, k, vrel, vd, d);
+    for (int r = 0; r < 3; ++r)
+      dabs[r] = s.fbk.torso_rot_mat_z(r, 0) * d[0] + s.fbk.torso_rot_mat_z(r, 1) * d[1] + s.fbk.torso_rot_mat_z(r, 2) * d[2];
+    for (int r = 0; r < 3; ++r)
+      abs_[r] = s.fbk.torso_rot_mat_z(r, 0) * s.param.default_foot_pos_rel(0, i) +
+                s.fbk.torso_rot_mat_z(r, 1) * s.param.default_foot_pos_rel(1, i) +
+                s.fbk.torso_rot_mat_z(r, 2) * s.param.default_foot_pos_rel(2, i);
+    abs_[0] += dabs[0];
+    abs_[1] += dabs[1];
+    for (int r = 0; r < 3; ++r) {
+      s.ctrl.foot_pos_target_abs(r, i) = abs_[r];
+      s.ctrl.foot_pos_target_rel(r, i) = s.fbk.torso_rot_mat(0, r) * abs_[0] + s.fbk.torso_rot_mat(1, r) * abs_[1] +
+                                         s.fbk.torso_rot_mat(2, r) * abs_[2];
+      s.ctrl.foot_pos_target_world(r, i) = abs_[r] + s.fbk.torso_pos_world[r];
+    }
+  }
+}
+
 }  // namespace legged

@@ -286,6 +286,86 @@ int qh_sense_one(const qmpc_sense_params* sense, double tick, const double* x, d
   else qmpc_loop::loop_sense_one(*sense, tick, x, m);
   return 1;
 }
+// ... and its gait record (qmpc_loop_run_gaits*; null or the identity: the reference's trot)
+void qh_loop_set_gait(void* p, const qmpc_gait_params* gait) { static_cast<LoopHarness*>(p)->loop->set_gait(gait); }
+// the rule itself (qmpc_loop_math.h: loop_gait_*, the one source the device compiles too): 1 for a valid record at tick dt ...
+int qh_gait_valid(const qmpc_gait_params* gait, double dt) { return qmpc_loop::loop_gait_valid(*gait, dt) ? 1 : 0; }
+int qh_gait_identity(const qmpc_gait_params* gait, double lp_gait_freq) { return qmpc_loop::loop_gait_identity(*gait, lp_gait_freq) ? 1 : 0; }
+// ... the reset of the four legs of a state record in place (what qmpc_loop_state_set_gait does: contacts = the legs' states) ...
+void qh_gait_reset(const qmpc_gait_params* gait, qmpc_loop_state* s) {
+  for (int l = 0; l < 4; ++l) {
+    qmpc_loop::loop_gait_reset(*gait, l, s->leg[l]);
+    s->contacts[l] = s->leg[l].state;
+  }
+}
+// ... and `ticks` updates of the four legs of a state record in place, on scripted feet: cur / tgt [ticks][12] (foot positions
+// and Raibert targets), flags [ticks][4]; legs_out [ticks][4] receives the legs after each tick (or null), contacts [ticks][4]
+void qh_gait_run(const qmpc_gait_params* gait, qmpc_loop_state* s, double dt, int ticks, const double* cur, const double* tgt,
+                 const double* flags, qmpc_loop_leg* legs_out, double* contacts) {
+  legged::QuinticCurveHip curve;
+  auto swing = [&](float t, float T, const double* a, const double* b, double* out) { curve.get_foot_swing_target(t, T, a, b, out); };
+  for (int t = 0; t < ticks; ++t)
+    for (int l = 0; l < 4; ++l) {
+      s->gait_counter[l] = qmpc_loop::loop_gait_update(*gait, l, s->leg[l], dt, cur + 12 * t + 3 * l, tgt + 12 * t + 3 * l,
+                                                       flags[4 * t + l] != 0.0, swing);
+      s->contacts[l] = s->leg[l].state;
+      if (legs_out) legs_out[4 * t + l] = s->leg[l];
+      if (contacts) contacts[4 * t + l] = s->leg[l].state;
+    }
+}
+// the fixed path on the same script: LeggedContactFSMHip with the trot table (set_gait not called) -- or, with gait given, the
+// class after set_gait -- exported in the record layout after each tick
+void qh_gait_run_class(const qmpc_gait_params* gait, double gait_freq, double dt, int ticks, const double* cur, const double* tgt,
+                       const double* flags, qmpc_loop_leg* legs_out) {
+  legged::LeggedContactFSMHip fsm[4];
+  for (int l = 0; l < 4; ++l) {
+    fsm[l].reset_params(gait_freq, l);
+    if (gait) fsm[l].set_gait(gait->first_stance[l], gait->split[l], gait->phase0[l]);
+    else fsm[l].reset();
+  }
+  for (int t = 0; t < ticks; ++t)
+    for (int l = 0; l < 4; ++l) {
+      fsm[l].update(dt, gait ? gait->gait_freq : gait_freq, cur + 12 * t + 3 * l, tgt + 12 * t + 3 * l, flags[4 * t + l] != 0.0);
+      const legged::LeggedContactFSMHip& F = fsm[l];
+      qmpc_loop_leg& L = legs_out[4 * t + l];
+      std::memset(&L, 0, sizeof L);
+      L.gait_phase = F.phase();
+      L.state = (double)F.get_contact_state();
+      L.pattern_index = F.pattern_index();
+      L.prev_pattern_index = F.prev_pattern_index();
+      L.start_time = F.state_start_time();
+      L.end_time = F.state_end_time();
+      L.not_first_call = F.first_call_done() ? 1.0 : 0.0;
+      L.terrain_height = F.terrain_height;
+      for (int a = 0; a < 3; ++a) {
+        L.swing_start[a] = F.swing_start()[a];
+        L.swing_end[a] = F.swing_end()[a];
+        L.fsm_pos[a] = F.FSM_foot_pos_target_world[a];
+        L.fsm_vel[a] = F.FSM_foot_vel_target_world[a];
+        L.fsm_acc[a] = F.FSM_foot_acc_target_world[a];
+      }
+    }
+}
+// Raibert targets of one feedback: the general rule (gait given) or the fixed text (null); R_z from yaw, tgt_world [12] out
+void qh_gait_raibert(const qmpc_gait_params* gait, double gait_freq, const double* default_foot_pos_rel, double yaw, const double* pos,
+                     const double* vel_world, const double* vel_d_rel, double* tgt_world) {
+  LeggedStateLite s;
+  s.param.gait_freq = gait_freq;
+  const double c = std::cos(yaw), sn = std::sin(yaw);
+  const double Rz[9] = {c, -sn, 0.0, sn, c, 0.0, 0.0, 0.0, 1.0};
+  for (int r = 0; r < 3; ++r) {
+    for (int k = 0; k < 3; ++k) { s.fbk.torso_rot_mat_z(r, k) = Rz[3 * r + k]; s.fbk.torso_rot_mat(r, k) = Rz[3 * r + k]; }
+    s.fbk.torso_pos_world[r] = pos[r];
+    s.fbk.torso_lin_vel_world[r] = vel_world[r];
+    s.ctrl.torso_lin_vel_d_rel[r] = vel_d_rel[r];
+  }
+  for (int l = 0; l < 4; ++l)
+    for (int a = 0; a < 3; ++a) s.param.default_foot_pos_rel(a, l) = default_foot_pos_rel[3 * l + a];
+  if (gait) legged::raibert_foot_targets_gait(s, *gait);
+  else legged::raibert_foot_targets(s);
+  for (int l = 0; l < 4; ++l)
+    for (int a = 0; a < 3; ++a) tgt_world[3 * l + a] = s.ctrl.foot_pos_target_world(a, l);
+}
 void qh_loop_destroy(void* p) {
   LoopHarness* h = static_cast<LoopHarness*>(p);
   if (!h) return;

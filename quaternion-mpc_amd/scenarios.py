@@ -370,3 +370,20 @@ def random_go1_senses(batch: int, seed: int = 0, first: int = 0, pos_noise=(0.0,
                         pos_noise=lin(pos_noise, u[:, 0])[:, None] * np.ones(3), att_noise=lin(att_noise, u[:, 1])[:, None] * np.ones(3),
                         vel_noise=lin(vel_noise, u[:, 2])[:, None] * np.ones(3), gyro_noise=lin(gyro_noise, u[:, 3])[:, None] * np.ones(3),
                         gyro_bias=lin(gyro_bias, u[:, 4:7]) * sign(u[:, 7:10]), pos_bias=lin(pos_bias, u[:, 10:13]) * sign(u[:, 13:16]))
+
+
+def random_go1_gaits(batch: int, seed: int = 0, first: int = 0, gaits=("trot", "pace", "bound", "trot_overlap", "crawl", "amble"),
+                     gait_freq=(1.5, 3.0)) -> np.ndarray:
+    """`batch` gait records (``struct qmpc_gait_params``, for Solver.loop_run_gaits), robot indices first .. first+batch-1, the
+    counter-based generator of random_go1_pushes (a shard equals its block of the whole).  Per robot one of the named `gaits`,
+    uniformly, and a frequency U(gait_freq) [Hz].  The frequency range is an ASSUMPTION: the reference's configurations ship
+    1.7, 2.0 and 2.2 Hz for the Go1's trot, the range here brackets them by about a third on either side and is not a
+    measurement of what a Go1 can step at in any of the other gaits -- sweep it.  (At the 5 ms tick a record is valid up to
+    12.5 Hz.)  Two uniforms per robot: the gait's index, the frequency."""
+    from . import gait_params
+
+    idx = np.arange(first, first + batch, dtype=np.uint64)
+    u = _uniform(0x5EED7000 + int(seed), idx, 2)
+    names = list(gaits)
+    k = np.minimum(np.floor(len(names) * u[:, 0]).astype(np.int64), len(names) - 1)
+    return gait_params(batch, gait=[names[j] for j in k], gait_freq=gait_freq[0] + (gait_freq[1] - gait_freq[0]) * u[:, 1])

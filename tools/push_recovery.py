@@ -7,6 +7,7 @@ inertia); the controller is the handle's and is not told about the push.
                                   [--recover 200] [--horizon 10] [--controller quat|convex|both] [--ctrl-records] [--warm] [--json FILE]
                                   [--mu-true LO HI [--mu-steps 5]] [--delay LO HI] [--tau LO HI [--tau-steps 3]]
                                   [--gyro-bias LO HI] [--pos-noise LO HI] [--att-noise LO HI] [--vel-noise LO HI] [--sense-steps 3]
+                                  [--gait NAME[,NAME...]] [--gait-freq LO HI [--gait-steps 3]]
 Every robot stands for 6 ticks, trots at --speed for --settle ticks, is shoved at tick 6 + settle + start for --length ticks with
 force impulse / (length dt) in its cell's direction (0 degrees: ahead, 90: to its left), and trots on until --recover ticks after
 the last start.  Down: below 0.15 m or tilted beyond 60 degrees (qmpc_default_outcome_params); stop_when_down halts a fallen robot.
@@ -28,6 +29,11 @@ for --sense-steps gyro biases from LO to HI rad/s (on all three body axes, the s
 attitude [rad], world-frame velocity [m/s], standard deviation per axis -- so the noises rise together.  Every robot draws its own
 noise (seed = its index).  A table of falls per (impulse, gyro bias, noise level) cell is printed after the tables above, which
 then pool them.
+--gait NAME[,NAME...], --gait-freq LO HI: the gait axes (qmpc_loop_run_gaits: every robot walks its own gait).  The grid is repeated
+for every named gait (trot, pace, bound, trot_overlap, crawl, amble) and for --gait-steps frequencies from LO to HI Hz (without
+--gait-freq: the loop's 2.2 Hz).  The six standing ticks put every leg at its gait's starting phase.  The start ticks stay spread over
+the 91 ticks of the 2.2 Hz period whatever the frequency.  A table of falls per (impulse, gait, frequency) cell is printed after the
+tables above, which then pool them.  Without --gait and --gait-freq the call is the sensing call and the robots trot as before.
 --ctrl-records: every robot also carries a controller record (the handle's values: the same controller) and the handle takes
 QMPC_INSTANCES_AUTO, a ConvexMpc handle with qmpc_set_convex_lane_records as well -- the launch a sweep over per-robot controllers
 takes: from the switch-over on the lane kernel with per-lane parameters under either controller.
@@ -79,6 +85,9 @@ def main():
     ap.add_argument("--att-noise", type=float, nargs=2, default=None, metavar=("LO", "HI"))
     ap.add_argument("--vel-noise", type=float, nargs=2, default=None, metavar=("LO", "HI"))
     ap.add_argument("--sense-steps", type=int, default=3)
+    ap.add_argument("--gait", default=None, help="names of quaternion_mpc_amd.GAITS, comma-separated")
+    ap.add_argument("--gait-freq", type=float, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--gait-steps", type=int, default=3)
     a = ap.parse_args()
     pkg = load_pkg()
     lib = pkg.load_library()
@@ -101,11 +110,18 @@ def run(a, pkg, lib, controller):
     gbs = np.linspace(a.gyro_bias[0], a.gyro_bias[1], a.sense_steps) if a.gyro_bias else np.array([0.0])
     levels = np.arange(a.sense_steps) if noises else np.array([0])
     sensed = bool(a.gyro_bias or noises)
-    gi, gs, gd, gm, gl, gt, gb, gn, gk = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8),
-                                                                         np.arange(len(mus)), np.arange(len(delays)), np.arange(len(taus)),
-                                                                         np.arange(len(gbs)), np.arange(len(levels)), np.arange(a.per_cell),
-                                                                         indexing="ij"))
-    tail = len(gbs) * len(levels) * a.per_cell      # the robots of one (impulse, start, direction, mu, delay, tau) cell
+    gaited = bool(a.gait or a.gait_freq)
+    names = a.gait.split(",") if a.gait else ["trot"]
+    unknown = [n for n in names if n not in pkg.GAITS]
+    if unknown:
+        raise SystemExit(f"--gait: unknown {unknown}; one of {', '.join(pkg.GAITS)}")
+    freqs = np.linspace(a.gait_freq[0], a.gait_freq[1], a.gait_steps) if a.gait_freq else np.array([pkg.default_loop_params(lib).gait_freq])
+    gi, gs, gd, gm, gl, gt, gb, gn, gg, gf, gk = (g.ravel() for g in np.meshgrid(np.arange(len(impulses)), np.arange(len(starts)), np.arange(8),
+                                                                                 np.arange(len(mus)), np.arange(len(delays)), np.arange(len(taus)),
+                                                                                 np.arange(len(gbs)), np.arange(len(levels)), np.arange(len(names)),
+                                                                                 np.arange(len(freqs)), np.arange(a.per_cell), indexing="ij"))
+    inner = len(names) * len(freqs) * a.per_cell      # the robots of one (..., gyro bias, noise level) cell
+    tail = len(gbs) * len(levels) * inner      # the robots of one (impulse, start, direction, mu, delay, tau) cell
     members = len(mus) * len(delays) * len(taus) * tail
     B = gi.size
     convex = controller == "convex"
@@ -140,6 +156,7 @@ def run(a, pkg, lib, controller):
         level = lambda r: np.linspace(r[0], r[1], a.sense_steps)[gn][:, None] * np.ones(3)      # noqa: E731
         sense = pkg.sense_params(B, seed=np.arange(B, dtype=np.float64), gyro_bias=gbs[gb][:, None] * signs,
                                  **{k + "_noise": level(r) for k, r in noises.items()})
+    gait = pkg.gait_params(B, [names[k] for k in gg], gait_freq=freqs[gf]) if gaited else None
     op = pkg.default_outcome_params(lib, stop_when_down=True)
     s = pkg.Solver(p, B, device=0, lib=lib)
     if convex:
@@ -155,11 +172,11 @@ def run(a, pkg, lib, controller):
     form = s.loop_instances_plan(B, ctrl is not None, a.warm)
     total = a.settle + PERIOD + a.recover
     w0 = time.perf_counter()
-    # (sense = None: the actuation call; act = None: the ground call; ground = None: the push call)
-    st, oc, ta, line, seen = s.loop_run_sensing(st, 6, sense, None, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op)
+    # (gait = None: the sensing call; sense = None: the actuation call; act = None: the ground call; ground = None: the push call)
+    st, oc, ta, line, seen = s.loop_run_gaits(st, 6, gait, sense, None, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op)
     st["movement_mode"] = 1.0
-    st, oc, ta, line, seen = s.loop_run_sensing(st, total, sense, seen, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc,
-                                                tallies=ta)
+    st, oc, ta, line, seen = s.loop_run_gaits(st, total, gait, sense, seen, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc,
+                                              tallies=ta)
     wall = time.perf_counter() - w0
     s.close()
     up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, members)
@@ -214,7 +231,7 @@ def run(a, pkg, lib, controller):
                    "down": down.sum(axis=(1, 2, 3, 6)).tolist()}
     by_sense = None
     if sensed:
-        shape = (len(impulses), len(starts), 8, len(mus) * len(delays) * len(taus), len(gbs), len(levels), a.per_cell)
+        shape = (len(impulses), len(starts), 8, len(mus) * len(delays) * len(taus), len(gbs), len(levels), inner)
         down = (oc["down_tick"] >= 0).reshape(shape)
         cell = down[0, :, :, :, 0, 0].size
         what = ", ".join(f"{k} {r[0]:g} .. {r[1]:g}" for k, r in noises.items()) or "none"
@@ -230,7 +247,22 @@ def run(a, pkg, lib, controller):
               " ".join(f"{int(j)}: {int(before[:, :, :, :, :, j].sum())}" for j in range(len(levels))) + "\n")
         by_sense = {"gyro_bias": gbs.tolist(), "noise": {k: np.linspace(r[0], r[1], a.sense_steps).tolist() for k, r in noises.items()},
                     "cell": cell, "down": down.sum(axis=(1, 2, 3, 6)).tolist(), "measurements": int(seen["ticks"].sum())}
-    return {"controller": controller, "by_mu_true": by_mu, "by_actuation": by_time, "by_sensing": by_sense, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
+    by_gait = None
+    if gaited:
+        shape = (len(impulses), len(starts), 8, len(mus) * len(delays) * len(taus) * len(gbs) * len(levels), len(names), len(freqs), a.per_cell)
+        down = (oc["down_tick"] >= 0).reshape(shape)
+        cell = down[0, :, :, :, 0, 0].size
+        print(f"gaits: robots down per (impulse, gait, frequency) cell, of {cell}; frequency in Hz")
+        print("impulse         gait " + " ".join(f"{f:7.2f}" for f in freqs))
+        for i, imp in enumerate(impulses):
+            for g, n in enumerate(names):
+                print(f"{imp:5g}   {n:>12s} " + " ".join(f"{int(down[i, :, :, :, g, f].sum()):7d}" for f in range(len(freqs))))
+        before = ((oc["down_tick"] >= 0) & (oc["down_tick"] <= push["start_tick"][:, 0])).reshape(shape)
+        print("  ... of them down before their shove began, by gait: " +
+              " ".join(f"{n}: {int(before[:, :, :, :, g].sum())}" for g, n in enumerate(names)) + "\n")
+        by_gait = {"gaits": names, "gait_freq": freqs.tolist(), "cell": cell, "down": down.sum(axis=(1, 2, 3, 6)).tolist(),
+                   "down_before_shove": before.sum(axis=(0, 1, 2, 3, 5, 6)).tolist()}
+    return {"controller": controller, "by_mu_true": by_mu, "by_actuation": by_time, "by_sensing": by_sense, "by_gait": by_gait, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
             "per_cell": members, "length_ticks": a.length, "speed": a.speed, "form": form, "share_up": share.tolist()}
 
 
