@@ -770,6 +770,116 @@ __device__ __forceinline__ void srbd_step_w(const DevParams& P, const double gb[
     xn[3 + r] = x[3 + r] + P.h * (0.5 * (G[3 * r] * wm[0] + G[3 * r + 1] * wm[1] + G[3 * r + 2] * wm[2]));
 }
 
+// ---- the rollouts' knot with the translation held one component per lane (LN: the all-LDS form, one wave per SIMD, where
+// the knot is bound by the instructions one wave can issue).  Lane a < 3 of a 16-lane row holds p_a and v_a, forms
+// the attitude error's component a and row 3 + a of e = Abar dx, and reads its own six entries of the Jacobian blocks;
+// the quaternion and the body rate stay in every lane: their update is a signed permutation per term, which costs a lane
+// as many slots in moves and sign flips as the products it saves (profiles/HISTORY_r25.md).  The other lanes of the row
+// run lane 0's part on lane 0's operands.  Every sum is pinned to the pairing the compiler chose for srbd_step_w /
+// state_diff in the scalar form (read from the listing of the all-LDS kernel): same operations, same order, same bytes.
+__device__ __forceinline__ double flip_sign(double x, int m) {      // m = 0 or the sign bit of the high word
+  return __hiloint2double(__double2hiint(x) ^ m, __double2loint(x));
+}
+// G(q) w, the four sums of quat_G's rows
+__device__ __forceinline__ void quat_G_mul_pinned(const double q[4], const double w[3], double d[4]) {
+#pragma clang fp contract(off)
+  const double s = q[0], x = q[1], y = q[2], z = q[3];
+  d[0] = fma(-w[2], z, fma(w[1], -y, -(w[0] * x)));
+  d[1] = fma(w[2], y, fma(w[0], s, -(w[1] * z)));
+  d[2] = fma(-w[2], x, fma(w[0], z, w[1] * s));
+  d[3] = fma(w[2], s, fma(w[1], x, -(w[0] * y)));
+}
+// the lane's operands of one knot: the old quaternion and body rate (every lane), the lane's old p_a / v_a, the old
+// quaternion in the order and with the signs of column a of G(q_o) (g[0] is subtracted), the lane's rows of A1 and A3
+struct RollLoadsL {
+  double qo[4], wo[3], po, vo, g[4], ab[6];
+};
+struct LanePat {
+  int a, iq[4], ms[4];
+  __device__ __forceinline__ void init(int lane) {
+    const int c = lane & 15;
+    a = (c < 3) ? c : 0;
+    // column a of G(q_o) against (s, x, y, z) of q_c, first term first: a = 0: -x, s, z, -y;  1: -y, -z, s, x;  2: -z, y, -x, s
+    iq[0] = a + 1;
+    iq[1] = (a == 0) ? 0 : ((a == 1) ? 3 : 2);
+    iq[2] = (a == 0) ? 3 : ((a == 1) ? 0 : 1);
+    iq[3] = 2 - a;
+    const int sb = (int)0x80000000u;
+    ms[0] = 0; ms[1] = (a == 1) ? sb : 0; ms[2] = (a == 2) ? sb : 0; ms[3] = (a == 0) ? sb : 0;
+  }
+};
+__device__ __forceinline__ void roll_load_lane(const Layout& L, const double* sm, int k, const LanePat& lp, RollLoadsL& r) {
+  const double* xk = sm + L.X + 13 * k;
+  const double* abk = sm + L.AB + kAB * k + 3 * lp.a;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r.qo[i] = xk[3 + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r.wo[i] = xk[10 + i];
+  r.po = xk[lp.a];
+  r.vo = xk[7 + lp.a];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) r.g[t] = xk[3 + lp.iq[t]];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { r.ab[j] = abk[j]; r.ab[3 + j] = abk[9 + j]; }
+}
+// s = [Xw | xw] or [Xz | xz] row of the lane times (Abar dx, alpha): QuatModel::state_diff, e = Abar dx and the gain row's sum
+__device__ __forceinline__ double roll_gain_lane(double h, const double q[4], const double om[3], double S, double V,
+                                                 const RollLoadsL& r, const LanePat& lp, const double kd[13], double alpha) {
+#pragma clang fp contract(off)
+  const double isc = fast_rcp(fma(q[3], r.qo[3], fma(q[2], r.qo[2], fma(q[0], r.qo[0], q[1] * r.qo[1]))));
+  const double g1 = flip_sign(r.g[1], lp.ms[1]), g2 = flip_sign(r.g[2], lp.ms[2]), g3 = flip_sign(r.g[3], lp.ms[3]);
+  const double d = fma(q[3], g3, fma(q[2], g2, fma(q[1], g1, -(q[0] * r.g[0])))) * isc;
+  double e[12];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) e[9 + i] = om[i] - r.wo[i];
+  const double dp = S - r.po, dv = V - r.vo;
+  const double e0 = fma(h, dv, dp);
+  const double d3 = row_bcast<0>(d), d4 = row_bcast<1>(d), d5 = row_bcast<2>(d);
+  const double e3 = fma(r.ab[2], d5, fma(r.ab[0], d3, r.ab[1] * d4)) + fma(r.ab[5], e[11], fma(r.ab[3], e[9], r.ab[4] * e[10]));
+  e[0] = row_bcast<0>(e0); e[1] = row_bcast<1>(e0); e[2] = row_bcast<2>(e0);
+  e[3] = row_bcast<0>(e3); e[4] = row_bcast<1>(e3); e[5] = row_bcast<2>(e3);
+  e[6] = row_bcast<0>(dv); e[7] = row_bcast<1>(dv); e[8] = row_bcast<2>(dv);
+  const double p0 = fma(kd[2], e[2], fma(kd[1], e[1], fma(kd[0], e[0], alpha * kd[12])));
+  const double p1 = fma(kd[5], e[5], fma(kd[3], e[3], kd[4] * e[4]));
+  const double p2 = fma(kd[8], e[8], fma(kd[6], e[6], kd[7] * e[7]));
+  const double p3 = fma(kd[11], e[11], fma(kd[9], e[9], kd[10] * e[10]));
+  return (p0 + p1) + (p2 + p3);
+}
+// srbd_step_w: wf = the force component a of the knot's wrench (the lane's own), wt = its torque (every lane), gba = gb[a]
+__device__ __forceinline__ void roll_step_lane(const DevParams& P, double gba, const double wd0[3], double wf, const double wt[3],
+                                               double q[4], double om[3], double& S, double& V) {
+#pragma clang fp contract(off)
+  double wd[3], wm[3], d[4], qm[4];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) wd[i] = wd0[i] + wt[i];
+  const double vd = fma(P.inv_mass, wf, gba);
+  quat_G_mul_pinned(q, om, d);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) qm[r] = fma(P.hh, d[r] * 0.5, q[r]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) wm[i] = fma(P.hh, wd[i], om[i]);
+  quat_G_mul_pinned(qm, wm, d);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) q[r] = fma(P.h, d[r] * 0.5, q[r]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) om[i] = fma(P.h, wd[i], om[i]);
+  const double t = fma(P.hh, vd, V);
+  S = fma(P.h, t, S);
+  V = fma(P.h, vd, V);
+}
+// X_{k+1}: lanes 0..2 of the wave store their p_a and v_a, and the quaternion and body rate that every lane holds (the three
+// lanes write the same seven values to the same words)
+__device__ __forceinline__ void roll_store_lane(double* xk, int lane, const double q[4], const double om[3], double S, double V) {
+  if (lane < 3) {
+    xk[lane] = S;
+    xk[7 + lane] = V;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) xk[3 + r] = q[r];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) xk[10 + i] = om[i];
+  }
+}
+
 // wrench of every knot from the inputs U (WITH_DU: U + dU), lane (k, i), i < 6
 // ONEW (the all-LDS form, one wave per SIMD: nothing hides a wait): the lane's inputs and its point-map row are loaded
 // up front into registers of their own, so that the sums wait for LDS once instead of once per register quad
@@ -834,6 +944,32 @@ __device__ inline void rollout_scaled_w(const DevParams& P, const Layout& L, con
   double gb[3], wd0[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) { gb[a] = cst[D::C_GB + a]; wd0[a] = cst[D::C_WD0 + a]; }
+  if constexpr (ONEW && MD != WM_CONVEX) {
+    // the translation one component per lane (roll_step_lane); the next knot's wrench is loaded ahead as below
+    LanePat lp;
+    lp.init(lane);
+    const double gba = cst[D::C_GB + lp.a];
+    double q[4], om[3], wt[3], wtn[3];
+    double S = cst[D::C_X0 + lp.a], V = cst[D::C_X0 + 7 + lp.a];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q[i] = cst[D::C_X0 + 3 + i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { om[i] = cst[D::C_X0 + 10 + i]; wt[i] = sm[LW.WR + 3 + i]; }
+    double wf = sm[LW.WR + lp.a];
+    for (int k = 0; k < N; ++k) {
+      const int kn = (k + 1 < N) ? k + 1 : k;
+      const double wfn = sm[LW.WR + 6 * kn + lp.a];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) wtn[i] = sm[LW.WR + 6 * kn + 3 + i];
+      roll_step_lane(P, gba, wd0, wf, wt, q, om, S, V);
+      wf = wfn;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) wt[i] = wtn[i];
+      roll_store_lane(sm + L.Xc + 13 * (k + 1), lane, q, om, S, V);
+    }
+    QSYNC();
+    return;
+  }
   double x[13], xn[13], w[6], wn[6];
 #pragma unroll
   for (int i = 0; i < 13; ++i) x[i] = cst[D::C_X0 + i];
@@ -1003,7 +1139,9 @@ __device__ __forceinline__ void roll_load_gains(const LayoutW& LW, const double*
 // as everything is without PF (two waves per SIMD hide the loads).  With xo and ab prefetched too (62 registers more per
 // set) the two sets did not fit beside what is live across the rollout, and the compiler parked about 90 registers in
 // AGPRs in front of the rollout and fetched them back behind it, in every iteration (profiles/HISTORY_r18.md).
-template <bool PROF, bool PF, int NL = 4, int MD = WM_QUAT, bool BC = false>
+// LN (with PF and BC, QuatMpc's models): the knot in the lane form above -- the gain row's sum takes e through row
+// broadcasts from lanes 0..2, lanes 0..2 take their force component from their own sum and the torque is broadcast.
+template <bool PROF, bool PF, int NL = 4, int MD = WM_QUAT, bool BC = false, bool LN = false>
 __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, const LayoutW& LW, double* sm,
                                         const double* KD, double* ROT, int lane, Prof<PROF>& prof, double alpha = 1.0) {
   typedef Dim<NL> D;
@@ -1014,6 +1152,42 @@ __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, con
   for (int a = 0; a < 3; ++a) { gb[a] = cst[D::C_GB + a]; wd0[a] = cst[D::C_WD0 + a]; }
   const int row = (lane < 12) ? lane : 0, wi = (lane < 6) ? lane : 0;
   const bool zlane = lane >= 6 && lane < 12;
+  if constexpr (LN && MD != WM_CONVEX) {
+    static_assert(PF && BC, "the lane form belongs to the all-LDS form with one wave per SIMD");
+    LanePat lp;
+    lp.init(lane);
+    const double gba = cst[D::C_GB + lp.a];
+    double q[4], om[3];
+    double S = cst[D::C_X0 + lp.a], V = cst[D::C_X0 + 7 + lp.a];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q[i] = cst[D::C_X0 + 3 + i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) om[i] = cst[D::C_X0 + 10 + i];
+    roll_store_lane(sm + L.Xc, lane, q, om, S, V);
+    auto knot = [&](int k, RollLoadsW& cur, RollLoadsW& nxt) {
+      RollLoadsL rl;
+      roll_load_lane(L, sm, k, lp, rl);
+      const double s = roll_gain_lane(P.h, q, om, S, V, rl, lp, cur.kd, alpha);
+      if (zlane) ROT[zeta_slot<NL>(k, lane - 6)] = s;
+      double wn = cur.wk + s;
+      tick_dep1(prof, PH_R_GAIN, wn);
+      if (k + 1 < N) roll_load_gains(LW, sm, KD, k + 1, row, wi, nxt);      // one knot ahead
+      double wt[3];
+      wt[0] = row_bcast<3>(wn); wt[1] = row_bcast<4>(wn); wt[2] = row_bcast<5>(wn);
+      tick_dep(prof, PH_R_BCAST, wt[0], wt[2]);
+      roll_step_lane(P, gba, wd0, wn, wt, q, om, S, V);
+      roll_store_lane(sm + L.Xc + 13 * (k + 1), lane, q, om, S, V);
+      tick_dep(prof, PH_R_STEP, q[0], om[0]);
+    };
+    RollLoadsW ra, rb;
+    roll_load_gains(LW, sm, KD, 0, row, wi, ra);
+    for (int k = 0; k < N; k += 2) {
+      knot(k, ra, rb);
+      if (k + 1 < N) knot(k + 1, rb, ra);
+    }
+    QSYNC();
+    return;
+  }
   double xc[13], xn[13];
 #pragma unroll
   for (int i = 0; i < 13; ++i) xc[i] = cst[D::C_X0 + i];

@@ -142,7 +142,7 @@
     if (backward_pass_w<PROF, false, WMT>(P, L, bp, sm, KD, GK, lane, prof)) { status = QMPC_NOT_PD; break; }
     QSYNC();
     double ap, ad;
-    rollout_closed_w<PROF, !KDG, WNL, WMT, !KDG>(P, L, LW, sm, KD, ROT, lane, prof);      // trial step
+    rollout_closed_w<PROF, !KDG, WNL, WMT, !KDG, !KDG>(P, L, LW, sm, KD, ROT, lane, prof);      // trial step
     prof.tick(PH_ROLL);
     {      // input recovery + directions, one lane per (knot, contact point)
       double stp_;      // a non-finite trial step is not applied and must not become the reported step
