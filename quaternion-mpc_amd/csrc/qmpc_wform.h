@@ -1141,6 +1141,14 @@ __device__ __forceinline__ void roll_load_gains(const LayoutW& LW, const double*
 // AGPRs in front of the rollout and fetched them back behind it, in every iteration (profiles/HISTORY_r18.md).
 // LN (with PF and BC, QuatMpc's models): the knot in the lane form above -- the gain row's sum takes e through row
 // broadcasts from lanes 0..2, lanes 0..2 take their force component from their own sum and the torque is broadcast.
+// Its operands are ONE RollLoadsL (19 doubles: q_o, w_o, the lane's p_o / v_o, q_o in the lane's column order, the lane's
+// rows of A1 and A3) and the gain row and wrench component of ONE RollLoadsW, loaded for knot 0 in front of the loop.
+// All of them are dead once the gain row's sum and wn = wk + s exist, so the operands of knot min(k + 1, N - 1) are loaded
+// right there into the same registers and arrive under the state's step: no LDS round trip at the head of a knot's
+// serial chain, no second register set (which never fitted: see above and profiles/HISTORY_r25.md), no role swap and so
+// no loop unrolled by pairs.  The load is unconditional: the clamp stands in for `if (k + 1 < N)`, and the last knot
+// reloads its own operands, which nothing reads.  Nothing these loads read is written during the rollout: L.X, L.AB, KD
+// and LW.WR are read-only here, the stores go to L.Xc and ROT.
 template <bool PROF, bool PF, int NL = 4, int MD = WM_QUAT, bool BC = false, bool LN = false>
 __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, const LayoutW& LW, double* sm,
                                         const double* KD, double* ROT, int lane, Prof<PROF>& prof, double alpha = 1.0) {
@@ -1164,26 +1172,26 @@ __device__ inline void rollout_closed_w(const DevParams& P, const Layout& L, con
 #pragma unroll
     for (int i = 0; i < 3; ++i) om[i] = cst[D::C_X0 + 10 + i];
     roll_store_lane(sm + L.Xc, lane, q, om, S, V);
-    auto knot = [&](int k, RollLoadsW& cur, RollLoadsW& nxt) {
-      RollLoadsL rl;
-      roll_load_lane(L, sm, k, lp, rl);
-      const double s = roll_gain_lane(P.h, q, om, S, V, rl, lp, cur.kd, alpha);
+    RollLoadsL rl;
+    RollLoadsW rw;
+    roll_load_gains(LW, sm, KD, 0, row, wi, rw);
+    roll_load_lane(L, sm, 0, lp, rl);
+    for (int k = 0; k < N; ++k) {
+      const double s = roll_gain_lane(P.h, q, om, S, V, rl, lp, rw.kd, alpha);
       if (zlane) ROT[zeta_slot<NL>(k, lane - 6)] = s;
-      double wn = cur.wk + s;
+      double wn = rw.wk + s;
       tick_dep1(prof, PH_R_GAIN, wn);
-      if (k + 1 < N) roll_load_gains(LW, sm, KD, k + 1, row, wi, nxt);      // one knot ahead
+      // rl, rw.kd and rw.wk are dead from here: the next knot's operands into the same registers, under the state step
+      // (the last knot reloads its own, which nothing reads: no branch)
+      const int kn = (k + 1 < N) ? k + 1 : k;
+      roll_load_gains(LW, sm, KD, kn, row, wi, rw);
+      roll_load_lane(L, sm, kn, lp, rl);
       double wt[3];
       wt[0] = row_bcast<3>(wn); wt[1] = row_bcast<4>(wn); wt[2] = row_bcast<5>(wn);
       tick_dep(prof, PH_R_BCAST, wt[0], wt[2]);
       roll_step_lane(P, gba, wd0, wn, wt, q, om, S, V);
       roll_store_lane(sm + L.Xc + 13 * (k + 1), lane, q, om, S, V);
       tick_dep(prof, PH_R_STEP, q[0], om[0]);
-    };
-    RollLoadsW ra, rb;
-    roll_load_gains(LW, sm, KD, 0, row, wi, ra);
-    for (int k = 0; k < N; k += 2) {
-      knot(k, ra, rb);
-      if (k + 1 < N) knot(k + 1, rb, ra);
     }
     QSYNC();
     return;
