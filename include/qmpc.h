@@ -671,8 +671,8 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
  * unless the handle opted in (qmpc_set_loop_warm_records below; off by default) and for a handle whose knobs leave no
  * wrench-form kernel (QMPC_WFORM=0); QMPC_BATCH_TOO_LARGE above max_batch.  With
  * plant only, everything the plain loop supports works, the warm start included, and the per-tick form keeps the plain
- * loop's solve (lane kernel and hand-off included).  The joint-level loop is not covered: run
- * qmpc_loop_joint_commands_device on the states afterwards.
+ * loop's solve (lane kernel and hand-off included).  Joint commands are not part of these calls: run
+ * qmpc_loop_joint_commands_device on the states afterwards.  Motor torque limits inside the loop: qmpc_loop_run_motors* below.
  *
  * Launch (qmpc_query QMPC_QUERY_LOOP_INSTANCES_PLAN): the persistent kernel up to the plain loop's threshold (2048
  * robots, 4096 warm) on the wrench-form variant the plain loop takes; beyond, the per-tick sequence, whose solve is the
@@ -1202,6 +1202,90 @@ qmpc_status qmpc_loop_run_gaits_device(qmpc_handle* h, const qmpc_loop_params* l
                                        const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
                                        const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen,
                                        const qmpc_gait_params* d_gait, void* stream);
+
+/* ---- motor torque limits and joint torque peaks per robot (which motor is too small; what torque does this fleet need?) ----
+ * The only actuator limit above is qmpc_ground_params::fz_max, a cap on a foot's normal force that knows nothing of the leg's
+ * posture.  A robot's motors saturate in joint torque.  qmpc_loop_run_motors* is qmpc_loop_run_gaits* -- the same arguments in
+ * their order, robots, launch forms (QMPC_QUERY_LOOP_INSTANCES_PLAN answers for it too), refusals, ticks = 0 behaviour,
+ * freezing, halting, ConvexMpc and warm-record opt-ins, the lane tick under QMPC_INSTANCES_AUTO -- with three more arguments
+ * before `stream`: geom (a HOST pointer in both calls, read during the call like op; one geometry for all robots; NULL:
+ * qmpc_default_go1_geometry), per robot a motor record, and per robot a tally, in/out, that accumulates over calls and is
+ * required when motor is given (QMPC_BAD_ARGUMENT otherwise).  motor == NULL: the call IS qmpc_loop_run_gaits*.
+ *
+ * The rule (loop_motor_* in csrc/qmpc_joint_math.h: one source for the device, the host class and the tests) runs in the post
+ * step of a tick, after the body-frame force u that the actuators produce is known (forces_body, or with an actuation record
+ * what the delay line and lag return) and before the ground clamp and the plant step, on R, pos_world and foot_pos_world as
+ * they are there -- the pose before the plant step:
+ *   angles    every leg, every tick: pb = R'(foot - p); q = the closed-form inverse kinematics of pb with the hip branch
+ *             nearest joint_pos[3l].  A NaN in q keeps the previous angles and adds 1 to unreachable_leg_ticks (the rule of
+ *             qmpc_loop_joint_commands).  joint_pos takes q.
+ *   demand    stance legs only (contacts[l] != 0; a swing leg delivers nothing and is not looked at): J = the leg Jacobian at
+ *             q, tau_j = -(J[3j] u0 + J[3j+1] u1 + J[3j+2] u2); peak_tau[3l+j] = max(peak_tau[3l+j], |tau_j|).
+ *   clip      if no |tau_j| > tau_max[3l+j] the leg is untouched -- no arithmetic reaches its bytes; equality does not bind, a
+ *             +inf limit never binds.  Otherwise t_j = copysign(tau_max, tau_j) on the binding joints and tau_j on the others,
+ *             sat_ticks of each binding joint gets +1, and u' solves J' u' = -t (a pivoted 3x3 elimination).  If a component of
+ *             u' is not finite (a singular leg) the leg stays untouched and unreachable_leg_ticks gets +1; otherwise the leg
+ *             delivers u'.
+ *   changed   a leg the motor changed gets grf_world[l] = R u' before the ground clamp sees it; the plant receives u', or R' f
+ *             if the ground changes the leg too.  A leg it did not change keeps exactly what the gaits call gives it.
+ *   fields    forces_body and the trace row hold the command, grf_world the delivered force.  The actuation line's `applied`
+ *             is not touched: the lag is inside the motor, the clip comes after it.  Outcome records, pushes, sensing and gaits
+ *             read what they read in the gaits call.
+ *   tally     if any leg was changed in the tick clipped_ticks gets +1 and first_clipped_tick is set once, to state.tick after
+ *             the tick.
+ *
+ * A record is VALID when every tau_max > 0 (+inf passes, NaN fails) and the reserved words are 0; a tally when its joint_pos is
+ * finite and its counters (sat_ticks, clipped_ticks, unreachable_leg_ticks) are non-negative integers below 2^53.  An invalid
+ * one makes its robot the robot of an invalid plant record (QMPC_BAD_PARAMS, marked by a check kernel after the gait check; its
+ * tally untouched, every other robot unaffected bit for bit).
+ *
+ * IDENTITY: with every limit +inf the robot's state, outcome record, ground tally, delay line, seen and trace rows are the
+ * gaits call's bytes in every launch form; joint_pos and peak_tau are still filled in -- the "what torque does this need" use.
+ *
+ * Buffers: those of the gaits call; the host-buffer call stages records and tallies in a buffer of its own ((128 + 320) B x
+ * max_batch), allocated on its first use (by ticks = 0 too) and counted in QMPC_QUERY_DEVICE_BYTES.  No other call allocates it.
+ * Not modelled: torque-speed derating, a geometry per robot, joint position limits.  The 8-point model and the reference mode
+ * are refused exactly as the gaits call refuses them. */
+typedef struct qmpc_motor_params {   /* 16 doubles, 128 B */
+  double tau_max[12];      /* N m, leg-major (hip, thigh, calf); +inf: no limit */
+  double reserved[4];      /* must be 0 */
+} qmpc_motor_params;
+typedef struct qmpc_motor_tally {    /* 40 doubles, 320 B; in/out, accumulates over calls */
+  double joint_pos[12];    /* the hip-branch memory of the inverse kinematics; start: the stand pose of qmpc_loop_joint_init */
+  double peak_tau[12];     /* the largest |torque| demanded of the joint while its leg stood, before clipping */
+  double sat_ticks[12];    /* the ticks the joint was clipped */
+  double clipped_ticks;    /* the ticks in which the motors changed a leg */
+  double first_clipped_tick;     /* state.tick after the first such tick; -1 until then */
+  double unreachable_leg_ticks;  /* leg-ticks with a foot out of reach or a singular leg under a binding limit */
+  double reserved;
+} qmpc_motor_tally;
+int32_t qmpc_sizeof_motor_params(void);
+int32_t qmpc_sizeof_motor_tally(void);
+/* Host-side; every byte is written: every limit +inf, reserved 0 */
+void    qmpc_default_motor_params(qmpc_motor_params* out);
+/* Host-side; every byte is written: joint_pos the stand pose, first_clipped_tick -1, everything else 0 */
+void    qmpc_motor_tally_init(qmpc_motor_tally* out);
+/* Host buffers: qmpc_loop_run_gaits's arguments, then geom (or NULL), motor [batch] (or NULL), tally [batch].  Synchronous. */
+qmpc_status qmpc_loop_run_motors(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                 int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant,
+                                 double* trace_forces, double* trace_contacts, const qmpc_outcome_params* op,
+                                 qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int32_t pushes_per_robot,
+                                 const qmpc_ground_params* ground, qmpc_ground_tally* tally,
+                                 const qmpc_actuation_params* act, qmpc_actuation_line* line,
+                                 const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait,
+                                 const qmpc_leg_geometry* geom, const qmpc_motor_params* motor, qmpc_motor_tally* motor_tally);
+/* Device buffers (op and geom are host pointers, read during the call), stream-ordered (NULL stream = the handle's). */
+qmpc_status qmpc_loop_run_motors_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch,
+                                        qmpc_loop_state* d_states, int32_t ticks,
+                                        const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                        double* d_trace_forces, double* d_trace_contacts,
+                                        const qmpc_outcome_params* op, qmpc_loop_outcome* d_outcomes,
+                                        const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                        const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
+                                        const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
+                                        const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen,
+                                        const qmpc_gait_params* d_gait, const qmpc_leg_geometry* geom,
+                                        const qmpc_motor_params* d_motor, qmpc_motor_tally* d_motor_tally, void* stream);
 
 /* Stand-pose joint angles (0, 0.67, -1.3 per leg: the reference's Gazebo start pose) for `batch`
  * robots, host buffer [batch][12]. */

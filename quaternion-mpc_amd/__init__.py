@@ -431,6 +431,43 @@ def loop_states_set_gait(states: np.ndarray, gait: np.ndarray, lib: "C.CDLL | No
     return st
 
 
+# struct qmpc_motor_params (qmpc_loop_run_motors*): one robot's joint torque limits, 16 doubles = 128 B.  Joints leg-major
+# (FL, FR, RL, RR) x (hip, thigh, calf)
+MOTOR_PARAMS_DTYPE = np.dtype([("tau_max", "<f8", (12,)), ("reserved", "<f8", (4,))], align=False)
+assert MOTOR_PARAMS_DTYPE.itemsize == 16 * 8
+# struct qmpc_motor_tally: what the motors of one robot were asked for, 40 doubles = 320 B; in/out, accumulates over calls
+MOTOR_TALLY_DTYPE = np.dtype([("joint_pos", "<f8", (12,)), ("peak_tau", "<f8", (12,)), ("sat_ticks", "<f8", (12,)),
+                              ("clipped_ticks", "<f8"), ("first_clipped_tick", "<f8"), ("unreachable_leg_ticks", "<f8"),
+                              ("reserved", "<f8")], align=False)
+assert MOTOR_TALLY_DTYPE.itemsize == 40 * 8
+# the Go1's joint torque limits [N m] per joint type (hip, thigh, calf): 23.7 at the motor, the calf through its 1.5 linkage
+GO1_TAU_MAX = (23.7, 23.7, 35.55)
+
+
+def motor_params(batch: int, tau_max=np.inf) -> np.ndarray:
+    """[batch] motor records: tau_max [N m] a scalar, three values per joint type (hip, thigh, calf), or the full [batch][12]
+    (leg-major).  motor_params(B) is qmpc_default_motor_params: every limit +inf -- nothing binds, the tally still records the
+    torque every joint was asked for."""
+    B = int(batch)
+    out = np.zeros(B, dtype=MOTOR_PARAMS_DTYPE)
+    t = np.asarray(tau_max, dtype=np.float64)
+    if t.ndim == 1 and t.shape == (3,):
+        t = np.tile(t, 4)
+    elif t.ndim not in (0, 2) or (t.ndim == 2 and t.shape != (B, 12)):
+        raise ValueError(f"tau_max: shape {t.shape}, expected a scalar, (3,) or ({B}, 12)")
+    out["tau_max"] = np.broadcast_to(t, (B, 12))
+    return out
+
+
+def motor_tallies(batch: int, lib: "C.CDLL | None" = None) -> np.ndarray:
+    """[batch] motor tallies of qmpc_motor_tally_init: joint_pos the stand pose, first_clipped_tick -1, everything else 0."""
+    lib = lib or load_library()
+    out = np.zeros(int(batch), dtype=MOTOR_TALLY_DTYPE)
+    for i in range(out.shape[0]):
+        lib.qmpc_motor_tally_init(C.c_void_p(out[i:i + 1].ctypes.data))
+    return out
+
+
 # struct qmpc_info: 2 x int32 + 4 doubles = 40 B
 INFO_DTYPE = np.dtype(
     [
@@ -573,6 +610,16 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_loop_run_gaits_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
                                                i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.qmpc_loop_run_gaits_device.restype = i32
+    lib.qmpc_default_motor_params.argtypes = [vp]
+    lib.qmpc_default_motor_params.restype = None
+    lib.qmpc_motor_tally_init.argtypes = [vp]
+    lib.qmpc_motor_tally_init.restype = None
+    lib.qmpc_loop_run_motors.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp,
+                                         vp, vp, vp, vp, vp, C.POINTER(LegGeometry), vp, vp]
+    lib.qmpc_loop_run_motors.restype = i32
+    lib.qmpc_loop_run_motors_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
+                                                i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LegGeometry), vp, vp, vp]
+    lib.qmpc_loop_run_motors_device.restype = i32
     lib.qmpc_set_instances_policy.argtypes = [vp, i32]
     lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_set_loop_warm_records.argtypes = [vp, i32]
@@ -655,7 +702,7 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
                  "qmpc_sizeof_input8", "qmpc_sizeof_loop_state", "qmpc_sizeof_instance_params", "qmpc_sizeof_plant_params",
                  "qmpc_sizeof_loop_outcome", "qmpc_sizeof_push_params", "qmpc_sizeof_ground_params", "qmpc_sizeof_ground_tally",
                  "qmpc_sizeof_actuation_params", "qmpc_sizeof_actuation_line", "qmpc_sizeof_sense_params", "qmpc_sizeof_sense_seen",
-                 "qmpc_sizeof_gait_params"):
+                 "qmpc_sizeof_gait_params", "qmpc_sizeof_motor_params", "qmpc_sizeof_motor_tally"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = i32
     if lib.qmpc_sizeof_input() != INPUT_DTYPE.itemsize:
@@ -687,6 +734,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         raise RuntimeError("qmpc_sense_params / qmpc_sense_seen ABI size mismatch")
     if lib.qmpc_sizeof_gait_params() != GAIT_PARAMS_DTYPE.itemsize:
         raise RuntimeError("qmpc_gait_params ABI size mismatch")
+    if lib.qmpc_sizeof_motor_params() != MOTOR_PARAMS_DTYPE.itemsize or lib.qmpc_sizeof_motor_tally() != MOTOR_TALLY_DTYPE.itemsize:
+        raise RuntimeError("qmpc_motor_params / qmpc_motor_tally ABI size mismatch")
     return lib
 
 
@@ -791,6 +840,12 @@ EXPORTED_SYMBOLS = (
     "qmpc_loop_state_set_gait",
     "qmpc_loop_run_gaits",
     "qmpc_loop_run_gaits_device",
+    "qmpc_sizeof_motor_params",
+    "qmpc_sizeof_motor_tally",
+    "qmpc_default_motor_params",
+    "qmpc_motor_tally_init",
+    "qmpc_loop_run_motors",
+    "qmpc_loop_run_motors_device",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
@@ -1487,6 +1542,85 @@ class Solver:
         if rc != OK:
             raise QmpcError(rc, "qmpc_loop_run_gaits_device")
 
+    def loop_run_motors(self, states: np.ndarray, ticks: int, motor: np.ndarray | None, mtallies: np.ndarray | None = None,
+                        geom: "LegGeometry | None" = None, gait: np.ndarray | None = None, sense: np.ndarray | None = None,
+                        seen: np.ndarray | None = None, act: np.ndarray | None = None, lines: np.ndarray | None = None,
+                        ground: np.ndarray | None = None, push: np.ndarray | None = None, lp: LoopParams | None = None,
+                        ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
+                        outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None, trace: bool = False,
+                        want_seen: bool = True, want_motor_tallies: bool = True):
+        """qmpc_loop_run_motors: loop_run_gaits in which the foot force a stance leg delivers respects the joint torque limits of
+        the robot's motors, and which records the torque every joint was asked for.  motor: [B] MOTOR_PARAMS_DTYPE records,
+        motor_params(); None: exactly loop_run_gaits.  mtallies: [B] MOTOR_TALLY_DTYPE, carried over calls (None: fresh ones
+        of module-level motor_tallies()); geom: one LegGeometry for all robots (None: the Go1's).  Every other record may be None
+        as there.  Returns (states, outcomes, tallies, lines, seen, motor_tallies[, forces, contacts]); the arguments are not
+        modified."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
+        B = st.shape[0]
+
+        def records(a, dtype, name, copy=False):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.shape != (B,):
+                raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
+            return a.copy() if copy else a
+
+        ctrl = records(ctrl, INSTANCE_PARAMS_DTYPE, "ctrl")
+        plant = records(plant, PLANT_PARAMS_DTYPE, "plant")
+        ground = records(ground, GROUND_PARAMS_DTYPE, "ground")
+        act = records(act, ACTUATION_PARAMS_DTYPE, "act")
+        sense = records(sense, SENSE_PARAMS_DTYPE, "sense")
+        gait = records(gait, GAIT_PARAMS_DTYPE, "gait")
+        motor = records(motor, MOTOR_PARAMS_DTYPE, "motor")
+        per_robot = 0
+        if push is not None:
+            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
+            if push.ndim == 1:
+                push = push.reshape(-1, 1)
+            if push.ndim != 2 or push.shape[0] != B:
+                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
+            per_robot = push.shape[1]
+            if per_robot == 0:
+                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
+        oc = loop_outcomes(B, self.lib) if outcomes is None else records(outcomes, LOOP_OUTCOME_DTYPE, "outcomes", copy=True)
+        ta = ground_tallies(B) if tallies is None else records(tallies, GROUND_TALLY_DTYPE, "tallies", copy=True)
+        li = actuation_lines(B) if lines is None else records(lines, ACTUATION_LINE_DTYPE, "lines", copy=True)
+        sn = sense_seen(B) if seen is None else records(seen, SENSE_SEEN_DTYPE, "seen", copy=True)
+        mt = (motor_tallies(B, self.lib) if mtallies is None
+              else records(mtallies, MOTOR_TALLY_DTYPE, "mtallies", copy=True))
+        tf = np.zeros((ticks, B, 12)) if trace else None
+        tc = np.zeros((ticks, B, 4)) if trace else None
+        rc = self.lib.qmpc_loop_run_motors(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
+                                           C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta), _ptr(act),
+                                           _ptr(li), _ptr(sense), _ptr(sn) if want_seen else None, _ptr(gait),
+                                           C.byref(geom) if geom is not None else None, _ptr(motor),
+                                           _ptr(mt) if want_motor_tallies else None)
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_motors")
+        return (st, oc, ta, li, sn, mt, tf, tc) if trace else (st, oc, ta, li, sn, mt)
+
+    def loop_run_motors_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_motor: int, d_motor_tally: int,
+                               geom: "LegGeometry | None" = None, d_gait: int = 0, d_sense: int = 0, d_seen: int = 0, d_act: int = 0,
+                               d_line: int = 0, d_ground: int = 0, d_tally: int = 0, d_push: int = 0, pushes_per_robot: int = 0,
+                               lp: LoopParams | None = None, op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0,
+                               d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_motors_device: device pointers (ints; 0 = NULL), stream-ordered; geom is a host record (None: the Go1's);
+        d_motor, d_gait, d_sense, d_act, d_ground and d_push are read in place, d_motor_tally, d_seen (or 0), d_line and d_tally
+        (or 0) are read and written."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        rc = self.lib.qmpc_loop_run_motors_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
+                                                  p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
+                                                  int(pushes_per_robot), p(d_ground), p(d_tally), p(d_act), p(d_line), p(d_sense),
+                                                  p(d_seen), p(d_gait), C.byref(geom) if geom is not None else None, p(d_motor),
+                                                  p(d_motor_tally), p(stream))
+        if rc != OK:
+            raise QmpcError(rc, "qmpc_loop_run_motors_device")
+
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family
         as KERNEL_FAMILY -- or None where the call is refused (QMPC_QUERY_LOOP_INSTANCES_PLAN).  Answers under the handle's
@@ -1799,5 +1933,6 @@ class Solver:
 
 from .scenarios import (go1_stand_input, quat_to_rot, random_go1_trot_states,  # noqa: E402,F401
                         random_go1_convex_states, random_biped8_states, random_go1_variants, random_go1_convex_variants, random_go1_plants,
-                        random_go1_pushes, random_go1_grounds, random_go1_actuations, random_go1_senses, random_go1_gaits)
+                        random_go1_pushes, random_go1_grounds, random_go1_actuations, random_go1_senses, random_go1_gaits,
+                        random_go1_motors)
 from .sharding import StepPipeline, gather_forces, shard_range, solve_sharded  # noqa: E402,F401

@@ -76,8 +76,9 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
 // (qmpc_loop_run_actuation*), the same entry points once more, no front kernel either.  qmpc_loop_sense.hip: the actuation loop
 // whose controller reads a measured state (qmpc_loop_run_sensing*), with a front kernel of its own that takes the sensing arguments.
 // qmpc_loop_gait.hip: the sensing loop in which every robot walks a gait of its own (qmpc_loop_run_gaits*); its front kernel takes
-// the last argument too.
-#define QMPC_REC_DECLARE(ns)                                                                                                         \
+// the gait argument too.  qmpc_loop_motor.hip: the gait loop whose delivered foot force respects the motors' torque limits
+// (qmpc_loop_run_motors*); its post and persistent kernels take the last three arguments.
+#define QMPC_REC_DECLARE(ns)                                                                                                        \
   namespace ns {                                                                                                                     \
   hipError_t rec_set_lds();                                                                                                          \
   hipError_t rec_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,            \
@@ -86,7 +87,8 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
                               qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,                             \
                               const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act,         \
                               qmpc_actuation_line* line, const qmpc_sense_params* sense, qmpc_sense_seen* seen,                      \
-                              const qmpc_gait_params* gait);                                                                         \
+                              const qmpc_gait_params* gait, const qmpc_leg_geometry* geom, const qmpc_motor_params* motor,           \
+                              qmpc_motor_tally* mtally);                                                                             \
   hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, int* row,            \
                               const void* plants, int batch, const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes,      \
                               const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait);                 \
@@ -94,7 +96,8 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
                              const qmpc_info* info, double* trace_f, double* trace_c, const int* row, const void* plants, int batch, \
                              const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push,              \
                              int per_robot, const qmpc_ground_params* ground, qmpc_ground_tally* tally,                              \
-                             const qmpc_actuation_params* act, qmpc_actuation_line* line);                                           \
+                             const qmpc_actuation_params* act, qmpc_actuation_line* line, const qmpc_leg_geometry* geom,             \
+                             const qmpc_motor_params* motor, qmpc_motor_tally* mtally);                                              \
   }
 QMPC_REC_DECLARE(qmpc_inst_tu)
 QMPC_REC_DECLARE(qmpc_outc_tu)
@@ -108,6 +111,8 @@ QMPC_REC_DECLARE(qmpc_sense_tu)     // qmpc_loop_sense.hip
 QMPC_REC_DECLARE(qmpc_csense_tu)    // qmpc_loop_csense.hip: the sensing call on such a ConvexMpc handle
 QMPC_REC_DECLARE(qmpc_gait_tu)      // qmpc_loop_gait.hip
 QMPC_REC_DECLARE(qmpc_cgait_tu)     // qmpc_loop_cgait.hip: the gait call on such a ConvexMpc handle
+QMPC_REC_DECLARE(qmpc_motor_tu)     // qmpc_loop_motor.hip
+QMPC_REC_DECLARE(qmpc_cmotor_tu)    // qmpc_loop_cmotor.hip: the motor call on such a ConvexMpc handle
 #undef QMPC_REC_DECLARE
 enum { REC_PLAIN = 0, REC_OUTCOME = 1, REC_PUSH = 2 };      // the kind of a call with records: QMPC_REC_EXT of its unit
 enum { REC_CONVEX = 3 };                                    // ... the unit that serves those three kinds for ConvexMpc's problem
@@ -115,12 +120,13 @@ enum { REC_GROUND = 4, REC_CGROUND = 5 };                   // the ground call's
 enum { REC_ACT = 6, REC_CACT = 7 };                         // the actuation call's kind (EXT 4), and its unit for ConvexMpc's problem
 enum { REC_SENSE = 8, REC_CSENSE = 9 };                     // the sensing call's kind (EXT 5), and its unit for ConvexMpc's problem
 enum { REC_GAIT = 10, REC_CGAIT = 11 };                     // the gait call's kind (EXT 6), and its unit for ConvexMpc's problem
+enum { REC_MOTOR = 12, REC_CMOTOR = 13 };                   // the motor call's kind (EXT 7), and its unit for ConvexMpc's problem
 static const struct {
   decltype(&qmpc_inst_tu::rec_set_lds) set_lds;
   decltype(&qmpc_inst_tu::rec_fused_launch) fused_launch;
   decltype(&qmpc_inst_tu::rec_front_launch) front_launch;
   decltype(&qmpc_inst_tu::rec_post_launch) post_launch;
-} kRec[12] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
+} kRec[14] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
              {qmpc_outc_tu::rec_set_lds, qmpc_outc_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_outc_tu::rec_post_launch},
              {qmpc_push_tu::rec_set_lds, qmpc_push_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_push_tu::rec_post_launch},
              {qmpc_crec_tu::rec_set_lds, qmpc_crec_tu::rec_fused_launch, qmpc_crec_tu::rec_front_launch, qmpc_crec_tu::rec_post_launch},
@@ -131,7 +137,9 @@ static const struct {
              {qmpc_sense_tu::rec_set_lds, qmpc_sense_tu::rec_fused_launch, qmpc_sense_tu::rec_front_launch, qmpc_sense_tu::rec_post_launch},
              {qmpc_csense_tu::rec_set_lds, qmpc_csense_tu::rec_fused_launch, qmpc_csense_tu::rec_front_launch, qmpc_csense_tu::rec_post_launch},
              {qmpc_gait_tu::rec_set_lds, qmpc_gait_tu::rec_fused_launch, qmpc_gait_tu::rec_front_launch, qmpc_gait_tu::rec_post_launch},
-             {qmpc_cgait_tu::rec_set_lds, qmpc_cgait_tu::rec_fused_launch, qmpc_cgait_tu::rec_front_launch, qmpc_cgait_tu::rec_post_launch}};
+             {qmpc_cgait_tu::rec_set_lds, qmpc_cgait_tu::rec_fused_launch, qmpc_cgait_tu::rec_front_launch, qmpc_cgait_tu::rec_post_launch},
+             {qmpc_motor_tu::rec_set_lds, qmpc_motor_tu::rec_fused_launch, qmpc_motor_tu::rec_front_launch, qmpc_motor_tu::rec_post_launch},
+             {qmpc_cmotor_tu::rec_set_lds, qmpc_cmotor_tu::rec_fused_launch, qmpc_cmotor_tu::rec_front_launch, qmpc_cmotor_tu::rec_post_launch}};
 // ... and the kernels each unit has beside them: the expansions of the plant blocks and the check of the windows
 hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, const qmpc_plant_params* plant,
                                         const qmpc_instance_params* ctrl, const int* ctrl_status, void* bcast_out, void* plants_out,
@@ -150,6 +158,9 @@ hipError_t rec_sense_check_launch(hipStream_t s, const qmpc_sense_params* sense,
 }
 namespace qmpc_gait_tu {
 hipError_t rec_gait_check_launch(hipStream_t s, const qmpc_gait_params* gait, void* plants, double dt, int batch);
+}
+namespace qmpc_motor_tu {
+hipError_t rec_motor_check_launch(hipStream_t s, const qmpc_motor_params* motor, const qmpc_motor_tally* mtally, void* plants, int batch);
 }
 
 // qmpc_lane.hip (third translation unit): the lane-per-instance kernel of large batches
@@ -283,6 +294,8 @@ struct qmpc_handle {
                                   // records (256 B each), then max_batch seen records (128 B each)
   void* d_gait;                   // staging of qmpc_loop_run_gaits (the host-buffer call), on its first use: max_batch gait records
                                   // (128 B each)
+  void* d_motor;                  // staging of qmpc_loop_run_motors (the host-buffer call), on its first use: max_batch motor tallies
+                                  // (320 B each), then max_batch motor records (128 B each)
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -513,6 +526,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_act) (void)hipFree(h->d_act);
   if (h->d_sense) (void)hipFree(h->d_sense);
   if (h->d_gait) (void)hipFree(h->d_gait);
+  if (h->d_motor) (void)hipFree(h->d_motor);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1244,6 +1258,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_act) b += (sizeof(qmpc_actuation_params) + sizeof(qmpc_actuation_line)) * (size_t)h->max_batch;
       if (h->d_sense) b += (sizeof(qmpc_sense_params) + sizeof(qmpc_sense_seen)) * (size_t)h->max_batch;
       if (h->d_gait) b += sizeof(qmpc_gait_params) * (size_t)h->max_batch;
+      if (h->d_motor) b += (sizeof(qmpc_motor_params) + sizeof(qmpc_motor_tally)) * (size_t)h->max_batch;
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
       return QMPC_OK;
@@ -1731,6 +1746,14 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
   return loop_run_impl(h, lp, batch, d_states, ticks, nullptr, nullptr, g, d_joint_pos, d_cmd, d_trace_cmd, stream);
 }
 
+// the three arguments of qmpc_loop_run_motors* beyond the gait call's (REC_MOTOR only): the geometry on the host, the records
+// and tallies where the call's other records are
+struct loop_motor_args {
+  const qmpc_leg_geometry* geom;
+  const qmpc_motor_params* motor;
+  qmpc_motor_tally* tally;
+};
+
 static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
@@ -1738,20 +1761,21 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
                                        const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
                                        const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
                                        const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
-                                       void* stream);
+                                       void* stream, const loop_motor_args* mo = nullptr);
 
 // The host-buffer closed loop of every kind (qmpc_loop_run*, its arguments checked): states and traces through the handle's
 // staging, which only grows -- [states | force trace | contact trace]; the records given go to the staging halves of the
 // per-instance and plant buffers, outcome records and windows to h->d_outcome and h->d_push, ground records and tallies to
-// h->d_ground, actuation records and delay lines to h->d_act, sensing records and seen to h->d_sense, gait records to h->d_gait
-// (all allocated by the caller)
+// h->d_ground, actuation records and delay lines to h->d_act, sensing records and seen to h->d_sense, gait records to h->d_gait,
+// motor tallies and records to h->d_motor (all allocated by the caller)
 static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
                                      int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                      double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                      const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
                                      qmpc_ground_tally* tally, const qmpc_actuation_params* act = nullptr,
                                      qmpc_actuation_line* line = nullptr, const qmpc_sense_params* sense = nullptr,
-                                     qmpc_sense_seen* seen = nullptr, const qmpc_gait_params* gait = nullptr) {
+                                     qmpc_sense_seen* seen = nullptr, const qmpc_gait_params* gait = nullptr,
+                                     const loop_motor_args* mo = nullptr) {
   const size_t B = (size_t)batch, T = (size_t)ticks;
   const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
                n_tc = trace_contacts ? 4 * B * T : 0;
@@ -1784,10 +1808,19 @@ static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_p
   if (d_sn) HIP_TRY(hipMemcpyAsync(d_sn, seen, sizeof(qmpc_sense_seen) * B, hipMemcpyHostToDevice, h->stream));
   qmpc_gait_params* d_ga = gait ? static_cast<qmpc_gait_params*>(h->d_gait) : nullptr;
   if (d_ga) HIP_TRY(hipMemcpyAsync(d_ga, gait, sizeof(qmpc_gait_params) * B, hipMemcpyHostToDevice, h->stream));
+  loop_motor_args d_mo = {nullptr, nullptr, nullptr};
+  if (mo) {
+    d_mo.geom = mo->geom;
+    d_mo.tally = static_cast<qmpc_motor_tally*>(h->d_motor);
+    d_mo.motor = reinterpret_cast<qmpc_motor_params*>(static_cast<qmpc_motor_tally*>(h->d_motor) + h->max_batch);
+    HIP_TRY(hipMemcpyAsync(const_cast<qmpc_motor_params*>(d_mo.motor), mo->motor, sizeof(qmpc_motor_params) * B, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_mo.tally, mo->tally, sizeof(qmpc_motor_tally) * B, hipMemcpyHostToDevice, h->stream));
+  }
   const qmpc_status rs = loop_records_device(kind, h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
                                              d_tf, d_tc, op, outcomes ? h->d_outcome : nullptr, push ? h->d_push : nullptr, per_robot,
-                                             d_gr, d_ta, d_ac, d_li, d_se, d_sn, d_ga, nullptr);
+                                             d_gr, d_ta, d_ac, d_li, d_se, d_sn, d_ga, nullptr, mo ? &d_mo : nullptr);
   if (rs != QMPC_OK) return rs;
+  if (mo) HIP_TRY(hipMemcpyAsync(mo->tally, d_mo.tally, sizeof(qmpc_motor_tally) * B, hipMemcpyDeviceToHost, h->stream));
   if (d_sn) HIP_TRY(hipMemcpyAsync(seen, d_sn, sizeof(qmpc_sense_seen) * B, hipMemcpyDeviceToHost, h->stream));
   if (d_li) HIP_TRY(hipMemcpyAsync(line, d_li, sizeof(qmpc_actuation_line) * B, hipMemcpyDeviceToHost, h->stream));
   if (d_ta) HIP_TRY(hipMemcpyAsync(tally, d_ta, sizeof(qmpc_ground_tally) * B, hipMemcpyDeviceToHost, h->stream));
@@ -1881,6 +1914,8 @@ static qmpc_status loop_instances_buffers(qmpc_handle* h, int32_t batch, bool ha
 // may be NULL too (no clamp; checked when given), d_act and the count of d_line are checked last.  REC_SENSE
 // (qmpc_loop_run_sensing_device): d_act may be NULL too (checked when given), d_sense is checked last, d_seen may be NULL.
 // REC_GAIT (qmpc_loop_run_gaits_device): d_sense may be NULL too (checked when given), d_gait is checked last.
+// REC_MOTOR (qmpc_loop_run_motors_device): d_gait may be NULL too (checked when given), mo's records and tallies are checked last;
+// mo->geom is a host pointer and travels as a kernel argument.
 static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
@@ -1888,8 +1923,9 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
                                        const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
                                        const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
                                        const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
-                                       void* stream) {
+                                       void* stream, const loop_motor_args* mo) {
   if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !d_states)) return QMPC_BAD_ARGUMENT;
+  if ((kind == REC_MOTOR) != (mo != nullptr) || (mo && (!mo->geom || (batch > 0 && (!mo->motor || !mo->tally))))) return QMPC_BAD_ARGUMENT;
   if (kind != REC_PLAIN && (!op || (batch > 0 && !d_outcomes))) return QMPC_BAD_ARGUMENT;
   if (kind == REC_PLAIN && !d_ctrl && !d_plant)
     return loop_run_impl(h, lp, batch, d_states, ticks, d_trace_forces, d_trace_contacts, nullptr, nullptr, nullptr, nullptr, stream);
@@ -1909,14 +1945,14 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   // a ConvexMpc handle (opted in): one unit for the three kinds -- a call without windows passes none (per_robot = 0), a call
   // without outcome records the handle's scratch and parameters that never halt a robot
   const bool crec = convex_records(h);
-  const auto& R = kRec[kind == REC_GAIT ? (crec ? REC_CGAIT : REC_GAIT) : kind == REC_SENSE ? (crec ? REC_CSENSE : REC_SENSE) : kind == REC_ACT ? (crec ? REC_CACT : REC_ACT) : kind == REC_GROUND ? (crec ? REC_CGROUND : REC_GROUND) : crec ? REC_CONVEX : kind];
+  const auto& R = kRec[kind == REC_MOTOR ? (crec ? REC_CMOTOR : REC_MOTOR) : kind == REC_GAIT ? (crec ? REC_CGAIT : REC_GAIT) : kind == REC_SENSE ? (crec ? REC_CSENSE : REC_SENSE) : kind == REC_ACT ? (crec ? REC_CACT : REC_ACT) : kind == REC_GROUND ? (crec ? REC_CGROUND : REC_GROUND) : crec ? REC_CONVEX : kind];
   qmpc_outcome_params op_none;
   std::memset(&op_none, 0, sizeof op_none);
   if (crec && kind == REC_PLAIN) {
     op = &op_none;
     d_outcomes = h->d_outcome;
   }
-  if ((crec && kind != REC_PUSH && kind != REC_GROUND && kind != REC_ACT && kind != REC_SENSE && kind != REC_GAIT) || !d_push) {
+  if ((crec && kind != REC_PUSH && kind != REC_GROUND && kind != REC_ACT && kind != REC_SENSE && kind != REC_GAIT && kind != REC_MOTOR) || !d_push) {
     d_push = nullptr;
     per_robot = 0;
   }
@@ -1930,15 +1966,19 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
   else
     HIP_TRY(qmpc_loop_outcome_expand_base_launch(s, &h->dev, sizeof h->dev, bcast, plant_dev(h), (int)batch));
   if (d_push) HIP_TRY(qmpc_loop_push_check_launch(s, d_push, (int)per_robot, plant_dev(h), (int)batch));
-  if (kind == REC_GROUND || ((kind == REC_ACT || kind == REC_SENSE || kind == REC_GAIT) && d_ground))
+  if (kind == REC_GROUND || ((kind == REC_ACT || kind == REC_SENSE || kind == REC_GAIT || kind == REC_MOTOR) && d_ground))
     HIP_TRY(qmpc_ground_tu::rec_ground_check_launch(s, d_ground, plant_dev(h), (int)batch));
-  if (kind == REC_ACT || ((kind == REC_SENSE || kind == REC_GAIT) && d_act)) HIP_TRY(qmpc_act_tu::rec_act_check_launch(s, d_act, d_line, plant_dev(h), (int)batch));
-  if (kind == REC_SENSE || (kind == REC_GAIT && d_sense)) HIP_TRY(qmpc_sense_tu::rec_sense_check_launch(s, d_sense, plant_dev(h), (int)batch));
-  if (kind == REC_GAIT) HIP_TRY(qmpc_gait_tu::rec_gait_check_launch(s, d_gait, plant_dev(h), lp->dt, (int)batch));
+  if (kind == REC_ACT || ((kind == REC_SENSE || kind == REC_GAIT || kind == REC_MOTOR) && d_act)) HIP_TRY(qmpc_act_tu::rec_act_check_launch(s, d_act, d_line, plant_dev(h), (int)batch));
+  if (kind == REC_SENSE || ((kind == REC_GAIT || kind == REC_MOTOR) && d_sense)) HIP_TRY(qmpc_sense_tu::rec_sense_check_launch(s, d_sense, plant_dev(h), (int)batch));
+  if (kind == REC_GAIT || (kind == REC_MOTOR && d_gait)) HIP_TRY(qmpc_gait_tu::rec_gait_check_launch(s, d_gait, plant_dev(h), lp->dt, (int)batch));
+  if (kind == REC_MOTOR) HIP_TRY(qmpc_motor_tu::rec_motor_check_launch(s, mo->motor, mo->tally, plant_dev(h), (int)batch));
+  const qmpc_leg_geometry* m_geom = mo ? mo->geom : nullptr;
+  const qmpc_motor_params* m_rec = mo ? mo->motor : nullptr;
+  qmpc_motor_tally* m_tally = mo ? mo->tally : nullptr;
   if (lpp.fused) {
     HIP_TRY(R.fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, d_states, h->d_in, h->d_forces, h->d_info,
                            d_trace_forces, d_trace_contacts, (int)ticks, lpp.gws ? h->d_gws : nullptr, op, d_outcomes, d_push,
-                           (int)per_robot, d_ground, d_tally, d_act, d_line, d_sense, d_seen, d_gait));
+                           (int)per_robot, d_ground, d_tally, d_act, d_line, d_sense, d_seen, d_gait, m_geom, m_rec, m_tally));
     return QMPC_OK;
   }
   auto one_tick = [&](bool first) -> qmpc_status {
@@ -1950,7 +1990,7 @@ static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop
                                                 batch, h->d_in, h->d_forces, h->d_info, warm ? h->d_traj_u : nullptr, nullptr, s);
     if (st != QMPC_OK) return st;
     HIP_TRY(R.post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, h->d_loop_row, plant_dev(h),
-                          (int)batch, op, d_outcomes, d_push, (int)per_robot, d_ground, d_tally, d_act, d_line));
+                          (int)batch, op, d_outcomes, d_push, (int)per_robot, d_ground, d_tally, d_act, d_line, m_geom, m_rec, m_tally));
     return QMPC_OK;
   };
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
@@ -2014,14 +2054,15 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
 // qmpc_loop_run_outcomes): per_robot windows per robot, staged in h->d_push; ground (qmpc_loop_run_ground, with or without push)
 // and tally (or NULL): staged in h->d_ground; act and line (qmpc_loop_run_actuation, with or without ground): staged in h->d_act;
 // sense and seen (or NULL) (qmpc_loop_run_sensing, with or without act): staged in h->d_sense; gait (qmpc_loop_run_gaits, with or
-// without sense): staged in h->d_gait
+// without sense): staged in h->d_gait; mo (qmpc_loop_run_motors, with or without gait): records and tallies staged in h->d_motor
 static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
                                       const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                       double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                       const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
                                       qmpc_ground_tally* tally, const qmpc_actuation_params* act = nullptr,
                                       qmpc_actuation_line* line = nullptr, const qmpc_sense_params* sense = nullptr,
-                                      qmpc_sense_seen* seen = nullptr, const qmpc_gait_params* gait = nullptr) {
+                                      qmpc_sense_seen* seen = nullptr, const qmpc_gait_params* gait = nullptr,
+                                      const loop_motor_args* mo = nullptr) {
   if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!states || !outcomes))) return QMPC_BAD_ARGUMENT;
   const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
   if (cs != QMPC_OK || batch == 0) return cs;
@@ -2037,7 +2078,7 @@ static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp
   }
   // (the push call's ticks = 0 allocates everything a later push call needs, the records' staging included; the outcome call's
   // ticks = 0 stops before it, as it always did)
-  if ((push || ground || act || sense || gait) && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
+  if ((push || ground || act || sense || gait || mo) && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
   if (ground && !h->d_ground)
     HIP_TRY(hipMalloc(&h->d_ground, (sizeof(qmpc_ground_params) + sizeof(qmpc_ground_tally)) * (size_t)h->max_batch));
   if (act && !h->d_act)
@@ -2045,10 +2086,11 @@ static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp
   if (sense && !h->d_sense)
     HIP_TRY(hipMalloc(&h->d_sense, (sizeof(qmpc_sense_params) + sizeof(qmpc_sense_seen)) * (size_t)h->max_batch));
   if (gait && !h->d_gait) HIP_TRY(hipMalloc(&h->d_gait, sizeof(qmpc_gait_params) * (size_t)h->max_batch));
+  if (mo && !h->d_motor) HIP_TRY(hipMalloc(&h->d_motor, (sizeof(qmpc_motor_params) + sizeof(qmpc_motor_tally)) * (size_t)h->max_batch));
   if (ticks == 0) return es;
   if (!h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
-  return loop_records_host(gait ? REC_GAIT : sense ? REC_SENSE : act ? REC_ACT : ground ? REC_GROUND : push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant,
-                           trace_forces, trace_contacts, op, outcomes, push, per_robot, ground, tally, act, line, sense, seen, gait);
+  return loop_records_host(mo ? REC_MOTOR : gait ? REC_GAIT : sense ? REC_SENSE : act ? REC_ACT : ground ? REC_GROUND : push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant,
+                           trace_forces, trace_contacts, op, outcomes, push, per_robot, ground, tally, act, line, sense, seen, gait, mo);
 }
 
 qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2295,6 +2337,69 @@ qmpc_status qmpc_loop_run_gaits(qmpc_handle* h, const qmpc_loop_params* lp, int3
   return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
                             push ? pushes_per_robot : 0, ground, ground ? tally : nullptr, act, act ? line : nullptr, sense,
                             sense ? seen : nullptr, gait);
+}
+
+// ---- the gait loop whose delivered foot force respects the motors' torque limits (qmpc_loop_motor.hip, qmpc_loop_cmotor.hip) --------
+static_assert(sizeof(qmpc_motor_params) == 128, "qmpc_motor_params is 16 doubles");
+static_assert(sizeof(qmpc_motor_tally) == 320, "qmpc_motor_tally is 40 doubles");
+int32_t qmpc_sizeof_motor_params(void) { return (int32_t)sizeof(qmpc_motor_params); }
+int32_t qmpc_sizeof_motor_tally(void) { return (int32_t)sizeof(qmpc_motor_tally); }
+
+void qmpc_default_motor_params(qmpc_motor_params* out) {
+  if (!out) return;
+  for (int a = 0; a < 12; ++a) out->tau_max[a] = HUGE_VAL;
+  for (int a = 0; a < 4; ++a) out->reserved[a] = 0.0;
+}
+
+void qmpc_motor_tally_init(qmpc_motor_tally* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof *out);
+  qmpc_loop_joint_init(out->joint_pos, 1);
+  out->first_clipped_tick = -1.0;
+}
+
+qmpc_status qmpc_loop_run_motors_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
+                                        int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
+                                        double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
+                                        qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t pushes_per_robot,
+                                        const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
+                                        const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
+                                        const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
+                                        const qmpc_leg_geometry* geom, const qmpc_motor_params* d_motor,
+                                        qmpc_motor_tally* d_motor_tally, void* stream) {
+  if (!d_motor)
+    return qmpc_loop_run_gaits_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
+                                      d_push, pushes_per_robot, d_ground, d_tally, d_act, d_line, d_sense, d_seen, d_gait, stream);
+  if (!d_motor_tally) return QMPC_BAD_ARGUMENT;
+  if (d_act && !d_line) return QMPC_BAD_ARGUMENT;
+  if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
+  qmpc_leg_geometry go1;
+  if (!geom) qmpc_default_go1_geometry(&go1);
+  const loop_motor_args mo = {geom ? geom : &go1, d_motor, d_motor_tally};
+  return loop_records_device(REC_MOTOR, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
+                             d_push, d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_act ? d_line : nullptr,
+                             d_sense, d_sense ? d_seen : nullptr, d_gait, stream, &mo);
+}
+
+qmpc_status qmpc_loop_run_motors(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
+                                 const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
+                                 double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
+                                 const qmpc_push_params* push, int32_t pushes_per_robot, const qmpc_ground_params* ground,
+                                 qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line,
+                                 const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait,
+                                 const qmpc_leg_geometry* geom, const qmpc_motor_params* motor, qmpc_motor_tally* motor_tally) {
+  if (!motor)
+    return qmpc_loop_run_gaits(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
+                               pushes_per_robot, ground, tally, act, line, sense, seen, gait);
+  if (!motor_tally) return QMPC_BAD_ARGUMENT;
+  if (act && !line) return QMPC_BAD_ARGUMENT;
+  if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
+  qmpc_leg_geometry go1;
+  if (!geom) qmpc_default_go1_geometry(&go1);
+  const loop_motor_args mo = {geom ? geom : &go1, motor, motor_tally};
+  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
+                            push ? pushes_per_robot : 0, ground, ground ? tally : nullptr, act, act ? line : nullptr, sense,
+                            sense ? seen : nullptr, gait, &mo);
 }
 
 // Diagnostic: per-instance phase cycle counts (s_memtime) of one solve launch.

@@ -4,6 +4,8 @@
 //   A1Kinematics::jac       legged_ctrl/src/utils/A1Kinematics.cpp:15-19 (closed form :86-128)
 //   A1Kinematics::inv_kin   A1Kinematics.cpp:335-459, single-precision atan2 approximation :291-312
 // Host and device run the same expressions; they differ only through sin / cos / acos / sqrt of their math libraries.
+// loop_motor_* at the end: the motor torque limits of the closed loop (qmpc_loop_run_motors*, include/qmpc.h), the one source
+// of that rule for the record-loop kernels (qmpc_loop_rec.inc, QMPC_REC_EXT 7), host/ClosedLoopHost.h and the tests.
 #pragma once
 
 #include "qmpc_loop_math.h"
@@ -165,6 +167,110 @@ QMPC_HD void leg_command(const double* rho_opt, const double* rho_fix, const dou
     vel_tgt[j] = bad_v ? qd[j] : qv[j];
     tau_tgt[j] = planned_contact ? tau[j] : 0.0;            // :367-371
   }
+}
+
+// ---- motor torque limits in the closed loop (qmpc_loop_run_motors*, include/qmpc.h: the rule in full) ----------------------
+// One leg of a tick's motor step, before the ground clamp and the plant step.  R (row-major body -> world), pos and foot are
+// the pose BEFORE the plant step; q_io (3) is the leg's joint_pos, the hip-branch memory, and takes this tick's angles (a foot
+// out of reach keeps the previous ones: the rule of loop_joint_leg); u (3) is the body-frame force the actuators produce,
+// tau_max (3) the leg's limits.  A stance leg: demand (3) gets |tau_j|, tau = -J' u in the shape of leg_command; where some
+// |tau_j| > tau_max[j] (equality does not bind, +inf never binds) the binding torques go to copysign(tau_max, tau) and u_out (3)
+// gets the solution of J' u' = -t (solve3 on the transposed array), unless a component is not finite (a singular leg).  u_out
+// is written for LOOP_MOTOR_CLIPPED only; no arithmetic reaches a leg without that bit (the rule of loop_ground_leg).
+// Returns the leg's word: LOOP_MOTOR_STANCE (demand is set), LOOP_MOTOR_CLIPPED, LOOP_MOTOR_NO_IK and LOOP_MOTOR_SINGULAR (one
+// unreachable_leg_ticks each), LOOP_MOTOR_SAT << j for binding joint j.
+enum { LOOP_MOTOR_CLIPPED = 1, LOOP_MOTOR_NO_IK = 2, LOOP_MOTOR_SINGULAR = 4, LOOP_MOTOR_STANCE = 8, LOOP_MOTOR_SAT = 16 };
+QMPC_HD int loop_motor_leg(const double* rho_opt, const double* rho_fix, const double* R, const double* pos, const double* foot,
+                           bool stance, const double* tau_max, double* q_io, const double* u, double* u_out, double* demand) {
+  QMPC_NO_CONTRACT
+  int v = 0;
+  const double d[3] = {foot[0] - pos[0], foot[1] - pos[1], foot[2] - pos[2]};
+  double pb[3], q[3];
+  for (int a = 0; a < 3; ++a) pb[a] = R[a] * d[0] + R[3 + a] * d[1] + R[6 + a] * d[2];
+  leg_inverse(pb, q_io[0], rho_fix, q);
+  if ((q[0] != q[0]) || (q[1] != q[1]) || (q[2] != q[2])) {
+    for (int a = 0; a < 3; ++a) q[a] = q_io[a];
+    v |= LOOP_MOTOR_NO_IK;
+  }
+  for (int a = 0; a < 3; ++a) q_io[a] = q[a];
+  if (!stance) return v;
+  v |= LOOP_MOTOR_STANCE;
+  const LegPlane k = leg_plane(q, rho_opt, rho_fix);
+  double J[9], tau[3];
+  leg_jacobian(k, J);
+  bool bind = false;
+  for (int j = 0; j < 3; ++j) {
+    tau[j] = -(J[3 * j] * u[0] + J[3 * j + 1] * u[1] + J[3 * j + 2] * u[2]);
+    demand[j] = fabs(tau[j]);
+    if (demand[j] > tau_max[j]) {
+      v |= LOOP_MOTOR_SAT << j;
+      bind = true;
+    }
+  }
+  if (!bind) return v;
+  double JT[9], b[3], x[3];      // J' column-major: JT[3c + r] = J'(r, c) = J(c, r) = J[3r + c]
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) JT[3 * c + r] = J[3 * r + c];
+    b[r] = -((v & (LOOP_MOTOR_SAT << r)) ? copysign(tau_max[r], tau[r]) : tau[r]);
+  }
+  solve3(JT, b, x);
+  if (!((x[0] - x[0] == 0.0) && (x[1] - x[1] == 0.0) && (x[2] - x[2] == 0.0))) return v | LOOP_MOTOR_SINGULAR;
+  for (int a = 0; a < 3; ++a) u_out[a] = x[a];
+  return v | LOOP_MOTOR_CLIPPED;
+}
+
+// A motor record is valid when every tau_max > 0 (+inf passes, a NaN fails the comparison) and the reserved words are 0; a
+// tally when its joint_pos is finite (x - x is 0 only for a finite x) and its counters -- sat_ticks, clipped_ticks,
+// unreachable_leg_ticks -- are non-negative integers that `+ 1.0` still advances (below 2^53).  The robot of an invalid one is
+// frozen like that of an invalid plant record.
+QMPC_HD bool loop_motor_count_valid(double n) { return n >= 0.0 && n < 9007199254740992.0 && n == (double)(long long)n; }
+QMPC_HD bool loop_motor_valid(const qmpc_motor_params& m, const qmpc_motor_tally& t) {
+  QMPC_NO_CONTRACT
+  bool ok = true;
+  for (int a = 0; a < 12; ++a)
+    ok = ok && (m.tau_max[a] > 0.0) && (t.joint_pos[a] - t.joint_pos[a] == 0.0) && loop_motor_count_valid(t.sat_ticks[a]);
+  for (int a = 0; a < 4; ++a) ok = ok && (m.reserved[a] == 0.0);
+  return ok && loop_motor_count_valid(t.clipped_ticks) && loop_motor_count_valid(t.unreachable_leg_ticks);
+}
+
+// The tally of a tick whose leg l returned word[l] and demand[3l ..]; tick_after is state.tick AFTER the tick.  joint_pos is
+// not touched here: loop_motor_leg writes it in place.
+QMPC_HD void loop_motor_tally_one(const int* word, const double* demand, double tick_after, qmpc_motor_tally& t) {
+  int any = 0;
+  for (int l = 0; l < 4; ++l) {
+    const int w = word[l];
+    any |= w & LOOP_MOTOR_CLIPPED;
+    if (w & LOOP_MOTOR_NO_IK) t.unreachable_leg_ticks += 1.0;
+    if (w & LOOP_MOTOR_SINGULAR) t.unreachable_leg_ticks += 1.0;
+    if (w & LOOP_MOTOR_STANCE)
+      for (int j = 0; j < 3; ++j) {
+        if (demand[3 * l + j] > t.peak_tau[3 * l + j]) t.peak_tau[3 * l + j] = demand[3 * l + j];
+        if (w & (LOOP_MOTOR_SAT << j)) t.sat_ticks[3 * l + j] += 1.0;
+      }
+  }
+  if (any) {
+    t.clipped_ticks += 1.0;
+    if (t.first_clipped_tick < 0.0) t.first_clipped_tick = tick_after;
+  }
+}
+
+// The motor step of one robot's tick: the four legs and the tally.  rho_opt [4][3] and rho_fix [4][5] are the geometry's, u
+// (12) the body-frame force the actuators produce; um (12) receives u' on the legs with changed[l] != 0 and is not written
+// elsewhere.  m and t must be valid (loop_motor_valid); t may live in global memory: every word is read and written once.
+// Returns whether any leg changed.
+QMPC_HD int loop_motor_one(const double (*rho_opt)[3], const double (*rho_fix)[5], const qmpc_motor_params& m, qmpc_motor_tally& t,
+                           const double* R, const double* pos, const double* feet, const double* contacts, const double* u,
+                           double tick_after, double* um, int* changed) {
+  int word[4], any = 0;
+  double demand[12];
+  for (int l = 0; l < 4; ++l) {
+    word[l] = loop_motor_leg(rho_opt[l], rho_fix[l], R, pos, feet + 3 * l, contacts[l] != 0.0, m.tau_max + 3 * l,
+                             t.joint_pos + 3 * l, u + 3 * l, um + 3 * l, demand + 3 * l);
+    changed[l] = word[l] & LOOP_MOTOR_CLIPPED;
+    any |= changed[l];
+  }
+  loop_motor_tally_one(word, demand, tick_after, t);
+  return any;
 }
 
 }  // namespace qmpc_joint

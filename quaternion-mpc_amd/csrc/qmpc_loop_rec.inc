@@ -1,6 +1,6 @@
 // qmpc_loop_rec.inc -- the kernels of the closed loop with per-robot records and their launchers, defined once.  Included by
-// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip, qmpc_loop_ground.hip, qmpc_loop_act.hip, qmpc_loop_sense.hip and
-// qmpc_loop_gait.hip inside the unit's namespace, after qmpc_loop.hip, with
+// qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip, qmpc_loop_ground.hip, qmpc_loop_act.hip, qmpc_loop_sense.hip,
+// qmpc_loop_gait.hip and qmpc_loop_motor.hip inside the unit's namespace, after qmpc_loop.hip, with
 //   QMPC_REC_EXT 0   controller and plant records only                          (qmpc_loop_run_instances*)
 //                1   ... and the outcome step after the post step               (qmpc_loop_run_outcomes*)
 //                2   ... whose plant step integrates under timed push windows   (qmpc_loop_run_pushes*)
@@ -12,6 +12,8 @@
 //                    same with QMPC_REC_CONVEX; the actuation record may be absent too).  The first layer in the FRONT end
 //                6   ... and walks the robot's own gait                          (qmpc_loop_run_gaits*; qmpc_loop_cgait.hip: the
 //                    same with QMPC_REC_CONVEX; the sensing record may be absent too)
+//                7   ... whose delivered foot force respects the motors' torque limits (qmpc_loop_run_motors*; qmpc_loop_cmotor.hip:
+//                    the same with QMPC_REC_CONVEX; the gait record may be absent too).  Back in the POST step
 // and, for the sibling controller (qmpc_loop_crec.hip; a handle opts in with qmpc_set_convex_records),
 //   QMPC_REC_CONVEX  defined: ConvexMpc's problem -- ConvexModel and the wrench-form body with QMPC_WMODEL WM_CONVEX, the front
 //                    end loop_front_convex_one on qmpc_convex_input records, the world-frame back end with the robot's plant
@@ -35,7 +37,12 @@
 #endif
 // the post step and, at EXT 3, the two arguments it has beyond the plant block: robot i_'s ground record and tally; at EXT 4
 // (where there may be no ground record) the robot's actuation record and delay line after them; at EXT 5 those may be absent too
-#if QMPC_REC_EXT >= 5
+#if QMPC_REC_EXT >= 7
+#define QMPC_REC_POST loop_post_actuation_one
+#define QMPC_REC_POST_GROUND(i_)                                                                                               \
+  , ground ? ground + (size_t)(i_) : nullptr, tally ? tally + (size_t)(i_) : nullptr, act ? act + (size_t)(i_) : nullptr, \
+      line ? line + (size_t)(i_) : nullptr, G, motor + (size_t)(i_), mtally + (size_t)(i_)
+#elif QMPC_REC_EXT >= 5
 #define QMPC_REC_POST loop_post_actuation_one
 #define QMPC_REC_POST_GROUND(i_)                                                                                               \
   , ground ? ground + (size_t)(i_) : nullptr, tally ? tally + (size_t)(i_) : nullptr, act ? act + (size_t)(i_) : nullptr, \
@@ -90,6 +97,11 @@
 #else
 #define QMPC_REC_GAIT(...)
 #endif
+#if QMPC_REC_EXT >= 7
+#define QMPC_REC_MOTOR(...) __VA_ARGS__
+#else
+#define QMPC_REC_MOTOR(...)
+#endif
 
 // the trace row of a robot that does not move in this tick
 __device__ inline void loop_zero_row(double* __restrict__ trace_f, double* __restrict__ trace_c) {
@@ -120,6 +132,27 @@ __device__ inline PlantDev push_plant(const PlantDev& pl, const qmpc_push_params
 }
 #endif
 
+#if QMPC_REC_EXT >= 7
+// The motor step of a robot's tick (qmpc_loop_run_motors*; the rule: qmpc_joint::loop_motor_one of qmpc_joint_math.h), called by
+// loop_post_actuation_one below once u, the body-frame force the actuators produce, is known.  Out of line: the inverse
+// kinematics and the 3x3 elimination get a register allocation of their own and stay out of the solve's.  m and t point at the
+// robot's 128 B record and 320 B tally in global memory; t is read-modify-written in place.  um receives u' on the legs with
+// changed[l] != 0.  s is read only: R, pos_world and foot_pos_world are the pose before the plant step, s.tick + 1 the tick after.
+__device__ __noinline__ int loop_post_motor(const LegGeom& G, const qmpc_motor_params* __restrict__ m, qmpc_motor_tally* __restrict__ t,
+                                            const double* R, const qmpc_loop_state& s, const double* u, double* um, int* changed) {
+  return qmpc_joint::loop_motor_one(G.rho_opt, G.rho_fix, *m, *t, R, s.pos_world, s.foot_pos_world, s.contacts, u, s.tick + 1.0, um,
+                                    changed);
+}
+// dst_[3l ..] = R u' on the legs the motors changed, in the expression of the non-identity actuation branch
+#define QMPC_REC_MOTOR_GRF(dst_)                                                                                         \
+  do {                                                                                                                   \
+    for (int l = 0; l < 4; ++l)                                                                                          \
+      if (mch[l])                                                                                                        \
+        for (int r = 0; r < 3; ++r)                                                                                      \
+          (dst_)[3 * l + r] = R[3 * r] * um[3 * l] + R[3 * r + 1] * um[3 * l + 1] + R[3 * r + 2] * um[3 * l + 2];       \
+  } while (0)
+#endif
+
 #if QMPC_REC_EXT >= 4
 // The back end of a tick whose force reaches the feet through the robot's delay line and actuator lag
 // (qmpc_loop_run_actuation*), a sibling of loop_post_ground_one below.  After forces_body holds the tick's command,
@@ -130,12 +163,18 @@ __device__ inline PlantDev push_plant(const PlantDev& pl, const qmpc_push_params
 // tally untouched.  grf_world holds the delivered force, forces_body and the trace row the command.  act, line, g and tally
 // point into global memory: one ring slot is read, one written and applied read-modify-written here, inside the post step --
 // nothing of the feature is live across the solve, no block is copied, the ring is indexed in global memory.
+// EXT 7 (qmpc_loop_run_motors*): between a and the ground clamp the motor step (loop_post_motor above) runs on a -- or, for an
+// identity robot, on the forces_body bytes.  A leg it changed gets grf_world = R u' before the clamp sees it and hands the plant
+// u' (R' f if the ground changes it too); every other leg goes through the text below as it stands.  `applied` stays what the
+// line made it.  ConvexMpc with a rejected solve and no ground record: only the changed legs' grf_world entries are written.
 template <int OCC = 1>
 QMPC_LOOP_FN void loop_post_actuation_one(const PlantDev& pl, const qmpc_loop_params& LP, qmpc_loop_state& s,
                                           const double* __restrict__ forces, const qmpc_info& inf, double* __restrict__ trace_f,
                                           double* __restrict__ trace_c, const qmpc_ground_params* __restrict__ g,
                                           qmpc_ground_tally* __restrict__ tally, const qmpc_actuation_params* __restrict__ act,
-                                          qmpc_actuation_line* __restrict__ line) {
+                                          qmpc_actuation_line* __restrict__ line
+                                          QMPC_REC_MOTOR(, const LegGeom& G, const qmpc_motor_params* __restrict__ motor,
+                                                         qmpc_motor_tally* __restrict__ mtally)) {
 #pragma clang fp contract(off)
   const int status = inf.status;
   s.status = (double)status;
@@ -166,10 +205,31 @@ QMPC_LOOP_FN void loop_post_actuation_one(const PlantDev& pl, const qmpc_loop_pa
   if (act)
 #endif
   qmpc_loop::loop_actuation_one(*act, *line, s.forces_body, s.contacts, u);
+#if QMPC_REC_EXT >= 7
+  double um[12];     // u' of the legs the motors changed (mch)
+  int mch[4];
+  const int many = loop_post_motor(G, motor, mtally, R, s, ident ? s.forces_body : u, um, mch);
+#endif
   if (ident) {
 #ifdef QMPC_REC_CONVEX
     if (accepted) {
+#if QMPC_REC_EXT >= 7
+      if (many) QMPC_REC_MOTOR_GRF(s.grf_world);
+#endif
       if (g) any = qmpc_loop::loop_ground_clamp(*g, s.contacts, s.grf_world, verdict);
+#if QMPC_REC_EXT >= 7
+    } else if (g || many) {
+      double fw[12];
+      for (int l = 0; l < 4; ++l)
+        for (int r = 0; r < 3; ++r)
+          fw[3 * l + r] = R[3 * r] * s.forces_body[3 * l] + R[3 * r + 1] * s.forces_body[3 * l + 1] + R[3 * r + 2] * s.forces_body[3 * l + 2];
+      if (many) QMPC_REC_MOTOR_GRF(fw);
+      if (g) any = qmpc_loop::loop_ground_clamp(*g, s.contacts, fw, verdict);
+      for (int l = 0; l < 4; ++l)
+        if (verdict[l] || (many && mch[l]))
+          for (int r = 0; r < 3; ++r) s.grf_world[3 * l + r] = fw[3 * l + r];
+    }
+#else
     } else if (g) {
       double fw[12];
       for (int l = 0; l < 4; ++l)
@@ -180,15 +240,31 @@ QMPC_LOOP_FN void loop_post_actuation_one(const PlantDev& pl, const qmpc_loop_pa
         if (verdict[l])
           for (int r = 0; r < 3; ++r) s.grf_world[3 * l + r] = fw[3 * l + r];
     }
+#endif
 #else
     for (int l = 0; l < 4; ++l)
       for (int r = 0; r < 3; ++r)
         s.grf_world[3 * l + r] = R[3 * r] * s.forces_body[3 * l] + R[3 * r + 1] * s.forces_body[3 * l + 1] +
                                  R[3 * r + 2] * s.forces_body[3 * l + 2];
+#if QMPC_REC_EXT >= 7
+    if (many) QMPC_REC_MOTOR_GRF(s.grf_world);
+#endif
     if (g) any = qmpc_loop::loop_ground_clamp(*g, s.contacts, s.grf_world, verdict);
 #endif
     for (int a = 0; a < 12; ++a) u[a] = s.forces_body[a];
+#if QMPC_REC_EXT >= 7
+    if (many)
+      for (int l = 0; l < 4; ++l)
+        if (mch[l])
+          for (int r = 0; r < 3; ++r) u[3 * l + r] = um[3 * l + r];
+#endif
   } else {
+#if QMPC_REC_EXT >= 7
+    if (many)
+      for (int l = 0; l < 4; ++l)
+        if (mch[l])
+          for (int r = 0; r < 3; ++r) u[3 * l + r] = um[3 * l + r];
+#endif
     for (int l = 0; l < 4; ++l)
       for (int r = 0; r < 3; ++r)
         s.grf_world[3 * l + r] = s.contacts[l] == 0.0 ? 0.0
@@ -406,7 +482,8 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
     const int* __restrict__ row, const PlantDev* __restrict__ pl, QMPC_REC_OUTCOME(qmpc_loop_outcome* __restrict__ oc, )
     QMPC_REC_PUSH(const qmpc_push_params* __restrict__ push, int per_robot, )
     QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, )
-    QMPC_REC_ACT(const qmpc_actuation_params* __restrict__ act, qmpc_actuation_line* __restrict__ line, ) int batch) {
+    QMPC_REC_ACT(const qmpc_actuation_params* __restrict__ act, qmpc_actuation_line* __restrict__ line, )
+    QMPC_REC_MOTOR(LegGeom G, const qmpc_motor_params* __restrict__ motor, qmpc_motor_tally* __restrict__ mtally, ) int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
   const size_t slot = (trace_f || trace_c) ? (size_t)(*row) * batch + i : 0;
@@ -453,6 +530,8 @@ __global__ __launch_bounds__(64) void qmpc_loop_rec_post_kernel(
 // EXT 5: lane 0's FRONT step reaches the robot's 256 B sensing record and its 128 B seen by pointer (loop_front_sense_one): the 13
 // true doubles it saves live across the front end's call only -- the same rule, nothing of the feature is live across the solve.
 // EXT 6: ... and the robot's 128 B gait record, read inside the front end it selects -- the same rule once more.
+// EXT 7: lane 0's POST step calls loop_post_motor, out of line, on the robot's 128 B motor record and 320 B tally by pointer; the
+// geometry (256 B) is a kernel argument -- nothing of the feature is live across the solve.
 // (The two zero-fill loops stay written out: as calls of one inline function they compile to other instructions.)
 template <int VAR>
 __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmpc_loop_rec_fused_kernel(
@@ -463,7 +542,9 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
     QMPC_REC_GROUND(const qmpc_ground_params* __restrict__ ground, qmpc_ground_tally* __restrict__ tally, )
     QMPC_REC_ACT(const qmpc_actuation_params* __restrict__ act, qmpc_actuation_line* __restrict__ line, )
     QMPC_REC_SENSE(const qmpc_sense_params* __restrict__ sense, qmpc_sense_seen* __restrict__ seen, )
-    QMPC_REC_GAIT(const qmpc_gait_params* __restrict__ gait, ) int ticks, int batch, double* __restrict__ gws) {
+    QMPC_REC_GAIT(const qmpc_gait_params* __restrict__ gait, )
+    QMPC_REC_MOTOR(LegGeom G, const qmpc_motor_params* __restrict__ motor, qmpc_motor_tally* __restrict__ mtally, ) int ticks, int batch,
+    double* __restrict__ gws) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int b = blockIdx.x;
   if (b >= batch) return;
@@ -551,6 +632,26 @@ __global__ __launch_bounds__(64, QMPC_SOLVE_WAVES(QMPC_REC_MODEL, VAR)) void qmp
   if (lane == 0) outcomes[b] = oc;
 #endif
 }
+
+#if QMPC_REC_EXT == 7 && !defined(QMPC_REC_CONVEX)
+// ---- the check of the motor records and tallies (QuatMpc's unit only: it does not depend on the model) ----------------------
+// One thread per robot: the verdict of the robot's record and tally (qmpc_joint::loop_motor_valid) into its plant block (a
+// verdict already there stays); the tally is read, never written
+__global__ __launch_bounds__(256) void qmpc_motor_check_kernel(const qmpc_motor_params* __restrict__ motor,
+                                                               const qmpc_motor_tally* __restrict__ mtally, PlantDev* __restrict__ pl,
+                                                               int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  if (!qmpc_joint::loop_motor_valid(motor[i], mtally[i])) pl[i].status = QMPC_BAD_PARAMS;
+}
+
+__attribute__((visibility("hidden"))) hipError_t rec_motor_check_launch(hipStream_t s, const qmpc_motor_params* motor,
+                                                                        const qmpc_motor_tally* mtally, void* plants, int batch) {
+  hipLaunchKernelGGL(qmpc_motor_check_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, motor, mtally,
+                     static_cast<PlantDev*>(plants), batch);
+  return hipGetLastError();
+}
+#endif
 
 #if QMPC_REC_EXT == 6 && !defined(QMPC_REC_CONVEX)
 // ---- the check of the gait records (QuatMpc's unit only: it does not depend on the model) ----------------------------------
@@ -640,13 +741,15 @@ __attribute__((visibility("hidden"))) hipError_t rec_fused_launch(
     qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws,
     const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,
     const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line,
-    const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait) {
+    const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait, const qmpc_leg_geometry* geom,
+    const qmpc_motor_params* motor, qmpc_motor_tally* mtally) {
   const int k = qmpc::wform_index(var);
   if (k < 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kRecFused[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks),
                      static_cast<const PlantDev*>(plants), *lp, QMPC_REC_OUTCOME(*op, ) st, rec, forces, info, trace_f, trace_c,
                      QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, )
-                     QMPC_REC_ACT(act, line, ) QMPC_REC_SENSE(sense, seen, ) QMPC_REC_GAIT(gait, ) ticks, batch, gws);
+                     QMPC_REC_ACT(act, line, ) QMPC_REC_SENSE(sense, seen, ) QMPC_REC_GAIT(gait, )
+                     QMPC_REC_MOTOR(*reinterpret_cast<const LegGeom*>(geom), motor, mtally, ) ticks, batch, gws);
   return hipGetLastError();
 }
 
@@ -668,10 +771,13 @@ __attribute__((visibility("hidden"))) hipError_t rec_post_launch(hipStream_t s, 
                                                                  const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                                                  const qmpc_push_params* push, int per_robot,
                                                                  const qmpc_ground_params* ground, qmpc_ground_tally* tally,
-                                                                 const qmpc_actuation_params* act, qmpc_actuation_line* line) {
+                                                                 const qmpc_actuation_params* act, qmpc_actuation_line* line,
+                                                                 const qmpc_leg_geometry* geom, const qmpc_motor_params* motor,
+                                                                 qmpc_motor_tally* mtally) {
   hipLaunchKernelGGL(qmpc_loop_rec_post_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, *lp, QMPC_REC_OUTCOME(*op, ) st, forces, info,
                      trace_f, trace_c, row, static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, )
-                     QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, ) QMPC_REC_ACT(act, line, ) batch);
+                     QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, ) QMPC_REC_ACT(act, line, )
+                     QMPC_REC_MOTOR(*reinterpret_cast<const LegGeom*>(geom), motor, mtally, ) batch);
   return hipGetLastError();
 }
 
@@ -681,6 +787,10 @@ __attribute__((visibility("hidden"))) hipError_t rec_post_launch(hipStream_t s, 
 #undef QMPC_REC_ACT
 #undef QMPC_REC_SENSE
 #undef QMPC_REC_GAIT
+#undef QMPC_REC_MOTOR
+#ifdef QMPC_REC_MOTOR_GRF
+#undef QMPC_REC_MOTOR_GRF
+#endif
 #ifdef QMPC_REC_FRONT_GAIT
 #undef QMPC_REC_FRONT_GAIT
 #endif

@@ -52,6 +52,10 @@ class ClosedLoopHostBase {
   // the fixed text).  Legs that have not walked yet are reset to their starting phase; walking legs take the new split and
   // frequency at their next transition
   virtual void set_gait(const qmpc_gait_params* gait) = 0;
+  // the robot's motor record and tally (qmpc_loop_run_motors*): all copied (motor or tally null: none -- the legs deliver what
+  // the actuators produce; geom null: the Go1's); the tally the ticks accumulate into is read back with motor_tally
+  virtual void set_motors(const qmpc_leg_geometry* geom, const qmpc_motor_params* motor, const qmpc_motor_tally* tally) = 0;
+  virtual const qmpc_motor_tally& motor_tally() const = 0;
   State state;
 };
 
@@ -137,6 +141,14 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
       else mpc->leg_FSM[l].clear_gait();
     }
   }
+  void set_motors(const qmpc_leg_geometry* geom, const qmpc_motor_params* motor, const qmpc_motor_tally* tally) override {
+    has_motor_ = motor != nullptr && tally != nullptr;
+    if (!has_motor_) return;
+    motor_ = *motor;
+    mtally_ = *tally;
+    mgeom_ = geom ? *geom : joints_.geom;
+  }
+  const qmpc_motor_tally& motor_tally() const override { return mtally_; }
   void reset_outcome() {                                    // qmpc_loop_outcome_init
     std::memset(&outcome_, 0, sizeof outcome_);
     outcome_.down_tick = outcome_.first_rejected_tick = -1.0;
@@ -216,6 +228,15 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
     for (int a = 0; a < 12; ++a) u[a] = state.ctrl.optimized_input[a];
     int verdict[4] = {0, 0, 0, 0};
     bool shaped = false;
+    // the device's motor step (qmpc_joint_math.h: loop_motor_one), on the force the actuators produce and the pose before the
+    // plant step: um holds u' on the legs it changed (mch)
+    int mch[4] = {0, 0, 0, 0};
+    double um[12];
+    bool motored = false;
+    auto motor_step = [&](const double* R, const double* con, const double* ua) {
+      qmpc_joint::loop_motor_one(mgeom_.rho_opt, mgeom_.rho_fix, motor_, mtally_, R, x_, feet_, con, ua, (double)(ticks_ + 1), um, mch);
+      motored = true;
+    };
     if (has_act_) {      // the device's actuation tick (qmpc_loop_math.h: loop_actuation_one): the command enters the robot's delay
                          // line; an identity record goes on as below, any other hands on a, what the actuators produce:
                          // mpc_grf_world = R a (a swing leg: +0.0), clamped on the ground when there is one
@@ -224,8 +245,12 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
       for (int k = 0; k < 12; ++k) c[k] = state.ctrl.optimized_input[k];
       for (int l = 0; l < NUM_LEG; ++l) con[l] = state.ctrl.plan_contacts[l] ? 1.0 : 0.0;
       qmpc_loop::loop_actuation_one(act_, line_, c, con, a);
+      if (has_motor_) motor_step(R, con, qmpc_loop::loop_actuation_identity(act_) ? c : a);
       if (!qmpc_loop::loop_actuation_identity(act_)) {
         shaped = true;
+        for (int l = 0; l < NUM_LEG; ++l)      // (the line's applied keeps a: the clip comes after the lag)
+          if (mch[l])
+            for (int r = 0; r < 3; ++r) a[3 * l + r] = um[3 * l + r];
         double grf[12];
         for (int l = 0; l < NUM_LEG; ++l)
           for (int r = 0; r < 3; ++r)
@@ -235,6 +260,18 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
         for (int l = 0; l < NUM_LEG; ++l)
           if (verdict[l]) qmpc_loop::loop_ground_to_body(R, grf + 3 * l, u + 3 * l);
       }
+    }
+    if (has_motor_ && !shaped) {   // a changed leg: mpc_grf_world = R u' before the ground sees it, the plant receives u'
+      double R[9], con[4];
+      qmpc_loop::quat_to_rot(&x_[3], R);
+      for (int l = 0; l < NUM_LEG; ++l) con[l] = state.ctrl.plan_contacts[l] ? 1.0 : 0.0;
+      if (!motored) motor_step(R, con, u);
+      for (int l = 0; l < NUM_LEG; ++l)
+        if (mch[l])
+          for (int r = 0; r < 3; ++r) {
+            state.ctrl.mpc_grf_world[3 * l + r] = R[3 * r] * um[3 * l] + R[3 * r + 1] * um[3 * l + 1] + R[3 * r + 2] * um[3 * l + 2];
+            u[3 * l + r] = um[3 * l + r];
+          }
     }
     if (has_ground_ && !shaped) {   // the device's ground tick (qmpc_loop_math.h: loop_ground_clamp): the stance legs' world-frame forces are
                          // clamped, a changed leg hands the plant R' f and mpc_grf_world the delivered force; optimized_input stays
@@ -250,7 +287,7 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
           for (int a = 0; a < 3; ++a) state.ctrl.mpc_grf_world[3 * l + a] = grf[3 * l + a];
         }
     }
-    if (n_push_ > 0 || has_ground_ || has_act_) {   // the device's push tick: the plant's constant wrench (none without a plant record, on the handle's mass and
+    if (n_push_ > 0 || has_ground_ || has_act_ || has_motor_) {   // the device's push tick: the plant's constant wrench (none without a plant record, on the handle's mass and
                          // inverse inertia then) under the windows acting at state.tick = ticks_ (qmpc_loop_math.h: loop_push_wrench)
       double f[3] = {0.0, 0.0, 0.0}, tq[3] = {0.0, 0.0, 0.0};
       if (has_plant_)
@@ -412,6 +449,10 @@ class ClosedLoopHostT : public ClosedLoopHostBase<State> {
   bool has_sense_ = false;
   qmpc_gait_params gait_;
   bool has_gait_ = false;
+  qmpc_leg_geometry mgeom_;
+  qmpc_motor_params motor_;
+  qmpc_motor_tally mtally_ = {};
+  bool has_motor_ = false;
   long ticks_ = 0;
 };
 

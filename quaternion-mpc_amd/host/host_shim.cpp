@@ -366,6 +366,14 @@ void qh_gait_raibert(const qmpc_gait_params* gait, double gait_freq, const doubl
   for (int l = 0; l < 4; ++l)
     for (int a = 0; a < 3; ++a) tgt_world[3 * l + a] = s.ctrl.foot_pos_target_world(a, l);
 }
+// ... and its motor record and tally (qmpc_loop_run_motors*; geom null: the Go1's; motor or tally null: none); the tally the ticks
+// accumulate into is read back with qh_loop_motor_tally
+void qh_loop_set_motors(void* p, const qmpc_leg_geometry* geom, const qmpc_motor_params* motor, const qmpc_motor_tally* tally) {
+  static_cast<LoopHarness*>(p)->loop->set_motors(geom, motor, tally);
+}
+void qh_loop_motor_tally(void* p, qmpc_motor_tally* out) { *out = static_cast<LoopHarness*>(p)->loop->motor_tally(); }
+// the rule itself (qmpc_joint_math.h: loop_motor_*, the one source the device compiles too): 1 for a valid record and tally
+int qh_motor_valid(const qmpc_motor_params* motor, const qmpc_motor_tally* tally) { return qmpc_joint::loop_motor_valid(*motor, *tally) ? 1 : 0; }
 void qh_loop_destroy(void* p) {
   LoopHarness* h = static_cast<LoopHarness*>(p);
   if (!h) return;

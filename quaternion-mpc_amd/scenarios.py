@@ -387,3 +387,17 @@ def random_go1_gaits(batch: int, seed: int = 0, first: int = 0, gaits=("trot", "
     names = list(gaits)
     k = np.minimum(np.floor(len(names) * u[:, 0]).astype(np.int64), len(names) - 1)
     return gait_params(batch, gait=[names[j] for j in k], gait_freq=gait_freq[0] + (gait_freq[1] - gait_freq[0]) * u[:, 1])
+
+
+def random_go1_motors(batch: int, seed: int = 0, first: int = 0, scale=(0.5, 1.2)) -> np.ndarray:
+    """`batch` motor records (``struct qmpc_motor_params``, for Solver.loop_run_motors), robot indices first .. first+batch-1, the
+    counter-based generator of random_go1_pushes (a shard equals its block of the whole).  Per robot the Go1's joint torque
+    limits -- 23.7 / 23.7 / 35.55 N m for hip / thigh / calf -- times one factor U(scale) per joint type.  The range is an
+    ASSUMPTION: a worn or derated motor on the low side, a generously specified one on the high side; it is not a measurement
+    of any robot -- sweep it.  Three uniforms per robot."""
+    from . import GO1_TAU_MAX, motor_params
+
+    idx = np.arange(first, first + batch, dtype=np.uint64)
+    u = _uniform(0x5EED8000 + int(seed), idx, 3)
+    k = scale[0] + (scale[1] - scale[0]) * u
+    return motor_params(batch, tau_max=np.tile(k * np.asarray(GO1_TAU_MAX), (1, 4)))

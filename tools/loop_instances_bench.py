@@ -40,6 +40,11 @@ per-robot calls include their expansion kernels.
     front end costs; the sensing call's bytes, stated in the row) and then with a mixed-gait fleet (random_go1_gaits: six gaits at
     1.5 - 3 Hz, started from qmpc_loop_state_set_gait; the robots solve other problems and, on the lane tick, fill more classes of
     the stance sort -- a description of that fleet, not an overhead), with plant records and with controller + plant records.
+--motors [--tau-scale-lo 0.15 --tau-scale-hi 0.6]: instead, same-job pairs of qmpc_loop_run_gaits_device (--gaits' identity case: the
+    same fleet and records) against qmpc_loop_run_motors_device on the same records, first with +inf limits (what a tick's inverse
+    kinematics, Jacobians and tally cost; the gaits call's bytes, stated in the row) and then with the Go1's limits times
+    U(lo, hi) per joint type (random_go1_motors: limits that bind, the robots compute something else), with plant records and
+    with controller + plant records.  Beside each row the fleet's peak torque per joint type and the robots clipped.
 --records uniform|random: every robot carries the handle's values (default), or random_go1_variants / random_go1_plants.
 --warm-records [--mu0 1e-6]: instead, the warm-started loop with controller + plant records (qmpc_set_loop_warm_records) as same-job
     pairs: the plain loop and the call with records, each cold-started (a handle on the default barrier parameter) and
@@ -544,6 +549,104 @@ def gaits(pkg, lib, torch, N, B, a):
     return row
 
 
+def motors(pkg, lib, torch, N, B, a):
+    """the gaits call (--gaits' identity case: the same fleet and records) against the motor call, with +inf limits and with the
+    random limits of random_go1_motors (see the module docstring)"""
+    p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+    lp = pkg.default_loop_params(lib)
+    T = a.ticks
+    rng = np.random.default_rng(5)
+    cmds = np.zeros((B, 7))
+    cmds[:, 0] = rng.uniform(-0.4, 0.4, B); cmds[:, 1] = rng.uniform(-0.15, 0.15, B)
+    cmds[:, 2] = rng.uniform(0.26, 0.32, B); cmds[:, 5] = rng.uniform(-0.4, 0.4, B)
+    cmds[:, 6] = (rng.random(B) < 0.85).astype(float)
+    stand = cmds.copy(); stand[:, 6] = 0.0
+    st = pkg.loop_states(stand, lp, height=0.3, yaw=rng.uniform(-3, 3, B), lib=lib)
+    s = pkg.Solver(p, B, device=0, lib=lib)
+    s.set_instances_policy(a.policy if a.policy != "both" else "wave")
+    s.prepare(B)
+    s.prepare_instances()
+    st = s.loop_run(st, 6, lp)
+    st["movement_mode"] = cmds[:, 6]
+    if a.records == "random":
+        ctrl = pkg.random_go1_variants(B, seed=12, base=p)
+        ctrl["mu"] = np.maximum(ctrl["mu"], 0.5)
+        plant = pkg.random_go1_plants(B, seed=11, base=p, payload=(-1.0, 3.0), force=(0.0, 10.0))
+    else:
+        ctrl, plant = pkg.instance_params(p, B), pkg.plant_params(p, B)
+    push = pkg.random_go1_pushes(B, seed=13, per_robot=1, impulse=(1.0, 5.0), dt=lp.dt)
+    push["start_tick"] += 1e9      # beyond any run
+    loose = pkg.ground_params(B)
+    loose["mu"], loose["fz_max"] = 10.0, 1e4
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).cuda()      # noqa: E731
+    d_st0, d_oc0, d_ta0, d_ctrl, d_plant, d_push = dev(st), dev(pkg.loop_outcomes(B, lib)), dev(pkg.ground_tallies(B)), dev(ctrl), dev(plant), dev(push)
+    d_li0, d_sn0, d_mt0 = dev(pkg.actuation_lines(B, pkg.stand_forces_body(p.mass))), dev(pkg.sense_seen(B)), dev(pkg.motor_tallies(B, lib))
+    d_loose, d_act, d_sense, d_gait = dev(loose), dev(pkg.actuation_params(B)), dev(pkg.sense_params(B)), dev(pkg.gait_params(B, lp=lp))
+    d_free, d_bind = dev(pkg.motor_params(B)), dev(pkg.random_go1_motors(B, seed=16, scale=(a.tau_scale_lo, a.tau_scale_hi)))
+    d_st, d_oc, d_ta, d_li, d_sn, d_mt = d_st0.clone(), d_oc0.clone(), d_ta0.clone(), d_li0.clone(), d_sn0.clone(), d_mt0.clone()
+    op = pkg.default_outcome_params(lib)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    torch.cuda.synchronize()
+    calls = {}
+    for name, c in (("plant", 0), ("ctrl_plant", d_ctrl.data_ptr())):
+        calls[name + "_gaits"] = lambda c=c: s.loop_run_gaits_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), d_gait.data_ptr(), d_sense.data_ptr(),
+                                                                    d_sn.data_ptr(), d_act.data_ptr(), d_li.data_ptr(), d_loose.data_ptr(),
+                                                                    d_ta.data_ptr(), d_push.data_ptr(), 1, lp, op, d_ctrl=c,
+                                                                    d_plant=d_plant.data_ptr(), stream=sp)
+        for kind, d_m in (("free", d_free), ("binding", d_bind)):
+            calls[name + "_" + kind] = lambda c=c, d_m=d_m: s.loop_run_motors_device(B, d_st.data_ptr(), T, d_oc.data_ptr(), d_m.data_ptr(), d_mt.data_ptr(),
+                                                                                     None, d_gait.data_ptr(), d_sense.data_ptr(), d_sn.data_ptr(),
+                                                                                     d_act.data_ptr(), d_li.data_ptr(), d_loose.data_ptr(),
+                                                                                     d_ta.data_ptr(), d_push.data_ptr(), 1, lp, op, d_ctrl=c,
+                                                                                     d_plant=d_plant.data_ptr(), stream=sp)
+    times, bits, fin, tal = {k: [] for k in calls}, {}, {}, {}
+    for r in range(a.warmup + a.reps):
+        for k, fn in calls.items():
+            with torch.cuda.stream(stream):
+                d_st.copy_(d_st0)
+                d_oc.copy_(d_oc0)
+                d_ta.copy_(d_ta0)
+                d_li.copy_(d_li0)
+                d_sn.copy_(d_sn0)
+                d_mt.copy_(d_mt0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            if r >= a.warmup:
+                times[k].append(e0.elapsed_time(e1))
+            bits[k] = (d_st.cpu().numpy().tobytes(), d_oc.cpu().numpy().tobytes(), d_ta.cpu().numpy().tobytes(), d_li.cpu().numpy().tobytes())
+            fin[k] = d_st.cpu().numpy().view(pkg.LOOP_STATE_DTYPE).reshape(B)
+            tal[k] = d_mt.cpu().numpy().view(pkg.MOTOR_TALLY_DTYPE).reshape(B)
+    forms = {"plant": s.loop_instances_plan(B, False, False), "ctrl_plant": s.loop_instances_plan(B, True, False)}
+    s.close()
+    ms = {k: float(np.median(v)) for k, v in times.items()}
+    row = {"N": N, "B": B, "ticks": T, "records": a.records, "policy": a.policy}
+    for k in ("plant", "ctrl_plant"):
+        q = k + "_gaits"
+        row.update({q + "_ms": ms[q], k + "_form": forms[k], q + "_spread": (max(times[q]) - min(times[q])) / ms[q]})
+        print(f"N={N:2d} B={B:6d} {k:10s} {forms[k]}: gaits call {ms[q]:9.3f} ms (min {min(times[q]):.3f}, max {max(times[q]):.3f}, spread "
+              f"{100 * row[q + '_spread']:.1f} %)", flush=True)
+        for kind, what in (("free", "+inf limits"), ("binding", f"Go1 limits x U({a.tau_scale_lo}, {a.tau_scale_hi})")):
+            g = k + "_" + kind
+            same = bits[g] == bits[q]
+            ok = int(np.isin(fin[g]["status"], (pkg.OK, pkg.MAX_ITER)).sum())
+            t = tal[g]
+            peak = t["peak_tau"].reshape(B, 4, 3).max(axis=1)
+            row.update({g + "_ms": ms[g], g + "_ratio": ms[g] / ms[q], g + "_spread": (max(times[g]) - min(times[g])) / ms[g],
+                        g + "_same_bytes_as_gaits": same, g + "_robots_ok": ok, g + "_robots_clipped": int((t["clipped_ticks"] > 0).sum()),
+                        g + "_peak_tau_by_type_max": peak.max(axis=0).tolist(), g + "_peak_tau_by_type_median": np.median(peak, axis=0).tolist(),
+                        g + "_unreachable_leg_ticks": float(t["unreachable_leg_ticks"].sum())})
+            print(f"    motor call, {what:28s} {ms[g]:9.3f} ms (min {min(times[g]):.3f}, max {max(times[g]):.3f}, spread "
+                  f"{100 * row[g + '_spread']:.1f} %)   motor / gaits {row[g + '_ratio']:.4f}   the gaits call's bytes: {same}   "
+                  f"robots OK: {ok}, clipped: {row[g + '_robots_clipped']}, peak torque hip / thigh / calf [N m] max "
+                  f"{np.round(peak.max(axis=0), 2).tolist()} median {np.round(np.median(peak, axis=0), 2).tolist()}, unreachable leg-ticks "
+                  f"{row[g + '_unreachable_leg_ticks']:.0f}", flush=True)
+    return row
+
+
 def warm_records(pkg, lib, torch, N, B, a):
     """cold against warm, the plain loop and the call with controller + plant records (see the module docstring)"""
     lp_c = pkg.default_loop_params(lib)
@@ -665,6 +768,9 @@ def main():
     ap.add_argument("--actuation", action="store_true")
     ap.add_argument("--sensing", action="store_true")
     ap.add_argument("--gaits", action="store_true")
+    ap.add_argument("--motors", action="store_true")
+    ap.add_argument("--tau-scale-lo", type=float, default=0.15)
+    ap.add_argument("--tau-scale-hi", type=float, default=0.6)
     ap.add_argument("--policy", choices=("wave", "auto", "both"), default="wave")
     ap.add_argument("--records", choices=("uniform", "random"), default="uniform")
     ap.add_argument("--warm-records", action="store_true")
@@ -679,7 +785,7 @@ def main():
     if a.stop and not a.outcomes:
         ap.error("--stop goes with --outcomes")
     convex = a.model == "convex"
-    if convex and (a.pushes or a.stop or a.ground or a.actuation or a.sensing or a.gaits):
+    if convex and (a.pushes or a.stop or a.ground or a.actuation or a.sensing or a.gaits or a.motors):
         ap.error("--model convex goes with the default comparison, --outcomes and --warm-records")
     for item in a.sizes.split(","):
         N, B = (int(x) for x in item.split(":"))
@@ -698,6 +804,9 @@ def main():
             continue
         if a.gaits:
             rows.append(gaits(pkg, lib, torch, N, B, a))
+            continue
+        if a.motors:
+            rows.append(motors(pkg, lib, torch, N, B, a))
             continue
         if a.warm_records:
             rows.append(warm_records(pkg, lib, torch, N, B, a))

@@ -7,7 +7,7 @@ inertia); the controller is the handle's and is not told about the push.
                                   [--recover 200] [--horizon 10] [--controller quat|convex|both] [--ctrl-records] [--warm] [--json FILE]
                                   [--mu-true LO HI [--mu-steps 5]] [--delay LO HI] [--tau LO HI [--tau-steps 3]]
                                   [--gyro-bias LO HI] [--pos-noise LO HI] [--att-noise LO HI] [--vel-noise LO HI] [--sense-steps 3]
-                                  [--gait NAME[,NAME...]] [--gait-freq LO HI [--gait-steps 3]]
+                                  [--gait NAME[,NAME...]] [--gait-freq LO HI [--gait-steps 3]] [--tau-max S]
 Every robot stands for 6 ticks, trots at --speed for --settle ticks, is shoved at tick 6 + settle + start for --length ticks with
 force impulse / (length dt) in its cell's direction (0 degrees: ahead, 90: to its left), and trots on until --recover ticks after
 the last start.  Down: below 0.15 m or tilted beyond 60 degrees (qmpc_default_outcome_params); stop_when_down halts a fallen robot.
@@ -34,6 +34,11 @@ for every named gait (trot, pace, bound, trot_overlap, crawl, amble) and for --g
 --gait-freq: the loop's 2.2 Hz).  The six standing ticks put every leg at its gait's starting phase.  The start ticks stay spread over
 the 91 ticks of the 2.2 Hz period whatever the frequency.  A table of falls per (impulse, gait, frequency) cell is printed after the
 tables above, which then pool them.  Without --gait and --gait-freq the call is the sensing call and the robots trot as before.
+
+--tau-max S: the motor axis (qmpc_loop_run_motors: the foot force a stance leg delivers respects the joint torque limits).  Every robot
+gets the Go1's 23.7 / 23.7 / 35.55 N m (hip, thigh, calf) times S.  After the tables above: per leg and joint the share of ticks the
+joint saturated and the peak torque it was asked for (median and maximum over the robots).  S = inf limits nothing and reports the
+torque the grid needs.
 --ctrl-records: every robot also carries a controller record (the handle's values: the same controller) and the handle takes
 QMPC_INSTANCES_AUTO, a ConvexMpc handle with qmpc_set_convex_lane_records as well -- the launch a sweep over per-robot controllers
 takes: from the switch-over on the lane kernel with per-lane parameters under either controller.
@@ -88,6 +93,7 @@ def main():
     ap.add_argument("--gait", default=None, help="names of quaternion_mpc_amd.GAITS, comma-separated")
     ap.add_argument("--gait-freq", type=float, nargs=2, default=None, metavar=("LO", "HI"))
     ap.add_argument("--gait-steps", type=int, default=3)
+    ap.add_argument("--tau-max", type=float, default=None, metavar="S", help="the Go1's joint torque limits times S on every robot")
     a = ap.parse_args()
     pkg = load_pkg()
     lib = pkg.load_library()
@@ -173,10 +179,13 @@ def run(a, pkg, lib, controller):
     total = a.settle + PERIOD + a.recover
     w0 = time.perf_counter()
     # (gait = None: the sensing call; sense = None: the actuation call; act = None: the ground call; ground = None: the push call)
-    st, oc, ta, line, seen = s.loop_run_gaits(st, 6, gait, sense, None, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op)
+    # (motor = None: the gaits call)
+    motor = pkg.motor_params(B, a.tau_max * np.asarray(pkg.GO1_TAU_MAX)) if a.tau_max is not None else None
+    st, oc, ta, line, seen, mt = s.loop_run_motors(st, 6, motor, None, None, gait, sense, None, act, line, ground, push, lp, ctrl=ctrl, plant=plant,
+                                                   op=op)
     st["movement_mode"] = 1.0
-    st, oc, ta, line, seen = s.loop_run_gaits(st, total, gait, sense, seen, act, line, ground, push, lp, ctrl=ctrl, plant=plant, op=op, outcomes=oc,
-                                              tallies=ta)
+    st, oc, ta, line, seen, mt = s.loop_run_motors(st, total, motor, mt, None, gait, sense, seen, act, line, ground, push, lp, ctrl=ctrl,
+                                                   plant=plant, op=op, outcomes=oc, tallies=ta)
     wall = time.perf_counter() - w0
     s.close()
     up = (oc["down_tick"] < 0).reshape(len(impulses), len(starts), 8, members)
@@ -262,7 +271,22 @@ def run(a, pkg, lib, controller):
               " ".join(f"{n}: {int(before[:, :, :, :, g].sum())}" for g, n in enumerate(names)) + "\n")
         by_gait = {"gaits": names, "gait_freq": freqs.tolist(), "cell": cell, "down": down.sum(axis=(1, 2, 3, 6)).tolist(),
                    "down_before_shove": before.sum(axis=(0, 1, 2, 3, 5, 6)).tolist()}
-    return {"controller": controller, "by_mu_true": by_mu, "by_actuation": by_time, "by_sensing": by_sense, "by_gait": by_gait, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
+    by_motor = None
+    if motor is not None:
+        ticks = np.maximum(oc["ticks"], 1.0)[:, None]      # (robots that went down stop counting at their down tick)
+        share_sat = (mt["sat_ticks"].reshape(B, 4, 3) / ticks[:, :, None]).mean(axis=0)
+        peak = mt["peak_tau"].reshape(B, 4, 3)
+        lim = a.tau_max * np.asarray(pkg.GO1_TAU_MAX)
+        print(f"motors: the Go1's limits x {a.tau_max:g} = {np.round(lim, 2).tolist()} N m (hip, thigh, calf); {int((mt['clipped_ticks'] > 0).sum())} of {B} "
+              f"robots clipped, {mt['clipped_ticks'].mean():.1f} clipped ticks per robot, {int(mt['unreachable_leg_ticks'].sum())} unreachable leg-ticks")
+        print("leg    share of ticks saturated (hip thigh calf)    peak torque asked, N m: median (hip thigh calf) | max (hip thigh calf)")
+        for l, n in enumerate(("FL", "FR", "RL", "RR")):
+            print(f"{n:4s}  " + " ".join(f"{v:7.4f}" for v in share_sat[l]) + "        " +
+                  " ".join(f"{v:7.2f}" for v in np.median(peak[:, l], axis=0)) + "  | " + " ".join(f"{v:7.2f}" for v in peak[:, l].max(axis=0)))
+        print()
+        by_motor = {"tau_max_scale": a.tau_max, "tau_max": lim.tolist(), "robots_clipped": int((mt["clipped_ticks"] > 0).sum()),
+                    "sat_share": share_sat.tolist(), "peak_tau_median": np.median(peak, axis=0).tolist(), "peak_tau_max": peak.max(axis=0).tolist()}
+    return {"controller": controller, "by_motor": by_motor, "by_mu_true": by_mu, "by_actuation": by_time, "by_sensing": by_sense, "by_gait": by_gait, "impulses": impulses, "starts": starts, "directions_deg": np.degrees(angles).tolist(),
             "per_cell": members, "length_ticks": a.length, "speed": a.speed, "form": form, "share_up": share.tolist()}
 
 
