@@ -315,8 +315,11 @@ enum qmpc_query_what {
                                            (qmpc_set_convex_records); 0 (default): they refuse it */
   QMPC_QUERY_CONVEX_LANE_RECORDS  = 14, /* 1: ConvexMpc's calls with per-instance records may take the lane kernel with per-lane
                                            parameters under QMPC_INSTANCES_AUTO (qmpc_set_convex_lane_records); 0 (default) */
-  QMPC_QUERY_CONVEX_WARM_RECORDS  = 15  /* 1: the closed loops with controller records accept lp->warm_start on this ConvexMpc
+  QMPC_QUERY_CONVEX_WARM_RECORDS  = 15, /* 1: the closed loops with controller records accept lp->warm_start on this ConvexMpc
                                            handle (qmpc_set_convex_warm_records, with qmpc_set_convex_records); 0 (default) */
+  QMPC_QUERY_KERNEL_FOR_SCHEDULE  = 16  /* arg = batch: the qmpc_kernel_family qmpc_solve_schedule* launches for that size
+                                           (QMPC_KERNEL_NONE: the handle refuses the call); the same under either
+                                           qmpc_instances_policy */
 };
 enum qmpc_kernel_family {
   QMPC_KERNEL_NONE         = 0,
@@ -402,6 +405,48 @@ typedef enum qmpc_instances_policy {
                                 qmpc_solve_instances* and in the closed loops' ticks with controller records */
 } qmpc_instances_policy;
 qmpc_status qmpc_set_instances_policy(qmpc_handle* h, int32_t policy);
+
+/* ---- a contact schedule over the horizon (QuatMpc handle, converged mode, four contact points) ------------------------------
+ * qmpc_input::contacts pins a leg to stance or swing at all N knots (QuatMpc.cpp:118-125 does the same).  These calls take
+ * the stance set PER KNOT: schedule[b][k], k = 0 ... N-1, one byte per knot, bit l set where leg l stands during knot k
+ * (qmpc_gait_predict below writes such rows from a robot's gait state).  The problem of instance b:
+ *   - a leg in the air at a knot carries exactly zero force there and is no variable there; traj_u[k][3l ..] is +0.0
+ *   - the cone rows of a (knot, leg) exist only where the bit is set
+ *   - the input reference is the knot's: u_ref_k[3l+2] = c_kl mass 9.81 / nc_k, nc_k the number of legs standing at knot k
+ *   - dynamics, state cost, attitude cost, references and foot_pos_body (ONE position per leg for the whole horizon) are those
+ *     of qmpc_solve.  For a leg that is in the air now and lands inside the horizon the caller sets foot_pos_body[l] to the
+ *     touchdown point: the leg's foot_target_world, taken to the body frame like the other feet.  No knot-0 arithmetic reads
+ *     the position of a leg that is in the air at knot 0.
+ *   - qmpc_input::contacts is NOT read.  Knot 0 of the schedule decides which legs get a force: forces_body is knot 0 of the
+ *     solution.
+ * A schedule that repeats the record's contacts at every knot gives qmpc_solve_instances*' wave-kernel results bit for bit
+ * (forces, info, trajectories).
+ *
+ * iparams: per-instance robot and cost records as in qmpc_solve_instances, or NULL: the handle's own values for every
+ * instance.  Per instance: a knot without a stance leg gives QMPC_NO_CONTACT (flight phases are not covered), a byte above 15
+ * QMPC_BAD_PARAMS, an invalid record QMPC_BAD_PARAMS; each with zero forces, zero trajectory rows and 0 iterations, the other
+ * instances unaffected.  Call level: QMPC_UNSUPPORTED for a ConvexMpc or 8-point handle, a reference-mode handle, or a handle
+ * whose knobs leave no wrench-form kernel (QMPC_WFORM=0); QMPC_BATCH_TOO_LARGE above max_batch; QMPC_BAD_ARGUMENT for a null
+ * in, schedule or forces_body.
+ *
+ * Kernel: qmpc_solve_w_sched_kernel, the wave-per-instance wrench-form kernel of qmpc_solve_instances with the stance set
+ * asked per knot -- the variant that call takes for the size under QMPC_INSTANCES_WAVE, under either policy (the lane kernel
+ * has no schedule form).  qmpc_query(QMPC_QUERY_KERNEL_FOR_SCHEDULE) names the family for a batch size,
+ * QMPC_QUERY_LAST_KERNEL the one the last call took.  Buffers: those of qmpc_prepare_instances, and for the host-buffer call
+ * N bytes per instance of schedule staging, allocated on first use and counted in QMPC_QUERY_DEVICE_BYTES.
+ * Not covered: warm starts, the closed loops, the lane kernel, ConvexMpc, the 8-point model, the reference mode, a second
+ * foothold per leg inside one horizon. */
+/* Synchronous, host buffers: in [batch], iparams [batch] or NULL, schedule [batch][N], forces_body [batch][12]; info, traj_u
+ * ([batch][N][12]) and traj_x ([batch][N+1][13]) may be NULL. */
+qmpc_status qmpc_solve_schedule(qmpc_handle* h, int32_t batch, const qmpc_input* in,
+                                const qmpc_instance_params* iparams, const uint8_t* schedule, double* forces_body,
+                                qmpc_info* info, double* traj_u, double* traj_x);
+/* Device buffers, stream-ordered (NULL stream = the handle's), nothing synchronised; d_iparams, d_info, d_traj_u and d_traj_x
+ * may be NULL.  One launch in flight per handle. */
+qmpc_status qmpc_solve_schedule_device(qmpc_handle* h, int32_t batch, const qmpc_input* d_in,
+                                       const qmpc_instance_params* d_iparams, const uint8_t* d_schedule,
+                                       double* d_forces_body, qmpc_info* d_info, double* d_traj_u, double* d_traj_x,
+                                       void* stream);
 
 /* ---- per-instance robot and cost parameters for ConvexMpc's problem (ConvexMpc handle, converged mode) ------------------
  * qmpc_solve_instances* for the sibling controller: qmpc_convex_input records, world-frame forces, and the same 304-byte
@@ -1183,6 +1228,18 @@ void    qmpc_default_gait_params(const qmpc_loop_params* lp, qmpc_gait_params* o
 /* Host-side: the reset rule above on the four legs of s, and contacts = the legs' states.  After qmpc_loop_state_init, for a
  * robot that walks (movement_mode != 0) from tick 0 in the gait's own pattern.  The record is not checked. */
 void    qmpc_loop_state_set_gait(qmpc_loop_state* s, const qmpc_gait_params* gait);
+/* The contact schedule a robot's gait state implies over a horizon: masks[k], k = 0 ... N-1, bit l set where leg l stands during
+ * knot k -- a row of qmpc_solve_schedule*'s schedule.  Host-side, no GPU involved.  masks[0] is s->contacts as it stands; then a
+ * copy of each leg's gait_phase, state, pattern_index, start_time and end_time is advanced N - 1 times by gait_freq * h with the
+ * schedule step of the loop's tick (the stance exit at end_time, the swing exit at the end of the swing arc, the pattern's
+ * next entry), without early contacts and without the swing trajectory, one mask after each advance.  *s is not changed.
+ * g == NULL: the reference's trot at lp->gait_freq (qmpc_default_gait_params); otherwise lp may be NULL.  h: the knot spacing
+ * (the handle's params.h).  Nothing is written for a null s or masks, N < 1, or g and lp both null.
+ * For a leg the schedule lands inside the horizon the caller of qmpc_solve_schedule* puts the touchdown point into
+ * qmpc_input::foot_pos_body[l]: the leg's foot_target_world, taken to the body frame like the other feet.  (The closed loops do
+ * not call this yet.) */
+void    qmpc_gait_predict(const qmpc_loop_params* lp, const qmpc_gait_params* g, const qmpc_loop_state* s, double h, int32_t N,
+                          uint8_t* masks);
 /* Host buffers: qmpc_loop_run_sensing's arguments, then gait [batch] (or NULL).  Synchronous. */
 qmpc_status qmpc_loop_run_gaits(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
                                 int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant,

@@ -431,6 +431,58 @@ def loop_states_set_gait(states: np.ndarray, gait: np.ndarray, lib: "C.CDLL | No
     return st
 
 
+def constant_schedule(inputs: np.ndarray, N: int) -> np.ndarray:
+    """[B, N] uint8 schedule for Solver.solve_schedule: the record's contacts at every knot (bit l: leg l stands).  With it the
+    call gives solve_instances' results bit for bit."""
+    inputs = np.ascontiguousarray(inputs, dtype=INPUT_DTYPE)
+    m = ((inputs["contacts"] != 0.0).astype(np.uint8) << np.arange(4, dtype=np.uint8)).sum(axis=1).astype(np.uint8)
+    return np.ascontiguousarray(np.repeat(m[:, None], int(N), axis=1))
+
+
+def predict_schedule(lp: "LoopParams | None", gait: "np.ndarray | None", states: np.ndarray, h: float, N: int,
+                     lib: "C.CDLL | None" = None) -> np.ndarray:
+    """qmpc_gait_predict per robot: [B, N] uint8, row b the contact schedule robot b's gait state implies over N knots h apart
+    (knot 0: its current contacts).  gait None: the reference's trot at lp.gait_freq for every robot.  `states` is not changed."""
+    lib = lib or load_library()
+    st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE)
+    B = st.shape[0]
+    g = None if gait is None else np.ascontiguousarray(gait, dtype=GAIT_PARAMS_DTYPE)
+    if g is not None and g.shape != (B,):
+        raise ValueError(f"gait: shape {g.shape}, expected ({B},)")
+    if g is None and lp is None:
+        lp = default_loop_params(lib)
+    out = np.zeros((B, int(N)), dtype=np.uint8)
+    for i in range(B):
+        lib.qmpc_gait_predict(C.byref(lp) if lp is not None else None, C.c_void_p(g[i:i + 1].ctypes.data) if g is not None else None,
+                              C.c_void_p(st[i:i + 1].ctypes.data), float(h), int(N), C.c_void_p(out[i:i + 1].ctypes.data))
+    return out
+
+
+SCHEDULE_FAMILIES = ("constant", "trot_four_other", "trot_other", "trot_three")
+
+
+def schedule_families(inputs: np.ndarray, N: int) -> dict:
+    """The four schedule families the schedule tests and tools/instance_params_bench.py --schedule share, for a batch of trot
+    records, as {name: [B, N] uint8}.  With m the record's stance set and o the legs it leaves out -- the other diagonal of a
+    trot record; for a record whose four legs all stand, the diagonal FL + RR (the robot starts to trot):
+      constant         m at every knot
+      trot_four_other  m for 3 knots, all four legs for 2, o for the rest      (at N = 10: 3 + 2 + 5)
+      trot_other       m for the first 2N/5 knots, o for the rest, no overlap  (4 + 6)
+      trot_three       m for the first N/2 knots, then m plus the lowest-numbered other leg  (5 + 5)"""
+    N = int(N)
+    c = constant_schedule(inputs, N)
+    m = c[:, 0]
+    o = (np.uint8(15) & ~m).astype(np.uint8)
+    o = np.where(o == 0, np.uint8(9), o).astype(np.uint8)
+    low = (o & (~o + np.uint8(1))).astype(np.uint8)      # lowest set bit of the other diagonal
+    k = np.arange(N)[None, :]
+    four = np.where(k < 3, m[:, None], np.where(k < 5, np.uint8(15), o[:, None])).astype(np.uint8)
+    other = np.where(k < (2 * N) // 5, m[:, None], o[:, None]).astype(np.uint8)
+    three = np.where(k < N // 2, m[:, None], (m | low)[:, None]).astype(np.uint8)
+    return {"constant": c, "trot_four_other": np.ascontiguousarray(four), "trot_other": np.ascontiguousarray(other),
+            "trot_three": np.ascontiguousarray(three)}
+
+
 # struct qmpc_motor_params (qmpc_loop_run_motors*): one robot's joint torque limits, 16 doubles = 128 B.  Joints leg-major
 # (FL, FR, RL, RR) x (hip, thigh, calf)
 MOTOR_PARAMS_DTYPE = np.dtype([("tau_max", "<f8", (12,)), ("reserved", "<f8", (4,))], align=False)
@@ -546,6 +598,12 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_solve_instances.restype = i32
     lib.qmpc_solve_instances_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.qmpc_solve_instances_device.restype = i32
+    lib.qmpc_solve_schedule.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.qmpc_solve_schedule.restype = i32
+    lib.qmpc_solve_schedule_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.qmpc_solve_schedule_device.restype = i32
+    lib.qmpc_gait_predict.argtypes = [vp, vp, vp, C.c_double, i32, vp]
+    lib.qmpc_gait_predict.restype = None
     lib.qmpc_convex_solve_instances.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     lib.qmpc_convex_solve_instances.restype = i32
     lib.qmpc_convex_solve_instances_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
@@ -846,6 +904,9 @@ EXPORTED_SYMBOLS = (
     "qmpc_motor_tally_init",
     "qmpc_loop_run_motors",
     "qmpc_loop_run_motors_device",
+    "qmpc_solve_schedule",
+    "qmpc_solve_schedule_device",
+    "qmpc_gait_predict",
 )
 
 # enum qmpc_query_what / qmpc_kernel_family (include/qmpc.h)
@@ -857,6 +918,7 @@ QUERY_KERNEL_FOR_CONVEX_INSTANCES = 12
 QUERY_CONVEX_RECORDS = 13
 QUERY_CONVEX_LANE_RECORDS = 14
 QUERY_CONVEX_WARM_RECORDS = 15
+QUERY_KERNEL_FOR_SCHEDULE = 16
 # enum qmpc_instances_policy
 INSTANCES_WAVE, INSTANCES_AUTO = 0, 1
 INSTANCES_POLICY = {"wave": INSTANCES_WAVE, "auto": INSTANCES_AUTO}
@@ -1140,6 +1202,40 @@ class Solver:
                                                   C.c_void_p(d_info) if d_info else None, C.c_void_p(stream) if stream else None)
         if st != OK:
             raise QmpcError(st, "qmpc_solve_instances_device")
+
+    def solve_schedule(self, inputs: np.ndarray, schedule: np.ndarray, iparams: np.ndarray | None = None, want_traj: bool = False):
+        """qmpc_solve_schedule: instance i solved with the stance set schedule[i, k] at knot k (uint8, bit l: leg l stands; the
+        record's contacts are not read) and, with iparams (INSTANCE_PARAMS_DTYPE), its own robot and cost record -- None: the
+        handle's values.  Returns (forces [B,12], info) or, with want_traj, also traj_u [B,N,12] and traj_x [B,N+1,13]."""
+        inputs = np.ascontiguousarray(inputs, dtype=INPUT_DTYPE)
+        B, N = inputs.shape[0], self.params.horizon
+        schedule = np.ascontiguousarray(schedule, dtype=np.uint8)
+        if schedule.shape != (B, N):
+            raise ValueError(f"schedule: shape {schedule.shape}, expected ({B}, {N})")
+        if iparams is not None:
+            iparams = np.ascontiguousarray(iparams, dtype=INSTANCE_PARAMS_DTYPE)
+            if iparams.shape != (B,):
+                raise ValueError(f"iparams: shape {iparams.shape}, expected ({B},)")
+        forces = np.zeros((B, NU), dtype=np.float64)
+        info = np.zeros(B, dtype=INFO_DTYPE)
+        tu = np.zeros((B, N, NU)) if want_traj else None
+        tx = np.zeros((B, N + 1, NX)) if want_traj else None
+        st = self.lib.qmpc_solve_schedule(self._h, B, _ptr(inputs), _ptr(iparams), _ptr(schedule), _ptr(forces), _ptr(info), _ptr(tu), _ptr(tx))
+        if st != OK:
+            raise QmpcError(st, "qmpc_solve_schedule")
+        return (forces, info, tu, tx) if want_traj else (forces, info)
+
+    def solve_schedule_device(self, batch: int, d_in: int, d_iparams: int, d_schedule: int, d_forces: int, d_info: int = 0,
+                              d_traj_u: int = 0, d_traj_x: int = 0, stream: int = 0):
+        """qmpc_solve_schedule_device: device pointers (ints; 0 for an optional one), stream-ordered, no synchronisation."""
+        opt = lambda a: C.c_void_p(a) if a else None      # noqa: E731
+        st = self.lib.qmpc_solve_schedule_device(self._h, int(batch), C.c_void_p(d_in), opt(d_iparams), C.c_void_p(d_schedule),
+                                                 C.c_void_p(d_forces), opt(d_info), opt(d_traj_u), opt(d_traj_x), opt(stream))
+        if st != OK:
+            raise QmpcError(st, "qmpc_solve_schedule_device")
+
+    def kernel_for_schedule(self, batch: int) -> str:
+        return KERNEL_FAMILY[self.query(QUERY_KERNEL_FOR_SCHEDULE, batch)]
 
     def loop_run_instances(self, states: np.ndarray, ticks: int, lp: LoopParams | None = None, ctrl: np.ndarray | None = None,
                            plant: np.ndarray | None = None, trace: bool = False):

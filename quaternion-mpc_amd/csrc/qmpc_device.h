@@ -41,10 +41,39 @@ constexpr int MAT = 12 * LD;    // 192 doubles = 3 MFMA fragments of 64 lanes
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
+#ifdef QMPC_WSCHED
+// The contact schedule of one instance (qmpc_solve_schedule*, qmpc_wform_sched.hip), compiled in only by a
+// unit that defines QMPC_WSCHED ahead of its includes: nibble k of the 128 bits is the stance set of knot k (bit l: leg l), uz<n>
+// the vertical input reference of a stance leg at a knot where n legs stand, mass 9.81 / n (QuatMpc.cpp:
+// 121-125 per knot).  Wave-uniform: the words live in scalar registers, a lane shifts them by its own knot.
+struct WSched {
+  unsigned long long w0, w1;      // knots 0 .. 15, 16 .. 31
+  double uz1, uz2, uz3, uz4;
+  // (every member is read into a value before a select: a conditional on the members themselves is a conditional ADDRESS, and
+  // the layout that carries this struct would live in scratch instead of registers)
+  __device__ __forceinline__ unsigned mask(int k) const {
+    const unsigned long long lo = w0, hi = w1;
+    const unsigned long long w = (k < 16) ? lo : hi;
+    return (unsigned)(w >> (4 * (k & 15))) & 15u;
+  }
+  __device__ __forceinline__ bool stance(int k, int l) const { return (mask(k) >> l) & 1u; }
+  __device__ __forceinline__ double uref_z(int k, int l) const {
+    const unsigned m = mask(k);
+    const int n = __popc(m);
+    const double a = uz1, b = uz2, c = uz3, d = uz4;
+    const double v = n == 1 ? a : (n == 2 ? b : (n == 3 ? c : d));
+    return ((m >> l) & 1u) ? v : 0.0;
+  }
+};
+#endif
+
 // ---- per-instance LDS layout (offsets in doubles) ---------------------------
 struct Layout {
   int cst, bw0, refp, uref, X, U, Xc, dU, S, LAM, DS, DLAM, RC, AB, XT, KD, ROT, tile, total;
   int CV;      // wrench-form layouts of ConvexMpc's problem (make_layout_w): 8 doubles per knot, Iw(yaw_m)^-1 and Iw(yaw_m)
+#ifdef QMPC_WSCHED
+  WSched sc;   // travels with the layout: every function of qmpc_wform.h that asks for a stance set already takes one
+#endif
 };
 
 // Per-knot record sizes

@@ -226,6 +226,14 @@ hipError_t qmpc_wform_cinst_warm_launch(int var, int batch, size_t lds, hipStrea
                                         const qmpc_input* in, const double* u_init, double* forces, qmpc_info* info, double* traj_u,
                                         double* gws, int check_prev);
 
+// qmpc_wform_sched.hip: QuatMpc's solve with a contact schedule over the horizon (qmpc_solve_schedule*)
+hipError_t qmpc_wform_sched_set_lds();
+hipError_t qmpc_wform_sched_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
+                                   const qmpc_input* in, const unsigned char* sched, double* forces, qmpc_info* info, double* traj_u,
+                                   double* traj_x, double* gws);
+hipError_t qmpc_wform_sched_expand_uniform_launch(int batch, hipStream_t s, const void* dev_params, size_t dev_params_size,
+                                                  const qmpc_instance_params* rec, void* dev_out, int* status_out);
+
 // qmpc_wform_cinst.hip: ConvexMpc's solve with per-instance parameters (qmpc_convex_solve_instances*)
 hipError_t qmpc_wform_cinst_set_lds();
 hipError_t qmpc_wform_cinst_solve_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const int* status,
@@ -296,6 +304,8 @@ struct qmpc_handle {
                                   // (128 B each)
   void* d_motor;                  // staging of qmpc_loop_run_motors (the host-buffer call), on its first use: max_batch motor tallies
                                   // (320 B each), then max_batch motor records (128 B each)
+  unsigned char* d_sched;         // staging of qmpc_solve_schedule (the host-buffer call), on its first use: max_batch schedules
+                                  // of N bytes
 };
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
@@ -454,6 +464,7 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   HIP_TRY(qmpc_wform_inst_warm_set_lds());
   HIP_TRY(qmpc_wform_cinst_set_lds());
   HIP_TRY(qmpc_wform_cinst_warm_set_lds());
+  HIP_TRY(qmpc_wform_sched_set_lds());
   HIP_TRY(hipMalloc(&h->d_gws, sizeof(double) * (size_t)N * (13 * nu + 21 * nl + 30 * nl) * (size_t)max_batch));
   return QMPC_OK;
 }
@@ -527,6 +538,7 @@ void qmpc_destroy(qmpc_handle* h) {
   if (h->d_sense) (void)hipFree(h->d_sense);
   if (h->d_gait) (void)hipFree(h->d_gait);
   if (h->d_motor) (void)hipFree(h->d_motor);
+  if (h->d_sched) (void)hipFree(h->d_sched);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1180,6 +1192,79 @@ qmpc_status qmpc_convex_solve_instances(qmpc_handle* h, int32_t batch, const qmp
   return solve_instances_host(h, true, batch, reinterpret_cast<const qmpc_input*>(in), iparams, forces_world, info, traj_u, traj_x);
 }
 
+// ---- a contact schedule over the horizon (qmpc_wform_sched.hip: qmpc_solve_w_sched_kernel) -------------
+// The buffers, the expansion kernel and the verdicts of qmpc_solve_instances*; the schedule is one more kernel argument.
+static qmpc_status schedule_check(const qmpc_handle* h, int32_t batch) {
+  if (h->params.model != QMPC_MODEL_QUAT || h->params.mode != QMPC_MODE_CONVERGED) return QMPC_UNSUPPORTED;
+  if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
+  if (batch > 0 && plan_schedule(h->sel, batch).family == QMPC_KERNEL_NONE) return QMPC_UNSUPPORTED;
+  return QMPC_OK;
+}
+// expansion (the records, or the handle's own values once per call) + solve on stream s; everything in device-addressable memory
+static qmpc_status launch_schedule(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_rec,
+                                   const uint8_t* d_sched, double* d_forces, qmpc_info* d_info, double* d_tu, double* d_tx, hipStream_t s) {
+  const qmpc_plan p = plan_schedule(h->sel, batch);
+  const qmpc_status es = ensure_instance_buffers(h);
+  if (es != QMPC_OK) return es;
+  HIP_TRY(hipEventRecord(h->ev0, s));
+  if (d_rec) {
+    HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_rec, inst_dev(h), inst_status(h)));
+  } else {
+    qmpc_instance_params own;
+    qmpc_instance_params_from(&h->params, &own);
+    HIP_TRY(qmpc_wform_sched_expand_uniform_launch((int)batch, s, &h->dev, sizeof h->dev, &own, inst_dev(h), inst_status(h)));
+  }
+  HIP_TRY(qmpc_wform_sched_launch(p.variant, (int)batch, p.lds, s, inst_dev(h), inst_status(h), d_in, d_sched, d_forces, d_info, d_tu, d_tx,
+                                  p.gws ? h->d_gws : nullptr));
+  h->last_kernel = p.family;
+  HIP_TRY(hipEventRecord(h->ev1, s));
+  h->timed = true;
+  return QMPC_OK;
+}
+
+qmpc_status qmpc_solve_schedule_device(qmpc_handle* h, int32_t batch, const qmpc_input* d_in, const qmpc_instance_params* d_iparams,
+                                       const uint8_t* d_schedule, double* d_forces_body, qmpc_info* d_info, double* d_traj_u,
+                                       double* d_traj_x, void* stream) {
+  if (!h || batch < 0 || (batch > 0 && (!d_in || !d_schedule || !d_forces_body))) return QMPC_BAD_ARGUMENT;
+  const qmpc_status cs = schedule_check(h, batch);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  HIP_TRY(hipSetDevice(h->device));
+  return launch_schedule(h, batch, d_in, d_iparams, d_schedule, d_forces_body, d_info, d_traj_u, d_traj_x,
+                         stream ? (hipStream_t)stream : h->stream);
+}
+
+qmpc_status qmpc_solve_schedule(qmpc_handle* h, int32_t batch, const qmpc_input* in, const qmpc_instance_params* iparams,
+                                const uint8_t* schedule, double* forces_body, qmpc_info* info, double* traj_u, double* traj_x) {
+  if (!h || batch < 0 || (batch > 0 && (!in || !schedule || !forces_body))) return QMPC_BAD_ARGUMENT;
+  const qmpc_status cs = schedule_check(h, batch);
+  if (cs != QMPC_OK || batch == 0) return cs;
+  HIP_TRY(hipSetDevice(h->device));
+  // an earlier qmpc_solve_async was never waited for: complete it first (it owes a pageable caller its copy-out)
+  if (h->pending.forces || h->pending.info || h->stage_in_busy) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    finish_pending(h);
+    h->stage_in_busy = 0;
+  }
+  const int N = h->params.horizon;
+  const qmpc_status es = ensure_instance_buffers(h);
+  if (es != QMPC_OK) return es;
+  if (!h->d_sched) HIP_TRY(hipMalloc(&h->d_sched, (size_t)N * (size_t)h->max_batch));
+  if (traj_u && !h->d_traj_u) HIP_TRY(hipMalloc(&h->d_traj_u, sizeof(double) * 12 * N * (size_t)h->max_batch));
+  if (traj_x && !h->d_traj_x) HIP_TRY(hipMalloc(&h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)h->max_batch));
+  HIP_TRY(hipMemcpyAsync(h->d_in, in, sizeof(qmpc_input) * (size_t)batch, hipMemcpyDefault, h->stream));
+  if (iparams) HIP_TRY(hipMemcpyAsync(inst_rec(h), iparams, sizeof(qmpc_instance_params) * (size_t)batch, hipMemcpyDefault, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_sched, schedule, (size_t)N * (size_t)batch, hipMemcpyDefault, h->stream));
+  const qmpc_status st = launch_schedule(h, batch, h->d_in, iparams ? inst_rec(h) : nullptr, h->d_sched, h->d_forces, h->d_info,
+                                         traj_u ? h->d_traj_u : nullptr, traj_x ? h->d_traj_x : nullptr, h->stream);
+  if (st != QMPC_OK) return st;
+  HIP_TRY(hipMemcpyAsync(forces_body, h->d_forces, sizeof(double) * 12 * (size_t)batch, hipMemcpyDefault, h->stream));
+  if (info) HIP_TRY(hipMemcpyAsync(info, h->d_info, sizeof(qmpc_info) * (size_t)batch, hipMemcpyDefault, h->stream));
+  if (traj_u) HIP_TRY(hipMemcpyAsync(traj_u, h->d_traj_u, sizeof(double) * 12 * N * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  if (traj_x) HIP_TRY(hipMemcpyAsync(traj_x, h->d_traj_x, sizeof(double) * 13 * (N + 1) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return QMPC_OK;
+}
+
 qmpc_status qmpc_prepare_instances(qmpc_handle* h) {
   if (!h) return QMPC_BAD_ARGUMENT;
   const bool convex = h->params.model == QMPC_MODEL_CONVEX;      // (ConvexMpc: the lane form on a handle that opted in only)
@@ -1259,6 +1344,7 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_sense) b += (sizeof(qmpc_sense_params) + sizeof(qmpc_sense_seen)) * (size_t)h->max_batch;
       if (h->d_gait) b += sizeof(qmpc_gait_params) * (size_t)h->max_batch;
       if (h->d_motor) b += (sizeof(qmpc_motor_params) + sizeof(qmpc_motor_tally)) * (size_t)h->max_batch;
+      if (h->d_sched) b += (size_t)N * (size_t)h->max_batch;
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
       return QMPC_OK;
@@ -1284,6 +1370,10 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       return QMPC_OK;
     case QMPC_QUERY_CONVEX_LANE_RECORDS: *value = h->opts.convex_lane; return QMPC_OK;
     case QMPC_QUERY_CONVEX_WARM_RECORDS: *value = h->opts.convex_warm; return QMPC_OK;
+    case QMPC_QUERY_KERNEL_FOR_SCHEDULE:
+      if (arg < 1 || arg > h->max_batch) return QMPC_BAD_ARGUMENT;
+      *value = plan_schedule(h->sel, (int)arg).family;
+      return QMPC_OK;
     default: return QMPC_BAD_ARGUMENT;
   }
 }
@@ -2303,6 +2393,14 @@ void qmpc_loop_state_set_gait(qmpc_loop_state* s, const qmpc_gait_params* gait) 
     qmpc_loop::loop_gait_reset(*gait, l, s->leg[l]);
     s->contacts[l] = s->leg[l].state;
   }
+}
+
+void qmpc_gait_predict(const qmpc_loop_params* lp, const qmpc_gait_params* g, const qmpc_loop_state* s, double h, int32_t N,
+                       uint8_t* masks) {
+  if (!s || !masks || (!g && !lp)) return;
+  qmpc_gait_params trot;
+  if (!g) qmpc_default_gait_params(lp, &trot);      // the reference's trot at lp->gait_freq, the identity record
+  qmpc_loop::loop_gait_predict(g ? *g : trot, *s, h, (int)N, masks);
 }
 
 qmpc_status qmpc_loop_run_gaits_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,

@@ -104,4 +104,9 @@ static inline int wform_convex_inst_slot(int var) { return wform_index(var); }
 constexpr int kWformConvexInstWarmSlots = 3;
 static inline int wform_convex_inst_warm_slot(int var) { return wform_index(var); }
 
+// ---- qmpc_wform_sched.hip -----------------------------------------------------------------------------------------------
+// qmpc_solve_w_sched_kernel<WVAR> (qmpc_solve_schedule*: QuatMpc's problem with a contact schedule over the horizon): 3 5 6
+constexpr int kWformSchedSlots = 3;
+static inline int wform_sched_slot(int var) { return wform_index(var); }
+
 }  // namespace qmpc

@@ -555,6 +555,43 @@ QMPC_HD double loop_gait_update(const qmpc_gait_params& g, int leg, qmpc_loop_le
   }
   return L.gait_phase;
 }
+// The contact schedule a robot's gait state implies over a horizon of N knots h apart (qmpc_gait_predict, include/qmpc.h; the
+// rows qmpc_solve_schedule* reads): masks[k], bit l set where leg l stands during knot k.  Knot 0 is the state's current contacts;
+// then a COPY of each leg's schedule fields (gait_phase, state, pattern_index, start_time, end_time) is advanced N - 1 times by
+// gait_freq h with exactly the schedule step of loop_gait_update -- the stance-exit test, the percent >= 1 swing exit,
+// loop_gait_common_enter -- without an early contact (flag = false) and without the swing trajectory.  Nothing in *s changes.
+QMPC_HD void loop_gait_predict(const qmpc_gait_params& g, const qmpc_loop_state& s, double h, int N, unsigned char* masks) {
+  QMPC_NO_CONTRACT
+  if (N < 1) return;
+  qmpc_loop_leg L[4] = {};
+  unsigned m0 = 0;
+  for (int l = 0; l < 4; ++l) {
+    L[l].gait_phase = s.leg[l].gait_phase;
+    L[l].state = s.leg[l].state;
+    L[l].pattern_index = s.leg[l].pattern_index;
+    L[l].start_time = s.leg[l].start_time;
+    L[l].end_time = s.leg[l].end_time;
+    m0 |= (s.contacts[l] != 0.0) ? (1u << l) : 0u;
+  }
+  masks[0] = (unsigned char)m0;
+  for (int k = 1; k < N; ++k) {
+    unsigned m = 0;
+    for (int l = 0; l < 4; ++l) {
+      L[l].gait_phase += g.gait_freq * h;
+      if (L[l].state == 1.0) {
+        if (L[l].gait_phase >= L[l].end_time) {
+          loop_gait_common_enter(g, l, L[l]);               // swing_enter
+          L[l].state = 0.0;
+        }
+      } else if (loop_gait_percent(L[l]) >= 1.0) {
+        L[l].state = 1.0;
+        loop_gait_common_enter(g, l, L[l]);                 // stance_enter
+      }
+      m |= (L[l].state != 0.0) ? (1u << l) : 0u;
+    }
+    masks[k] = (unsigned char)m;
+  }
+}
 // Raibert foothold offset of one leg in the yaw frame (BaseInterface.cpp:266-288 with the leg's own stance time (1 / f)(1 - w)):
 // vrel = R_z' v, vd = last tick's torso_lin_vel_d_rel, k = sqrt(|z| / 9.81); d (3) receives the clamped offset, d[2] = 0
 QMPC_HD void loop_gait_raibert_delta(const qmpc_gait_params& g, int leg, double k, const double* vrel, const double* vd, double* d) {

@@ -326,6 +326,15 @@ static inline qmpc_plan plan_instances(const qmpc_select& s, const qmpc_opts& o,
   return p.variant == 4 ? p : w;
 }
 
+// The plan of qmpc_solve_schedule* (a contact schedule over the horizon; qmpc_wform_sched.hip: qmpc_solve_w_sched_kernel<3|5|6>):
+// the wave wrench-form variant plan_instances picks for the size with the lane kernel off, under either policy -- the lane
+// kernel has no schedule form.  The kernel adds nothing to the layout (the schedule lives in registers), so LDS and workspace
+// are that plan's.  NONE where plan_instances refuses: not QuatMpc's problem with four points in the converged mode, or no
+// wrench-form kernel under the handle's knobs.
+static inline qmpc_plan plan_schedule(const qmpc_select& s, int batch) {
+  return plan_instances(s, qmpc_opts(), batch, true);
+}
+
 // The plan of qmpc_convex_solve_instances* (ConvexMpc's problem with per-instance parameters; qmpc_wform_cinst.hip:
 // qmpc_solve_cw_inst_kernel<3|5|6>).  NONE unless the handle is ConvexMpc in the converged mode with the wrench form on.
 // This is the wave form: the plan of every handle that did not opt in to the lane form (the overload below).

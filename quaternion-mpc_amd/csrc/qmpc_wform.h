@@ -34,6 +34,19 @@
 // body of one solve, the counterpart of qmpc_solve_body.inc.
 #pragma once
 
+// Per-knot stance sets (qmpc_solve_schedule*, qmpc_wform_sched.hip).  A unit that defines QMPC_WSCHED ahead
+// of its includes gets the converged mode's functions below with "is leg l in stance?" asked for the knot at hand, from the
+// schedule in the layout (qmpc_device.h: WSched); every other unit gets the expression it always had, so its code stays as it
+// is (a macro and not a template parameter: the units' namespaces differ, their functions' names must not).  The reference
+// mode's functions refuse to be instantiated with it.
+#ifdef QMPC_WSCHED
+#define QMPC_STANCE_AT(L, k, l, plain) ((L).sc.stance((k), (l)))
+#define QMPC_NO_WSCHED(NL) static_assert((NL) == 0, "the reference mode has no per-knot contact schedule")
+#else
+#define QMPC_STANCE_AT(L, k, l, plain) (plain)
+#define QMPC_NO_WSCHED(NL)
+#endif
+
 namespace qmpc {
 
 
@@ -102,6 +115,41 @@ __host__ __device__ inline Layout make_layout_w(int N, LayoutW* W, bool kd_globa
 // the costate zeta_k (6) of the trial rollout is parked in the spare slots of the knot's first two ROT records
 template <int NL = 4>
 __device__ __forceinline__ int zeta_slot(int k, int i) { return 21 * NL * k + 21 * (i / 3) + 18 + (i % 3); }
+
+#ifdef QMPC_WSCHED
+// setup_instance (qmpc_kernels.hip) for a solve with a contact schedule: the record's contacts[] is not read -- its slots take
+// the UNION of the schedule's stance sets (`any`, never empty: the caller has refused an empty knot), so that Bw0 keeps the
+// column of every leg that stands at some knot; the input reference model_setup leaves in L.uref is not read either
+// (WSched::uref_z).  A leg in the air at a knot has u = du = 0 there exactly, whatever its column.
+template <class MD>
+__device__ inline void setup_instance_sched(const DevParams& P, const Layout& L, double* sm, const void* in, int lane,
+                                            unsigned any, int* status) {
+  typedef typename MD::D D;
+  static_assert(MD::NX == 13 && MD::NL == 4, "the contact schedule: QuatMpc's problem with four contact points");
+  const double* rec = reinterpret_cast<const double*>(in);
+  double v = (lane < D::REC) ? rec[lane] : 0.0;
+  if (lane >= D::R_CON && lane < D::R_CON + MD::NL) v = ((any >> (lane - D::R_CON)) & 1u) ? 1.0 : 0.0;
+  const unsigned long long bad = __ballot(lane < D::REC && !isfinite(v));
+  double* raw = sm + L.tile;  // scratch
+  if (lane < D::REC) raw[lane] = v;
+  QSYNC();
+  *status = bad ? QMPC_NAN_INPUT : QMPC_OK;
+  if (*status != QMPC_OK) return;
+  model_setup<MD>(P, L, sm, raw, lane, __popc(any));
+}
+// cost_plain (qmpc_kernels.hip) with the input reference of the lane's knot
+template <class MD>
+__device__ inline double cost_sched_w(const DevParams& P, const Layout& L, double* sm, int lane) {
+  double J = 0.0;
+  if (lane <= P.N) {
+    double ur[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) ur[j] = (j % 3 == 2 && lane < P.N) ? L.sc.uref_z(lane, j / 3) : 0.0;
+    J = MD::knot_cost(P, sm + L.refp, ur, lane, sm + L.X + 13 * lane, (lane < P.N) ? sm + L.U + MD::D::NU * lane : nullptr);
+  }
+  return wave_sum(J);
+}
+#endif
 
 constexpr int S6I_(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
 __host__ __device__ constexpr int S6I(int i, int j) { return i <= j ? S6I_(i, j) : S6I_(j, i); }      // also at run time
@@ -186,7 +234,7 @@ __device__ inline void prepass_w(const DevParams& P, const Layout& L, double* sm
     double acc[kGK];
 #pragma unroll
     for (int i = 0; i < kGK; ++i) acc[i] = 0.0;
-    const bool stance = live && cst[D::C_CON + l] != 0.0;
+    const bool stance = live && QMPC_STANCE_AT(L, k, l, cst[D::C_CON + l] != 0.0);
     if (live && !stance) {
       out[0] = 1; out[1] = 0; out[2] = 0; out[3] = 0; out[4] = 1; out[5] = 0; out[6] = 0; out[7] = 0; out[8] = 1;
       out[9] = 0; out[10] = 0; out[11] = 0; out[12] = 1; out[13] = 1; out[14] = 1; out[15] = 0; out[16] = 0; out[17] = 0;
@@ -253,7 +301,12 @@ __device__ inline void prepass_w(const DevParams& P, const Layout& L, double* sm
       for (int a = 0; a < 3; ++a) { T[3 * a] = q1[a]; T[3 * a + 1] = q2[a]; T[3 * a + 2] = q3[a]; }
       const double Rl[3] = {R0, R1, R2};
       const double* u = sm + L.U + D::NU * k + 3 * l;
+#ifdef QMPC_WSCHED
+      const double urk[3] = {0.0, 0.0, L.sc.uref_z(k, l)};      // u_ref of knot k
+      const double* ur = urk;
+#else
       const double* ur = sm + L.uref + 3 * l;
+#endif
       const double ru[3] = {R0 * (u[0] - ur[0]), R1 * (u[1] - ur[1]), R2 * (u[2] - ur[2])};
       double gq[3];
       double d00, d01, d02, d11, d12, d22;
@@ -1282,6 +1335,7 @@ template <int MD = WM_QUAT, int NL = 4>
 __device__ inline double expected_decrease_w(const DevParams& P, const Layout& L, double* sm, const double* KD,
                                              const double* ROT, const double* y0, int lane) {
   typedef Dim<NL> D;
+  QMPC_NO_WSCHED(NL);
   constexpr int LSH = (NL == 8) ? 3 : 2;
   const int N = P.N;
   const double* cst = sm + L.cst;
@@ -1340,7 +1394,7 @@ __device__ inline int recover_inputs_w(const DevParams& P, const Layout& L, doub
   for (int q = lane; q < NL * N; q += kWave) {
     const int k = q >> LSH, l = q & (NL - 1);
     double du[3] = {0.0, 0.0, 0.0};
-    if (cst[D::C_CON + l] != 0.0) {
+    if (QMPC_STANCE_AT(L, k, l, cst[D::C_CON + l] != 0.0)) {
       const double* rec = ROT + D::ROT * k + 21 * l;
       double T[9], z[6];
 #pragma unroll
@@ -1410,7 +1464,7 @@ __device__ inline int recover_directions_w(const DevParams& P, const Layout& L, 
   int j = 0;
   for (int q = lane; q < NL * N; q += kWave, ++j) {
     const int k = q >> LSH, l = q & (NL - 1);
-    const bool stance = cst[D::C_CON + l] != 0.0;
+    const bool stance = QMPC_STANCE_AT(L, k, l, cst[D::C_CON + l] != 0.0);
     const double* rec = ROT + D::ROT * k + 21 * l;
     const int i0 = D::NC * k + 6 * l;
     double T[9], z[6], sv[6], lv[6], kap[6], rc[6];
@@ -1513,7 +1567,7 @@ __device__ inline void apply_w(const DevParams& P, const Layout& L, double* sl, 
   int j = 0;
   for (int q = lane; q < NL * N; q += kWave, ++j) {
     const int k = q >> LSH, l = q & (NL - 1);
-    if (!(conmask & (1u << l))) continue;
+    if (!QMPC_STANCE_AT(L, k, l, conmask & (1u << l))) continue;
     const int i0 = D::NC * k + 6 * l;
     double s0[6], l0[6], ds[6], dl[6], rc[6];
 #pragma unroll
@@ -1570,6 +1624,7 @@ __device__ inline double rollout_trials_w(const DevParams& P, const Layout& L, c
                                           const double* KD, double* ZG, double alpha_g, int lane) {
   typedef typename std::conditional<MD == WM_CONVEX, ConvexModel, typename std::conditional<NL == 8, Quat8Model, QuatModel>::type>::type TM;
   typedef Dim<NL> D;
+  QMPC_NO_WSCHED(NL);
   const int N = P.N;
   const double* cst = sm + L.cst;
   double gb[3], wd0[3];
@@ -1647,6 +1702,7 @@ __device__ inline void trial_inputs_w(const DevParams& P, const Layout& L, const
                                       const double* ROT, const double* ZG, const double* Rl, double alpha, double rho,
                                       int lane, double Ju[4], double mer[4], double vi[4]) {
   typedef Dim<NL> D;
+  QMPC_NO_WSCHED(NL);
   constexpr int LSH = (NL == 8) ? 3 : 2;
   const int N = P.N;
   const double* cst = sm + L.cst;
@@ -1731,6 +1787,7 @@ template <int MD = WM_QUAT, int NL = 4>
 __device__ inline double stationarity_w(const DevParams& P, const Layout& L, double* sm, const double* sl, double* my,
                                         const double* Rl, double rho, unsigned conmask, int lane) {
   typedef Dim<NL> D;
+  QMPC_NO_WSCHED(NL);
   constexpr int LSH = (NL == 8) ? 3 : 2;
   const int N = P.N;
   const double* cst = sm + L.cst;

@@ -7,6 +7,8 @@
 //   instance);  double* gws;  int wslot (the slice: the instance index b, or the workgroup's);  long long* prof_out;  int b, lane;  double sm[] (the dynamic LDS block, make_layout_w);
 //   int warm_t (> 0: sm[L.U] holds a previous solution to start from);  const double* resume (the state record of a
 //   straggler hand-off to continue from, or null)
+// In a unit compiled with QMPC_WSCHED (qmpc_wform.h; qmpc_wform_sched.hip): also  WSched wsched  -- the instance's contact schedule,
+// every knot's stance set non-empty.  A cold solve of QuatMpc's problem only: no warm start, no hand-off record.
 // `return` leaves the including function (early exits on rejected inputs).
 #ifndef QMPC_WNL
 #define QMPC_WNL 4      // contact points: 4 (QuatMpc's problem on Go1) unless the including kernel says 8 (the biped of config 5)
@@ -26,7 +28,14 @@
   constexpr bool SLG = WVAR == 6;                   // ... and the slack / multiplier / residual arrays (round 5: long horizons)
   constexpr bool LEAN = WNL == 8 || SLG;            // no direction arrays, weakly-active flags in a register (qmpc_wform.h)
   LayoutW LW;
+#ifdef QMPC_WSCHED
+  static_assert(WNL == 4 && WMT == WM_QUAT, "the contact schedule: QuatMpc's problem with four contact points");
+  Layout Lsc_ = make_layout_w<WNL>(N, &LW, KDG, SLG, WMT == WM_CONVEX);
+  Lsc_.sc = wsched;
+  const Layout L = Lsc_;
+#else
   const Layout L = make_layout_w<WNL>(N, &LW, KDG, SLG, WMT == WM_CONVEX);
+#endif
   double* wsb = KDG ? gws + (size_t)wslot * wform_slice<WNL>(N, SLG) : sm;
   double* KD = wsb + L.KD;
   double* ROT = wsb + L.ROT;
@@ -36,7 +45,15 @@
   int status = QMPC_OK;
   Prof<PROF> prof;
   prof.start();
+#ifdef QMPC_WSCHED
+  {
+    unsigned any_ = 0;      // every leg that stands at some knot
+    for (int k = 0; k < N; ++k) any_ |= L.sc.mask(k);
+    setup_instance_sched<WMD>(P, L, sm, in, lane, any_, &status);
+  }
+#else
   setup_instance<WMD>(P, L, sm, in, lane, &status);
+#endif
   if (status != QMPC_OK) {
     if (lane < NU) forces[NU * (size_t)b + lane] = 0.0;
     if (lane == 0 && info) {
@@ -68,7 +85,11 @@
       }
     }
   } else {
+#ifdef QMPC_WSCHED
+    for (int i = lane; i < N * NU; i += kWave) sm[L.U + i] = ((i % NU) % 3 == 2) ? L.sc.uref_z(i / NU, (i % NU) / 3) : 0.0;      // u_ref of the knot
+#else
     for (int i = lane; i < N * NU; i += kWave) sm[L.U + i] = sm[L.uref + (i % NU)];
+#endif
   }
   QSYNC();
   rollout_open<WMD, false>(P, L, sm, lane);
@@ -111,14 +132,20 @@
     sl[L.RC + i] = c0 + s0;
     sl[L.LAM + i] = lam0;
     if (!LEAN) sl[L.DS + i] = 0.0;
-    if (conmask & (1u << ((i % NC) / 6))) {
+    if (QMPC_STANCE_AT(L, i / NC, (i % NC) / 6, conmask & (1u << ((i % NC) / 6)))) {
       sl_part += s0 * lam0;
       rc_part = fmax(rc_part, fabs(c0 + s0));
     }
   }
   QSYNC();
   prof.tick(PH_SETUP);
+#ifdef QMPC_WSCHED
+  int rows_ = 0;      // the cone rows that exist: six per (knot, stance leg)
+  for (int k = 0; k < N; ++k) rows_ += __popc(L.sc.mask(k));
+  const double inv_rows = 1.0 / (double)(6 * rows_);
+#else
   const double inv_rows = 1.0 / (double)(6 * N * __popc(conmask));
+#endif
   const int it_start = resume ? (int)resume[4] + 1 : 1;      // a handed-over instance continues where the lane kernel stopped
   int it = 0, iters = it_start - 1;
   double mu = 0.0, resid = 0.0, last_step = resume ? resume[3] : 1e300, last_ap = resume ? resume[1] : 0.0,
@@ -185,11 +212,15 @@
       }
     }
   if (info) {
+#ifdef QMPC_WSCHED
+    const double J = cost_sched_w<WMD>(P, L, sm, lane);
+#else
     const double J = cost_plain<WMD>(P, L, sm, lane);
+#endif
     double viol = 0.0;
     for (int i = lane; i < N * NC; i += kWave) {
       const int l = (i % NC) / 6;
-      if (conmask & (1u << l)) viol = fmax(viol, fmax(cone_value<WD>(P, L, sm, i), 0.0));
+      if (QMPC_STANCE_AT(L, i / NC, l, conmask & (1u << l))) viol = fmax(viol, fmax(cone_value<WD>(P, L, sm, i), 0.0));
     }
     viol = wave_max(viol);
     if (lane == 0) {

@@ -298,6 +298,10 @@ void qh_gait_reset(const qmpc_gait_params* gait, qmpc_loop_state* s) {
     s->contacts[l] = s->leg[l].state;
   }
 }
+// ... the contact schedule the record's gait state implies over N knots h apart (what qmpc_gait_predict does with a record) ...
+void qh_gait_predict(const qmpc_gait_params* gait, const qmpc_loop_state* s, double h, int N, unsigned char* masks) {
+  qmpc_loop::loop_gait_predict(*gait, *s, h, N, masks);
+}
 // ... and `ticks` updates of the four legs of a state record in place, on scripted feet: cur / tgt [ticks][12] (foot positions
 // and Raibert targets), flags [ticks][4]; legs_out [ticks][4] receives the legs after each tick (or null), contacts [ticks][4]
 void qh_gait_run(const qmpc_gait_params* gait, qmpc_loop_state* s, double dt, int ticks, const double* cur, const double* tgt,

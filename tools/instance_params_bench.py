@@ -11,7 +11,11 @@ instance) and, under AUTO, the stance sort and the hand-off.
     (qmpc_set_convex_lane_records), so the AUTO column is qmpc_lane_cinst_kernel from the switch-over on and the WAVE column the
     wave form, as for QuatMpc.
 --plain-lib FILE: another build of the library (e.g. the parent revision's) whose plain solve joins the alternation as
-    "base_plain", with a handle of its own on the same buffers: the per-instance call over THAT plain solve, in the same job."""
+    "base_plain", with a handle of its own on the same buffers: the per-instance call over THAT plain solve, in the same job.
+--schedule: the solve with a contact schedule over the horizon (qmpc_solve_schedule_device) beside qmpc_solve_instances_device in
+    the same alternation, uniform records, sizes 10:1024,10:8192,20:4096 unless --sizes says otherwise: with constant schedules
+    (the same problems as the per-instance call, the same bytes: the price of the per-knot predicate) and with the "trot -> four
+    -> other" family of schedule_families (other problems: their time and mean iteration count)."""
 import argparse
 import ctypes as C
 import importlib.util
@@ -60,6 +64,61 @@ class BasePlain:
         self.lib.qmpc_destroy(self.h)
 
 
+SCHEDULE_SIZES = "10:1024,10:8192,20:4096"
+
+
+def schedule_main(a, pkg, lib, torch):
+    rows = []
+    for item in (a.sizes if a.sizes != DEFAULT_SIZES else SCHEDULE_SIZES).split(","):
+        N, B = (int(x) for x in item.split(":"))
+        p = pkg.default_params(N, pkg.MODE_CONVERGED, lib)
+        rec = pkg.random_go1_trot_states(B, config_id=2)
+        fam = pkg.schedule_families(rec, N)
+        s = pkg.Solver(p, B, device=0, lib=lib)
+        s.prepare(B)
+        s.prepare_instances()
+        d_in = torch.from_numpy(rec.view(np.uint8).copy()).cuda()
+        d_ip = torch.from_numpy(pkg.instance_params(p, B).view(np.uint8).copy()).cuda()
+        d_sc = {k: torch.from_numpy(fam[k].copy()).cuda() for k in ("constant", "trot_four_other")}
+        d_f = torch.zeros((B, 12), dtype=torch.float64, device="cuda")
+        d_info = {k: torch.zeros(B * pkg.INFO_DTYPE.itemsize, dtype=torch.uint8, device="cuda") for k in ("instances", "constant", "trot_four_other")}
+        stream = torch.cuda.Stream()
+        st = stream.cuda_stream
+        torch.cuda.synchronize()
+        calls = {"instances": lambda: s.solve_instances_device(B, d_in.data_ptr(), d_ip.data_ptr(), d_f.data_ptr(), d_info["instances"].data_ptr(),
+                                                               stream=st)}
+        for k in d_sc:
+            calls[k] = (lambda k=k: s.solve_schedule_device(B, d_in.data_ptr(), d_ip.data_ptr(), d_sc[k].data_ptr(), d_f.data_ptr(),
+                                                            d_info[k].data_ptr(), stream=st))
+        times = {k: [] for k in calls}
+        for r in range(a.warmup + a.reps):
+            for k, fn in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                fn()
+                e1.record(stream)
+                e1.synchronize()
+                if r >= a.warmup:
+                    times[k].append(e0.elapsed_time(e1))
+        row = {"N": N, "B": B, "kernel": s.kernel_for_schedule(B), "instances_kernel": s.kernel_for_instances(B)}
+        s.close()
+        line = f"N={N:2d} B={B:6d} [{row['kernel']}]"
+        for k, v in times.items():
+            info = np.frombuffer(d_info[k].cpu().numpy().tobytes(), dtype=pkg.INFO_DTYPE)
+            ms = float(np.median(v))
+            row[f"{k}_ms"], row[f"{k}_Msolves_s"] = ms, B / ms / 1e3
+            row[f"{k}_spread"] = float((np.percentile(v, 75) - np.percentile(v, 25)) / ms)
+            row[f"{k}_mean_iterations"], row[f"{k}_ok"] = float(info["iterations"].mean()), float((info["status"] == 0).mean())
+            line += f"  {k} {ms:7.3f} ms {B / ms / 1e3:6.3f} M/s iters {row[f'{k}_mean_iterations']:.2f} ok {row[f'{k}_ok']:.4f}"
+        row["constant_over_instances"] = row["constant_ms"] / row["instances_ms"]
+        line += f"  constant/instances {row['constant_over_instances']:.3f}  mixed/instances {row['trot_four_other_ms'] / row['instances_ms']:.3f}"
+        rows.append(row)
+        print(line, flush=True)
+    if a.json:
+        Path(a.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.json).write_text(json.dumps(rows, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -69,11 +128,14 @@ def main():
     ap.add_argument("--policy", default="both", choices=("wave", "auto", "both"))
     ap.add_argument("--model", default="quat", choices=("quat", "convex"))
     ap.add_argument("--plain-lib", default=None)
+    ap.add_argument("--schedule", action="store_true")
     a = ap.parse_args()
     import torch
 
     pkg = load_pkg()
     lib = pkg.load_library()
+    if a.schedule:
+        return schedule_main(a, pkg, lib, torch)
     rows = []
     for item in a.sizes.split(","):
         N, B = (int(x) for x in item.split(":"))
