@@ -535,6 +535,11 @@ INFO_DTYPE = np.dtype(
 assert INFO_DTYPE.itemsize == 40
 
 
+# how many arguments each closed-loop call with records takes after trace_contacts (include/qmpc.h), of: op, outcomes, push,
+# pushes_per_robot, ground, tally, act, line, sense, seen, gait, geom, motor, motor_tally
+_LOOP_RECORD_ARGS = {"instances": 0, "outcomes": 2, "pushes": 4, "ground": 6, "actuation": 8, "sensing": 10, "gaits": 11, "motors": 14}
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -611,73 +616,39 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.qmpc_prepare_instances.argtypes = [vp]
     lib.qmpc_plant_params_from.argtypes = [C.POINTER(Params), vp]
     lib.qmpc_plant_params_from.restype = None
-    lib.qmpc_loop_run_instances.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp]
-    lib.qmpc_loop_run_instances.restype = i32
-    lib.qmpc_loop_run_instances_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, vp]
-    lib.qmpc_loop_run_instances_device.restype = i32
     lib.qmpc_prepare_instances.restype = i32
+    # the closed-loop calls with per-robot records: every entry point takes the arguments of the one before it, then its own
+    # (_LOOP_RECORD_ARGS of them in all), the device-buffer form a stream after them
+    head = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp]
+    tail = [C.POINTER(OutcomeParams), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LegGeometry), vp, vp]
+    for name, n in _LOOP_RECORD_ARGS.items():
+        for fn, args in ((getattr(lib, "qmpc_loop_run_" + name), head + tail[:n]),
+                         (getattr(lib, "qmpc_loop_run_" + name + "_device"), head + tail[:n] + [vp])):
+            fn.argtypes, fn.restype = args, i32
     lib.qmpc_default_outcome_params.argtypes = [C.POINTER(OutcomeParams)]
     lib.qmpc_default_outcome_params.restype = None
     lib.qmpc_loop_outcome_init.argtypes = [vp, i32]
     lib.qmpc_loop_outcome_init.restype = None
-    lib.qmpc_loop_run_outcomes.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp]
-    lib.qmpc_loop_run_outcomes.restype = i32
-    lib.qmpc_loop_run_outcomes_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp]
-    lib.qmpc_loop_run_outcomes_device.restype = i32
-    lib.qmpc_loop_run_pushes.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32]
-    lib.qmpc_loop_run_pushes.restype = i32
-    lib.qmpc_loop_run_pushes_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
-                                                i32, vp]
-    lib.qmpc_loop_run_pushes_device.restype = i32
     lib.qmpc_ground_params_init.argtypes = [vp, i32]
     lib.qmpc_ground_params_init.restype = None
     lib.qmpc_ground_tally_init.argtypes = [vp, i32]
     lib.qmpc_ground_tally_init.restype = None
-    lib.qmpc_loop_run_ground.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp]
-    lib.qmpc_loop_run_ground.restype = i32
-    lib.qmpc_loop_run_ground_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
-                                                i32, vp, vp, vp]
-    lib.qmpc_loop_run_ground_device.restype = i32
     lib.qmpc_actuation_params_init.argtypes = [vp, i32]
     lib.qmpc_actuation_params_init.restype = None
     lib.qmpc_actuation_line_init.argtypes = [vp, i32, vp]
     lib.qmpc_actuation_line_init.restype = None
-    lib.qmpc_loop_run_actuation.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp,
-                                            vp, vp]
-    lib.qmpc_loop_run_actuation.restype = i32
-    lib.qmpc_loop_run_actuation_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
-                                                   i32, vp, vp, vp, vp, vp]
-    lib.qmpc_loop_run_actuation_device.restype = i32
     lib.qmpc_sense_params_init.argtypes = [vp, i32]
     lib.qmpc_sense_params_init.restype = None
     lib.qmpc_sense_seen_init.argtypes = [vp, i32]
     lib.qmpc_sense_seen_init.restype = None
-    lib.qmpc_loop_run_sensing.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp,
-                                          vp, vp, vp, vp]
-    lib.qmpc_loop_run_sensing.restype = i32
-    lib.qmpc_loop_run_sensing_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
-                                                 i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.qmpc_loop_run_sensing_device.restype = i32
     lib.qmpc_default_gait_params.argtypes = [C.POINTER(LoopParams), vp]
     lib.qmpc_default_gait_params.restype = None
     lib.qmpc_loop_state_set_gait.argtypes = [vp, vp]
     lib.qmpc_loop_state_set_gait.restype = None
-    lib.qmpc_loop_run_gaits.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp,
-                                        vp, vp, vp, vp, vp]
-    lib.qmpc_loop_run_gaits.restype = i32
-    lib.qmpc_loop_run_gaits_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
-                                               i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.qmpc_loop_run_gaits_device.restype = i32
     lib.qmpc_default_motor_params.argtypes = [vp]
     lib.qmpc_default_motor_params.restype = None
     lib.qmpc_motor_tally_init.argtypes = [vp]
     lib.qmpc_motor_tally_init.restype = None
-    lib.qmpc_loop_run_motors.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp, i32, vp, vp,
-                                         vp, vp, vp, vp, vp, C.POINTER(LegGeometry), vp, vp]
-    lib.qmpc_loop_run_motors.restype = i32
-    lib.qmpc_loop_run_motors_device.argtypes = [vp, C.POINTER(LoopParams), i32, vp, i32, vp, vp, vp, vp, C.POINTER(OutcomeParams), vp, vp,
-                                                i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LegGeometry), vp, vp, vp]
-    lib.qmpc_loop_run_motors_device.restype = i32
     lib.qmpc_set_instances_policy.argtypes = [vp, i32]
     lib.qmpc_set_instances_policy.restype = i32
     lib.qmpc_set_loop_warm_records.argtypes = [vp, i32]
@@ -1270,398 +1241,25 @@ class Solver:
         if rc != OK:
             raise QmpcError(rc, "qmpc_loop_run_instances_device")
 
-    def loop_run_outcomes(self, states: np.ndarray, ticks: int, lp: LoopParams | None = None, ctrl: np.ndarray | None = None,
-                          plant: np.ndarray | None = None, op: OutcomeParams | None = None, outcomes: np.ndarray | None = None,
-                          trace: bool = False):
-        """qmpc_loop_run_outcomes: loop_run_instances that also accumulates one outcome record per robot (LOOP_OUTCOME_DTYPE) on
-        the device.  outcomes: the records to go on accumulating into (None: empty ones); op: default_outcome_params().  Returns
-        (states, outcomes[, forces, contacts]); the arguments are not modified."""
+    def _loop_run_records(self, name, states, ticks, lp, op, trace, ctrl=None, plant=None, outcomes=None, push=None, ground=None,
+                          tallies=None, act=None, lines=None, sense=None, seen=None, want_seen=True, gait=None, geom=None,
+                          motor=None, mtallies=None, want_motor_tallies=True):
+        """The host-buffer call qmpc_loop_run_<name> of loop_run_outcomes .. loop_run_motors: the records coerced and checked for
+        shape (B,), the windows as [B][per_robot], the accumulators the entry point takes -- the caller's, copied, or fresh ones
+        -- and the traces.  Returns states, (outcomes, tallies, lines, seen, motor_tallies) with None for what the entry point
+        does not take, and (forces, contacts) or ()."""
         lp = lp or default_loop_params(self.lib)
         op = op or default_outcome_params(self.lib)
         st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
         B = st.shape[0]
-        if ctrl is not None:
-            ctrl = np.ascontiguousarray(ctrl, dtype=INSTANCE_PARAMS_DTYPE)
-            if ctrl.shape != (B,):
-                raise ValueError(f"ctrl: shape {ctrl.shape}, expected ({B},)")
-        if plant is not None:
-            plant = np.ascontiguousarray(plant, dtype=PLANT_PARAMS_DTYPE)
-            if plant.shape != (B,):
-                raise ValueError(f"plant: shape {plant.shape}, expected ({B},)")
-        if outcomes is None:
-            oc = loop_outcomes(B, self.lib)
-        else:
-            oc = np.ascontiguousarray(outcomes, dtype=LOOP_OUTCOME_DTYPE).copy()
-            if oc.shape != (B,):
-                raise ValueError(f"outcomes: shape {oc.shape}, expected ({B},)")
-        tf = np.zeros((ticks, B, 12)) if trace else None
-        tc = np.zeros((ticks, B, 4)) if trace else None
-        rc = self.lib.qmpc_loop_run_outcomes(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
-                                             C.byref(op), _ptr(oc))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_outcomes")
-        return (st, oc, tf, tc) if trace else (st, oc)
+        n = _LOOP_RECORD_ARGS[name]
 
-    def loop_run_outcomes_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, lp: LoopParams | None = None,
-                                 op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0,
-                                 d_trace_contacts: int = 0, stream: int = 0):
-        """qmpc_loop_run_outcomes_device: device pointers (ints; 0 = NULL), stream-ordered."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-        rc = self.lib.qmpc_loop_run_outcomes_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
-                                                    p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(stream))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_outcomes_device")
-
-    def loop_run_pushes(self, states: np.ndarray, ticks: int, push: np.ndarray | None, lp: LoopParams | None = None,
-                        ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
-                        outcomes: np.ndarray | None = None, trace: bool = False):
-        """qmpc_loop_run_pushes: loop_run_outcomes whose plant integrates under timed push windows per robot.  push:
-        [B][per_robot] (or [B]: one window each) PUSH_PARAMS_DTYPE records, push_params(); None: exactly loop_run_outcomes.
-        Returns what loop_run_outcomes returns; the arguments are not modified."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
-        B = st.shape[0]
-        if ctrl is not None:
-            ctrl = np.ascontiguousarray(ctrl, dtype=INSTANCE_PARAMS_DTYPE)
-            if ctrl.shape != (B,):
-                raise ValueError(f"ctrl: shape {ctrl.shape}, expected ({B},)")
-        if plant is not None:
-            plant = np.ascontiguousarray(plant, dtype=PLANT_PARAMS_DTYPE)
-            if plant.shape != (B,):
-                raise ValueError(f"plant: shape {plant.shape}, expected ({B},)")
-        per_robot = 0
-        if push is not None:
-            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
-            if push.ndim == 1:
-                push = push.reshape(-1, 1)
-            if push.ndim != 2 or push.shape[0] != B:
-                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
-            per_robot = push.shape[1]      # 0 or above QMPC_MAX_PUSHES: the library refuses (QMPC_BAD_ARGUMENT)
-            if per_robot == 0:
-                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
-        if outcomes is None:
-            oc = loop_outcomes(B, self.lib)
-        else:
-            oc = np.ascontiguousarray(outcomes, dtype=LOOP_OUTCOME_DTYPE).copy()
-            if oc.shape != (B,):
-                raise ValueError(f"outcomes: shape {oc.shape}, expected ({B},)")
-        tf = np.zeros((ticks, B, 12)) if trace else None
-        tc = np.zeros((ticks, B, 4)) if trace else None
-        rc = self.lib.qmpc_loop_run_pushes(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
-                                           C.byref(op), _ptr(oc), _ptr(push), int(per_robot))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_pushes")
-        return (st, oc, tf, tc) if trace else (st, oc)
-
-    def loop_run_pushes_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_push: int, pushes_per_robot: int,
-                               lp: LoopParams | None = None, op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0,
-                               d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
-        """qmpc_loop_run_pushes_device: device pointers (ints; 0 = NULL), stream-ordered; d_push is read in place."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-        rc = self.lib.qmpc_loop_run_pushes_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
-                                                  p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
-                                                  int(pushes_per_robot), p(stream))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_pushes_device")
-
-    def loop_run_ground(self, states: np.ndarray, ticks: int, ground: np.ndarray | None, push: np.ndarray | None = None,
-                        lp: LoopParams | None = None, ctrl: np.ndarray | None = None, plant: np.ndarray | None = None,
-                        op: OutcomeParams | None = None, outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None,
-                        trace: bool = False):
-        """qmpc_loop_run_ground: loop_run_pushes whose plant integrates under the force the robot's TRUE ground delivers.
-        ground: [B] GROUND_PARAMS_DTYPE records, ground_params(); None: exactly loop_run_pushes (the tallies come back as given).
-        tallies: the GROUND_TALLY_DTYPE records to go on accumulating into (None: empty ones).  Returns (states, outcomes,
-        tallies[, forces, contacts]); the arguments are not modified."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
-        B = st.shape[0]
-        if ctrl is not None:
-            ctrl = np.ascontiguousarray(ctrl, dtype=INSTANCE_PARAMS_DTYPE)
-            if ctrl.shape != (B,):
-                raise ValueError(f"ctrl: shape {ctrl.shape}, expected ({B},)")
-        if plant is not None:
-            plant = np.ascontiguousarray(plant, dtype=PLANT_PARAMS_DTYPE)
-            if plant.shape != (B,):
-                raise ValueError(f"plant: shape {plant.shape}, expected ({B},)")
-        per_robot = 0
-        if push is not None:
-            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
-            if push.ndim == 1:
-                push = push.reshape(-1, 1)
-            if push.ndim != 2 or push.shape[0] != B:
-                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
-            per_robot = push.shape[1]
-            if per_robot == 0:
-                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
-        if ground is not None:
-            ground = np.ascontiguousarray(ground, dtype=GROUND_PARAMS_DTYPE)
-            if ground.shape != (B,):
-                raise ValueError(f"ground: shape {ground.shape}, expected ({B},)")
-        if outcomes is None:
-            oc = loop_outcomes(B, self.lib)
-        else:
-            oc = np.ascontiguousarray(outcomes, dtype=LOOP_OUTCOME_DTYPE).copy()
-            if oc.shape != (B,):
-                raise ValueError(f"outcomes: shape {oc.shape}, expected ({B},)")
-        if tallies is None:
-            ta = ground_tallies(B)
-        else:
-            ta = np.ascontiguousarray(tallies, dtype=GROUND_TALLY_DTYPE).copy()
-            if ta.shape != (B,):
-                raise ValueError(f"tallies: shape {ta.shape}, expected ({B},)")
-        tf = np.zeros((ticks, B, 12)) if trace else None
-        tc = np.zeros((ticks, B, 4)) if trace else None
-        rc = self.lib.qmpc_loop_run_ground(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
-                                           C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_ground")
-        return (st, oc, ta, tf, tc) if trace else (st, oc, ta)
-
-    def loop_run_ground_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_ground: int, d_tally: int = 0,
-                               d_push: int = 0, pushes_per_robot: int = 0, lp: LoopParams | None = None,
-                               op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0,
-                               d_trace_contacts: int = 0, stream: int = 0):
-        """qmpc_loop_run_ground_device: device pointers (ints; 0 = NULL), stream-ordered; d_ground and d_push are read in place,
-        d_tally (or 0) is read and written."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-        rc = self.lib.qmpc_loop_run_ground_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
-                                                  p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
-                                                  int(pushes_per_robot), p(d_ground), p(d_tally), p(stream))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_ground_device")
-
-    def loop_run_actuation(self, states: np.ndarray, ticks: int, act: np.ndarray | None, lines: np.ndarray | None = None,
-                           ground: np.ndarray | None = None, push: np.ndarray | None = None, lp: LoopParams | None = None,
-                           ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
-                           outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None, trace: bool = False):
-        """qmpc_loop_run_actuation: loop_run_ground whose plant receives each robot's command of delay_ticks ticks ago through
-        its first-order actuator.  act: [B] ACTUATION_PARAMS_DTYPE records, actuation_params(); None: exactly loop_run_ground
-        (the lines come back as given).  lines: the ACTUATION_LINE_DTYPE records to go on from (None: actuation_lines(B), zeros).
-        ground may be None (no clamp).  Returns (states, outcomes, tallies, lines[, forces, contacts]); the arguments are not
-        modified."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
-        B = st.shape[0]
-
-        def records(a, dtype, name, copy=False):
+        def records(a, dtype, what, copy=False):
             if a is None:
                 return None
             a = np.ascontiguousarray(a, dtype=dtype)
             if a.shape != (B,):
-                raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
-            return a.copy() if copy else a
-
-        ctrl = records(ctrl, INSTANCE_PARAMS_DTYPE, "ctrl")
-        plant = records(plant, PLANT_PARAMS_DTYPE, "plant")
-        ground = records(ground, GROUND_PARAMS_DTYPE, "ground")
-        act = records(act, ACTUATION_PARAMS_DTYPE, "act")
-        per_robot = 0
-        if push is not None:
-            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
-            if push.ndim == 1:
-                push = push.reshape(-1, 1)
-            if push.ndim != 2 or push.shape[0] != B:
-                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
-            per_robot = push.shape[1]
-            if per_robot == 0:
-                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
-        oc = loop_outcomes(B, self.lib) if outcomes is None else records(outcomes, LOOP_OUTCOME_DTYPE, "outcomes", copy=True)
-        ta = ground_tallies(B) if tallies is None else records(tallies, GROUND_TALLY_DTYPE, "tallies", copy=True)
-        li = actuation_lines(B) if lines is None else records(lines, ACTUATION_LINE_DTYPE, "lines", copy=True)
-        tf = np.zeros((ticks, B, 12)) if trace else None
-        tc = np.zeros((ticks, B, 4)) if trace else None
-        rc = self.lib.qmpc_loop_run_actuation(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
-                                              C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta), _ptr(act),
-                                              _ptr(li))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_actuation")
-        return (st, oc, ta, li, tf, tc) if trace else (st, oc, ta, li)
-
-    def loop_run_actuation_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_act: int, d_line: int,
-                                  d_ground: int = 0, d_tally: int = 0, d_push: int = 0, pushes_per_robot: int = 0,
-                                  lp: LoopParams | None = None, op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0,
-                                  d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
-        """qmpc_loop_run_actuation_device: device pointers (ints; 0 = NULL), stream-ordered; d_act, d_ground and d_push are read in
-        place, d_line and d_tally (or 0) are read and written."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-        rc = self.lib.qmpc_loop_run_actuation_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
-                                                     p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
-                                                     int(pushes_per_robot), p(d_ground), p(d_tally), p(d_act), p(d_line), p(stream))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_actuation_device")
-
-    def loop_run_sensing(self, states: np.ndarray, ticks: int, sense: np.ndarray | None, seen: np.ndarray | None = None,
-                         act: np.ndarray | None = None, lines: np.ndarray | None = None, ground: np.ndarray | None = None,
-                         push: np.ndarray | None = None, lp: LoopParams | None = None, ctrl: np.ndarray | None = None,
-                         plant: np.ndarray | None = None, op: OutcomeParams | None = None, outcomes: np.ndarray | None = None,
-                         tallies: np.ndarray | None = None, trace: bool = False, want_seen: bool = True):
-        """qmpc_loop_run_sensing: loop_run_actuation whose controller reads each robot's MEASURED state -- the true one plus the
-        record's bias and reproducible bounded noise -- while plant, outcome record, pushes, ground and actuation work on the
-        truth.  sense: [B] SENSE_PARAMS_DTYPE records, sense_params(); None: exactly loop_run_actuation (seen comes back as
-        given).  seen: the SENSE_SEEN_DTYPE records to go on from (None: sense_seen(B)); want_seen=False passes NULL.  act may be
-        None (every command acts in its own tick; the lines come back as given), ground may be None (no clamp).  Returns (states,
-        outcomes, tallies, lines, seen[, forces, contacts]); the arguments are not modified."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
-        B = st.shape[0]
-
-        def records(a, dtype, name, copy=False):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, dtype=dtype)
-            if a.shape != (B,):
-                raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
-            return a.copy() if copy else a
-
-        ctrl = records(ctrl, INSTANCE_PARAMS_DTYPE, "ctrl")
-        plant = records(plant, PLANT_PARAMS_DTYPE, "plant")
-        ground = records(ground, GROUND_PARAMS_DTYPE, "ground")
-        act = records(act, ACTUATION_PARAMS_DTYPE, "act")
-        sense = records(sense, SENSE_PARAMS_DTYPE, "sense")
-        per_robot = 0
-        if push is not None:
-            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
-            if push.ndim == 1:
-                push = push.reshape(-1, 1)
-            if push.ndim != 2 or push.shape[0] != B:
-                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
-            per_robot = push.shape[1]
-            if per_robot == 0:
-                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
-        oc = loop_outcomes(B, self.lib) if outcomes is None else records(outcomes, LOOP_OUTCOME_DTYPE, "outcomes", copy=True)
-        ta = ground_tallies(B) if tallies is None else records(tallies, GROUND_TALLY_DTYPE, "tallies", copy=True)
-        li = actuation_lines(B) if lines is None else records(lines, ACTUATION_LINE_DTYPE, "lines", copy=True)
-        sn = sense_seen(B) if seen is None else records(seen, SENSE_SEEN_DTYPE, "seen", copy=True)
-        tf = np.zeros((ticks, B, 12)) if trace else None
-        tc = np.zeros((ticks, B, 4)) if trace else None
-        rc = self.lib.qmpc_loop_run_sensing(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
-                                            C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta), _ptr(act),
-                                            _ptr(li), _ptr(sense), _ptr(sn) if want_seen else None)
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_sensing")
-        return (st, oc, ta, li, sn, tf, tc) if trace else (st, oc, ta, li, sn)
-
-    def loop_run_sensing_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_sense: int, d_seen: int = 0,
-                                d_act: int = 0, d_line: int = 0, d_ground: int = 0, d_tally: int = 0, d_push: int = 0,
-                                pushes_per_robot: int = 0, lp: LoopParams | None = None, op: OutcomeParams | None = None,
-                                d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
-        """qmpc_loop_run_sensing_device: device pointers (ints; 0 = NULL), stream-ordered; d_sense, d_act, d_ground and d_push are
-        read in place, d_seen (or 0), d_line and d_tally (or 0) are read and written."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-        rc = self.lib.qmpc_loop_run_sensing_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
-                                                   p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
-                                                   int(pushes_per_robot), p(d_ground), p(d_tally), p(d_act), p(d_line), p(d_sense),
-                                                   p(d_seen), p(stream))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_sensing_device")
-
-    def loop_run_gaits(self, states: np.ndarray, ticks: int, gait: np.ndarray | None, sense: np.ndarray | None = None,
-                       seen: np.ndarray | None = None, act: np.ndarray | None = None, lines: np.ndarray | None = None,
-                       ground: np.ndarray | None = None, push: np.ndarray | None = None, lp: LoopParams | None = None,
-                       ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
-                       outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None, trace: bool = False,
-                       want_seen: bool = True):
-        """qmpc_loop_run_gaits: loop_run_sensing in which every robot walks its own gait -- frequency, contact pattern, split and
-        starting phase per leg.  gait: [B] GAIT_PARAMS_DTYPE records, gait_params(); None: exactly loop_run_sensing.  Every other
-        record may be None as there.  The schedule lives in the states (leg, contacts, gait_counter): there is no record to carry
-        over calls, and a record changed between calls takes effect at each leg's next transition (phase0 at the next reset).
-        Returns (states, outcomes, tallies, lines, seen[, forces, contacts]); the arguments are not modified."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
-        B = st.shape[0]
-
-        def records(a, dtype, name, copy=False):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, dtype=dtype)
-            if a.shape != (B,):
-                raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
-            return a.copy() if copy else a
-
-        ctrl = records(ctrl, INSTANCE_PARAMS_DTYPE, "ctrl")
-        plant = records(plant, PLANT_PARAMS_DTYPE, "plant")
-        ground = records(ground, GROUND_PARAMS_DTYPE, "ground")
-        act = records(act, ACTUATION_PARAMS_DTYPE, "act")
-        sense = records(sense, SENSE_PARAMS_DTYPE, "sense")
-        gait = records(gait, GAIT_PARAMS_DTYPE, "gait")
-        per_robot = 0
-        if push is not None:
-            push = np.ascontiguousarray(push, dtype=PUSH_PARAMS_DTYPE)
-            if push.ndim == 1:
-                push = push.reshape(-1, 1)
-            if push.ndim != 2 or push.shape[0] != B:
-                raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
-            per_robot = push.shape[1]
-            if per_robot == 0:
-                push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
-        oc = loop_outcomes(B, self.lib) if outcomes is None else records(outcomes, LOOP_OUTCOME_DTYPE, "outcomes", copy=True)
-        ta = ground_tallies(B) if tallies is None else records(tallies, GROUND_TALLY_DTYPE, "tallies", copy=True)
-        li = actuation_lines(B) if lines is None else records(lines, ACTUATION_LINE_DTYPE, "lines", copy=True)
-        sn = sense_seen(B) if seen is None else records(seen, SENSE_SEEN_DTYPE, "seen", copy=True)
-        tf = np.zeros((ticks, B, 12)) if trace else None
-        tc = np.zeros((ticks, B, 4)) if trace else None
-        rc = self.lib.qmpc_loop_run_gaits(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
-                                          C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta), _ptr(act),
-                                          _ptr(li), _ptr(sense), _ptr(sn) if want_seen else None, _ptr(gait))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_gaits")
-        return (st, oc, ta, li, sn, tf, tc) if trace else (st, oc, ta, li, sn)
-
-    def loop_run_gaits_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_gait: int, d_sense: int = 0,
-                              d_seen: int = 0, d_act: int = 0, d_line: int = 0, d_ground: int = 0, d_tally: int = 0, d_push: int = 0,
-                              pushes_per_robot: int = 0, lp: LoopParams | None = None, op: OutcomeParams | None = None,
-                              d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
-        """qmpc_loop_run_gaits_device: device pointers (ints; 0 = NULL), stream-ordered; d_gait, d_sense, d_act, d_ground and
-        d_push are read in place, d_seen (or 0), d_line and d_tally (or 0) are read and written."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-        rc = self.lib.qmpc_loop_run_gaits_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
-                                                 p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
-                                                 int(pushes_per_robot), p(d_ground), p(d_tally), p(d_act), p(d_line), p(d_sense),
-                                                 p(d_seen), p(d_gait), p(stream))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_gaits_device")
-
-    def loop_run_motors(self, states: np.ndarray, ticks: int, motor: np.ndarray | None, mtallies: np.ndarray | None = None,
-                        geom: "LegGeometry | None" = None, gait: np.ndarray | None = None, sense: np.ndarray | None = None,
-                        seen: np.ndarray | None = None, act: np.ndarray | None = None, lines: np.ndarray | None = None,
-                        ground: np.ndarray | None = None, push: np.ndarray | None = None, lp: LoopParams | None = None,
-                        ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
-                        outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None, trace: bool = False,
-                        want_seen: bool = True, want_motor_tallies: bool = True):
-        """qmpc_loop_run_motors: loop_run_gaits in which the foot force a stance leg delivers respects the joint torque limits of
-        the robot's motors, and which records the torque every joint was asked for.  motor: [B] MOTOR_PARAMS_DTYPE records,
-        motor_params(); None: exactly loop_run_gaits.  mtallies: [B] MOTOR_TALLY_DTYPE, carried over calls (None: fresh ones
-        of module-level motor_tallies()); geom: one LegGeometry for all robots (None: the Go1's).  Every other record may be None
-        as there.  Returns (states, outcomes, tallies, lines, seen, motor_tallies[, forces, contacts]); the arguments are not
-        modified."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        st = np.ascontiguousarray(states, dtype=LOOP_STATE_DTYPE).copy()
-        B = st.shape[0]
-
-        def records(a, dtype, name, copy=False):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, dtype=dtype)
-            if a.shape != (B,):
-                raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
+                raise ValueError(f"{what}: shape {a.shape}, expected ({B},)")
             return a.copy() if copy else a
 
         ctrl = records(ctrl, INSTANCE_PARAMS_DTYPE, "ctrl")
@@ -1678,25 +1276,200 @@ class Solver:
                 push = push.reshape(-1, 1)
             if push.ndim != 2 or push.shape[0] != B:
                 raise ValueError(f"push: shape {push.shape}, expected ({B}, per_robot)")
-            per_robot = push.shape[1]
+            per_robot = push.shape[1]      # 0 or above QMPC_MAX_PUSHES: the library refuses (QMPC_BAD_ARGUMENT)
             if per_robot == 0:
                 push = np.zeros((B, 1), dtype=PUSH_PARAMS_DTYPE)      # a non-NULL pointer for the library to refuse
         oc = loop_outcomes(B, self.lib) if outcomes is None else records(outcomes, LOOP_OUTCOME_DTYPE, "outcomes", copy=True)
-        ta = ground_tallies(B) if tallies is None else records(tallies, GROUND_TALLY_DTYPE, "tallies", copy=True)
-        li = actuation_lines(B) if lines is None else records(lines, ACTUATION_LINE_DTYPE, "lines", copy=True)
-        sn = sense_seen(B) if seen is None else records(seen, SENSE_SEEN_DTYPE, "seen", copy=True)
-        mt = (motor_tallies(B, self.lib) if mtallies is None
-              else records(mtallies, MOTOR_TALLY_DTYPE, "mtallies", copy=True))
+        ta = li = sn = mt = None
+        if n >= 6:
+            ta = ground_tallies(B) if tallies is None else records(tallies, GROUND_TALLY_DTYPE, "tallies", copy=True)
+        if n >= 8:
+            li = actuation_lines(B) if lines is None else records(lines, ACTUATION_LINE_DTYPE, "lines", copy=True)
+        if n >= 10:
+            sn = sense_seen(B) if seen is None else records(seen, SENSE_SEEN_DTYPE, "seen", copy=True)
+        if n >= 14:
+            mt = motor_tallies(B, self.lib) if mtallies is None else records(mtallies, MOTOR_TALLY_DTYPE, "mtallies", copy=True)
         tf = np.zeros((ticks, B, 12)) if trace else None
         tc = np.zeros((ticks, B, 4)) if trace else None
-        rc = self.lib.qmpc_loop_run_motors(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc),
-                                           C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta), _ptr(act),
-                                           _ptr(li), _ptr(sense), _ptr(sn) if want_seen else None, _ptr(gait),
-                                           C.byref(geom) if geom is not None else None, _ptr(motor),
-                                           _ptr(mt) if want_motor_tallies else None)
+        tail = (C.byref(op), _ptr(oc), _ptr(push), int(per_robot), _ptr(ground), _ptr(ta), _ptr(act), _ptr(li), _ptr(sense),
+                _ptr(sn) if want_seen else None, _ptr(gait), C.byref(geom) if geom is not None else None, _ptr(motor),
+                _ptr(mt) if want_motor_tallies else None)
+        fn = "qmpc_loop_run_" + name
+        rc = getattr(self.lib, fn)(self._h, C.byref(lp), B, _ptr(st), int(ticks), _ptr(ctrl), _ptr(plant), _ptr(tf), _ptr(tc), *tail[:n])
         if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_motors")
-        return (st, oc, ta, li, sn, mt, tf, tc) if trace else (st, oc, ta, li, sn, mt)
+            raise QmpcError(rc, fn)
+        return st, (oc, ta, li, sn, mt), ((tf, tc) if trace else ())
+
+    def _loop_run_records_device(self, name, batch, d_states, ticks, lp, op, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, stream,
+                                 d_outcomes, d_push=0, pushes_per_robot=0, d_ground=0, d_tally=0, d_act=0, d_line=0, d_sense=0,
+                                 d_seen=0, d_gait=0, geom=None, d_motor=0, d_motor_tally=0):
+        """The device-buffer call qmpc_loop_run_<name>_device of loop_run_outcomes_device .. loop_run_motors_device: device
+        pointers (ints; 0 = NULL), of which the entry point gets those it takes."""
+        lp = lp or default_loop_params(self.lib)
+        op = op or default_outcome_params(self.lib)
+        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        tail = (C.byref(op), p(d_outcomes), p(d_push), int(pushes_per_robot), p(d_ground), p(d_tally), p(d_act), p(d_line), p(d_sense),
+                p(d_seen), p(d_gait), C.byref(geom) if geom is not None else None, p(d_motor), p(d_motor_tally))
+        fn = "qmpc_loop_run_" + name + "_device"
+        rc = getattr(self.lib, fn)(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant), p(d_trace_forces),
+                                   p(d_trace_contacts), *tail[:_LOOP_RECORD_ARGS[name]], p(stream))
+        if rc != OK:
+            raise QmpcError(rc, fn)
+
+    def loop_run_outcomes(self, states: np.ndarray, ticks: int, lp: LoopParams | None = None, ctrl: np.ndarray | None = None,
+                          plant: np.ndarray | None = None, op: OutcomeParams | None = None, outcomes: np.ndarray | None = None,
+                          trace: bool = False):
+        """qmpc_loop_run_outcomes: loop_run_instances that also accumulates one outcome record per robot (LOOP_OUTCOME_DTYPE) on
+        the device.  outcomes: the records to go on accumulating into (None: empty ones); op: default_outcome_params().  Returns
+        (states, outcomes[, forces, contacts]); the arguments are not modified."""
+        st, acc, tr = self._loop_run_records(
+            "outcomes", states, ticks, lp, op, trace, ctrl=ctrl, plant=plant, outcomes=outcomes)
+        return (st, *acc[:1], *tr)
+
+    def loop_run_outcomes_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, lp: LoopParams | None = None,
+                                 op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0,
+                                 d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_outcomes_device: device pointers (ints; 0 = NULL), stream-ordered."""
+        self._loop_run_records_device(
+            "outcomes", batch, d_states, ticks, lp, op, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, stream, d_outcomes)
+
+    def loop_run_pushes(self, states: np.ndarray, ticks: int, push: np.ndarray | None, lp: LoopParams | None = None,
+                        ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
+                        outcomes: np.ndarray | None = None, trace: bool = False):
+        """qmpc_loop_run_pushes: loop_run_outcomes whose plant integrates under timed push windows per robot.  push:
+        [B][per_robot] (or [B]: one window each) PUSH_PARAMS_DTYPE records, push_params(); None: exactly loop_run_outcomes.
+        Returns what loop_run_outcomes returns; the arguments are not modified."""
+        st, acc, tr = self._loop_run_records(
+            "pushes", states, ticks, lp, op, trace, ctrl=ctrl, plant=plant, outcomes=outcomes, push=push)
+        return (st, *acc[:1], *tr)
+
+    def loop_run_pushes_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_push: int, pushes_per_robot: int,
+                               lp: LoopParams | None = None, op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0,
+                               d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_pushes_device: device pointers (ints; 0 = NULL), stream-ordered; d_push is read in place."""
+        self._loop_run_records_device(
+            "pushes", batch, d_states, ticks, lp, op, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, stream, d_outcomes,
+            d_push=d_push, pushes_per_robot=pushes_per_robot)
+
+    def loop_run_ground(self, states: np.ndarray, ticks: int, ground: np.ndarray | None, push: np.ndarray | None = None,
+                        lp: LoopParams | None = None, ctrl: np.ndarray | None = None, plant: np.ndarray | None = None,
+                        op: OutcomeParams | None = None, outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None,
+                        trace: bool = False):
+        """qmpc_loop_run_ground: loop_run_pushes whose plant integrates under the force the robot's TRUE ground delivers.
+        ground: [B] GROUND_PARAMS_DTYPE records, ground_params(); None: exactly loop_run_pushes (the tallies come back as given).
+        tallies: the GROUND_TALLY_DTYPE records to go on accumulating into (None: empty ones).  Returns (states, outcomes,
+        tallies[, forces, contacts]); the arguments are not modified."""
+        st, acc, tr = self._loop_run_records(
+            "ground", states, ticks, lp, op, trace, ctrl=ctrl, plant=plant, outcomes=outcomes, push=push, ground=ground,
+            tallies=tallies)
+        return (st, *acc[:2], *tr)
+
+    def loop_run_ground_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_ground: int, d_tally: int = 0,
+                               d_push: int = 0, pushes_per_robot: int = 0, lp: LoopParams | None = None,
+                               op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0,
+                               d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_ground_device: device pointers (ints; 0 = NULL), stream-ordered; d_ground and d_push are read in place,
+        d_tally (or 0) is read and written."""
+        self._loop_run_records_device(
+            "ground", batch, d_states, ticks, lp, op, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, stream, d_outcomes,
+            d_push=d_push, pushes_per_robot=pushes_per_robot, d_ground=d_ground, d_tally=d_tally)
+
+    def loop_run_actuation(self, states: np.ndarray, ticks: int, act: np.ndarray | None, lines: np.ndarray | None = None,
+                           ground: np.ndarray | None = None, push: np.ndarray | None = None, lp: LoopParams | None = None,
+                           ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
+                           outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None, trace: bool = False):
+        """qmpc_loop_run_actuation: loop_run_ground whose plant receives each robot's command of delay_ticks ticks ago through
+        its first-order actuator.  act: [B] ACTUATION_PARAMS_DTYPE records, actuation_params(); None: exactly loop_run_ground
+        (the lines come back as given).  lines: the ACTUATION_LINE_DTYPE records to go on from (None: actuation_lines(B), zeros).
+        ground may be None (no clamp).  Returns (states, outcomes, tallies, lines[, forces, contacts]); the arguments are not
+        modified."""
+        st, acc, tr = self._loop_run_records(
+            "actuation", states, ticks, lp, op, trace, ctrl=ctrl, plant=plant, outcomes=outcomes, push=push, ground=ground,
+            tallies=tallies, act=act, lines=lines)
+        return (st, *acc[:3], *tr)
+
+    def loop_run_actuation_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_act: int, d_line: int,
+                                  d_ground: int = 0, d_tally: int = 0, d_push: int = 0, pushes_per_robot: int = 0,
+                                  lp: LoopParams | None = None, op: OutcomeParams | None = None, d_ctrl: int = 0, d_plant: int = 0,
+                                  d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_actuation_device: device pointers (ints; 0 = NULL), stream-ordered; d_act, d_ground and d_push are read in
+        place, d_line and d_tally (or 0) are read and written."""
+        self._loop_run_records_device(
+            "actuation", batch, d_states, ticks, lp, op, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, stream, d_outcomes,
+            d_push=d_push, pushes_per_robot=pushes_per_robot, d_ground=d_ground, d_tally=d_tally, d_act=d_act, d_line=d_line)
+
+    def loop_run_sensing(self, states: np.ndarray, ticks: int, sense: np.ndarray | None, seen: np.ndarray | None = None,
+                         act: np.ndarray | None = None, lines: np.ndarray | None = None, ground: np.ndarray | None = None,
+                         push: np.ndarray | None = None, lp: LoopParams | None = None, ctrl: np.ndarray | None = None,
+                         plant: np.ndarray | None = None, op: OutcomeParams | None = None, outcomes: np.ndarray | None = None,
+                         tallies: np.ndarray | None = None, trace: bool = False, want_seen: bool = True):
+        """qmpc_loop_run_sensing: loop_run_actuation whose controller reads each robot's MEASURED state -- the true one plus the
+        record's bias and reproducible bounded noise -- while plant, outcome record, pushes, ground and actuation work on the
+        truth.  sense: [B] SENSE_PARAMS_DTYPE records, sense_params(); None: exactly loop_run_actuation (seen comes back as
+        given).  seen: the SENSE_SEEN_DTYPE records to go on from (None: sense_seen(B)); want_seen=False passes NULL.  act may be
+        None (every command acts in its own tick; the lines come back as given), ground may be None (no clamp).  Returns (states,
+        outcomes, tallies, lines, seen[, forces, contacts]); the arguments are not modified."""
+        st, acc, tr = self._loop_run_records(
+            "sensing", states, ticks, lp, op, trace, ctrl=ctrl, plant=plant, outcomes=outcomes, push=push, ground=ground,
+            tallies=tallies, act=act, lines=lines, sense=sense, seen=seen, want_seen=want_seen)
+        return (st, *acc[:4], *tr)
+
+    def loop_run_sensing_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_sense: int, d_seen: int = 0,
+                                d_act: int = 0, d_line: int = 0, d_ground: int = 0, d_tally: int = 0, d_push: int = 0,
+                                pushes_per_robot: int = 0, lp: LoopParams | None = None, op: OutcomeParams | None = None,
+                                d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_sensing_device: device pointers (ints; 0 = NULL), stream-ordered; d_sense, d_act, d_ground and d_push are
+        read in place, d_seen (or 0), d_line and d_tally (or 0) are read and written."""
+        self._loop_run_records_device(
+            "sensing", batch, d_states, ticks, lp, op, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, stream, d_outcomes,
+            d_push=d_push, pushes_per_robot=pushes_per_robot, d_ground=d_ground, d_tally=d_tally, d_act=d_act, d_line=d_line,
+            d_sense=d_sense, d_seen=d_seen)
+
+    def loop_run_gaits(self, states: np.ndarray, ticks: int, gait: np.ndarray | None, sense: np.ndarray | None = None,
+                       seen: np.ndarray | None = None, act: np.ndarray | None = None, lines: np.ndarray | None = None,
+                       ground: np.ndarray | None = None, push: np.ndarray | None = None, lp: LoopParams | None = None,
+                       ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
+                       outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None, trace: bool = False,
+                       want_seen: bool = True):
+        """qmpc_loop_run_gaits: loop_run_sensing in which every robot walks its own gait -- frequency, contact pattern, split and
+        starting phase per leg.  gait: [B] GAIT_PARAMS_DTYPE records, gait_params(); None: exactly loop_run_sensing.  Every other
+        record may be None as there.  The schedule lives in the states (leg, contacts, gait_counter): there is no record to carry
+        over calls, and a record changed between calls takes effect at each leg's next transition (phase0 at the next reset).
+        Returns (states, outcomes, tallies, lines, seen[, forces, contacts]); the arguments are not modified."""
+        st, acc, tr = self._loop_run_records(
+            "gaits", states, ticks, lp, op, trace, ctrl=ctrl, plant=plant, outcomes=outcomes, push=push, ground=ground,
+            tallies=tallies, act=act, lines=lines, sense=sense, seen=seen, want_seen=want_seen, gait=gait)
+        return (st, *acc[:4], *tr)
+
+    def loop_run_gaits_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_gait: int, d_sense: int = 0,
+                              d_seen: int = 0, d_act: int = 0, d_line: int = 0, d_ground: int = 0, d_tally: int = 0, d_push: int = 0,
+                              pushes_per_robot: int = 0, lp: LoopParams | None = None, op: OutcomeParams | None = None,
+                              d_ctrl: int = 0, d_plant: int = 0, d_trace_forces: int = 0, d_trace_contacts: int = 0, stream: int = 0):
+        """qmpc_loop_run_gaits_device: device pointers (ints; 0 = NULL), stream-ordered; d_gait, d_sense, d_act, d_ground and
+        d_push are read in place, d_seen (or 0), d_line and d_tally (or 0) are read and written."""
+        self._loop_run_records_device(
+            "gaits", batch, d_states, ticks, lp, op, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, stream, d_outcomes,
+            d_push=d_push, pushes_per_robot=pushes_per_robot, d_ground=d_ground, d_tally=d_tally, d_act=d_act, d_line=d_line,
+            d_sense=d_sense, d_seen=d_seen, d_gait=d_gait)
+
+    def loop_run_motors(self, states: np.ndarray, ticks: int, motor: np.ndarray | None, mtallies: np.ndarray | None = None,
+                        geom: "LegGeometry | None" = None, gait: np.ndarray | None = None, sense: np.ndarray | None = None,
+                        seen: np.ndarray | None = None, act: np.ndarray | None = None, lines: np.ndarray | None = None,
+                        ground: np.ndarray | None = None, push: np.ndarray | None = None, lp: LoopParams | None = None,
+                        ctrl: np.ndarray | None = None, plant: np.ndarray | None = None, op: OutcomeParams | None = None,
+                        outcomes: np.ndarray | None = None, tallies: np.ndarray | None = None, trace: bool = False,
+                        want_seen: bool = True, want_motor_tallies: bool = True):
+        """qmpc_loop_run_motors: loop_run_gaits in which the foot force a stance leg delivers respects the joint torque limits of
+        the robot's motors, and which records the torque every joint was asked for.  motor: [B] MOTOR_PARAMS_DTYPE records,
+        motor_params(); None: exactly loop_run_gaits.  mtallies: [B] MOTOR_TALLY_DTYPE, carried over calls (None: fresh ones
+        of module-level motor_tallies()); geom: one LegGeometry for all robots (None: the Go1's).  Every other record may be None
+        as there.  Returns (states, outcomes, tallies, lines, seen, motor_tallies[, forces, contacts]); the arguments are not
+        modified."""
+        st, acc, tr = self._loop_run_records(
+            "motors", states, ticks, lp, op, trace, ctrl=ctrl, plant=plant, outcomes=outcomes, push=push, ground=ground,
+            tallies=tallies, act=act, lines=lines, sense=sense, seen=seen, want_seen=want_seen, gait=gait, geom=geom,
+            motor=motor, mtallies=mtallies, want_motor_tallies=want_motor_tallies)
+        return (st, *acc[:5], *tr)
 
     def loop_run_motors_device(self, batch: int, d_states: int, ticks: int, d_outcomes: int, d_motor: int, d_motor_tally: int,
                                geom: "LegGeometry | None" = None, d_gait: int = 0, d_sense: int = 0, d_seen: int = 0, d_act: int = 0,
@@ -1706,16 +1479,10 @@ class Solver:
         """qmpc_loop_run_motors_device: device pointers (ints; 0 = NULL), stream-ordered; geom is a host record (None: the Go1's);
         d_motor, d_gait, d_sense, d_act, d_ground and d_push are read in place, d_motor_tally, d_seen (or 0), d_line and d_tally
         (or 0) are read and written."""
-        lp = lp or default_loop_params(self.lib)
-        op = op or default_outcome_params(self.lib)
-        p = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-        rc = self.lib.qmpc_loop_run_motors_device(self._h, C.byref(lp), int(batch), p(d_states), int(ticks), p(d_ctrl), p(d_plant),
-                                                  p(d_trace_forces), p(d_trace_contacts), C.byref(op), p(d_outcomes), p(d_push),
-                                                  int(pushes_per_robot), p(d_ground), p(d_tally), p(d_act), p(d_line), p(d_sense),
-                                                  p(d_seen), p(d_gait), C.byref(geom) if geom is not None else None, p(d_motor),
-                                                  p(d_motor_tally), p(stream))
-        if rc != OK:
-            raise QmpcError(rc, "qmpc_loop_run_motors_device")
+        self._loop_run_records_device(
+            "motors", batch, d_states, ticks, lp, op, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, stream, d_outcomes,
+            d_push=d_push, pushes_per_robot=pushes_per_robot, d_ground=d_ground, d_tally=d_tally, d_act=d_act, d_line=d_line,
+            d_sense=d_sense, d_seen=d_seen, d_gait=d_gait, geom=geom, d_motor=d_motor, d_motor_tally=d_motor_tally)
 
     def loop_instances_plan(self, batch: int, ctrl: bool = False, warm: bool = False):
         """The launch qmpc_loop_run_instances* takes for `batch` robots: (form, family) -- form "persistent" / "per_tick", family

@@ -23,6 +23,7 @@
 #include <new>
 
 #include "qmpc_kernel_slots.h"
+#include "qmpc_loop_records.h"
 #include "qmpc_plan_fill.h"
 
 using namespace qmpc;
@@ -71,33 +72,19 @@ hipError_t qmpc_wform_inst_solve_launch(int var, int batch, size_t lds, hipStrea
 // qmpc_loop_inst.hip, qmpc_loop_outcome.hip, qmpc_loop_push.hip, qmpc_loop_ground.hip: the closed loop with per-robot records --
 // controller and plant records (qmpc_loop_run_instances*), with the outcome step (qmpc_loop_run_outcomes*), under timed push
 // windows (qmpc_loop_run_pushes*), on the robot's true ground (qmpc_loop_run_ground*).  Each unit defines the same entry points in
-// its namespace (qmpc_loop_rec.inc) and ignores the trailing arguments its kernels do not take; the push and ground units have no
-// front kernel of their own.  qmpc_loop_act.hip: the ground loop behind the robot's delay line and actuator lag
-// (qmpc_loop_run_actuation*), the same entry points once more, no front kernel either.  qmpc_loop_sense.hip: the actuation loop
-// whose controller reads a measured state (qmpc_loop_run_sensing*), with a front kernel of its own that takes the sensing arguments.
-// qmpc_loop_gait.hip: the sensing loop in which every robot walks a gait of its own (qmpc_loop_run_gaits*); its front kernel takes
-// the gait argument too.  qmpc_loop_motor.hip: the gait loop whose delivered foot force respects the motors' torque limits
-// (qmpc_loop_run_motors*); its post and persistent kernels take the last three arguments.
-#define QMPC_REC_DECLARE(ns)                                                                                                        \
-  namespace ns {                                                                                                                     \
-  hipError_t rec_set_lds();                                                                                                          \
-  hipError_t rec_fused_launch(int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants,            \
-                              const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info,    \
-                              double* trace_f, double* trace_c, int ticks, double* gws, const qmpc_outcome_params* op,              \
-                              qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,                             \
-                              const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act,         \
-                              qmpc_actuation_line* line, const qmpc_sense_params* sense, qmpc_sense_seen* seen,                      \
-                              const qmpc_gait_params* gait, const qmpc_leg_geometry* geom, const qmpc_motor_params* motor,           \
-                              qmpc_motor_tally* mtally);                                                                             \
-  hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, qmpc_input* rec, int* row,            \
-                              const void* plants, int batch, const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes,      \
-                              const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait);                 \
-  hipError_t rec_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st, const double* forces,                  \
-                             const qmpc_info* info, double* trace_f, double* trace_c, const int* row, const void* plants, int batch, \
-                             const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push,              \
-                             int per_robot, const qmpc_ground_params* ground, qmpc_ground_tally* tally,                              \
-                             const qmpc_actuation_params* act, qmpc_actuation_line* line, const qmpc_leg_geometry* geom,             \
-                             const qmpc_motor_params* motor, qmpc_motor_tally* mtally);                                              \
+// its namespace (qmpc_loop_rec.inc): each takes the call's buffers and its records (qmpc_loop_records.h) and passes its kernels what
+// they take; the push and ground units have no front kernel of their own.  qmpc_loop_act.hip: the ground loop behind the robot's
+// delay line and actuator lag (qmpc_loop_run_actuation*), the same entry points once more, no front kernel either.
+// qmpc_loop_sense.hip: the actuation loop whose controller reads a measured state (qmpc_loop_run_sensing*), with a front kernel of
+// its own that takes the sensing records.  qmpc_loop_gait.hip: the sensing loop in which every robot walks a gait of its own
+// (qmpc_loop_run_gaits*); its front kernel takes the gait record too.  qmpc_loop_motor.hip: the gait loop whose delivered foot force
+// respects the motors' torque limits (qmpc_loop_run_motors*); its post and persistent kernels take the geometry and the motor records.
+#define QMPC_REC_DECLARE(ns)                                                                                                  \
+  namespace ns {                                                                                                               \
+  hipError_t rec_set_lds();                                                                                                    \
+  hipError_t rec_fused_launch(int var, size_t lds, int ticks, double* gws, const rec_launch& L, const loop_recs& r);           \
+  hipError_t rec_front_launch(const rec_launch& L, const loop_recs& r);                                                        \
+  hipError_t rec_post_launch(const rec_launch& L, const loop_recs& r);                                                         \
   }
 QMPC_REC_DECLARE(qmpc_inst_tu)
 QMPC_REC_DECLARE(qmpc_outc_tu)
@@ -114,32 +101,24 @@ QMPC_REC_DECLARE(qmpc_cgait_tu)     // qmpc_loop_cgait.hip: the gait call on suc
 QMPC_REC_DECLARE(qmpc_motor_tu)     // qmpc_loop_motor.hip
 QMPC_REC_DECLARE(qmpc_cmotor_tu)    // qmpc_loop_cmotor.hip: the motor call on such a ConvexMpc handle
 #undef QMPC_REC_DECLARE
-enum { REC_PLAIN = 0, REC_OUTCOME = 1, REC_PUSH = 2 };      // the kind of a call with records: QMPC_REC_EXT of its unit
-enum { REC_CONVEX = 3 };                                    // ... the unit that serves those three kinds for ConvexMpc's problem
-enum { REC_GROUND = 4, REC_CGROUND = 5 };                   // the ground call's kind (EXT 3), and its unit for ConvexMpc's problem
-enum { REC_ACT = 6, REC_CACT = 7 };                         // the actuation call's kind (EXT 4), and its unit for ConvexMpc's problem
-enum { REC_SENSE = 8, REC_CSENSE = 9 };                     // the sensing call's kind (EXT 5), and its unit for ConvexMpc's problem
-enum { REC_GAIT = 10, REC_CGAIT = 11 };                     // the gait call's kind (EXT 6), and its unit for ConvexMpc's problem
-enum { REC_MOTOR = 12, REC_CMOTOR = 13 };                   // the motor call's kind (EXT 7), and its unit for ConvexMpc's problem
+// the launchers of a call with records by [kind][the handle is ConvexMpc's] (REC_*: qmpc_loop_records.h).  QMPC_REC_UNIT(u, f): unit
+// u's, with the front kernel of unit f (the QuatMpc units of REC_PUSH .. REC_ACT launch the outcome unit's); one ConvexMpc unit
+// serves the first three kinds
+#define QMPC_REC_UNIT(u, f) {u::rec_set_lds, u::rec_fused_launch, f::rec_front_launch, u::rec_post_launch}
 static const struct {
   decltype(&qmpc_inst_tu::rec_set_lds) set_lds;
   decltype(&qmpc_inst_tu::rec_fused_launch) fused_launch;
   decltype(&qmpc_inst_tu::rec_front_launch) front_launch;
   decltype(&qmpc_inst_tu::rec_post_launch) post_launch;
-} kRec[14] = {{qmpc_inst_tu::rec_set_lds, qmpc_inst_tu::rec_fused_launch, qmpc_inst_tu::rec_front_launch, qmpc_inst_tu::rec_post_launch},
-             {qmpc_outc_tu::rec_set_lds, qmpc_outc_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_outc_tu::rec_post_launch},
-             {qmpc_push_tu::rec_set_lds, qmpc_push_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_push_tu::rec_post_launch},
-             {qmpc_crec_tu::rec_set_lds, qmpc_crec_tu::rec_fused_launch, qmpc_crec_tu::rec_front_launch, qmpc_crec_tu::rec_post_launch},
-             {qmpc_ground_tu::rec_set_lds, qmpc_ground_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_ground_tu::rec_post_launch},
-             {qmpc_cground_tu::rec_set_lds, qmpc_cground_tu::rec_fused_launch, qmpc_cground_tu::rec_front_launch, qmpc_cground_tu::rec_post_launch},
-             {qmpc_act_tu::rec_set_lds, qmpc_act_tu::rec_fused_launch, qmpc_outc_tu::rec_front_launch, qmpc_act_tu::rec_post_launch},
-             {qmpc_cact_tu::rec_set_lds, qmpc_cact_tu::rec_fused_launch, qmpc_cact_tu::rec_front_launch, qmpc_cact_tu::rec_post_launch},
-             {qmpc_sense_tu::rec_set_lds, qmpc_sense_tu::rec_fused_launch, qmpc_sense_tu::rec_front_launch, qmpc_sense_tu::rec_post_launch},
-             {qmpc_csense_tu::rec_set_lds, qmpc_csense_tu::rec_fused_launch, qmpc_csense_tu::rec_front_launch, qmpc_csense_tu::rec_post_launch},
-             {qmpc_gait_tu::rec_set_lds, qmpc_gait_tu::rec_fused_launch, qmpc_gait_tu::rec_front_launch, qmpc_gait_tu::rec_post_launch},
-             {qmpc_cgait_tu::rec_set_lds, qmpc_cgait_tu::rec_fused_launch, qmpc_cgait_tu::rec_front_launch, qmpc_cgait_tu::rec_post_launch},
-             {qmpc_motor_tu::rec_set_lds, qmpc_motor_tu::rec_fused_launch, qmpc_motor_tu::rec_front_launch, qmpc_motor_tu::rec_post_launch},
-             {qmpc_cmotor_tu::rec_set_lds, qmpc_cmotor_tu::rec_fused_launch, qmpc_cmotor_tu::rec_front_launch, qmpc_cmotor_tu::rec_post_launch}};
+} kRec[REC_KINDS][2] = {{QMPC_REC_UNIT(qmpc_inst_tu, qmpc_inst_tu), QMPC_REC_UNIT(qmpc_crec_tu, qmpc_crec_tu)},
+                        {QMPC_REC_UNIT(qmpc_outc_tu, qmpc_outc_tu), QMPC_REC_UNIT(qmpc_crec_tu, qmpc_crec_tu)},
+                        {QMPC_REC_UNIT(qmpc_push_tu, qmpc_outc_tu), QMPC_REC_UNIT(qmpc_crec_tu, qmpc_crec_tu)},
+                        {QMPC_REC_UNIT(qmpc_ground_tu, qmpc_outc_tu), QMPC_REC_UNIT(qmpc_cground_tu, qmpc_cground_tu)},
+                        {QMPC_REC_UNIT(qmpc_act_tu, qmpc_outc_tu), QMPC_REC_UNIT(qmpc_cact_tu, qmpc_cact_tu)},
+                        {QMPC_REC_UNIT(qmpc_sense_tu, qmpc_sense_tu), QMPC_REC_UNIT(qmpc_csense_tu, qmpc_csense_tu)},
+                        {QMPC_REC_UNIT(qmpc_gait_tu, qmpc_gait_tu), QMPC_REC_UNIT(qmpc_cgait_tu, qmpc_cgait_tu)},
+                        {QMPC_REC_UNIT(qmpc_motor_tu, qmpc_motor_tu), QMPC_REC_UNIT(qmpc_cmotor_tu, qmpc_cmotor_tu)}};
+#undef QMPC_REC_UNIT
 // ... and the kernels each unit has beside them: the expansions of the plant blocks and the check of the windows
 hipError_t qmpc_loop_inst_expand_launch(hipStream_t s, const void* dev_params, size_t dev_params_size, const qmpc_plant_params* plant,
                                         const qmpc_instance_params* ctrl, const int* ctrl_status, void* bcast_out, void* plants_out,
@@ -294,19 +273,42 @@ struct qmpc_handle {
   qmpc_loop_outcome* d_outcome;   // staging of qmpc_loop_run_outcomes (the host-buffer call), on its first use: [max_batch] records
   qmpc_push_params* d_push;       // staging of qmpc_loop_run_pushes (the host-buffer call), on its first use: [max_batch][push_cap]
   int push_cap;                   // ... windows per robot it holds (grown when a call brings more)
-  void* d_ground;                 // staging of qmpc_loop_run_ground (the host-buffer call), on its first use: max_batch ground
-                                  // records (64 B each), then max_batch tallies (32 B each)
-  void* d_act;                    // staging of qmpc_loop_run_actuation (the host-buffer call), on its first use: max_batch delay
-                                  // lines (896 B each), then max_batch actuation records (32 B each)
-  void* d_sense;                  // staging of qmpc_loop_run_sensing (the host-buffer call), on its first use: max_batch sensing
-                                  // records (256 B each), then max_batch seen records (128 B each)
-  void* d_gait;                   // staging of qmpc_loop_run_gaits (the host-buffer call), on its first use: max_batch gait records
-                                  // (128 B each)
-  void* d_motor;                  // staging of qmpc_loop_run_motors (the host-buffer call), on its first use: max_batch motor tallies
-                                  // (320 B each), then max_batch motor records (128 B each)
+  // staging of the optional record kinds of the host-buffer calls (qmpc_loop_run_ground .. qmpc_loop_run_motors), each on its
+  // first use: which records a buffer holds, in which order and at which size is kRecStage's to say (below, at loop_records_host)
+  void* d_ground;
+  void* d_act;
+  void* d_sense;
+  void* d_gait;
+  void* d_motor;
   unsigned char* d_sched;         // staging of qmpc_solve_schedule (the host-buffer call), on its first use: max_batch schedules
                                   // of N bytes
 };
+
+// The staging of the optional record kinds of a host-buffer call, one row per record in the order of the copies in (the copies
+// out walk the rows backwards): the handle's buffer, the record's size, the size of the record that lies BEFORE it in the buffer
+// (a buffer is max_batch records of one type, then max_batch of the other; 0: this one comes first), whether the record comes
+// back, and the record's place in loop_recs.  Allocation (loop_records_host), both copies and qmpc_query's byte count walk it.
+struct rec_stage {
+  void* qmpc_handle::*buf;
+  size_t elem, before;
+  bool out;
+  void* (*get)(const loop_recs&);
+  void (*set)(loop_recs&, void*);
+};
+#define QMPC_STAGE(buf_, T_, before_, out_, field_)                                                                   \
+  {&qmpc_handle::buf_, sizeof(T_), before_, out_,                                                                     \
+   [](const loop_recs& r) -> void* { return const_cast<void*>(static_cast<const void*>(r.field_)); },                 \
+   [](loop_recs& r, void* p) { r.field_ = static_cast<T_*>(p); }}
+static const rec_stage kRecStage[] = {QMPC_STAGE(d_ground, qmpc_ground_params, 0, false, ground),
+                                      QMPC_STAGE(d_ground, qmpc_ground_tally, sizeof(qmpc_ground_params), true, tally),
+                                      QMPC_STAGE(d_act, qmpc_actuation_params, sizeof(qmpc_actuation_line), false, act),
+                                      QMPC_STAGE(d_act, qmpc_actuation_line, 0, true, line),
+                                      QMPC_STAGE(d_sense, qmpc_sense_params, 0, false, sense),
+                                      QMPC_STAGE(d_sense, qmpc_sense_seen, sizeof(qmpc_sense_params), true, seen),
+                                      QMPC_STAGE(d_gait, qmpc_gait_params, 0, false, gait),
+                                      QMPC_STAGE(d_motor, qmpc_motor_params, sizeof(qmpc_motor_tally), false, motor),
+                                      QMPC_STAGE(d_motor, qmpc_motor_tally, 0, true, mtally)};
+#undef QMPC_STAGE
 
 constexpr unsigned kLaneMaxSlots = 1024 * 64;   // one wavefront per SIMD of the chip
 
@@ -459,7 +461,9 @@ static qmpc_status create_resources(qmpc_handle* h, int N, int nl, int nu) {
   HIP_TRY(set_max_lds(kDenseSolve, kDenseRef, kLinearize));
   HIP_TRY(qmpc_loop_fused_set_lds());
   HIP_TRY(qmpc_wform_set_lds());
-  for (const auto& r : kRec) HIP_TRY(r.set_lds());
+  for (int k = 0; k < REC_KINDS; ++k)
+    for (int c = 0; c < 2; ++c)      // (once per unit: the ConvexMpc unit of the first three kinds is one)
+      if (k == 0 || kRec[k][c].set_lds != kRec[k - 1][c].set_lds) HIP_TRY(kRec[k][c].set_lds());
   HIP_TRY(qmpc_wform_inst_list_set_lds());
   HIP_TRY(qmpc_wform_inst_warm_set_lds());
   HIP_TRY(qmpc_wform_cinst_set_lds());
@@ -1339,11 +1343,8 @@ qmpc_status qmpc_query(qmpc_handle* h, int32_t what, int64_t arg, int64_t* value
       if (h->d_plant) b += plant_bytes(h->max_batch);
       if (h->d_outcome) b += sizeof(qmpc_loop_outcome) * (size_t)h->max_batch;
       if (h->d_push) b += sizeof(qmpc_push_params) * (size_t)h->push_cap * (size_t)h->max_batch;
-      if (h->d_ground) b += (sizeof(qmpc_ground_params) + sizeof(qmpc_ground_tally)) * (size_t)h->max_batch;
-      if (h->d_act) b += (sizeof(qmpc_actuation_params) + sizeof(qmpc_actuation_line)) * (size_t)h->max_batch;
-      if (h->d_sense) b += (sizeof(qmpc_sense_params) + sizeof(qmpc_sense_seen)) * (size_t)h->max_batch;
-      if (h->d_gait) b += sizeof(qmpc_gait_params) * (size_t)h->max_batch;
-      if (h->d_motor) b += (sizeof(qmpc_motor_params) + sizeof(qmpc_motor_tally)) * (size_t)h->max_batch;
+      for (const rec_stage& s : kRecStage)
+        if (h->*s.buf) b += s.elem * (size_t)h->max_batch;
       if (h->d_sched) b += (size_t)N * (size_t)h->max_batch;
       b += sizeof(double) * (h->leg_cap + h->loop_cap);
       *value = (int64_t)b;
@@ -1836,100 +1837,12 @@ qmpc_status qmpc_loop_run_joint_device(qmpc_handle* h, const qmpc_loop_params* l
   return loop_run_impl(h, lp, batch, d_states, ticks, nullptr, nullptr, g, d_joint_pos, d_cmd, d_trace_cmd, stream);
 }
 
-// the three arguments of qmpc_loop_run_motors* beyond the gait call's (REC_MOTOR only): the geometry on the host, the records
-// and tallies where the call's other records are
-struct loop_motor_args {
-  const qmpc_leg_geometry* geom;
-  const qmpc_motor_params* motor;
-  qmpc_motor_tally* tally;
-};
-
-static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
-                                       int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
-                                       double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
-                                       qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot,
-                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
-                                       const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
-                                       const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
-                                       void* stream, const loop_motor_args* mo = nullptr);
-
-// The host-buffer closed loop of every kind (qmpc_loop_run*, its arguments checked): states and traces through the handle's
-// staging, which only grows -- [states | force trace | contact trace]; the records given go to the staging halves of the
-// per-instance and plant buffers, outcome records and windows to h->d_outcome and h->d_push, ground records and tallies to
-// h->d_ground, actuation records and delay lines to h->d_act, sensing records and seen to h->d_sense, gait records to h->d_gait,
-// motor tallies and records to h->d_motor (all allocated by the caller)
 static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
-                                     int32_t ticks, const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
-                                     double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
-                                     const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
-                                     qmpc_ground_tally* tally, const qmpc_actuation_params* act = nullptr,
-                                     qmpc_actuation_line* line = nullptr, const qmpc_sense_params* sense = nullptr,
-                                     qmpc_sense_seen* seen = nullptr, const qmpc_gait_params* gait = nullptr,
-                                     const loop_motor_args* mo = nullptr) {
-  const size_t B = (size_t)batch, T = (size_t)ticks;
-  const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = trace_forces ? 12 * B * T : 0,
-               n_tc = trace_contacts ? 4 * B * T : 0;
-  if (h->loop_cap < n_st + n_tf + n_tc) {
-    if (h->d_loop) (void)hipFree(h->d_loop);
-    h->d_loop = nullptr;
-    h->loop_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_loop, sizeof(double) * (n_st + n_tf + n_tc)));
-    h->loop_cap = n_st + n_tf + n_tc;
-  }
-  qmpc_loop_state* d_st = reinterpret_cast<qmpc_loop_state*>(h->d_loop);
-  double* d_tf = trace_forces ? h->d_loop + n_st : nullptr;
-  double* d_tc = trace_contacts ? h->d_loop + n_st + n_tf : nullptr;
-  HIP_TRY(hipMemcpyAsync(d_st, states, sizeof(qmpc_loop_state) * B, hipMemcpyHostToDevice, h->stream));
-  if (outcomes) HIP_TRY(hipMemcpyAsync(h->d_outcome, outcomes, sizeof(qmpc_loop_outcome) * B, hipMemcpyHostToDevice, h->stream));
-  if (ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
-  if (plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
-  if (push) HIP_TRY(hipMemcpyAsync(h->d_push, push, sizeof(qmpc_push_params) * B * (size_t)per_robot, hipMemcpyHostToDevice, h->stream));
-  qmpc_ground_params* d_gr = ground ? static_cast<qmpc_ground_params*>(h->d_ground) : nullptr;
-  qmpc_ground_tally* d_ta = (ground && tally) ? reinterpret_cast<qmpc_ground_tally*>(static_cast<qmpc_ground_params*>(h->d_ground) + h->max_batch) : nullptr;
-  if (d_gr) HIP_TRY(hipMemcpyAsync(d_gr, ground, sizeof(qmpc_ground_params) * B, hipMemcpyHostToDevice, h->stream));
-  if (d_ta) HIP_TRY(hipMemcpyAsync(d_ta, tally, sizeof(qmpc_ground_tally) * B, hipMemcpyHostToDevice, h->stream));
-  qmpc_actuation_line* d_li = act ? static_cast<qmpc_actuation_line*>(h->d_act) : nullptr;
-  qmpc_actuation_params* d_ac = act ? reinterpret_cast<qmpc_actuation_params*>(static_cast<qmpc_actuation_line*>(h->d_act) + h->max_batch) : nullptr;
-  if (d_ac) HIP_TRY(hipMemcpyAsync(d_ac, act, sizeof(qmpc_actuation_params) * B, hipMemcpyHostToDevice, h->stream));
-  if (d_li) HIP_TRY(hipMemcpyAsync(d_li, line, sizeof(qmpc_actuation_line) * B, hipMemcpyHostToDevice, h->stream));
-  qmpc_sense_params* d_se = sense ? static_cast<qmpc_sense_params*>(h->d_sense) : nullptr;
-  qmpc_sense_seen* d_sn = (sense && seen) ? reinterpret_cast<qmpc_sense_seen*>(static_cast<qmpc_sense_params*>(h->d_sense) + h->max_batch) : nullptr;
-  if (d_se) HIP_TRY(hipMemcpyAsync(d_se, sense, sizeof(qmpc_sense_params) * B, hipMemcpyHostToDevice, h->stream));
-  if (d_sn) HIP_TRY(hipMemcpyAsync(d_sn, seen, sizeof(qmpc_sense_seen) * B, hipMemcpyHostToDevice, h->stream));
-  qmpc_gait_params* d_ga = gait ? static_cast<qmpc_gait_params*>(h->d_gait) : nullptr;
-  if (d_ga) HIP_TRY(hipMemcpyAsync(d_ga, gait, sizeof(qmpc_gait_params) * B, hipMemcpyHostToDevice, h->stream));
-  loop_motor_args d_mo = {nullptr, nullptr, nullptr};
-  if (mo) {
-    d_mo.geom = mo->geom;
-    d_mo.tally = static_cast<qmpc_motor_tally*>(h->d_motor);
-    d_mo.motor = reinterpret_cast<qmpc_motor_params*>(static_cast<qmpc_motor_tally*>(h->d_motor) + h->max_batch);
-    HIP_TRY(hipMemcpyAsync(const_cast<qmpc_motor_params*>(d_mo.motor), mo->motor, sizeof(qmpc_motor_params) * B, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_mo.tally, mo->tally, sizeof(qmpc_motor_tally) * B, hipMemcpyHostToDevice, h->stream));
-  }
-  const qmpc_status rs = loop_records_device(kind, h, lp, batch, d_st, ticks, ctrl ? inst_rec(h) : nullptr, plant ? plant_rec(h) : nullptr,
-                                             d_tf, d_tc, op, outcomes ? h->d_outcome : nullptr, push ? h->d_push : nullptr, per_robot,
-                                             d_gr, d_ta, d_ac, d_li, d_se, d_sn, d_ga, nullptr, mo ? &d_mo : nullptr);
-  if (rs != QMPC_OK) return rs;
-  if (mo) HIP_TRY(hipMemcpyAsync(mo->tally, d_mo.tally, sizeof(qmpc_motor_tally) * B, hipMemcpyDeviceToHost, h->stream));
-  if (d_sn) HIP_TRY(hipMemcpyAsync(seen, d_sn, sizeof(qmpc_sense_seen) * B, hipMemcpyDeviceToHost, h->stream));
-  if (d_li) HIP_TRY(hipMemcpyAsync(line, d_li, sizeof(qmpc_actuation_line) * B, hipMemcpyDeviceToHost, h->stream));
-  if (d_ta) HIP_TRY(hipMemcpyAsync(tally, d_ta, sizeof(qmpc_ground_tally) * B, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
-  if (outcomes) HIP_TRY(hipMemcpyAsync(outcomes, h->d_outcome, sizeof(qmpc_loop_outcome) * B, hipMemcpyDeviceToHost, h->stream));
-  if (d_tf) HIP_TRY(hipMemcpyAsync(trace_forces, d_tf, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream));
-  if (d_tc) HIP_TRY(hipMemcpyAsync(trace_contacts, d_tc, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return QMPC_OK;
-}
+                                     int32_t ticks, const loop_recs& r);
 
 qmpc_status qmpc_loop_run(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
                           int32_t ticks, double* trace_forces, double* trace_contacts) {
-  if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !states)) return QMPC_BAD_ARGUMENT;
-  if (h->params.model != QMPC_MODEL_QUAT && h->params.model != QMPC_MODEL_CONVEX) return QMPC_BAD_ARGUMENT;
-  if (batch == 0 || ticks == 0) return QMPC_OK;
-  if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
-  HIP_TRY(hipSetDevice(h->device));
-  return loop_records_host(REC_PLAIN, h, lp, batch, states, ticks, nullptr, nullptr, trace_forces, trace_contacts, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+  return loop_records_host(REC_PLAIN, h, lp, batch, states, ticks, loop_recs{nullptr, nullptr, trace_forces, trace_contacts});
 }
 
 // ---- the closed loop with per-robot controller and plant records (qmpc_loop_inst.hip) -------------------------------------
@@ -1995,118 +1908,185 @@ static qmpc_status loop_instances_buffers(qmpc_handle* h, int32_t batch, bool ha
   return QMPC_OK;
 }
 
-// The device-buffer closed loop of every kind with records.  kind REC_PLAIN (qmpc_loop_run_instances_device): the call without
-// records is the plain loop.  REC_OUTCOME / REC_PUSH (qmpc_loop_run_outcomes_device / qmpc_loop_run_pushes_device): the same call
-// with the kernels of the kind's unit in place of the plain unit's; without records (both NULL) every robot's plant block carries
-// the handle's mass and inverse inertia, and the call-level checks are those of a call with plant records.  d_push (REC_PUSH):
-// per_robot windows per robot, checked once after the plant expansion.  REC_GROUND (qmpc_loop_run_ground_device): d_push may be
-// NULL (no windows), d_ground is checked after the windows, d_tally may be NULL.  REC_ACT (qmpc_loop_run_actuation_device): d_ground
-// may be NULL too (no clamp; checked when given), d_act and the count of d_line are checked last.  REC_SENSE
-// (qmpc_loop_run_sensing_device): d_act may be NULL too (checked when given), d_sense is checked last, d_seen may be NULL.
-// REC_GAIT (qmpc_loop_run_gaits_device): d_sense may be NULL too (checked when given), d_gait is checked last.
-// REC_MOTOR (qmpc_loop_run_motors_device): d_gait may be NULL too (checked when given), mo's records and tallies are checked last;
-// mo->geom is a host pointer and travels as a kernel argument.
+// The device-buffer closed loop of every kind, on the call's records as loop_recs_normalise left them (qmpc_loop_records.h: what
+// is not NULL is part of the call).  REC_PLAIN without records is the plain loop.  Above it the kernels of the kind's unit run in
+// place of the plain unit's; without ctrl and plant every robot's plant block carries the handle's mass and inverse inertia, and
+// the call-level checks are those of a call with plant records.  Every record that is there is checked once after the plant
+// expansion, in the order of the kinds: a robot whose record is refused is frozen through its plant block.  r.geom is a host
+// pointer and travels as a kernel argument.
 static qmpc_status loop_records_device(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
-                                       int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
-                                       double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
-                                       qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t per_robot,
-                                       const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
-                                       const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
-                                       const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
-                                       void* stream, const loop_motor_args* mo) {
+                                       int32_t ticks, const loop_recs& recs, void* stream) {
   if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !d_states)) return QMPC_BAD_ARGUMENT;
-  if ((kind == REC_MOTOR) != (mo != nullptr) || (mo && (!mo->geom || (batch > 0 && (!mo->motor || !mo->tally))))) return QMPC_BAD_ARGUMENT;
-  if (kind != REC_PLAIN && (!op || (batch > 0 && !d_outcomes))) return QMPC_BAD_ARGUMENT;
-  if (kind == REC_PLAIN && !d_ctrl && !d_plant)
-    return loop_run_impl(h, lp, batch, d_states, ticks, d_trace_forces, d_trace_contacts, nullptr, nullptr, nullptr, nullptr, stream);
-  const qmpc_status cs = loop_instances_check(h, lp, batch, d_ctrl != nullptr);
+  if (kind == REC_PLAIN && !recs.ctrl && !recs.plant)
+    return loop_run_impl(h, lp, batch, d_states, ticks, recs.trace_forces, recs.trace_contacts, nullptr, nullptr, nullptr, nullptr, stream);
+  const bool has_ctrl = recs.ctrl != nullptr;
+  const qmpc_status cs = loop_instances_check(h, lp, batch, has_ctrl);
   if (cs != QMPC_OK || batch == 0) return cs;
   const bool warm = lp->warm_start != 0.0;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   qmpc_plan lpp;
-  const qmpc_status es = loop_instances_buffers(h, batch, d_ctrl != nullptr, warm, &lpp);
+  const qmpc_status es = loop_instances_buffers(h, batch, has_ctrl, warm, &lpp);
   if (es != QMPC_OK || ticks == 0) return es;      // ticks = 0: the buffers only (e.g. before the caller's stream capture)
   const qmpc_status ss = loop_setup(h, s, warm && !lpp.fused);
   if (ss != QMPC_OK) return ss;
   // the cold first tick of a warm-started call with controller records has a plan of its own (the lane form: no cap, no hand-off)
-  const qmpc_plan lpp_first = (d_ctrl && warm && !lpp.fused) ? plan_loop_instances(h->sel, h->opts, batch, true, warm, /*first=*/true) : lpp;
+  const qmpc_plan lpp_first = (has_ctrl && warm && !lpp.fused) ? plan_loop_instances(h->sel, h->opts, batch, true, warm, /*first=*/true) : lpp;
   const qmpc_loop_params LP = *lp;
-  // a ConvexMpc handle (opted in): one unit for the three kinds -- a call without windows passes none (per_robot = 0), a call
-  // without outcome records the handle's scratch and parameters that never halt a robot
+  // a ConvexMpc handle (opted in): one unit for the first three kinds -- a call without windows passes none (per_robot = 0), a
+  // call without outcome records the handle's scratch and parameters that never halt a robot
   const bool crec = convex_records(h);
-  const auto& R = kRec[kind == REC_MOTOR ? (crec ? REC_CMOTOR : REC_MOTOR) : kind == REC_GAIT ? (crec ? REC_CGAIT : REC_GAIT) : kind == REC_SENSE ? (crec ? REC_CSENSE : REC_SENSE) : kind == REC_ACT ? (crec ? REC_CACT : REC_ACT) : kind == REC_GROUND ? (crec ? REC_CGROUND : REC_GROUND) : crec ? REC_CONVEX : kind];
+  const auto& R = kRec[kind][crec];
+  loop_recs r = recs;
   qmpc_outcome_params op_none;
   std::memset(&op_none, 0, sizeof op_none);
   if (crec && kind == REC_PLAIN) {
-    op = &op_none;
-    d_outcomes = h->d_outcome;
-  }
-  if ((crec && kind != REC_PUSH && kind != REC_GROUND && kind != REC_ACT && kind != REC_SENSE && kind != REC_GAIT && kind != REC_MOTOR) || !d_push) {
-    d_push = nullptr;
-    per_robot = 0;
+    r.op = &op_none;
+    r.outcomes = h->d_outcome;
   }
   // the records are expanded once per call: the controllers' blocks (or, for the persistent kernel without controller records,
   // the handle's block per robot) and the plant blocks with each robot's verdict
-  if (d_ctrl) HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, d_ctrl, inst_dev(h), inst_status(h)));
-  void* bcast = (!d_ctrl && lpp.fused) ? inst_dev(h) : nullptr;
-  if (d_ctrl || d_plant)
-    HIP_TRY(qmpc_loop_inst_expand_launch(s, &h->dev, sizeof h->dev, d_plant, d_ctrl, d_ctrl ? inst_status(h) : nullptr, bcast,
+  if (has_ctrl) HIP_TRY(qmpc_wform_inst_expand_launch((int)batch, s, &h->dev, sizeof h->dev, r.ctrl, inst_dev(h), inst_status(h)));
+  void* bcast = (!has_ctrl && lpp.fused) ? inst_dev(h) : nullptr;
+  if (r.ctrl || r.plant)
+    HIP_TRY(qmpc_loop_inst_expand_launch(s, &h->dev, sizeof h->dev, r.plant, r.ctrl, has_ctrl ? inst_status(h) : nullptr, bcast,
                                          plant_dev(h), (int)batch));
   else
     HIP_TRY(qmpc_loop_outcome_expand_base_launch(s, &h->dev, sizeof h->dev, bcast, plant_dev(h), (int)batch));
-  if (d_push) HIP_TRY(qmpc_loop_push_check_launch(s, d_push, (int)per_robot, plant_dev(h), (int)batch));
-  if (kind == REC_GROUND || ((kind == REC_ACT || kind == REC_SENSE || kind == REC_GAIT || kind == REC_MOTOR) && d_ground))
-    HIP_TRY(qmpc_ground_tu::rec_ground_check_launch(s, d_ground, plant_dev(h), (int)batch));
-  if (kind == REC_ACT || ((kind == REC_SENSE || kind == REC_GAIT || kind == REC_MOTOR) && d_act)) HIP_TRY(qmpc_act_tu::rec_act_check_launch(s, d_act, d_line, plant_dev(h), (int)batch));
-  if (kind == REC_SENSE || ((kind == REC_GAIT || kind == REC_MOTOR) && d_sense)) HIP_TRY(qmpc_sense_tu::rec_sense_check_launch(s, d_sense, plant_dev(h), (int)batch));
-  if (kind == REC_GAIT || (kind == REC_MOTOR && d_gait)) HIP_TRY(qmpc_gait_tu::rec_gait_check_launch(s, d_gait, plant_dev(h), lp->dt, (int)batch));
-  if (kind == REC_MOTOR) HIP_TRY(qmpc_motor_tu::rec_motor_check_launch(s, mo->motor, mo->tally, plant_dev(h), (int)batch));
-  const qmpc_leg_geometry* m_geom = mo ? mo->geom : nullptr;
-  const qmpc_motor_params* m_rec = mo ? mo->motor : nullptr;
-  qmpc_motor_tally* m_tally = mo ? mo->tally : nullptr;
+  if (r.push) HIP_TRY(qmpc_loop_push_check_launch(s, r.push, (int)r.per_robot, plant_dev(h), (int)batch));
+  if (r.ground) HIP_TRY(qmpc_ground_tu::rec_ground_check_launch(s, r.ground, plant_dev(h), (int)batch));
+  if (r.act) HIP_TRY(qmpc_act_tu::rec_act_check_launch(s, r.act, r.line, plant_dev(h), (int)batch));
+  if (r.sense) HIP_TRY(qmpc_sense_tu::rec_sense_check_launch(s, r.sense, plant_dev(h), (int)batch));
+  if (r.gait) HIP_TRY(qmpc_gait_tu::rec_gait_check_launch(s, r.gait, plant_dev(h), lp->dt, (int)batch));
+  if (r.motor) HIP_TRY(qmpc_motor_tu::rec_motor_check_launch(s, r.motor, r.mtally, plant_dev(h), (int)batch));
+  const rec_launch L = {s, inst_dev(h), plant_dev(h), &LP, d_states, h->d_in, h->d_forces, h->d_info, h->d_loop_row, (int)batch};
   if (lpp.fused) {
-    HIP_TRY(R.fused_launch(lpp.variant, (int)batch, lpp.lds, s, inst_dev(h), plant_dev(h), &LP, d_states, h->d_in, h->d_forces, h->d_info,
-                           d_trace_forces, d_trace_contacts, (int)ticks, lpp.gws ? h->d_gws : nullptr, op, d_outcomes, d_push,
-                           (int)per_robot, d_ground, d_tally, d_act, d_line, d_sense, d_seen, d_gait, m_geom, m_rec, m_tally));
+    HIP_TRY(R.fused_launch(lpp.variant, lpp.lds, (int)ticks, lpp.gws ? h->d_gws : nullptr, L, r));
     return QMPC_OK;
   }
   auto one_tick = [&](bool first) -> qmpc_status {
-    HIP_TRY(R.front_launch(s, &LP, d_states, h->d_in, h->d_loop_row, plant_dev(h), (int)batch, op, d_outcomes, d_sense, d_seen, d_gait));
+    HIP_TRY(R.front_launch(L, r));
     // with controller records the solve on the blocks expanded above (a warm-started call's solution travels through
     // h->d_traj_u), without them the plain loop's
-    const qmpc_status st = !d_ctrl ? loop_tick_solve(h, batch, s, warm, first, crec)
-                                   : inst_solve(h, first ? lpp_first : lpp, crec, !warm ? INST_TICK_COLD : first ? INST_TICK_FIRST : INST_TICK_WARM,
-                                                batch, h->d_in, h->d_forces, h->d_info, warm ? h->d_traj_u : nullptr, nullptr, s);
+    const qmpc_status st = !has_ctrl ? loop_tick_solve(h, batch, s, warm, first, crec)
+                                     : inst_solve(h, first ? lpp_first : lpp, crec, !warm ? INST_TICK_COLD : first ? INST_TICK_FIRST : INST_TICK_WARM,
+                                                  batch, h->d_in, h->d_forces, h->d_info, warm ? h->d_traj_u : nullptr, nullptr, s);
     if (st != QMPC_OK) return st;
-    HIP_TRY(R.post_launch(s, &LP, d_states, h->d_forces, h->d_info, d_trace_forces, d_trace_contacts, h->d_loop_row, plant_dev(h),
-                          (int)batch, op, d_outcomes, d_push, (int)per_robot, d_ground, d_tally, d_act, d_line, m_geom, m_rec, m_tally));
+    HIP_TRY(R.post_launch(L, r));
     return QMPC_OK;
   };
   // (the lane kernel's block in the table of the unit with per-lane parameters: once per call, outside the capture)
-  if (d_ctrl && lpp.variant == 4)
+  if (has_ctrl && lpp.variant == 4)
     for (int w = 0; w <= (warm ? 1 : 0); ++w) HIP_TRY(kLaneInst[crec].start[w].upload_params(h->lane_pslot, s, &h->dev, sizeof h->dev));
   return replay_ticks(h, lpp, s, ticks, warm, one_tick);
+}
+
+// The host-buffer closed loop of every kind (qmpc_loop_run*), on the call's records as loop_recs_normalise left them: its checks,
+// its buffers -- all allocated before the ticks = 0 return, which so prepares a later call of the same kind (the outcome call's
+// ticks = 0 stops before h->d_outcome, as it always did; a call that stages windows or an optional record allocates it) -- and the
+// staging, which only grows: states and traces through h->d_loop, [states | force trace | contact trace]; ctrl and plant to the
+// staging halves of the per-instance and plant buffers, outcome records and windows to h->d_outcome and h->d_push, the optional
+// records where kRecStage says.  Then the device-buffer call on the staged copies, and what it wrote comes back.
+static qmpc_status loop_records_host(int kind, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states,
+                                     int32_t ticks, const loop_recs& r) {
+  if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !states)) return QMPC_BAD_ARGUMENT;
+  const size_t B = (size_t)batch, T = (size_t)ticks, MB = (size_t)h->max_batch;
+  if (kind == REC_PLAIN && !r.ctrl && !r.plant) {      // the plain loop
+    if (h->params.model != QMPC_MODEL_QUAT && h->params.model != QMPC_MODEL_CONVEX) return QMPC_BAD_ARGUMENT;
+    if (batch == 0 || ticks == 0) return QMPC_OK;
+    if (batch > h->max_batch) return QMPC_BATCH_TOO_LARGE;
+    HIP_TRY(hipSetDevice(h->device));
+  } else {
+    const qmpc_status cs = loop_instances_check(h, lp, batch, r.ctrl != nullptr);
+    if (cs != QMPC_OK || batch == 0) return cs;
+    HIP_TRY(hipSetDevice(h->device));
+    const qmpc_status es = loop_instances_buffers(h, batch, r.ctrl != nullptr, lp->warm_start != 0.0, nullptr);
+    if (es != QMPC_OK) return es;
+    if (r.push && h->push_cap < r.per_robot) {
+      if (h->d_push) (void)hipFree(h->d_push);
+      h->d_push = nullptr;
+      h->push_cap = 0;
+      HIP_TRY(hipMalloc(&h->d_push, sizeof(qmpc_push_params) * (size_t)r.per_robot * MB));
+      h->push_cap = r.per_robot;
+    }
+    bool staged = r.push != nullptr;
+    for (const rec_stage& s : kRecStage) staged = staged || s.get(r);
+    if (staged && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * MB));
+    for (const rec_stage& s : kRecStage) {
+      if (!s.get(r) || h->*s.buf) continue;
+      size_t both = 0;      // the buffer holds max_batch of every record the table places in it
+      for (const rec_stage& o : kRecStage) both += o.buf == s.buf ? o.elem : 0;
+      HIP_TRY(hipMalloc(&(h->*s.buf), both * MB));
+    }
+    if (ticks == 0) return QMPC_OK;
+    if (kind != REC_PLAIN && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * MB));
+  }
+  const size_t n_st = (sizeof(qmpc_loop_state) / sizeof(double)) * B, n_tf = r.trace_forces ? 12 * B * T : 0,
+               n_tc = r.trace_contacts ? 4 * B * T : 0;
+  if (h->loop_cap < n_st + n_tf + n_tc) {
+    if (h->d_loop) (void)hipFree(h->d_loop);
+    h->d_loop = nullptr;
+    h->loop_cap = 0;
+    HIP_TRY(hipMalloc(&h->d_loop, sizeof(double) * (n_st + n_tf + n_tc)));
+    h->loop_cap = n_st + n_tf + n_tc;
+  }
+  qmpc_loop_state* d_st = reinterpret_cast<qmpc_loop_state*>(h->d_loop);
+  loop_recs d = r;      // the call on the staged copies: op and geom stay on the host
+  d.trace_forces = r.trace_forces ? h->d_loop + n_st : nullptr;
+  d.trace_contacts = r.trace_contacts ? h->d_loop + n_st + n_tf : nullptr;
+  HIP_TRY(hipMemcpyAsync(d_st, states, sizeof(qmpc_loop_state) * B, hipMemcpyHostToDevice, h->stream));
+  if (r.outcomes) HIP_TRY(hipMemcpyAsync(h->d_outcome, r.outcomes, sizeof(qmpc_loop_outcome) * B, hipMemcpyHostToDevice, h->stream));
+  if (r.ctrl) HIP_TRY(hipMemcpyAsync(inst_rec(h), r.ctrl, sizeof(qmpc_instance_params) * B, hipMemcpyHostToDevice, h->stream));
+  if (r.plant) HIP_TRY(hipMemcpyAsync(plant_rec(h), r.plant, sizeof(qmpc_plant_params) * B, hipMemcpyHostToDevice, h->stream));
+  if (r.push) HIP_TRY(hipMemcpyAsync(h->d_push, r.push, sizeof(qmpc_push_params) * B * (size_t)r.per_robot, hipMemcpyHostToDevice, h->stream));
+  d.outcomes = r.outcomes ? h->d_outcome : nullptr;
+  d.ctrl = r.ctrl ? inst_rec(h) : nullptr;
+  d.plant = r.plant ? plant_rec(h) : nullptr;
+  d.push = r.push ? h->d_push : nullptr;
+  for (const rec_stage& s : kRecStage) {
+    if (!s.get(r)) continue;
+    void* dst = static_cast<unsigned char*>(h->*s.buf) + s.before * MB;
+    HIP_TRY(hipMemcpyAsync(dst, s.get(r), s.elem * B, hipMemcpyHostToDevice, h->stream));
+    s.set(d, dst);
+  }
+  const qmpc_status rs = loop_records_device(kind, h, lp, batch, d_st, ticks, d, nullptr);
+  if (rs != QMPC_OK) return rs;
+  for (size_t i = sizeof kRecStage / sizeof kRecStage[0]; i-- > 0;) {
+    const rec_stage& s = kRecStage[i];
+    if (s.out && s.get(r)) HIP_TRY(hipMemcpyAsync(s.get(r), s.get(d), s.elem * B, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(states, d_st, sizeof(qmpc_loop_state) * B, hipMemcpyDeviceToHost, h->stream));
+  if (r.outcomes) HIP_TRY(hipMemcpyAsync(r.outcomes, h->d_outcome, sizeof(qmpc_loop_outcome) * B, hipMemcpyDeviceToHost, h->stream));
+  if (d.trace_forces) HIP_TRY(hipMemcpyAsync(r.trace_forces, d.trace_forces, sizeof(double) * 12 * B * T, hipMemcpyDeviceToHost, h->stream));
+  if (d.trace_contacts) HIP_TRY(hipMemcpyAsync(r.trace_contacts, d.trace_contacts, sizeof(double) * 4 * B * T, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return QMPC_OK;
+}
+
+// An entry point of kind `entry` with its caller's arguments r (what it does not take: NULL): the call they are
+// (loop_recs_normalise: pointer checks only, before anything touches the handle) on the device-buffer path (device; stream) or the
+// host-buffer path
+static qmpc_status loop_records_call(bool device, int entry, qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch,
+                                     qmpc_loop_state* states, int32_t ticks, loop_recs r, void* stream) {
+  qmpc_leg_geometry go1;
+  if (r.motor && !r.geom) qmpc_default_go1_geometry(&go1);
+  int kind;
+  if (loop_recs_normalise(entry, batch, &go1, &r, &kind) != QMPC_OK) return QMPC_BAD_ARGUMENT;
+  return device ? loop_records_device(kind, h, lp, batch, states, ticks, r, stream) : loop_records_host(kind, h, lp, batch, states, ticks, r);
 }
 
 qmpc_status qmpc_loop_run_instances_device(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* d_states,
                                            int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                            double* d_trace_forces, double* d_trace_contacts, void* stream) {
-  return loop_records_device(REC_PLAIN, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, nullptr, nullptr,
-                             nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  const loop_recs r = {d_ctrl, d_plant, d_trace_forces, d_trace_contacts};
+  return loop_records_call(true, REC_PLAIN, h, lp, batch, d_states, ticks, r, stream);
 }
 
 qmpc_status qmpc_loop_run_instances(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
                                     const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                     double* trace_contacts) {
-  if (!h || !lp || batch < 0 || ticks < 0 || (batch > 0 && !states)) return QMPC_BAD_ARGUMENT;
-  if (!ctrl && !plant) return qmpc_loop_run(h, lp, batch, states, ticks, trace_forces, trace_contacts);
-  const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
-  if (cs != QMPC_OK || batch == 0) return cs;
-  HIP_TRY(hipSetDevice(h->device));
-  const qmpc_status es = loop_instances_buffers(h, batch, ctrl != nullptr, lp->warm_start != 0.0, nullptr);
-  if (es != QMPC_OK || ticks == 0) return es;
-  return loop_records_host(REC_PLAIN, h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+  const loop_recs r = {ctrl, plant, trace_forces, trace_contacts};
+  return loop_records_call(false, REC_PLAIN, h, lp, batch, states, ticks, r, nullptr);
 }
 
 // ---- the same closed loop with per-robot outcome records (qmpc_loop_outcome.hip) -------------------------------------------
@@ -2136,57 +2116,15 @@ qmpc_status qmpc_loop_run_outcomes_device(qmpc_handle* h, const qmpc_loop_params
                                           int32_t ticks, const qmpc_instance_params* d_ctrl, const qmpc_plant_params* d_plant,
                                           double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                           qmpc_loop_outcome* d_outcomes, void* stream) {
-  return loop_records_device(REC_OUTCOME, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
-                             nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-// the host-buffer call's checks and buffers (the staging itself: loop_records_host); push (qmpc_loop_run_pushes; NULL:
-// qmpc_loop_run_outcomes): per_robot windows per robot, staged in h->d_push; ground (qmpc_loop_run_ground, with or without push)
-// and tally (or NULL): staged in h->d_ground; act and line (qmpc_loop_run_actuation, with or without ground): staged in h->d_act;
-// sense and seen (or NULL) (qmpc_loop_run_sensing, with or without act): staged in h->d_sense; gait (qmpc_loop_run_gaits, with or
-// without sense): staged in h->d_gait; mo (qmpc_loop_run_motors, with or without gait): records and tallies staged in h->d_motor
-static qmpc_status loop_outcomes_host(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
-                                      const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
-                                      double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
-                                      const qmpc_push_params* push, int32_t per_robot, const qmpc_ground_params* ground,
-                                      qmpc_ground_tally* tally, const qmpc_actuation_params* act = nullptr,
-                                      qmpc_actuation_line* line = nullptr, const qmpc_sense_params* sense = nullptr,
-                                      qmpc_sense_seen* seen = nullptr, const qmpc_gait_params* gait = nullptr,
-                                      const loop_motor_args* mo = nullptr) {
-  if (!h || !lp || !op || batch < 0 || ticks < 0 || (batch > 0 && (!states || !outcomes))) return QMPC_BAD_ARGUMENT;
-  const qmpc_status cs = loop_instances_check(h, lp, batch, ctrl != nullptr);
-  if (cs != QMPC_OK || batch == 0) return cs;
-  HIP_TRY(hipSetDevice(h->device));
-  const qmpc_status es = loop_instances_buffers(h, batch, ctrl != nullptr, lp->warm_start != 0.0, nullptr);
-  if (es != QMPC_OK) return es;
-  if (push && h->push_cap < per_robot) {      // the windows' staging: before the ticks = 0 return, like every other buffer
-    if (h->d_push) (void)hipFree(h->d_push);
-    h->d_push = nullptr;
-    h->push_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_push, sizeof(qmpc_push_params) * (size_t)per_robot * (size_t)h->max_batch));
-    h->push_cap = per_robot;
-  }
-  // (the push call's ticks = 0 allocates everything a later push call needs, the records' staging included; the outcome call's
-  // ticks = 0 stops before it, as it always did)
-  if ((push || ground || act || sense || gait || mo) && !h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
-  if (ground && !h->d_ground)
-    HIP_TRY(hipMalloc(&h->d_ground, (sizeof(qmpc_ground_params) + sizeof(qmpc_ground_tally)) * (size_t)h->max_batch));
-  if (act && !h->d_act)
-    HIP_TRY(hipMalloc(&h->d_act, (sizeof(qmpc_actuation_params) + sizeof(qmpc_actuation_line)) * (size_t)h->max_batch));
-  if (sense && !h->d_sense)
-    HIP_TRY(hipMalloc(&h->d_sense, (sizeof(qmpc_sense_params) + sizeof(qmpc_sense_seen)) * (size_t)h->max_batch));
-  if (gait && !h->d_gait) HIP_TRY(hipMalloc(&h->d_gait, sizeof(qmpc_gait_params) * (size_t)h->max_batch));
-  if (mo && !h->d_motor) HIP_TRY(hipMalloc(&h->d_motor, (sizeof(qmpc_motor_params) + sizeof(qmpc_motor_tally)) * (size_t)h->max_batch));
-  if (ticks == 0) return es;
-  if (!h->d_outcome) HIP_TRY(hipMalloc(&h->d_outcome, sizeof(qmpc_loop_outcome) * (size_t)h->max_batch));
-  return loop_records_host(mo ? REC_MOTOR : gait ? REC_GAIT : sense ? REC_SENSE : act ? REC_ACT : ground ? REC_GROUND : push ? REC_PUSH : REC_OUTCOME, h, lp, batch, states, ticks, ctrl, plant,
-                           trace_forces, trace_contacts, op, outcomes, push, per_robot, ground, tally, act, line, sense, seen, gait, mo);
+  const loop_recs r = {d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes};
+  return loop_records_call(true, REC_OUTCOME, h, lp, batch, d_states, ticks, r, stream);
 }
 
 qmpc_status qmpc_loop_run_outcomes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
                                    const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                    double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes) {
-  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, nullptr, 0, nullptr, nullptr);
+  const loop_recs r = {ctrl, plant, trace_forces, trace_contacts, op, outcomes};
+  return loop_records_call(false, REC_OUTCOME, h, lp, batch, states, ticks, r, nullptr);
 }
 
 // ---- the outcome loop under timed push windows per robot (qmpc_loop_push.hip) ------------------------------------------------
@@ -2198,22 +2136,16 @@ qmpc_status qmpc_loop_run_pushes_device(qmpc_handle* h, const qmpc_loop_params* 
                                         double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                         qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t pushes_per_robot,
                                         void* stream) {
-  if (!d_push)
-    return qmpc_loop_run_outcomes_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
-                                         stream);
-  if (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES) return QMPC_BAD_ARGUMENT;
-  return loop_records_device(REC_PUSH, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             pushes_per_robot, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  const loop_recs r = {d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push, pushes_per_robot};
+  return loop_records_call(true, REC_PUSH, h, lp, batch, d_states, ticks, r, stream);
 }
 
 qmpc_status qmpc_loop_run_pushes(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
                                  const qmpc_instance_params* ctrl, const qmpc_plant_params* plant, double* trace_forces,
                                  double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                  const qmpc_push_params* push, int32_t pushes_per_robot) {
-  if (!push) return qmpc_loop_run_outcomes(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes);
-  if (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES) return QMPC_BAD_ARGUMENT;
-  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot, nullptr,
-                            nullptr);
+  const loop_recs r = {ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot};
+  return loop_records_call(false, REC_PUSH, h, lp, batch, states, ticks, r, nullptr);
 }
 
 // ---- the push loop on the robot's true ground: friction and normal-force limits per leg (qmpc_loop_ground.hip, qmpc_loop_cground.hip) ----
@@ -2241,12 +2173,9 @@ qmpc_status qmpc_loop_run_ground_device(qmpc_handle* h, const qmpc_loop_params* 
                                         double* d_trace_forces, double* d_trace_contacts, const qmpc_outcome_params* op,
                                         qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t pushes_per_robot,
                                         const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally, void* stream) {
-  if (!d_ground)
-    return qmpc_loop_run_pushes_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                                       pushes_per_robot, stream);
-  if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  return loop_records_device(REC_GROUND, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             d_push ? pushes_per_robot : 0, d_ground, d_tally, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  const loop_recs r = {d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push, pushes_per_robot, d_ground,
+                       d_tally};
+  return loop_records_call(true, REC_GROUND, h, lp, batch, d_states, ticks, r, stream);
 }
 
 qmpc_status qmpc_loop_run_ground(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2254,11 +2183,8 @@ qmpc_status qmpc_loop_run_ground(qmpc_handle* h, const qmpc_loop_params* lp, int
                                  double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                  const qmpc_push_params* push, int32_t pushes_per_robot, const qmpc_ground_params* ground,
                                  qmpc_ground_tally* tally) {
-  if (!ground)
-    return qmpc_loop_run_pushes(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot);
-  if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
-                            push ? pushes_per_robot : 0, ground, tally);
+  const loop_recs r = {ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot, ground, tally};
+  return loop_records_call(false, REC_GROUND, h, lp, batch, states, ticks, r, nullptr);
 }
 
 // ---- the ground loop behind the robot's delay line and actuator lag (qmpc_loop_act.hip, qmpc_loop_cact.hip) ----------------------
@@ -2294,13 +2220,9 @@ qmpc_status qmpc_loop_run_actuation_device(qmpc_handle* h, const qmpc_loop_param
                                            qmpc_loop_outcome* d_outcomes, const qmpc_push_params* d_push, int32_t pushes_per_robot,
                                            const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
                                            const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line, void* stream) {
-  if (!d_act)
-    return qmpc_loop_run_ground_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                                       pushes_per_robot, d_ground, d_tally, stream);
-  if (!d_line) return QMPC_BAD_ARGUMENT;
-  if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  return loop_records_device(REC_ACT, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_line, nullptr, nullptr, nullptr, stream);
+  const loop_recs r = {d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push, pushes_per_robot, d_ground,
+                       d_tally, d_act, d_line};
+  return loop_records_call(true, REC_ACT, h, lp, batch, d_states, ticks, r, stream);
 }
 
 qmpc_status qmpc_loop_run_actuation(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2308,13 +2230,8 @@ qmpc_status qmpc_loop_run_actuation(qmpc_handle* h, const qmpc_loop_params* lp, 
                                     double* trace_contacts, const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
                                     const qmpc_push_params* push, int32_t pushes_per_robot, const qmpc_ground_params* ground,
                                     qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line) {
-  if (!act)
-    return qmpc_loop_run_ground(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot,
-                                ground, tally);
-  if (!line) return QMPC_BAD_ARGUMENT;
-  if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
-                            push ? pushes_per_robot : 0, ground, ground ? tally : nullptr, act, line);
+  const loop_recs r = {ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot, ground, tally, act, line};
+  return loop_records_call(false, REC_ACT, h, lp, batch, states, ticks, r, nullptr);
 }
 
 // ---- the actuation loop whose controller reads a measured state (qmpc_loop_sense.hip, qmpc_loop_csense.hip) -----------------------
@@ -2347,14 +2264,9 @@ qmpc_status qmpc_loop_run_sensing_device(qmpc_handle* h, const qmpc_loop_params*
                                          const qmpc_ground_params* d_ground, qmpc_ground_tally* d_tally,
                                          const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
                                          const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, void* stream) {
-  if (!d_sense)
-    return qmpc_loop_run_actuation_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
-                                          d_push, pushes_per_robot, d_ground, d_tally, d_act, d_line, stream);
-  if (d_act && !d_line) return QMPC_BAD_ARGUMENT;
-  if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  return loop_records_device(REC_SENSE, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_act ? d_line : nullptr, d_sense,
-                             d_seen, nullptr, stream);
+  const loop_recs r = {d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push, pushes_per_robot, d_ground,
+                       d_tally, d_act, d_line, d_sense, d_seen};
+  return loop_records_call(true, REC_SENSE, h, lp, batch, d_states, ticks, r, stream);
 }
 
 qmpc_status qmpc_loop_run_sensing(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2363,13 +2275,9 @@ qmpc_status qmpc_loop_run_sensing(qmpc_handle* h, const qmpc_loop_params* lp, in
                                   const qmpc_push_params* push, int32_t pushes_per_robot, const qmpc_ground_params* ground,
                                   qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line,
                                   const qmpc_sense_params* sense, qmpc_sense_seen* seen) {
-  if (!sense)
-    return qmpc_loop_run_actuation(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
-                                   pushes_per_robot, ground, tally, act, line);
-  if (act && !line) return QMPC_BAD_ARGUMENT;
-  if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
-                            push ? pushes_per_robot : 0, ground, ground ? tally : nullptr, act, act ? line : nullptr, sense, seen);
+  const loop_recs r = {ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot, ground, tally, act, line,
+                       sense, seen};
+  return loop_records_call(false, REC_SENSE, h, lp, batch, states, ticks, r, nullptr);
 }
 
 // ---- the sensing loop in which every robot walks a gait of its own (qmpc_loop_gait.hip, qmpc_loop_cgait.hip) ---------------------
@@ -2411,14 +2319,9 @@ qmpc_status qmpc_loop_run_gaits_device(qmpc_handle* h, const qmpc_loop_params* l
                                        const qmpc_actuation_params* d_act, qmpc_actuation_line* d_line,
                                        const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
                                        void* stream) {
-  if (!d_gait)
-    return qmpc_loop_run_sensing_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
-                                        d_push, pushes_per_robot, d_ground, d_tally, d_act, d_line, d_sense, d_seen, stream);
-  if (d_act && !d_line) return QMPC_BAD_ARGUMENT;
-  if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  return loop_records_device(REC_GAIT, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push,
-                             d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_act ? d_line : nullptr, d_sense,
-                             d_sense ? d_seen : nullptr, d_gait, stream);
+  const loop_recs r = {d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push, pushes_per_robot, d_ground,
+                       d_tally, d_act, d_line, d_sense, d_seen, d_gait};
+  return loop_records_call(true, REC_GAIT, h, lp, batch, d_states, ticks, r, stream);
 }
 
 qmpc_status qmpc_loop_run_gaits(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2427,14 +2330,9 @@ qmpc_status qmpc_loop_run_gaits(qmpc_handle* h, const qmpc_loop_params* lp, int3
                                 const qmpc_push_params* push, int32_t pushes_per_robot, const qmpc_ground_params* ground,
                                 qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line,
                                 const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait) {
-  if (!gait)
-    return qmpc_loop_run_sensing(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
-                                 pushes_per_robot, ground, tally, act, line, sense, seen);
-  if (act && !line) return QMPC_BAD_ARGUMENT;
-  if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
-                            push ? pushes_per_robot : 0, ground, ground ? tally : nullptr, act, act ? line : nullptr, sense,
-                            sense ? seen : nullptr, gait);
+  const loop_recs r = {ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot, ground, tally, act, line,
+                       sense, seen, gait};
+  return loop_records_call(false, REC_GAIT, h, lp, batch, states, ticks, r, nullptr);
 }
 
 // ---- the gait loop whose delivered foot force respects the motors' torque limits (qmpc_loop_motor.hip, qmpc_loop_cmotor.hip) --------
@@ -2465,18 +2363,9 @@ qmpc_status qmpc_loop_run_motors_device(qmpc_handle* h, const qmpc_loop_params* 
                                         const qmpc_sense_params* d_sense, qmpc_sense_seen* d_seen, const qmpc_gait_params* d_gait,
                                         const qmpc_leg_geometry* geom, const qmpc_motor_params* d_motor,
                                         qmpc_motor_tally* d_motor_tally, void* stream) {
-  if (!d_motor)
-    return qmpc_loop_run_gaits_device(h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
-                                      d_push, pushes_per_robot, d_ground, d_tally, d_act, d_line, d_sense, d_seen, d_gait, stream);
-  if (!d_motor_tally) return QMPC_BAD_ARGUMENT;
-  if (d_act && !d_line) return QMPC_BAD_ARGUMENT;
-  if (d_push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  qmpc_leg_geometry go1;
-  if (!geom) qmpc_default_go1_geometry(&go1);
-  const loop_motor_args mo = {geom ? geom : &go1, d_motor, d_motor_tally};
-  return loop_records_device(REC_MOTOR, h, lp, batch, d_states, ticks, d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes,
-                             d_push, d_push ? pushes_per_robot : 0, d_ground, d_ground ? d_tally : nullptr, d_act, d_act ? d_line : nullptr,
-                             d_sense, d_sense ? d_seen : nullptr, d_gait, stream, &mo);
+  const loop_recs r = {d_ctrl, d_plant, d_trace_forces, d_trace_contacts, op, d_outcomes, d_push, pushes_per_robot, d_ground,
+                       d_tally, d_act, d_line, d_sense, d_seen, d_gait, geom, d_motor, d_motor_tally};
+  return loop_records_call(true, REC_MOTOR, h, lp, batch, d_states, ticks, r, stream);
 }
 
 qmpc_status qmpc_loop_run_motors(qmpc_handle* h, const qmpc_loop_params* lp, int32_t batch, qmpc_loop_state* states, int32_t ticks,
@@ -2486,18 +2375,9 @@ qmpc_status qmpc_loop_run_motors(qmpc_handle* h, const qmpc_loop_params* lp, int
                                  qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line,
                                  const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait,
                                  const qmpc_leg_geometry* geom, const qmpc_motor_params* motor, qmpc_motor_tally* motor_tally) {
-  if (!motor)
-    return qmpc_loop_run_gaits(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
-                               pushes_per_robot, ground, tally, act, line, sense, seen, gait);
-  if (!motor_tally) return QMPC_BAD_ARGUMENT;
-  if (act && !line) return QMPC_BAD_ARGUMENT;
-  if (push && (pushes_per_robot < 1 || pushes_per_robot > QMPC_MAX_PUSHES)) return QMPC_BAD_ARGUMENT;
-  qmpc_leg_geometry go1;
-  if (!geom) qmpc_default_go1_geometry(&go1);
-  const loop_motor_args mo = {geom ? geom : &go1, motor, motor_tally};
-  return loop_outcomes_host(h, lp, batch, states, ticks, ctrl, plant, trace_forces, trace_contacts, op, outcomes, push,
-                            push ? pushes_per_robot : 0, ground, ground ? tally : nullptr, act, act ? line : nullptr, sense,
-                            sense ? seen : nullptr, gait, &mo);
+  const loop_recs r = {ctrl, plant, trace_forces, trace_contacts, op, outcomes, push, pushes_per_robot, ground, tally, act, line,
+                       sense, seen, gait, geom, motor, motor_tally};
+  return loop_records_call(false, REC_MOTOR, h, lp, batch, states, ticks, r, nullptr);
 }
 
 // Diagnostic: per-instance phase cycle counts (s_memtime) of one solve launch.

@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "qmpc_kernel_slots.h"
+#include "qmpc_loop_records.h"
 
 namespace qmpc_cmotor_tu {
 

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "qmpc_kernel_slots.h"
+#include "qmpc_loop_records.h"
 
 namespace qmpc_crec_tu {
 

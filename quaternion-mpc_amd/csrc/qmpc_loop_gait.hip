@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "qmpc_kernel_slots.h"
+#include "qmpc_loop_records.h"
 
 namespace qmpc_gait_tu {
 

@@ -22,6 +22,7 @@
 #include <cstring>
 
 #include "qmpc_kernel_slots.h"
+#include "qmpc_loop_records.h"
 
 namespace qmpc_inst_tu {
 

@@ -26,6 +26,7 @@
 #include <cstring>
 
 #include "qmpc_kernel_slots.h"
+#include "qmpc_loop_records.h"
 
 namespace qmpc_outc_tu {
 

@@ -26,8 +26,9 @@
 //               around the solve the C entry point launches
 //   persistent  qmpc_loop_rec_fused_kernel<3|5|6>: qmpc_loop_fused_kernel<VAR, false, false, false> (QuatMpc's problem,
 //               converged mode, wrench-form body) with the robot's own controller and plant
-//   launchers   rec_set_lds, rec_fused_launch, rec_front_launch, rec_post_launch: one signature for all units, the
-//               arguments beyond the unit's EXT ignored (declared for qmpc_hip.hip by its QMPC_REC_DECLARE)
+//   launchers   rec_set_lds, rec_fused_launch, rec_front_launch, rec_post_launch: one signature for all units -- the call's
+//               buffers (rec_launch) and its records (loop_recs), both of qmpc_loop_records.h, of which a unit passes its
+//               kernels what they take (declared for qmpc_hip.hip by its QMPC_REC_DECLARE)
 #ifdef QMPC_REC_CONVEX
 #define QMPC_REC_MODEL ConvexModel
 #define QMPC_REC_FRONT(OCC_, LP_, s_, r_) loop_front_convex_one<OCC_>(LP_, s_, reinterpret_cast<qmpc_convex_input&>(r_))
@@ -735,49 +736,36 @@ static_assert(sizeof kRecFused / sizeof kRecFused[0] == qmpc::kWformVars, "qmpc_
 
 __attribute__((visibility("hidden"))) hipError_t rec_set_lds() { return set_max_lds(kRecFused); }
 
+// The launchers read what their kernels take from the call's buffers L and its records r (qmpc_loop_records.h) through the
+// QMPC_REC_* macros; the structs themselves go to no kernel.
 // one launch for all ticks: var 3 / 5 / 6 (qmpc_plan.h: plan_loop_instances)
-__attribute__((visibility("hidden"))) hipError_t rec_fused_launch(
-    int var, int batch, size_t lds, hipStream_t s, const void* dev_blocks, const void* plants, const qmpc_loop_params* lp,
-    qmpc_loop_state* st, qmpc_input* rec, double* forces, qmpc_info* info, double* trace_f, double* trace_c, int ticks, double* gws,
-    const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes, const qmpc_push_params* push, int per_robot,
-    const qmpc_ground_params* ground, qmpc_ground_tally* tally, const qmpc_actuation_params* act, qmpc_actuation_line* line,
-    const qmpc_sense_params* sense, qmpc_sense_seen* seen, const qmpc_gait_params* gait, const qmpc_leg_geometry* geom,
-    const qmpc_motor_params* motor, qmpc_motor_tally* mtally) {
+__attribute__((visibility("hidden"))) hipError_t rec_fused_launch(int var, size_t lds, int ticks, double* gws, const rec_launch& L,
+                                                                  const loop_recs& r) {
   const int k = qmpc::wform_index(var);
   if (k < 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kRecFused[k], dim3((unsigned)batch), dim3(kWave), lds, s, static_cast<const DevParams*>(dev_blocks),
-                     static_cast<const PlantDev*>(plants), *lp, QMPC_REC_OUTCOME(*op, ) st, rec, forces, info, trace_f, trace_c,
-                     QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, )
-                     QMPC_REC_ACT(act, line, ) QMPC_REC_SENSE(sense, seen, ) QMPC_REC_GAIT(gait, )
-                     QMPC_REC_MOTOR(*reinterpret_cast<const LegGeom*>(geom), motor, mtally, ) ticks, batch, gws);
+  hipLaunchKernelGGL(kRecFused[k], dim3((unsigned)L.batch), dim3(kWave), lds, (hipStream_t)L.stream, static_cast<const DevParams*>(L.dev_blocks),
+                     static_cast<const PlantDev*>(L.plants), *L.lp, QMPC_REC_OUTCOME(*r.op, ) L.st, L.rec, L.forces, L.info, r.trace_forces,
+                     r.trace_contacts, QMPC_REC_OUTCOME(r.outcomes, ) QMPC_REC_PUSH(r.push, (int)r.per_robot, ) QMPC_REC_GROUND(r.ground, r.tally, )
+                     QMPC_REC_ACT(r.act, r.line, ) QMPC_REC_SENSE(r.sense, r.seen, ) QMPC_REC_GAIT(r.gait, )
+                     QMPC_REC_MOTOR(*reinterpret_cast<const LegGeom*>(r.geom), r.motor, r.mtally, ) ticks, L.batch, gws);
   return hipGetLastError();
 }
 
 #if QMPC_REC_EXT <= 1 || QMPC_REC_EXT >= 5 || defined(QMPC_REC_CONVEX)
-__attribute__((visibility("hidden"))) hipError_t rec_front_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st,
-                                                                  qmpc_input* rec, int* row, const void* plants, int batch,
-                                                                  const qmpc_outcome_params* op, const qmpc_loop_outcome* outcomes,
-                                                                  const qmpc_sense_params* sense, qmpc_sense_seen* seen,
-                                                                  const qmpc_gait_params* gait) {
-  hipLaunchKernelGGL(qmpc_loop_rec_front_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, *lp, QMPC_REC_OUTCOME(*op, ) st, rec, row,
-                     static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, ) QMPC_REC_SENSE(sense, seen, ) QMPC_REC_GAIT(gait, ) batch);
+__attribute__((visibility("hidden"))) hipError_t rec_front_launch(const rec_launch& L, const loop_recs& r) {
+  hipLaunchKernelGGL(qmpc_loop_rec_front_kernel, dim3((unsigned)((L.batch + 63) / 64)), dim3(64), 0, (hipStream_t)L.stream, *L.lp,
+                     QMPC_REC_OUTCOME(*r.op, ) L.st, L.rec, L.row, static_cast<const PlantDev*>(L.plants),
+                     QMPC_REC_OUTCOME((const qmpc_loop_outcome*)r.outcomes, ) QMPC_REC_SENSE(r.sense, r.seen, ) QMPC_REC_GAIT(r.gait, ) L.batch);
   return hipGetLastError();
 }
 #endif
 
-__attribute__((visibility("hidden"))) hipError_t rec_post_launch(hipStream_t s, const qmpc_loop_params* lp, qmpc_loop_state* st,
-                                                                 const double* forces, const qmpc_info* info, double* trace_f,
-                                                                 double* trace_c, const int* row, const void* plants, int batch,
-                                                                 const qmpc_outcome_params* op, qmpc_loop_outcome* outcomes,
-                                                                 const qmpc_push_params* push, int per_robot,
-                                                                 const qmpc_ground_params* ground, qmpc_ground_tally* tally,
-                                                                 const qmpc_actuation_params* act, qmpc_actuation_line* line,
-                                                                 const qmpc_leg_geometry* geom, const qmpc_motor_params* motor,
-                                                                 qmpc_motor_tally* mtally) {
-  hipLaunchKernelGGL(qmpc_loop_rec_post_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, *lp, QMPC_REC_OUTCOME(*op, ) st, forces, info,
-                     trace_f, trace_c, row, static_cast<const PlantDev*>(plants), QMPC_REC_OUTCOME(outcomes, )
-                     QMPC_REC_PUSH(push, per_robot, ) QMPC_REC_GROUND(ground, tally, ) QMPC_REC_ACT(act, line, )
-                     QMPC_REC_MOTOR(*reinterpret_cast<const LegGeom*>(geom), motor, mtally, ) batch);
+__attribute__((visibility("hidden"))) hipError_t rec_post_launch(const rec_launch& L, const loop_recs& r) {
+  hipLaunchKernelGGL(qmpc_loop_rec_post_kernel, dim3((unsigned)((L.batch + 63) / 64)), dim3(64), 0, (hipStream_t)L.stream, *L.lp,
+                     QMPC_REC_OUTCOME(*r.op, ) L.st, (const double*)L.forces, (const qmpc_info*)L.info, r.trace_forces, r.trace_contacts,
+                     (const int*)L.row, static_cast<const PlantDev*>(L.plants), QMPC_REC_OUTCOME(r.outcomes, )
+                     QMPC_REC_PUSH(r.push, (int)r.per_robot, ) QMPC_REC_GROUND(r.ground, r.tally, ) QMPC_REC_ACT(r.act, r.line, )
+                     QMPC_REC_MOTOR(*reinterpret_cast<const LegGeom*>(r.geom), r.motor, r.mtally, ) L.batch);
   return hipGetLastError();
 }
 
